@@ -1,6 +1,6 @@
 """bench.py — denoising steps/sec of the Latte-XL/2 16x256x256 sampling loop on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: one process per GPU over RCCL.  Under torch.distributed.run (WORLD_SIZE / RANK / LOCAL_RANK in the environment, the
 driver's launch line) the process is one rank and asserts WORLD_SIZE == --gpus; started plainly (`python bench.py --gpus N`)
@@ -77,7 +77,13 @@ def parse():
                    help="launch N ranks, rendezvous, one all-reduce, print {launch_check, n_gpus, collective_ranks} and exit: "
                         "exercises the --gpus contract without measuring anything (runs without a GPU on the gloo backend)")
     p.add_argument("--cpu-steps", type=int, default=3, help="timed DDIM steps of the CPU baseline (about 5 s each)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, write the latents they returned as DIR/samples.npy (fp32; DIR/samples_rank<r>.npy "
+                        "per rank when N > 1) so that two builds can be compared output for output on the same seeded inputs")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def build_model(device, dtype, batch, extras=1, num_classes=1000):
@@ -614,6 +620,22 @@ def note(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this much over all ranks
+
+
+def dump_outputs(out_dir, name, t, world):
+    """--dump-outputs: `t` as out_dir/<name>.npy in fp32.  Past this rank's share of DUMP_BYTES, a fixed seeded sample of its
+    elements (the same indices in every run with the same arguments) is written instead, flattened."""
+    import numpy as np
+    a = t.detach().float().cpu()
+    n = DUMP_BYTES // 4 // world
+    if a.numel() > n:
+        idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:n].sort().values
+        a = a.reshape(-1)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks (one per GPU) under torch.distributed.run."""
     import socket
@@ -716,6 +738,8 @@ def main():
         elapsed = float(tt.item())
     finite = bool(torch.isfinite(xx).all())
     note(f'timed region done: {elapsed:.3f}s')
+    if args.dump_outputs:   # the sampling loop's result: the latents after the last timed step, updated in place in xx
+        dump_outputs(args.dump_outputs, "samples" if world == 1 else f"samples_rank{rank}", xx, world)
 
     other = None
     if world == 1:

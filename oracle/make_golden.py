@@ -1,12 +1,15 @@
 """Generate ``tests/golden/*.npz`` by running the REAL reference (build container only).
 
 TEST INFRASTRUCTURE ONLY.  Usage:  python -m oracle.make_golden
+(``--pinned``: only pinned_reference.npz, in a process started with MKL_CBWR=COMPATIBLE; main() starts that process itself)
 The fixtures are outputs of /root/reference code (models/latte.py via the timm stand-in,
 diffusion/* unmodified); the oracle restatement and the HIP engine are both tested against them.
 """
 import hashlib
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import torch
@@ -16,7 +19,8 @@ from oracle import latte_oracle as lo
 from oracle.reference_loader import (load_reference_diffusion, load_reference_latte,
                                      randomize_zero_init)
 
-OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.path.join(ROOT, "tests", "golden")
 
 TINY = dict(depth=2, hidden_size=128, patch_size=2, num_heads=2, input_size=8, num_frames=4,
             num_classes=5, extras=2, learn_sigma=True)
@@ -198,6 +202,10 @@ def training_inputs(n_steps):
 
 
 def training(rd):
+    np.savez_compressed(os.path.join(OUT, "training_losses.npz"), **training_outputs(rd))
+
+
+def training_outputs(rd):
     """GaussianDiffusion.training_losses (gd:719-795) run by the reference on the synthetic model."""
     out = {}
     for tag, kw, spec in TRAINING_CASES:
@@ -208,7 +216,38 @@ def training(rd):
         for k, v in terms.items():
             out[f"{tag}::{k}"] = v.numpy()
         out[f"{tag}::x_t"] = d.q_sample(x0, t, noise=noise).numpy()
-    np.savez_compressed(os.path.join(OUT, "training_losses.npz"), **out)
+    return out
+
+
+def pinned_reference(rl, rd):
+    """tests/golden/pinned_reference.npz: the reference outputs the tests compare with the oracle at bit level (tests/_util.pinned),
+    computed on MKL's vendor-neutral code path on one thread -- MKL's default path depends on the CPU, so only this arithmetic is
+    reproduced on every x86 host.  Training-loss terms, and the tiny models' forwards on the weights and inputs of tiny_*.npz."""
+    assert os.environ.get("MKL_CBWR") == "COMPATIBLE", "MKL reads MKL_CBWR when the process starts its first call"
+    torch.set_num_threads(1)
+    out = {"training::" + k: v for k, v in training_outputs(rd).items() if not k.endswith("::x_t")}
+    for name in ("tiny_classcond", "tiny_uncond", "tiny_textcond"):
+        z = np.load(os.path.join(OUT, name + ".npz"))
+        kw = json.loads(bytes(z["cfg_json"]).decode())
+        sd = {k[4:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("sd::")}
+        if "text_w_seed" in z.files:
+            sd["text_embedding_projection.1.weight"] = lo.text_projection_weight(kw["hidden_size"], int(z["text_w_seed"]))
+        model = rl.Latte(**kw).eval()
+        model.load_state_dict(sd)
+        x, t = torch.from_numpy(z["x"]), torch.from_numpy(z["t"])
+        with torch.no_grad():
+            if kw["extras"] == 2:
+                out[f"forward::{name}"] = model(x, t, y=torch.from_numpy(z["y"])).numpy()
+                out[f"forward_with_cfg::{name}"] = model.forward_with_cfg(torch.from_numpy(z["x_cfg"]), t, y=torch.from_numpy(z["y_cfg"]),
+                                                                          cfg_scale=7.0).numpy()
+            elif kw["extras"] == 78:
+                te = torch.from_numpy(z["text_embedding"])
+                out[f"forward::{name}"] = model(x, t, text_embedding=te).numpy()
+                out[f"forward_with_cfg::{name}"] = model.forward_with_cfg(torch.from_numpy(z["x_cfg"]), t, cfg_scale=7.0,
+                                                                          text_embedding=te).numpy()
+            else:
+                out[f"forward::{name}"] = model(x, t).numpy()
+    np.savez_compressed(os.path.join(OUT, "pinned_reference.npz"), **out)
 
 
 TRAIN_STEP = dict(depth=2, hidden_size=128, patch_size=2, num_heads=2, input_size=8, num_frames=4, num_classes=5, extras=2,
@@ -278,9 +317,14 @@ def main():
     sampler_types(rd)
     training(rd)
     train_step(rl, rd)
+    subprocess.run([sys.executable, "-m", "oracle.make_golden", "--pinned"], cwd=ROOT, check=True,
+                   env=dict(os.environ, MKL_CBWR="COMPATIBLE"))
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 
 
 if __name__ == "__main__":
-    main()
+    if "--pinned" in sys.argv:
+        pinned_reference(load_reference_latte(), load_reference_diffusion())
+    else:
+        main()

@@ -9,6 +9,27 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
+def _pin_mkl():
+    os.environ["MKL_CBWR"] = "COMPATIBLE"
+    torch.set_num_threads(1)
+
+
+_PINNED = []
+
+
+def pinned(fn, *args):
+    """fn(*args) in a child Python whose MKL runs its vendor-neutral code path (MKL_CBWR=COMPATIBLE) on one thread: the CPU arithmetic
+    of the reference outputs in tests/golden/pinned_reference.npz (oracle/make_golden.py:pinned_reference).  MKL's default code path
+    depends on the CPU (vendor and ISA) and its GEMM blocking on the thread count, so comparisons at bit level hold on every x86 host
+    only this way.  MKL reads MKL_CBWR at its first call, hence a separate process: one, spawned on first use, serves the session.
+    fn is a module-level function; pass and return numpy arrays (they are pickled)."""
+    if not _PINNED:
+        import multiprocessing
+        from concurrent.futures import ProcessPoolExecutor
+        _PINNED.append(ProcessPoolExecutor(1, mp_context=multiprocessing.get_context("spawn"), initializer=_pin_mkl))
+    return _PINNED[0].submit(fn, *args).result()
+
+
 def rel_l2(a, b):
     a, b = a.double().cpu(), b.double().cpu()
     return float((a - b).norm() / b.norm().clamp_min(1e-30))

@@ -57,7 +57,7 @@ def test_get_models_reads_reference_config_keys(tmp_path):
         latte_amd.get_models(cfg)                                       # the reference's config needs pretrained_model_path too
 
 
-def test_create_diffusion_surface():
+def test_create_diffusion_surface(lib):
     d = latte_amd.create_diffusion("250")
     assert d.num_timesteps == 250 and d.timestep_map[:3] == [0, 4, 8] and d.timestep_map[-1] == 999
     assert abs(d.betas[-1] - 0.077519344992350026) < 1e-18
@@ -71,7 +71,7 @@ def test_create_diffusion_surface():
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="CPU-only behaviour")
-def test_product_path_fails_loudly_without_gpu():
+def test_product_path_fails_loudly_without_gpu(lib):
     m = latte_amd.Latte_models["Latte-S/2"](input_size=8, num_frames=4)
     with pytest.raises(latte_amd.LatteError):
         m(torch.zeros(1, 4, 4, 8, 8), torch.zeros(1, dtype=torch.int64))
@@ -233,3 +233,19 @@ def test_bench_vae_conv_algorithmic_bytes():
     b = bench.vae_conv_bytes(32)
     assert 14.3e9 < b < 14.5e9
     assert bench.vae_conv_bytes(32, frames=1) < b / 14          # the weights (96 MB) are read once per decode, not per frame
+
+
+def test_bench_dump_outputs_full_or_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the timed path's result in fp32, whole while it fits its rank's share of DUMP_BYTES, otherwise the same
+    seeded sample of its elements in every run."""
+    import bench
+    t = torch.randn(2, 3, 4, 5, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), "samples", t, 1)
+    got = np.load(tmp_path / "a" / "samples.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 3, 4, 5) and np.array_equal(got, t.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * 40)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), "samples_rank1", t, 2)
+    s = np.load(tmp_path / "b" / "samples_rank1.npy")
+    assert s.shape == (20,) and np.array_equal(s, np.load(tmp_path / "c" / "samples_rank1.npy"))
+    assert np.isin(s, t.float().numpy().reshape(-1)).all() and len(np.unique(s)) == 20

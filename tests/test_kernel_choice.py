@@ -3,15 +3,12 @@ on when no variant is forced.  Pure host code behind the C-ABI debug entry latte
 Epilogues: 0 bias -> half (qkv), 1 bias + GELU -> half (fc1), 2 gated fp32 read-modify-write (out-projection, fc2; latte.py:179-180)."""
 import pytest
 
-from latte_amd._lib import load_library
-
 TILE_N = {1: 128, 2: 128, 3: 256, 4: 128, 5: 192, 6: 256, 7: 128, 8: 192, 9: 256, 10: 192, 11: 192, 12: 144, 13: 144, 18: 144, 19: 144}
 ROWS_PER_VIDEO = 16 * 256          # Latte-XL/2 at 256 px: 16 frames x 256 tokens
 
 
 @pytest.mark.parametrize("B", [1, 2, 4, 8, 16])
-def test_xl2_block_choices(B):
-    lib = load_library()
+def test_xl2_block_choices(B, lib):
     M, D = B * ROWS_PER_VIDEO, 1152
     proj = lib.latte_debug_gemm_choice(M, D, D, 2)
     fc2 = lib.latte_debug_gemm_choice(M, D, 4 * D, 2)
@@ -31,11 +28,11 @@ def test_xl2_block_choices(B):
 @pytest.mark.parametrize("shape", [(1024, 384, 384), (1024, 1536, 384), (20480, 768, 3072), (4096, 1024, 1024), (8292, 2432, 192),
                                    (300, 288, 64), (64, 128, 64), (4096, 1152, 64), (33000, 1152, 1152), (700, 384, 64)])
 @pytest.mark.parametrize("epi", [0, 1, 2, 3])
-def test_choice_is_launchable(shape, epi):
+def test_choice_is_launchable(shape, epi, lib):
     """Whatever is picked must be able to run the shape: whole tile columns (whole wave widths for the persistent kernels 7-9),
     the 12-wave kernel only with >= 2 K tiles, the small tile only for the gated epilogue with at most one tile per CU."""
     M, N, K = shape
-    v = load_library().latte_debug_gemm_choice(M, N, K, epi)
+    v = lib.latte_debug_gemm_choice(M, N, K, epi)
     assert v in TILE_N
     width = TILE_N[v] // 4 if 7 <= v <= 9 else TILE_N[v]
     assert N % width == 0, (v, N)
@@ -47,10 +44,10 @@ def test_choice_is_launchable(shape, epi):
         assert K >= 128 and ((M + 255) // 256) * (N // 144) <= 512
 
 
-def test_fused_qkv_attention_shape_rule():
+def test_fused_qkv_attention_shape_rule(lib):
     """csrc/qkv_attn.hip: which attention blocks run as ONE projection + attention kernel (latte.py:48-70 without the qkv round
     trip through HBM): 256 tokens per frame (spatial) / 16 frames with a multiple of 16 tokens (temporal), head_dim 64 | 72."""
-    fus = load_library().latte_debug_qkv_attention_fusable
+    fus = lib.latte_debug_qkv_attention_fusable
     rows = 8 * ROWS_PER_VIDEO
     assert fus(1152, 16, 16, 256, 0, rows) == 1 and fus(1152, 16, 16, 256, 1, rows) == 1      # Latte-XL/2 at 256 px, both block kinds
     assert fus(1152, 16, 16, 1024, 0, rows) == 0 and fus(1152, 16, 16, 1024, 1, rows) == 1    # Latte-1 at 512 px: temporal blocks only
@@ -62,13 +59,13 @@ def test_fused_qkv_attention_shape_rule():
 
 @pytest.mark.parametrize("shape", [(20480, 768, 768), (20480, 3072, 768), (20480, 768, 3072), (128, 384, 384), (64, 1152, 1152),
                                    (8192, 1152, 4608), (100, 384, 384)])
-def test_weight_gradient_split_plan(shape):
+def test_weight_gradient_split_plan(shape, lib):
     """csrc/gemm_tn.hip: the contraction of dW = dY^T X is cut into whole multiples of 64 rows, the cuts cover M exactly once,
     and the partial products fill the chip without exceeding the trainer's workspace rule (splits * N * K floats)."""
     import ctypes
     M, N, K = shape
     rows = ctypes.c_int(0)
-    splits = load_library().latte_debug_gemm_tn_plan(M, N, K, ctypes.byref(rows))
+    splits = lib.latte_debug_gemm_tn_plan(M, N, K, ctypes.byref(rows))
     assert splits >= 1 and rows.value % 64 == 0 and rows.value > 0
     assert (splits - 1) * rows.value < M <= splits * rows.value
     assert splits * ((N + 255) // 256) * ((K + 255) // 256) <= 768

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import GOLDEN, rel_l2
+from _util import GOLDEN, pinned, rel_l2
 from oracle import diffusion_oracle as do
 from oracle.make_golden import TRAINING_CASES, training_inputs
 
@@ -20,19 +20,29 @@ def _golden():
     return np.load(os.path.join(GOLDEN, "training_losses.npz"))
 
 
-@pytest.mark.parametrize("case", TRAINING_CASES, ids=lambda c: c[0])
-def test_oracle_training_losses_bit_identical_to_reference(case):
+def _oracle_training_losses(case):
+    """-> (q_sample, training_losses terms) of the oracle on the fixture's inputs; run through pinned()."""
     tag, kw, spec = case
-    z = _golden()
     s = do.Schedule(spec, predict_xstart=kw.get("predict_xstart", False), learn_sigma=kw.get("learn_sigma", True))
     x0, noise, t = training_inputs(s.num_timesteps)
     oc = 8 if kw.get("learn_sigma", True) else 4
-    assert torch.equal(do.q_sample(s, x0, t, noise), torch.from_numpy(z[f"{tag}::x_t"]))
     terms = do.training_losses(s, lambda x, tt: do.synthetic_model(x, tt, oc), x0, t, noise, LOSS_OF[tag])
+    return do.q_sample(s, x0, t, noise).numpy(), {k: v.numpy() for k, v in terms.items()}
+
+
+@pytest.mark.parametrize("case", TRAINING_CASES, ids=lambda c: c[0])
+def test_oracle_training_losses_bit_identical_to_reference(case):
+    """The terms on the pinned arithmetic (tests/_util.pinned) against the reference's on it (oracle/make_golden.py:pinned_reference)."""
+    tag, kw, spec = case
+    z = _golden()
+    p = np.load(os.path.join(GOLDEN, "pinned_reference.npz"))
+    x_t, terms = pinned(_oracle_training_losses, case)
+    assert torch.equal(torch.from_numpy(x_t), torch.from_numpy(z[f"{tag}::x_t"]))
     keys = {k.split("::")[1] for k in z.files if k.startswith(tag + "::")} - {"x_t"}
-    assert set(terms) == keys
+    assert set(terms) == keys and {k for k in p.files if k.startswith(f"training::{tag}::")} == {f"training::{tag}::{k}" for k in keys}
     for k in keys:
-        assert torch.equal(terms[k], torch.from_numpy(z[f"{tag}::{k}"])), (tag, k)
+        assert torch.equal(torch.from_numpy(terms[k]), torch.from_numpy(p[f"training::{tag}::{k}"])), (tag, k)
+    x0, _, t = training_inputs(do.Schedule(spec).num_timesteps)
     assert int(t[0]) == 0 and float(x0.abs().max()) == 1.0        # the fixture exercises the decoder-NLL and tail branches
 
 
