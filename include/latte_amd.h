@@ -307,7 +307,8 @@ int latte_vae_create(int latent_size, int max_frames, int compute_dtype, latte_v
 int latte_vae_create_temporal(int latent_size, int max_frames, int compute_dtype, latte_vae_t** out);
 void latte_vae_destroy(latte_vae_t* v);
 /* load_state_dict for ONE tensor named by its diffusers key ("decoder.up_blocks.2.resnets.0.conv1.weight",
- * "post_quant_conv.bias", ...); fp32, reference shape; encoder.* / quant_conv.* keys are not accepted. */
+ * "post_quant_conv.bias", ...); fp32, reference shape; a decoder handle does not accept encoder.* / quant_conv.* keys (an encoder
+ * handle accepts only those). */
 int latte_vae_num_keys(const latte_vae_t* v);
 const char* latte_vae_key(const latte_vae_t* v, int i);
 int latte_vae_load_tensor(latte_vae_t* v, const char* key, const float* data, int64_t numel, int on_device,
@@ -324,6 +325,27 @@ int latte_vae_decode(latte_vae_t* v, const float* z, int n_frames, float z_scale
  * fp32 -> half copies).  Synchronises the stream; bench.py's `vae_decode.roofline_table` is built from it. */
 int latte_vae_profile_decode(latte_vae_t* v, const float* z, int n_frames, float z_scale, int out_mode, void* out, float* ms_out,
                              int* launches_out, int n, void* stream);
+
+/* ------------------------------------------------------------------ VAE encoder
+ * diffusers.AutoencoderKL.encode (the reference's training step, train.py:204-211: vae.encode(x).latent_dist.sample().mul_(0.18215))
+ * for the same sd-vae-ft architecture: the same handle type, so latte_vae_num_keys / key / load_tensor / check_weights / destroy apply;
+ * its slots are the diffusers keys "encoder.*" and "quant_conv.*".  image_size: H = W of the frames, a multiple of 128, at most 512
+ * (latent h = image_size / 8); max_frames: largest N of one encode call; compute_dtype LATTE_DTYPE_F16 only.  latte_vae_decode on an
+ * encoder handle, and latte_vae_encode on a decoder handle, return LATTE_ERR_INVALID.  Parity with diffusers unpinned
+ * (tests/vae_encoder_reference.py restates it). */
+int latte_vae_create_encoder(int image_size, int max_frames, int compute_dtype, latte_vae_t** out);
+/* x: in_mode 0 fp32 NCHW [N, 3, H, W] in [-1, 1]; in_mode 1 uint8 NHWC [N, H, W, 3] read as x / 127.5 - 1.  out (fp32 NCHW):
+ * out_mode 0 the moments [N, 8, h, w] (DiagonalGaussianDistribution.parameters: mean = channels 0..3, logvar = 4..7);
+ * 1 mean * scale [N, 4, h, w] (.mode()); 2 (mean + exp(0.5 clamp(logvar, -30, 20)) noise) * scale [N, 4, h, w] (.sample() with the
+ * caller's N(0, 1) noise [N, 4, h, w]; noise may be NULL otherwise). */
+int latte_vae_encode(latte_vae_t* v, const void* x, int n_frames, int in_mode, const float* noise, float scale, int out_mode, float* out,
+                     void* stream);
+/* The posterior on moments [n, 8, hw] already encoded -> out [n, 4, hw]: what 1 mean * scale (mode), 2 (mean + std noise) * scale
+ * (sample, noise [n, 4, hw]), 3 logvar (clamped to [-30, 20]), 4 std = exp(0.5 logvar), 5 var = exp(logvar); scale applies to 1 and 2. */
+int latte_vae_posterior(const float* moments, const float* noise, int n, int hw, float scale, int what, float* out, void* stream);
+/* latte_vae_profile_decode for the encoder: the same five kernel classes (4 = conv_in, conv_out + posterior, fp32 -> half copies). */
+int latte_vae_profile_encode(latte_vae_t* v, const void* x, int n_frames, int in_mode, const float* noise, float scale, int out_mode, float* out,
+                             float* ms_out, int* launches_out, int n, void* stream);
 
 /* ------------------------------------------------------------------ LatteT2V denoiser (Latte-1 text-to-video)
  * LatteT2V.forward, /root/reference/models/latte_t2v.py:677-941 (constructor :475-672).

@@ -136,6 +136,21 @@ int latte_debug_groupnorm_f32(const float* x, void* y, const float* gamma, const
 struct latte_vae;
 int latte_debug_vae_trace(struct latte_vae* v, const float* z, int n_frames, float z_scale, int stop_after, float* trace_out,
                           int64_t* trace_numel, int* trace_dims, void* stream);
+/* The same for the VAE encoder (latte_vae_create_encoder; x and in_mode as latte_vae_encode).  Stages: 0 conv_in, then per down block i
+ * its two resnets and (i < 3) the down-sampler -> 1..11, 12 mid.resnets.0, 13 mid.attentions.0, 14 mid.resnets.1 (NHWC fp32 stream,
+ * trace_dims = N, H, W, C), 15 the moments (fp32 NCHW [N, 8, h, w], trace_dims = N, 8, h, w). */
+int latte_debug_vae_encode_trace(struct latte_vae* v, const void* x, int n_frames, int in_mode, int stop_after, float* trace_out,
+                                 int64_t* trace_numel, int* trace_dims, void* stream);
+/* The encoder's Downsample2D convolution alone: out32 [N, Hin/2, Win/2, Cout] = conv3x3(pad(in, (0, 1, 0, 1)), stride 2) + bias (+ res32);
+ * in half NHWC [N, Hin, Win, Cin], w fp32 [Cout, Cin, 3, 3] (packed to f16 here). */
+int latte_debug_conv3x3_down_f32(const void* in, const float* w, const float* bias, const float* res32, float* out32, int N, int Hin,
+                                 int Win, int Cin, int Cout, int dtype, void* stream);
+/* encoder.conv_in alone: x (in_mode 0 fp32 NCHW [N, 3, H, W], 1 uint8 NHWC [N, H, W, 3]), w fp32 [128, 3, 3, 3] -> out fp32 NHWC [N, H, W, 128]. */
+int latte_debug_vae_enc_conv_in(const void* x, int in_mode, const float* w, const float* bias, float* out, int N, int H, int W, void* stream);
+/* The encoder's tail after GroupNorm + SiLU: x half NHWC [N, H, W, 512] (x_lo: its f16 rounding residual, or NULL), conv_out w fp32
+ * [8, 512, 3, 3] + b [8], quant_conv qw [8, 8, 1, 1] + qb [8] -> moments fp32 NCHW [N, 8, H, W]. */
+int latte_debug_vae_enc_tail(const void* x, const void* x_lo, const float* w, const float* b, const float* qw, const float* qb, float* moments,
+                             int N, int H, int W, void* stream);
 
 /* Operand-path probe (measurement): 256 workgroups x `waves` waves, every wave issues `reps` bursts of 16 loads over a
  * cache-hot 16 KB window of `src` (>= 8 MiB readable).  mode 0: buffer_load_dwordx4 ... lds, 1: buffer_load_dword ... lds,
@@ -157,7 +172,9 @@ int latte_debug_dma_probe(const void* src, long long* out, int mode, int waves, 
  *                     4 = its persistent form (round 6: bit-identical, measured 6 - 13 % slower, not a default anywhere)
  *   "vae_split"       1024 + m: which stages of the temporal decoder run split-operand convolutions -- bits 0..4 of m = the spatial resnets of
  *                     {mid block, up block 0..3} add the pass on the activation's f16 rounding residual, bits 5..9 = the temporal resnets of the
- *                     same stages run three passes (hi*hi + lo*hi + hi*lo) instead of one (csrc/vae_engine.cpp: vae_split_mask)
+ *                     same stages run three passes (hi*hi + lo*hi + hi*lo) instead of one (csrc/vae_engine.cpp: vae_split_mask); the SD-VAE
+ *                     encoder reads the same layout once per encode call (bit 0 mid block, 1 + i down block i, 12 + i / 21 + i the down-sampler of
+ *                     block i, 11 conv_out; csrc/vae_engine.cpp: encode_split_mask)
  * Anything else is refused (LATTE_ERR_INVALID).  Replaces the LATTE_* environment variables round 3 read at every launch; the
  * measurement ablations whose results are garbage (attention variants 7-10, 16-19) exist only in a LATTE_DEBUG_BUILD=1 library. */
 int latte_debug_set_choice(const char* name, int value);

@@ -109,6 +109,10 @@ PROTOTYPES = {
     "latte_vae_check_weights": (c_int, [c_void]),
     "latte_vae_decode": (c_int, [c_void, c_void, c_int, c_f32, c_int, c_void, c_void]),
     "latte_vae_profile_decode": (c_int, [c_void, c_void, c_int, c_f32, c_int, c_void, c_void, c_void, c_int, c_void]),
+    "latte_vae_create_encoder": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_void)]),
+    "latte_vae_encode": (c_int, [c_void, c_void, c_int, c_int, c_void, c_f32, c_int, c_void, c_void]),
+    "latte_vae_posterior": (c_int, [c_void, c_void, c_int, c_int, c_f32, c_int, c_void, c_void]),
+    "latte_vae_profile_encode": (c_int, [c_void, c_void, c_int, c_int, c_void, c_f32, c_int, c_void, c_void, c_void, c_int, c_void]),
     # test hooks
     "latte_debug_gemm_lo8": (c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_int,
                                      c_int, c_void]),
@@ -147,6 +151,10 @@ PROTOTYPES = {
     "latte_debug_conv3x3": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                     c_void]),
     "latte_debug_vae_trace": (c_int, [c_void, c_void, c_int, c_f32, c_int, c_void, c_void, c_void, c_void]),
+    "latte_debug_vae_encode_trace": (c_int, [c_void, c_void, c_int, c_int, c_int, c_void, c_void, c_void, c_void]),
+    "latte_debug_conv3x3_down_f32": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_void]),
+    "latte_debug_vae_enc_conv_in": (c_int, [c_void, c_int, c_void, c_void, c_void, c_int, c_int, c_int, c_void]),
+    "latte_debug_vae_enc_tail": (c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_void]),
     "latte_debug_conv3rows_f32": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_void]),
     "latte_debug_conv3x3_f32": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                         c_void]),

@@ -248,7 +248,7 @@ int launch_fill_normal(float* out, size_t n, uint64_t seed, uint64_t offset, hip
 // out32 != nullptr: fp32 output  out32 = conv + bias (+ res32)  (the decoder's residual stream is fp32); else half `out` (+ res)
 int launch_conv3x3(const half_t* in, const half_t* w, const float* bias, const half_t* res, half_t* out,
                    const half_t* zeros, int N, int Hin, int Win, int Cin, int Cout, int ups, int dtype, hipStream_t st,
-                   const float* res32 = nullptr, float* out32 = nullptr, int taps3 = 0);
+                   const float* res32 = nullptr, float* out32 = nullptr, int taps3 = 0, int down = 0);   // down 1: the encoder's pad (0,1,0,1) + stride-2 form, Hout = Hin / 2
 // AutoencoderKLTemporalDecoder pieces: Conv3d (3,1,1) weight pack (optionally scaled by sigmoid(*mix)), bias scale, time_conv_out
 int launch_pack_conv_t(const float* w, half_t* out, int Cout, int Cin, const float* mix, int dtype, hipStream_t st, half_t* out_lo = nullptr);
 int launch_scale_by_sigmoid(const float* in, float* out, int n, const float* mix, hipStream_t st);
@@ -262,6 +262,13 @@ int launch_conv_in(const float* x, const float* wt, const float* bias, float* ou
 int launch_conv_out(const half_t* x, const float* wt, const float* bias, void* out, int N, int H, int W, int C, int out_mode,
                     int dtype, hipStream_t st, const half_t* x_lo = nullptr);   // x_lo: the f16 rounding residual of x (split input), or nullptr
 int launch_softmax_rows(const float* s, half_t* p, int rows, int L, float scale, int dtype, hipStream_t st);
+// SD-VAE encoder pieces: conv_in 3 -> 128 (in_mode 0 fp32 NCHW, 1 uint8 NHWC), conv_out 512 -> 8 with quant_conv folded in (moments fp32
+// NCHW), the fold itself, and the diagonal-Gaussian posterior (what 1 mode, 2 sample, 3 logvar, 4 std, 5 var)
+int launch_enc_conv_in(const void* x, int in_mode, const float* wt, const float* bias, float* out, int N, int H, int W, hipStream_t st);
+int launch_enc_conv_out(const half_t* x, const half_t* x_lo, const float* wt, const float* bias, float* moments, int N, int H, int W, int C,
+                        int dtype, hipStream_t st);
+int launch_fold_quant_conv(const float* co, const float* cb, const float* q, const float* qb, float* w, float* b, int K, hipStream_t st);
+int launch_posterior(const float* moments, const float* noise, int n, int hw, float scale, int what, float* out, hipStream_t st);
 int launch_pack_conv_w(const float* w, half_t* out, int Cout, int Cin, int dtype, hipStream_t st, half_t* out_lo = nullptr);   // out_lo: the f16 rounding residual
 int launch_pack_small_w(const float* w, float* out, int Cout, int Cin, int transpose, hipStream_t st);
 

@@ -348,6 +348,50 @@ int latte_debug_conv3x3_f32(const void* in, const float* w, const float* bias, c
   return rc;
 }
 
+int latte_debug_conv3x3_down_f32(const void* in, const float* w, const float* bias, const float* res32, float* out32, int N, int Hin,
+                                 int Win, int Cin, int Cout, int dtype, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  half_t *wp = nullptr, *zeros = nullptr;
+  LATTE_HIP(hipMalloc((void**)&wp, (size_t)Cout * Cin * 9 * 2));
+  LATTE_HIP(hipMalloc((void**)&zeros, 64));
+  LATTE_HIP(hipMemsetAsync(zeros, 0, 64, st));
+  int rc = launch_pack_conv_w(w, wp, Cout, Cin, dtype, st);
+  if (!rc) rc = launch_conv3x3((const half_t*)in, wp, bias, nullptr, nullptr, zeros, N, Hin, Win, Cin, Cout, 0, dtype, st, res32, out32, 0, 1);
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(wp);
+  (void)hipFree(zeros);
+  return rc;
+}
+
+int latte_debug_vae_enc_conv_in(const void* x, int in_mode, const float* w, const float* bias, float* out, int N, int H, int W, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  float* wt = nullptr;
+  LATTE_HIP(hipMalloc((void**)&wt, (size_t)27 * 128 * 4));
+  int rc = launch_pack_small_w(w, wt, 128, 3, 1, st);
+  if (!rc) rc = launch_enc_conv_in(x, in_mode, wt, bias, out, N, H, W, st);
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(wt);
+  return rc;
+}
+
+int latte_debug_vae_enc_tail(const void* x, const void* x_lo, const float* w, const float* b, const float* qw, const float* qb, float* moments,
+                             int N, int H, int W, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  constexpr int C = 512;
+  float *raw = nullptr, *wf = nullptr, *bf = nullptr;
+  LATTE_HIP(hipMalloc((void**)&raw, (size_t)8 * 9 * C * 4));
+  LATTE_HIP(hipMalloc((void**)&wf, (size_t)8 * 9 * C * 4));
+  LATTE_HIP(hipMalloc((void**)&bf, 64));
+  int rc = launch_pack_small_w(w, raw, 8, C, 0, st);
+  if (!rc) rc = launch_fold_quant_conv(raw, b, qw, qb, wf, bf, 9 * C, st);
+  if (!rc) rc = launch_enc_conv_out((const half_t*)x, (const half_t*)x_lo, wf, bf, moments, N, H, W, C, LATTE_DTYPE_F16, st);
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(raw);
+  (void)hipFree(wf);
+  (void)hipFree(bf);
+  return rc;
+}
+
 int latte_debug_groupnorm_f32(const float* x, void* y, const float* gamma, const float* beta, int N, int HW, int C, int silu,
                               int dtype, void* stream) {
   hipStream_t st = (hipStream_t)stream;

@@ -1,4 +1,4 @@
-// SD-VAE decoder kernels (gfx950):  AutoencoderKL.decode of diffusers 0.24.0, called by the reference at
+// SD-VAE decoder (and encoder) kernels (gfx950):  AutoencoderKL.decode of diffusers 0.24.0, called by the reference at
 // /root/reference/sample/sample.py:113-115 and sample_ddp.py:165-168 (class not vendored: see oracle/vae_oracle.py).
 //
 // Activations are NHWC half [N, H, W, C] (a pixel's channels are contiguous), so
@@ -10,7 +10,9 @@
 //                 tap reads pixel (y >> 1, x >> 1)) -- the upsampled tensor is never materialised;
 //   GroupNorm   = partial sums per (image, slab, group) -> finalize -> apply (+ SiLU), fp32 statistics;
 //   conv_in / post_quant_conv / conv_out (4 -> 4, 4 -> 512, 128 -> 3 channels) = small direct kernels;
-//   attention   = 1 head of 512 over H*W tokens: plain GEMMs (gemm.hip) + a row softmax.
+//   attention   = 1 head of 512 over H*W tokens: plain GEMMs (gemm.hip) + a row softmax;
+//   encoder     = the same conv with a stride-2 gather (Downsample2D, ConvArgs::down), conv_in 3 -> 128 from fp32 or uint8 frames,
+//                 conv_out 512 -> 8 with quant_conv folded in, and the diagonal-Gaussian posterior.
 #include "mfma_util.h"
 
 namespace latte {
@@ -41,6 +43,8 @@ struct ConvArgs {
   float* out32;         // fp32 output: out32 = acc + bias (+ res32), nothing is rounded to half
   const half_t* zeros;  // >= 16 bytes of zeros (padded taps)
   int N, Hin, Win, Cin, Cout, ups;   // Hout = Hin << ups
+  int down;    // 1: Downsample2D(use_conv, padding 0) of the SD-VAE encoder = F.pad(x, (0, 1, 0, 1)) then stride 2, no padding:
+               // Hout = Hin >> 1, output (y, x) reads input (2y + ky, 2x + kx), a tap at row Hin / column Win reads zero (never with ups)
   int taps3;   // 1: a 3-tap convolution along the image ROWS (w = [Cout, 3 * Cin], k = ky * Cin + ci; the temporal Conv3d (3,1,1) of
                // AutoencoderKLTemporalDecoder on the "image" [frames][h * w] of one video)
 };
@@ -56,7 +60,8 @@ __global__ void __launch_bounds__(256) conv3x3_kernel(ConvArgs g) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const int Hout = g.Hin << g.ups, Wout = g.Win << g.ups;
+  const int Hout = (g.Hin << g.ups) >> g.down, Wout = (g.Win << g.ups) >> g.down;
+  const int Hg = Hout << g.down, Wg = Wout << g.down;   // extent of the gather grid (the upsampled / the input image)
   const int M = g.N * Hout * Wout;
   const int K = (g.taps3 ? 3 : 9) * g.Cin;
   int tm, tn;
@@ -91,11 +96,11 @@ __global__ void __launch_bounds__(256) conv3x3_kernel(ConvArgs g) {
     char* sA = smem + buf * STAGE + wave * 1024;
     char* sB = sA + A_BYTES;
     const int tap = kt / cpt, c0 = (kt - tap * cpt) << 6;
-    const int dy = g.taps3 ? tap - 1 : tap / 3 - 1, dx = g.taps3 ? 0 : tap - (tap / 3) * 3 - 1;
+    const int dy = g.taps3 ? tap - 1 : tap / 3 - 1 + g.down, dx = g.taps3 ? 0 : tap - (tap / 3) * 3 - 1 + g.down;
 #pragma unroll
     for (int j = 0; j < INSTR; ++j) {
-      const int yy = py[j] + dy, xx = px[j] + dx;
-      const bool ok = yy >= 0 && yy < Hout && xx >= 0 && xx < Wout;
+      const int yy = (py[j] << g.down) + dy, xx = (px[j] << g.down) + dx;
+      const bool ok = yy >= 0 && yy < Hg && xx >= 0 && xx < Wg;
       const int sy = yy >> g.ups, sx = xx >> g.ups;
       const half_t* src = ok ? g.in + ((size_t)(pbase[j] + sy * g.Win + sx) * g.Cin + c0 + schunk * 8) : g.zeros;
       glds16(src, sA + j * NW * 1024);
@@ -190,7 +195,8 @@ __global__ void __launch_bounds__(512) conv3x3_pp_kernel(ConvArgs g) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int grp = wave >> 2, wn = wave & 3;
-  const int Hout = g.Hin << g.ups, Wout = g.Win << g.ups;
+  const int Hout = (g.Hin << g.ups) >> g.down, Wout = (g.Win << g.ups) >> g.down;
+  const int Hg = Hout << g.down, Wg = Wout << g.down;   // extent of the gather grid (the upsampled / the input image)
   const int M = g.N * Hout * Wout;
   const int K = (g.taps3 ? 3 : 9) * g.Cin;
   int tm, tn;
@@ -203,7 +209,7 @@ __global__ void __launch_bounds__(512) conv3x3_pp_kernel(ConvArgs g) {
   // Per pixel row of this lane (row grp*128 + srow + 32 j): without upsampling, the byte offset of the pixel's own channel chunk and
   // a bit mask of the taps that stay inside the image -- a tap is then ONE add of a scalar delta and a select; with the nearest-2x
   // upsample the source pixel of a tap depends on the parities, so (y, x, image) are kept and the address is formed per tap.
-  const bool fast = g.ups == 0;
+  const bool fast = g.ups == 0;   // (the stride-2 down-sampling form is always fast)
   int pyx[AH_INSTR], pbase[AH_INSTR];                   // ups: (y << 16 | x), image base pixel;  fast: tap mask, centre byte offset
   const int ntap = g.taps3 ? 3 : 9;
 #pragma unroll
@@ -215,11 +221,11 @@ __global__ void __launch_bounds__(512) conv3x3_pp_kernel(ConvArgs g) {
       if (fast) {
         int mask = 0;
         for (int tap = 0; tap < ntap; ++tap) {
-          const int yy = y + (g.taps3 ? tap - 1 : tap / 3 - 1), xx = x + (g.taps3 ? 0 : tap % 3 - 1);
-          if (yy >= 0 && yy < Hout && xx >= 0 && xx < Wout) mask |= 1 << tap;
+          const int yy = (y << g.down) + (g.taps3 ? tap - 1 : tap / 3 - 1 + g.down), xx = (x << g.down) + (g.taps3 ? 0 : tap % 3 - 1 + g.down);
+          if (yy >= 0 && yy < Hg && xx >= 0 && xx < Wg) mask |= 1 << tap;
         }
-        pyx[j] = mask;
-        pbase[j] = (int)(((unsigned)(img * g.Hin * g.Win + y * g.Win + x) * (unsigned)g.Cin + (unsigned)(schunk * 8)) * 2u);
+        pyx[j] = mask;   // down: the base pixel is (2y, 2x), only the bottom / right taps can leave the image
+        pbase[j] = (int)(((unsigned)(img * g.Hin * g.Win + (y << g.down) * g.Win + (x << g.down)) * (unsigned)g.Cin + (unsigned)(schunk * 8)) * 2u);
       } else {
         pyx[j] = (y << 16) | x;
         pbase[j] = img * g.Hin * g.Win;
@@ -241,7 +247,7 @@ __global__ void __launch_bounds__(512) conv3x3_pp_kernel(ConvArgs g) {
   auto dma_a_half = [&](int kt) {
     char* sA = smem + (kt & 1) * STAGE + grp * 128 * 128 + wn * 1024;
     const int tap = kt / cpt, c0 = (kt - tap * cpt) << 6;
-    const int dy = g.taps3 ? tap - 1 : tap / 3 - 1, dx = g.taps3 ? 0 : tap - (tap / 3) * 3 - 1;
+    const int dy = g.taps3 ? tap - 1 : tap / 3 - 1 + g.down, dx = g.taps3 ? 0 : tap - (tap / 3) * 3 - 1 + g.down;
     if (fast) {
       const int delta = ((dy * g.Win + dx) * g.Cin + c0) * 2;   // wave-uniform byte step of this tap / channel tile
 #pragma unroll
@@ -381,7 +387,8 @@ __global__ void __launch_bounds__(512) conv3x3_pps_kernel(ConvArgs g) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int grp = wave >> 2, wn = wave & 3;
-  const int Hout = g.Hin << g.ups, Wout = g.Win << g.ups;
+  const int Hout = (g.Hin << g.ups) >> g.down, Wout = (g.Win << g.ups) >> g.down;
+  const int Hg = Hout << g.down, Wg = Wout << g.down;   // extent of the gather grid (the upsampled / the input image)
   const int M = g.N * Hout * Wout;
   const int K = (g.taps3 ? 3 : 9) * g.Cin;
   const int nk = K / 64;
@@ -421,11 +428,11 @@ __global__ void __launch_bounds__(512) conv3x3_pps_kernel(ConvArgs g) {
         if (fast) {
           int mask = 0;
           for (int tap = 0; tap < ntap; ++tap) {
-            const int yy = y + (g.taps3 ? tap - 1 : tap / 3 - 1), xx = x + (g.taps3 ? 0 : tap % 3 - 1);
-            if (yy >= 0 && yy < Hout && xx >= 0 && xx < Wout) mask |= 1 << tap;
+            const int yy = (y << g.down) + (g.taps3 ? tap - 1 : tap / 3 - 1 + g.down), xx = (x << g.down) + (g.taps3 ? 0 : tap % 3 - 1 + g.down);
+            if (yy >= 0 && yy < Hg && xx >= 0 && xx < Wg) mask |= 1 << tap;
           }
           pyx[j] = mask;
-          pbase[j] = (int)(((unsigned)(img * g.Hin * g.Win + y * g.Win + x) * (unsigned)g.Cin + (unsigned)(schunk * 8)) * 2u);
+          pbase[j] = (int)(((unsigned)(img * g.Hin * g.Win + (y << g.down) * g.Win + (x << g.down)) * (unsigned)g.Cin + (unsigned)(schunk * 8)) * 2u);
         } else {
           pyx[j] = (y << 16) | x;
           pbase[j] = img * g.Hin * g.Win;
@@ -446,7 +453,7 @@ __global__ void __launch_bounds__(512) conv3x3_pps_kernel(ConvArgs g) {
   auto dma_a_half = [&](int kt, int stg) {
     char* sA = smem + stg * STAGE + grp * 128 * 128 + wn * 1024;
     const int tap = kt / cpt, c0 = (kt - tap * cpt) << 6;
-    const int dy = g.taps3 ? tap - 1 : tap / 3 - 1, dx = g.taps3 ? 0 : tap - (tap / 3) * 3 - 1;
+    const int dy = g.taps3 ? tap - 1 : tap / 3 - 1 + g.down, dx = g.taps3 ? 0 : tap - (tap / 3) * 3 - 1 + g.down;
     if (fast) {
       const int delta = ((dy * g.Win + dx) * g.Cin + c0) * 2;
 #pragma unroll
@@ -958,6 +965,150 @@ __global__ void __launch_bounds__(256) conv_out_c128_kernel(const half_t* __rest
   }
 }
 
+// ------------------------------------------------------------------------------------------------ SD-VAE encoder (small kernels)
+// encoder.conv_in: 3 -> 128 channels, 3x3 pad 1, at the image's full resolution (K = 27: below the MFMA tile) -> the fp32 NHWC residual
+// stream [N, H, W, 128].  wt = [27][128] fp32 (k = (ky * 3 + kx) * 3 + ci).  in_mode 0: x fp32 NCHW [N, 3, H, W] (what the reference
+// feeds vae.encode); 1: x uint8 NHWC [N, H, W, 3] read as u / 127.5 - 1 (ToTensorVideo then Normalize(0.5, 0.5), so a video is never
+// copied to float).  Eight pixels per workgroup, 32 lanes per pixel with four output channels each (512 contiguous bytes per pixel).
+__global__ void __launch_bounds__(256) enc_conv_in_kernel(const void* __restrict__ x, int in_mode, const float* __restrict__ wt,
+                                                          const float* __restrict__ bias, float* __restrict__ out, int N, int H, int W) {
+  constexpr int C = 128;
+  __shared__ __attribute__((aligned(16))) float wl[27 * C];
+  __shared__ float patch[8][28];
+  for (int i = threadIdx.x; i < 27 * C; i += 256) wl[i] = wt[i];
+  const int pl = threadIdx.x >> 5, lane = threadIdx.x & 31;
+  const long total = (long)N * H * W;
+  const long p = (long)blockIdx.x * 8 + pl;
+  if (p < total && lane < 27) {
+#pragma clang fp contract(off)
+    const int n = (int)(p / ((long)H * W)), rem = (int)(p - (long)n * H * W), y = rem / W, xw = rem - y * W;
+    const int tap = lane / 3, ci = lane - tap * 3;
+    const int yy = y + tap / 3 - 1, xx = xw + tap % 3 - 1;
+    float v = 0.f;
+    if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
+      if (in_mode == 0) v = ((const float*)x)[(((size_t)n * 3 + ci) * H + yy) * W + xx];
+      else v = (float)((const unsigned char*)x)[(((size_t)n * H + yy) * W + xx) * 3 + ci] / 127.5f - 1.0f;
+    }
+    patch[pl][lane] = v;
+  }
+  __syncthreads();
+  if (p >= total) return;
+  const float4 b4 = *(const float4*)(bias + lane * 4);
+  float a0 = b4.x, a1 = b4.y, a2 = b4.z, a3 = b4.w;
+#pragma unroll
+  for (int k = 0; k < 27; ++k) {
+    const float v = patch[pl][k];
+    const float4 w4 = *(const float4*)(wl + k * C + lane * 4);
+    a0 = fmaf(v, w4.x, a0); a1 = fmaf(v, w4.y, a1); a2 = fmaf(v, w4.z, a2); a3 = fmaf(v, w4.w, a3);
+  }
+  *(float4*)(out + (size_t)p * C + lane * 4) = make_float4(a0, a1, a2, a3);
+}
+
+// encoder.conv_out (512 -> 8, 3x3 pad 1) with quant_conv (8 -> 8, 1x1) folded into its weights (fold_quant_conv_kernel) -> the posterior's
+// moments, fp32 NCHW [N, 8, H, W] (DiagonalGaussianDistribution.parameters).  x: half GroupNorm+SiLU output [N, H, W, 512] (+ x_lo, its
+// f16 rounding residual, or nullptr).  One wave per 8 consecutive pixels of a row (W % 8 == 0): lane = 8-channel octet, the 64 weights of
+// a (tap, octet) are loaded once per tap and reused for the 8 pixels; the 64 partial sums are reduced over the wave at the end.
+template <int DT>
+__global__ void __launch_bounds__(256) enc_conv_out_kernel(const half_t* __restrict__ x, const half_t* __restrict__ x_lo,
+                                                           const float* __restrict__ wt, const float* __restrict__ bias,
+                                                           float* __restrict__ moments, int N, int H, int W) {
+  constexpr int C = 512, CO = 8, PX = 8;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long total = (long)N * H * W;
+  const long base = ((long)blockIdx.x * 4 + wave) * PX;
+  if (base >= total) return;
+  const int n = (int)(base / ((long)H * W));
+  const int rem = (int)(base - (long)n * H * W), y = rem / W, x0 = rem - y * W;
+  float acc[PX][CO];
+#pragma unroll
+  for (int q = 0; q < PX; ++q)
+#pragma unroll
+    for (int o = 0; o < CO; ++o) acc[q][o] = 0.f;
+  for (int tap = 0; tap < 9; ++tap) {
+    const int dy = tap / 3 - 1, dx = tap % 3 - 1, yy = y + dy;
+    if (yy < 0 || yy >= H) continue;                          // wave-uniform
+    float w[CO][8];
+#pragma unroll
+    for (int o = 0; o < CO; ++o) {
+      const float4 wa = *(const float4*)(wt + (size_t)o * 9 * C + tap * C + lane * 8), wb = *(const float4*)(wt + (size_t)o * 9 * C + tap * C + lane * 8 + 4);
+      w[o][0] = wa.x; w[o][1] = wa.y; w[o][2] = wa.z; w[o][3] = wa.w; w[o][4] = wb.x; w[o][5] = wb.y; w[o][6] = wb.z; w[o][7] = wb.w;
+    }
+    const size_t rowo = ((size_t)n * H + yy) * W * C + lane * 8;
+#pragma unroll
+    for (int q = 0; q < PX; ++q) {
+      const int xx = x0 + q + dx;
+      if (xx < 0 || xx >= W) continue;                        // wave-uniform
+      const u32x4 v = *(const u32x4*)(x + rowo + (size_t)xx * C);
+      float f[8];
+      unpack2<DT>(v[0], f[0], f[1]); unpack2<DT>(v[1], f[2], f[3]);
+      unpack2<DT>(v[2], f[4], f[5]); unpack2<DT>(v[3], f[6], f[7]);
+      if (x_lo != nullptr) {
+        const u32x4 l = *(const u32x4*)(x_lo + rowo + (size_t)xx * C);
+        float g[8];
+        unpack2<DT>(l[0], g[0], g[1]); unpack2<DT>(l[1], g[2], g[3]);
+        unpack2<DT>(l[2], g[4], g[5]); unpack2<DT>(l[3], g[6], g[7]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] += g[e];
+      }
+#pragma unroll
+      for (int o = 0; o < CO; ++o)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[q][o] = fmaf(f[e], w[o][e], acc[q][o]);
+    }
+  }
+  float mine = 0.f;   // lane q * 8 + o keeps the sum of (pixel q, output o)
+#pragma unroll
+  for (int q = 0; q < PX; ++q)
+#pragma unroll
+    for (int o = 0; o < CO; ++o) {
+      float a = acc[q][o];
+#pragma unroll
+      for (int s = 32; s > 0; s >>= 1) a += __shfl_xor(a, s, 64);
+      if (lane == q * CO + o) mine = a;
+    }
+  const int q = lane >> 3, o = lane & 7;
+  moments[(((size_t)n * CO + o) * H + y) * W + x0 + q] = mine + bias[o];
+}
+
+// quant_conv folded into conv_out in fp32: w[o][k] = sum_j q[o][j] co[j][k], b[o] = sum_j q[o][j] cb[j] + qb[o]  (co = [8][K] packed)
+__global__ void fold_quant_conv_kernel(const float* __restrict__ co, const float* __restrict__ cb, const float* __restrict__ q,
+                                       const float* __restrict__ qb, float* __restrict__ w, float* __restrict__ b, int K) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < 8 * K) {
+    const int o = i / K, k = i - o * K;
+    float a = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a = fmaf(q[o * 8 + j], co[(size_t)j * K + k], a);
+    w[i] = a;
+  }
+  if (i < 8) {
+    float a = qb[i];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a = fmaf(q[i * 8 + j], cb[j], a);
+    b[i] = a;
+  }
+}
+
+// DiagonalGaussianDistribution on the moments [n, 8, hw] (mean = channels 0..3, logvar = 4..7; logvar clamped to [-30, 20]) -> [n, 4, hw]:
+// what 1 mode * scale, 2 (mean + exp(0.5 logvar) noise) * scale (.sample() with the caller's N(0, 1) noise), 3 logvar, 4 std, 5 var
+__global__ void posterior_kernel(const float* __restrict__ m, const float* __restrict__ noise, int n, int hw, float scale, int what,
+                                 float* __restrict__ out) {
+#pragma clang fp contract(off)
+  const size_t total = (size_t)n * 4 * hw, per = (size_t)4 * hw;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t img = i / per, r = i - img * per;
+    const float mean = m[img * 2 * per + r];
+    const float lv = fminf(fmaxf(m[img * 2 * per + per + r], -30.0f), 20.0f);
+    float v;
+    if (what == 1) v = mean * scale;
+    else if (what == 2) v = (mean + expf(0.5f * lv) * noise[i]) * scale;
+    else if (what == 3) v = lv;
+    else if (what == 4) v = expf(0.5f * lv);
+    else v = expf(lv);
+    out[i] = v;
+  }
+}
+
 // P[row, :] = softmax(scale * S[row, :]) -> half; one wave per row (L % 64 == 0, L <= 4096)
 template <int DT>
 __global__ void __launch_bounds__(256) softmax_rows_kernel(const float* __restrict__ s, half_t* __restrict__ p, int rows, int L,
@@ -1090,18 +1241,21 @@ inline int grid_for(size_t n, int block) {
 
 int launch_conv3x3(const half_t* in, const half_t* w, const float* bias, const half_t* res, half_t* out,
                    const half_t* zeros, int N, int Hin, int Win, int Cin, int Cout, int ups, int dtype, hipStream_t st,
-                   const float* res32, float* out32, int taps3) {
+                   const float* res32, float* out32, int taps3, int down) {
   if (Cin % 64 != 0 || Cout % 128 != 0) return fail(LATTE_ERR_INVALID, "conv3x3: need Cin % 64 == 0 and Cout % 128 == 0");
   if (!out && !out32) return fail(LATTE_ERR_INVALID, "conv3x3: no output");
   if (taps3 && ups) return fail(LATTE_ERR_INVALID, "conv3x3: the 3-tap form has no upsampling");
-  ConvArgs a{in, w, bias, res, out, res32, out32, zeros, N, Hin, Win, Cin, Cout, ups, taps3};
-  const int M = N * (Hin << ups) * (Win << ups);
+  if (down && (ups || taps3 || down != 1)) return fail(LATTE_ERR_INVALID, "conv3x3: the stride-2 form has no upsampling and no 3-tap mode");
+  if (down && (Hin % 2 || Win % 2)) return fail(LATTE_ERR_INVALID, "conv3x3: the stride-2 form needs an even input height and width");
+  ConvArgs a{in, w, bias, res, out, res32, out32, zeros, N, Hin, Win, Cin, Cout, ups, down, taps3};
+  const int M = N * ((Hin << ups) >> down) * ((Win << ups) >> down);
   if (dtype != LATTE_DTYPE_F16) return fail(LATTE_ERR_INVALID, "conv3x3: the VAE kernels are built for f16 operands only");
   // the ping-pong kernel (256 pixels x 128 | 256 channels) wherever its tiles fill the chip; small maps keep the 128 x 128 tile
   // (latte_debug_set_choice("conv_kernel", 1) forces the plain kernel: A/B tests)
   const int bn = Cout % 256 == 0 ? 256 : 128;
   const int pp_tiles = ((M + 255) / 256) * (Cout / bn);
-  // its gather addresses the input through 32-bit buffer offsets and, with the upsample, packs (y, x) into 16 bits each
+  // its gather addresses the input through 32-bit buffer offsets and, with the upsample, packs (y, x) into 16 bits each (the stride-2
+  // form takes the tap-mask path: the input's byte size is the bound there too)
   const bool pp_ok = (uint64_t)N * Hin * Win * Cin * 2 < (1ull << 32) && (uint64_t)Cout * 9 * Cin * 2 < (1ull << 32) &&
                      (!ups || ((Hin << ups) < 32768 && (Win << ups) < 65536));
   // round 6: the persistent form of the ping-pong kernel (conv3x3_pps_kernel) is bit-identical and SLOWER (SD-VAE decode: convolutions
@@ -1195,6 +1349,42 @@ int launch_conv_out(const half_t* x, const float* wt, const float* bias, void* o
     hipLaunchKernelGGL(conv_out_c128_kernel<LATTE_DTYPE_F16>, dim3((total + 63) / 64), dim3(256), lds, st, x, wt, bias, out, N, H, W, out_mode, x_lo);
   else
     hipLaunchKernelGGL(conv_out_kernel<LATTE_DTYPE_F16>, dim3((total + 255) / 256), dim3(256), lds, st, x, wt, bias, out, N, H, W, C, out_mode, x_lo);
+  kprof_mark(VC_SMALL, st);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+
+int launch_enc_conv_in(const void* x, int in_mode, const float* wt, const float* bias, float* out, int N, int H, int W, hipStream_t st) {
+  if (in_mode != 0 && in_mode != 1) return fail(LATTE_ERR_INVALID, "encoder conv_in: in_mode must be 0 (fp32 NCHW) or 1 (uint8 NHWC)");
+  const long total = (long)N * H * W;
+  hipLaunchKernelGGL(enc_conv_in_kernel, dim3((unsigned)((total + 7) / 8)), dim3(256), 0, st, x, in_mode, wt, bias, out, N, H, W);
+  kprof_mark(VC_SMALL, st);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+
+int launch_enc_conv_out(const half_t* x, const half_t* x_lo, const float* wt, const float* bias, float* moments, int N, int H, int W, int C,
+                        int dtype, hipStream_t st) {
+  if (dtype != LATTE_DTYPE_F16) return fail(LATTE_ERR_INVALID, "encoder conv_out: the VAE kernels are built for f16 operands only");
+  if (C != 512 || W % 8 != 0) return fail(LATTE_ERR_INVALID, "encoder conv_out: needs 512 input channels and W % 8 == 0");
+  const long total = (long)N * H * W;
+  hipLaunchKernelGGL(enc_conv_out_kernel<LATTE_DTYPE_F16>, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, st, x, x_lo, wt, bias, moments, N, H, W);
+  kprof_mark(VC_SMALL, st);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+
+int launch_fold_quant_conv(const float* co, const float* cb, const float* q, const float* qb, float* w, float* b, int K, hipStream_t st) {
+  hipLaunchKernelGGL(fold_quant_conv_kernel, dim3((8 * K + 255) / 256), dim3(256), 0, st, co, cb, q, qb, w, b, K);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+
+int launch_posterior(const float* moments, const float* noise, int n, int hw, float scale, int what, float* out, hipStream_t st) {
+  if (what < 1 || what > 5) return fail(LATTE_ERR_INVALID, "vae_posterior: what must be 1 (mode), 2 (sample), 3 (logvar), 4 (std) or 5 (var)");
+  if (what == 2 && !noise) return fail(LATTE_ERR_INVALID, "vae_posterior: sample needs noise");
+  if (n <= 0 || hw <= 0) return fail(LATTE_ERR_INVALID, "vae_posterior: bad shape");
+  hipLaunchKernelGGL(posterior_kernel, dim3(grid_for((size_t)n * 4 * hw, 256)), dim3(256), 0, st, moments, noise, n, hw, scale, what, out);
   kprof_mark(VC_SMALL, st);
   LATTE_HIP(hipGetLastError());
   return LATTE_OK;

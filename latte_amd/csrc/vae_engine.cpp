@@ -1,4 +1,4 @@
-// Host logic of the SD-VAE decoder: weight ingestion by diffusers state-dict key, workspace, decode().
+// Host logic of the SD-VAE decoder and encoder: weight ingestion by diffusers state-dict key, workspace, decode(), encode().
 //
 //   AutoencoderKL.decode(z).sample      diffusers 0.24.0 (un-vendored; oracle/vae_oracle.py restates it)
 //   called by the reference at          /root/reference/sample/sample.py:113-115, sample_ddp.py:165-168
@@ -94,6 +94,16 @@ struct latte_vae {
   bool temporal = false;
   TResnet tmid[2], tup[4][3];
   float *tco_w = nullptr, *tco_b = nullptr;
+  // SD-VAE ENCODER mode (latte_vae_create_encoder): h is the latent size, img = 8 h the image size; encoder.* / quant_conv.* slots only
+  bool encoder = false;
+  int img = 0;
+  Resnet down[4][2];
+  half_t *dnc_w[3] = {nullptr, nullptr, nullptr}, *dnc_w_lo[3] = {nullptr, nullptr, nullptr};   // Downsample2D conv weights (+ f16 residual)
+  float* dnc_b[3] = {nullptr, nullptr, nullptr};
+  float *eco_raw = nullptr, *eco_rb = nullptr, *eq_w = nullptr, *eq_b = nullptr;   // conv_out [8][9 * 512] packed, its bias, quant_conv 8 x 8 + 8
+  float *eco_w = nullptr, *eco_b = nullptr;   // conv_out with quant_conv folded in (fp32, at the first encode after a load)
+  float* moments = nullptr;                   // [max_frames, 8, h, w] when the caller asked for mode / sample
+  int enc_split = 0;                          // split-operand mask of the running encode (read once per call)
 };
 
 namespace {
@@ -174,8 +184,16 @@ int make_tresnet(latte_vae* v, TResnet& t, const std::string& p, int c) {
 // spatial resnets of the five stages add the pass on the WEIGHTS' f16 rounding residual; bit 20: the shortcuts' weight residual; bits 21..23: the
 // upsamplers' weight residual.
 // latte_debug_set_choice("vae_split", (1 << 24) | mask) overrides the default (measurement / parity sweeps).
+// The encoder uses the same bit layout with its own stages (resnets: bit 0 = mid block, 1 + i = down block i; bits 12..14 / 21..23 = the
+// down-sampler of down block i; bit 11 = conv_out); its mask is read once per encode call (encode_split_mask) and held in enc_split.
 constexpr int VAE_SPLIT_DEFAULT_TEMPORAL = 0x319c03, VAE_SPLIT_DEFAULT_SPATIAL = 0x301c00;
+constexpr int VAE_SPLIT_DEFAULT_ENCODER = 0xf07c00;   // 1.01e-3 -> 7.7e-4 worst of five draws for +0.8 ms
+int encode_split_mask() {
+  const int c = debug_choice(DBG_VAE_SPLIT);
+  return (c >> 24) == 1 ? (c & 0xffffff) : VAE_SPLIT_DEFAULT_ENCODER;
+}
 int vae_split_mask(const latte_vae* v) {
+  if (v->encoder) return v->enc_split;
   const int c = debug_choice(DBG_VAE_SPLIT);
   return (c >> 24) == 1 ? (c & 0xffffff) : (v->temporal ? VAE_SPLIT_DEFAULT_TEMPORAL : VAE_SPLIT_DEFAULT_SPATIAL);
 }
@@ -272,6 +290,7 @@ int run_tresnet(latte_vae* v, const TResnet& t, float* x, half_t* c, half_t* clo
 }
 
 int vae_create_impl(int latent_size, int max_frames, int compute_dtype, bool temporal, latte_vae_t** out);
+int vae_create_encoder_impl(int image_size, int max_frames, int compute_dtype, latte_vae_t** out);
 
 }  // namespace
 
@@ -283,10 +302,69 @@ int latte_vae_create(int latent_size, int max_frames, int compute_dtype, latte_v
 int latte_vae_create_temporal(int latent_size, int max_frames, int compute_dtype, latte_vae_t** out) {
   return vae_create_impl(latent_size, max_frames, compute_dtype, true, out);
 }
+int latte_vae_create_encoder(int image_size, int max_frames, int compute_dtype, latte_vae_t** out) {
+  return vae_create_encoder_impl(image_size, max_frames, compute_dtype, out);
+}
 
 }  // extern "C"
 
 namespace {
+// UNetMidBlock2D's attention: weights and scratch under prefix a ("decoder.mid_block.attentions.0." / "encoder.mid_block.attentions.0.")
+int make_mid_attention(latte_vae* v, const std::string& a) {
+  const int top = v->ch[3];
+  int rc;
+#define ATRY(x) do { if ((rc = (x))) return rc; } while (0)
+  ATRY(valloc(v, &v->agn_w, top)); ATRY(valloc(v, &v->agn_b, top));
+  ATRY(valloc(v, &v->aq_b, top)); ATRY(valloc(v, &v->ak_b, top)); ATRY(valloc(v, &v->av_b, top)); ATRY(valloc(v, &v->ao_b, top));
+  ATRY(valloc(v, &v->ao_b_eff, top)); ATRY(valloc(v, &v->zero_bias, 4096));
+  ATRY(valloc(v, &v->aq_w, (size_t)top * top)); ATRY(valloc(v, &v->ak_w, (size_t)top * top));
+  ATRY(valloc(v, &v->av_w, (size_t)top * top)); ATRY(valloc(v, &v->ao_w, (size_t)top * top));
+  ATRY(valloc(v, &v->ao_w_f32, (size_t)top * top));
+  vslot(v, a + "group_norm.weight", top, VP_F32, v->agn_w);
+  vslot(v, a + "group_norm.bias", top, VP_F32, v->agn_b);
+  vslot(v, a + "to_q.weight", (int64_t)top * top, VP_LINEAR_H16, v->aq_w);
+  vslot(v, a + "to_q.bias", top, VP_F32, v->aq_b);
+  vslot(v, a + "to_k.weight", (int64_t)top * top, VP_LINEAR_H16, v->ak_w);
+  vslot(v, a + "to_k.bias", top, VP_F32, v->ak_b);
+  vslot(v, a + "to_v.weight", (int64_t)top * top, VP_LINEAR_H16, v->av_w);
+  vslot(v, a + "to_v.bias", top, VP_F32, v->av_b);
+  vslot(v, a + "to_out.0.weight", (int64_t)top * top, VP_LINEAR_H16, v->ao_w);
+  vslot(v, a + "to_out.0.bias", top, VP_F32, v->ao_b);
+#undef ATRY
+  return LATTE_OK;
+}
+
+// UNetMidBlock2D's attention on the fp32 stream a [N, H, W, 512] (in place): 1 head, dim 512, tokens = H*W per frame; b, c, d: half scratch
+int run_mid_attention(latte_vae* v, float* a, half_t* b, half_t* c, half_t* d, int N, int H, int W, hipStream_t st) {
+  int rc;
+  const int dt = v->dtype, top = v->ch[3];
+  const int L = H * W;
+  if (L % 128 != 0) return fail(LATTE_ERR_INVALID, "vae: H*W must be a multiple of 128 for the attention GEMMs");
+  if ((rc = launch_groupnorm(a, 1, c, v->agn_w, v->agn_b, v->gn_partial, v->gn_stats, N, L, top, 0, dt, st))) return rc;
+  if ((rc = gemm_h16(c, v->aq_w, v->aq_b, b, nullptr, N * L, top, top, EPI_BIAS_H16, dt, st))) return rc;   // q  [N L, 512]
+  if ((rc = gemm_h16(c, v->ak_w, v->ak_b, d, nullptr, N * L, top, top, EPI_BIAS_H16, dt, st))) return rc;   // k  [N L, 512]
+  half_t* vt = b + (size_t)N * L * top;   // V0^T per frame [512, L], behind q in buffer b
+  half_t* pm = d + (size_t)N * L * top;   // P per frame [L, L], behind k in buffer d
+  half_t* o = c + (size_t)N * L * top;    // attention output [N L, 512], behind the normed input in buffer c
+  const float scale = 1.0f / std::sqrt((float)top);
+  for (int f = 0; f < N; ++f) {
+    const half_t* hf = c + (size_t)f * L * top;
+    if ((rc = gemm_h16(v->av_w, hf, v->zero_bias, vt, nullptr, top, L, top, EPI_BIAS_H16, dt, st))) return rc;          // V0^T = Wv h^T
+    if ((rc = gemm_h16(b + (size_t)f * L * top, d + (size_t)f * L * top, v->zero_bias, v->scores, nullptr, L, L, top,
+                       EPI_BIAS_F32, dt, st))) return rc;                                                               // S = q k^T
+    if ((rc = launch_softmax_rows(v->scores, pm, L, L, scale, dt, st))) return rc;
+    if ((rc = gemm_h16(pm, vt, v->zero_bias, o + (size_t)f * L * top, nullptr, L, top, L, EPI_BIAS_H16, dt, st))) return rc;  // P V0
+  }
+  {  // to_out + residual straight into the fp32 stream: stream += 1 * (o Wo^T + b_eff)
+    GemmArgs g{};
+    g.A = o; g.W = v->ao_w; g.bias = v->ao_b_eff; g.out = a; g.gate = v->ones; g.gate_stride = 0;
+    g.M = N * L; g.N = top; g.K = top; g.rows_per_sample = N * L;
+    if ((rc = launch_gemm(g, EPI_GATE_RES_F32, dt, 1, st))) return rc;
+    kprof_mark(VC_ATTN, st);
+  }
+  return LATTE_OK;
+}
+
 int vae_create_impl(int latent_size, int max_frames, int compute_dtype, bool temporal, latte_vae_t** out) {
   if (!out || latent_size <= 0 || max_frames <= 0) return fail(LATTE_ERR_INVALID, "vae_create: bad arguments");
   if (compute_dtype != LATTE_DTYPE_F16)
@@ -315,25 +393,7 @@ int vae_create_impl(int latent_size, int max_frames, int compute_dtype, bool tem
   vslot(v, "decoder.conv_in.bias", top, VP_F32, v->ci_b);
   TRY(make_resnet(v, v->mid[0], "decoder.mid_block.resnets.0." + sp, top, top));
   if (temporal) TRY(make_tresnet(v, v->tmid[0], "decoder.mid_block.resnets.0.", top));
-  {
-    const std::string a = "decoder.mid_block.attentions.0.";
-    TRY(valloc(v, &v->agn_w, top)); TRY(valloc(v, &v->agn_b, top));
-    TRY(valloc(v, &v->aq_b, top)); TRY(valloc(v, &v->ak_b, top)); TRY(valloc(v, &v->av_b, top)); TRY(valloc(v, &v->ao_b, top));
-    TRY(valloc(v, &v->ao_b_eff, top)); TRY(valloc(v, &v->zero_bias, 4096));
-    TRY(valloc(v, &v->aq_w, (size_t)top * top)); TRY(valloc(v, &v->ak_w, (size_t)top * top));
-    TRY(valloc(v, &v->av_w, (size_t)top * top)); TRY(valloc(v, &v->ao_w, (size_t)top * top));
-    TRY(valloc(v, &v->ao_w_f32, (size_t)top * top));
-    vslot(v, a + "group_norm.weight", top, VP_F32, v->agn_w);
-    vslot(v, a + "group_norm.bias", top, VP_F32, v->agn_b);
-    vslot(v, a + "to_q.weight", (int64_t)top * top, VP_LINEAR_H16, v->aq_w);
-    vslot(v, a + "to_q.bias", top, VP_F32, v->aq_b);
-    vslot(v, a + "to_k.weight", (int64_t)top * top, VP_LINEAR_H16, v->ak_w);
-    vslot(v, a + "to_k.bias", top, VP_F32, v->ak_b);
-    vslot(v, a + "to_v.weight", (int64_t)top * top, VP_LINEAR_H16, v->av_w);
-    vslot(v, a + "to_v.bias", top, VP_F32, v->av_b);
-    vslot(v, a + "to_out.0.weight", (int64_t)top * top, VP_LINEAR_H16, v->ao_w);
-    vslot(v, a + "to_out.0.bias", top, VP_F32, v->ao_b);
-  }
+  TRY(make_mid_attention(v, "decoder.mid_block.attentions.0."));
   TRY(make_resnet(v, v->mid[1], "decoder.mid_block.resnets.1." + sp, top, top));
   if (temporal) TRY(make_tresnet(v, v->tmid[1], "decoder.mid_block.resnets.1.", top));
   int prev = top;
@@ -378,6 +438,74 @@ int vae_create_impl(int latent_size, int max_frames, int compute_dtype, bool tem
   TRY(valloc(v, &v->zeros, 64));
   TRY(valloc(v, &v->pq_out, (size_t)max_frames * latent_size * latent_size * 4));
   const size_t L = (size_t)latent_size * latent_size;
+  TRY(valloc(v, &v->scores, L * L));
+  TRY(valloc(v, &v->gn_partial, (size_t)max_frames * groupnorm_max_slabs() * 64));
+  TRY(valloc(v, &v->gn_stats, (size_t)max_frames * 64));
+  TRY(valloc(v, &v->stage, (size_t)v->stage_numel));
+#undef TRY
+  *out = v;
+  return LATTE_OK;
+}
+
+// diffusers Encoder (down_block_types 4 x DownEncoderBlock2D, layers_per_block 2, double_z) + quant_conv of the sd-vae-ft architecture
+int vae_create_encoder_impl(int image_size, int max_frames, int compute_dtype, latte_vae_t** out) {
+  if (!out || image_size <= 0 || max_frames <= 0) return fail(LATTE_ERR_INVALID, "vae_create_encoder: bad arguments");
+  if (compute_dtype != LATTE_DTYPE_F16)
+    return fail(LATTE_ERR_INVALID, "vae_create_encoder: the encoder runs f16 MFMA operands only (as the decoder; bf16 operands are not offered)");
+  if (image_size % 128 != 0 || image_size > 512)
+    return fail(LATTE_ERR_INVALID, "vae_create_encoder: image_size must be a multiple of 128, at most 512 (the latent's h * w a multiple of 128 "
+                                   "for the mid-block attention GEMMs)");
+  auto* v = new latte_vae();
+  v->encoder = true;
+  v->img = image_size; v->h = image_size / 8; v->max_frames = max_frames; v->dtype = compute_dtype;
+  const int top = v->ch[3];
+  int rc = LATTE_OK;
+#define TRY(x) do { if ((rc = (x))) { latte_vae_destroy(v); return rc; } } while (0)
+  TRY(valloc(v, &v->ci_wt, (size_t)27 * v->ch[0])); TRY(valloc(v, &v->ci_b, v->ch[0]));
+  vslot(v, "encoder.conv_in.weight", (int64_t)v->ch[0] * 27, VP_SMALL_T, v->ci_wt, v->ch[0], 3);
+  vslot(v, "encoder.conv_in.bias", v->ch[0], VP_F32, v->ci_b);
+  int prev = v->ch[0];
+  for (int i = 0; i < 4; ++i) {
+    const int cout = v->ch[i];
+    for (int r = 0; r < 2; ++r)
+      TRY(make_resnet(v, v->down[i][r], "encoder.down_blocks." + std::to_string(i) + ".resnets." + std::to_string(r) + ".", r == 0 ? prev : cout, cout));
+    prev = cout;
+    if (i < 3) {
+      TRY(valloc(v, &v->dnc_w[i], (size_t)cout * cout * 9)); TRY(valloc(v, &v->dnc_w_lo[i], (size_t)cout * cout * 9));
+      TRY(valloc(v, &v->dnc_b[i], cout));
+      const std::string p = "encoder.down_blocks." + std::to_string(i) + ".downsamplers.0.conv.";
+      vslot(v, p + "weight", (int64_t)cout * cout * 9, VP_CONV3, v->dnc_w[i], cout, cout);
+      v->slots.back().dst_lo = v->dnc_w_lo[i];
+      vslot(v, p + "bias", cout, VP_F32, v->dnc_b[i]);
+    }
+  }
+  TRY(make_resnet(v, v->mid[0], "encoder.mid_block.resnets.0.", top, top));
+  TRY(make_mid_attention(v, "encoder.mid_block.attentions.0."));
+  TRY(make_resnet(v, v->mid[1], "encoder.mid_block.resnets.1.", top, top));
+  TRY(valloc(v, &v->no_w, top)); TRY(valloc(v, &v->no_b, top));
+  vslot(v, "encoder.conv_norm_out.weight", top, VP_F32, v->no_w);
+  vslot(v, "encoder.conv_norm_out.bias", top, VP_F32, v->no_b);
+  TRY(valloc(v, &v->eco_raw, (size_t)8 * 9 * top)); TRY(valloc(v, &v->eco_rb, 8));
+  TRY(valloc(v, &v->eq_w, 64)); TRY(valloc(v, &v->eq_b, 8));
+  TRY(valloc(v, &v->eco_w, (size_t)8 * 9 * top)); TRY(valloc(v, &v->eco_b, 8));
+  vslot(v, "encoder.conv_out.weight", (int64_t)8 * 9 * top, VP_SMALL, v->eco_raw, 8, top);
+  vslot(v, "encoder.conv_out.bias", 8, VP_F32, v->eco_rb);
+  vslot(v, "quant_conv.weight", 64, VP_F32, v->eq_w);
+  vslot(v, "quant_conv.bias", 8, VP_F32, v->eq_b);
+
+  // workspace: the largest NHWC map is [N, H, W, 128] at the full image size (conv_in, down block 0)
+  const size_t big = (size_t)max_frames * image_size * image_size * v->ch[0];
+  for (int i = 0; i < 3; ++i) TRY(valloc(v, &v->buf[i], big));
+  for (int i = 0; i < 2; ++i) TRY(valloc(v, &v->sbuf[i], big));
+  TRY(valloc(v, &v->tbuf, big));
+  TRY(valloc(v, &v->ones, 512));
+  {
+    std::vector<float> one(512, 1.0f);
+    LATTE_HIP(hipMemcpy(v->ones, one.data(), sizeof(float) * 512, hipMemcpyHostToDevice));
+  }
+  TRY(valloc(v, &v->zeros, 64));
+  const size_t L = (size_t)v->h * v->h;
+  TRY(valloc(v, &v->moments, (size_t)max_frames * 8 * L));
   TRY(valloc(v, &v->scores, L * L));
   TRY(valloc(v, &v->gn_partial, (size_t)max_frames * groupnorm_max_slabs() * 64));
   TRY(valloc(v, &v->gn_stats, (size_t)max_frames * 64));
@@ -433,7 +561,7 @@ int latte_vae_load_tensor(latte_vae_t* v, const char* key, const float* data, in
     }
   }
   if (rc) return rc;
-  if (s.key == "decoder.mid_block.attentions.0.to_out.0.weight")
+  if (s.key == "decoder.mid_block.attentions.0.to_out.0.weight" || s.key == "encoder.mid_block.attentions.0.to_out.0.weight")
     LATTE_HIP(hipMemcpyAsync(v->ao_w_f32, src, sizeof(float) * numel, hipMemcpyDeviceToDevice, st));
   if (!on_device) LATTE_HIP(hipStreamSynchronize(st));
   s.loaded = true;
@@ -488,6 +616,7 @@ int latte_debug_vae_trace(latte_vae_t* v, const float* z, int n_frames, float z_
 static int vae_decode_impl(latte_vae_t* v, const float* z, int n_frames, float z_scale, int out_mode, void* out, void* stream,
                            int stop_after, float* trace_out, int64_t* trace_numel, int* trace_dims) {
   if (!v || !z || !out) return fail(LATTE_ERR_INVALID, "vae_decode: null argument");
+  if (v->encoder) return fail(LATTE_ERR_INVALID, "vae_decode: this handle is an encoder (latte_vae_create_encoder); decode needs a decoder handle");
   if (n_frames <= 0 || n_frames > v->max_frames) return fail(LATTE_ERR_STATE, "vae_decode: n_frames exceeds max_frames");
   if (out_mode != 0 && out_mode != 1) return fail(LATTE_ERR_INVALID, "vae_decode: out_mode must be 0 (fp32 NCHW) or 1 (uint8 NHWC)");
   int rc = latte_vae_check_weights(v);
@@ -529,32 +658,7 @@ static int vae_decode_impl(latte_vae_t* v, const float* z, int n_frames, float z
   if ((rc = run_resnet(v, v->mid[0], &a, &a2, b, c, d, N, H, W, st, 0))) return rc;
   if (v->temporal && (rc = run_tresnet(v, v->tmid[0], a, c, d, N, H, W, st, 0))) return rc;
   if (traced(rc)) return rc;
-  {  // mid-block attention: 1 head, dim 512, tokens = H*W per frame
-    const int L = H * W;
-    if (L % 128 != 0) return fail(LATTE_ERR_INVALID, "vae_decode: H*W must be a multiple of 128 for the attention GEMMs");
-    if ((rc = launch_groupnorm(a, 1, c, v->agn_w, v->agn_b, v->gn_partial, v->gn_stats, N, L, top, 0, dt, st))) return rc;
-    if ((rc = gemm_h16(c, v->aq_w, v->aq_b, b, nullptr, N * L, top, top, EPI_BIAS_H16, dt, st))) return rc;   // q  [N L, 512]
-    if ((rc = gemm_h16(c, v->ak_w, v->ak_b, d, nullptr, N * L, top, top, EPI_BIAS_H16, dt, st))) return rc;   // k  [N L, 512]
-    half_t* vt = b + (size_t)N * L * top;   // V0^T per frame [512, L], behind q in buffer b
-    half_t* pm = d + (size_t)N * L * top;   // P per frame [L, L], behind k in buffer d
-    half_t* o = c + (size_t)N * L * top;    // attention output [N L, 512], behind the normed input in buffer c
-    const float scale = 1.0f / std::sqrt((float)top);
-    for (int f = 0; f < N; ++f) {
-      const half_t* hf = c + (size_t)f * L * top;
-      if ((rc = gemm_h16(v->av_w, hf, v->zero_bias, vt, nullptr, top, L, top, EPI_BIAS_H16, dt, st))) return rc;          // V0^T = Wv h^T
-      if ((rc = gemm_h16(b + (size_t)f * L * top, d + (size_t)f * L * top, v->zero_bias, v->scores, nullptr, L, L, top,
-                         EPI_BIAS_F32, dt, st))) return rc;                                                               // S = q k^T
-      if ((rc = launch_softmax_rows(v->scores, pm, L, L, scale, dt, st))) return rc;
-      if ((rc = gemm_h16(pm, vt, v->zero_bias, o + (size_t)f * L * top, nullptr, L, top, L, EPI_BIAS_H16, dt, st))) return rc;  // P V0
-    }
-    {  // to_out + residual straight into the fp32 stream: stream += 1 * (o Wo^T + b_eff)
-      GemmArgs g{};
-      g.A = o; g.W = v->ao_w; g.bias = v->ao_b_eff; g.out = a; g.gate = v->ones; g.gate_stride = 0;
-      g.M = N * L; g.N = top; g.K = top; g.rows_per_sample = N * L;
-      if ((rc = launch_gemm(g, EPI_GATE_RES_F32, dt, 1, st))) return rc;
-      kprof_mark(VC_ATTN, st);
-    }
-  }
+  if ((rc = run_mid_attention(v, a, b, c, d, N, H, W, st))) return rc;
   if (traced(rc)) return rc;
   if ((rc = run_resnet(v, v->mid[1], &a, &a2, b, c, d, N, H, W, st, 0))) return rc;
   if (v->temporal && (rc = run_tresnet(v, v->tmid[1], a, c, d, N, H, W, st, 0))) return rc;
@@ -590,6 +694,130 @@ static int vae_decode_impl(latte_vae_t* v, const float* z, int n_frames, float z
   // conv_out to fp32 NCHW frames, then time_conv_out over the frames of the chunk
   if ((rc = launch_conv_out(c, v->co_w, v->co_b, v->tbuf, N, H, W, v->ch[0], 0, dt, st, co_lo))) return rc;
   return launch_time_conv_out(v->tbuf, v->tco_w, v->tco_b, out, N, H * W, out_mode, st);
+}
+
+// ------------------------------------------------------------------------------------------------ SD-VAE encoder
+// AutoencoderKL.encode(x).latent_dist (diffusers 0.24.0; the reference's training step, train.py:204-211):
+//   conv_in (3 -> 128) -> 4 x DownEncoderBlock2D (2 ResnetBlock2D each, Downsample2D = pad (0, 1, 0, 1) + 3x3 stride 2 on blocks 0..2)
+//   -> UNetMidBlock2D (resnet, attention, resnet) -> GroupNorm + SiLU -> conv_out (512 -> 8) -> quant_conv (8 -> 8) = the moments.
+// The same fp32 residual stream / half MFMA operand scheme as the decoder; the down-sampler is the implicit-GEMM conv's stride-2 gather
+// (launch_conv3x3 down = 1) on a half copy of the stream.
+static int vae_encode_impl(latte_vae_t* v, const void* x, int n_frames, int in_mode, const float* noise, float scale, int out_mode, float* out,
+                           void* stream, int stop_after, float* trace_out, int64_t* trace_numel, int* trace_dims) {
+  if (!v || !x || !out) return fail(LATTE_ERR_INVALID, "vae_encode: null argument");
+  if (!v->encoder) return fail(LATTE_ERR_INVALID, "vae_encode: this handle is a decoder; encode needs latte_vae_create_encoder");
+  if (n_frames <= 0 || n_frames > v->max_frames) return fail(LATTE_ERR_STATE, "vae_encode: n_frames exceeds max_frames");
+  if (in_mode != 0 && in_mode != 1) return fail(LATTE_ERR_INVALID, "vae_encode: in_mode must be 0 (fp32 NCHW) or 1 (uint8 NHWC)");
+  if (out_mode < 0 || out_mode > 2) return fail(LATTE_ERR_INVALID, "vae_encode: out_mode must be 0 (moments), 1 (mode) or 2 (sample)");
+  if (out_mode == 2 && !noise) return fail(LATTE_ERR_INVALID, "vae_encode: out_mode 2 (sample) needs noise [N, 4, h, w]");
+  int rc = latte_vae_check_weights(v);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int N = n_frames, dt = v->dtype, top = v->ch[3];
+  if (!v->bias_folded) {   // the attention's value bias (see vae_decode_impl) and quant_conv into conv_out
+    if ((rc = launch_small_linear(IN_PLAIN, v->av_b, nullptr, v->ao_w_f32, v->ao_b, nullptr, nullptr, v->ao_b_eff, 1, top, top, top, st))) return rc;
+    if ((rc = launch_fold_quant_conv(v->eco_raw, v->eco_rb, v->eq_w, v->eq_b, v->eco_w, v->eco_b, 9 * top, st))) return rc;
+    v->bias_folded = true;
+  }
+  v->enc_split = encode_split_mask();   // once per call (vae_split_mask reads it for run_resnet)
+  const int split = v->enc_split;
+  half_t *b = v->buf[0], *c = v->buf[1], *d = v->buf[2];
+  float *a = v->sbuf[0], *a2 = v->sbuf[1];
+  int H = v->img, W = v->img, stage_no = 0, cur_c = v->ch[0];
+  // stage numbering: 0 conv_in | per down block i: resnets 0, 1 (+ down-sampler, i < 3) -> 1..11 | 12 mid.resnet0 | 13 mid.attention |
+  // 14 mid.resnet1 | 15 the moments
+  auto traced = [&](int& rc_out) -> bool {
+    if (stage_no++ != stop_after) return false;
+    const int64_t n = (int64_t)N * H * W * cur_c;
+    rc_out = LATTE_OK;
+    if (hipMemcpyAsync(trace_out, a, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, st) != hipSuccess)
+      rc_out = fail(LATTE_ERR_HIP, "vae_encode_trace: copy failed");
+    *trace_numel = n;
+    trace_dims[0] = N; trace_dims[1] = H; trace_dims[2] = W; trace_dims[3] = cur_c;
+    return true;
+  };
+  if ((rc = launch_enc_conv_in(x, in_mode, v->ci_wt, v->ci_b, a, N, H, W, st))) return rc;
+  if (traced(rc)) return rc;
+  for (int i = 0; i < 4; ++i) {
+    for (int r = 0; r < 2; ++r) {
+      if ((rc = run_resnet(v, v->down[i][r], &a, &a2, b, c, d, N, H, W, st, 1 + i))) return rc;
+      cur_c = v->down[i][r].cout;
+      if (traced(rc)) return rc;
+    }
+    if (i < 3) {   // Downsample2D: pad (0, 1, 0, 1) + stride 2 in the conv's gather, on a half copy of the stream (split: hi d + lo c)
+      const bool dn_lo = (split >> (12 + i)) & 1;
+      if (dn_lo) rc = launch_convert_f32_to_h16_split(a, d, c, (int64_t)N * H * W * cur_c, dt, st);
+      else rc = launch_convert_f32_to_h16(a, d, (int64_t)N * H * W * cur_c, dt, st);
+      if (rc) return rc;
+      kprof_mark(VC_SMALL, st);
+      if ((rc = launch_conv3x3(d, v->dnc_w[i], v->dnc_b[i], nullptr, nullptr, v->zeros, N, H, W, cur_c, cur_c, 0, dt, st, nullptr, a2, 0, 1))) return rc;
+      if (dn_lo && (rc = launch_conv3x3(c, v->dnc_w[i], v->zero_bias, nullptr, nullptr, v->zeros, N, H, W, cur_c, cur_c, 0, dt, st, a2, a2, 0, 1))) return rc;
+      if (((split >> (21 + i)) & 1) &&
+          (rc = launch_conv3x3(d, v->dnc_w_lo[i], v->zero_bias, nullptr, nullptr, v->zeros, N, H, W, cur_c, cur_c, 0, dt, st, a2, a2, 0, 1))) return rc;
+      std::swap(a, a2);
+      H /= 2;
+      W /= 2;
+      if (traced(rc)) return rc;
+    }
+  }
+  if ((rc = run_resnet(v, v->mid[0], &a, &a2, b, c, d, N, H, W, st, 0))) return rc;
+  if (traced(rc)) return rc;
+  if ((rc = run_mid_attention(v, a, b, c, d, N, H, W, st))) return rc;
+  if (traced(rc)) return rc;
+  if ((rc = run_resnet(v, v->mid[1], &a, &a2, b, c, d, N, H, W, st, 0))) return rc;
+  if (traced(rc)) return rc;
+  half_t* co_lo = ((split >> 11) & 1) ? b : nullptr;   // conv_out reads the GroupNorm output as hi + lo (its weights are fp32)
+  if ((rc = launch_groupnorm(a, 1, c, v->no_w, v->no_b, v->gn_partial, v->gn_stats, N, H * W, top, 1, dt, st, 1e-6f, groupnorm_max_slabs(), co_lo))) return rc;
+  float* mom = (out_mode == 0 && stop_after < 0) ? out : v->moments;
+  if ((rc = launch_enc_conv_out(c, co_lo, v->eco_w, v->eco_b, mom, N, H, W, top, dt, st))) return rc;
+  if (stop_after >= 0) {
+    if (stage_no != stop_after) return fail(LATTE_ERR_INVALID, "vae_encode_trace: stage index beyond the last traced stage (15, the moments)");
+    const int64_t n = (int64_t)N * 8 * H * W;
+    if (hipMemcpyAsync(trace_out, mom, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return fail(LATTE_ERR_HIP, "vae_encode_trace: copy failed");
+    *trace_numel = n;
+    trace_dims[0] = N; trace_dims[1] = 8; trace_dims[2] = H; trace_dims[3] = W;
+    return LATTE_OK;
+  }
+  if (out_mode == 0) return LATTE_OK;
+  return launch_posterior(mom, noise, N, H * W, scale, out_mode, out, st);
+}
+
+int latte_vae_encode(latte_vae_t* v, const void* x, int n_frames, int in_mode, const float* noise, float scale, int out_mode, float* out,
+                     void* stream) {
+  return vae_encode_impl(v, x, n_frames, in_mode, noise, scale, out_mode, out, stream, -1, nullptr, nullptr, nullptr);
+}
+
+int latte_vae_posterior(const float* moments, const float* noise, int n, int hw, float scale, int what, float* out, void* stream) {
+  if (!moments || !out) return fail(LATTE_ERR_INVALID, "vae_posterior: null argument");
+  return launch_posterior(moments, noise, n, hw, scale, what, out, (hipStream_t)stream);
+}
+
+int latte_vae_profile_encode(latte_vae_t* v, const void* x, int n_frames, int in_mode, const float* noise, float scale, int out_mode, float* out,
+                             float* ms_out, int* launches_out, int n, void* stream) {
+  if (!ms_out || !launches_out || n < VC_NUM_CLASSES) return fail(LATTE_ERR_INVALID, "vae_profile_encode: bad arguments");
+  KProf prof;
+  g_kprof = &prof;
+  kprof_mark(VC_START, (hipStream_t)stream);
+  int rc = vae_encode_impl(v, x, n_frames, in_mode, noise, scale, out_mode, out, stream, -1, nullptr, nullptr, nullptr);
+  g_kprof = nullptr;
+  if (!rc && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = fail(LATTE_ERR_HIP, "vae_profile_encode: device error");
+  for (int i = 0; i < n; ++i) { ms_out[i] = 0.f; launches_out[i] = 0; }
+  for (size_t i = 1; !rc && i < prof.ev.size(); ++i) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, prof.ev[i - 1], prof.ev[i]) != hipSuccess) { rc = fail(LATTE_ERR_HIP, "vae_profile_encode: event"); break; }
+    const int c = prof.cls[i];
+    if (c >= 0 && c < n) { ms_out[c] += ms; launches_out[c] += 1; }
+  }
+  for (auto ev : prof.ev) (void)hipEventDestroy(ev);
+  return rc;
+}
+
+/* test hook (include/latte_amd_debug.h): run the encoder up to and including stage `stop_after` */
+int latte_debug_vae_encode_trace(latte_vae_t* v, const void* x, int n_frames, int in_mode, int stop_after, float* trace_out,
+                                 int64_t* trace_numel, int* trace_dims, void* stream) {
+  if (!trace_out || !trace_numel || !trace_dims || stop_after < 0) return fail(LATTE_ERR_INVALID, "vae_encode_trace: bad arguments");
+  return vae_encode_impl(v, x, n_frames, in_mode, nullptr, 1.0f, 0, trace_out, stream, stop_after, trace_out, trace_numel, trace_dims);
 }
 
 }  // extern "C"

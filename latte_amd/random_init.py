@@ -1,7 +1,7 @@
 """Random weights of the right shapes for plumbing runs and benchmarks (there are no checkpoints offline).
 
 Not test infrastructure and not an oracle: these only FILL state dicts with reference-format keys (diffusers
-``AutoencoderKL`` decoder keys of the sd-vae-ft architecture, ``LatteT2V`` keys of models/latte_t2v.py) so that
+``AutoencoderKL`` decoder and encoder keys of the sd-vae-ft architecture, ``LatteT2V`` keys of models/latte_t2v.py) so that
 ``bench.py`` and ``tools/*`` can time the device path.  ``Latte`` itself initialises like the reference
 (latte.py:257-295); ``randomize_zero_init`` re-draws what that leaves at zero so outputs are not trivially 0.
 """
@@ -65,6 +65,43 @@ def vae_decoder_keys(block_out=(128, 256, 512, 512), layers=2, latent=4):
     ks["decoder.conv_norm_out.weight"], ks["decoder.conv_norm_out.bias"] = (block_out[0],), (block_out[0],)
     ks["decoder.conv_out.weight"], ks["decoder.conv_out.bias"] = (3, block_out[0], 3, 3), (3,)
     return ks
+
+
+def vae_encoder_keys(block_out=(128, 256, 512, 512), layers=2, latent=4):
+    """diffusers AutoencoderKL encoder half (encoder.* + quant_conv), sd-vae-ft layout (double_z: conv_out has 2 * latent channels)."""
+    ks = {"encoder.conv_in.weight": (block_out[0], 3, 3, 3), "encoder.conv_in.bias": (block_out[0],)}
+
+    def resnet(p, cin, cout):
+        ks[p + "norm1.weight"], ks[p + "norm1.bias"] = (cin,), (cin,)
+        ks[p + "conv1.weight"], ks[p + "conv1.bias"] = (cout, cin, 3, 3), (cout,)
+        ks[p + "norm2.weight"], ks[p + "norm2.bias"] = (cout,), (cout,)
+        ks[p + "conv2.weight"], ks[p + "conv2.bias"] = (cout, cout, 3, 3), (cout,)
+        if cin != cout:
+            ks[p + "conv_shortcut.weight"], ks[p + "conv_shortcut.bias"] = (cout, cin, 1, 1), (cout,)
+
+    prev = block_out[0]
+    for i, cout in enumerate(block_out):
+        for r in range(layers):
+            resnet(f"encoder.down_blocks.{i}.resnets.{r}.", prev if r == 0 else cout, cout)
+        prev = cout
+        if i != len(block_out) - 1:
+            ks[f"encoder.down_blocks.{i}.downsamplers.0.conv.weight"] = (cout, cout, 3, 3)
+            ks[f"encoder.down_blocks.{i}.downsamplers.0.conv.bias"] = (cout,)
+    top = block_out[-1]
+    resnet("encoder.mid_block.resnets.0.", top, top)
+    a = "encoder.mid_block.attentions.0."
+    ks[a + "group_norm.weight"], ks[a + "group_norm.bias"] = (top,), (top,)
+    for n in ("to_q", "to_k", "to_v", "to_out.0"):
+        ks[a + n + ".weight"], ks[a + n + ".bias"] = (top, top), (top,)
+    resnet("encoder.mid_block.resnets.1.", top, top)
+    ks["encoder.conv_norm_out.weight"], ks["encoder.conv_norm_out.bias"] = (top,), (top,)
+    ks["encoder.conv_out.weight"], ks["encoder.conv_out.bias"] = (2 * latent, top, 3, 3), (2 * latent,)
+    ks["quant_conv.weight"], ks["quant_conv.bias"] = (2 * latent, 2 * latent, 1, 1), (2 * latent,)
+    return ks
+
+
+def vae_encoder_state_dict(seed=0):
+    return _fill(vae_encoder_keys(), seed)
 
 
 def vae_decoder_state_dict(seed=0):

@@ -7,8 +7,13 @@ One process per GPU (train.py:55-66), the model replicated, `local_batch_size` l
 `LatteTrainer.train_step` = q_sample + forward + training_losses + backward (gradient slices all-reduced over RCCL bucket by bucket
 under the backward) + clip_grad_norm_ + AdamW + update_ema (train.py:197-236).  Checkpoints are the reference's
 `{"model": state_dict, "ema": state_dict}` (train.py:257-262) and load back through `find_model` / `--pretrained`.
-The reference's VAE ENCODER step (train.py:205-211) is outside the engine: `data_path` holds latent clips (.npy [F, 4, h, w], already
-scaled by 0.18215) or is "synthetic" (N(0, 1) latents: throughput and plumbing, not a model worth keeping).
+`data_path` holds one of
+  - uint8 frame clips (.npy [F, H, W, 3], H == W == image_size): every batch is encoded on the GPU as the reference does
+    (train.py:204-211, `vae.encode(x).latent_dist.sample().mul_(0.18215)`) through `AutoencoderKL.encode_video_uint8`, the VAE
+    loaded from `<pretrained_model_path>/vae` with the encoder (train.py:94), fresh posterior noise every step from a seeded generator;
+  - latent clips (.npy [F, 4, h, w], already scaled by 0.18215; tools/encode_clips.py writes them from frame clips once, instead of
+    encoding every epoch);
+  - "synthetic" (N(0, 1) latents: throughput and plumbing, not a model worth keeping).
 """
 import argparse
 import glob
@@ -36,6 +41,13 @@ class LatentClips:
         self.files = [] if self.synthetic else sorted(glob.glob(os.path.join(path, "*.npy")))
         if not self.synthetic and not self.files:
             raise SystemExit(f"no .npy latent clips under {path}")
+        # uint8 frame clips [F, H, W, 3] at the training image size are encoded on the GPU per batch (frames=True)
+        self.frames = False
+        if self.files:
+            first = np.load(self.files[0], mmap_mode="r")
+            if first.dtype == np.uint8:
+                self.shape = (frames, 8 * latent, 8 * latent, 3)
+                self.frames = True
 
     def batch(self, step, n):
         g = torch.Generator("cpu").manual_seed(self.seed * 1000003 + step * self.world + self.rank)
@@ -48,7 +60,7 @@ class LatentClips:
         for i in idx:
             a = np.load(self.files[i])
             assert a.shape == self.shape, f"{self.files[i]}: expected {self.shape}, got {a.shape}"
-            xs.append(torch.from_numpy(a).float())
+            xs.append(torch.from_numpy(a) if self.frames else torch.from_numpy(a).float())
             name = os.path.basename(self.files[i])
             ys.append(int(name.split("_")[0]) if name.split("_")[0].isdigit() else 0)
         return torch.stack(xs), torch.tensor(ys)
@@ -101,6 +113,11 @@ def main():
             first_step = int(stem)
             trainer.train_steps = first_step
     data = LatentClips(args.get("data_path"), int(args.num_frames), args.latent_size, rank, world, seed, int(args.get("num_classes") or 0))
+    vae = None
+    if data.frames:                                           # train.py:94 (+ the encoder): frames -> latents on the GPU every step
+        if not args.get("pretrained_model_path"):
+            raise SystemExit("data_path holds uint8 frame clips: set pretrained_model_path (its vae/ subfolder is the SD-VAE to encode with)")
+        vae = latte_amd.AutoencoderKL.from_pretrained(args.pretrained_model_path, subfolder="vae", with_encoder=True).to(device)
     out_dir = a.out or args.results_dir
     max_steps = a.max_steps or int(args.max_train_steps)
     log_every = a.log_every or int(args.log_every)
@@ -114,6 +131,9 @@ def main():
     seen_skips = 0.0
     for step in range(first_step + 1, max_steps + 1):
         x, y = data.batch(step, nb)
+        if vae is not None:                                   # train.py:204-211, posterior noise from this step's seeded generator
+            gen = torch.Generator(device).manual_seed(seed * 1000003 + step * world + rank)
+            x = vae.encode_video_uint8(x.to(device), generator=gen)
         out = trainer.train_step(x.to(device), y=y.to(device) if int(args.extras) == 2 else None)
         running += float(out["loss"].mean())                  # (the reference's loss.item(), train.py:239)
         log_steps += 1
