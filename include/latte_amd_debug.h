@@ -104,6 +104,34 @@ int latte_debug_gemm_tn_colsum(const void* dY, const void* X, float* dW, float* 
 int latte_debug_ln_modulate(float* x, void* y, const float* shift, const float* scale, int mod_stride, int M, int D,
                             int rows_per_sample, const float* temp_embed, int T, int F, int dtype, void* stream);
 int latte_debug_convert(const float* in, void* out, int64_t n, int dtype, void* stream);
+/* Row kernels of the training step (csrc/train.hip), one launch each as the trainer makes it.  Rows are [M, D] with M a multiple of
+ * rows_per_sample; per-sample vectors (gate, shift, scale) are rows of [M / rows_per_sample][stride] fp32.
+ * latte_debug_gated_add_ln: x_out = x_in + gate * y (+ temp_embed[(m / T) % F] when temp_embed != NULL) and xn (half) =
+ * LN(x_out) (1 + scale) + shift, eps 1e-6 (latte.py:179-180 and the next block's modulated LayerNorm). */
+int latte_debug_gated_add_ln(const float* x_in, const void* y, const float* gate, int gate_stride, float* x_out, void* xn,
+                             const float* shift, const float* scale, int mod_stride, int M, int D, int rows_per_sample,
+                             const float* temp_embed, int T, int F, int dtype, void* stream);
+/* LayerNorm + modulate backward: for y = LN(x) (1 + scale) + shift and dy (half), dx_out = dx_in + dx (dx_in may be NULL or equal
+ * to dx_out, the trainer's in-place form).  dshift / dscale != NULL: per-sample sums [M / rows_per_sample][out_stride] through the
+ * finalize kernel.  y2 != NULL (then gate2, dy2 and gpartial too): the gated residual's backward of the branch below on the same
+ * pass, dy2 (half) = gate2 * dx_out and gpartial [M / 32][2][D] = {sum dx_out * y2, sum gate2 * dx_out} over each 32 consecutive rows.
+ * workspace: >= (M / 32) * 2 * D floats (the kernel's partial rows).  rows_per_sample must be a multiple of 32, D % 4 == 0, D <= 1280. */
+int latte_debug_ln_bwd(const void* dy, const float* x, const float* scale, int mod_stride, const float* dx_in, float* dx_out,
+                       float* dshift, float* dscale, int out_stride, int M, int D, int rows_per_sample, const void* y2,
+                       const float* gate2, int gate2_stride, void* dy2, float* gpartial, float* workspace, int64_t workspace_floats,
+                       int dtype, void* stream);
+/* Gated residual backward: dy (half) = gate * dx; partial [M / 32][1 + bias_partial][D] = {sum dx * y [, sum gate * dx]} over each
+ * 32 consecutive rows; dgate != NULL: per-sample sums of the first, [M / rows_per_sample][out_stride], through the finalize kernel.
+ * Same shape rules as latte_debug_ln_bwd. */
+int latte_debug_gate_bwd(const float* dx, const void* y, const float* gate, int gate_stride, void* dy, float* partial,
+                         int64_t partial_floats, float* dgate, int out_stride, int M, int D, int rows_per_sample, int bias_partial,
+                         int dtype, void* stream);
+/* d mean_b(terms["loss"]) / d model_output of GaussianDiffusion.training_losses (gaussian_diffusion.py:719-795) for the schedule's
+ * model types: loss_type 0 MSE, 1 RESCALED_MSE; x_start / x_t / noise [batch, frames, channels, hw], model_out and dmodel_out
+ * [batch, frames, channels (x 2 when the schedule learns sigma), hw] fp32; t: int64 [batch] timestep indices. */
+int latte_debug_loss_grad(const struct latte_schedule* s, int loss_type, const float* x_start, const float* x_t, const float* noise,
+                          const float* model_out, const int64_t* t, int batch, int frames, int channels, int hw, float* dmodel_out,
+                          void* stream);
 int latte_debug_fill_normal(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream);
 /* Writes, for every lane l (0..63) and element j (0..3), the LDS element INDEX that
  * ds_read_b64_tr_b16 returned when lane l supplies byte address 8*l (LDS pre-filled with

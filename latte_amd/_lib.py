@@ -144,6 +144,14 @@ PROTOTYPES = {
     "latte_debug_ln_modulate": (c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void, c_int,
                                         c_int, c_int, c_void]),
     "latte_debug_convert": (c_int, [c_void, c_void, c_i64, c_int, c_void]),
+    "latte_debug_gated_add_ln": (c_int, [c_void, c_void, c_void, c_int, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int,
+                                         c_void, c_int, c_int, c_int, c_void]),
+    "latte_debug_ln_bwd": (c_int, [c_void, c_void, c_void, c_int, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void,
+                                   c_void, c_int, c_void, c_void, c_void, c_i64, c_int, c_void]),
+    "latte_debug_gate_bwd": (c_int, [c_void, c_void, c_void, c_int, c_void, c_void, c_i64, c_void, c_int, c_int, c_int, c_int, c_int,
+                                     c_int, c_void]),
+    "latte_debug_loss_grad": (c_int, [c_void, c_int, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void,
+                                      c_void]),
     "latte_debug_fill_normal": (c_int, [c_void, c_i64, c_u64, c_u64, c_void]),
     "latte_debug_tr16_probe": (c_int, [c_void, c_void]),
     "latte_debug_set_choice": (c_int, [c_char, c_int]),

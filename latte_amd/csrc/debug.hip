@@ -295,6 +295,56 @@ int latte_debug_ln_modulate(float* x, void* y, const float* shift, const float* 
                             (hipStream_t)stream);
 }
 
+int latte_debug_gated_add_ln(const float* x_in, const void* y, const float* gate, int gate_stride, float* x_out, void* xn,
+                             const float* shift, const float* scale, int mod_stride, int M, int D, int rows_per_sample,
+                             const float* temp_embed, int T, int F, int dtype, void* stream) {
+  if (M <= 0 || rows_per_sample <= 0 || M % rows_per_sample || (temp_embed && (T <= 0 || F <= 0)))
+    return fail(LATTE_ERR_INVALID, "gated_add_ln: need whole samples (M % rows_per_sample == 0) and T, F > 0 with temp_embed");
+  return launch_gated_add_ln(x_in, (const half_t*)y, gate, gate_stride, x_out, (half_t*)xn, shift, scale, mod_stride, M, D,
+                             rows_per_sample, temp_embed, T, F, dtype, (hipStream_t)stream);
+}
+
+// the kernels' partial rows: one per 4 runs of train_rows_per_run(rps) rows (rps % 32 == 0: 32 rows), nsum rows of D floats each
+static int64_t train_partial_floats(int M, int D, int rps, int nsum) {
+  return (int64_t)(M / (4 * train_rows_per_run(rps))) * nsum * D;
+}
+
+int latte_debug_ln_bwd(const void* dy, const float* x, const float* scale, int mod_stride, const float* dx_in, float* dx_out,
+                       float* dshift, float* dscale, int out_stride, int M, int D, int rows_per_sample, const void* y2,
+                       const float* gate2, int gate2_stride, void* dy2, float* gpartial, float* workspace, int64_t workspace_floats,
+                       int dtype, void* stream) {
+  if (M <= 0 || rows_per_sample <= 0 || M % rows_per_sample || D <= 0)
+    return fail(LATTE_ERR_INVALID, "ln_bwd: need whole samples (M % rows_per_sample == 0)");
+  if (!dshift != !dscale) return fail(LATTE_ERR_INVALID, "ln_bwd: dshift and dscale are finalized together");
+  if (train_partial_floats(M, D, rows_per_sample, 2) > workspace_floats) return fail(LATTE_ERR_INVALID, "ln_bwd: workspace too small");
+  return launch_ln_bwd((const half_t*)dy, x, scale, mod_stride, dx_in, dx_out, workspace, dshift, dscale, out_stride, M, D,
+                       rows_per_sample, dtype, (hipStream_t)stream, (const half_t*)y2, gate2, gate2_stride, (half_t*)dy2, gpartial);
+}
+
+int latte_debug_gate_bwd(const float* dx, const void* y, const float* gate, int gate_stride, void* dy, float* partial,
+                         int64_t partial_floats, float* dgate, int out_stride, int M, int D, int rows_per_sample, int bias_partial,
+                         int dtype, void* stream) {
+  if (M <= 0 || rows_per_sample <= 0 || M % rows_per_sample || D <= 0 || (bias_partial != 0 && bias_partial != 1))
+    return fail(LATTE_ERR_INVALID, "gate_bwd: need whole samples (M % rows_per_sample == 0), bias_partial 0 or 1");
+  if (train_partial_floats(M, D, rows_per_sample, 1 + bias_partial) > partial_floats)
+    return fail(LATTE_ERR_INVALID, "gate_bwd: partial buffer too small");
+  return launch_gate_bwd(dx, (const half_t*)y, gate, gate_stride, (half_t*)dy, partial, dgate, out_stride, M, D, rows_per_sample, dtype,
+                         (hipStream_t)stream, bias_partial);
+}
+
+int latte_debug_loss_grad(const latte_schedule* s, int loss_type, const float* x_start, const float* x_t, const float* noise,
+                          const float* model_out, const int64_t* t, int batch, int frames, int channels, int hw, float* dmodel_out,
+                          void* stream) {
+  if (!s || !x_start || !x_t || !noise || !model_out || !t || !dmodel_out || batch <= 0 || frames <= 0 || channels <= 0 || hw <= 0)
+    return fail(LATTE_ERR_INVALID, "loss_grad: bad arguments");
+  if (loss_type != 0 && loss_type != 1) return fail(LATTE_ERR_INVALID, "loss_grad: loss_type must be 0 MSE or 1 RESCALED_MSE");
+  const float* tab = nullptr;
+  if (int rc = schedule_device_tables(s, &tab, (hipStream_t)stream)) return rc;
+  const float vb_scale = loss_type == 1 ? (float)(s->num_timesteps / 1000.0) : 1.0f;   // as latte_trainer_forward_backward
+  return launch_loss_grad(tab, s->num_timesteps, s->mean_type, s->var_type, x_start, x_t, noise, model_out, t, batch, frames, channels,
+                          hw, vb_scale, dmodel_out, (hipStream_t)stream);
+}
+
 int latte_debug_convert(const float* in, void* out, int64_t n, int dtype, void* stream) {
   return launch_convert_f32_to_h16(in, (half_t*)out, n, dtype, (hipStream_t)stream);
 }
