@@ -1,6 +1,6 @@
 """bench.py — denoising steps/sec of the Latte-XL/2 16x256x256 sampling loop on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: one process per GPU over RCCL.  Under torch.distributed.run (WORLD_SIZE / RANK / LOCAL_RANK in the environment, the
 driver's launch line) the process is one rank and asserts WORLD_SIZE == --gpus; started plainly (`python bench.py --gpus N`)
@@ -18,13 +18,20 @@ collective (the reference's sample_ddp.py has none either); the only payload col
 RCCL broadcast of the timestep-embedding table before the timed region.
 `value` = aggregate denoising sample-steps/s = n_gpus * batch * K / max-over-ranks time.
 
-Beside the headline, in the same JSON line:
+A plain run does only what the headline needs: set up, W warm-up steps, the K timed steps, --dump-outputs, and one JSON line
+with the headline fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `n_gpus`, `config`, `finite`,
+...), all computed from the timed region.  `dtype` = f16 (round 4): the MFMA operand type that holds the 1e-3 parity bar on
+weights with trained-checkpoint gate magnitudes (profiles/r4_gate_parity.json; latte_amd.Latte docstring) and the reference's
+own half mode (sample.py:72-75).  Everything else takes runs of its own and is measured only with `--full` (about a minute more
+at N = 1); `--no-side`, `--no-vae` and `--no-cpu-baseline` leave parts of it out.
+
+With `--full`, beside the headline, in the same JSON line:
+  * `other_sampler` (N = 1): the other sampler of DDIM / DDPM on the same loop, up to 60 steps;
   * `roofline`: the DOMINANT kernel of the step (largest share of the forward by HIP events on the launch
     stream) and `roofline_table`: every kernel class with its bound, algorithmic work per launch, average
     launch time and fraction of the MI355X peak (MFMA 2.5 PFLOP/s dense bf16/f16, HBM 8 TB/s);
-  * `dtype` = f16 (round 4): the MFMA operand type that holds the 1e-3 parity bar on weights with trained-checkpoint gate
-    magnitudes (profiles/r4_gate_parity.json; latte_amd.Latte docstring) and the reference's own half mode (sample.py:72-75);
-    `bf16`: the same timed loop with bf16 operands (BASELINE config 2's word; 1e-3 only at near-zero gates), reported beside it;
+  * `bf16`: the same timed loop with bf16 operands (BASELINE config 2's word; 1e-3 only at near-zero gates), and `batch2` /
+    `batch1`: the headline loop at per-GPU batch 2 and 1;
   * `config3`: BASELINE config 3's per-GPU share -- UCF101 class-conditional Latte-XL/2, CFG 7.0, 8 samples =
     16 sequences per GPU through forward_with_cfg (aggregate guided sample-steps/s over all ranks);
   * `config5`: BASELINE config 5's per-GPU share -- one optimisation step of train.py on Latte-B/2 16x256x256 synthetic
@@ -70,13 +77,17 @@ def parse():
     p.add_argument("--gemm-variant", type=int, default=0)
     p.add_argument("--engine-option", action="append", default=[], metavar="NAME=VALUE",
                    help="latte_engine_set_option on the headline engine before the timed region (A/B measurements, e.g. fuse_qkv_attn=0)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-vae", action="store_true", help="skip the (untimed-region) VAE decode rate report")
-    p.add_argument("--no-side", action="store_true", help="skip the f16 / config-3 side measurements")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, run every other measurement of the JSON line: the other sampler, the other operand type, "
+                        "batches 2 / 1, configs 3 / 4 / 5, the roofline tables, power check and energy, VAE decode, CPU baseline")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-vae", action="store_true", help="with --full: skip the (untimed-region) VAE decode rate report")
+    p.add_argument("--no-side", action="store_true",
+                   help="with --full: skip the other-operand-type / batch / config 3 / config 5 side measurements, the power check and config 4")
     p.add_argument("--launch-check", action="store_true",
                    help="launch N ranks, rendezvous, one all-reduce, print {launch_check, n_gpus, collective_ranks} and exit: "
                         "exercises the --gpus contract without measuring anything (runs without a GPU on the gloo backend)")
-    p.add_argument("--cpu-steps", type=int, default=3, help="timed DDIM steps of the CPU baseline (about 5 s each)")
+    p.add_argument("--cpu-steps", type=int, default=3, help="with --full: timed DDIM steps of the CPU baseline (about 5 s each)")
     p.add_argument("--dump-outputs", metavar="DIR",
                    help="after the timed steps, write the latents they returned as DIR/samples.npy (fp32; DIR/samples_rank<r>.npy "
                         "per rank when N > 1) so that two builds can be compared output for output on the same seeded inputs")
@@ -741,6 +752,36 @@ def main():
     if args.dump_outputs:   # the sampling loop's result: the latents after the last timed step, updated in place in xx
         dump_outputs(args.dump_outputs, "samples" if world == 1 else f"samples_rank{rank}", xx, world)
 
+    res = None
+    if rank == 0:
+        value = world * B * args.steps / elapsed
+        res = {
+            "metric": "denoising steps/sec", "value": round(value, 3), "unit": "sample-steps/s",
+            "n_gpus": world, "collective_ranks": dist.get_world_size() if dist is not None else 1,
+            "collective_backend": (("rccl" if backend == "nccl" else backend) if dist is not None else None), "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": "Latte-XL/2 FaceForensics (uncond) 16x256x256 -> latents 16x4x32x32, "
+                                   f"{args.method.upper()} on the '250' respacing, random-init weights",
+                       "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"dp{world} (independent samples)"},
+            "latent_frames_per_sec": round(world * B * 16 / (elapsed / args.steps * 250), 3),
+            "model_mfma_frac": round(value / world * FLOPS_PER_SAMPLE_STEP["Latte-XL/2"] / (MFMA_PEAK_TFLOPS * 1e12), 4),
+            "finite": finite,
+        }
+    if args.full:
+        full_measurements(args, res, lib, model, diffusion, x, device, world, rank, dist)
+    if rank == 0:
+        print(json.dumps(res))
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_measurements(args, res, lib, model, diffusion, x, device, world, rank, dist):
+    """--full: every measurement of the JSON line beside the headline, after the timed region and --dump-outputs.  Side timings run on
+    every rank (max over ranks at N > 1); rank 0 adds them, the roofline tables and the N = 1 reports to its headline line `res`."""
+    import latte_amd
+    B = args.batch
     other = None
     if world == 1:
         # BASELINE.json configs[1] words the same FaceForensics job as DDPM-250 (the YAML default `sample_method: 'ddpm'`),
@@ -835,95 +876,80 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             for k, v in zip(keys, tt.tolist()):
                 side[k]["ms_per_step"] = v
-    if rank == 0:
-        value = world * B * args.steps / elapsed
-        flops = FLOPS_PER_SAMPLE_STEP["Latte-XL/2"]
-        # rooflines, timed live with HIP events on the launch stream
-        t = torch.full((B,), 500, device=device, dtype=torch.int64)
-        model.profile_forward(x, t)
-        prof = model.profile_forward(x, t)
-        table, total_ms = roofline_table(prof, B, args.dtype)
-        dom = table[0]                                   # the dominant kernel = largest share of the forward
-        res = {
-            "metric": "denoising steps/sec", "value": round(value, 3), "unit": "sample-steps/s",
-            "n_gpus": world, "collective_ranks": dist.get_world_size() if dist is not None else 1,
-            "collective_backend": (("rccl" if backend == "nccl" else backend) if dist is not None else None), "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": "Latte-XL/2 FaceForensics (uncond) 16x256x256 -> latents 16x4x32x32, "
-                                   f"{args.method.upper()} on the '250' respacing, random-init weights",
-                       "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"dp{world} (independent samples)"},
-            "other_sampler": other,
-            "latent_frames_per_sec": round(world * B * 16 / (elapsed / args.steps * 250), 3),
-            "model_mfma_frac": round(value / world * flops / (MFMA_PEAK_TFLOPS * 1e12), 4),
-            "finite": finite,
-            "roofline": {"bound": dom["bound"], "kernel": dom["kernel"], "achieved": dom["achieved"], "peak": dom["peak"],
-                         "unit": dom["unit"], "frac": dom["frac"], "traffic": dom["traffic"], "traffic_source": dom["traffic_source"],
-                         "avg_launch_ms": dom["avg_launch_ms"], "share_of_forward": dom["share_of_forward"]},
-            "roofline_table": table,
-            "kernel_ms_per_forward": {k: round(v[0], 4) for k, v in prof.items()},
-            "forward_ms_eager_events": round(total_ms, 4),
-        }
-        for k, v in side.items():
-            if k == "config3":
-                sps = world * 8 / (v["ms_per_step"] * 1e-3)
-                res["config3"] = {"workload": "Latte-XL/2 UCF101 class-conditional (101 classes + null), CFG 7.0 through "
-                                              "forward_with_cfg, 8 samples = 16 sequences per GPU, f16 operands, attention output and fc1 "
-                                              "operand carried as f16 + a low-precision remainder (fp8 / fp4 with a per-row scale) whose product runs on the "
-                                              "block-scaled MFMA inside the same GEMM launch (guided_split 20, the default of guided calls)",
-                                  "value": round(sps, 3), "unit": "guided sample-steps/s", "ms_per_step": round(v["ms_per_step"], 3),
-                                  "other_guided_split_settings": {
-                                      f"guided_split_{gs}": {"value": round(world * 8 / (v[f"ms_per_step_guided_split_{gs}"] * 1e-3), 3),
-                                                             "ms_per_step": round(v[f"ms_per_step_guided_split_{gs}"], 3),
-                                                             "note": {0: "plain f16 operands (rounds 1-4): the guided XL/2 output at trained-scale gates is AT "
-                                                                         "1e-3 of the fp32 reference, 0.61-1.07e-3 over 12 draws",
-                                                                      4: "fp8 remainder of the attention output only: 0.51-0.87e-3 over the 12 draws",
-                                                                      12: "both remainders as fp8 (the first form of round 6): 0.43-0.72e-3",
-                                                                      3: "round 5's default: both operands as f16 pairs [hi | lo] . [W | W]: 0.43-0.72e-3, "
-                                                                         "the parity of the low-precision forms at two to three times their cost"}[gs]}
-                                      for gs in (0, 4, 12, 3) if f"ms_per_step_guided_split_{gs}" in v},
-                                  "parity_of_the_default": "0.44-0.73e-3 (eps channels 0.44-0.79e-3) over gate_std {0.3, 1.0} x t {999, 500, 50} x 2 seeds "
-                                                           "against the fp32 oracle (profiles/r6_gate_parity_guided.json)",
-                                  "steps": v["steps"], "global_batch": 8 * world,
-                                  "model_mfma_frac": round(2 * sps / world * flops / (MFMA_PEAK_TFLOPS * 1e12), 4),
-                                  "roofline_table": v.get("roofline_table"), "forward_ms_eager_events": v.get("forward_ms_eager_events")}
-            elif k == "config5":
-                tb, D5, dep5, M5 = 5, 768, 12, 5 * 16 * 256
-                fwd5 = dep5 * 2.0 * M5 * 12 * D5 * D5 + (dep5 // 2) * (4.0 * tb * 16 * 256 * 256 * D5 + 4.0 * tb * 256 * 16 * 16 * D5)
-                res["config5"] = {"workload": "train.py step, Latte-B/2 16x256x256 synthetic latents, local batch 5, f16 operands (loss-scaled backward: the "
-                                              "mantissa of the reference's TF32 matmuls) / fp32 masters: forward + MSE/VB loss + backward + grad all-reduce + clip + AdamW + EMA",
-                                  "value": round(world * tb / (v["ms_per_step"] * 1e-3), 3), "unit": "training samples/s",
-                                  "ms_per_step": round(v["ms_per_step"], 3), "steps": v["steps"], "global_batch": tb * world,
-                                  "algorithmic_tflops_per_gpu": round(3 * fwd5 / (v["ms_per_step"] * 1e-3) / 1e12, 1),
-                                  "loss_finite": v.get("loss_finite"),
-                                  "fuse_small_0": {"ms_per_step": round(v.get("ms_per_step_separate_launches", 0.0), 3),
-                                                   "note": "trainer option fuse_small = 0 (the separate finalize / column-sum / adaLN / gate-backward "
-                                                           "launches of rounds 2 - 6) on the same box; the default folds them (latte_amd/csrc/train_fin.hip)"}}
-            else:
-                res[k] = {"value": round(world * v.get("batch", B) / (v["ms_per_step"] * 1e-3), 3), "unit": "sample-steps/s",
-                          "ms_per_step": round(v["ms_per_step"], 4), "steps": v["steps"]}
-                if "batch" in v:
-                    res[k]["per_gpu_batch"] = v["batch"]
-        if world == 1 and not args.no_side:
-            note('power check (socket power / shader clock in the forward; dominant GEMM on quiet operands)')
-            try:
-                res["power_check"] = power_check(device, model, x, args.dtype)
-            except Exception as ex:  # noqa: BLE001  (rocm-smi absent or unreadable: the line must still print)
-                res["power_check"] = {"error": repr(ex)[:200]}
-            res["energy"] = energy_columns(res, world)
-        if world == 1 and not args.no_vae:
-            res["vae_decode"] = vae_decode_rate(device)
-        if world == 1 and not args.no_side:
-            note('config 4 (Latte-1 T2V guided step + temporal decoder)')
-            res["config4"] = config4_rate(device)
-        if world == 1 and not args.no_cpu_baseline:
-            note('cpu baseline (oracle on host cores)')
-            res["cpu_baseline"] = cpu_baseline(args.cpu_steps)
-            note('cpu baseline done')
-        print(json.dumps(res))
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    if rank != 0:
+        return
+    flops = FLOPS_PER_SAMPLE_STEP["Latte-XL/2"]
+    # rooflines, timed live with HIP events on the launch stream
+    t = torch.full((B,), 500, device=device, dtype=torch.int64)
+    model.profile_forward(x, t)
+    prof = model.profile_forward(x, t)
+    table, total_ms = roofline_table(prof, B, args.dtype)
+    dom = table[0]                                   # the dominant kernel = largest share of the forward
+    res.update({
+        "other_sampler": other,
+        "roofline": {"bound": dom["bound"], "kernel": dom["kernel"], "achieved": dom["achieved"], "peak": dom["peak"],
+                     "unit": dom["unit"], "frac": dom["frac"], "traffic": dom["traffic"], "traffic_source": dom["traffic_source"],
+                     "avg_launch_ms": dom["avg_launch_ms"], "share_of_forward": dom["share_of_forward"]},
+        "roofline_table": table,
+        "kernel_ms_per_forward": {k: round(v[0], 4) for k, v in prof.items()},
+        "forward_ms_eager_events": round(total_ms, 4),
+    })
+    for k, v in side.items():
+        if k == "config3":
+            sps = world * 8 / (v["ms_per_step"] * 1e-3)
+            res["config3"] = {"workload": "Latte-XL/2 UCF101 class-conditional (101 classes + null), CFG 7.0 through "
+                                          "forward_with_cfg, 8 samples = 16 sequences per GPU, f16 operands, attention output and fc1 "
+                                          "operand carried as f16 + a low-precision remainder (fp8 / fp4 with a per-row scale) whose product runs on the "
+                                          "block-scaled MFMA inside the same GEMM launch (guided_split 20, the default of guided calls)",
+                              "value": round(sps, 3), "unit": "guided sample-steps/s", "ms_per_step": round(v["ms_per_step"], 3),
+                              "other_guided_split_settings": {
+                                  f"guided_split_{gs}": {"value": round(world * 8 / (v[f"ms_per_step_guided_split_{gs}"] * 1e-3), 3),
+                                                         "ms_per_step": round(v[f"ms_per_step_guided_split_{gs}"], 3),
+                                                         "note": {0: "plain f16 operands (rounds 1-4): the guided XL/2 output at trained-scale gates is AT "
+                                                                     "1e-3 of the fp32 reference, 0.61-1.07e-3 over 12 draws",
+                                                                  4: "fp8 remainder of the attention output only: 0.51-0.87e-3 over the 12 draws",
+                                                                  12: "both remainders as fp8 (the first form of round 6): 0.43-0.72e-3",
+                                                                  3: "round 5's default: both operands as f16 pairs [hi | lo] . [W | W]: 0.43-0.72e-3, "
+                                                                     "the parity of the low-precision forms at two to three times their cost"}[gs]}
+                                  for gs in (0, 4, 12, 3) if f"ms_per_step_guided_split_{gs}" in v},
+                              "parity_of_the_default": "0.44-0.73e-3 (eps channels 0.44-0.79e-3) over gate_std {0.3, 1.0} x t {999, 500, 50} x 2 seeds "
+                                                       "against the fp32 oracle (profiles/r6_gate_parity_guided.json)",
+                              "steps": v["steps"], "global_batch": 8 * world,
+                              "model_mfma_frac": round(2 * sps / world * flops / (MFMA_PEAK_TFLOPS * 1e12), 4),
+                              "roofline_table": v.get("roofline_table"), "forward_ms_eager_events": v.get("forward_ms_eager_events")}
+        elif k == "config5":
+            tb, D5, dep5, M5 = 5, 768, 12, 5 * 16 * 256
+            fwd5 = dep5 * 2.0 * M5 * 12 * D5 * D5 + (dep5 // 2) * (4.0 * tb * 16 * 256 * 256 * D5 + 4.0 * tb * 256 * 16 * 16 * D5)
+            res["config5"] = {"workload": "train.py step, Latte-B/2 16x256x256 synthetic latents, local batch 5, f16 operands (loss-scaled backward: the "
+                                          "mantissa of the reference's TF32 matmuls) / fp32 masters: forward + MSE/VB loss + backward + grad all-reduce + clip + AdamW + EMA",
+                              "value": round(world * tb / (v["ms_per_step"] * 1e-3), 3), "unit": "training samples/s",
+                              "ms_per_step": round(v["ms_per_step"], 3), "steps": v["steps"], "global_batch": tb * world,
+                              "algorithmic_tflops_per_gpu": round(3 * fwd5 / (v["ms_per_step"] * 1e-3) / 1e12, 1),
+                              "loss_finite": v.get("loss_finite"),
+                              "fuse_small_0": {"ms_per_step": round(v.get("ms_per_step_separate_launches", 0.0), 3),
+                                               "note": "trainer option fuse_small = 0 (the separate finalize / column-sum / adaLN / gate-backward "
+                                                       "launches of rounds 2 - 6) on the same box; the default folds them (latte_amd/csrc/train_fin.hip)"}}
+        else:
+            res[k] = {"value": round(world * v.get("batch", B) / (v["ms_per_step"] * 1e-3), 3), "unit": "sample-steps/s",
+                      "ms_per_step": round(v["ms_per_step"], 4), "steps": v["steps"]}
+            if "batch" in v:
+                res[k]["per_gpu_batch"] = v["batch"]
+    if world == 1 and not args.no_side:
+        note('power check (socket power / shader clock in the forward; dominant GEMM on quiet operands)')
+        try:
+            res["power_check"] = power_check(device, model, x, args.dtype)
+        except Exception as ex:  # noqa: BLE001  (rocm-smi absent or unreadable: the line must still print)
+            res["power_check"] = {"error": repr(ex)[:200]}
+        res["energy"] = energy_columns(res, world)
+    if world == 1 and not args.no_vae:
+        res["vae_decode"] = vae_decode_rate(device)
+    if world == 1 and not args.no_side:
+        note('config 4 (Latte-1 T2V guided step + temporal decoder)')
+        res["config4"] = config4_rate(device)
+    if world == 1 and not args.no_cpu_baseline:
+        note('cpu baseline (oracle on host cores)')
+        res["cpu_baseline"] = cpu_baseline(args.cpu_steps)
+        note('cpu baseline done')
 
 
 if __name__ == "__main__":

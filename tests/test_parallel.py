@@ -165,14 +165,14 @@ def test_broadcast_temb_table_rccl_two_gpus(tmp_path):
     assert all(torch.load(os.path.join(str(tmp_path), f"r{r}.pt"))["ok"] for r in range(2))
 
 
-def _run_bench(extra, timeout):
+def _run_bench(extra, timeout, gpus=2):
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["LATTE_BENCH_BACKEND"] = "gloo"      # two ranks on fewer than two GPUs: RCCL wants one device per rank
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2"] + extra, env=env, capture_output=True,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus)] + extra, env=env, capture_output=True,
                        text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -194,7 +194,22 @@ import pytest  # noqa: E402
 def test_bench_two_ranks_full_path_on_the_gpu():
     """The whole N = 2 code path of bench.py (temb-table broadcast, barriers, max-over-ranks reduction, one JSON line) with
     both ranks on the lease's GPU over gloo: `--gpus 2` alone starts them.  Numbers are not asserted, the contract fields are."""
-    res = _run_bench(["--steps", "2", "--warmup", "1", "--batch", "1", "--no-side", "--no-vae", "--no-cpu-baseline"], 900)
+    res = _run_bench(["--steps", "2", "--warmup", "1", "--batch", "1", "--full", "--no-side", "--no-vae", "--no-cpu-baseline"], 900)
     assert res["n_gpus"] == 2 and res["collective_ranks"] == 2 and res["steps"] == 2 and res["warmup"] == 1
     assert res["config"]["global_batch"] == 2 and res["scaling"] == "weak" and res["finite"]
     assert res["value"] > 0 and res["roofline"]["frac"] > 0
+
+
+FULL_ONLY = {"other_sampler", "roofline", "roofline_table", "kernel_ms_per_forward", "forward_ms_eager_events", "bf16", "batch2", "batch1",
+             "config3", "config4", "config5", "power_check", "energy", "vae_decode", "cpu_baseline"}
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_measures_the_headline_only():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` prints the headline fields, all from its timed region, and runs none of what
+    --full adds (other samplers, operand types and configurations, roofline tables, power check, VAE decode, CPU baseline)."""
+    res = _run_bench(["--steps", "2", "--warmup", "1", "--batch", "1"], 600, gpus=1)
+    assert res["metric"] == "denoising steps/sec" and res["unit"] == "sample-steps/s" and res["higher_is_better"] is True
+    assert res["dtype"] == "f16" and res["n_gpus"] == 1 and res["steps"] == 2 and res["warmup"] == 1 and res["finite"]
+    assert res["value"] > 0 and abs(res["value"] - 1e3 / res["ms_per_step"]) < 1e-3 * res["value"]     # batch 1: value = 1 / step time
+    assert not FULL_ONLY & set(res), sorted(FULL_ONLY & set(res))
