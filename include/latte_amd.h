@@ -397,6 +397,35 @@ int latte_t2v_guided_ddim_loop(latte_t2v_t* e, float* x, int samples, int n_step
                                const double* alpha_t, const double* alpha_prev, float guidance_scale,
                                int enable_temporal_attentions, void* stream);
 
+/* ------------------------------------------------------------------ T5 v1.1 text encoder
+ * transformers.T5EncoderModel (feed_forward_proj "gated-gelu"): the text_encoder of Latte-1 text-to-video (T5-v1.1-XXL: d_model 4096,
+ * d_kv 64, 64 heads, d_ff 10240, 24 layers).  Pre-norm blocks on an fp32 residual stream, RMSNorm statistics and softmax in fp32, no
+ * bias anywhere, scores unscaled, + position_bias[h][key - query] from block 0's relative_attention_bias (bidirectional buckets) and a
+ * key mask that removes padded keys exactly.  Projection operands (activations and weights) are split f16 pairs
+ * (hi + 2^-11 lo, csrc/t5.hip), attention operands plain f16.  d_kv must be 64, d_model and d_ff multiples of 64, max_len <= 512,
+ * compute_dtype LATTE_DTYPE_F16. */
+typedef struct latte_t5 latte_t5_t;
+typedef struct {
+  int d_model, d_kv, num_heads, d_ff, num_layers, vocab_size;
+  int relative_attention_num_buckets;   /* 32 */
+  int relative_attention_max_distance;  /* 128 */
+  float layer_norm_epsilon;             /* 1e-6 */
+  int compute_dtype;
+} latte_t5_config_t;
+/* Allocates the packed weights and the workspace of max_batch x max_len tokens on the current device. */
+int latte_t5_create(const latte_t5_config_t* cfg, int max_batch, int max_len, latte_t5_t** out);
+void latte_t5_destroy(latte_t5_t* t);
+int latte_t5_num_keys(const latte_t5_t* t);
+const char* latte_t5_key(const latte_t5_t* t, int i);
+/* load_state_dict for ONE tensor under its transformers key ("shared.weight", "encoder.block.3.layer.1.DenseReluDense.wi_0.weight",
+ * ...): fp32 in DEVICE memory, shape[ndim] checked against the configuration; packed here, `data` is not kept.
+ * "encoder.embed_tokens.weight" is the tied duplicate of "shared.weight": either fills the one table. */
+int latte_t5_load_weight(latte_t5_t* t, const char* key, const float* data, const int64_t* shape, int ndim, void* stream);
+int latte_t5_check_weights(latte_t5_t* t);
+/* last_hidden_state: ids int64 [B, L], mask fp32 [B, L] (> 0.5 = attend; NULL = all), out fp32 [B, L, d_model]; all device memory.
+ * An id outside [0, vocab_size) reads embedding row 0.  A row's result does not depend on B or on the other rows. */
+int latte_t5_forward(latte_t5_t* t, const int64_t* ids, const float* mask, int B, int L, float* out, void* stream);
+
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * Runs ONE denoiser forward eagerly with HIP events around every kernel launch on `stream`,
  * synchronises, and reports per-kernel-class totals.  classes (fixed order):

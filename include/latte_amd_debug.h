@@ -207,6 +207,29 @@ int latte_debug_dma_probe(const void* src, long long* out, int mode, int waves, 
  * measurement ablations whose results are garbage (attention variants 7-10, 16-19) exist only in a LATTE_DEBUG_BUILD=1 library. */
 int latte_debug_set_choice(const char* name, int value);
 
+/* T5 encoder kernels (csrc/t5.hip) one at a time.  A "pair" is two f16 arrays hi / lo of one shape: value = hi + lo / 2048.
+ *   embed        x[m, :] = table[ids[m], :]
+ *   rmsnorm      w * x * rsqrt(mean(x^2) + eps) of fp32 rows -> the pair (out_f32 == NULL) or fp32
+ *   bucket       the bidirectional bucket of key - query = rel (host)
+ *   bias_table   table[h][d] = rel[bucket(d - (max_len - 1))][h], [heads, 2 max_len - 1]; synchronises
+ *   attention    qkv f16 [B L, 3 heads 64] ([q | k | v], column head * 64 + d) -> the pair [B L, heads 64]; table as above, mask fp32
+ *                [B, L] or NULL
+ *   gated_act    u fp32 [M, 2 F] -> the pair [M, F] of gelu_new(u[:, :F]) * u[:, F:]
+ *   pack         fp32 -> pair
+ *   proj         out[M, N] (fp32) += A[M, K] . W[N, K]^T on pairs; A's arrays must hold M rounded up to 256 rows; slabs: scratch of
+ *                proj_splits(N, K) * M * N floats */
+int latte_debug_t5_embed(const int64_t* ids, const float* table, float* x, int M, int D, int vocab, void* stream);
+int latte_debug_t5_rmsnorm(float* x, const float* w, void* out_hi, void* out_lo, float* out_f32, int M, int D, float eps, void* stream);
+int latte_debug_t5_bucket(int rel, int num_buckets, int max_distance);
+int latte_debug_t5_bias_table(const float* rel, int heads, int num_buckets, int max_distance, int max_len, float* table, void* stream);
+int latte_debug_t5_attention(const void* qkv, const float* table, const float* mask, void* out_hi, void* out_lo, int B, int L, int heads,
+                             int max_len, void* stream);
+int latte_debug_t5_gated_act(const float* u, void* out_hi, void* out_lo, int M, int F, void* stream);
+int latte_debug_t5_pack(const float* w, void* hi, void* lo, int64_t n, void* stream);
+int latte_debug_t5_proj_splits(int N, int K);
+int latte_debug_t5_proj(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, float* slabs, float* out, int M, int N, int K,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 
 Public surface = the reference entry points for the sampling hot path:
 ``Latte_models`` / ``get_models`` / ``find_model`` (models/latte.py, models/__init__.py, utils.py),
-``create_diffusion`` (diffusion/__init__.py), ``AutoencoderKL`` (diffusers, decode only), ``LatteT2V`` / ``LattePipeline`` (models/latte_t2v.py, sample/pipeline_latte.py:
+``create_diffusion`` (diffusion/__init__.py), ``AutoencoderKL`` (diffusers, decode only), ``T5EncoderModel`` (transformers, the text encoder of text-to-video), ``LatteT2V`` / ``LattePipeline`` (models/latte_t2v.py, sample/pipeline_latte.py:
 the Latte-1 text-to-video denoiser and its sampling loop), ``load_config`` (OmegaConf.load stand-in for the YAMLs).
 """
 from ._lib import LatteError, load_library  # noqa: F401
@@ -11,6 +11,7 @@ from .diffusion import SpacedDiffusion, create_diffusion  # noqa: F401
 from .models import Latte, Latte_models, find_model, get_models  # noqa: F401
 from .pipeline import LattePipeline  # noqa: F401
 from .t2v import LatteT2V  # noqa: F401
+from .t5 import T5EncoderModel  # noqa: F401
 from .training import LatteTrainer  # noqa: F401
 from .vae import AutoencoderKL, AutoencoderKLTemporalDecoder  # noqa: F401
 from .video_io import read_avi, read_mp4, write_avi, write_mp4  # noqa: F401

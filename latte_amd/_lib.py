@@ -32,6 +32,12 @@ class T2VConfig(ctypes.Structure):
                                      "max_text_tokens", "compute_dtype")]
 
 
+class T5Config(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("d_model", "d_kv", "num_heads", "d_ff", "num_layers", "vocab_size",
+                                     "relative_attention_num_buckets", "relative_attention_max_distance")] \
+        + [("layer_norm_epsilon", c_f32), ("compute_dtype", c_int)]
+
+
 DTYPES = {"bf16": 0, "bfloat16": 0, "f16": 1, "fp16": 1, "float16": 1}
 
 # name -> (restype, argtypes); mirrors include/latte_amd.h and include/latte_amd_debug.h
@@ -113,7 +119,23 @@ PROTOTYPES = {
     "latte_vae_encode": (c_int, [c_void, c_void, c_int, c_int, c_void, c_f32, c_int, c_void, c_void]),
     "latte_vae_posterior": (c_int, [c_void, c_void, c_int, c_int, c_f32, c_int, c_void, c_void]),
     "latte_vae_profile_encode": (c_int, [c_void, c_void, c_int, c_int, c_void, c_f32, c_int, c_void, c_void, c_void, c_int, c_void]),
+    "latte_t5_create": (c_int, [ctypes.POINTER(T5Config), c_int, c_int, ctypes.POINTER(c_void)]),
+    "latte_t5_destroy": (None, [c_void]),
+    "latte_t5_num_keys": (c_int, [c_void]),
+    "latte_t5_key": (c_char, [c_void, c_int]),
+    "latte_t5_load_weight": (c_int, [c_void, c_char, c_void, ctypes.POINTER(c_i64), c_int, c_void]),
+    "latte_t5_check_weights": (c_int, [c_void]),
+    "latte_t5_forward": (c_int, [c_void, c_void, c_void, c_int, c_int, c_void, c_void]),
     # test hooks
+    "latte_debug_t5_embed": (c_int, [c_void, c_void, c_void, c_int, c_int, c_int, c_void]),
+    "latte_debug_t5_rmsnorm": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_f32, c_void]),
+    "latte_debug_t5_bucket": (c_int, [c_int, c_int, c_int]),
+    "latte_debug_t5_bias_table": (c_int, [c_void, c_int, c_int, c_int, c_int, c_void, c_void]),
+    "latte_debug_t5_attention": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void]),
+    "latte_debug_t5_gated_act": (c_int, [c_void, c_void, c_void, c_int, c_int, c_void]),
+    "latte_debug_t5_pack": (c_int, [c_void, c_void, c_void, c_i64, c_void]),
+    "latte_debug_t5_proj_splits": (c_int, [c_int, c_int]),
+    "latte_debug_t5_proj": (c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_void]),
     "latte_debug_gemm_lo8": (c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_int,
                                      c_int, c_void]),
     "latte_debug_attention_split8": (c_int, [c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_int, c_void]),

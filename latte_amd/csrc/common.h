@@ -272,6 +272,21 @@ int launch_posterior(const float* moments, const float* noise, int n, int hw, fl
 int launch_pack_conv_w(const float* w, half_t* out, int Cout, int Cin, int dtype, hipStream_t st, half_t* out_lo = nullptr);   // out_lo: the f16 rounding residual
 int launch_pack_small_w(const float* w, float* out, int Cout, int Cin, int transpose, hipStream_t st);
 
+// ---- T5 v1.1 encoder kernels (t5.hip).  Projection operands are split pairs: hi = f16(x), lo = f16((x - hi) * 2^11)
+int launch_t5_embed(const int64_t* ids, const float* table, float* x, int M, int D, int vocab, hipStream_t st);
+// x[m, :] += sum of nsplit slabs (nsplit 0: x unchanged); w != nullptr: RMSNorm(x) * w -> the pair out_hi / out_lo, or fp32 out_f32
+int launch_t5_res_norm(float* x, const float* slabs, int nsplit, size_t slab_stride, const float* w, half_t* out_hi, half_t* out_lo,
+                       float* out_f32, int M, int D, float eps, hipStream_t st);
+int launch_t5_bias_table(const float* rel, const int* bucket, float* table, int heads, int span, hipStream_t st);
+int launch_t5_pack_w(const float* w, half_t* hi, half_t* lo, size_t n, hipStream_t st);
+int launch_t5_reduce_h16(const float* slabs, int nsplit, size_t slab_stride, half_t* out, size_t n, hipStream_t st);
+int launch_t5_gated_act(const float* slabs, int nsplit, size_t slab_stride, half_t* out_hi, half_t* out_lo, int M, int F, hipStream_t st);
+int t5_proj_splits(int N, int K);   // K chunks (= slabs written) of launch_t5_proj: depends on the weight shape only
+int launch_t5_proj(const half_t* Ahi, const half_t* Alo, const half_t* Whi, const half_t* Wlo, float* slabs, size_t slab_stride, int M,
+                   int N, int K, hipStream_t st);
+int launch_t5_attention(const half_t* qkv, const float* table, const float* mask, half_t* out_hi, half_t* out_lo, int B, int L, int heads,
+                        int Lmax, hipStream_t st);
+
 // ---- training-step kernels (train.hip, train_attn.hip) --------------------------------------------------------------
 int train_rows_per_run(int rps);
 int launch_gated_add(const float* x_in, const half_t* y, const float* gate, int gate_stride, float* x_out, int M, int D, int rps,

@@ -169,3 +169,49 @@ def t2v_keys(num_attention_heads=16, attention_head_dim=72, in_channels=4, out_c
 
 def t2v_state_dict(seed=0, **config):
     return _fill(t2v_keys(**config), seed)
+
+
+def t5_keys(d_model=4096, d_kv=64, num_heads=64, d_ff=10240, num_layers=24, vocab_size=32128, relative_attention_num_buckets=32,
+            **unused):
+    """State-dict keys of ``transformers.T5EncoderModel`` (T5 v1.1, gated-gelu); the defaults are Latte-1's text_encoder (XXL).
+    ``encoder.embed_tokens.weight`` is the tied duplicate of ``shared.weight`` that ``state_dict()`` also lists."""
+    inner = num_heads * d_kv
+    ks = {"shared.weight": (vocab_size, d_model), "encoder.embed_tokens.weight": (vocab_size, d_model)}
+    for i in range(num_layers):
+        a, f = f"encoder.block.{i}.layer.0.", f"encoder.block.{i}.layer.1."
+        for n in "qkv":
+            ks[a + f"SelfAttention.{n}.weight"] = (inner, d_model)
+        ks[a + "SelfAttention.o.weight"] = (d_model, inner)
+        if i == 0:
+            ks[a + "SelfAttention.relative_attention_bias.weight"] = (relative_attention_num_buckets, num_heads)
+        ks[a + "layer_norm.weight"] = (d_model,)
+        ks[f + "DenseReluDense.wi_0.weight"], ks[f + "DenseReluDense.wi_1.weight"] = (d_ff, d_model), (d_ff, d_model)
+        ks[f + "DenseReluDense.wo.weight"] = (d_model, d_ff)
+        ks[f + "layer_norm.weight"] = (d_model,)
+    ks["encoder.final_layer_norm.weight"] = (d_model,)
+    return ks
+
+
+def t5_state_dict(seed=0, **config):
+    """``transformers``' own init scales (T5PreTrainedModel._init_weights, factor 1), except: ``relative_attention_bias`` has unit
+    variance (stock: d_model^-0.5) and the norm weights are 1 + 0.2 randn (stock: exactly 1), so that a wrong bias index or a
+    dropped norm weight changes the output by far more than any parity bound."""
+    ks = t5_keys(**config)
+    d_model = ks["shared.weight"][1]
+    d_kv = config.get("d_kv", 64)
+    g = torch.Generator("cpu").manual_seed(seed)
+    sd = {}
+    for k, shp in ks.items():
+        if k == "encoder.embed_tokens.weight":
+            sd[k] = sd["shared.weight"]
+            continue
+        r = torch.randn(shp, generator=g)
+        if k.endswith("layer_norm.weight"):
+            sd[k] = 1.0 + 0.2 * r
+        elif k == "shared.weight" or k.endswith("relative_attention_bias.weight"):
+            sd[k] = r
+        elif k.endswith("SelfAttention.q.weight"):
+            sd[k] = r * (d_model * d_kv) ** -0.5
+        else:                                   # k, v, wi_0, wi_1: d_model^-0.5; o: inner^-0.5; wo: d_ff^-0.5 (all = fan_in^-0.5)
+            sd[k] = r * shp[1] ** -0.5
+    return sd

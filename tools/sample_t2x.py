@@ -3,10 +3,11 @@
   python tools/sample_t2x.py --config configs/t2v_sample.yaml [--random] [--steps N] [--layers L]
 
 With a real checkpoint directory (`pretrained_model_path` holding transformer/, vae/, tokenizer/, text_encoder/) the flow is
-the reference's (sample_t2x.py:21-140): T5 tokenizer + encoder from `transformers`, `LatteT2V.from_pretrained_2d`,
-`AutoencoderKL.from_pretrained`, a DDIM scheduler, `LattePipeline(...)`, one video per prompt.  Offline there are no
-weights: `--random` builds randomly initialised models and random prompt embeddings of the right shape, which exercises the
-whole device path (denoiser, guidance loop, VAE decode, video hand-off) and times it.  Videos are written as .mp4
+the reference's (sample_t2x.py:21-140): the T5 tokenizer from `transformers`, the T5 encoder on the engine
+(`latte_amd.T5EncoderModel.from_pretrained`), `LatteT2V.from_pretrained_2d`, `AutoencoderKL.from_pretrained`, a DDIM scheduler,
+`LattePipeline(...)`, one video per prompt.  Offline there are no weights: `--random` builds randomly initialised models, the text
+encoder among them (`--t5-layers` of the XXL shape), and a deterministic stand-in tokenizer (`latte_amd.t5.HashTokenizer`), so the
+run goes prompt string -> ids -> T5 -> denoiser -> VAE -> mp4 on the device path and times it.  Videos are written as .mp4
 (Motion-JPEG samples, latte_amd.video_io).  Only the DDIM scheduler has a self-contained stand-in (latte_amd/schedulers.py); any diffusers
 scheduler object can be passed to LattePipeline instead.
 """
@@ -27,7 +28,8 @@ from latte_amd.schedulers import DDIMScheduler  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True)
-    ap.add_argument("--random", action="store_true", help="random weights and prompt embeddings (no checkpoints offline)")
+    ap.add_argument("--random", action="store_true", help="random weights and a stand-in tokenizer (no checkpoints offline)")
+    ap.add_argument("--t5-layers", type=int, default=24, help="--random: depth of the randomly initialised T5 encoder (XXL shape)")
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--layers", type=int, default=28)
     ap.add_argument("--out", default=None)
@@ -43,7 +45,10 @@ def main():
     scheduler = DDIMScheduler(beta_start=args.beta_start, beta_end=args.beta_end, beta_schedule=args.beta_schedule, clip_sample=False)
     tokenizer = text_encoder = None
     if a.random:
-        from latte_amd.random_init import t2v_state_dict, vae_decoder_state_dict
+        from latte_amd.random_init import t2v_state_dict, t5_state_dict, vae_decoder_state_dict
+        from latte_amd.t5 import HashTokenizer
+        tokenizer = HashTokenizer()
+        text_encoder = latte_amd.T5EncoderModel(num_layers=a.t5_layers, max_batch=1).load_state_dict(t5_state_dict(0, num_layers=a.t5_layers))
         transformer = latte_amd.LatteT2V(num_layers=a.layers, sample_size=latent, video_length=args.video_length,
                                          compute_dtype=cdt, max_batch=2).load_state_dict(t2v_state_dict(0, num_layers=a.layers))
         if args.enable_vae_temporal_decoder:                       # sample_t2x.py:31-32
@@ -54,7 +59,7 @@ def main():
             vae = latte_amd.AutoencoderKL(latent_size=latent, max_frames=args.video_length, compute_dtype="f16")
             vae.load_state_dict(vae_decoder_state_dict(0))
     else:
-        from transformers import T5EncoderModel, T5Tokenizer
+        from transformers import T5Tokenizer
         p = args.pretrained_model_path
         transformer = latte_amd.LatteT2V.from_pretrained_2d(p, subfolder="transformer", video_length=args.video_length,
                                                             compute_dtype=cdt, max_batch=2)
@@ -64,7 +69,7 @@ def main():
         else:
             vae = latte_amd.AutoencoderKL.from_pretrained(p, subfolder="vae", latent_size=latent, max_frames=args.video_length)
         tokenizer = T5Tokenizer.from_pretrained(p, subfolder="tokenizer")
-        text_encoder = T5EncoderModel.from_pretrained(p, subfolder="text_encoder", torch_dtype=torch.float16).to(device).eval()
+        text_encoder = latte_amd.T5EncoderModel.from_pretrained(p, subfolder="text_encoder", max_batch=1).eval()
     pipe = latte_amd.LattePipeline(vae=vae, text_encoder=text_encoder, tokenizer=tokenizer, scheduler=scheduler,
                                    transformer=transformer).to(device)
     out_dir = a.out or args.save_img_path
@@ -73,12 +78,7 @@ def main():
     g = torch.Generator("cpu").manual_seed(int(args.seed or 0))
     for n, prompt in enumerate(args.text_prompt):
         print(f"Processing the ({prompt}) prompt")
-        kw = {}
-        if a.random:                                                  # stand-in for the T5 features of the prompt / of ""
-            k = min(8 + len(prompt.split()), 120)
-            kw = dict(prompt_embeds=torch.randn(1, k, 4096, generator=g), negative_prompt_embeds=torch.randn(1, k, 4096, generator=g))
-        else:
-            kw = dict(prompt=prompt)
+        kw = dict(prompt=prompt)
         torch.cuda.synchronize()
         t0 = time.time()
         video = pipe(video_length=args.video_length, height=args.image_size[0], width=args.image_size[1],
