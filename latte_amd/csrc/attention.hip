@@ -21,77 +21,12 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mfma_util.h"
 
 namespace latte {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
-template <int DT>
-__device__ __forceinline__ f32x4 mfma_k32(u32x4 a, u32x4 b, f32x4 c) {
-  if constexpr (DT == LATTE_DTYPE_BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-template <int DT>
-__device__ __forceinline__ f32x4 mfma_k16(u32x2 a, u32x2 b, f32x4 c) {
-  if constexpr (DT == LATTE_DTYPE_BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4, a), __builtin_bit_cast(f16x4, b), c, 0, 0, 0);
-}
-template <int DT>
-__device__ __forceinline__ unsigned int pack2(float lo, float hi) {
-  if constexpr (DT == LATTE_DTYPE_BF16) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-    bf16x2 v = {(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(unsigned int, v);
-  } else {
-    typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-    f16x2 v = {(_Float16)lo, (_Float16)hi};
-    return __builtin_bit_cast(unsigned int, v);
-  }
-}
-
-constexpr float NEG_BIG = -1.0e30f;
 constexpr int PITCH = 144;  // LDS row pitch in bytes: 9 x 16-B chunks (odd -> b128 reads spread over banks)
-
-__device__ __forceinline__ int64_t seq_base_row(const AttnArgs& a, int seq) {
-  return (int64_t)(seq / a.U) * a.sample_stride + (int64_t)(seq % a.U) * a.seq_stride;
-}
-
-// ------------------------------------------------------------------------------------------------
-// hardware transpose read: lane i of a 16-lane group supplies the address of 4 d-values of key (i >> 2) of a ROW-MAJOR image
-// and receives the 4 keys of d-column i (see attn_full_kernel below)
-typedef __attribute__((__vector_size__(4 * sizeof(short)))) short i16v4;
-template <int DT>
-__device__ __forceinline__ u32x2 lds_tr16(const char* p) {   // 16-bit elements: the bit pattern is dtype-agnostic
-  i16v4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16v4*)p);
-  return __builtin_bit_cast(u32x2, v);
-}
-
-// CROSS = true (LatteT2V attn2): queries from a [rows, q_ld] buffer, Lk keys / values per SAMPLE from a.kv ([K | V], 2D
-// columns), an optional additive score bias per (sample, key); everything else is the same kernel.
-// (mfma_util.h: split8_f16, restated here: this file keeps its own fragment helpers) four values -> their nearest f16 and one word of four
-// OCP e4m3 codes of (v - hi) * 2^LO8_A_SHIFT, clamped to +-448
-__device__ __forceinline__ unsigned int split8_f16(float v0, float v1, float v2, float v3, unsigned int& hi01, unsigned int& hi23) {
-  const _Float16 h0 = (_Float16)v0, h1 = (_Float16)v1, h2 = (_Float16)v2, h3 = (_Float16)v3;
-  hi01 = pack2<LATTE_DTYPE_F16>((float)h0, (float)h1);
-  hi23 = pack2<LATTE_DTYPE_F16>((float)h2, (float)h3);
-  constexpr float S = (float)(1 << LO8_A_SHIFT);
-  auto cl = [](float r) { return __builtin_fminf(__builtin_fmaxf(r, -448.f), 448.f); };
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(cl((v0 - (float)h0) * S), cl((v1 - (float)h1) * S), 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(cl((v2 - (float)h2) * S), cl((v3 - (float)h3) * S), w, true);
-  return (unsigned int)w;
-}
 
 // One output piece of an attention kernel: four consecutive head-dim values of a token -> 8 bytes of half at `dst` (a.out based), and,
 // with LO8 (f16; guided calls, engine option guided_split bit 2), their fp8 remainder word at the same element offset of a.out8
@@ -109,6 +44,8 @@ __device__ __forceinline__ void store_out4(const AttnArgs& a, half_t* dst, float
   }
 }
 
+// CROSS = true (LatteT2V attn2): queries from a [rows, q_ld] buffer, Lk keys / values per SAMPLE from a.kv ([K | V], 2D
+// columns), an optional additive score bias per (sample, key); everything else is the same kernel.
 template <int HD, int DT, bool CROSS = false, bool LO8 = false>
 __global__ void __launch_bounds__(256) attn_flash_kernel(AttnArgs a) {
   constexpr int KS = (HD + 31) / 32;  // k-steps of the QK^T contraction (hd padded to 32)
@@ -180,7 +117,7 @@ __global__ void __launch_bounds__(256) attn_flash_kernel(AttnArgs a) {
         const int ch = g + 4 * ks;
         u32x4 kf = *(const u32x4*)(k_lds + (16 * j + fl) * PITCH + ch * 16);
         if (ch >= NCH) kf = (u32x4){0u, 0u, 0u, 0u};
-        st[j] = mfma_k32<DT>(kf, qf[ks], st[j]);
+        st[j] = mfma16<DT>(kf, qf[ks], st[j]);
       }
     }
     // online softmax over the key axis (rows of S^T): in-lane over 16 values, then lanes g = 0..3
@@ -226,9 +163,9 @@ __global__ void __launch_bounds__(256) attn_flash_kernel(AttnArgs a) {
       for (int d = 0; d < DF; ++d) {
         // pad d-columns (>= HD) read finite neighbouring data and only produce unused O rows
         const char* vb = v_lds + (32 * ks2 + 4 * g + (fl >> 2)) * VP + (fl & 3) * 8 + d * 32;
-        const u32x2 lo = lds_tr16<DT>(vb);
-        const u32x2 hi = lds_tr16<DT>(vb + 16 * VP);
-        o[d] = mfma_k32<DT>((u32x4){lo[0], lo[1], hi[0], hi[1]}, pb, o[d]);
+        const u32x2 lo = lds_tr16(vb);
+        const u32x2 hi = lds_tr16(vb + 16 * VP);
+        o[d] = mfma16<DT>((u32x4){lo[0], lo[1], hi[0], hi[1]}, pb, o[d]);
       }
     }
   }
@@ -363,8 +300,8 @@ __global__ void __launch_bounds__(256, 2) attn_full_kernel(AttnArgs a) {
       st[1][kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        st[0][kt] = mfma_k32<DT>(kf[kt & 3][ks], qf[0][ks], st[0][kt]);
-        st[1][kt] = mfma_k32<DT>(kf[kt & 3][ks], qf[1][ks], st[1][kt]);
+        st[0][kt] = mfma16<DT>(kf[kt & 3][ks], qf[0][ks], st[0][kt]);
+        st[1][kt] = mfma16<DT>(kf[kt & 3][ks], qf[1][ks], st[1][kt]);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -420,8 +357,8 @@ __global__ void __launch_bounds__(256, 2) attn_full_kernel(AttnArgs a) {
     auto load_v = [&](int ks2, u32x4 (&dst)[DF]) {
 #pragma unroll
       for (int d = 0; d < DF; ++d) {
-        const u32x2 lo = lds_tr16<DT>(vbase + (32 * ks2) * RP + d * 32);
-        const u32x2 hi = lds_tr16<DT>(vbase + (32 * ks2 + 16) * RP + d * 32);
+        const u32x2 lo = lds_tr16(vbase + (32 * ks2) * RP + d * 32);
+        const u32x2 hi = lds_tr16(vbase + (32 * ks2 + 16) * RP + d * 32);
         dst[d] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
       }
     };
@@ -438,8 +375,8 @@ __global__ void __launch_bounds__(256, 2) attn_full_kernel(AttnArgs a) {
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int d = 0; d < DF; ++d) {
-        o[0][d] = mfma_k32<DT>(vfr[ks2 & 1][d], pb[0], o[0][d]);
-        o[1][d] = mfma_k32<DT>(vfr[ks2 & 1][d], pb[1], o[1][d]);
+        o[0][d] = mfma16<DT>(vfr[ks2 & 1][d], pb[0], o[0][d]);
+        o[1][d] = mfma16<DT>(vfr[ks2 & 1][d], pb[1], o[1][d]);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -478,14 +415,7 @@ __global__ void __launch_bounds__(256, 2) attn_full_kernel(AttnArgs a) {
 // flight while block kb is multiplied (counted vmcnt, one barrier per block), and each block is staged half as often.
 // Online softmax across blocks: running max on the raw scores (the scale is positive), alpha = exp2((m_old - m_new) c).
 // The V^T fragments come from the transpose read in its inline-assembly form: in front of the builtin hipcc drains every LDS
-// DMA in flight (see gemm_tn.hip), which would serialise the ring again.
-template <int OFF>
-__device__ __forceinline__ u32x2 lds_tr16_asm(const char* p) {
-  u32x2 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"((unsigned)(size_t)(const __attribute__((address_space(3))) char*)p), "i"(OFF));
-  return v;
-}
-
+// DMA in flight (mfma_util.h: lds_tr16_asm), which would serialise the ring again.
 template <int HD, int DT, int ABL = 0, bool LO8 = false>
 __global__ void __launch_bounds__(512) attn_stream_kernel(AttnArgs a) {
   constexpr int KS = (HD + 31) / 32, DF = (HD + 15) / 16, NCH = HD / 8;
@@ -612,8 +542,8 @@ __global__ void __launch_bounds__(512) attn_stream_kernel(AttnArgs a) {
       st[1][kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        st[0][kt] = mfma_k32<DT>(kf[kt & 3][ks], qf[0][ks], st[0][kt]);
-        st[1][kt] = mfma_k32<DT>(kf[kt & 3][ks], qf[1][ks], st[1][kt]);
+        st[0][kt] = mfma16<DT>(kf[kt & 3][ks], qf[0][ks], st[0][kt]);
+        st[1][kt] = mfma16<DT>(kf[kt & 3][ks], qf[1][ks], st[1][kt]);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -726,8 +656,8 @@ __global__ void __launch_bounds__(512) attn_stream_kernel(AttnArgs a) {
 #pragma unroll
       for (int d = 0; d < DF; ++d) {
         const u32x4 vfrag = {vlo[ks2 & 1][d][0], vlo[ks2 & 1][d][1], vhi[ks2 & 1][d][0], vhi[ks2 & 1][d][1]};
-        o[0][d] = mfma_k32<DT>(vfrag, pb[0], o[0][d]);
-        o[1][d] = mfma_k32<DT>(vfrag, pb[1], o[1][d]);
+        o[0][d] = mfma16<DT>(vfrag, pb[0], o[0][d]);
+        o[1][d] = mfma16<DT>(vfrag, pb[1], o[1][d]);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -1272,8 +1202,8 @@ __global__ void __launch_bounds__(512) attn_cross_kernel(AttnArgs a) {
       st[1][kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        st[0][kt] = mfma_k32<DT>(kf[kt & 3][ks], qf[0][ks], st[0][kt]);
-        st[1][kt] = mfma_k32<DT>(kf[kt & 3][ks], qf[1][ks], st[1][kt]);
+        st[0][kt] = mfma16<DT>(kf[kt & 3][ks], qf[0][ks], st[0][kt]);
+        st[1][kt] = mfma16<DT>(kf[kt & 3][ks], qf[1][ks], st[1][kt]);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -1326,11 +1256,11 @@ __global__ void __launch_bounds__(512) attn_cross_kernel(AttnArgs a) {
 #pragma unroll
       for (int d = 0; d < DF; ++d) {
         const char* vb = vbase + (32 * ks2) * RP + d * 32;
-        const u32x2 lo = lds_tr16<DT>(vb);
-        const u32x2 hi = lds_tr16<DT>(vb + 16 * RP);
+        const u32x2 lo = lds_tr16(vb);
+        const u32x2 hi = lds_tr16(vb + 16 * RP);
         const u32x4 vfrag = {lo[0], lo[1], hi[0], hi[1]};
-        o[0][d] = mfma_k32<DT>(vfrag, pb[0], o[0][d]);
-        o[1][d] = mfma_k32<DT>(vfrag, pb[1], o[1][d]);
+        o[0][d] = mfma16<DT>(vfrag, pb[0], o[0][d]);
+        o[1][d] = mfma16<DT>(vfrag, pb[1], o[1][d]);
       }
     }
   }
@@ -1395,7 +1325,7 @@ __global__ void __launch_bounds__(256) attn_small_kernel(AttnArgs a) {
   }
   f32x4 st = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) st = mfma_k32<DT>(kf[ks], qf[ks], st);  // S^T[key = 4g + r][q = fl]
+  for (int ks = 0; ks < KS; ++ks) st = mfma16<DT>(kf[ks], qf[ks], st);  // S^T[key = 4g + r][q = fl]
 
   // softmax in the exp2 domain, max on the RAW scores (c > 0), p = exp2(fma(s, c, -max c)): every operation is explicit (one
   // multiply, one fma, no contraction left to the compiler), so the fused kernel of qkv_attn.hip -- which repeats exactly this
@@ -1429,9 +1359,9 @@ __global__ void __launch_bounds__(256) attn_small_kernel(AttnArgs a) {
     // read: lane i of a 16-lane group supplies the address of 4 d-values of key (i >> 2) and receives the 4 keys of
     // d-column i (one ds_read_b64_tr_b16 instead of four 2-byte reads + packing).  Pad columns (>= HD) of the last
     // fragment read the next row's first bytes / the slack row: finite, and only feed unused O rows.
-    const u32x2 vf = lds_tr16<DT>(v_lds + (4 * g + (fl >> 2)) * VP + (fl & 3) * 8 + d * 32);
+    const u32x2 vf = lds_tr16(v_lds + (4 * g + (fl >> 2)) * VP + (fl & 3) * 8 + d * 32);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = mfma_k16<DT>(vf, pb, acc);  // O^T[d = 16 d + 4g + r][q = fl]
+    acc = mfma16_k16<DT>(vf, pb, acc);  // O^T[d = 16 d + 4g + r][q = fl]
     const int dd = 16 * d + 4 * g;
     if (active && fl < a.L && dd < HD) {
       store_out4<DT, LO8>(a, orow + dd, acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv);

@@ -108,7 +108,7 @@ struct GemmArgs {
   // FP4 correction pass (round 6, second form; rolling kernel, LO = 2): A4 / W4 hold OCP e2m1 codes, two per byte (element k in bits
   // 4 (k & 1) of byte k >> 1), rows of lo4_pitch(K) bytes (K rounded up to 256, zero padded), with ONE E8M0 scale byte per ROW
   // (A4s [Mpad], W4s [N]): value = code * 2^(scale - 127).  v_mfma_scale_f32_16x16x128_f8f6f4 with cbsz = blgp = 4 runs at twice the
-  // fp8 rate and a K tile of 128 row bytes is K = 256 (mfma_util.h: quant4; tools/mx_probe.hip layout H0).
+  // fp8 rate and a K tile of 128 row bytes is K = 256 (device_util.h: quant4_exponent, quant4_pk4; tools/mx_probe.hip layout H0).
   const uint8_t* A4;
   const uint8_t* W4;
   const uint8_t* A4s;
@@ -119,8 +119,8 @@ struct GemmArgs {
 // |w| < 7; the MFMA multiplies the products back by 2^-(LO8_A_SHIFT + LO8_W_SHIFT) (E8M0 scale bytes 127 - shift)
 constexpr int LO8_A_SHIFT = 12, LO8_W_SHIFT = 6;
 inline int lo4_pitch(int K) { return (K + 255) / 256 * 128; }   // bytes per row of an fp4 correction operand
-bool gemm_lo8_ok(int M, int N, int K);
-bool gemm_lo4_ok(int M, int N, int K);   // the shape takes the fp4 correction pass (whole 192-wide tile columns, K % 64 == 0, 32-bit offsets)   // the shape takes the correction pass (whole 192-wide tile columns, K % 128 == 0, 32-bit offsets)
+bool gemm_lo8_ok(int M, int N, int K);   // the shape takes the fp8 correction pass (whole 192-wide tile columns, K % 128 == 0, 32-bit offsets)
+bool gemm_lo4_ok(int M, int N, int K);   // the shape takes the fp4 correction pass (whole 192-wide tile columns, K % 64 == 0, 32-bit offsets)
 // variant: 0 = pick for the shape; simple double-buffered kernel: 1 = 128x128 tile, 2 = 256x128, 3 = 256x256;
 // ping-pong kernel: 4 = 256x128, 5 = 256x192, 6 = 256x256; persistent ping-pong kernel: 7 = 256x128,
 // 8 = 256x192, 9 = 256x256   (N % tileN == 0 required)

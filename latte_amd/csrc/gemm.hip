@@ -25,13 +25,6 @@
 namespace latte {
 namespace {
 
-// GELU(tanh approximation) = x * sigmoid(2u), u = sqrt(2/pi) (x + 0.044715 x^3)   (latte.py:170)
-// = x / (1 + exp2(x (a + b x^2))) with a = -2 log2(e) sqrt(2/pi), b = 0.044715 a: 3 mul + 1 fma + 1 add + exp2 + rcp
-__device__ __forceinline__ float gelu_tanh(float x) {
-  const float p = __builtin_fmaf(x * x, -0.10294324f, -2.3022082f);
-  return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(p * x));
-}
-
 // One accumulator fragment -> memory.  Lane holds 4 consecutive columns n..n+3 of row m.
 template <int EPI, int DT>
 __device__ __forceinline__ void epilogue_store(const GemmArgs& g, const f32x4& a, int m, int n, const float* gate_row) {
@@ -585,11 +578,6 @@ __global__ void __launch_bounds__(512) gemm_pp_kernel(GemmArgs g) {
 // Tile sequence of a workgroup: XCD x (= blockIdx & 7) owns a contiguous chunk of the grouped tile
 // order (tile_coords' order); slot s (= blockIdx >> 3) takes positions s, s + G/8, ... of that chunk, so
 // the 32 workgroups of one XCD work on a compact patch of tiles at any time (shared A / W panels in L2).
-typedef __attribute__((address_space(3))) void lds_void;
-__device__ __forceinline__ void bload_lds16(__amdgpu_buffer_rsrc_t rs, char* lds_wave_base, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)lds_wave_base, 16, voff, soff, 0, 0);
-}
-
 // RMW_AHEAD / RMW_NT: the gated fp32 read-modify-write epilogue keeps RMW_AHEAD residual fragments (1 KB per wave each)
 // in flight ahead of the stores; RMW_NT loads them with the non-temporal policy (they are read exactly once).
 // TAG only separates the instantiations of the two gated-residual call sites (0 = attention out-projection, 1 = fc2), which

@@ -31,25 +31,6 @@
 namespace latte {
 namespace {
 
-template <int DT>
-__device__ __forceinline__ void unpack2pw(unsigned int u, float& a, float& b) {   // two halves of a word -> fp32
-  if constexpr (DT == LATTE_DTYPE_BF16) {
-    a = __builtin_bit_cast(float, u << 16);
-    b = __builtin_bit_cast(float, u & 0xffff0000u);
-  } else {
-    typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_;
-    const f16x2_ h = __builtin_bit_cast(f16x2_, u);
-    a = (float)h[0];
-    b = (float)h[1];
-  }
-}
-
-
-typedef __attribute__((address_space(3))) void lds_void_pw;
-__device__ __forceinline__ void pw_bload_lds16(__amdgpu_buffer_rsrc_t rs, char* lds_wave_base, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_pw*)lds_wave_base, 16, voff, soff, 0, 0);
-}
-
 // In-place accumulate, pinned by inline assembly: with the fragments carried around the loop (rolling kernel) the register
 // allocator otherwise moves accumulators into fragment registers that have just been freed and ends up spilling three of
 // them per K tile.  The compiler's hazard recogniser does not look inside: no VALU / memory instruction may read an
@@ -158,13 +139,13 @@ __global__ void __launch_bounds__(768) gemm_pw_kernel(GemmArgs g) {
       char* sA = smem + stg * A_BYTES + half * 128 * 128 + pw * 1024;
       const unsigned so = (unsigned)(tm_ * BM + half * 128 + pw * 8) * row_bytes + (unsigned)kt * 128u;
 #pragma unroll
-      for (int j = 0; j < AH_INSTR; ++j) pw_bload_lds16(rsA, sA + j * 4 * 1024, voff, so + (unsigned)j * step32);
+      for (int j = 0; j < AH_INSTR; ++j) bload_lds16(rsA, sA + j * 4 * 1024, voff, so + (unsigned)j * step32);
     };
     auto dma_b = [&](int tn_, int kt, int stg) {
       char* sB = smem + B_BASE + stg * B_BYTES + pw * 1024;
       const unsigned so = (unsigned)(tn_ * BN + pw * 8) * row_bytes + (unsigned)kt * 128u;
 #pragma unroll
-      for (int j = 0; j < BG_INSTR; ++j) pw_bload_lds16(rsB, sB + j * 4 * 1024, voff, so + (unsigned)j * step32);
+      for (int j = 0; j < BG_INSTR; ++j) bload_lds16(rsB, sB + j * 4 * 1024, voff, so + (unsigned)j * step32);
     };
     // Two walkers over the K tiles of this workgroup's tile sequence: `b` (for B) is one K tile ahead of the consumers,
     // `a` (for A, the operand that streams from HBM in the long-K GEMMs) two.
@@ -485,12 +466,12 @@ __global__ void __launch_bounds__(768) gemm_pwr_kernel(GemmArgs g) {
       if (LO && kt >= nk) {
         const unsigned so = (unsigned)(tm_ * BM + pw * 8) * row_bytes8 + (unsigned)(kt - nk) * 128u;
 #pragma unroll
-        for (int j = 0; j < 2 * AH_INSTR; ++j) pw_bload_lds16(rsA8, sA + j * 4 * 1024, voff8, so + (unsigned)j * step32_8);
+        for (int j = 0; j < 2 * AH_INSTR; ++j) bload_lds16(rsA8, sA + j * 4 * 1024, voff8, so + (unsigned)j * step32_8);
         return;
       }
       const unsigned so = (unsigned)(tm_ * BM + pw * 8) * row_bytes + (unsigned)kt * 128u;
 #pragma unroll
-      for (int j = 0; j < 2 * AH_INSTR; ++j) pw_bload_lds16(rsA, sA + j * 4 * 1024, voff, so + (unsigned)j * step32);
+      for (int j = 0; j < 2 * AH_INSTR; ++j) bload_lds16(rsA, sA + j * 4 * 1024, voff, so + (unsigned)j * step32);
     };
     auto dma_b = [&](int tn_, int kt, int stg) {
       char* sB = smem + B_BASE + stg * B_BYTES + pw * 1024;
@@ -499,12 +480,12 @@ __global__ void __launch_bounds__(768) gemm_pwr_kernel(GemmArgs g) {
       if (LO && kt >= nk) {
         const unsigned so = (unsigned)(tn_ * BN + pw * 8) * row_bytes8 + (unsigned)(kt - nk) * 128u;
 #pragma unroll
-        for (int j = 0; j < BG_INSTR; ++j) pw_bload_lds16(rsB8, sB + j * 4 * 1024, voff8, so + (unsigned)j * step32_8);
+        for (int j = 0; j < BG_INSTR; ++j) bload_lds16(rsB8, sB + j * 4 * 1024, voff8, so + (unsigned)j * step32_8);
         return;
       }
       const unsigned so = (unsigned)(tn_ * BN + pw * 8) * row_bytes + (unsigned)kt * 128u;
 #pragma unroll
-      for (int j = 0; j < BG_INSTR; ++j) pw_bload_lds16(rsB, sB + j * 4 * 1024, voff, so + (unsigned)j * step32);
+      for (int j = 0; j < BG_INSTR; ++j) bload_lds16(rsB, sB + j * 4 * 1024, voff, so + (unsigned)j * step32);
     };
     struct Walk { int pos, tm, tn, kt; };
     auto advance = [&](Walk& w) {
@@ -608,8 +589,8 @@ __global__ void __launch_bounds__(768) gemm_pwr_kernel(GemmArgs g) {
           }
           if constexpr (EPI == EPI_DGELU_H16) {   // train.hip: gelu_kernel<BWD>, the same arithmetic on the unrounded product
             float x[4];
-            unpack2pw<DT>(side[j][0], x[0], x[1]);
-            unpack2pw<DT>(side[j][1], x[2], x[3]);
+            unpack2<DT>(side[j][0], x[0], x[1]);
+            unpack2<DT>(side[j][1], x[2], x[3]);
             auto dgelu = [](float xx) {
               const float p = __builtin_fmaf(xx * xx, -0.10294324f, -2.3022082f);
               const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(p * xx));
@@ -622,8 +603,8 @@ __global__ void __launch_bounds__(768) gemm_pwr_kernel(GemmArgs g) {
           *(u32x2*)(patch + fr * 112 + j * 32 + gq * 8) = pk;
           if constexpr (EPI == EPI_BIAS_GELU_DUAL_H16) {   // the GELU of the ROUNDED pre-activation (what gelu_kernel<FWD> computes from u)
             float x[4];
-            unpack2pw<DT>(pk[0], x[0], x[1]);
-            unpack2pw<DT>(pk[1], x[2], x[3]);
+            unpack2<DT>(pk[0], x[0], x[1]);
+            unpack2<DT>(pk[1], x[2], x[3]);
             side[j] = (u32x2){pack2<DT>(gelu(x[0]), gelu(x[1])), pack2<DT>(gelu(x[2]), gelu(x[3]))};
           }
           acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1097,13 +1078,13 @@ __global__ void __launch_bounds__(768) gemm_dacc_kernel(GemmArgs g) {
       char* sA = smem + stg * A_BYTES + pw * 1024;
       const unsigned so = (unsigned)(w.tm * BM + w.half * HM + pw * 8) * row_bytes + (unsigned)w.kt * 128u;
 #pragma unroll
-      for (int j = 0; j < AH_INSTR; ++j) pw_bload_lds16(rsA, sA + j * 4 * 1024, voff, so + (unsigned)j * step32);
+      for (int j = 0; j < AH_INSTR; ++j) bload_lds16(rsA, sA + j * 4 * 1024, voff, so + (unsigned)j * step32);
     };
     auto dma_b = [&](const Walk& w, int stg) {
       char* sB = smem + B_BASE + stg * B_BYTES + pw * 1024;
       const unsigned so = (unsigned)(w.tn * BN + pw * 8) * row_bytes + (unsigned)w.kt * 128u;
 #pragma unroll
-      for (int j = 0; j < BG_INSTR; ++j) pw_bload_lds16(rsB, sB + j * 4 * 1024, voff, so + (unsigned)j * step32);
+      for (int j = 0; j < BG_INSTR; ++j) bload_lds16(rsB, sB + j * 4 * 1024, voff, so + (unsigned)j * step32);
     };
     auto advance = [&](Walk& w) {
       if (++w.kt == nk) {
@@ -1127,8 +1108,8 @@ __global__ void __launch_bounds__(768) gemm_dacc_kernel(GemmArgs g) {
       const int row0 = min(tm_ * BM + (pp & 1) * HM, g.M - 1);
       char* dst = smem + SIDE_BASE + (pp & 1) * 2048 + pw * 512;
       const unsigned col = (unsigned)(tn_ * BN + pw * WTN) * 4u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsBias, (lds_void_pw*)dst, 4, (unsigned)lane * 4u, col, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsGate, (lds_void_pw*)(dst + 256), 4, (unsigned)lane * 4u,
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsBias, (lds_void*)dst, 4, (unsigned)lane * 4u, col, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsGate, (lds_void*)(dst + 256), 4, (unsigned)lane * 4u,
                                                (unsigned)(row0 / g.rows_per_sample) * (unsigned)g.gate_stride * 4u + col, 0, 0);
     };
     const int U = NP * nk;

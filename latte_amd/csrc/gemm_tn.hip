@@ -19,12 +19,6 @@
 namespace latte {
 namespace {
 
-typedef __attribute__((__vector_size__(4 * sizeof(short)))) short i16v4t;
-__device__ __forceinline__ u32x2 tr16t(const char* p) {
-  i16v4t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16v4t*)p);
-  return __builtin_bit_cast(u32x2, v);
-}
-
 constexpr int TN_PITCH = 288;
 
 struct TnArgs {
@@ -105,8 +99,8 @@ __global__ void __launch_bounds__(WN * 128) gemm_tn_kernel(TnArgs g) {
       for (int c = 0; c < 4; ++c) {
         const char* pa = a + rrow * PITCH_A + rcol + (wn * 64 + c * 16) * 2;
         const char* pb = b + rrow * TN_PITCH + rcol + (wk * 64 + c * 16) * 2;
-        const u32x2 alo = tr16t(pa), ahi = tr16t(pa + 16 * PITCH_A);
-        const u32x2 blo = tr16t(pb), bhi = tr16t(pb + 16 * TN_PITCH);
+        const u32x2 alo = lds_tr16(pa), ahi = lds_tr16(pa + 16 * PITCH_A);
+        const u32x2 blo = lds_tr16(pb), bhi = lds_tr16(pb + 16 * TN_PITCH);
         nf[c] = (u32x4){alo[0], alo[1], ahi[0], ahi[1]};
         kf[c] = (u32x4){blo[0], blo[1], bhi[0], bhi[1]};
       }
@@ -146,21 +140,8 @@ __global__ void __launch_bounds__(WN * 128) gemm_tn_kernel(TnArgs g) {
 // Group g's waves stage their own dY half (4 instructions per wave and stage), group 0's also the X tile (8): the DMA split and
 // every hand-off are those of gemm_pp_kernel.  Requires M % 64 == 0 (no ragged contraction rows), N % 128 == 0, K % 128 == 0;
 // a half-image beyond N / K is not staged and its outputs are not stored.
-// Transpose read as inline assembly for the DMA-staged kernel: hipcc puts `s_waitcnt vmcnt(0)` in front of the BUILTIN whenever an
-// LDS DMA is in flight (it treats the pending DMA as a store the read may alias), which drained the next tiles' DMA at the top of
-// every K step (5.4 k clocks per step instead of ~3 k).  The asm form is invisible to that bookkeeping; its completion is waited
-// for by the kernel's own `s_waitcnt lgkmcnt(0)` + barrier before the MFMAs (cdna_hip_programming.md section 5.7, form (iii)).
-template <int OFF>
-__device__ __forceinline__ u32x2 tr16_asm(unsigned lds_addr) {
-  u32x2 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(lds_addr), "i"(OFF));
-  return v;
-}
-typedef __attribute__((address_space(3))) void lds_void_tn;
-__device__ __forceinline__ void dma16tn(__amdgpu_buffer_rsrc_t rs, char* lds_wave_base, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_tn*)lds_wave_base, 16, voff, soff, 0, 0);
-}
-
+// The transpose reads are the inline-assembly form (mfma_util.h: lds_tr16_asm): the wait that hipcc puts in front of the builtin
+// drained the next tiles' DMA at the top of every K step (5.4 k clocks per step instead of ~3 k).
 // COLSUM (round 6b): the bias gradient db[n] = sum_m dY[m, n] rides on the launch -- the dY fragments of a K step are in registers
 // anyway (lane (fl, gq) holds column 16 i + fl, rows 32 ks + 4 gq + {0..3, 16..19}), so wave 0 of each group in the k-tile-0
 // workgroups adds its 8 halves per fragment with four v_dot2c_f32_f16 against (1, 1) (fp32 accumulate) between the MFMAs; 8 extra
@@ -168,13 +149,11 @@ __device__ __forceinline__ void dma16tn(__amdgpu_buffer_rsrc_t rs, char* lds_wav
 template <int DT>
 __device__ __forceinline__ float dot2_ones(unsigned int w, float acc) {
   if constexpr (DT == LATTE_DTYPE_BF16) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 b2t;
-    const b2t one = {(__bf16)1.0f, (__bf16)1.0f};
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(b2t, w), one, acc, false);
+    const bf16x2 one = {(__bf16)1.0f, (__bf16)1.0f};
+    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, w), one, acc, false);
   } else {
-    typedef __attribute__((ext_vector_type(2))) _Float16 h2t;
-    const h2t one = {(_Float16)1.0f, (_Float16)1.0f};
-    return __builtin_amdgcn_fdot2(__builtin_bit_cast(h2t, w), one, acc, false);
+    const f16x2 one = {(_Float16)1.0f, (_Float16)1.0f};
+    return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, w), one, acc, false);
   }
 }
 template <int DT, bool COLSUM>
@@ -221,16 +200,16 @@ __global__ void __launch_bounds__(512) gemm_tn8_kernel(TnArgs g) {
     char* dst = smem + stg * STG + grp * HALF + wk * 1024;
     const unsigned so = (unsigned)(m_begin + kt * 64 + wk * 4) * ldy + (unsigned)(n0 + grp * 128) * 2u;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) dma16tn(rsY, dst + j * 4096, voy_w, so + (unsigned)(16 * j) * ldy);
+    for (int j = 0; j < 4; ++j) bload_lds16(rsY, dst + j * 4096, voy_w, so + (unsigned)(16 * j) * ldy);
   };
   auto dma_x = [&](int kt, int stg) {       // both X halves of K tile kt (group 0's waves)
     char* dst = smem + stg * STG + 2 * HALF + wk * 1024;
     const unsigned so = (unsigned)(m_begin + kt * 64 + wk * 4) * ldx + (unsigned)k0 * 2u;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) dma16tn(rsX, dst + j * 4096, vox_w, so + (unsigned)(16 * j) * ldx);
+    for (int j = 0; j < 4; ++j) bload_lds16(rsX, dst + j * 4096, vox_w, so + (unsigned)(16 * j) * ldx);
     if (x1_ok) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) dma16tn(rsX, dst + HALF + j * 4096, vox_w, so + 256u + (unsigned)(16 * j) * ldx);
+      for (int j = 0; j < 4; ++j) bload_lds16(rsX, dst + HALF + j * 4096, vox_w, so + 256u + (unsigned)(16 * j) * ldx);
     }
   };
 
@@ -269,14 +248,14 @@ __global__ void __launch_bounds__(512) gemm_tn8_kernel(TnArgs g) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const unsigned pb = sb + (unsigned)(xb + (lane_base ^ ((xc0 + c) << 5)));
-      const u32x2 l0 = tr16_asm<0>(pb), h0 = tr16_asm<4096>(pb), l1 = tr16_asm<8192>(pb), h1 = tr16_asm<12288>(pb);
+      const u32x2 l0 = lds_tr16_asm<0>(pb), h0 = lds_tr16_asm<4096>(pb), l1 = lds_tr16_asm<8192>(pb), h1 = lds_tr16_asm<12288>(pb);
       kf[0][c] = (u32x4){l0[0], l0[1], h0[0], h0[1]};
       kf[1][c] = (u32x4){l1[0], l1[1], h1[0], h1[1]};
     }
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       const unsigned pa = sb + (unsigned)(yb + (lane_base ^ (c << 5)));
-      const u32x2 l0 = tr16_asm<0>(pa), h0 = tr16_asm<4096>(pa), l1 = tr16_asm<8192>(pa), h1 = tr16_asm<12288>(pa);
+      const u32x2 l0 = lds_tr16_asm<0>(pa), h0 = lds_tr16_asm<4096>(pa), l1 = lds_tr16_asm<8192>(pa), h1 = lds_tr16_asm<12288>(pa);
       nf[0][c] = (u32x4){l0[0], l0[1], h0[0], h0[1]};
       nf[1][c] = (u32x4){l1[0], l1[1], h1[0], h1[1]};
     }

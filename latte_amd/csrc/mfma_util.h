@@ -1,17 +1,22 @@
-// Device helpers shared by the MFMA kernels (gemm.hip, vae.hip): fragment types, the 16x16x32 MFMA wrapper,
-// half packing, LDS DMA and the XCD-aware tile order.  gfx950 only.
+// Device helpers shared by every .hip file that builds or stores MFMA fragments: the vector types, the 16x16x32 and 16x16x16 MFMA
+// wrappers, half packing and the split operands, the LDS transpose reads, the global / buffer -> LDS DMA, the per-sequence row base
+// of the attention kernels and the XCD-aware tile order.  Everything else that is shared lives in device_util.h.  gfx950 only.
 #pragma once
 #include "common.h"
+#include "device_util.h"
 
 namespace latte {
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
+typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
+// 16 x 16 output tile, K = 32: a lane supplies 8 halves of its row / column per operand
 template <int DT>
 __device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
   if constexpr (DT == LATTE_DTYPE_BF16)
@@ -19,15 +24,21 @@ __device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
   else
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
+// the same tile, K = 16: 4 halves per operand
+template <int DT>
+__device__ __forceinline__ f32x4 mfma16_k16(u32x2 a, u32x2 b, f32x4 c) {
+  if constexpr (DT == LATTE_DTYPE_BF16)
+    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4, a), __builtin_bit_cast(f16x4, b), c, 0, 0, 0);
+}
 
 template <int DT>
 __device__ __forceinline__ unsigned int pack2(float lo, float hi) {
   if constexpr (DT == LATTE_DTYPE_BF16) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
     bf16x2 v = {(__bf16)lo, (__bf16)hi};
     return __builtin_bit_cast(unsigned int, v);
   } else {
-    typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
     f16x2 v = {(_Float16)lo, (_Float16)hi};
     return __builtin_bit_cast(unsigned int, v);
   }
@@ -63,9 +74,42 @@ __device__ __forceinline__ unsigned int split8_f16(float v0, float v1, float v2,
   return (unsigned int)w;
 }
 
+// Hardware transpose read of 16-bit elements (the bit pattern is dtype-agnostic): lane i of a 16-lane group supplies the address of 4
+// d-values of key (i >> 2) of a ROW-MAJOR LDS image and receives the 4 keys of d-column i (attention.hip: attn_full_kernel).
+typedef __attribute__((__vector_size__(4 * sizeof(short)))) short i16v4;
+__device__ __forceinline__ u32x2 lds_tr16(const char* p) {
+  i16v4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16v4*)p);
+  return __builtin_bit_cast(u32x2, v);
+}
+// The same read as inline assembly, from a 32-bit LDS address or a pointer: hipcc puts `s_waitcnt vmcnt(0)` in front of the BUILTIN
+// whenever an LDS DMA is in flight (it treats the pending DMA as a store the read may alias).  The asm form is invisible to that
+// bookkeeping; completion is the caller's own s_waitcnt lgkmcnt(0) + sched_barrier (cdna_hip_programming.md section 5.7, form (iii)).
+template <int OFF>
+__device__ __forceinline__ u32x2 lds_tr16_asm(unsigned lds_addr) {
+  u32x2 v;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(lds_addr), "i"(OFF));
+  return v;
+}
+template <int OFF>
+__device__ __forceinline__ u32x2 lds_tr16_asm(const char* p) {
+  return lds_tr16_asm<OFF>((unsigned)(size_t)(const __attribute__((address_space(3))) char*)p);
+}
+
+// 16 bytes per lane, global / buffer memory -> LDS without a register stop (one instruction fills 1 KB behind lds_wave_base)
+typedef __attribute__((address_space(3))) void lds_void;
 __device__ __forceinline__ void glds16(const half_t* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (lds_void*)lds_wave_base, 16, 0, 0);
+}
+__device__ __forceinline__ void bload_lds16(__amdgpu_buffer_rsrc_t rs, char* lds_wave_base, unsigned voff, unsigned soff) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)lds_wave_base, 16, voff, soff, 0, 0);
+}
+
+// Attention kernels: the score of a masked key in the exp2-domain softmax, and the first row of sequence `seq` in the canonical
+// [B, F, T, D] token order (AttnArgs, AttnBwdArgs: U sequences per sample)
+constexpr float NEG_BIG = -1.0e30f;
+template <class Args>
+__device__ __forceinline__ int64_t seq_base_row(const Args& a, int seq) {
+  return (int64_t)(seq / a.U) * a.sample_stride + (int64_t)(seq % a.U) * a.seq_stride;
 }
 
 // XCD-aware bijective remap (blocks are dispatched round-robin over the 8 XCDs): give every XCD a

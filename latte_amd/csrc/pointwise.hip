@@ -7,79 +7,10 @@
 //  cfg_combine   : classifier-free guidance on the first 4 channels              latte.py:394-398
 //  sampler_update: p_mean_variance + p_sample / ddim_sample                      gaussian_diffusion.py:254-336,380-421,517-564
 #include "common.h"
+#include "mfma_util.h"
 
 namespace latte {
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-template <int DT>
-__device__ __forceinline__ unsigned int pack2(float lo, float hi) {
-  if constexpr (DT == LATTE_DTYPE_BF16) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-    bf16x2 v = {(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(unsigned int, v);
-  } else {
-    typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-    f16x2 v = {(_Float16)lo, (_Float16)hi};
-    return __builtin_bit_cast(unsigned int, v);
-  }
-}
-
-// split-operand pair (mfma_util.h: split2): hi = nearest half, lo = nearest half of the remainder
-template <int DT>
-__device__ __forceinline__ void split2(float v0, float v1, unsigned int& hi, unsigned int& lo) {
-  if constexpr (DT == LATTE_DTYPE_BF16) {
-    const __bf16 h0 = (__bf16)v0, h1 = (__bf16)v1;
-    hi = pack2<DT>((float)h0, (float)h1);
-    lo = pack2<DT>(v0 - (float)h0, v1 - (float)h1);
-  } else {
-    const _Float16 h0 = (_Float16)v0, h1 = (_Float16)v1;
-    hi = pack2<DT>((float)h0, (float)h1);
-    lo = pack2<DT>(v0 - (float)h0, v1 - (float)h1);
-  }
-}
-
-// fp8 remainder of a split operand (round 6, common.h: LO8_A_SHIFT): four values -> their nearest f16 (hi01 / hi23) and ONE word of
-// four OCP e4m3 codes of (v - hi) * 2^LO8_A_SHIFT, clamped to the format's +-448 (the conversion itself does not saturate) -- the
-// operand of the GEMMs' block-scaled correction pass (gemm_pw.hip), whose constant E8M0 scale multiplies the 2^-LO8_A_SHIFT back.
-__device__ __forceinline__ unsigned int split8_f16(float v0, float v1, float v2, float v3, unsigned int& hi01, unsigned int& hi23) {
-  const _Float16 h0 = (_Float16)v0, h1 = (_Float16)v1, h2 = (_Float16)v2, h3 = (_Float16)v3;
-  hi01 = pack2<LATTE_DTYPE_F16>((float)h0, (float)h1);
-  hi23 = pack2<LATTE_DTYPE_F16>((float)h2, (float)h3);
-  constexpr float S = (float)(1 << LO8_A_SHIFT);
-  auto cl = [](float r) { return __builtin_fminf(__builtin_fmaxf(r, -448.f), 448.f); };
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(cl((v0 - (float)h0) * S), cl((v1 - (float)h1) * S), 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(cl((v2 - (float)h2) * S), cl((v3 - (float)h3) * S), w, true);
-  return (unsigned int)w;
-}
-
-__device__ __forceinline__ float silu(float x) { return x / (1.0f + __expf(-x)); }
-
-// FP4 (e2m1) block quantisation with a power-of-two scale (round 6): the E8M0 exponent for a block whose largest magnitude is `amax`
-// -- ONE BELOW the smallest e with amax / 2^e <= 6 (the format's largest value): the top binade of the block saturates at 6 and everything
-// else gains a bit (remainders of N(0, 1)-like rows keep 1.7 - 2.2 % of their variance instead of 3 - 4.6 %, heavy-tailed rows 5.6 % instead
-// of 12 %: simulation in DESIGN.md section 2), clamped to the scale byte's range -- and four values -> one
-// half-word of four codes (element j in bits 4 j) by the hardware convert (round to nearest even, saturating at +-6).
-__device__ __forceinline__ int quant4_exponent(float amax) {
-  if (!(amax > 0.f)) return -127;
-  int ex;
-  const float m = __builtin_frexpf(amax * (1.0f / 6.0f), &ex);   // amax / 6 = m 2^ex, m in [0.5, 1)
-  const int e = (m == 0.5f ? ex - 1 : ex) - 1;
-  return e < -127 ? -127 : e > 127 ? 127 : e;
-}
-__device__ __forceinline__ unsigned int quant4_pk4(float v0, float v1, float v2, float v3, float scale_pow2) {
-  unsigned int w = 0;
-  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, v0, v1, scale_pow2, 0);
-  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, v2, v3, scale_pow2, 1);
-  return w & 0xffffu;
-}
-
-
 
 // ------------------------------------------------------------------------------------------------
 // One wave per token row; lane owns the 16-byte chunks {lane + 64 c} of the row (float4 loads, 8-byte half stores: the
@@ -147,8 +78,7 @@ __global__ void __launch_bounds__(256) ln_modulate_kernel(const float* __restric
     }
   }
   const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / D) + 1e-6f);
-  typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
-  u32x2_t* yr = (u32x2_t*)(y + (size_t)row * (SPLIT == 1 ? 2 * D : D));
+  u32x2* yr = (u32x2*)(y + (size_t)row * (SPLIT == 1 ? 2 * D : D));
   if constexpr (SPLIT == 3) {
     // f16 + FP4 remainder with one E8M0 scale per ROW (GemmArgs::A4 / A4s): y8 = [M, lo4_pitch(D)] bytes of e2m1 codes, y4s = [M] scale bytes
     float lo[NQ][4];
@@ -162,7 +92,7 @@ __global__ void __launch_bounds__(256) ln_modulate_kernel(const float* __restric
         const float o2 = (v[c].z - mean) * rstd * (1.0f + b.z) + a.z;
         const float o3 = (v[c].w - mean) * rstd * (1.0f + b.w) + a.w;
         const _Float16 h0 = (_Float16)o0, h1 = (_Float16)o1, h2 = (_Float16)o2, h3 = (_Float16)o3;
-        yr[c * 64 + lane] = (u32x2_t){pack2<LATTE_DTYPE_F16>((float)h0, (float)h1), pack2<LATTE_DTYPE_F16>((float)h2, (float)h3)};
+        yr[c * 64 + lane] = (u32x2){pack2<LATTE_DTYPE_F16>((float)h0, (float)h1), pack2<LATTE_DTYPE_F16>((float)h2, (float)h3)};
         lo[c][0] = o0 - (float)h0; lo[c][1] = o1 - (float)h1; lo[c][2] = o2 - (float)h2; lo[c][3] = o3 - (float)h3;
         amax = fmaxf(amax, fmaxf(fmaxf(fabsf(lo[c][0]), fabsf(lo[c][1])), fmaxf(fabsf(lo[c][2]), fabsf(lo[c][3]))));
       } else {
@@ -192,16 +122,16 @@ __global__ void __launch_bounds__(256) ln_modulate_kernel(const float* __restric
         unsigned int h0_, l0_, h1_, l1_;
         split2<DT>(o0, o1, h0_, l0_);
         split2<DT>(o2, o3, h1_, l1_);
-        const u32x2_t hi = {h0_, h1_}, lo = {l0_, l1_};
+        const u32x2 hi = {h0_, h1_}, lo = {l0_, l1_};
         yr[c * 64 + lane] = hi;
         yr[NT + c * 64 + lane] = lo;     // + D halves = NT 8-byte chunks
       } else if constexpr (SPLIT == 2) {
         unsigned int h0_, h1_;
         const unsigned int l8 = split8_f16(o0, o1, o2, o3, h0_, h1_);
-        yr[c * 64 + lane] = (u32x2_t){h0_, h1_};
+        yr[c * 64 + lane] = (u32x2){h0_, h1_};
         ((unsigned int*)(y8 + (size_t)row * D))[c * 64 + lane] = l8;
       } else {
-        yr[c * 64 + lane] = (u32x2_t){pack2<DT>(o0, o1), pack2<DT>(o2, o3)};
+        yr[c * 64 + lane] = (u32x2){pack2<DT>(o0, o1), pack2<DT>(o2, o3)};
       }
     }
   }
@@ -805,8 +735,7 @@ __global__ void __launch_bounds__(256) pack_w4_kernel(const half_t* __restrict__
   float amax = 0.f;
   for (int k = lane * 4; k < K; k += 256) {
     const uint2 q = *(const uint2*)(r + k);
-    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_;
-    const f16x4_ hv = __builtin_bit_cast(f16x4_, q);
+    const f16x4 hv = __builtin_bit_cast(f16x4, q);
     const float a = (float)hv[0], b = (float)hv[1], c = (float)hv[2], d = (float)hv[3];
     amax = fmaxf(amax, fmaxf(fmaxf(fabsf(a), fabsf(b)), fmaxf(fabsf(c), fabsf(d))));
   }
@@ -819,8 +748,7 @@ __global__ void __launch_bounds__(256) pack_w4_kernel(const half_t* __restrict__
     unsigned short code = 0;
     if (k < K) {
       const uint2 q = *(const uint2*)(r + k);
-      typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_;
-      const f16x4_ hv = __builtin_bit_cast(f16x4_, q);
+      const f16x4 hv = __builtin_bit_cast(f16x4, q);
       const float a = (float)hv[0], b = (float)hv[1], c = (float)hv[2], d = (float)hv[3];
       code = (unsigned short)quant4_pk4(a, b, c, d, sc2);
     }
@@ -831,11 +759,10 @@ __global__ void __launch_bounds__(256) pack_w4_kernel(const half_t* __restrict__
 
 // W8 of the GEMMs' fp8 correction pass (common.h: LO8_W_SHIFT): four f16 weights -> four OCP e4m3 codes of w * 2^LO8_W_SHIFT, clamped
 __global__ void pack_w8_kernel(const half_t* __restrict__ in, unsigned char* __restrict__ out, size_t n4) {
-  typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
   constexpr float S = (float)(1 << LO8_W_SHIFT);
   auto cl = [](float r) { return __builtin_fminf(__builtin_fmaxf(r, -448.f), 448.f); };
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    const u32x2_t v = ((const u32x2_t*)in)[i];
+    const u32x2 v = ((const u32x2*)in)[i];
     // (scalar copies first: bit-casting the vector elements directly is miscompiled into re-using element 0, gemm.hip)
     const unsigned int lo = v[0], hi = v[1];
     const float w0 = (float)__builtin_bit_cast(_Float16, (unsigned short)(lo & 0xffffu)), w1 = (float)__builtin_bit_cast(_Float16, (unsigned short)(lo >> 16));

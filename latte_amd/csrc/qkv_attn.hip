@@ -33,40 +33,6 @@
 namespace latte {
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_t;
-typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((__vector_size__(4 * sizeof(short)))) short i16v4_t;
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-constexpr float NEG_BIG_F = -1.0e30f;
-
-template <int DT>
-__device__ __forceinline__ f32x4 mfma_k16h(u32x2 a, u32x2 b, f32x4 c) {
-  if constexpr (DT == LATTE_DTYPE_BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4_t, a), __builtin_bit_cast(s16x4_t, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4_t, a), __builtin_bit_cast(f16x4_t, b), c, 0, 0, 0);
-}
-// hardware transpose read (see attention.hip): lane i of a 16-lane group supplies the address of 4 d-values of key (i >> 2) of a
-// ROW-MAJOR image and receives the 4 keys of d-column i
-__device__ __forceinline__ u32x2 tr16(const char* p) {
-  i16v4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16v4_t*)p);
-  return __builtin_bit_cast(u32x2, v);
-}
-// The same read as inline assembly: in front of the BUILTIN hipcc waits (s_waitcnt vmcnt) for any LDS DMA in flight, which in the
-// temporal attention phase is the next unit's operand fill issued a few instructions earlier.  Completion: the caller's own
-// s_waitcnt lgkmcnt(0) + sched_barrier (cdna_hip_programming.md section 5.7, form (iii)).
-template <int OFF>
-__device__ __forceinline__ u32x2 tr16_asm(const char* p) {
-  u32x2 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"((unsigned)(size_t)(const __attribute__((address_space(3))) char*)p), "i"(OFF));
-  return v;
-}
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, char* lds_wave_base, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)lds_wave_base, 16, voff, soff, 0, 0);
-}
-
 // Row pitches of the images: Q and K 144 B (9 x 16 B: b128 fragment reads of 16 consecutive rows spread over all banks, and the
 // 8-byte image writes of the 16 rows of an accumulator fragment are 2-way instead of 4-way conflicted), V 160 B (the pitch at which
 // the transpose reads of 8 rows x 32 B tile the 64 banks).  At hd = 72 a Q / K row has no pad: chunk 9 of the padded contraction
@@ -190,12 +156,12 @@ __global__ void __launch_bounds__(512) qkv_attn_kernel(QkvAttnArgs a) {
     char* sA = smem + (stg ? A1_OFF : A0_OFF) + (grp * 16 + w4) * 1024;
     const unsigned so = u.a_so0 + (unsigned)kt * 128u;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) dma16(rsA, sA + j * 4096, voff_a, so + (unsigned)j * a_jstep);
+    for (int j = 0; j < 4; ++j) bload_lds16(rsA, sA + j * 4096, voff_a, so + (unsigned)j * a_jstep);
   };
   auto dma_b_all = [&](const Unit& u, int kt, int stg) {
     char* sB = smem + (stg ? B1_OFF : B0_OFF) + w4 * 1024;
 #pragma unroll
-    for (int j = 0; j < B_MAIN; ++j) dma16(rsB, sB + j * 4096, voff_b, u.b_so[j] + (unsigned)kt * 128u);
+    for (int j = 0; j < B_MAIN; ++j) bload_lds16(rsB, sB + j * 4096, voff_b, u.b_so[j] + (unsigned)kt * 128u);
   };
   // K tile 0 of a unit into stage 0.  Nothing of the ping-pong stagger applies here (the fill is drained by every wave before
   // the barrier that opens the unit), so the W tile's groups are spread over all 8 waves: gi = wave + 8 j (same swizzle parity
@@ -208,7 +174,7 @@ __global__ void __launch_bounds__(512) qkv_attn_kernel(QkvAttnArgs a) {
       const int gi = wave + 8 * j;
       if (gi < NPAD / 8) {
         const int mat = gi / GPM, wi = gi - mat * GPM;
-        dma16(rsB, sB + j * 8192, voff_b, (unsigned)((mat < 3 ? mat : 0) * D + u.head * HD + wi * 8) * row_bytes);
+        bload_lds16(rsB, sB + j * 8192, voff_b, (unsigned)((mat < 3 ? mat : 0) * D + u.head * HD + wi * 8) * row_bytes);
       }
     }
   };
@@ -385,7 +351,7 @@ __global__ void __launch_bounds__(512) qkv_attn_kernel(QkvAttnArgs a) {
         float inv[NG];
 #pragma unroll
         for (int gq = 0; gq < NG; ++gq) {
-          float mx = NEG_BIG_F;
+          float mx = NEG_BIG;
 #pragma unroll
           for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
@@ -426,8 +392,8 @@ __global__ void __launch_bounds__(512) qkv_attn_kernel(QkvAttnArgs a) {
         auto load_v = [&](int ks2, u32x4 (&dst)[DF]) {
 #pragma unroll
           for (int d = 0; d < DF; ++d) {
-            const u32x2 lo = tr16(vbase + (32 * ks2) * RPV + d * 32);
-            const u32x2 hi = tr16(vbase + (32 * ks2 + 16) * RPV + d * 32);
+            const u32x2 lo = lds_tr16(vbase + (32 * ks2) * RPV + d * 32);
+            const u32x2 hi = lds_tr16(vbase + (32 * ks2 + 16) * RPV + d * 32);
             dst[d] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
           }
         };
@@ -509,7 +475,7 @@ __global__ void __launch_bounds__(512) qkv_attn_kernel(QkvAttnArgs a) {
       for (int s2 = 0; s2 < 2; ++s2) {
         const int p = wave * 2 + s2;
         f32x4 st = st2[s2];
-        float mx = NEG_BIG_F;
+        float mx = NEG_BIG;
 #pragma unroll
         for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[r]);
         mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
@@ -529,7 +495,7 @@ __global__ void __launch_bounds__(512) qkv_attn_kernel(QkvAttnArgs a) {
         u32x2 vf[5];
         {
           const char* vp = v_img + (16 * p + 4 * g + (fr >> 2)) * RPV + (fr & 3) * 8;
-          vf[0] = tr16_asm<0>(vp); vf[1] = tr16_asm<32>(vp); vf[2] = tr16_asm<64>(vp); vf[3] = tr16_asm<96>(vp); vf[4] = tr16_asm<128>(vp);
+          vf[0] = lds_tr16_asm<0>(vp); vf[1] = lds_tr16_asm<32>(vp); vf[2] = lds_tr16_asm<64>(vp); vf[3] = lds_tr16_asm<96>(vp); vf[4] = lds_tr16_asm<128>(vp);
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -537,7 +503,7 @@ __global__ void __launch_bounds__(512) qkv_attn_kernel(QkvAttnArgs a) {
 #pragma unroll
         for (int d = 0; d < DF; ++d) {
           f32x4 oacc = {0.f, 0.f, 0.f, 0.f};
-          oacc = mfma_k16h<DT>(vf[d], pb, oacc);                               // O^T[d = 16 d + 4g + r][q = fr]
+          oacc = mfma16_k16<DT>(vf[d], pb, oacc);                               // O^T[d = 16 d + 4g + r][q = fr]
           const int dd = 16 * d + 4 * g;
           l8w[d] = 0u;
           if (dd < HD) {

@@ -21,7 +21,6 @@ __device__ __forceinline__ void split_lo(float v, _Float16& hi, _Float16& lo) {
   const float r = (v - (float)hi) * T5_LO_SCALE;
   lo = (_Float16)__builtin_fminf(__builtin_fmaxf(r, -F16_MAX), F16_MAX);
 }
-__device__ __forceinline__ unsigned short h16_bits(_Float16 h) { return __builtin_bit_cast(unsigned short, h); }
 
 // ---- embedding gather: x[m, :] = table[ids[m], :] (no scaling); an id outside the vocabulary reads row 0
 __global__ void t5_embed_kernel(const int64_t* __restrict__ ids, const float* __restrict__ table, float* __restrict__ x, int D, int vocab) {

@@ -19,38 +19,10 @@
 #include <cmath>
 
 #include "common.h"
+#include "mfma_util.h"
 
 namespace latte {
 namespace {
-
-__device__ __forceinline__ float wave_sum_t(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-template <int DT>
-__device__ __forceinline__ unsigned int pack2t(float lo, float hi) {
-  if constexpr (DT == LATTE_DTYPE_BF16) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-    bf16x2 v = {(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(unsigned int, v);
-  } else {
-    typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-    f16x2 v = {(_Float16)lo, (_Float16)hi};
-    return __builtin_bit_cast(unsigned int, v);
-  }
-}
-template <int DT>
-__device__ __forceinline__ float h2f(unsigned short h) {
-  if constexpr (DT == LATTE_DTYPE_BF16) return __builtin_bit_cast(float, (unsigned int)h << 16);
-  else return (float)__builtin_bit_cast(_Float16, h);
-}
-template <int DT>
-__device__ __forceinline__ void unpack4(const uint2 p, float& a, float& b, float& c, float& d) {
-  a = h2f<DT>((unsigned short)(p.x & 0xffffu)); b = h2f<DT>((unsigned short)(p.x >> 16));
-  c = h2f<DT>((unsigned short)(p.y & 0xffffu)); d = h2f<DT>((unsigned short)(p.y >> 16));
-}
 
 constexpr int NQ_MAX = 5;   // float4 chunk groups per lane: D <= 1280
 
@@ -116,7 +88,7 @@ __global__ void __launch_bounds__(256) gated_add_ln_kernel(const float* __restri
   float s = 0.f;
 #pragma unroll
   for (int c = 0; c < NQ_MAX; ++c) s += (v[c].x + v[c].y) + (v[c].z + v[c].w);     // absent chunks hold zeros
-  const float mean = wave_sum_t(s) * invD;
+  const float mean = wave_sum(s) * invD;
   float q = 0.f;
 #pragma unroll
   for (int c = 0; c < NQ_MAX; ++c) {
@@ -125,7 +97,7 @@ __global__ void __launch_bounds__(256) gated_add_ln_kernel(const float* __restri
       q += (a * a + b * b) + (d * d + e * e);
     }
   }
-  const float rstd = 1.0f / sqrtf(wave_sum_t(q) * invD + 1e-6f);
+  const float rstd = 1.0f / sqrtf(wave_sum(q) * invD + 1e-6f);
 #pragma unroll
   for (int c = 0; c < NQ_MAX; ++c) {
     const int ch = c * 64 + lane;
@@ -136,8 +108,8 @@ __global__ void __launch_bounds__(256) gated_add_ln_kernel(const float* __restri
       const float o2 = (v[c].z - mean) * rstd * (1.0f + b.z) + a.z;
       const float o3 = (v[c].w - mean) * rstd * (1.0f + b.w) + a.w;
       uint2 o;
-      o.x = pack2t<DT>(o0, o1);
-      o.y = pack2t<DT>(o2, o3);
+      o.x = pack2<DT>(o0, o1);
+      o.y = pack2<DT>(o2, o3);
       ((uint2*)xn)[ro + ch] = o;
     }
   }
@@ -176,8 +148,8 @@ __global__ void __launch_bounds__(256) gate_bwd_kernel(const float* __restrict__
         const float4 gd = make_float4(g[c].x * d.x, g[c].y * d.y, g[c].z * d.z, g[c].w * d.w);
         if constexpr (BIAS) { accb[c].x += gd.x; accb[c].y += gd.y; accb[c].z += gd.z; accb[c].w += gd.w; }
         uint2 o;
-        o.x = pack2t<DT>(gd.x, gd.y);
-        o.y = pack2t<DT>(gd.z, gd.w);
+        o.x = pack2<DT>(gd.x, gd.y);
+        o.y = pack2<DT>(gd.z, gd.w);
         ((uint2*)dy)[ro + ch] = o;
       }
     }
@@ -300,7 +272,7 @@ __global__ void __launch_bounds__(256, NQ <= 3 ? 3 : 2) ln_bwd_kernel(const half
         }
       }
     }
-    const float mean = wave_sum_t(s) * invD;
+    const float mean = wave_sum(s) * invD;
     float q = 0.f;
 #pragma unroll
     for (int c = 0; c < NQ; ++c) {
@@ -309,7 +281,7 @@ __global__ void __launch_bounds__(256, NQ <= 3 ? 3 : 2) ln_bwd_kernel(const half
         q += (v[c].x * v[c].x + v[c].y * v[c].y) + (v[c].z * v[c].z + v[c].w * v[c].w);
       }
     }
-    const float rstd = 1.0f / sqrtf(wave_sum_t(q) * invD + 1e-6f);
+    const float rstd = 1.0f / sqrtf(wave_sum(q) * invD + 1e-6f);
     float m1 = 0.f, m2 = 0.f;
 #pragma unroll
     for (int c = 0; c < NQ; ++c) {
@@ -326,8 +298,8 @@ __global__ void __launch_bounds__(256, NQ <= 3 ? 3 : 2) ln_bwd_kernel(const half
         m2 += (g[c].x * v[c].x + g[c].y * v[c].y) + (g[c].z * v[c].z + g[c].w * v[c].w);
       }
     }
-    m1 = wave_sum_t(m1) * invD;
-    m2 = wave_sum_t(m2) * invD;
+    m1 = wave_sum(m1) * invD;
+    m2 = wave_sum(m2) * invD;
 #pragma unroll
     for (int c = 0; c < NQ; ++c) {
       const int ch = c * 64 + lane;
@@ -346,8 +318,8 @@ __global__ void __launch_bounds__(256, NQ <= 3 ? 3 : 2) ln_bwd_kernel(const half
           const float4 gd = make_float4(g2[c].x * o.x, g2[c].y * o.y, g2[c].z * o.z, g2[c].w * o.w);
           a_b[c].x += gd.x; a_b[c].y += gd.y; a_b[c].z += gd.z; a_b[c].w += gd.w;
           uint2 w;
-          w.x = pack2t<DT>(gd.x, gd.y);
-          w.y = pack2t<DT>(gd.z, gd.w);
+          w.x = pack2<DT>(gd.x, gd.y);
+          w.y = pack2<DT>(gd.z, gd.w);
           ((uint2*)dy2)[ro + ch] = w;
         }
       }
@@ -403,10 +375,6 @@ __global__ void __launch_bounds__(256, NQ <= 3 ? 3 : 2) ln_bwd_kernel(const half
 
 // ---------------------------------------------------------------------------------------------- GELU(tanh)
 // gelu(x) = x s(x), s = sigmoid(2u), u = sqrt(2/pi)(x + 0.044715 x^3);  gelu'(x) = s + x s (1 - s) 2 u',  u' = sqrt(2/pi)(1 + 3*0.044715 x^2)
-__device__ __forceinline__ float gelu_sig(float x) {
-  const float p = __builtin_fmaf(x * x, -0.10294324f, -2.3022082f);     // -2 log2(e) sqrt(2/pi) (1 + 0.044715 x^2)
-  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(p * x));
-}
 template <int DT, bool BWD>
 __global__ void __launch_bounds__(256) gelu_kernel(const half_t* __restrict__ u, const half_t* __restrict__ dh, half_t* __restrict__ out,
                                                    size_t n4) {
@@ -428,8 +396,8 @@ __global__ void __launch_bounds__(256) gelu_kernel(const half_t* __restrict__ u,
       for (int k = 0; k < 4; ++k) o[k] = x[k] * gelu_sig(x[k]);
     }
     uint2 p;
-    p.x = pack2t<DT>(o[0], o[1]);
-    p.y = pack2t<DT>(o[2], o[3]);
+    p.x = pack2<DT>(o[0], o[1]);
+    p.y = pack2<DT>(o[2], o[3]);
     ((uint2*)out)[i] = p;
   }
 }
@@ -522,7 +490,7 @@ __global__ void __launch_bounds__(256) pack_weight_kernel(const float* __restric
     if (n0 + r < N && k0 + tx < K) v = w[(size_t)(n0 + r) * K + k0 + tx];
     tile[r][tx] = v;
     if (wn && n0 + r < N && k0 + tx < K) {
-      const unsigned int p = pack2t<DT>(v, 0.f);
+      const unsigned int p = pack2<DT>(v, 0.f);
       wn[(size_t)(n0 + r) * K + k0 + tx] = (half_t)(p & 0xffffu);
     }
   }
@@ -530,7 +498,7 @@ __global__ void __launch_bounds__(256) pack_weight_kernel(const float* __restric
   if (wt) {
     for (int r = ty; r < 32; r += 8) {
       if (k0 + r < K && n0 + tx < N) {
-        const unsigned int p = pack2t<DT>(tile[tx][r], 0.f);
+        const unsigned int p = pack2<DT>(tile[tx][r], 0.f);
         wt[(size_t)(k0 + r) * N + n0 + tx] = (half_t)(p & 0xffffu);
       }
     }

@@ -18,47 +18,11 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "mfma_util.h"
 
 namespace latte {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8b;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8b;
-typedef __attribute__((ext_vector_type(4))) float f32x4b;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4b;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2b;
-
-template <int DT>
-__device__ __forceinline__ f32x4b mfma32(u32x4b a, u32x4b b, f32x4b c) {
-  if constexpr (DT == LATTE_DTYPE_BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8b, a), __builtin_bit_cast(bf16x8b, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8b, a), __builtin_bit_cast(f16x8b, b), c, 0, 0, 0);
-}
-template <int DT>
-__device__ __forceinline__ unsigned int pk2(float lo, float hi) {
-  if constexpr (DT == LATTE_DTYPE_BF16) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-    bf16x2 v = {(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(unsigned int, v);
-  } else {
-    typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-    f16x2 v = {(_Float16)lo, (_Float16)hi};
-    return __builtin_bit_cast(unsigned int, v);
-  }
-}
-template <int DT>
-__device__ __forceinline__ float hf(unsigned short h) {
-  if constexpr (DT == LATTE_DTYPE_BF16) return __builtin_bit_cast(float, (unsigned int)h << 16);
-  else return (float)__builtin_bit_cast(_Float16, h);
-}
-typedef __attribute__((__vector_size__(4 * sizeof(short)))) short i16v4b;
-__device__ __forceinline__ u32x2b tr16(const char* p) {
-  i16v4b v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16v4b*)p);
-  return __builtin_bit_cast(u32x2b, v);
-}
-
-constexpr float NEG_BIG_B = -1.0e30f;
 constexpr int RPB = 160;   // row pitch of every LDS image (bytes): conflict-free for the b128 row reads and the transpose reads
 
 struct AttnBwdArgs {
@@ -73,10 +37,6 @@ struct AttnBwdArgs {
   int force_tiles;     // test / measurement hook: 1 = the two tile kernels also for L <= 16, 2 = also for 64 < L <= 256 (no resident images)
 };
 
-__device__ __forceinline__ int64_t seq_base(const AttnBwdArgs& a, int seq) {
-  return (int64_t)(seq / a.U) * a.sample_stride + (int64_t)(seq % a.U) * a.seq_stride;
-}
-
 // stage 64 rows (tile `tile` of a sequence) of a [rows, ld] matrix, columns [col0, col0 + HD), into a row-major LDS image
 template <int HD, int NT = 256>
 __device__ __forceinline__ void stage_tile(char* img, const half_t* src, size_t ld, int col0, int64_t base, int64_t row_stride, int tile,
@@ -85,7 +45,7 @@ __device__ __forceinline__ void stage_tile(char* img, const half_t* src, size_t 
   for (int id = tid; id < 64 * NCH; id += NT) {
     const int r = id / NCH, ch = id % NCH;
     const int rl = min(tile * 64 + r, L - 1);
-    *(u32x4b*)(img + r * RPB + ch * 16) = *(const u32x4b*)(src + (size_t)(base + (int64_t)rl * row_stride) * ld + col0 + ch * 8);
+    *(u32x4*)(img + r * RPB + ch * 16) = *(const u32x4*)(src + (size_t)(base + (int64_t)rl * row_stride) * ld + col0 + ch * 8);
   }
 }
 
@@ -95,7 +55,7 @@ template <int HD, int NT>
 __device__ __forceinline__ void stage_pair_all(char* img_a, const half_t* src_a, size_t ld_a, int col_a, char* img_b, const half_t* src_b,
                                                size_t ld_b, int col_b, int64_t base, int64_t row_stride, int tiles, int L, int tid) {
   constexpr int NCH = HD / 8, IT = (64 * NCH + NT - 1) / NT, TIMG = 64 * RPB;
-  u32x4b ra[4][IT], rb[4][IT];
+  u32x4 ra[4][IT], rb[4][IT];
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -104,8 +64,8 @@ __device__ __forceinline__ void stage_pair_all(char* img_a, const half_t* src_a,
       if (t < tiles && id < 64 * NCH) {
         const int r = id / NCH, ch = id % NCH;
         const int64_t row = base + (int64_t)min(t * 64 + r, L - 1) * row_stride;
-        ra[t][it] = *(const u32x4b*)(src_a + (size_t)row * ld_a + col_a + ch * 8);
-        rb[t][it] = *(const u32x4b*)(src_b + (size_t)row * ld_b + col_b + ch * 8);
+        ra[t][it] = *(const u32x4*)(src_a + (size_t)row * ld_a + col_a + ch * 8);
+        rb[t][it] = *(const u32x4*)(src_b + (size_t)row * ld_b + col_b + ch * 8);
       }
     }
 #pragma unroll
@@ -115,65 +75,65 @@ __device__ __forceinline__ void stage_pair_all(char* img_a, const half_t* src_a,
       const int id = tid + it * NT;
       if (t < tiles && id < 64 * NCH) {
         const int r = id / NCH, ch = id % NCH;
-        *(u32x4b*)(img_a + t * TIMG + r * RPB + ch * 16) = ra[t][it];
-        *(u32x4b*)(img_b + t * TIMG + r * RPB + ch * 16) = rb[t][it];
+        *(u32x4*)(img_a + t * TIMG + r * RPB + ch * 16) = ra[t][it];
+        *(u32x4*)(img_b + t * TIMG + r * RPB + ch * 16) = rb[t][it];
       }
     }
 }
 
 // T^T[tile row 16 j + 4 g + r][own row fl] for the 64 tile rows: st[j][r]
 template <int HD, int DT>
-__device__ __forceinline__ void score_product(const char* img, const u32x4b* own, f32x4b* st, int fl, int g) {
+__device__ __forceinline__ void score_product(const char* img, const u32x4* own, f32x4* st, int fl, int g) {
   constexpr int KS = (HD + 31) / 32, NCH = HD / 8;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    st[j] = (f32x4b){0.f, 0.f, 0.f, 0.f};
+    st[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int ch = g + 4 * ks;
-      u32x4b f = *(const u32x4b*)(img + (16 * j + fl) * RPB + ch * 16);
-      if (ch >= NCH) f = (u32x4b){0u, 0u, 0u, 0u};
-      st[j] = mfma32<DT>(f, own[ks], st[j]);
+      u32x4 f = *(const u32x4*)(img + (16 * j + fl) * RPB + ch * 16);
+      if (ch >= NCH) f = (u32x4){0u, 0u, 0u, 0u};
+      st[j] = mfma16<DT>(f, own[ks], st[j]);
     }
   }
 }
 // Out^T[d][own row] += sum over the 64 tile rows of img[row][d] * w[row][own row];  w = st-layout values
 template <int HD, int DT>
-__device__ __forceinline__ void value_product(const char* img, const f32x4b* w, f32x4b* out, int fl, int g) {
+__device__ __forceinline__ void value_product(const char* img, const f32x4* w, f32x4* out, int fl, int g) {
   constexpr int DF = (HD + 15) / 16;
 #pragma unroll
   for (int ks2 = 0; ks2 < 2; ++ks2) {
-    const u32x4b pb = {pk2<DT>(w[2 * ks2][0], w[2 * ks2][1]), pk2<DT>(w[2 * ks2][2], w[2 * ks2][3]),
-                       pk2<DT>(w[2 * ks2 + 1][0], w[2 * ks2 + 1][1]), pk2<DT>(w[2 * ks2 + 1][2], w[2 * ks2 + 1][3])};
+    const u32x4 pb = {pack2<DT>(w[2 * ks2][0], w[2 * ks2][1]), pack2<DT>(w[2 * ks2][2], w[2 * ks2][3]),
+                       pack2<DT>(w[2 * ks2 + 1][0], w[2 * ks2 + 1][1]), pack2<DT>(w[2 * ks2 + 1][2], w[2 * ks2 + 1][3])};
 #pragma unroll
     for (int d = 0; d < DF; ++d) {
       const char* vb = img + (32 * ks2 + 4 * g + (fl >> 2)) * RPB + (fl & 3) * 8 + d * 32;
-      const u32x2b lo = tr16(vb);
-      const u32x2b hi = tr16(vb + 16 * RPB);
-      out[d] = mfma32<DT>((u32x4b){lo[0], lo[1], hi[0], hi[1]}, pb, out[d]);
+      const u32x2 lo = lds_tr16(vb);
+      const u32x2 hi = lds_tr16(vb + 16 * RPB);
+      out[d] = mfma16<DT>((u32x4){lo[0], lo[1], hi[0], hi[1]}, pb, out[d]);
     }
   }
 }
 // own-row fragments of a [rows, ld] matrix: lane = (row fl, chunk g + 4 ks)
 template <int HD>
-__device__ __forceinline__ void load_own(u32x4b* f, const half_t* rowp, int g) {
+__device__ __forceinline__ void load_own(u32x4* f, const half_t* rowp, int g) {
   constexpr int KS = (HD + 31) / 32, NCH = HD / 8;
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
     const int ch = g + 4 * ks;
-    f[ks] = (u32x4b){0u, 0u, 0u, 0u};
-    if (ch < NCH) f[ks] = *(const u32x4b*)(rowp + ch * 8);
+    f[ks] = (u32x4){0u, 0u, 0u, 0u};
+    if (ch < NCH) f[ks] = *(const u32x4*)(rowp + ch * 8);
   }
 }
 template <int HD, int DT>
-__device__ __forceinline__ void store_own(half_t* rowp, const f32x4b* o, float mul, int g) {
+__device__ __forceinline__ void store_own(half_t* rowp, const f32x4* o, float mul, int g) {
   constexpr int DF = (HD + 15) / 16;
 #pragma unroll
   for (int d = 0; d < DF; ++d) {
     const int dd = 16 * d + 4 * g;
     if (dd < HD) {
-      const u32x2b p = {pk2<DT>(o[d][0] * mul, o[d][1] * mul), pk2<DT>(o[d][2] * mul, o[d][3] * mul)};
-      *(u32x2b*)(rowp + dd) = p;
+      const u32x2 p = {pack2<DT>(o[d][0] * mul, o[d][1] * mul), pack2<DT>(o[d][2] * mul, o[d][3] * mul)};
+      *(u32x2*)(rowp + dd) = p;
     }
   }
 }
@@ -191,12 +151,12 @@ __global__ void __launch_bounds__(256) attn_bwd_q_kernel(AttnBwdArgs a) {
   const int qt = blockIdx.x % tiles;
   const int head = (blockIdx.x / tiles) % a.heads;
   const int seq = blockIdx.x / (tiles * a.heads);
-  const int64_t base = seq_base(a, seq);
+  const int64_t base = seq_base_row(a, seq);
   const size_t ld3 = (size_t)3 * a.D;
   const int q_idx = qt * 64 + wave * 16 + fl;
   const int q_ld = min(q_idx, a.L - 1);
   const int64_t q_row = base + (int64_t)q_ld * a.row_stride;
-  u32x4b qf[KS], dof[KS];
+  u32x4 qf[KS], dof[KS];
   load_own<HD>(qf, a.qkv + (size_t)q_row * ld3 + head * HD, g);
   load_own<HD>(dof, a.dout + (size_t)q_row * a.D + head * HD, g);
   // D_q = dO . O over the head's columns: this lane's chunks, then the 4 lanes of the query
@@ -207,11 +167,11 @@ __global__ void __launch_bounds__(256) attn_bwd_q_kernel(AttnBwdArgs a) {
     for (int ks = 0; ks < KS; ++ks) {
       const int ch = g + 4 * ks;
       if (ch < NCH) {
-        const u32x4b ov = *(const u32x4b*)(orow + ch * 8);
+        const u32x4 ov = *(const u32x4*)(orow + ch * 8);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          dq_dot += hf<DT>((unsigned short)(ov[e] & 0xffffu)) * hf<DT>((unsigned short)(dof[ks][e] & 0xffffu));
-          dq_dot += hf<DT>((unsigned short)(ov[e] >> 16)) * hf<DT>((unsigned short)(dof[ks][e] >> 16));
+          dq_dot += h2f<DT>((unsigned short)(ov[e] & 0xffffu)) * h2f<DT>((unsigned short)(dof[ks][e] & 0xffffu));
+          dq_dot += h2f<DT>((unsigned short)(ov[e] >> 16)) * h2f<DT>((unsigned short)(dof[ks][e] >> 16));
         }
       }
     }
@@ -220,20 +180,20 @@ __global__ void __launch_bounds__(256) attn_bwd_q_kernel(AttnBwdArgs a) {
   }
   const float c = a.scale * 1.4426950408889634f;
   // ---- sweep 1: row maximum and sum (exp2 domain)
-  float m_run = NEG_BIG_B, l_run = 0.f;
+  float m_run = NEG_BIG, l_run = 0.f;
   for (int kt = 0; kt < tiles; ++kt) {
     __syncthreads();
     stage_tile<HD>(k_img, a.qkv, ld3, a.D + head * HD, base, a.row_stride, kt, a.L, tid);
     __syncthreads();
-    f32x4b st[4];
+    f32x4 st[4];
     score_product<HD, DT>(k_img, qf, st, fl, g);
-    float mx = NEG_BIG_B;
+    float mx = NEG_BIG;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = kt * 64 + 16 * j + 4 * g + r;
-        const float z = key < a.L ? st[j][r] * c : NEG_BIG_B;
+        const float z = key < a.L ? st[j][r] * c : NEG_BIG;
         st[j][r] = z;
         mx = fmaxf(mx, z);
       }
@@ -256,15 +216,15 @@ __global__ void __launch_bounds__(256) attn_bwd_q_kernel(AttnBwdArgs a) {
     sp[0] = m_run; sp[1] = inv_l; sp[2] = dq_dot;
   }
   // ---- sweep 2: dS and dQ
-  f32x4b acc[DF];
+  f32x4 acc[DF];
 #pragma unroll
-  for (int d = 0; d < DF; ++d) acc[d] = (f32x4b){0.f, 0.f, 0.f, 0.f};
+  for (int d = 0; d < DF; ++d) acc[d] = (f32x4){0.f, 0.f, 0.f, 0.f};
   for (int kt = 0; kt < tiles; ++kt) {
     __syncthreads();
     stage_tile<HD>(k_img, a.qkv, ld3, a.D + head * HD, base, a.row_stride, kt, a.L, tid);
     stage_tile<HD>(v_img, a.qkv, ld3, 2 * a.D + head * HD, base, a.row_stride, kt, a.L, tid);
     __syncthreads();
-    f32x4b st[4], dp[4];
+    f32x4 st[4], dp[4];
     score_product<HD, DT>(k_img, qf, st, fl, g);
     score_product<HD, DT>(v_img, dof, dp, fl, g);
 #pragma unroll
@@ -294,20 +254,20 @@ __global__ void __launch_bounds__(256) attn_bwd_kv_kernel(AttnBwdArgs a) {
   const int kt = blockIdx.x % tiles;
   const int head = (blockIdx.x / tiles) % a.heads;
   const int seq = blockIdx.x / (tiles * a.heads);
-  const int64_t base = seq_base(a, seq);
+  const int64_t base = seq_base_row(a, seq);
   const size_t ld3 = (size_t)3 * a.D;
   const int k_idx = kt * 64 + wave * 16 + fl;
   const int k_ld = min(k_idx, a.L - 1);
   const int64_t k_row = base + (int64_t)k_ld * a.row_stride;
-  u32x4b kf[KS], vf[KS];
+  u32x4 kf[KS], vf[KS];
   load_own<HD>(kf, a.qkv + (size_t)k_row * ld3 + a.D + head * HD, g);
   load_own<HD>(vf, a.qkv + (size_t)k_row * ld3 + 2 * a.D + head * HD, g);
   const float c = a.scale * 1.4426950408889634f;
-  f32x4b dv[DF], dk[DF];
+  f32x4 dv[DF], dk[DF];
 #pragma unroll
   for (int d = 0; d < DF; ++d) {
-    dv[d] = (f32x4b){0.f, 0.f, 0.f, 0.f};
-    dk[d] = (f32x4b){0.f, 0.f, 0.f, 0.f};
+    dv[d] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    dk[d] = (f32x4){0.f, 0.f, 0.f, 0.f};
   }
   const float* sbase = a.stats + (size_t)(seq * a.heads + head) * a.L * 3;
   for (int qt = 0; qt < tiles; ++qt) {
@@ -322,7 +282,7 @@ __global__ void __launch_bounds__(256) attn_bwd_kv_kernel(AttnBwdArgs a) {
       qstat[tid][2] = ok ? sbase[(size_t)q * 3 + 2] : 0.f;
     }
     __syncthreads();
-    f32x4b st[4], dp[4];
+    f32x4 st[4], dp[4];
     score_product<HD, DT>(q_img, kf, st, fl, g);      // S[q][k]: tile row = query, own row = key
     score_product<HD, DT>(do_img, vf, dp, fl, g);     // dP[q][k] = dO[q] . V[k]
 #pragma unroll
@@ -368,13 +328,13 @@ __global__ void __launch_bounds__(WAVES * 64) attn_bwd_q_res_kernel(AttnBwdArgs 
   const int qb = blockIdx.x % qblocks;
   const int head = (blockIdx.x / qblocks) % a.heads;
   const int seq = blockIdx.x / (qblocks * a.heads);
-  const int64_t base = seq_base(a, seq);
+  const int64_t base = seq_base_row(a, seq);
   const size_t ld3 = (size_t)3 * a.D;
   stage_pair_all<HD, NT>(k_img, a.qkv, ld3, a.D + head * HD, v_img, a.qkv, ld3, 2 * a.D + head * HD, base, a.row_stride, tiles, a.L, tid);
   const int q_idx = qb * QB + wave * 16 + fl;
   const int q_ld = min(q_idx, a.L - 1);
   const int64_t q_row = base + (int64_t)q_ld * a.row_stride;
-  u32x4b qf[KS], dof[KS];
+  u32x4 qf[KS], dof[KS];
   load_own<HD>(qf, a.qkv + (size_t)q_row * ld3 + head * HD, g);
   load_own<HD>(dof, a.dout + (size_t)q_row * a.D + head * HD, g);
   float dq_dot = 0.f;
@@ -384,11 +344,11 @@ __global__ void __launch_bounds__(WAVES * 64) attn_bwd_q_res_kernel(AttnBwdArgs 
     for (int ks = 0; ks < KS; ++ks) {
       const int ch = g + 4 * ks;
       if (ch < NCH) {
-        const u32x4b ov = *(const u32x4b*)(orow + ch * 8);
+        const u32x4 ov = *(const u32x4*)(orow + ch * 8);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          dq_dot += hf<DT>((unsigned short)(ov[e] & 0xffffu)) * hf<DT>((unsigned short)(dof[ks][e] & 0xffffu));
-          dq_dot += hf<DT>((unsigned short)(ov[e] >> 16)) * hf<DT>((unsigned short)(dof[ks][e] >> 16));
+          dq_dot += h2f<DT>((unsigned short)(ov[e] & 0xffffu)) * h2f<DT>((unsigned short)(dof[ks][e] & 0xffffu));
+          dq_dot += h2f<DT>((unsigned short)(ov[e] >> 16)) * h2f<DT>((unsigned short)(dof[ks][e] >> 16));
         }
       }
     }
@@ -401,18 +361,18 @@ __global__ void __launch_bounds__(WAVES * 64) attn_bwd_q_res_kernel(AttnBwdArgs 
   // kept short: the running maximum is taken on the RAW scores (the scale is positive), exp2 takes one FMA as its argument, the
   // normaliser and the softmax scale enter as log2 terms of that argument, key masks only exist on a ragged last tile.
   const float c = a.scale * 1.4426950408889634f;
-  float m_raw = NEG_BIG_B, l_run = 0.f;   // running maximum of the raw scores; row sum in the exp2 domain relative to it
+  float m_raw = NEG_BIG, l_run = 0.f;   // running maximum of the raw scores; row sum in the exp2 domain relative to it
   for (int kt = 0; kt < tiles; ++kt) {
-    f32x4b st[4];
+    f32x4 st[4];
     score_product<HD, DT>(k_img + kt * TIMG, qf, st, fl, g);
     if (kt * 64 + 64 > a.L) {   // ragged last tile (wave-uniform)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (kt * 64 + 16 * j + 4 * g + r >= a.L) st[j][r] = NEG_BIG_B;
+          if (kt * 64 + 16 * j + 4 * g + r >= a.L) st[j][r] = NEG_BIG;
     }
-    float mx = NEG_BIG_B;
+    float mx = NEG_BIG;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -438,11 +398,11 @@ __global__ void __launch_bounds__(WAVES * 64) attn_bwd_q_res_kernel(AttnBwdArgs 
     sp[0] = m_run; sp[1] = inv_l; sp[2] = dq_dot;
   }
   const float nm2 = __builtin_amdgcn_logf(inv_l * a.scale) - m_run;   // (v_log_f32 = log2) dS = exp2(S c + nm2) (dP - D)
-  f32x4b acc[DF];
+  f32x4 acc[DF];
 #pragma unroll
-  for (int d = 0; d < DF; ++d) acc[d] = (f32x4b){0.f, 0.f, 0.f, 0.f};
+  for (int d = 0; d < DF; ++d) acc[d] = (f32x4){0.f, 0.f, 0.f, 0.f};
   for (int kt = 0; kt < tiles; ++kt) {
-    f32x4b st[4], dp[4];
+    f32x4 st[4], dp[4];
     score_product<HD, DT>(k_img + kt * TIMG, qf, st, fl, g);
     score_product<HD, DT>(v_img + kt * TIMG, dof, dp, fl, g);
 #pragma unroll
@@ -478,7 +438,7 @@ __global__ void __launch_bounds__(WAVES * 64) attn_bwd_kv_res_kernel(AttnBwdArgs
   const int kb = blockIdx.x % kblocks;
   const int head = (blockIdx.x / kblocks) % a.heads;
   const int seq = blockIdx.x / (kblocks * a.heads);
-  const int64_t base = seq_base(a, seq);
+  const int64_t base = seq_base_row(a, seq);
   const size_t ld3 = (size_t)3 * a.D;
   const float* sbase = a.stats + (size_t)(seq * a.heads + head) * a.L * 3;
   stage_pair_all<HD, NT>(q_img, a.qkv, ld3, head * HD, do_img, a.dout, (size_t)a.D, head * HD, base, a.row_stride, tiles, a.L, tid);
@@ -491,20 +451,20 @@ __global__ void __launch_bounds__(WAVES * 64) attn_bwd_kv_res_kernel(AttnBwdArgs
   const int k_idx = kb * QB + wave * 16 + fl;
   const int k_ld = min(k_idx, a.L - 1);
   const int64_t k_row = base + (int64_t)k_ld * a.row_stride;
-  u32x4b kf[KS], vf[KS];
+  u32x4 kf[KS], vf[KS];
   load_own<HD>(kf, a.qkv + (size_t)k_row * ld3 + a.D + head * HD, g);
   load_own<HD>(vf, a.qkv + (size_t)k_row * ld3 + 2 * a.D + head * HD, g);
   __syncthreads();
   if (kb * QB + wave * 16 >= a.L) return;   // (wave-uniform; no barrier below)
   const float c = a.scale * 1.4426950408889634f;
-  f32x4b dv[DF], dk[DF];
+  f32x4 dv[DF], dk[DF];
 #pragma unroll
   for (int d = 0; d < DF; ++d) {
-    dv[d] = (f32x4b){0.f, 0.f, 0.f, 0.f};
-    dk[d] = (f32x4b){0.f, 0.f, 0.f, 0.f};
+    dv[d] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    dk[d] = (f32x4){0.f, 0.f, 0.f, 0.f};
   }
   for (int qt = 0; qt < tiles; ++qt) {
-    f32x4b st[4], dp[4];
+    f32x4 st[4], dp[4];
     score_product<HD, DT>(q_img + qt * TIMG, kf, st, fl, g);      // S[q][k]: tile row = query, own row = key
     score_product<HD, DT>(do_img + qt * TIMG, vf, dp, fl, g);     // dP[q][k] = dO[q] . V[k]
 #pragma unroll
@@ -536,16 +496,6 @@ __global__ void __launch_bounds__(WAVES * 64) attn_bwd_kv_res_kernel(AttnBwdArgs
 // S for dK / dV, so that the softmax statistics -- per query -- are lane-local in the first and fetched by three lane shuffles per
 // query in the second), the three value-type products (dQ^T = K^T dS^T, dV^T = dO^T P, dK^T = Q^T dS) contract over the 16 tokens
 // with the 16 x 16 x 16 MFMA on hardware-transposed reads of wave-private row-major LDS images of K, dO and Q.
-template <int DT>
-__device__ __forceinline__ f32x4b mfma16k(u32x2b a, u32x2b b, f32x4b c) {
-  typedef __attribute__((ext_vector_type(4))) short s16x4b;
-  typedef __attribute__((ext_vector_type(4))) _Float16 f16x4b;
-  if constexpr (DT == LATTE_DTYPE_BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4b, a), __builtin_bit_cast(s16x4b, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4b, a), __builtin_bit_cast(f16x4b, b), c, 0, 0, 0);
-}
-
 template <int HD, int DT>
 __global__ void __launch_bounds__(256) attn_bwd_small_kernel(AttnBwdArgs a) {
   constexpr int KS = (HD + 31) / 32, DF = (HD + 15) / 16, NCH = HD / 8;
@@ -558,7 +508,7 @@ __global__ void __launch_bounds__(256) attn_bwd_small_kernel(AttnBwdArgs a) {
   const bool active = item < items;
   item = min(item, items - 1);
   const int seq = item / a.heads, head = item % a.heads;
-  const int64_t base = seq_base(a, seq);
+  const int64_t base = seq_base_row(a, seq);
   const size_t ld3 = (size_t)3 * a.D;
   const int tok = min(fl, a.L - 1);
   const int64_t row = base + (int64_t)tok * a.row_stride;
@@ -567,7 +517,7 @@ __global__ void __launch_bounds__(256) attn_bwd_small_kernel(AttnBwdArgs a) {
   char* const q_img = k_img + 2 * IMG;
 
   // own-row fragments: lane = (token fl, chunk g + 4 ks); the same chunks go into the row-major images
-  u32x4b qf[KS], kf[KS], vf[KS], dof[KS];
+  u32x4 qf[KS], kf[KS], vf[KS], dof[KS];
   const half_t* qrow = a.qkv + (size_t)row * ld3 + head * HD;
   load_own<HD>(qf, qrow, g);
   load_own<HD>(kf, qrow + a.D, g);
@@ -577,9 +527,9 @@ __global__ void __launch_bounds__(256) attn_bwd_small_kernel(AttnBwdArgs a) {
   for (int ks = 0; ks < KS; ++ks) {
     const int ch = g + 4 * ks;
     if (ch < NCH) {
-      *(u32x4b*)(k_img + fl * RPB + ch * 16) = kf[ks];
-      *(u32x4b*)(do_img + fl * RPB + ch * 16) = dof[ks];
-      *(u32x4b*)(q_img + fl * RPB + ch * 16) = qf[ks];
+      *(u32x4*)(k_img + fl * RPB + ch * 16) = kf[ks];
+      *(u32x4*)(do_img + fl * RPB + ch * 16) = dof[ks];
+      *(u32x4*)(q_img + fl * RPB + ch * 16) = qf[ks];
     }
   }
   // D_q = dO[q] . O[q] for q = fl (this lane's chunks, then the 4 lanes of the token)
@@ -590,11 +540,11 @@ __global__ void __launch_bounds__(256) attn_bwd_small_kernel(AttnBwdArgs a) {
     for (int ks = 0; ks < KS; ++ks) {
       const int ch = g + 4 * ks;
       if (ch < NCH) {
-        const u32x4b ov = *(const u32x4b*)(orow + ch * 8);
+        const u32x4 ov = *(const u32x4*)(orow + ch * 8);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          dsum += hf<DT>((unsigned short)(ov[e] & 0xffffu)) * hf<DT>((unsigned short)(dof[ks][e] & 0xffffu));
-          dsum += hf<DT>((unsigned short)(ov[e] >> 16)) * hf<DT>((unsigned short)(dof[ks][e] >> 16));
+          dsum += h2f<DT>((unsigned short)(ov[e] & 0xffffu)) * h2f<DT>((unsigned short)(dof[ks][e] & 0xffffu));
+          dsum += h2f<DT>((unsigned short)(ov[e] >> 16)) * h2f<DT>((unsigned short)(dof[ks][e] >> 16));
         }
       }
     }
@@ -603,16 +553,16 @@ __global__ void __launch_bounds__(256) attn_bwd_small_kernel(AttnBwdArgs a) {
   }
   const float c = a.scale * 1.4426950408889634f;
   // ---- orientation 1: S^T[key = 4 g + r][q = fl], dP^T likewise -> statistics of query fl, dS^T -> dQ
-  f32x4b st = {0.f, 0.f, 0.f, 0.f}, dpt = {0.f, 0.f, 0.f, 0.f};
+  f32x4 st = {0.f, 0.f, 0.f, 0.f}, dpt = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
-    st = mfma32<DT>(kf[ks], qf[ks], st);
-    dpt = mfma32<DT>(vf[ks], dof[ks], dpt);
+    st = mfma16<DT>(kf[ks], qf[ks], st);
+    dpt = mfma16<DT>(vf[ks], dof[ks], dpt);
   }
-  float mx = NEG_BIG_B;
+  float mx = NEG_BIG;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    if (4 * g + r >= a.L) st[r] = NEG_BIG_B;
+    if (4 * g + r >= a.L) st[r] = NEG_BIG;
     mx = fmaxf(mx, st[r]);
   }
   mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
@@ -628,29 +578,29 @@ __global__ void __launch_bounds__(256) attn_bwd_small_kernel(AttnBwdArgs a) {
   ls += __shfl_xor(ls, 16, 64);
   ls += __shfl_xor(ls, 32, 64);
   const float inv_l = 1.0f / ls;
-  f32x4b dst;
+  f32x4 dst;
 #pragma unroll
   for (int r = 0; r < 4; ++r) dst[r] = pt[r] * inv_l * (dpt[r] - dsum) * a.scale;       // dS^T[key][q]
   __syncthreads();   // the images of this wave are complete (block-wide barrier keeps it simple)
-  const u32x2b dsb = {pk2<DT>(dst[0], dst[1]), pk2<DT>(dst[2], dst[3])};                  // 4 keys x query fl
+  const u32x2 dsb = {pack2<DT>(dst[0], dst[1]), pack2<DT>(dst[2], dst[3])};                  // 4 keys x query fl
   const int tro = (4 * g + (fl >> 2)) * RPB + (fl & 3) * 8;                                // transpose-read lane offset inside an image
   const bool tok_ok = active && fl < a.L;
   half_t* drow = a.dqkv + (size_t)row * ld3 + head * HD;
 #pragma unroll
   for (int d = 0; d < DF; ++d) {
-    f32x4b o = {0.f, 0.f, 0.f, 0.f};
-    o = mfma16k<DT>(tr16(k_img + tro + d * 32), dsb, o);                                   // dQ^T[d][q = fl]
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    o = mfma16_k16<DT>(lds_tr16(k_img + tro + d * 32), dsb, o);                                   // dQ^T[d][q = fl]
     const int dd = 16 * d + 4 * g;
-    if (tok_ok && dd < HD) *(u32x2b*)(drow + dd) = (u32x2b){pk2<DT>(o[0], o[1]), pk2<DT>(o[2], o[3])};
+    if (tok_ok && dd < HD) *(u32x2*)(drow + dd) = (u32x2){pack2<DT>(o[0], o[1]), pack2<DT>(o[2], o[3])};
   }
   // ---- orientation 2: S[q = 4 g + r][key = fl], dP likewise; statistics of query 4 g + r from the lanes that own it
-  f32x4b s2 = {0.f, 0.f, 0.f, 0.f}, dp2 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 s2 = {0.f, 0.f, 0.f, 0.f}, dp2 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
-    s2 = mfma32<DT>(qf[ks], kf[ks], s2);
-    dp2 = mfma32<DT>(dof[ks], vf[ks], dp2);
+    s2 = mfma16<DT>(qf[ks], kf[ks], s2);
+    dp2 = mfma16<DT>(dof[ks], vf[ks], dp2);
   }
-  f32x4b p2, ds2;
+  f32x4 p2, ds2;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int q = 4 * g + r;                                   // lane q (g = 0) holds the statistics of query q
@@ -660,17 +610,17 @@ __global__ void __launch_bounds__(256) attn_bwd_small_kernel(AttnBwdArgs a) {
     p2[r] = p;
     ds2[r] = p * (dp2[r] - d_q) * a.scale;
   }
-  const u32x2b pb = {pk2<DT>(p2[0], p2[1]), pk2<DT>(p2[2], p2[3])};                        // 4 queries x key fl
-  const u32x2b dsb2 = {pk2<DT>(ds2[0], ds2[1]), pk2<DT>(ds2[2], ds2[3])};
+  const u32x2 pb = {pack2<DT>(p2[0], p2[1]), pack2<DT>(p2[2], p2[3])};                        // 4 queries x key fl
+  const u32x2 dsb2 = {pack2<DT>(ds2[0], ds2[1]), pack2<DT>(ds2[2], ds2[3])};
 #pragma unroll
   for (int d = 0; d < DF; ++d) {
-    f32x4b ov = {0.f, 0.f, 0.f, 0.f}, ok_ = {0.f, 0.f, 0.f, 0.f};
-    ov = mfma16k<DT>(tr16(do_img + tro + d * 32), pb, ov);                                 // dV^T[d][key = fl]
-    ok_ = mfma16k<DT>(tr16(q_img + tro + d * 32), dsb2, ok_);                              // dK^T[d][key = fl]
+    f32x4 ov = {0.f, 0.f, 0.f, 0.f}, ok_ = {0.f, 0.f, 0.f, 0.f};
+    ov = mfma16_k16<DT>(lds_tr16(do_img + tro + d * 32), pb, ov);                                 // dV^T[d][key = fl]
+    ok_ = mfma16_k16<DT>(lds_tr16(q_img + tro + d * 32), dsb2, ok_);                              // dK^T[d][key = fl]
     const int dd = 16 * d + 4 * g;
     if (tok_ok && dd < HD) {
-      *(u32x2b*)(drow + a.D + dd) = (u32x2b){pk2<DT>(ok_[0], ok_[1]), pk2<DT>(ok_[2], ok_[3])};
-      *(u32x2b*)(drow + 2 * a.D + dd) = (u32x2b){pk2<DT>(ov[0], ov[1]), pk2<DT>(ov[2], ov[3])};
+      *(u32x2*)(drow + a.D + dd) = (u32x2){pack2<DT>(ok_[0], ok_[1]), pack2<DT>(ok_[2], ok_[3])};
+      *(u32x2*)(drow + 2 * a.D + dd) = (u32x2){pack2<DT>(ov[0], ov[1]), pack2<DT>(ov[2], ov[3])};
     }
   }
 }

@@ -17,20 +17,10 @@
 #include <cmath>
 
 #include "common.h"
+#include "device_util.h"
 
 namespace latte {
 namespace {
-
-template <int DT>
-__device__ __forceinline__ unsigned short f2h_t(float v) {
-  if constexpr (DT == LATTE_DTYPE_BF16) {
-    const __bf16 h = (__bf16)v;
-    return __builtin_bit_cast(unsigned short, h);
-  } else {
-    const _Float16 h = (_Float16)v;
-    return __builtin_bit_cast(unsigned short, h);
-  }
-}
 
 constexpr int FIN_SB = 8;        // samples per pass of the finalize / dc kernels
 constexpr int FIN_DMAX = 1280;   // hidden size bound of the trainer
@@ -199,13 +189,13 @@ __global__ void __launch_bounds__(256) pack_weights_kernel(const PackDesc* __res
     float v = 0.f;
     if (n0 + r < d.N && k0 + tx < d.K) {
       v = d.w[(size_t)(n0 + r) * d.K + k0 + tx];
-      d.wn[(size_t)(n0 + r) * d.K + k0 + tx] = f2h_t<DT>(v);
+      d.wn[(size_t)(n0 + r) * d.K + k0 + tx] = f2h<DT>(v);
     }
     tile[r][tx] = v;
   }
   __syncthreads();
   for (int r = ty; r < 32; r += 8)
-    if (k0 + r < d.K && n0 + tx < d.N) d.wt[(size_t)(k0 + r) * d.N + n0 + tx] = f2h_t<DT>(tile[tx][r]);
+    if (k0 + r < d.K && n0 + tx < d.N) d.wt[(size_t)(k0 + r) * d.N + n0 + tx] = f2h<DT>(tile[tx][r]);
 }
 
 // ---------------------------------------------------------------------------------------------- narrow-operand products, exact fp32
@@ -315,8 +305,8 @@ __global__ void __launch_bounds__(320) narrow_dx_kernel(const float* __restrict_
           a.x += n.w * w[p4 * 4 + 3].x; a.y += n.w * w[p4 * 4 + 3].y; a.z += n.w * w[p4 * 4 + 3].z; a.w += n.w * w[p4 * 4 + 3].w;
         }
         uint2 o;
-        o.x = (unsigned int)f2h_t<DT>(a.x) | ((unsigned int)f2h_t<DT>(a.y) << 16);
-        o.y = (unsigned int)f2h_t<DT>(a.z) | ((unsigned int)f2h_t<DT>(a.w) << 16);
+        o.x = (unsigned int)f2h<DT>(a.x) | ((unsigned int)f2h<DT>(a.y) << 16);
+        o.y = (unsigned int)f2h<DT>(a.z) | ((unsigned int)f2h<DT>(a.w) << 16);
         ((uint2*)(out + (size_t)(r0 + r) * D))[tid] = o;
       }
     }

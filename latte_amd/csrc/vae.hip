@@ -18,21 +18,6 @@
 namespace latte {
 namespace {
 
-__device__ __forceinline__ float h2f_bf16(unsigned int lo16) { return __builtin_bit_cast(float, lo16 << 16); }
-template <int DT>
-__device__ __forceinline__ void unpack2(unsigned int u, float& a, float& b) {
-  if constexpr (DT == LATTE_DTYPE_BF16) {
-    a = __builtin_bit_cast(float, u << 16);
-    b = __builtin_bit_cast(float, u & 0xffff0000u);
-  } else {
-    typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-    const f16x2 h = __builtin_bit_cast(f16x2, u);
-    a = (float)h[0];
-    b = (float)h[1];
-  }
-}
-__device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
-
 struct ConvArgs {
   const half_t* in;     // [N, Hin, Win, Cin]
   const half_t* w;      // [Cout, 9 * Cin], k = (ky * 3 + kx) * Cin + ci
@@ -242,7 +227,6 @@ __global__ void __launch_bounds__(512) conv3x3_pp_kernel(ConvArgs g) {
   const unsigned voff_b = ((unsigned)srow * (unsigned)K + (unsigned)(schunk * 8)) * 2u;
   const unsigned b_step = 32u * (unsigned)K * 2u;
   const int cpt = g.Cin >> 6;   // K tiles per tap
-  typedef __attribute__((address_space(3))) void lds_void_c;
 
   auto dma_a_half = [&](int kt) {
     char* sA = smem + (kt & 1) * STAGE + grp * 128 * 128 + wn * 1024;
@@ -253,7 +237,7 @@ __global__ void __launch_bounds__(512) conv3x3_pp_kernel(ConvArgs g) {
 #pragma unroll
       for (int j = 0; j < AH_INSTR; ++j) {
         const unsigned voff = ((pyx[j] >> tap) & 1) ? (unsigned)(pbase[j] + delta) : 0xFFFFFFF0u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void_c*)(sA + j * 4 * 1024), 16, voff, 0u, 0, 0);
+        bload_lds16(rsA, sA + j * 4 * 1024, voff, 0u);
       }
       return;
     }
@@ -263,14 +247,14 @@ __global__ void __launch_bounds__(512) conv3x3_pp_kernel(ConvArgs g) {
       const bool ok = yy >= 0 && yy < Hout && xx >= 0 && xx < Wout;
       const int sy = yy >> g.ups, sx = xx >> g.ups;
       const unsigned voff = ok ? ((unsigned)(pbase[j] + sy * g.Win + sx) * (unsigned)g.Cin + (unsigned)(c0 + schunk * 8)) * 2u : 0xFFFFFFF0u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void_c*)(sA + j * 4 * 1024), 16, voff, 0u, 0, 0);
+      bload_lds16(rsA, sA + j * 4 * 1024, voff, 0u);
     }
   };
   auto dma_b_all = [&](int kt) {
     char* sB = smem + (kt & 1) * STAGE + A_BYTES + wn * 1024;
     const unsigned so = ((unsigned)n0 * (unsigned)K + (unsigned)kt * 64u) * 2u;
 #pragma unroll
-    for (int j = 0; j < BG_INSTR; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_void_c*)(sB + j * 4 * 1024), 16, voff_b, so + (unsigned)j * b_step, 0, 0);
+    for (int j = 0; j < BG_INSTR; ++j) bload_lds16(rsB, sB + j * 4 * 1024, voff_b, so + (unsigned)j * b_step);
   };
 
   const int frow = lane & 15;
@@ -448,7 +432,6 @@ __global__ void __launch_bounds__(512) conv3x3_pps_kernel(ConvArgs g) {
   const unsigned voff_b = ((unsigned)srow * (unsigned)K + (unsigned)(schunk * 8)) * 2u;
   const unsigned b_step = 32u * (unsigned)K * 2u;
   const int cpt = g.Cin >> 6;
-  typedef __attribute__((address_space(3))) void lds_void_c;
 
   auto dma_a_half = [&](int kt, int stg) {
     char* sA = smem + stg * STAGE + grp * 128 * 128 + wn * 1024;
@@ -459,7 +442,7 @@ __global__ void __launch_bounds__(512) conv3x3_pps_kernel(ConvArgs g) {
 #pragma unroll
       for (int j = 0; j < AH_INSTR; ++j) {
         const unsigned voff = ((pyx[j] >> tap) & 1) ? (unsigned)(pbase[j] + delta) : 0xFFFFFFF0u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void_c*)(sA + j * 4 * 1024), 16, voff, 0u, 0, 0);
+        bload_lds16(rsA, sA + j * 4 * 1024, voff, 0u);
       }
       return;
     }
@@ -469,14 +452,14 @@ __global__ void __launch_bounds__(512) conv3x3_pps_kernel(ConvArgs g) {
       const bool ok = yy >= 0 && yy < Hout && xx >= 0 && xx < Wout;
       const int sy = yy >> g.ups, sx = xx >> g.ups;
       const unsigned voff = ok ? ((unsigned)(pbase[j] + sy * g.Win + sx) * (unsigned)g.Cin + (unsigned)(c0 + schunk * 8)) * 2u : 0xFFFFFFF0u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void_c*)(sA + j * 4 * 1024), 16, voff, 0u, 0, 0);
+      bload_lds16(rsA, sA + j * 4 * 1024, voff, 0u);
     }
   };
   auto dma_b_all = [&](int n0_, int kt, int stg) {
     char* sB = smem + stg * STAGE + A_BYTES + wn * 1024;
     const unsigned so = ((unsigned)n0_ * (unsigned)K + (unsigned)kt * 64u) * 2u;
 #pragma unroll
-    for (int j = 0; j < BG_INSTR; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_void_c*)(sB + j * 4 * 1024), 16, voff_b, so + (unsigned)j * b_step, 0, 0);
+    for (int j = 0; j < BG_INSTR; ++j) bload_lds16(rsB, sB + j * 4 * 1024, voff_b, so + (unsigned)j * b_step);
   };
 
   // ---- DMA walker: issues global K tile v (stage v & 1), then advances; entering a tile recomputes the gather state
@@ -753,7 +736,7 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const void* __restrict__ 
     for (int e = 0; e < 8; ++e) {
       const float mean = e < 4 ? s0.x : s1.x, rstd = e < 4 ? s0.y : s1.y;
       float t = (f[e] - mean) * rstd * gam[e] + bet[e];
-      if constexpr (SILU) t = silu_f(t);
+      if constexpr (SILU) t = silu(t);
       o[e] = t;
     }
     const u32x4 w = {pack2<DT>(o[0], o[1]), pack2<DT>(o[2], o[3]), pack2<DT>(o[4], o[5]), pack2<DT>(o[6], o[7])};
