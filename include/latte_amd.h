@@ -347,6 +347,34 @@ int latte_vae_posterior(const float* moments, const float* noise, int n, int hw,
 int latte_vae_profile_encode(latte_vae_t* v, const void* x, int n_frames, int in_mode, const float* noise, float scale, int out_mode, float* out,
                              float* ms_out, int* launches_out, int n, void* stream);
 
+/* ------------------------------------------------------------------ video preprocessing in front of the encoder
+ * The reference's per-item frame pipeline (datasets/__init__.py:13-76, datasets/video_transforms.py) as one launch:
+ * ToTensorVideo -> [RandomHorizontalFlipVideo] -> UCFCenterCropVideo | CenterCropResizeVideo -> Normalize(0.5, 0.5).
+ * kind: LATTE_VT_NONE (taichi) flip and normalise only, output size = source size (out_h = out_w = 0 or the source size);
+ * LATTE_VT_UCF_CENTER_CROP (ffs, ucf101) resize_scale by out_h / min(src_h, src_w) -- torch's scale_factor form: intermediate size
+ * floor(dim * scale), source coordinates from the GIVEN scale's reciprocal -- then center_crop to out_h x out_w, which fails with the
+ * reference's "height and width must be no smaller than crop_size" when the intermediate is smaller;
+ * LATTE_VT_CENTER_CROP_RESIZE (sky) center_crop_using_short_edge then bilinear resize to out_h x out_w (coordinate scale in / out). */
+#define LATTE_VT_NONE 0
+#define LATTE_VT_UCF_CENTER_CROP 1
+#define LATTE_VT_CENTER_CROP_RESIZE 2
+/* What the host works out for one (kind, source size, output size) and the kernel consumes: output pixel (oy, ox) is intermediate
+ * pixel (oy + crop_i, ox + crop_j) of a mid_h x mid_w bilinear resize (align_corners = False, coordinate scales scale_h / scale_w)
+ * of the reg_h x reg_w region at (reg_y, reg_x) of the -- flipped, when asked -- source frame. */
+typedef struct latte_video_plan {
+  int kind, src_h, src_w, out_h, out_w;
+  int mid_h, mid_w, crop_i, crop_j;
+  int reg_y, reg_x, reg_h, reg_w;
+  float scale_h, scale_w;
+} latte_video_plan;
+/* Host only (no device needed). */
+int latte_video_transform_plan(int kind, int src_h, int src_w, int out_h, int out_w, latte_video_plan* plan);
+/* src: uint8 NHWC [n, src_h, src_w, 3] (device); flip: one byte per frame (device), non-zero = that frame is mirrored left-right
+ * BEFORE the crop and resize, as the reference does, or NULL; out: fp32 NCHW [n, 3, out_h, out_w] in [-1, 1] (device) =
+ * ((bilinear blend of x / 255) - 0.5) / 0.5 in torch's order of operations -- the in_mode 0 input of latte_vae_encode. */
+int latte_video_transform(const uint8_t* src, int n, int src_h, int src_w, int kind, int out_h, int out_w, const uint8_t* flip, float* out,
+                          void* stream);
+
 /* ------------------------------------------------------------------ LatteT2V denoiser (Latte-1 text-to-video)
  * LatteT2V.forward, /root/reference/models/latte_t2v.py:677-941 (constructor :475-672).
  * PixArt-alpha style blocks with norm_type "ada_norm_single", attention_bias = True, activation_fn "gelu-approximate",

@@ -38,6 +38,11 @@ class T5Config(ctypes.Structure):
         + [("layer_norm_epsilon", c_f32), ("compute_dtype", c_int)]
 
 
+class VideoPlan(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("kind", "src_h", "src_w", "out_h", "out_w", "mid_h", "mid_w", "crop_i", "crop_j",
+                                     "reg_y", "reg_x", "reg_h", "reg_w")] + [("scale_h", c_f32), ("scale_w", c_f32)]
+
+
 DTYPES = {"bf16": 0, "bfloat16": 0, "f16": 1, "fp16": 1, "float16": 1}
 
 # name -> (restype, argtypes); mirrors include/latte_amd.h and include/latte_amd_debug.h
@@ -119,6 +124,8 @@ PROTOTYPES = {
     "latte_vae_encode": (c_int, [c_void, c_void, c_int, c_int, c_void, c_f32, c_int, c_void, c_void]),
     "latte_vae_posterior": (c_int, [c_void, c_void, c_int, c_int, c_f32, c_int, c_void, c_void]),
     "latte_vae_profile_encode": (c_int, [c_void, c_void, c_int, c_int, c_void, c_f32, c_int, c_void, c_void, c_void, c_int, c_void]),
+    "latte_video_transform_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(VideoPlan)]),
+    "latte_video_transform": (c_int, [c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_void, c_void, c_void]),
     "latte_t5_create": (c_int, [ctypes.POINTER(T5Config), c_int, c_int, ctypes.POINTER(c_void)]),
     "latte_t5_destroy": (None, [c_void]),
     "latte_t5_num_keys": (c_int, [c_void]),

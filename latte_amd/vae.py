@@ -98,7 +98,7 @@ class AutoencoderKL:
     decode and are not offered: ``compute_dtype`` other than f16 and ``.to(torch.bfloat16)`` raise.
 
     ``with_encoder=True`` keeps the encoder half (``encoder.*``, ``quant_conv.*``) on load and enables ``encode`` /
-    ``encode_video_uint8`` on the same operand scheme; the encoder's device state is created on the first ``encode``."""
+    ``encode_video_uint8`` / ``encode_video_raw`` on the same operand scheme; the encoder's device state is created on the first ``encode``."""
     _TEMPORAL = False
 
     def __init__(self, latent_size=32, max_frames=16, compute_dtype="f16", scaling_factor=0.18215,
@@ -349,6 +349,22 @@ class AutoencoderKL:
         b, f, hh = frames.shape[0], frames.shape[1], frames.shape[2]
         noise = randn_tensor((b * f, 4, hh // 8, hh // 8), generator=generator, device=self._device)
         out = self._encode_run(frames.reshape(b * f, hh, hh, 3), 1, 2, noise, self.config.scaling_factor)
+        return out.view(b, f, *out.shape[1:])
+
+    def encode_video_raw(self, frames, transform, flip=None, generator=None):
+        """Raw-size clips to latents: uint8 frames [B, F, Hs, Ws, 3] (or [N, Hs, Ws, 3], one clip) on the GPU ->
+        ``transform(frames, flip)`` (a ``latte_amd.video_transforms.VideoTransform``: one launch, fp32 [B, F, 3, S, S]) ->
+        latents [B, F, 4, S/8, S/8] = encode(x).latent_dist.sample(generator) * scaling_factor on the fp32 encode path."""
+        if not self.with_encoder:
+            raise LatteError(_NO_ENCODER)
+        x = transform(frames.to(self._device), flip=flip)
+        if x.dim() == 4:
+            x = x.unsqueeze(0)
+        b, f, _, s, sw = x.shape
+        if s != sw:
+            raise LatteError(f"the transform must produce square frames for the encoder, got {s} x {sw}")
+        noise = randn_tensor((b * f, 4, s // 8, s // 8), generator=generator, device=self._device)
+        out = self._encode_run(x.reshape(b * f, 3, s, s), 0, 2, noise, self.config.scaling_factor)
         return out.view(b, f, *out.shape[1:])
 
     def profile_encode(self, x, in_mode=0):

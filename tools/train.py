@@ -13,7 +13,12 @@ under the backward) + clip_grad_norm_ + AdamW + update_ema (train.py:197-236).  
     loaded from `<pretrained_model_path>/vae` with the encoder (train.py:94), fresh posterior noise every step from a seeded generator;
   - latent clips (.npy [F, 4, h, w], already scaled by 0.18215; tools/encode_clips.py writes them from frame clips once, instead of
     encoding every epoch);
-  - "synthetic" (N(0, 1) latents: throughput and plumbing, not a model worth keeping).
+  - "synthetic" (N(0, 1) latents: throughput and plumbing, not a model worth keeping);
+  - with `frame_interval` set in the config (the reference's key, configs/tiny_train_raw.yaml): RAW uint8 clips (.npy [T, Hs, Ws, 3] of any
+    length and size, memory-mapped), read as the reference's dataset classes read a video (datasets/ucf101_datasets.py:198-216): per item
+    and step a `TemporalRandomCrop(num_frames * frame_interval)` window and the flip coin from a seeded generator, the `num_frames` frames
+    of `frame_indices` gathered on the host, one upload, one `latte_amd.video_transforms` launch for `dataset`'s pipeline
+    (ffs | ucf101 | taichi | sky), then the encode above -- nothing of the augmentation is frozen into the stored data.
 """
 import argparse
 import glob
@@ -29,6 +34,47 @@ sys.path.insert(0, ROOT)
 
 import latte_amd  # noqa: E402
 from latte_amd import parallel  # noqa: E402
+
+
+def clip_label(path):
+    name = os.path.basename(path)
+    return int(name.split("_")[0]) if name.split("_")[0].isdigit() else 0
+
+
+class RawClips:
+    """Raw uint8 clips [T, Hs, Ws, 3] of any length and size, memory-mapped: per item the reference's temporal window, frame indices and
+    flip coin (datasets/ucf101_datasets.py:198-216, video_transforms.py:386-427) from a generator seeded by (seed, step, rank)."""
+    frames = True
+
+    def __init__(self, path, args, rank, world, seed):
+        self.files = sorted(glob.glob(os.path.join(path, "*.npy")))
+        if not self.files:
+            raise SystemExit(f"no .npy clips under {path}")
+        self.args, self.rank, self.world, self.seed = args, rank, world, seed
+        self.num_frames = int(args.num_frames)
+
+    def _clip(self, i):
+        a = np.load(self.files[i], mmap_mode="r")             # mapped, not read: only the gathered frames are touched
+        if a.dtype != np.uint8 or a.ndim != 4 or a.shape[-1] != 3:
+            raise SystemExit(f"{self.files[i]}: raw clips are uint8 [T, Hs, Ws, 3], got {a.dtype} {a.shape}")
+        return a
+
+    def batch(self, step, n):
+        """-> ([(frames uint8 [num_frames, Hs, Ws, 3], flip)] * n, labels)"""
+        import random
+        from latte_amd import video_transforms
+        s = self.seed * 1000003 + step * self.world + self.rank
+        g = torch.Generator("cpu").manual_seed(s)
+        transform, temporal_sample = video_transforms.get_transform(self.args, rng=random.Random(s))
+        items, ys = [], []
+        for i in torch.randint(0, len(self.files), (n,), generator=g).tolist():
+            a = self._clip(i)
+            start, end = temporal_sample(a.shape[0])
+            assert end - start >= self.num_frames, f"{self.files[i]}: {a.shape[0]} frames, fewer than num_frames = {self.num_frames}"
+            idx = video_transforms.frame_indices(start, end, self.num_frames)
+            items.append((torch.from_numpy(np.ascontiguousarray(a[idx])), transform.draw_flips(1)[0]))
+            ys.append(clip_label(self.files[i]))
+        return items, torch.tensor(ys)
 
 
 class LatentClips:
@@ -61,8 +107,7 @@ class LatentClips:
             a = np.load(self.files[i])
             assert a.shape == self.shape, f"{self.files[i]}: expected {self.shape}, got {a.shape}"
             xs.append(torch.from_numpy(a) if self.frames else torch.from_numpy(a).float())
-            name = os.path.basename(self.files[i])
-            ys.append(int(name.split("_")[0]) if name.split("_")[0].isdigit() else 0)
+            ys.append(clip_label(self.files[i]))
         return torch.stack(xs), torch.tensor(ys)
 
 
@@ -112,7 +157,13 @@ def main():
         if stem.isdigit():
             first_step = int(stem)
             trainer.train_steps = first_step
-    data = LatentClips(args.get("data_path"), int(args.num_frames), args.latent_size, rank, world, seed, int(args.get("num_classes") or 0))
+    raw = args.get("frame_interval") not in (None, "") and args.get("data_path") not in (None, "", "synthetic")
+    if raw:                                                   # raw clips through the dataset's frame pipeline (datasets/__init__.py:13-76)
+        from latte_amd import video_transforms
+        data = RawClips(args.data_path, args, rank, world, seed)
+        raw_transform, _ = video_transforms.get_transform(args)
+    else:
+        data = LatentClips(args.get("data_path"), int(args.num_frames), args.latent_size, rank, world, seed, int(args.get("num_classes") or 0))
     vae = None
     if data.frames:                                           # train.py:94 (+ the encoder): frames -> latents on the GPU every step
         if not args.get("pretrained_model_path"):
@@ -133,7 +184,10 @@ def main():
         x, y = data.batch(step, nb)
         if vae is not None:                                   # train.py:204-211, posterior noise from this step's seeded generator
             gen = torch.Generator(device).manual_seed(seed * 1000003 + step * world + rank)
-            x = vae.encode_video_uint8(x.to(device), generator=gen)
+            if raw:                                           # per item (sizes differ): one upload, one transform launch, the encode
+                x = torch.cat([vae.encode_video_raw(fr.to(device).unsqueeze(0), raw_transform, flip=[fl], generator=gen) for fr, fl in x])
+            else:
+                x = vae.encode_video_uint8(x.to(device), generator=gen)
         out = trainer.train_step(x.to(device), y=y.to(device) if int(args.extras) == 2 else None)
         running += float(out["loss"].mean())                  # (the reference's loss.item(), train.py:239)
         log_steps += 1
