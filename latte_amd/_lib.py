@@ -241,3 +241,35 @@ def stream_ptr():
 
 def ptr(t):
     return c_void(t.data_ptr()) if t is not None else c_void(None)
+
+
+def to_device(args, kwargs, current, bf16_message):
+    """The device a holder class's ``.to(*args, **kwargs)`` names: the str / torch.device among the arguments (a bare "cuda" gets the
+    current index), else ``current``.  ``torch.bfloat16`` raises the caller's ``bf16_message``; other dtypes are accepted and ignored."""
+    dev = current
+    for a in list(args) + list(kwargs.values()):
+        if isinstance(a, (str, torch.device)):
+            dev = torch.device(a)
+            if dev.type == "cuda" and dev.index is None:
+                dev = torch.device("cuda", torch.cuda.current_device())
+        elif a == torch.bfloat16:
+            raise LatteError(bf16_message)
+    return dev
+
+
+def sync_weights(lib, family, handle, sd, device, optional=()):
+    """Load every tensor the engine ``handle`` lists (``latte_<family>_key(i)``, family "engine" | "t2v" | "vae") from the state dict
+    ``sd`` as fp32 on ``device``, check that nothing is missing, and wait for the packs.  Keys in ``optional`` may be absent."""
+    num_keys, key, load_tensor, check_weights = (getattr(lib, f"latte_{family}_{n}")
+                                                 for n in ("num_keys", "key", "load_tensor", "check_weights"))
+    with torch.cuda.device(device):
+        for i in range(num_keys(handle)):
+            k = key(handle, i).decode()
+            if k not in sd:
+                if k in optional:
+                    continue
+                raise LatteError(f'Missing key(s) in state_dict: "{k}"')
+            t = sd[k].detach().to(device=device, dtype=torch.float32).contiguous()
+            check(load_tensor(handle, k.encode(), ptr(t), t.numel(), 1, stream_ptr()))
+        check(check_weights(handle))
+        torch.cuda.current_stream().synchronize()

@@ -13,11 +13,10 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "weight_store.h"
 
 namespace latte {
 
@@ -48,15 +47,7 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
-enum PackKind { PK_F32, PK_F32_TRANSPOSE, PK_H16 };
-struct TensorSlot {
-  std::string key;
-  int64_t numel;
-  PackKind kind;
-  void* dst;
-  int rows, cols;  // for PK_F32_TRANSPOSE: source [rows][cols]
-  bool loaded = false;
-};
+enum PackKind { PK_F32, PK_F32_TRANSPOSE, PK_H16 };   // WeightSlot::kind; PK_F32_TRANSPOSE: source [rows][cols]
 
 struct BlockW {
   half_t *qkv_w, *proj_w, *fc1_w, *fc2_w;
@@ -115,8 +106,7 @@ struct latte_engine {
   float *ada_w = nullptr, *ada_b = nullptr, *pos = nullptr, *temp = nullptr, *pe_wt = nullptr, *pe_b = nullptr,
         *t0_w = nullptr, *t0_b = nullptr, *t2_w = nullptr, *t2_b = nullptr, *ytab = nullptr, *fin_wt = nullptr,
         *fin_b = nullptr;
-  float *xres = nullptr, *mod = nullptr, *temb0 = nullptr, *cvec = nullptr, *model_out = nullptr, *stage = nullptr,
-        *noise_buf = nullptr;
+  float *xres = nullptr, *mod = nullptr, *temb0 = nullptr, *cvec = nullptr, *model_out = nullptr, *noise_buf = nullptr;
   half_t *xn = nullptr, *qkv = nullptr, *hbuf = nullptr;
   int64_t* tmap_dev = nullptr;
   int64_t tmap_cap = 0;
@@ -135,38 +125,12 @@ struct latte_engine {
   std::vector<int64_t> temb_own_map;     // the timestep_map temb_own currently holds (empty: none); a chain run in several
                                          // latte_sample_loop segments computes its table once
   int64_t temb_table_cap = 0, temb_own_cap = 0, temb_cap = 0, cond_cap = 0, mod_all_cap = 0;
-  int64_t stage_numel = 0;
-  std::vector<TensorSlot> slots;
-  std::map<std::string, int> slot_index;
-  std::vector<void*> allocs;
+  WeightSlots weights;
+  DeviceArena arena;
   uint64_t seed = 0, rng_offset = 0;
 };
 
 namespace {
-
-template <typename Tp>
-int dev_alloc(latte_engine* e, Tp** p, size_t count, bool zero = true) {
-  void* q = nullptr;
-  const size_t bytes = count * sizeof(Tp);
-  LATTE_HIP(hipMalloc(&q, bytes ? bytes : 16));
-  if (zero) LATTE_HIP(hipMemset(q, 0, bytes ? bytes : 16));
-  e->allocs.push_back(q);
-  *p = (Tp*)q;
-  return LATTE_OK;
-}
-
-void add_slot(latte_engine* e, const std::string& key, int64_t numel, PackKind kind, void* dst, int rows = 0, int cols = 0) {
-  TensorSlot s;
-  s.key = key;
-  s.numel = numel;
-  s.kind = kind;
-  s.dst = dst;
-  s.rows = rows;
-  s.cols = cols;
-  e->slot_index[key] = (int)e->slots.size();
-  e->slots.push_back(s);
-  if (numel > e->stage_numel) e->stage_numel = numel;
-}
 
 struct Timer {  // optional per-launch HIP events (latte_profile_forward)
   Prof* p;
@@ -231,17 +195,17 @@ int ensure_split_weights(latte_engine* e, int need, hipStream_t st) {
     return 0;
   };
   bool fresh = false;
-  if ((need & 2) && !e->xn2 && dev_alloc(e, &e->xn2, (size_t)e->rows_pad * 2 * D)) return give_up("the [rows, 2 D] operand buffer");
-  if ((need & 12) && !e->lo8 && dev_alloc(e, &e->lo8, (size_t)e->rows_pad * D)) return give_up("the fp8 remainder buffer");
-  if ((need & 16) && !e->lo4 && (dev_alloc(e, &e->lo4, (size_t)e->rows_pad * lo4_pitch(D)) || dev_alloc(e, &e->lo4s, (size_t)e->rows_pad)))
-    return give_up("the fp4 remainder buffer");   // (dev_alloc zero-fills: the padding columns of a code row stay zero codes)
+  if ((need & 2) && !e->xn2 && e->arena.alloc(&e->xn2, (size_t)e->rows_pad * 2 * D)) return give_up("the [rows, 2 D] operand buffer");
+  if ((need & 12) && !e->lo8 && e->arena.alloc(&e->lo8, (size_t)e->rows_pad * D)) return give_up("the fp8 remainder buffer");
+  if ((need & 16) && !e->lo4 && (e->arena.alloc(&e->lo4, (size_t)e->rows_pad * lo4_pitch(D)) || e->arena.alloc(&e->lo4s, (size_t)e->rows_pad)))
+    return give_up("the fp4 remainder buffer");   // (zero-filled: the padding columns of a code row stay zero codes)
   for (auto& w : e->blocks) {
-    if ((need & 1) && !w.proj_w2) { if (dev_alloc(e, &w.proj_w2, (size_t)D * 2 * D, false)) return give_up("[W | W] of the out-projection"); fresh = true; }
-    if ((need & 2) && !w.fc1_w2) { if (dev_alloc(e, &w.fc1_w2, (size_t)Hm * 2 * D, false)) return give_up("[W | W] of fc1"); fresh = true; }
-    if ((need & 4) && !w.proj_w8) { if (dev_alloc(e, &w.proj_w8, (size_t)D * D, false)) return give_up("W8 of the out-projection"); fresh = true; }
-    if ((need & 8) && !w.fc1_w8) { if (dev_alloc(e, &w.fc1_w8, (size_t)Hm * D, false)) return give_up("W8 of fc1"); fresh = true; }
+    if ((need & 1) && !w.proj_w2) { if (e->arena.alloc(&w.proj_w2, (size_t)D * 2 * D, false)) return give_up("[W | W] of the out-projection"); fresh = true; }
+    if ((need & 2) && !w.fc1_w2) { if (e->arena.alloc(&w.fc1_w2, (size_t)Hm * 2 * D, false)) return give_up("[W | W] of fc1"); fresh = true; }
+    if ((need & 4) && !w.proj_w8) { if (e->arena.alloc(&w.proj_w8, (size_t)D * D, false)) return give_up("W8 of the out-projection"); fresh = true; }
+    if ((need & 8) && !w.fc1_w8) { if (e->arena.alloc(&w.fc1_w8, (size_t)Hm * D, false)) return give_up("W8 of fc1"); fresh = true; }
     if ((need & 16) && !w.fc1_w4) {
-      if (dev_alloc(e, &w.fc1_w4, (size_t)Hm * lo4_pitch(D), false) || dev_alloc(e, &w.fc1_w4s, (size_t)Hm, false)) return give_up("W4 of fc1");
+      if (e->arena.alloc(&w.fc1_w4, (size_t)Hm * lo4_pitch(D), false) || e->arena.alloc(&w.fc1_w4s, (size_t)Hm, false)) return give_up("W4 of fc1");
       fresh = true;
     }
   }
@@ -407,12 +371,11 @@ int run_forward(latte_engine* e, const float* x, const int64_t* t, const int64_t
 int grow(latte_engine* e, float** p, int64_t* cap, int64_t need) {
   if (*cap >= need) return LATTE_OK;
   if (*p) {   // release the smaller block (setup path: the implicit device synchronisation of hipFree is fine here)
-    e->allocs.erase(std::remove(e->allocs.begin(), e->allocs.end(), (void*)*p), e->allocs.end());
-    (void)hipFree(*p);
+    e->arena.release(*p);
     *p = nullptr;
     *cap = 0;
   }
-  int rc = dev_alloc(e, p, (size_t)need, false);
+  int rc = e->arena.alloc(p, (size_t)need, false);
   if (!rc) *cap = need;
   return rc;
 }
@@ -423,7 +386,7 @@ int compute_temb_table(latte_engine* e, const latte_schedule_t* s, float* out, h
   const int n = s->num_timesteps, D = e->D;
   int rc;
   if (e->tmap_cap < n) {
-    if ((rc = dev_alloc(e, &e->tmap_dev, (size_t)n, false))) return rc;
+    if ((rc = e->arena.alloc(&e->tmap_dev, (size_t)n, false))) return rc;
     e->tmap_cap = n;
   }
   LATTE_HIP(hipMemcpyAsync(e->tmap_dev, s->timestep_map.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, st));
@@ -510,82 +473,82 @@ int latte_engine_create(const latte_model_config_t* cfg, int max_batch, latte_en
   const int D = e->D;
   int rc = LATTE_OK;
 #define TRY(x) do { if ((rc = (x))) { latte_engine_destroy(e); return rc; } } while (0)
-  TRY(dev_alloc(e, &e->ada_w, (size_t)e->nmod * D));
-  TRY(dev_alloc(e, &e->ada_b, (size_t)e->nmod));
-  TRY(dev_alloc(e, &e->pos, (size_t)e->T * D));
-  TRY(dev_alloc(e, &e->temp, (size_t)e->F * D));
-  TRY(dev_alloc(e, &e->pe_wt, (size_t)e->KPE * D));
-  TRY(dev_alloc(e, &e->pe_b, (size_t)D));
-  TRY(dev_alloc(e, &e->t0_w, (size_t)D * 256));
-  TRY(dev_alloc(e, &e->t0_b, (size_t)D));
-  TRY(dev_alloc(e, &e->t2_w, (size_t)D * D));
-  TRY(dev_alloc(e, &e->t2_b, (size_t)D));
-  TRY(dev_alloc(e, &e->fin_wt, (size_t)D * e->P));
-  TRY(dev_alloc(e, &e->fin_b, (size_t)e->P));
-  add_slot(e, "pos_embed", (int64_t)e->T * D, PK_F32, e->pos);
-  add_slot(e, "temp_embed", (int64_t)e->F * D, PK_F32, e->temp);
-  add_slot(e, "x_embedder.proj.weight", (int64_t)D * e->KPE, PK_F32_TRANSPOSE, e->pe_wt, D, e->KPE);
-  add_slot(e, "x_embedder.proj.bias", D, PK_F32, e->pe_b);
-  add_slot(e, "t_embedder.mlp.0.weight", (int64_t)D * 256, PK_F32, e->t0_w);
-  add_slot(e, "t_embedder.mlp.0.bias", D, PK_F32, e->t0_b);
-  add_slot(e, "t_embedder.mlp.2.weight", (int64_t)D * D, PK_F32, e->t2_w);
-  add_slot(e, "t_embedder.mlp.2.bias", D, PK_F32, e->t2_b);
+  TRY(e->arena.alloc(&e->ada_w, (size_t)e->nmod * D));
+  TRY(e->arena.alloc(&e->ada_b, (size_t)e->nmod));
+  TRY(e->arena.alloc(&e->pos, (size_t)e->T * D));
+  TRY(e->arena.alloc(&e->temp, (size_t)e->F * D));
+  TRY(e->arena.alloc(&e->pe_wt, (size_t)e->KPE * D));
+  TRY(e->arena.alloc(&e->pe_b, (size_t)D));
+  TRY(e->arena.alloc(&e->t0_w, (size_t)D * 256));
+  TRY(e->arena.alloc(&e->t0_b, (size_t)D));
+  TRY(e->arena.alloc(&e->t2_w, (size_t)D * D));
+  TRY(e->arena.alloc(&e->t2_b, (size_t)D));
+  TRY(e->arena.alloc(&e->fin_wt, (size_t)D * e->P));
+  TRY(e->arena.alloc(&e->fin_b, (size_t)e->P));
+  e->weights.add("pos_embed", (int64_t)e->T * D, PK_F32, e->pos);
+  e->weights.add("temp_embed", (int64_t)e->F * D, PK_F32, e->temp);
+  e->weights.add("x_embedder.proj.weight", (int64_t)D * e->KPE, PK_F32_TRANSPOSE, e->pe_wt, D, e->KPE);
+  e->weights.add("x_embedder.proj.bias", D, PK_F32, e->pe_b);
+  e->weights.add("t_embedder.mlp.0.weight", (int64_t)D * 256, PK_F32, e->t0_w);
+  e->weights.add("t_embedder.mlp.0.bias", D, PK_F32, e->t0_b);
+  e->weights.add("t_embedder.mlp.2.weight", (int64_t)D * D, PK_F32, e->t2_w);
+  e->weights.add("t_embedder.mlp.2.bias", D, PK_F32, e->t2_b);
   if (c.extras == 2) {
-    TRY(dev_alloc(e, &e->ytab, (size_t)(c.num_classes + 1) * D));
-    add_slot(e, "y_embedder.embedding_table.weight", (int64_t)(c.num_classes + 1) * D, PK_F32, e->ytab);
+    TRY(e->arena.alloc(&e->ytab, (size_t)(c.num_classes + 1) * D));
+    e->weights.add("y_embedder.embedding_table.weight", (int64_t)(c.num_classes + 1) * D, PK_F32, e->ytab);
   }
   if (c.extras == 78) {
     constexpr int64_t TK = 77 * 768;   // latte.py:241
-    TRY(dev_alloc(e, &e->txt_w, (size_t)D * TK));
-    TRY(dev_alloc(e, &e->txt_b, (size_t)D));
-    TRY(dev_alloc(e, &e->txt_proj, (size_t)max_batch * D));
-    TRY(dev_alloc(e, &e->cvec_t, (size_t)max_batch * D));
-    TRY(dev_alloc(e, &e->iota, (size_t)max_batch));
+    TRY(e->arena.alloc(&e->txt_w, (size_t)D * TK));
+    TRY(e->arena.alloc(&e->txt_b, (size_t)D));
+    TRY(e->arena.alloc(&e->txt_proj, (size_t)max_batch * D));
+    TRY(e->arena.alloc(&e->cvec_t, (size_t)max_batch * D));
+    TRY(e->arena.alloc(&e->iota, (size_t)max_batch));
     TRY(launch_iota(e->iota, max_batch, nullptr));
     LATTE_HIP(hipStreamSynchronize(nullptr));
-    add_slot(e, "text_embedding_projection.1.weight", (int64_t)D * TK, PK_F32, e->txt_w);
-    add_slot(e, "text_embedding_projection.1.bias", D, PK_F32, e->txt_b);
+    e->weights.add("text_embedding_projection.1.weight", (int64_t)D * TK, PK_F32, e->txt_w);
+    e->weights.add("text_embedding_projection.1.bias", D, PK_F32, e->txt_b);
   }
   e->blocks.resize(c.depth);
   for (int i = 0; i < c.depth; ++i) {
     BlockW& w = e->blocks[i];
-    TRY(dev_alloc(e, &w.qkv_w, (size_t)3 * D * D));
-    TRY(dev_alloc(e, &w.proj_w, (size_t)D * D));
-    TRY(dev_alloc(e, &w.fc1_w, (size_t)e->Hm * D));
-    TRY(dev_alloc(e, &w.fc2_w, (size_t)D * e->Hm));
-    TRY(dev_alloc(e, &w.qkv_b, (size_t)3 * D));
-    TRY(dev_alloc(e, &w.proj_b, (size_t)D));
-    TRY(dev_alloc(e, &w.fc1_b, (size_t)e->Hm));
-    TRY(dev_alloc(e, &w.fc2_b, (size_t)D));
+    TRY(e->arena.alloc(&w.qkv_w, (size_t)3 * D * D));
+    TRY(e->arena.alloc(&w.proj_w, (size_t)D * D));
+    TRY(e->arena.alloc(&w.fc1_w, (size_t)e->Hm * D));
+    TRY(e->arena.alloc(&w.fc2_w, (size_t)D * e->Hm));
+    TRY(e->arena.alloc(&w.qkv_b, (size_t)3 * D));
+    TRY(e->arena.alloc(&w.proj_b, (size_t)D));
+    TRY(e->arena.alloc(&w.fc1_b, (size_t)e->Hm));
+    TRY(e->arena.alloc(&w.fc2_b, (size_t)D));
     const std::string p = "blocks." + std::to_string(i) + ".";
-    add_slot(e, p + "attn.qkv.weight", (int64_t)3 * D * D, PK_H16, w.qkv_w);
-    add_slot(e, p + "attn.qkv.bias", 3 * D, PK_F32, w.qkv_b);
-    add_slot(e, p + "attn.proj.weight", (int64_t)D * D, PK_H16, w.proj_w);
-    add_slot(e, p + "attn.proj.bias", D, PK_F32, w.proj_b);
-    add_slot(e, p + "mlp.fc1.weight", (int64_t)e->Hm * D, PK_H16, w.fc1_w);
-    add_slot(e, p + "mlp.fc1.bias", e->Hm, PK_F32, w.fc1_b);
-    add_slot(e, p + "mlp.fc2.weight", (int64_t)D * e->Hm, PK_H16, w.fc2_w);
-    add_slot(e, p + "mlp.fc2.bias", D, PK_F32, w.fc2_b);
-    add_slot(e, p + "adaLN_modulation.1.weight", (int64_t)6 * D * D, PK_F32, e->ada_w + (size_t)i * 6 * D * D);
-    add_slot(e, p + "adaLN_modulation.1.bias", 6 * D, PK_F32, e->ada_b + (size_t)i * 6 * D);
+    e->weights.add(p + "attn.qkv.weight", (int64_t)3 * D * D, PK_H16, w.qkv_w);
+    e->weights.add(p + "attn.qkv.bias", 3 * D, PK_F32, w.qkv_b);
+    e->weights.add(p + "attn.proj.weight", (int64_t)D * D, PK_H16, w.proj_w);
+    e->weights.add(p + "attn.proj.bias", D, PK_F32, w.proj_b);
+    e->weights.add(p + "mlp.fc1.weight", (int64_t)e->Hm * D, PK_H16, w.fc1_w);
+    e->weights.add(p + "mlp.fc1.bias", e->Hm, PK_F32, w.fc1_b);
+    e->weights.add(p + "mlp.fc2.weight", (int64_t)D * e->Hm, PK_H16, w.fc2_w);
+    e->weights.add(p + "mlp.fc2.bias", D, PK_F32, w.fc2_b);
+    e->weights.add(p + "adaLN_modulation.1.weight", (int64_t)6 * D * D, PK_F32, e->ada_w + (size_t)i * 6 * D * D);
+    e->weights.add(p + "adaLN_modulation.1.bias", 6 * D, PK_F32, e->ada_b + (size_t)i * 6 * D);
   }
-  add_slot(e, "final_layer.linear.weight", (int64_t)e->P * D, PK_F32_TRANSPOSE, e->fin_wt, e->P, D);
-  add_slot(e, "final_layer.linear.bias", e->P, PK_F32, e->fin_b);
-  add_slot(e, "final_layer.adaLN_modulation.1.weight", (int64_t)2 * D * D, PK_F32, e->ada_w + (size_t)c.depth * 6 * D * D);
-  add_slot(e, "final_layer.adaLN_modulation.1.bias", 2 * D, PK_F32, e->ada_b + (size_t)c.depth * 6 * D);
+  e->weights.add("final_layer.linear.weight", (int64_t)e->P * D, PK_F32_TRANSPOSE, e->fin_wt, e->P, D);
+  e->weights.add("final_layer.linear.bias", e->P, PK_F32, e->fin_b);
+  e->weights.add("final_layer.adaLN_modulation.1.weight", (int64_t)2 * D * D, PK_F32, e->ada_w + (size_t)c.depth * 6 * D * D);
+  e->weights.add("final_layer.adaLN_modulation.1.bias", 2 * D, PK_F32, e->ada_b + (size_t)c.depth * 6 * D);
 
-  TRY(dev_alloc(e, &e->stage, (size_t)e->stage_numel, false));
-  TRY(dev_alloc(e, &e->xres, (size_t)e->rows_pad * D));
-  TRY(dev_alloc(e, &e->split_ws, (size_t)SPLIT_WS_FLOATS, false));
-  TRY(dev_alloc(e, &e->zero_bias, (size_t)std::max(D, e->Hm)));
-  TRY(dev_alloc(e, &e->xn, (size_t)e->rows_pad * D));
-  TRY(dev_alloc(e, &e->qkv, (size_t)e->rows_pad * 3 * D));
-  TRY(dev_alloc(e, &e->hbuf, (size_t)e->rows_pad * e->Hm));
-  TRY(dev_alloc(e, &e->mod, (size_t)max_batch * e->nmod));
-  TRY(dev_alloc(e, &e->temb0, (size_t)max_batch * D));
-  TRY(dev_alloc(e, &e->cvec, (size_t)max_batch * D));
-  TRY(dev_alloc(e, &e->model_out, (size_t)max_batch * e->F * e->Cout * e->H * e->H));
-  TRY(dev_alloc(e, &e->noise_buf, (size_t)max_batch * e->F * e->Cin * e->H * e->H));
+  TRY(e->weights.alloc_stage(e->arena, false));
+  TRY(e->arena.alloc(&e->xres, (size_t)e->rows_pad * D));
+  TRY(e->arena.alloc(&e->split_ws, (size_t)SPLIT_WS_FLOATS, false));
+  TRY(e->arena.alloc(&e->zero_bias, (size_t)std::max(D, e->Hm)));
+  TRY(e->arena.alloc(&e->xn, (size_t)e->rows_pad * D));
+  TRY(e->arena.alloc(&e->qkv, (size_t)e->rows_pad * 3 * D));
+  TRY(e->arena.alloc(&e->hbuf, (size_t)e->rows_pad * e->Hm));
+  TRY(e->arena.alloc(&e->mod, (size_t)max_batch * e->nmod));
+  TRY(e->arena.alloc(&e->temb0, (size_t)max_batch * D));
+  TRY(e->arena.alloc(&e->cvec, (size_t)max_batch * D));
+  TRY(e->arena.alloc(&e->model_out, (size_t)max_batch * e->F * e->Cout * e->H * e->H));
+  TRY(e->arena.alloc(&e->noise_buf, (size_t)max_batch * e->F * e->Cin * e->H * e->H));
 #undef TRY
   *out = e;
   return LATTE_OK;
@@ -593,16 +556,12 @@ int latte_engine_create(const latte_model_config_t* cfg, int max_batch, latte_en
 
 void latte_engine_destroy(latte_engine_t* e) {
   if (!e) return;
-  for (void* p : e->allocs) (void)hipFree(p);
   if (e->load_event) (void)hipEventDestroy(e->load_event);
-  delete e;
+  delete e;   // the arena frees every device block
 }
 
-int latte_engine_num_keys(const latte_engine_t* e) { return e ? (int)e->slots.size() : 0; }
-const char* latte_engine_key(const latte_engine_t* e, int i) {
-  if (!e || i < 0 || i >= (int)e->slots.size()) return nullptr;
-  return e->slots[i].key.c_str();
-}
+int latte_engine_num_keys(const latte_engine_t* e) { return e ? e->weights.size() : 0; }
+const char* latte_engine_key(const latte_engine_t* e, int i) { return e ? e->weights.key(i) : nullptr; }
 
 int latte_engine_set_option(latte_engine_t* e, const char* name, int64_t value) {
   if (!e || !name) return fail(LATTE_ERR_INVALID, "set_option: null argument");
@@ -672,19 +631,12 @@ int latte_engine_get_option(const latte_engine_t* e, const char* name, int64_t* 
 int latte_engine_load_tensor(latte_engine_t* e, const char* key, const float* data, int64_t numel, int on_device,
                              void* stream) {
   if (!e || !key || !data) return fail(LATTE_ERR_INVALID, "load_tensor: null argument");
-  auto it = e->slot_index.find(key);
-  if (it == e->slot_index.end()) return fail(LATTE_ERR_INVALID, std::string("load_tensor: unexpected key '") + key + "'");
-  TensorSlot& s = e->slots[it->second];
-  if (numel != s.numel)
-    return fail(LATTE_ERR_INVALID, std::string("load_tensor: size mismatch for '") + key + "': got " + std::to_string(numel) +
-                                       ", expected " + std::to_string(s.numel));
   hipStream_t st = (hipStream_t)stream;
-  const float* src = data;
-  if (!on_device) {
-    LATTE_HIP(hipMemcpyAsync(e->stage, data, sizeof(float) * numel, hipMemcpyHostToDevice, st));
-    src = e->stage;
-  }
-  int rc = LATTE_OK;
+  WeightSlot* slot = nullptr;
+  const float* src = nullptr;
+  int rc = e->weights.begin_load("load_tensor", key, data, numel, on_device, st, &slot, &src);
+  if (rc) return rc;
+  WeightSlot& s = *slot;
   switch (s.kind) {
     case PK_F32:
       LATTE_HIP(hipMemcpyAsync(s.dst, src, sizeof(float) * numel, hipMemcpyDeviceToDevice, st));
@@ -696,9 +648,7 @@ int latte_engine_load_tensor(latte_engine_t* e, const char* key, const float* da
       rc = launch_convert_f32_to_h16(src, (half_t*)s.dst, numel, e->cfg.compute_dtype, st);
       break;
   }
-  if (rc) return rc;
-  if (!on_device) LATTE_HIP(hipStreamSynchronize(st));  // the staging buffer is reused by the next call
-  s.loaded = true;
+  if (rc || (rc = e->weights.end_load(s, on_device, st))) return rc;
   if (s.kind == PK_H16) {   // a block weight changed: the derived copies ([W | W], W8) are stale and must be rebuilt BEHIND this conversion
     e->split_w_ready = false;
     if (!e->load_event) LATTE_HIP(hipEventCreateWithFlags(&e->load_event, hipEventDisableTiming));
@@ -714,9 +664,7 @@ int latte_engine_load_tensor(latte_engine_t* e, const char* key, const float* da
 
 int latte_engine_check_weights(latte_engine_t* e) {
   if (!e) return fail(LATTE_ERR_INVALID, "check_weights: null engine");
-  for (const auto& s : e->slots)
-    if (!s.loaded) return fail(LATTE_ERR_STATE, "Missing key(s) in state_dict: \"" + s.key + "\"");
-  return LATTE_OK;
+  return e->weights.check_loaded();
 }
 
 int latte_engine_temb_table(latte_engine_t* e, const latte_schedule_t* s, float* out, void* stream) {

@@ -18,26 +18,17 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/latte_amd.h"
-#include "common.h"
+#include "weight_store.h"
 
 using namespace latte;
 
 namespace {
 
-enum T2VKind { TK_F32, TK_F32_TRANSPOSE, TK_H16, TK_SKIP };
-struct T2VSlot {
-  std::string key;
-  int64_t numel;
-  T2VKind kind;
-  void* dst;
-  int rows, cols;
-  bool loaded = false;
-};
+enum T2VKind { TK_F32, TK_F32_TRANSPOSE, TK_H16 };   // WeightSlot::kind
 
 struct T2VBlock {
   half_t *qkv_w, *o_w, *q2_w, *kv2_w, *o2_w, *fc1_w, *fc2_w;   // q2 / kv2 / o2: spatial blocks only
@@ -71,7 +62,7 @@ struct latte_t2v {
         *fin_b = nullptr, *cap1_b = nullptr, *cap2_b = nullptr, *ones = nullptr;
   half_t *cap1_w = nullptr, *cap2_w = nullptr;
   float *xin = nullptr, *xres = nullptr, *temb0 = nullptr, *temb = nullptr, *t6 = nullptr, *mod = nullptr, *out_bf = nullptr,
-        *kbias = nullptr, *stage = nullptr;
+        *kbias = nullptr;
   half_t *xn = nullptr, *qkv = nullptr, *hbuf = nullptr, *ctx_in = nullptr, *ctx1 = nullptr, *ctx = nullptr, *kv = nullptr;
   // text context of a chain (latte_t2v_set_text): cross-attention K|V of EVERY spatial block + the additive mask bias,
   // functions of the text alone, computed once instead of once per denoising step
@@ -80,33 +71,9 @@ struct latte_t2v {
   bool txt_has_mask = false;
   int64_t* tsteps = nullptr;        // device copy of a chain's timesteps (latte_t2v_guided_ddim_loop)
   int tsteps_cap = 0;
-  int64_t stage_numel = 0;
-  std::vector<T2VSlot> slots;
-  std::map<std::string, int> slot_index;
-  std::vector<void*> allocs;
+  WeightSlots weights;
+  DeviceArena arena;
 };
-
-namespace {
-
-template <typename Tp>
-int t2v_alloc(latte_t2v* e, Tp** p, size_t count) {
-  void* q = nullptr;
-  const size_t bytes = std::max<size_t>(count * sizeof(Tp), 16);
-  LATTE_HIP(hipMalloc(&q, bytes));
-  LATTE_HIP(hipMemset(q, 0, bytes));
-  e->allocs.push_back(q);
-  *p = (Tp*)q;
-  return LATTE_OK;
-}
-
-void t2v_slot(latte_t2v* e, const std::string& key, int64_t numel, T2VKind kind, void* dst, int rows = 0, int cols = 0) {
-  T2VSlot s{key, numel, kind, dst, rows, cols};
-  e->slot_index[key] = (int)e->slots.size();
-  e->slots.push_back(s);
-  if (numel > e->stage_numel) e->stage_numel = numel;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -147,87 +114,87 @@ int latte_t2v_create(const latte_t2v_config_t* cfg, int max_batch, latte_t2v_t**
   e->trows_pad = ((int64_t)max_batch * e->maxk + 255) / 256 * 256;
   int rc = LATTE_OK;
 #define TRY(x) do { if ((rc = (x))) { latte_t2v_destroy(e); return rc; } } while (0)
-  TRY(t2v_alloc(e, &e->tables, (size_t)e->nblk * 6 * D));
-  TRY(t2v_alloc(e, &e->head_table, (size_t)2 * D));
-  TRY(t2v_alloc(e, &e->pos, (size_t)e->T * D));
-  TRY(t2v_alloc(e, &e->temp, (size_t)e->F * D));
-  TRY(t2v_alloc(e, &e->pe_wt, (size_t)e->KPE * D));
-  TRY(t2v_alloc(e, &e->pe_b, (size_t)D));
-  TRY(t2v_alloc(e, &e->t1_w, (size_t)D * 256));
-  TRY(t2v_alloc(e, &e->t1_b, (size_t)D));
-  TRY(t2v_alloc(e, &e->t2_w, (size_t)D * D));
-  TRY(t2v_alloc(e, &e->t2_b, (size_t)D));
-  TRY(t2v_alloc(e, &e->ada_w, (size_t)6 * D * D));
-  TRY(t2v_alloc(e, &e->ada_b, (size_t)6 * D));
-  TRY(t2v_alloc(e, &e->fin_wt, (size_t)D * e->P));
-  TRY(t2v_alloc(e, &e->fin_b, (size_t)e->P));
-  TRY(t2v_alloc(e, &e->cap1_w, (size_t)D * e->Cc));
-  TRY(t2v_alloc(e, &e->cap1_b, (size_t)D));
-  TRY(t2v_alloc(e, &e->cap2_w, (size_t)D * D));
-  TRY(t2v_alloc(e, &e->cap2_b, (size_t)D));
-  TRY(t2v_alloc(e, &e->ones, (size_t)D));
+  TRY(e->arena.alloc(&e->tables, (size_t)e->nblk * 6 * D));
+  TRY(e->arena.alloc(&e->head_table, (size_t)2 * D));
+  TRY(e->arena.alloc(&e->pos, (size_t)e->T * D));
+  TRY(e->arena.alloc(&e->temp, (size_t)e->F * D));
+  TRY(e->arena.alloc(&e->pe_wt, (size_t)e->KPE * D));
+  TRY(e->arena.alloc(&e->pe_b, (size_t)D));
+  TRY(e->arena.alloc(&e->t1_w, (size_t)D * 256));
+  TRY(e->arena.alloc(&e->t1_b, (size_t)D));
+  TRY(e->arena.alloc(&e->t2_w, (size_t)D * D));
+  TRY(e->arena.alloc(&e->t2_b, (size_t)D));
+  TRY(e->arena.alloc(&e->ada_w, (size_t)6 * D * D));
+  TRY(e->arena.alloc(&e->ada_b, (size_t)6 * D));
+  TRY(e->arena.alloc(&e->fin_wt, (size_t)D * e->P));
+  TRY(e->arena.alloc(&e->fin_b, (size_t)e->P));
+  TRY(e->arena.alloc(&e->cap1_w, (size_t)D * e->Cc));
+  TRY(e->arena.alloc(&e->cap1_b, (size_t)D));
+  TRY(e->arena.alloc(&e->cap2_w, (size_t)D * D));
+  TRY(e->arena.alloc(&e->cap2_b, (size_t)D));
+  TRY(e->arena.alloc(&e->ones, (size_t)D));
   TRY(launch_fill_f32(e->ones, 1.0f, (size_t)D, nullptr));
 
-  t2v_slot(e, "scale_shift_table", 2 * D, TK_F32, e->head_table);
-  t2v_slot(e, "pos_embed.proj.weight", (int64_t)D * e->KPE, TK_F32_TRANSPOSE, e->pe_wt, D, e->KPE);
-  t2v_slot(e, "pos_embed.proj.bias", D, TK_F32, e->pe_b);
-  t2v_slot(e, "adaln_single.emb.timestep_embedder.linear_1.weight", (int64_t)D * 256, TK_F32, e->t1_w);
-  t2v_slot(e, "adaln_single.emb.timestep_embedder.linear_1.bias", D, TK_F32, e->t1_b);
-  t2v_slot(e, "adaln_single.emb.timestep_embedder.linear_2.weight", (int64_t)D * D, TK_F32, e->t2_w);
-  t2v_slot(e, "adaln_single.emb.timestep_embedder.linear_2.bias", D, TK_F32, e->t2_b);
-  t2v_slot(e, "adaln_single.linear.weight", (int64_t)6 * D * D, TK_F32, e->ada_w);
-  t2v_slot(e, "adaln_single.linear.bias", 6 * D, TK_F32, e->ada_b);
-  t2v_slot(e, "caption_projection.linear_1.weight", (int64_t)D * e->Cc, TK_H16, e->cap1_w);
-  t2v_slot(e, "caption_projection.linear_1.bias", D, TK_F32, e->cap1_b);
-  t2v_slot(e, "caption_projection.linear_2.weight", (int64_t)D * D, TK_H16, e->cap2_w);
-  t2v_slot(e, "caption_projection.linear_2.bias", D, TK_F32, e->cap2_b);
-  t2v_slot(e, "caption_projection.y_embedding", (int64_t)120 * e->Cc, TK_SKIP, nullptr);   // null-caption buffer, unused at inference
-  t2v_slot(e, "proj_out.weight", (int64_t)e->P * D, TK_F32_TRANSPOSE, e->fin_wt, e->P, D);
-  t2v_slot(e, "proj_out.bias", e->P, TK_F32, e->fin_b);
+  e->weights.add("scale_shift_table", 2 * D, TK_F32, e->head_table);
+  e->weights.add("pos_embed.proj.weight", (int64_t)D * e->KPE, TK_F32_TRANSPOSE, e->pe_wt, D, e->KPE);
+  e->weights.add("pos_embed.proj.bias", D, TK_F32, e->pe_b);
+  e->weights.add("adaln_single.emb.timestep_embedder.linear_1.weight", (int64_t)D * 256, TK_F32, e->t1_w);
+  e->weights.add("adaln_single.emb.timestep_embedder.linear_1.bias", D, TK_F32, e->t1_b);
+  e->weights.add("adaln_single.emb.timestep_embedder.linear_2.weight", (int64_t)D * D, TK_F32, e->t2_w);
+  e->weights.add("adaln_single.emb.timestep_embedder.linear_2.bias", D, TK_F32, e->t2_b);
+  e->weights.add("adaln_single.linear.weight", (int64_t)6 * D * D, TK_F32, e->ada_w);
+  e->weights.add("adaln_single.linear.bias", 6 * D, TK_F32, e->ada_b);
+  e->weights.add("caption_projection.linear_1.weight", (int64_t)D * e->Cc, TK_H16, e->cap1_w);
+  e->weights.add("caption_projection.linear_1.bias", D, TK_F32, e->cap1_b);
+  e->weights.add("caption_projection.linear_2.weight", (int64_t)D * D, TK_H16, e->cap2_w);
+  e->weights.add("caption_projection.linear_2.bias", D, TK_F32, e->cap2_b);
+  e->weights.add("caption_projection.y_embedding", (int64_t)120 * e->Cc, TK_F32, nullptr).optional = true;   // null-caption buffer, unused at inference
+  e->weights.add("proj_out.weight", (int64_t)e->P * D, TK_F32_TRANSPOSE, e->fin_wt, e->P, D);
+  e->weights.add("proj_out.bias", e->P, TK_F32, e->fin_b);
 
   e->blocks.resize(e->nblk);
   for (int i = 0; i < e->nblk; ++i) {
     T2VBlock& w = e->blocks[i];
     const bool spatial = (i % 2) == 0;
     const std::string p = std::string(spatial ? "transformer_blocks." : "temporal_transformer_blocks.") + std::to_string(i / 2) + ".";
-    TRY(t2v_alloc(e, &w.qkv_w, (size_t)3 * D * D));
-    TRY(t2v_alloc(e, &w.qkv_b, (size_t)3 * D));
-    TRY(t2v_alloc(e, &w.o_w, (size_t)D * D));
-    TRY(t2v_alloc(e, &w.o_b, (size_t)D));
-    TRY(t2v_alloc(e, &w.fc1_w, (size_t)e->Hm * D));
-    TRY(t2v_alloc(e, &w.fc1_b, (size_t)e->Hm));
-    TRY(t2v_alloc(e, &w.fc2_w, (size_t)D * e->Hm));
-    TRY(t2v_alloc(e, &w.fc2_b, (size_t)D));
-    t2v_slot(e, p + "scale_shift_table", 6 * D, TK_F32, e->tables + (size_t)i * 6 * D);
+    TRY(e->arena.alloc(&w.qkv_w, (size_t)3 * D * D));
+    TRY(e->arena.alloc(&w.qkv_b, (size_t)3 * D));
+    TRY(e->arena.alloc(&w.o_w, (size_t)D * D));
+    TRY(e->arena.alloc(&w.o_b, (size_t)D));
+    TRY(e->arena.alloc(&w.fc1_w, (size_t)e->Hm * D));
+    TRY(e->arena.alloc(&w.fc1_b, (size_t)e->Hm));
+    TRY(e->arena.alloc(&w.fc2_w, (size_t)D * e->Hm));
+    TRY(e->arena.alloc(&w.fc2_b, (size_t)D));
+    e->weights.add(p + "scale_shift_table", 6 * D, TK_F32, e->tables + (size_t)i * 6 * D);
     // to_q | to_k | to_v concatenated: one fused GEMM, columns ordered [3][heads][hd] like latte.py:50
-    t2v_slot(e, p + "attn1.to_q.weight", (int64_t)D * D, TK_H16, w.qkv_w);
-    t2v_slot(e, p + "attn1.to_k.weight", (int64_t)D * D, TK_H16, w.qkv_w + (size_t)D * D);
-    t2v_slot(e, p + "attn1.to_v.weight", (int64_t)D * D, TK_H16, w.qkv_w + (size_t)2 * D * D);
-    t2v_slot(e, p + "attn1.to_q.bias", D, TK_F32, w.qkv_b);
-    t2v_slot(e, p + "attn1.to_k.bias", D, TK_F32, w.qkv_b + D);
-    t2v_slot(e, p + "attn1.to_v.bias", D, TK_F32, w.qkv_b + 2 * D);
-    t2v_slot(e, p + "attn1.to_out.0.weight", (int64_t)D * D, TK_H16, w.o_w);
-    t2v_slot(e, p + "attn1.to_out.0.bias", D, TK_F32, w.o_b);
+    e->weights.add(p + "attn1.to_q.weight", (int64_t)D * D, TK_H16, w.qkv_w);
+    e->weights.add(p + "attn1.to_k.weight", (int64_t)D * D, TK_H16, w.qkv_w + (size_t)D * D);
+    e->weights.add(p + "attn1.to_v.weight", (int64_t)D * D, TK_H16, w.qkv_w + (size_t)2 * D * D);
+    e->weights.add(p + "attn1.to_q.bias", D, TK_F32, w.qkv_b);
+    e->weights.add(p + "attn1.to_k.bias", D, TK_F32, w.qkv_b + D);
+    e->weights.add(p + "attn1.to_v.bias", D, TK_F32, w.qkv_b + 2 * D);
+    e->weights.add(p + "attn1.to_out.0.weight", (int64_t)D * D, TK_H16, w.o_w);
+    e->weights.add(p + "attn1.to_out.0.bias", D, TK_F32, w.o_b);
     if (spatial) {
-      TRY(t2v_alloc(e, &w.q2_w, (size_t)D * D));
-      TRY(t2v_alloc(e, &w.q2_b, (size_t)D));
-      TRY(t2v_alloc(e, &w.kv2_w, (size_t)2 * D * D));
-      TRY(t2v_alloc(e, &w.kv2_b, (size_t)2 * D));
-      TRY(t2v_alloc(e, &w.o2_w, (size_t)D * D));
-      TRY(t2v_alloc(e, &w.o2_b, (size_t)D));
-      t2v_slot(e, p + "attn2.to_q.weight", (int64_t)D * D, TK_H16, w.q2_w);
-      t2v_slot(e, p + "attn2.to_q.bias", D, TK_F32, w.q2_b);
-      t2v_slot(e, p + "attn2.to_k.weight", (int64_t)D * D, TK_H16, w.kv2_w);
-      t2v_slot(e, p + "attn2.to_v.weight", (int64_t)D * D, TK_H16, w.kv2_w + (size_t)D * D);
-      t2v_slot(e, p + "attn2.to_k.bias", D, TK_F32, w.kv2_b);
-      t2v_slot(e, p + "attn2.to_v.bias", D, TK_F32, w.kv2_b + D);
-      t2v_slot(e, p + "attn2.to_out.0.weight", (int64_t)D * D, TK_H16, w.o2_w);
-      t2v_slot(e, p + "attn2.to_out.0.bias", D, TK_F32, w.o2_b);
+      TRY(e->arena.alloc(&w.q2_w, (size_t)D * D));
+      TRY(e->arena.alloc(&w.q2_b, (size_t)D));
+      TRY(e->arena.alloc(&w.kv2_w, (size_t)2 * D * D));
+      TRY(e->arena.alloc(&w.kv2_b, (size_t)2 * D));
+      TRY(e->arena.alloc(&w.o2_w, (size_t)D * D));
+      TRY(e->arena.alloc(&w.o2_b, (size_t)D));
+      e->weights.add(p + "attn2.to_q.weight", (int64_t)D * D, TK_H16, w.q2_w);
+      e->weights.add(p + "attn2.to_q.bias", D, TK_F32, w.q2_b);
+      e->weights.add(p + "attn2.to_k.weight", (int64_t)D * D, TK_H16, w.kv2_w);
+      e->weights.add(p + "attn2.to_v.weight", (int64_t)D * D, TK_H16, w.kv2_w + (size_t)D * D);
+      e->weights.add(p + "attn2.to_k.bias", D, TK_F32, w.kv2_b);
+      e->weights.add(p + "attn2.to_v.bias", D, TK_F32, w.kv2_b + D);
+      e->weights.add(p + "attn2.to_out.0.weight", (int64_t)D * D, TK_H16, w.o2_w);
+      e->weights.add(p + "attn2.to_out.0.bias", D, TK_F32, w.o2_b);
     }
-    t2v_slot(e, p + "ff.net.0.proj.weight", (int64_t)e->Hm * D, TK_H16, w.fc1_w);
-    t2v_slot(e, p + "ff.net.0.proj.bias", e->Hm, TK_F32, w.fc1_b);
-    t2v_slot(e, p + "ff.net.2.weight", (int64_t)D * e->Hm, TK_H16, w.fc2_w);
-    t2v_slot(e, p + "ff.net.2.bias", D, TK_F32, w.fc2_b);
+    e->weights.add(p + "ff.net.0.proj.weight", (int64_t)e->Hm * D, TK_H16, w.fc1_w);
+    e->weights.add(p + "ff.net.0.proj.bias", e->Hm, TK_F32, w.fc1_b);
+    e->weights.add(p + "ff.net.2.weight", (int64_t)D * e->Hm, TK_H16, w.fc2_w);
+    e->weights.add(p + "ff.net.2.bias", D, TK_F32, w.fc2_b);
   }
 
   // fixed tables (non-persistent buffers of the reference: PatchEmbed.pos_embed, temp_pos_embed, latte_t2v.py:571-581,670-671)
@@ -257,25 +224,25 @@ int latte_t2v_create(const latte_t2v_config_t* cfg, int max_batch, latte_t2v_t**
   }
 
   const int64_t R = e->rows_pad, TR = e->trows_pad;
-  TRY(t2v_alloc(e, &e->stage, (size_t)e->stage_numel));
-  TRY(t2v_alloc(e, &e->xin, (size_t)max_batch * e->F * c.in_channels * e->H * e->H));
-  TRY(t2v_alloc(e, &e->out_bf, (size_t)max_batch * e->F * c.out_channels * e->H * e->H));
-  TRY(t2v_alloc(e, &e->xres, (size_t)R * D));
-  TRY(t2v_alloc(e, &e->xn, (size_t)R * D));
-  TRY(t2v_alloc(e, &e->qkv, (size_t)R * 3 * D));
-  TRY(t2v_alloc(e, &e->hbuf, (size_t)R * e->Hm));
-  TRY(t2v_alloc(e, &e->ctx_in, (size_t)TR * e->Cc));
-  TRY(t2v_alloc(e, &e->ctx1, (size_t)TR * D));
-  TRY(t2v_alloc(e, &e->ctx, (size_t)TR * D));
-  TRY(t2v_alloc(e, &e->kv, (size_t)TR * 2 * D));
-  TRY(t2v_alloc(e, &e->kv_all, (size_t)c.num_layers * TR * 2 * D));
-  TRY(t2v_alloc(e, &e->tsteps, (size_t)1024));
+  TRY(e->weights.alloc_stage(e->arena, true));
+  TRY(e->arena.alloc(&e->xin, (size_t)max_batch * e->F * c.in_channels * e->H * e->H));
+  TRY(e->arena.alloc(&e->out_bf, (size_t)max_batch * e->F * c.out_channels * e->H * e->H));
+  TRY(e->arena.alloc(&e->xres, (size_t)R * D));
+  TRY(e->arena.alloc(&e->xn, (size_t)R * D));
+  TRY(e->arena.alloc(&e->qkv, (size_t)R * 3 * D));
+  TRY(e->arena.alloc(&e->hbuf, (size_t)R * e->Hm));
+  TRY(e->arena.alloc(&e->ctx_in, (size_t)TR * e->Cc));
+  TRY(e->arena.alloc(&e->ctx1, (size_t)TR * D));
+  TRY(e->arena.alloc(&e->ctx, (size_t)TR * D));
+  TRY(e->arena.alloc(&e->kv, (size_t)TR * 2 * D));
+  TRY(e->arena.alloc(&e->kv_all, (size_t)c.num_layers * TR * 2 * D));
+  TRY(e->arena.alloc(&e->tsteps, (size_t)1024));
   e->tsteps_cap = 1024;
-  TRY(t2v_alloc(e, &e->kbias, (size_t)max_batch * e->maxk));
-  TRY(t2v_alloc(e, &e->temb0, (size_t)max_batch * D));
-  TRY(t2v_alloc(e, &e->temb, (size_t)max_batch * D));
-  TRY(t2v_alloc(e, &e->t6, (size_t)max_batch * 6 * D));
-  TRY(t2v_alloc(e, &e->mod, (size_t)max_batch * (6 * e->nblk + 2) * D));
+  TRY(e->arena.alloc(&e->kbias, (size_t)max_batch * e->maxk));
+  TRY(e->arena.alloc(&e->temb0, (size_t)max_batch * D));
+  TRY(e->arena.alloc(&e->temb, (size_t)max_batch * D));
+  TRY(e->arena.alloc(&e->t6, (size_t)max_batch * 6 * D));
+  TRY(e->arena.alloc(&e->mod, (size_t)max_batch * (6 * e->nblk + 2) * D));
 #undef TRY
   LATTE_HIP(hipDeviceSynchronize());
   *out = e;
@@ -283,42 +250,26 @@ int latte_t2v_create(const latte_t2v_config_t* cfg, int max_batch, latte_t2v_t**
 }
 
 void latte_t2v_destroy(latte_t2v_t* e) {
-  if (!e) return;
-  for (void* p : e->allocs) (void)hipFree(p);
-  delete e;
+  delete e;   // the arena frees every device block
 }
 
-int latte_t2v_num_keys(const latte_t2v_t* e) { return e ? (int)e->slots.size() : 0; }
-const char* latte_t2v_key(const latte_t2v_t* e, int i) {
-  if (!e || i < 0 || i >= (int)e->slots.size()) return nullptr;
-  return e->slots[i].key.c_str();
-}
+int latte_t2v_num_keys(const latte_t2v_t* e) { return e ? e->weights.size() : 0; }
+const char* latte_t2v_key(const latte_t2v_t* e, int i) { return e ? e->weights.key(i) : nullptr; }
 
 int latte_t2v_load_tensor(latte_t2v_t* e, const char* key, const float* data, int64_t numel, int on_device, void* stream) {
   if (!e || !key || !data) return fail(LATTE_ERR_INVALID, "t2v_load_tensor: null argument");
-  auto it = e->slot_index.find(key);
-  if (it == e->slot_index.end()) return fail(LATTE_ERR_INVALID, std::string("t2v_load_tensor: unexpected key '") + key + "'");
-  T2VSlot& s = e->slots[it->second];
-  if (s.kind == TK_SKIP) { s.loaded = true; return LATTE_OK; }
-  if (numel != s.numel)
-    return fail(LATTE_ERR_INVALID, std::string("t2v_load_tensor: size mismatch for '") + key + "': got " + std::to_string(numel) +
-                                       ", expected " + std::to_string(s.numel));
   hipStream_t st = (hipStream_t)stream;
-  const float* src = data;
-  if (!on_device) {
-    LATTE_HIP(hipMemcpyAsync(e->stage, data, sizeof(float) * numel, hipMemcpyHostToDevice, st));
-    src = e->stage;
-  }
-  int rc = LATTE_OK;
+  WeightSlot* slot = nullptr;
+  const float* src = nullptr;
+  int rc = e->weights.begin_load("t2v_load_tensor", key, data, numel, on_device, st, &slot, &src);
+  if (rc || slot->optional) return rc;
+  WeightSlot& s = *slot;
   switch (s.kind) {
     case TK_F32: LATTE_HIP(hipMemcpyAsync(s.dst, src, sizeof(float) * numel, hipMemcpyDeviceToDevice, st)); break;
     case TK_F32_TRANSPOSE: rc = launch_transpose_f32(src, (float*)s.dst, s.rows, s.cols, st); break;
     case TK_H16: rc = launch_convert_f32_to_h16(src, (half_t*)s.dst, numel, e->cfg.compute_dtype, st); break;
-    default: break;
   }
-  if (rc) return rc;
-  if (!on_device) LATTE_HIP(hipStreamSynchronize(st));
-  s.loaded = true;
+  if (rc || (rc = e->weights.end_load(s, on_device, st))) return rc;
   e->txt_batch = 0;   // an installed text context was projected with the old weights
   return LATTE_OK;
 }
@@ -335,9 +286,7 @@ int latte_t2v_set_option(latte_t2v_t* e, const char* name, int64_t value) {
 
 int latte_t2v_check_weights(latte_t2v_t* e) {
   if (!e) return fail(LATTE_ERR_INVALID, "t2v_check_weights: null engine");
-  for (const auto& s : e->slots)
-    if (!s.loaded && s.kind != TK_SKIP) return fail(LATTE_ERR_STATE, "Missing key(s) in state_dict: \"" + s.key + "\"");
-  return LATTE_OK;
+  return e->weights.check_loaded();
 }
 
 // Text context: caption projection (latte_t2v.py:781-793: Linear -> GELU(tanh) -> Linear on [B * Lk, caption_channels]),

@@ -1,25 +1,15 @@
 // Host side of the T5 v1.1 encoder (latte_t5_* in include/latte_amd.h): weight slots under the transformers key names, the
 // workspace, the relative-position buckets, and the launch sequence of one encode.  Kernels: t5.hip.
 #include <cmath>
-#include <map>
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "weight_store.h"
 
 using namespace latte;
 
 namespace {
-enum T5Pack : int { TP_F32 = 0, TP_SPLIT };
-struct T5Slot {
-  std::string key;
-  std::vector<int64_t> shape;
-  int kind;
-  void* dst;       // fp32 destination, or the hi half of a split pair
-  void* dst_lo;
-  int group;       // slots of one group fill the same destination (the tied embedding): one loaded member satisfies all
-  bool loaded;
-};
+enum T5Pack : int { TP_F32 = 0, TP_SPLIT };   // WeightSlot::kind; TP_SPLIT fills the pair dst / dst_lo
 struct T5Layer {
   half_t *qkv_hi, *qkv_lo, *o_hi, *o_lo, *wi_hi, *wi_lo, *wo_hi, *wo_lo;
   float *ln0, *ln1;
@@ -29,9 +19,8 @@ struct T5Layer {
 struct latte_t5 {
   latte_t5_config_t cfg;
   int max_batch, max_len, inner;
-  std::vector<void*> allocs;
-  std::vector<T5Slot> slots;
-  std::map<std::string, int> index;
+  DeviceArena arena;
+  WeightSlots weights;
   std::vector<T5Layer> layers;
   float *emb = nullptr, *rel = nullptr, *table = nullptr, *final_ln = nullptr;
   int* bucket = nullptr;
@@ -43,20 +32,14 @@ struct latte_t5 {
 
 namespace {
 
-template <typename T>
-int t5_alloc(latte_t5* t, T** p, size_t n, bool zero = false) {
-  void* q = nullptr;
-  if (hipMalloc(&q, sizeof(T) * n) != hipSuccess)
-    return fail(LATTE_ERR_HIP, "t5: device allocation of " + std::to_string(sizeof(T) * n) + " bytes failed");
-  t->allocs.push_back(q);
-  if (zero && hipMemset(q, 0, sizeof(T) * n) != hipSuccess) return fail(LATTE_ERR_HIP, "t5: memset failed");
-  *p = (T*)q;
-  return LATTE_OK;
-}
-
+// a slot with its expected shape; `group` 0: the tied embedding, filled by either of its two names
 void t5_slot(latte_t5* t, const std::string& key, std::vector<int64_t> shape, int kind, void* dst, void* dst_lo = nullptr, int group = -1) {
-  t->index[key] = (int)t->slots.size();
-  t->slots.push_back(T5Slot{key, std::move(shape), kind, dst, dst_lo, group, false});
+  int64_t numel = 1;
+  for (int64_t d : shape) numel *= d;
+  WeightSlot& s = t->weights.add(key, numel, kind, dst);
+  s.shape = std::move(shape);
+  s.dst_lo = dst_lo;
+  s.group = group;
 }
 
 // T5Attention._relative_position_bucket (bidirectional) for rel = key - query, in the fp32 arithmetic of the reference:
@@ -102,22 +85,22 @@ int latte_t5_create(const latte_t5_config_t* c, int max_batch, int max_len, latt
   t->inner = inner;
   int rc;
 #define TRY(x) do { if ((rc = (x))) { latte_t5_destroy(t); return rc; } } while (0)
-  TRY(t5_alloc(t, &t->emb, (size_t)c->vocab_size * D));
+  TRY(t->arena.alloc(&t->emb, (size_t)c->vocab_size * D, false));
   t5_slot(t, "shared.weight", {c->vocab_size, D}, TP_F32, t->emb, nullptr, 0);
   t5_slot(t, "encoder.embed_tokens.weight", {c->vocab_size, D}, TP_F32, t->emb, nullptr, 0);
-  TRY(t5_alloc(t, &t->rel, (size_t)nbk * H));
-  TRY(t5_alloc(t, &t->table, (size_t)H * (2 * max_len - 1)));
-  TRY(t5_alloc(t, &t->bucket, (size_t)2 * max_len - 1));
+  TRY(t->arena.alloc(&t->rel, (size_t)nbk * H, false));
+  TRY(t->arena.alloc(&t->table, (size_t)H * (2 * max_len - 1), false));
+  TRY(t->arena.alloc(&t->bucket, (size_t)2 * max_len - 1, false));
   TRY(t5_upload_buckets(t->bucket, nbk, c->relative_attention_max_distance, max_len));
   t->layers.resize(c->num_layers);
   for (int i = 0; i < c->num_layers; ++i) {
     T5Layer& l = t->layers[i];
     const std::string a = "encoder.block." + std::to_string(i) + ".layer.0.", f = "encoder.block." + std::to_string(i) + ".layer.1.";
-    TRY(t5_alloc(t, &l.qkv_hi, (size_t)3 * inner * D)); TRY(t5_alloc(t, &l.qkv_lo, (size_t)3 * inner * D));
-    TRY(t5_alloc(t, &l.o_hi, (size_t)D * inner)); TRY(t5_alloc(t, &l.o_lo, (size_t)D * inner));
-    TRY(t5_alloc(t, &l.wi_hi, (size_t)2 * F * D)); TRY(t5_alloc(t, &l.wi_lo, (size_t)2 * F * D));
-    TRY(t5_alloc(t, &l.wo_hi, (size_t)D * F)); TRY(t5_alloc(t, &l.wo_lo, (size_t)D * F));
-    TRY(t5_alloc(t, &l.ln0, D)); TRY(t5_alloc(t, &l.ln1, D));
+    TRY(t->arena.alloc(&l.qkv_hi, (size_t)3 * inner * D, false)); TRY(t->arena.alloc(&l.qkv_lo, (size_t)3 * inner * D, false));
+    TRY(t->arena.alloc(&l.o_hi, (size_t)D * inner, false)); TRY(t->arena.alloc(&l.o_lo, (size_t)D * inner, false));
+    TRY(t->arena.alloc(&l.wi_hi, (size_t)2 * F * D, false)); TRY(t->arena.alloc(&l.wi_lo, (size_t)2 * F * D, false));
+    TRY(t->arena.alloc(&l.wo_hi, (size_t)D * F, false)); TRY(t->arena.alloc(&l.wo_lo, (size_t)D * F, false));
+    TRY(t->arena.alloc(&l.ln0, D, false)); TRY(t->arena.alloc(&l.ln1, D, false));
     const char* qkv_names[3] = {"q", "k", "v"};
     for (int j = 0; j < 3; ++j)
       t5_slot(t, a + "SelfAttention." + qkv_names[j] + ".weight", {inner, D}, TP_SPLIT, l.qkv_hi + (size_t)j * inner * D,
@@ -130,41 +113,36 @@ int latte_t5_create(const latte_t5_config_t* c, int max_batch, int max_len, latt
     t5_slot(t, f + "DenseReluDense.wo.weight", {D, F}, TP_SPLIT, l.wo_hi, l.wo_lo);
     t5_slot(t, f + "layer_norm.weight", {D}, TP_F32, l.ln1);
   }
-  TRY(t5_alloc(t, &t->final_ln, D));
+  TRY(t->arena.alloc(&t->final_ln, D, false));
   t5_slot(t, "encoder.final_layer_norm.weight", {D}, TP_F32, t->final_ln);
   // workspace: operand pairs in whole 256-row blocks (the projection stages rows past M, results of those rows are never stored)
   const size_t M = (size_t)max_batch * max_len, Mp = round256(M);
-  TRY(t5_alloc(t, &t->x, M * D));
-  TRY(t5_alloc(t, &t->n_hi, Mp * D, true)); TRY(t5_alloc(t, &t->n_lo, Mp * D, true));
-  TRY(t5_alloc(t, &t->c_hi, Mp * inner, true)); TRY(t5_alloc(t, &t->c_lo, Mp * inner, true));
-  TRY(t5_alloc(t, &t->a_hi, Mp * F, true)); TRY(t5_alloc(t, &t->a_lo, Mp * F, true));
-  TRY(t5_alloc(t, &t->qkv, M * 3 * inner));
+  TRY(t->arena.alloc(&t->x, M * D, false));
+  TRY(t->arena.alloc(&t->n_hi, Mp * D)); TRY(t->arena.alloc(&t->n_lo, Mp * D));
+  TRY(t->arena.alloc(&t->c_hi, Mp * inner)); TRY(t->arena.alloc(&t->c_lo, Mp * inner));
+  TRY(t->arena.alloc(&t->a_hi, Mp * F)); TRY(t->arena.alloc(&t->a_lo, Mp * F));
+  TRY(t->arena.alloc(&t->qkv, M * 3 * inner, false));
   size_t slab = 0;
   const int shapes[4][2] = {{3 * inner, D}, {D, inner}, {2 * F, D}, {D, F}};
   for (auto& s : shapes) slab = std::max(slab, (size_t)t5_proj_splits(s[0], s[1]) * M * s[0]);
-  TRY(t5_alloc(t, &t->slabs, slab));
+  TRY(t->arena.alloc(&t->slabs, slab, false));
 #undef TRY
   *out = t;
   return LATTE_OK;
 }
 
 void latte_t5_destroy(latte_t5_t* t) {
-  if (!t) return;
-  for (void* p : t->allocs) (void)hipFree(p);
-  delete t;
+  delete t;   // the arena frees every device block
 }
 
-int latte_t5_num_keys(const latte_t5_t* t) { return t ? (int)t->slots.size() : 0; }
-const char* latte_t5_key(const latte_t5_t* t, int i) {
-  if (!t || i < 0 || i >= (int)t->slots.size()) return nullptr;
-  return t->slots[i].key.c_str();
-}
+int latte_t5_num_keys(const latte_t5_t* t) { return t ? t->weights.size() : 0; }
+const char* latte_t5_key(const latte_t5_t* t, int i) { return t ? t->weights.key(i) : nullptr; }
 
 int latte_t5_load_weight(latte_t5_t* t, const char* key, const float* data, const int64_t* shape, int ndim, void* stream) {
   if (!t || !key || !data || !shape) return fail(LATTE_ERR_INVALID, "t5_load_weight: null argument");
-  auto it = t->index.find(key);
-  if (it == t->index.end()) return fail(LATTE_ERR_INVALID, std::string("t5_load_weight: unexpected key '") + key + "'");
-  T5Slot& s = t->slots[it->second];
+  WeightSlot* slot = nullptr;
+  if (int rc = t->weights.find("t5_load_weight", key, &slot)) return rc;
+  WeightSlot& s = *slot;
   bool same = ndim == (int)s.shape.size();
   for (int i = 0; same && i < ndim; ++i) same = shape[i] == s.shape[i];
   if (!same) {
@@ -172,8 +150,7 @@ int latte_t5_load_weight(latte_t5_t* t, const char* key, const float* data, cons
     return fail(LATTE_ERR_INVALID, std::string("t5_load_weight: size mismatch for '") + key + "': got shape " + str(shape, ndim) +
                                        ", expected " + str(s.shape.data(), s.shape.size()));
   }
-  size_t numel = 1;
-  for (int64_t d : s.shape) numel *= (size_t)d;
+  const size_t numel = (size_t)s.numel;
   hipStream_t st = (hipStream_t)stream;
   if (s.kind == TP_F32) {
     LATTE_HIP(hipMemcpyAsync(s.dst, data, sizeof(float) * numel, hipMemcpyDeviceToDevice, st));
@@ -181,20 +158,14 @@ int latte_t5_load_weight(latte_t5_t* t, const char* key, const float* data, cons
     int rc = launch_t5_pack_w(data, (half_t*)s.dst, (half_t*)s.dst_lo, numel, st);
     if (rc) return rc;
   }
-  s.loaded = true;
+  s.loaded = true;   // (a device source: nothing to drain)
   if (s.dst == t->rel) t->table_built = false;
   return LATTE_OK;
 }
 
 int latte_t5_check_weights(latte_t5_t* t) {
   if (!t) return fail(LATTE_ERR_INVALID, "t5_check_weights: null");
-  for (const auto& s : t->slots) {
-    bool ok = s.loaded;
-    if (!ok && s.group >= 0)
-      for (const auto& o : t->slots) ok = ok || (o.group == s.group && o.loaded);
-    if (!ok) return fail(LATTE_ERR_STATE, "Missing key(s) in state_dict: \"" + s.key + "\"");
-  }
-  return LATTE_OK;
+  return t->weights.check_loaded();
 }
 
 int latte_t5_forward(latte_t5_t* t, const int64_t* ids, const float* mask, int B, int L, float* out, void* stream) {

@@ -18,7 +18,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "weight_store.h"
 
 using namespace latte;
 
@@ -84,21 +84,10 @@ struct latte_trainer {
   bool weights_synced = false;
   int cur_batch = 0, next_stage = 1 << 30;   // step in flight: batch, labels (caller keeps them alive), next backward stage
   const int64_t* cur_y = nullptr;
-  std::vector<void*> allocs;
+  DeviceArena arena;
 };
 
 namespace {
-
-template <typename Tp>
-int talloc(latte_trainer* e, Tp** p, size_t count, bool zero = true) {
-  void* q = nullptr;
-  const size_t bytes = std::max<size_t>(count * sizeof(Tp), 16);
-  LATTE_HIP(hipMalloc(&q, bytes));
-  if (zero) LATTE_HIP(hipMemset(q, 0, bytes));
-  e->allocs.push_back(q);
-  *p = (Tp*)q;
-  return LATTE_OK;
-}
 
 void add_param(latte_trainer* e, const std::string& key, int64_t numel) {
   ParamInfo p{key, e->total, numel};
@@ -221,7 +210,7 @@ int latte_trainer_create(const latte_model_config_t* cfg, int max_batch, latte_t
 
   int rc = LATTE_OK;
   const size_t R = (size_t)e->rows_pad;
-  auto A = [&](auto** p, size_t n) { if (!rc) rc = talloc(e, p, n); };
+  auto A = [&](auto** p, size_t n) { if (!rc) rc = e->arena.alloc(p, n); };
   A(&e->pos, (size_t)e->T * D); A(&e->temp, (size_t)e->F * D); A(&e->pe_wt, (size_t)e->KPE * D); A(&e->fin_wt, (size_t)D * e->P);
   e->xs.resize(2 * c.depth + 1);
   for (auto& x : e->xs) A(&x, R * D);
@@ -290,9 +279,7 @@ int latte_trainer_create(const latte_model_config_t* cfg, int max_batch, latte_t
 }
 
 void latte_trainer_destroy(latte_trainer_t* e) {
-  if (!e) return;
-  for (void* p : e->allocs) (void)hipFree(p);
-  delete e;
+  delete e;   // the arena frees every device block
 }
 
 int latte_trainer_num_params(const latte_trainer_t* e) { return e ? (int)e->params.size() : 0; }
@@ -378,7 +365,7 @@ int latte_trainer_begin(latte_trainer_t* e, const latte_schedule_t* s, int loss_
   // ---- x_t, original timesteps
   if ((rc = launch_q_sample(tab, s->num_timesteps, x_start, noise, t, B, (size_t)F * e->Cin * hw, e->x_t, st))) return rc;
   if (e->tmap_of != s || e->tmap_n != s->num_timesteps) {
-    if (e->tmap_n < s->num_timesteps) { if ((rc = talloc(e, &e->tmap_dev, (size_t)s->num_timesteps, false))) return rc; }
+    if (e->tmap_n < s->num_timesteps) { if ((rc = e->arena.alloc(&e->tmap_dev, (size_t)s->num_timesteps, false))) return rc; }
     LATTE_HIP(hipMemcpyAsync(e->tmap_dev, s->timestep_map.data(), sizeof(int64_t) * s->num_timesteps, hipMemcpyHostToDevice, st));
     LATTE_HIP(hipStreamSynchronize(st));
     e->tmap_n = s->num_timesteps;

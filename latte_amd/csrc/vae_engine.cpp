@@ -11,11 +11,10 @@
 // the MFMA operands (GroupNorm+SiLU outputs, attention q/k/v/P, the half copies the shortcut / upsampler convs read) are
 // half: three half scratch buffers, all sized for the largest map ([N, 8h, 8w, 256]).
 #include <cmath>
-#include <map>
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "weight_store.h"
 
 using namespace latte;
 
@@ -40,16 +39,9 @@ void kprof_mark(int cls, hipStream_t st) {
 
 namespace {
 
+// WeightSlot::kind; rows / cols of a slot are cout / cin; dst_lo (VP_CONV3 / VP_LINEAR_H16): the f16 rounding residual of the packed
+// weight (split-operand passes), or nullptr
 enum VPack { VP_F32, VP_CONV3, VP_LINEAR_H16, VP_SMALL_T, VP_SMALL, VP_CONVT };
-struct VSlot {
-  std::string key;
-  int64_t numel;
-  VPack kind;
-  void* dst;
-  int cout, cin;
-  bool loaded = false;
-  void* dst_lo = nullptr;   // VP_CONV3 / VP_LINEAR_H16: the f16 rounding residual of the packed weight (split-operand passes), or nullptr
-};
 struct Resnet {
   int cin, cout;
   float *n1w, *n1b, *n2w, *n2b, *c1b, *c2b, *scb = nullptr;
@@ -69,9 +61,8 @@ struct TResnet {
 struct latte_vae {
   int h = 0, max_frames = 0, dtype = 0;
   int ch[4] = {128, 256, 512, 512};   // block_out_channels
-  std::vector<VSlot> slots;
-  std::map<std::string, int> index;
-  std::vector<void*> allocs;
+  WeightSlots weights;
+  DeviceArena arena;
   float *pq_w, *pq_b, *ci_wt, *ci_b, *co_w, *co_b, *no_w, *no_b;
   Resnet mid[2];
   Resnet up[4][3];
@@ -86,8 +77,7 @@ struct latte_vae {
   float* tbuf;         // fp32 conv1 output of a ResnetBlock2D (GroupNorm 2 normalises it before anything rounds it)
   float* ones;         // [512] gate vector of ones (attention out-projection through the gated fp32 residual epilogue)
   half_t* zeros;
-  float *pq_out, *scores, *gn_partial, *gn_stats, *stage;
-  int64_t stage_numel = 0;
+  float *pq_out, *scores, *gn_partial, *gn_stats;
   bool bias_folded = false;
   // AutoencoderKLTemporalDecoder mode (latte_vae_create_temporal): every resnet is a SpatioTemporalResBlock, no
   // post_quant_conv, time_conv_out after conv_out; one decode call = ONE video chunk of n_frames frames
@@ -108,49 +98,30 @@ struct latte_vae {
 
 namespace {
 
-template <typename Tp>
-int valloc(latte_vae* v, Tp** p, size_t count) {
-  void* q = nullptr;
-  const size_t bytes = count * sizeof(Tp);
-  LATTE_HIP(hipMalloc(&q, bytes ? bytes : 16));
-  LATTE_HIP(hipMemset(q, 0, bytes ? bytes : 16));
-  v->allocs.push_back(q);
-  *p = (Tp*)q;
-  return LATTE_OK;
-}
-
-void vslot(latte_vae* v, const std::string& key, int64_t numel, VPack kind, void* dst, int cout = 0, int cin = 0) {
-  VSlot s;
-  s.key = key; s.numel = numel; s.kind = kind; s.dst = dst; s.cout = cout; s.cin = cin;
-  v->index[key] = (int)v->slots.size();
-  v->slots.push_back(s);
-  if (numel > v->stage_numel) v->stage_numel = numel;
-}
-
 int make_resnet(latte_vae* v, Resnet& r, const std::string& p, int cin, int cout) {
   r.cin = cin; r.cout = cout;
   int rc;
-  if ((rc = valloc(v, &r.n1w, cin)) || (rc = valloc(v, &r.n1b, cin)) || (rc = valloc(v, &r.n2w, cout)) ||
-      (rc = valloc(v, &r.n2b, cout)) || (rc = valloc(v, &r.c1b, cout)) || (rc = valloc(v, &r.c2b, cout)) ||
-      (rc = valloc(v, &r.c1w, (size_t)cout * cin * 9)) || (rc = valloc(v, &r.c2w, (size_t)cout * cout * 9)))
+  if ((rc = v->arena.alloc(&r.n1w, cin)) || (rc = v->arena.alloc(&r.n1b, cin)) || (rc = v->arena.alloc(&r.n2w, cout)) ||
+      (rc = v->arena.alloc(&r.n2b, cout)) || (rc = v->arena.alloc(&r.c1b, cout)) || (rc = v->arena.alloc(&r.c2b, cout)) ||
+      (rc = v->arena.alloc(&r.c1w, (size_t)cout * cin * 9)) || (rc = v->arena.alloc(&r.c2w, (size_t)cout * cout * 9)))
     return rc;
-  vslot(v, p + "norm1.weight", cin, VP_F32, r.n1w);
-  vslot(v, p + "norm1.bias", cin, VP_F32, r.n1b);
-  vslot(v, p + "conv1.weight", (int64_t)cout * cin * 9, VP_CONV3, r.c1w, cout, cin);
-  if ((rc = valloc(v, &r.c1w_lo, (size_t)cout * cin * 9)) || (rc = valloc(v, &r.c2w_lo, (size_t)cout * cout * 9))) return rc;
-  v->slots.back().dst_lo = r.c1w_lo;
-  vslot(v, p + "conv1.bias", cout, VP_F32, r.c1b);
-  vslot(v, p + "norm2.weight", cout, VP_F32, r.n2w);
-  vslot(v, p + "norm2.bias", cout, VP_F32, r.n2b);
-  vslot(v, p + "conv2.weight", (int64_t)cout * cout * 9, VP_CONV3, r.c2w, cout, cout);
-  v->slots.back().dst_lo = r.c2w_lo;
-  vslot(v, p + "conv2.bias", cout, VP_F32, r.c2b);
+  v->weights.add(p + "norm1.weight", cin, VP_F32, r.n1w);
+  v->weights.add(p + "norm1.bias", cin, VP_F32, r.n1b);
+  v->weights.add(p + "conv1.weight", (int64_t)cout * cin * 9, VP_CONV3, r.c1w, cout, cin);
+  if ((rc = v->arena.alloc(&r.c1w_lo, (size_t)cout * cin * 9)) || (rc = v->arena.alloc(&r.c2w_lo, (size_t)cout * cout * 9))) return rc;
+  v->weights.back().dst_lo = r.c1w_lo;
+  v->weights.add(p + "conv1.bias", cout, VP_F32, r.c1b);
+  v->weights.add(p + "norm2.weight", cout, VP_F32, r.n2w);
+  v->weights.add(p + "norm2.bias", cout, VP_F32, r.n2b);
+  v->weights.add(p + "conv2.weight", (int64_t)cout * cout * 9, VP_CONV3, r.c2w, cout, cout);
+  v->weights.back().dst_lo = r.c2w_lo;
+  v->weights.add(p + "conv2.bias", cout, VP_F32, r.c2b);
   if (cin != cout) {
-    if ((rc = valloc(v, &r.scw, (size_t)cout * cin)) || (rc = valloc(v, &r.scb, cout))) return rc;
-    vslot(v, p + "conv_shortcut.weight", (int64_t)cout * cin, VP_LINEAR_H16, r.scw);
-    if ((rc = valloc(v, &r.scw_lo, (size_t)cout * cin))) return rc;
-    v->slots.back().dst_lo = r.scw_lo;
-    vslot(v, p + "conv_shortcut.bias", cout, VP_F32, r.scb);
+    if ((rc = v->arena.alloc(&r.scw, (size_t)cout * cin)) || (rc = v->arena.alloc(&r.scb, cout))) return rc;
+    v->weights.add(p + "conv_shortcut.weight", (int64_t)cout * cin, VP_LINEAR_H16, r.scw);
+    if ((rc = v->arena.alloc(&r.scw_lo, (size_t)cout * cin))) return rc;
+    v->weights.back().dst_lo = r.scw_lo;
+    v->weights.add(p + "conv_shortcut.bias", cout, VP_F32, r.scb);
   }
   return LATTE_OK;
 }
@@ -158,22 +129,22 @@ int make_resnet(latte_vae* v, Resnet& r, const std::string& p, int cin, int cout
 int make_tresnet(latte_vae* v, TResnet& t, const std::string& p, int c) {
   t.c = c;
   int rc;
-  if ((rc = valloc(v, &t.n1w, c)) || (rc = valloc(v, &t.n1b, c)) || (rc = valloc(v, &t.n2w, c)) || (rc = valloc(v, &t.n2b, c)) ||
-      (rc = valloc(v, &t.c1b, c)) || (rc = valloc(v, &t.c2b, c)) || (rc = valloc(v, &t.c2b_eff, c)) ||
-      (rc = valloc(v, &t.c2w_f32, (size_t)c * c * 3)) || (rc = valloc(v, &t.mix, 4)) || (rc = valloc(v, &t.c1w, (size_t)c * c * 3)) ||
-      (rc = valloc(v, &t.c2w, (size_t)c * c * 3)) || (rc = valloc(v, &t.c1w_lo, (size_t)c * c * 3)) ||
-      (rc = valloc(v, &t.c2w_lo, (size_t)c * c * 3)))
+  if ((rc = v->arena.alloc(&t.n1w, c)) || (rc = v->arena.alloc(&t.n1b, c)) || (rc = v->arena.alloc(&t.n2w, c)) || (rc = v->arena.alloc(&t.n2b, c)) ||
+      (rc = v->arena.alloc(&t.c1b, c)) || (rc = v->arena.alloc(&t.c2b, c)) || (rc = v->arena.alloc(&t.c2b_eff, c)) ||
+      (rc = v->arena.alloc(&t.c2w_f32, (size_t)c * c * 3)) || (rc = v->arena.alloc(&t.mix, 4)) || (rc = v->arena.alloc(&t.c1w, (size_t)c * c * 3)) ||
+      (rc = v->arena.alloc(&t.c2w, (size_t)c * c * 3)) || (rc = v->arena.alloc(&t.c1w_lo, (size_t)c * c * 3)) ||
+      (rc = v->arena.alloc(&t.c2w_lo, (size_t)c * c * 3)))
     return rc;
   const std::string q = p + "temporal_res_block.";
-  vslot(v, q + "norm1.weight", c, VP_F32, t.n1w);
-  vslot(v, q + "norm1.bias", c, VP_F32, t.n1b);
-  vslot(v, q + "conv1.weight", (int64_t)c * c * 3, VP_CONVT, &t, c, c);
-  vslot(v, q + "conv1.bias", c, VP_F32, t.c1b);
-  vslot(v, q + "norm2.weight", c, VP_F32, t.n2w);
-  vslot(v, q + "norm2.bias", c, VP_F32, t.n2b);
-  vslot(v, q + "conv2.weight", (int64_t)c * c * 3, VP_F32, t.c2w_f32);
-  vslot(v, q + "conv2.bias", c, VP_F32, t.c2b);
-  vslot(v, p + "time_mixer.mix_factor", 1, VP_F32, t.mix);
+  v->weights.add(q + "norm1.weight", c, VP_F32, t.n1w);
+  v->weights.add(q + "norm1.bias", c, VP_F32, t.n1b);
+  v->weights.add(q + "conv1.weight", (int64_t)c * c * 3, VP_CONVT, &t, c, c);
+  v->weights.add(q + "conv1.bias", c, VP_F32, t.c1b);
+  v->weights.add(q + "norm2.weight", c, VP_F32, t.n2w);
+  v->weights.add(q + "norm2.bias", c, VP_F32, t.n2b);
+  v->weights.add(q + "conv2.weight", (int64_t)c * c * 3, VP_F32, t.c2w_f32);
+  v->weights.add(q + "conv2.bias", c, VP_F32, t.c2b);
+  v->weights.add(p + "time_mixer.mix_factor", 1, VP_F32, t.mix);
   return LATTE_OK;
 }
 
@@ -314,22 +285,22 @@ int make_mid_attention(latte_vae* v, const std::string& a) {
   const int top = v->ch[3];
   int rc;
 #define ATRY(x) do { if ((rc = (x))) return rc; } while (0)
-  ATRY(valloc(v, &v->agn_w, top)); ATRY(valloc(v, &v->agn_b, top));
-  ATRY(valloc(v, &v->aq_b, top)); ATRY(valloc(v, &v->ak_b, top)); ATRY(valloc(v, &v->av_b, top)); ATRY(valloc(v, &v->ao_b, top));
-  ATRY(valloc(v, &v->ao_b_eff, top)); ATRY(valloc(v, &v->zero_bias, 4096));
-  ATRY(valloc(v, &v->aq_w, (size_t)top * top)); ATRY(valloc(v, &v->ak_w, (size_t)top * top));
-  ATRY(valloc(v, &v->av_w, (size_t)top * top)); ATRY(valloc(v, &v->ao_w, (size_t)top * top));
-  ATRY(valloc(v, &v->ao_w_f32, (size_t)top * top));
-  vslot(v, a + "group_norm.weight", top, VP_F32, v->agn_w);
-  vslot(v, a + "group_norm.bias", top, VP_F32, v->agn_b);
-  vslot(v, a + "to_q.weight", (int64_t)top * top, VP_LINEAR_H16, v->aq_w);
-  vslot(v, a + "to_q.bias", top, VP_F32, v->aq_b);
-  vslot(v, a + "to_k.weight", (int64_t)top * top, VP_LINEAR_H16, v->ak_w);
-  vslot(v, a + "to_k.bias", top, VP_F32, v->ak_b);
-  vslot(v, a + "to_v.weight", (int64_t)top * top, VP_LINEAR_H16, v->av_w);
-  vslot(v, a + "to_v.bias", top, VP_F32, v->av_b);
-  vslot(v, a + "to_out.0.weight", (int64_t)top * top, VP_LINEAR_H16, v->ao_w);
-  vslot(v, a + "to_out.0.bias", top, VP_F32, v->ao_b);
+  ATRY(v->arena.alloc(&v->agn_w, top)); ATRY(v->arena.alloc(&v->agn_b, top));
+  ATRY(v->arena.alloc(&v->aq_b, top)); ATRY(v->arena.alloc(&v->ak_b, top)); ATRY(v->arena.alloc(&v->av_b, top)); ATRY(v->arena.alloc(&v->ao_b, top));
+  ATRY(v->arena.alloc(&v->ao_b_eff, top)); ATRY(v->arena.alloc(&v->zero_bias, 4096));
+  ATRY(v->arena.alloc(&v->aq_w, (size_t)top * top)); ATRY(v->arena.alloc(&v->ak_w, (size_t)top * top));
+  ATRY(v->arena.alloc(&v->av_w, (size_t)top * top)); ATRY(v->arena.alloc(&v->ao_w, (size_t)top * top));
+  ATRY(v->arena.alloc(&v->ao_w_f32, (size_t)top * top));
+  v->weights.add(a + "group_norm.weight", top, VP_F32, v->agn_w);
+  v->weights.add(a + "group_norm.bias", top, VP_F32, v->agn_b);
+  v->weights.add(a + "to_q.weight", (int64_t)top * top, VP_LINEAR_H16, v->aq_w);
+  v->weights.add(a + "to_q.bias", top, VP_F32, v->aq_b);
+  v->weights.add(a + "to_k.weight", (int64_t)top * top, VP_LINEAR_H16, v->ak_w);
+  v->weights.add(a + "to_k.bias", top, VP_F32, v->ak_b);
+  v->weights.add(a + "to_v.weight", (int64_t)top * top, VP_LINEAR_H16, v->av_w);
+  v->weights.add(a + "to_v.bias", top, VP_F32, v->av_b);
+  v->weights.add(a + "to_out.0.weight", (int64_t)top * top, VP_LINEAR_H16, v->ao_w);
+  v->weights.add(a + "to_out.0.bias", top, VP_F32, v->ao_b);
 #undef ATRY
   return LATTE_OK;
 }
@@ -378,19 +349,19 @@ int vae_create_impl(int latent_size, int max_frames, int compute_dtype, bool tem
   const std::string sp = temporal ? "spatial_res_block." : "";
   int rc = LATTE_OK;
 #define TRY(x) do { if ((rc = (x))) { latte_vae_destroy(v); return rc; } } while (0)
-  TRY(valloc(v, &v->pq_w, 16)); TRY(valloc(v, &v->pq_b, 4));
-  TRY(valloc(v, &v->ci_wt, (size_t)36 * top)); TRY(valloc(v, &v->ci_b, top));
-  TRY(valloc(v, &v->co_w, (size_t)27 * v->ch[0])); TRY(valloc(v, &v->co_b, 4));
-  TRY(valloc(v, &v->no_w, v->ch[0])); TRY(valloc(v, &v->no_b, v->ch[0]));
+  TRY(v->arena.alloc(&v->pq_w, 16)); TRY(v->arena.alloc(&v->pq_b, 4));
+  TRY(v->arena.alloc(&v->ci_wt, (size_t)36 * top)); TRY(v->arena.alloc(&v->ci_b, top));
+  TRY(v->arena.alloc(&v->co_w, (size_t)27 * v->ch[0])); TRY(v->arena.alloc(&v->co_b, 4));
+  TRY(v->arena.alloc(&v->no_w, v->ch[0])); TRY(v->arena.alloc(&v->no_b, v->ch[0]));
   if (!temporal) {
-    vslot(v, "post_quant_conv.weight", 16, VP_F32, v->pq_w);
-    vslot(v, "post_quant_conv.bias", 4, VP_F32, v->pq_b);
+    v->weights.add("post_quant_conv.weight", 16, VP_F32, v->pq_w);
+    v->weights.add("post_quant_conv.bias", 4, VP_F32, v->pq_b);
   } else {   // AutoencoderKLTemporalDecoder has no post_quant_conv: the 1x1 kernel runs with the identity
     const float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     LATTE_HIP(hipMemcpy(v->pq_w, eye, sizeof(eye), hipMemcpyHostToDevice));
   }
-  vslot(v, "decoder.conv_in.weight", (int64_t)top * 36, VP_SMALL_T, v->ci_wt, top, 4);
-  vslot(v, "decoder.conv_in.bias", top, VP_F32, v->ci_b);
+  v->weights.add("decoder.conv_in.weight", (int64_t)top * 36, VP_SMALL_T, v->ci_wt, top, 4);
+  v->weights.add("decoder.conv_in.bias", top, VP_F32, v->ci_b);
   TRY(make_resnet(v, v->mid[0], "decoder.mid_block.resnets.0." + sp, top, top));
   if (temporal) TRY(make_tresnet(v, v->tmid[0], "decoder.mid_block.resnets.0.", top));
   TRY(make_mid_attention(v, "decoder.mid_block.attentions.0."));
@@ -406,42 +377,42 @@ int vae_create_impl(int latent_size, int max_frames, int compute_dtype, bool tem
     }
     prev = cout;
     if (i < 3) {
-      TRY(valloc(v, &v->upc_w[i], (size_t)cout * cout * 9));
-      TRY(valloc(v, &v->upc_b[i], cout));
+      TRY(v->arena.alloc(&v->upc_w[i], (size_t)cout * cout * 9));
+      TRY(v->arena.alloc(&v->upc_b[i], cout));
       const std::string p = "decoder.up_blocks." + std::to_string(i) + ".upsamplers.0.conv.";
-      vslot(v, p + "weight", (int64_t)cout * cout * 9, VP_CONV3, v->upc_w[i], cout, cout);
-      TRY(valloc(v, &v->upc_w_lo[i], (size_t)cout * cout * 9));
-      v->slots.back().dst_lo = v->upc_w_lo[i];
-      vslot(v, p + "bias", cout, VP_F32, v->upc_b[i]);
+      v->weights.add(p + "weight", (int64_t)cout * cout * 9, VP_CONV3, v->upc_w[i], cout, cout);
+      TRY(v->arena.alloc(&v->upc_w_lo[i], (size_t)cout * cout * 9));
+      v->weights.back().dst_lo = v->upc_w_lo[i];
+      v->weights.add(p + "bias", cout, VP_F32, v->upc_b[i]);
     }
   }
-  vslot(v, "decoder.conv_norm_out.weight", v->ch[0], VP_F32, v->no_w);
-  vslot(v, "decoder.conv_norm_out.bias", v->ch[0], VP_F32, v->no_b);
-  vslot(v, "decoder.conv_out.weight", (int64_t)27 * v->ch[0], VP_SMALL, v->co_w, 3, v->ch[0]);
-  vslot(v, "decoder.conv_out.bias", 3, VP_F32, v->co_b);
+  v->weights.add("decoder.conv_norm_out.weight", v->ch[0], VP_F32, v->no_w);
+  v->weights.add("decoder.conv_norm_out.bias", v->ch[0], VP_F32, v->no_b);
+  v->weights.add("decoder.conv_out.weight", (int64_t)27 * v->ch[0], VP_SMALL, v->co_w, 3, v->ch[0]);
+  v->weights.add("decoder.conv_out.bias", 3, VP_F32, v->co_b);
   if (temporal) {
-    TRY(valloc(v, &v->tco_w, 27)); TRY(valloc(v, &v->tco_b, 4));
-    vslot(v, "decoder.time_conv_out.weight", 27, VP_F32, v->tco_w);      // [3, 3, 3, 1, 1] = (co, ci, tap)
-    vslot(v, "decoder.time_conv_out.bias", 3, VP_F32, v->tco_b);
+    TRY(v->arena.alloc(&v->tco_w, 27)); TRY(v->arena.alloc(&v->tco_b, 4));
+    v->weights.add("decoder.time_conv_out.weight", 27, VP_F32, v->tco_w);      // [3, 3, 3, 1, 1] = (co, ci, tap)
+    v->weights.add("decoder.time_conv_out.bias", 3, VP_F32, v->tco_b);
   }
 
   // workspace: the largest NHWC map is [N, 8h, 8w, 256] (output of up_blocks.2's upsampler)
   const size_t big = (size_t)max_frames * (8 * latent_size) * (8 * latent_size) * 256;
-  for (int i = 0; i < 3; ++i) TRY(valloc(v, &v->buf[i], big));
-  for (int i = 0; i < 2; ++i) TRY(valloc(v, &v->sbuf[i], big));
-  TRY(valloc(v, &v->tbuf, big));
-  TRY(valloc(v, &v->ones, 512));
+  for (int i = 0; i < 3; ++i) TRY(v->arena.alloc(&v->buf[i], big));
+  for (int i = 0; i < 2; ++i) TRY(v->arena.alloc(&v->sbuf[i], big));
+  TRY(v->arena.alloc(&v->tbuf, big));
+  TRY(v->arena.alloc(&v->ones, 512));
   {
     std::vector<float> one(512, 1.0f);
     LATTE_HIP(hipMemcpy(v->ones, one.data(), sizeof(float) * 512, hipMemcpyHostToDevice));
   }
-  TRY(valloc(v, &v->zeros, 64));
-  TRY(valloc(v, &v->pq_out, (size_t)max_frames * latent_size * latent_size * 4));
+  TRY(v->arena.alloc(&v->zeros, 64));
+  TRY(v->arena.alloc(&v->pq_out, (size_t)max_frames * latent_size * latent_size * 4));
   const size_t L = (size_t)latent_size * latent_size;
-  TRY(valloc(v, &v->scores, L * L));
-  TRY(valloc(v, &v->gn_partial, (size_t)max_frames * groupnorm_max_slabs() * 64));
-  TRY(valloc(v, &v->gn_stats, (size_t)max_frames * 64));
-  TRY(valloc(v, &v->stage, (size_t)v->stage_numel));
+  TRY(v->arena.alloc(&v->scores, L * L));
+  TRY(v->arena.alloc(&v->gn_partial, (size_t)max_frames * groupnorm_max_slabs() * 64));
+  TRY(v->arena.alloc(&v->gn_stats, (size_t)max_frames * 64));
+  TRY(v->weights.alloc_stage(v->arena, true));
 #undef TRY
   *out = v;
   return LATTE_OK;
@@ -461,9 +432,9 @@ int vae_create_encoder_impl(int image_size, int max_frames, int compute_dtype, l
   const int top = v->ch[3];
   int rc = LATTE_OK;
 #define TRY(x) do { if ((rc = (x))) { latte_vae_destroy(v); return rc; } } while (0)
-  TRY(valloc(v, &v->ci_wt, (size_t)27 * v->ch[0])); TRY(valloc(v, &v->ci_b, v->ch[0]));
-  vslot(v, "encoder.conv_in.weight", (int64_t)v->ch[0] * 27, VP_SMALL_T, v->ci_wt, v->ch[0], 3);
-  vslot(v, "encoder.conv_in.bias", v->ch[0], VP_F32, v->ci_b);
+  TRY(v->arena.alloc(&v->ci_wt, (size_t)27 * v->ch[0])); TRY(v->arena.alloc(&v->ci_b, v->ch[0]));
+  v->weights.add("encoder.conv_in.weight", (int64_t)v->ch[0] * 27, VP_SMALL_T, v->ci_wt, v->ch[0], 3);
+  v->weights.add("encoder.conv_in.bias", v->ch[0], VP_F32, v->ci_b);
   int prev = v->ch[0];
   for (int i = 0; i < 4; ++i) {
     const int cout = v->ch[i];
@@ -471,45 +442,45 @@ int vae_create_encoder_impl(int image_size, int max_frames, int compute_dtype, l
       TRY(make_resnet(v, v->down[i][r], "encoder.down_blocks." + std::to_string(i) + ".resnets." + std::to_string(r) + ".", r == 0 ? prev : cout, cout));
     prev = cout;
     if (i < 3) {
-      TRY(valloc(v, &v->dnc_w[i], (size_t)cout * cout * 9)); TRY(valloc(v, &v->dnc_w_lo[i], (size_t)cout * cout * 9));
-      TRY(valloc(v, &v->dnc_b[i], cout));
+      TRY(v->arena.alloc(&v->dnc_w[i], (size_t)cout * cout * 9)); TRY(v->arena.alloc(&v->dnc_w_lo[i], (size_t)cout * cout * 9));
+      TRY(v->arena.alloc(&v->dnc_b[i], cout));
       const std::string p = "encoder.down_blocks." + std::to_string(i) + ".downsamplers.0.conv.";
-      vslot(v, p + "weight", (int64_t)cout * cout * 9, VP_CONV3, v->dnc_w[i], cout, cout);
-      v->slots.back().dst_lo = v->dnc_w_lo[i];
-      vslot(v, p + "bias", cout, VP_F32, v->dnc_b[i]);
+      v->weights.add(p + "weight", (int64_t)cout * cout * 9, VP_CONV3, v->dnc_w[i], cout, cout);
+      v->weights.back().dst_lo = v->dnc_w_lo[i];
+      v->weights.add(p + "bias", cout, VP_F32, v->dnc_b[i]);
     }
   }
   TRY(make_resnet(v, v->mid[0], "encoder.mid_block.resnets.0.", top, top));
   TRY(make_mid_attention(v, "encoder.mid_block.attentions.0."));
   TRY(make_resnet(v, v->mid[1], "encoder.mid_block.resnets.1.", top, top));
-  TRY(valloc(v, &v->no_w, top)); TRY(valloc(v, &v->no_b, top));
-  vslot(v, "encoder.conv_norm_out.weight", top, VP_F32, v->no_w);
-  vslot(v, "encoder.conv_norm_out.bias", top, VP_F32, v->no_b);
-  TRY(valloc(v, &v->eco_raw, (size_t)8 * 9 * top)); TRY(valloc(v, &v->eco_rb, 8));
-  TRY(valloc(v, &v->eq_w, 64)); TRY(valloc(v, &v->eq_b, 8));
-  TRY(valloc(v, &v->eco_w, (size_t)8 * 9 * top)); TRY(valloc(v, &v->eco_b, 8));
-  vslot(v, "encoder.conv_out.weight", (int64_t)8 * 9 * top, VP_SMALL, v->eco_raw, 8, top);
-  vslot(v, "encoder.conv_out.bias", 8, VP_F32, v->eco_rb);
-  vslot(v, "quant_conv.weight", 64, VP_F32, v->eq_w);
-  vslot(v, "quant_conv.bias", 8, VP_F32, v->eq_b);
+  TRY(v->arena.alloc(&v->no_w, top)); TRY(v->arena.alloc(&v->no_b, top));
+  v->weights.add("encoder.conv_norm_out.weight", top, VP_F32, v->no_w);
+  v->weights.add("encoder.conv_norm_out.bias", top, VP_F32, v->no_b);
+  TRY(v->arena.alloc(&v->eco_raw, (size_t)8 * 9 * top)); TRY(v->arena.alloc(&v->eco_rb, 8));
+  TRY(v->arena.alloc(&v->eq_w, 64)); TRY(v->arena.alloc(&v->eq_b, 8));
+  TRY(v->arena.alloc(&v->eco_w, (size_t)8 * 9 * top)); TRY(v->arena.alloc(&v->eco_b, 8));
+  v->weights.add("encoder.conv_out.weight", (int64_t)8 * 9 * top, VP_SMALL, v->eco_raw, 8, top);
+  v->weights.add("encoder.conv_out.bias", 8, VP_F32, v->eco_rb);
+  v->weights.add("quant_conv.weight", 64, VP_F32, v->eq_w);
+  v->weights.add("quant_conv.bias", 8, VP_F32, v->eq_b);
 
   // workspace: the largest NHWC map is [N, H, W, 128] at the full image size (conv_in, down block 0)
   const size_t big = (size_t)max_frames * image_size * image_size * v->ch[0];
-  for (int i = 0; i < 3; ++i) TRY(valloc(v, &v->buf[i], big));
-  for (int i = 0; i < 2; ++i) TRY(valloc(v, &v->sbuf[i], big));
-  TRY(valloc(v, &v->tbuf, big));
-  TRY(valloc(v, &v->ones, 512));
+  for (int i = 0; i < 3; ++i) TRY(v->arena.alloc(&v->buf[i], big));
+  for (int i = 0; i < 2; ++i) TRY(v->arena.alloc(&v->sbuf[i], big));
+  TRY(v->arena.alloc(&v->tbuf, big));
+  TRY(v->arena.alloc(&v->ones, 512));
   {
     std::vector<float> one(512, 1.0f);
     LATTE_HIP(hipMemcpy(v->ones, one.data(), sizeof(float) * 512, hipMemcpyHostToDevice));
   }
-  TRY(valloc(v, &v->zeros, 64));
+  TRY(v->arena.alloc(&v->zeros, 64));
   const size_t L = (size_t)v->h * v->h;
-  TRY(valloc(v, &v->moments, (size_t)max_frames * 8 * L));
-  TRY(valloc(v, &v->scores, L * L));
-  TRY(valloc(v, &v->gn_partial, (size_t)max_frames * groupnorm_max_slabs() * 64));
-  TRY(valloc(v, &v->gn_stats, (size_t)max_frames * 64));
-  TRY(valloc(v, &v->stage, (size_t)v->stage_numel));
+  TRY(v->arena.alloc(&v->moments, (size_t)max_frames * 8 * L));
+  TRY(v->arena.alloc(&v->scores, L * L));
+  TRY(v->arena.alloc(&v->gn_partial, (size_t)max_frames * groupnorm_max_slabs() * 64));
+  TRY(v->arena.alloc(&v->gn_stats, (size_t)max_frames * 64));
+  TRY(v->weights.alloc_stage(v->arena, true));
 #undef TRY
   *out = v;
   return LATTE_OK;
@@ -519,61 +490,46 @@ int vae_create_encoder_impl(int image_size, int max_frames, int compute_dtype, l
 extern "C" {
 
 void latte_vae_destroy(latte_vae_t* v) {
-  if (!v) return;
-  for (void* p : v->allocs) (void)hipFree(p);
-  delete v;
+  delete v;   // the arena frees every device block
 }
 
-int latte_vae_num_keys(const latte_vae_t* v) { return v ? (int)v->slots.size() : 0; }
-const char* latte_vae_key(const latte_vae_t* v, int i) {
-  if (!v || i < 0 || i >= (int)v->slots.size()) return nullptr;
-  return v->slots[i].key.c_str();
-}
+int latte_vae_num_keys(const latte_vae_t* v) { return v ? v->weights.size() : 0; }
+const char* latte_vae_key(const latte_vae_t* v, int i) { return v ? v->weights.key(i) : nullptr; }
 
 int latte_vae_load_tensor(latte_vae_t* v, const char* key, const float* data, int64_t numel, int on_device, void* stream) {
   if (!v || !key || !data) return fail(LATTE_ERR_INVALID, "vae_load_tensor: null argument");
-  auto it = v->index.find(key);
-  if (it == v->index.end()) return fail(LATTE_ERR_INVALID, std::string("vae_load_tensor: unexpected key '") + key + "'");
-  VSlot& s = v->slots[it->second];
-  if (numel != s.numel)
-    return fail(LATTE_ERR_INVALID, std::string("vae_load_tensor: size mismatch for '") + key + "': got " +
-                                       std::to_string(numel) + ", expected " + std::to_string(s.numel));
   hipStream_t st = (hipStream_t)stream;
-  const float* src = data;
-  if (!on_device) {
-    LATTE_HIP(hipMemcpyAsync(v->stage, data, sizeof(float) * numel, hipMemcpyHostToDevice, st));
-    src = v->stage;
-  }
-  int rc = LATTE_OK;
+  WeightSlot* slot = nullptr;
+  const float* src = nullptr;
+  int rc = v->weights.begin_load("vae_load_tensor", key, data, numel, on_device, st, &slot, &src);
+  if (rc) return rc;
+  WeightSlot& s = *slot;
   switch (s.kind) {
     case VP_F32: LATTE_HIP(hipMemcpyAsync(s.dst, src, sizeof(float) * numel, hipMemcpyDeviceToDevice, st)); break;
-    case VP_CONV3: rc = launch_pack_conv_w(src, (half_t*)s.dst, s.cout, s.cin, v->dtype, st, (half_t*)s.dst_lo); break;
+    case VP_CONV3: rc = launch_pack_conv_w(src, (half_t*)s.dst, s.rows, s.cols, v->dtype, st, (half_t*)s.dst_lo); break;
     case VP_LINEAR_H16:
       rc = s.dst_lo ? launch_convert_f32_to_h16_split(src, (half_t*)s.dst, (half_t*)s.dst_lo, numel, v->dtype, st)
                     : launch_convert_f32_to_h16(src, (half_t*)s.dst, numel, v->dtype, st);
       break;
-    case VP_SMALL_T: rc = launch_pack_small_w(src, (float*)s.dst, s.cout, s.cin, 1, st); break;
-    case VP_SMALL: rc = launch_pack_small_w(src, (float*)s.dst, s.cout, s.cin, 0, st); break;
+    case VP_SMALL_T: rc = launch_pack_small_w(src, (float*)s.dst, s.rows, s.cols, 1, st); break;
+    case VP_SMALL: rc = launch_pack_small_w(src, (float*)s.dst, s.rows, s.cols, 0, st); break;
     case VP_CONVT: {
       TResnet* t = (TResnet*)s.dst;
-      rc = launch_pack_conv_t(src, t->c1w, s.cout, s.cin, nullptr, v->dtype, st, t->c1w_lo);
+      rc = launch_pack_conv_t(src, t->c1w, s.rows, s.cols, nullptr, v->dtype, st, t->c1w_lo);
       break;
     }
   }
   if (rc) return rc;
   if (s.key == "decoder.mid_block.attentions.0.to_out.0.weight" || s.key == "encoder.mid_block.attentions.0.to_out.0.weight")
     LATTE_HIP(hipMemcpyAsync(v->ao_w_f32, src, sizeof(float) * numel, hipMemcpyDeviceToDevice, st));
-  if (!on_device) LATTE_HIP(hipStreamSynchronize(st));
-  s.loaded = true;
+  if ((rc = v->weights.end_load(s, on_device, st))) return rc;
   v->bias_folded = false;
   return LATTE_OK;
 }
 
 int latte_vae_check_weights(latte_vae_t* v) {
   if (!v) return fail(LATTE_ERR_INVALID, "vae_check_weights: null");
-  for (const auto& s : v->slots)
-    if (!s.loaded) return fail(LATTE_ERR_STATE, "Missing key(s) in state_dict: \"" + s.key + "\"");
-  return LATTE_OK;
+  return v->weights.check_loaded();
 }
 
 static int vae_decode_impl(latte_vae_t* v, const float* z, int n_frames, float z_scale, int out_mode, void* out, void* stream,

@@ -251,16 +251,7 @@ class Latte(nn.Module):
                 if odt == dtype:
                     check(lib.latte_engine_set_option(h, name.encode(), int(value)))
         if not rec[2]:
-            sd = self.state_dict()
-            with torch.cuda.device(dev):
-                for i in range(lib.latte_engine_num_keys(rec[0])):
-                    k = lib.latte_engine_key(rec[0], i).decode()
-                    if k not in sd:
-                        raise LatteError(f'Missing key(s) in state_dict: "{k}"')
-                    t = sd[k].detach().to(device=dev, dtype=torch.float32).contiguous()
-                    check(lib.latte_engine_load_tensor(rec[0], k.encode(), ptr(t), t.numel(), 1, stream_ptr()))
-                check(lib.latte_engine_check_weights(rec[0]))
-                torch.cuda.current_stream().synchronize()
+            _lib.sync_weights(lib, "engine", rec[0], self.state_dict(), dev)
             rec[2] = True
         return rec[0]
 

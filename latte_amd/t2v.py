@@ -70,13 +70,8 @@ class LatteT2V:
         return dict(self._sd)
 
     def to(self, *args, **kwargs):
-        for a in list(args) + list(kwargs.values()):
-            if isinstance(a, (str, torch.device)):
-                self._device = torch.device(a)
-                if self._device.type == "cuda" and self._device.index is None:
-                    self._device = torch.device("cuda", torch.cuda.current_device())
-            elif a == torch.bfloat16:
-                raise LatteError("latte_amd.LatteT2V runs with f16 MFMA operands only (see the constructor)")
+        self._device = _lib.to_device(args, kwargs, self._device,
+                                      "latte_amd.LatteT2V runs with f16 MFMA operands only (see the constructor)")
         self._synced = False
         return self
 
@@ -118,17 +113,7 @@ class LatteT2V:
             self._h, self._key, self._synced = h, key, False
             self.max_batch, self.max_text_tokens = want_b, want_k
         if not self._synced:
-            with torch.cuda.device(self._device):
-                for i in range(lib.latte_t2v_num_keys(self._h)):
-                    k = lib.latte_t2v_key(self._h, i).decode()
-                    if k not in self._sd:
-                        if k == "caption_projection.y_embedding":
-                            continue
-                        raise LatteError(f'Missing key(s) in state_dict: "{k}"')
-                    t = self._sd[k].to(device=self._device, dtype=torch.float32).contiguous()
-                    check(lib.latte_t2v_load_tensor(self._h, k.encode(), ptr(t), t.numel(), 1, stream_ptr()))
-                check(lib.latte_t2v_check_weights(self._h))
-                torch.cuda.current_stream().synchronize()
+            _lib.sync_weights(lib, "t2v", self._h, self._sd, self._device, optional=("caption_projection.y_embedding",))
             self._synced = True
         return self._h
 

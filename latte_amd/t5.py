@@ -119,13 +119,8 @@ class T5EncoderModel:
         return sd
 
     def to(self, *args, **kwargs):
-        for a in list(args) + list(kwargs.values()):
-            if isinstance(a, (str, torch.device)):
-                self._device = torch.device(a)
-                if self._device.type == "cuda" and self._device.index is None:
-                    self._device = torch.device("cuda", torch.cuda.current_device())
-            elif a == torch.bfloat16:
-                raise LatteError("latte_amd.T5EncoderModel runs f16 operand pairs only (class docstring)")
+        self._device = _lib.to_device(args, kwargs, self._device,
+                                      "latte_amd.T5EncoderModel runs f16 operand pairs only (class docstring)")
         return self                                  # the engine state follows the device of the first call (_ensure)
 
     def eval(self):

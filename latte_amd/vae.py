@@ -178,15 +178,9 @@ class AutoencoderKL:
         return dict(self._sd)
 
     def to(self, *args, **kwargs):
-        for a in list(args) + list(kwargs.values()):
-            if isinstance(a, (str, torch.device)):
-                self._device = torch.device(a)
-                if self._device.type == "cuda" and self._device.index is None:
-                    self._device = torch.device("cuda", torch.cuda.current_device())
-            elif a == torch.bfloat16:
-                raise LatteError("latte_amd.AutoencoderKL decodes with f16 MFMA operands only (class docstring)")
-            elif a in (torch.float16, torch.float32):                # sample.py:74 vae.to(dtype=torch.float16); fp32 = the default
-                pass
+        # (sample.py:74 vae.to(dtype=torch.float16); fp32 = the default: both accepted, the operands stay f16)
+        self._device = _lib.to_device(args, kwargs, self._device,
+                                      "latte_amd.AutoencoderKL decodes with f16 MFMA operands only (class docstring)")
         self._synced = False
         self._esynced = False
         return self
@@ -224,15 +218,7 @@ class AutoencoderKL:
             self._h, self._key, self._synced = h, key, False
             self.max_frames, self.latent_size = want, latent_size
         if not self._synced:
-            with torch.cuda.device(self._device):
-                for i in range(lib.latte_vae_num_keys(self._h)):
-                    k = lib.latte_vae_key(self._h, i).decode()
-                    if k not in self._sd:
-                        raise LatteError(f'Missing key(s) in state_dict: "{k}"')
-                    t = self._sd[k].to(device=self._device, dtype=torch.float32).contiguous()
-                    check(lib.latte_vae_load_tensor(self._h, k.encode(), ptr(t), t.numel(), 1, stream_ptr()))
-                check(lib.latte_vae_check_weights(self._h))
-                torch.cuda.current_stream().synchronize()
+            _lib.sync_weights(lib, "vae", self._h, self._sd, self._device)
             self._synced = True
         return self._h
 
@@ -299,15 +285,7 @@ class AutoencoderKL:
                 check(lib.latte_vae_create_encoder(image_size, self.max_frames, _lib.DTYPES[self.compute_dtype], h))
             self._eh, self._ekey, self._esynced = h, key, False
         if not self._esynced:
-            with torch.cuda.device(self._device):
-                for i in range(lib.latte_vae_num_keys(self._eh)):
-                    k = lib.latte_vae_key(self._eh, i).decode()
-                    if k not in self._sd:
-                        raise LatteError(f'Missing key(s) in state_dict: "{k}"')
-                    t = self._sd[k].to(device=self._device, dtype=torch.float32).contiguous()
-                    check(lib.latte_vae_load_tensor(self._eh, k.encode(), ptr(t), t.numel(), 1, stream_ptr()))
-                check(lib.latte_vae_check_weights(self._eh))
-                torch.cuda.current_stream().synchronize()
+            _lib.sync_weights(lib, "vae", self._eh, self._sd, self._device)
             self._esynced = True
         return self._eh
 
