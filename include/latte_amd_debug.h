@@ -201,8 +201,8 @@ int latte_debug_dma_probe(const void* src, long long* out, int mode, int waves, 
  *   "vae_split"       1024 + m: which stages of the temporal decoder run split-operand convolutions -- bits 0..4 of m = the spatial resnets of
  *                     {mid block, up block 0..3} add the pass on the activation's f16 rounding residual, bits 5..9 = the temporal resnets of the
  *                     same stages run three passes (hi*hi + lo*hi + hi*lo) instead of one (csrc/vae_engine.cpp: vae_split_mask); the SD-VAE
- *                     encoder reads the same layout once per encode call (bit 0 mid block, 1 + i down block i, 12 + i / 21 + i the down-sampler of
- *                     block i, 11 conv_out; csrc/vae_engine.cpp: encode_split_mask)
+ *                     encoder reads the same layout (bit 0 mid block, 1 + i down block i, 12 + i / 21 + i the down-sampler of block i, 11
+ *                     conv_out).  A decode / encode call reads the choice once, when it starts, and runs entirely on that mask
  * Anything else is refused (LATTE_ERR_INVALID).  Replaces the LATTE_* environment variables round 3 read at every launch; the
  * measurement ablations whose results are garbage (attention variants 7-10, 16-19) exist only in a LATTE_DEBUG_BUILD=1 library. */
 int latte_debug_set_choice(const char* name, int value);

@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "event_profile.h"
 #include "weight_store.h"
 
 namespace latte {
@@ -55,11 +56,6 @@ struct BlockW {
   half_t *proj_w2 = nullptr, *fc1_w2 = nullptr;   // [N, 2 K] = [W | W]: the weight of a split-operand linear (guided_split bits 0 / 1), built lazily
   unsigned char *fc1_w4 = nullptr, *fc1_w4s = nullptr;    // fp4 image of fc1's weight + its row scales (guided_split bit 4; GemmArgs::W4 / W4s)
   unsigned char *proj_w8 = nullptr, *fc1_w8 = nullptr;   // [N, K] e4m3(W 2^LO8_W_SHIFT): the weight of a GEMM's fp8 correction pass (bits 2 / 3)
-};
-
-struct Prof {
-  std::vector<hipEvent_t> ev;
-  std::vector<int> cls;
 };
 
 }  // namespace latte
@@ -133,15 +129,10 @@ struct latte_engine {
 namespace {
 
 struct Timer {  // optional per-launch HIP events (latte_profile_forward)
-  Prof* p;
+  EventProfile* p;
   hipStream_t st;
   void mark(int cls) {
-    if (!p) return;
-    hipEvent_t ev;
-    (void)hipEventCreate(&ev);
-    (void)hipEventRecord(ev, st);
-    p->ev.push_back(ev);
-    p->cls.push_back(cls);
+    if (p) p->mark(cls, st);
   }
 };
 enum { C_QKV = 0, C_PROJ, C_FC1, C_FC2, C_ATTN_S, C_ATTN_T, C_LN, C_COND, C_PATCH, C_FINAL, C_QKVATTN_S, C_QKVATTN_T, C_NONE = -1 };
@@ -230,7 +221,7 @@ int ensure_split_weights(latte_engine* e, int need, hipStream_t st) {
 // mod_override != nullptr: the adaLN outputs of this step were precomputed ([B or 1 rows, nmod], row stride mod_stride;
 // stride 0 = one row shared by every sample) and the conditioning launches are skipped.
 int run_forward(latte_engine* e, const float* x, const int64_t* t, const int64_t* y, int B, bool cfg_dup, float* out,
-                hipStream_t st, Prof* prof, const float* mod_override = nullptr, int mod_stride_override = 0) {
+                hipStream_t st, EventProfile* prof, const float* mod_override = nullptr, int mod_stride_override = 0) {
   const auto& c = e->cfg;
   if (B <= 0 || B > e->max_batch) return fail(LATTE_ERR_STATE, "forward: batch exceeds max_batch of the engine");
   if (c.extras == 2 && y == nullptr && !mod_override) return fail(LATTE_ERR_INVALID, "forward: class-conditional model needs y");
@@ -942,26 +933,12 @@ int latte_profile_forward_ex(latte_engine_t* e, const float* x, const int64_t* t
   if (!e || !ms_out || !launches_out || n < LATTE_NUM_KERNEL_CLASSES) return fail(LATTE_ERR_INVALID, "profile_forward: bad arguments");
   int rc = latte_engine_check_weights(e);
   if (rc) return rc;
-  Prof prof;
+  EventProfile prof;   // (destroys its events on every return path)
   hipStream_t st = (hipStream_t)stream;
   rc = run_forward(e, x, t, y, batch, guided != 0, out, st, &prof);
   if (rc) return rc;
   LATTE_HIP(hipStreamSynchronize(st));
-  for (int i = 0; i < n; ++i) {
-    ms_out[i] = 0.f;
-    launches_out[i] = 0;
-  }
-  for (size_t i = 1; i < prof.ev.size(); ++i) {
-    float ms = 0.f;
-    LATTE_HIP(hipEventElapsedTime(&ms, prof.ev[i - 1], prof.ev[i]));
-    const int c = prof.cls[i];
-    if (c >= 0 && c < n) {
-      ms_out[c] += ms;
-      launches_out[c] += 1;
-    }
-  }
-  for (auto ev : prof.ev) (void)hipEventDestroy(ev);
-  return LATTE_OK;
+  return prof.collect("profile_forward", ms_out, launches_out, n);
 }
 
 int latte_bench_gemm(int M, int N, int K, int epi, int dtype, int variant, int iters, float* ms_per_launch, void* stream) {

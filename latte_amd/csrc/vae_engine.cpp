@@ -14,30 +14,35 @@
 #include <string>
 #include <vector>
 
+#include "event_profile.h"
 #include "weight_store.h"
 
 using namespace latte;
 
 namespace {
-struct KProf {
-  std::vector<hipEvent_t> ev;
-  std::vector<int> cls;
-};
-thread_local KProf* g_kprof = nullptr;
+thread_local EventProfile* g_kprof = nullptr;   // armed by profile_vae_call on its thread
 }  // namespace
 
 namespace latte {
 void kprof_mark(int cls, hipStream_t st) {
-  if (!g_kprof) return;
-  hipEvent_t ev;
-  (void)hipEventCreate(&ev);
-  (void)hipEventRecord(ev, st);
-  g_kprof->ev.push_back(ev);
-  g_kprof->cls.push_back(cls);
+  if (g_kprof) g_kprof->mark(cls, st);
 }
 }  // namespace latte
 
 namespace {
+
+// The body of latte_vae_profile_decode / _encode: `call` (the decode / encode) with a HIP event behind every launch, then the per-class sums
+template <class Call>
+int profile_vae_call(const std::string& name, float* ms_out, int* launches_out, int n, hipStream_t st, Call call) {
+  if (!ms_out || !launches_out || n < VC_NUM_CLASSES) return fail(LATTE_ERR_INVALID, name + ": bad arguments");
+  EventProfile prof;
+  g_kprof = &prof;
+  kprof_mark(VC_START, st);
+  int rc = call();
+  g_kprof = nullptr;
+  if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(LATTE_ERR_HIP, name + ": device error");
+  return prof.collect(name, ms_out, launches_out, n, rc);
+}
 
 // WeightSlot::kind; rows / cols of a slot are cout / cin; dst_lo (VP_CONV3 / VP_LINEAR_H16): the f16 rounding residual of the packed
 // weight (split-operand passes), or nullptr
@@ -93,7 +98,6 @@ struct latte_vae {
   float *eco_raw = nullptr, *eco_rb = nullptr, *eq_w = nullptr, *eq_b = nullptr;   // conv_out [8][9 * 512] packed, its bias, quant_conv 8 x 8 + 8
   float *eco_w = nullptr, *eco_b = nullptr;   // conv_out with quant_conv folded in (fp32, at the first encode after a load)
   float* moments = nullptr;                   // [max_frames, 8, h, w] when the caller asked for mode / sample
-  int enc_split = 0;                          // split-operand mask of the running encode (read once per call)
 };
 
 namespace {
@@ -156,17 +160,25 @@ int make_tresnet(latte_vae* v, TResnet& t, const std::string& p, int c) {
 // upsamplers' weight residual.
 // latte_debug_set_choice("vae_split", (1 << 24) | mask) overrides the default (measurement / parity sweeps).
 // The encoder uses the same bit layout with its own stages (resnets: bit 0 = mid block, 1 + i = down block i; bits 12..14 / 21..23 = the
-// down-sampler of down block i; bit 11 = conv_out); its mask is read once per encode call (encode_split_mask) and held in enc_split.
+// down-sampler of down block i; bit 11 = conv_out).
+// vae_decode_impl / vae_encode_impl read the mask ONCE, at their top, and pass it down by value: a call runs entirely on the mask it started
+// with, whatever a concurrent latte_debug_set_choice does meanwhile.
 constexpr int VAE_SPLIT_DEFAULT_TEMPORAL = 0x319c03, VAE_SPLIT_DEFAULT_SPATIAL = 0x301c00;
 constexpr int VAE_SPLIT_DEFAULT_ENCODER = 0xf07c00;   // 1.01e-3 -> 7.7e-4 worst of five draws for +0.8 ms
-int encode_split_mask() {
+struct SplitMask {   // stage: 0 = mid block, 1 + i = up / down block i; i: up- / down-sampler of block i
+  int m;
+  bool act(int stage) const { return (m >> stage) & 1; }
+  bool temporal(int stage) const { return (m >> (5 + stage)) & 1; }
+  bool shortcut() const { return (m >> 10) & 1; }
+  bool conv_out() const { return (m >> 11) & 1; }
+  bool resample(int i) const { return (m >> (12 + i)) & 1; }
+  bool weight(int stage) const { return (m >> (15 + stage)) & 1; }
+  bool shortcut_weight() const { return (m >> 20) & 1; }
+  bool resample_weight(int i) const { return (m >> (21 + i)) & 1; }
+};
+SplitMask vae_split_mask(int dflt) {
   const int c = debug_choice(DBG_VAE_SPLIT);
-  return (c >> 24) == 1 ? (c & 0xffffff) : VAE_SPLIT_DEFAULT_ENCODER;
-}
-int vae_split_mask(const latte_vae* v) {
-  if (v->encoder) return v->enc_split;
-  const int c = debug_choice(DBG_VAE_SPLIT);
-  return (c >> 24) == 1 ? (c & 0xffffff) : (v->temporal ? VAE_SPLIT_DEFAULT_TEMPORAL : VAE_SPLIT_DEFAULT_SPATIAL);
+  return SplitMask{(c >> 24) == 1 ? (c & 0xffffff) : dflt};
 }
 
 int gemm_h16(const half_t* A, const half_t* W, const float* bias, void* out, const half_t* res, int M, int N, int K, int epi,
@@ -180,21 +192,33 @@ int gemm_h16(const half_t* A, const half_t* W, const float* bias, void* out, con
   return rc_;
 }
 
+// Split-operand 3x3 convolution into the fp32 map `out`: out = conv(hi, w) + bias (+ res), then -- accumulating into out -- conv(lo, w) when
+// lo, the f16 rounding residual of the activation, is given, and conv(hi, w_lo) when w_lo, the residual of the weight, is.
+// up / rows / down: launch_conv3x3's nearest-x2 gather, 3-tap (Conv3d (3,1,1)) and stride-2 forms
+int split_conv(const latte_vae* v, const half_t* hi, const half_t* lo, const half_t* w, const half_t* w_lo, const float* bias, int N, int H, int W,
+               int cin, int cout, int up, const float* res, float* out, int rows, int down, hipStream_t st) {
+  int rc;
+  if ((rc = launch_conv3x3(hi, w, bias, nullptr, nullptr, v->zeros, N, H, W, cin, cout, up, v->dtype, st, res, out, rows, down))) return rc;
+  if (lo && (rc = launch_conv3x3(lo, w, v->zero_bias, nullptr, nullptr, v->zeros, N, H, W, cin, cout, up, v->dtype, st, out, out, rows, down))) return rc;
+  if (w_lo) return launch_conv3x3(hi, w_lo, v->zero_bias, nullptr, nullptr, v->zeros, N, H, W, cin, cout, up, v->dtype, st, out, out, rows, down);
+  return LATTE_OK;
+}
+
 // ResnetBlock2D on the fp32 stream: x = *s -> *s (in place when cin == cout, else through *s2 and the two are swapped);
 // b, c, d: half scratch.  [N, H, W, C]
 int run_resnet(latte_vae* v, const Resnet& r, float** s, float** s2, half_t* b, half_t* c, half_t* d, int N, int H, int W,
-               hipStream_t st, int stage) {
+               hipStream_t st, int stage, SplitMask mask) {
   int rc;
   const int HW = H * W, dt = v->dtype;
   float* x = *s;
   // temporal-decoder mode: the activation operand of both 3x3 convolutions is split hi + lo (b = the f16 rounding residual of the
   // GroupNorm output) and a second pass adds conv(lo): the decoder with twice as many blocks per stage stays under the 1e-3 bar
-  // (round 6: per decoder stage -- split_mask bit `stage`, 0 = mid block, 1 + i = up block i; vae_split_mask())
-  half_t* lo = ((vae_split_mask(v) >> stage) & 1) ? b : nullptr;
-  const bool wlo = (vae_split_mask(v) >> (15 + stage)) & 1;   // + the pass hi * (weight residual)
+  // (round 6: per decoder stage -- SplitMask::act(stage), 0 = mid block, 1 + i = up block i)
+  half_t* lo = mask.act(stage) ? b : nullptr;
+  const bool wlo = mask.weight(stage);   // + the pass hi * (weight residual)
   if (r.cin != r.cout) {   // conv_shortcut 1x1 = a GEMM over pixels on a half copy of the stream, fp32 result (first: b is free here)
     float* y = *s2;
-    if ((vae_split_mask(v) >> 10) & 1) {   // the half copy as hi + lo: y = hi W^T + b, then y += lo W^T (gated-residual epilogue, gate = 1)
+    if (mask.shortcut()) {   // the half copy as hi + lo: y = hi W^T + b, then y += lo W^T (gated-residual epilogue, gate = 1)
       if ((rc = launch_convert_f32_to_h16_split(x, d, b, (int64_t)N * HW * r.cin, dt, st))) return rc;
       kprof_mark(VC_SMALL, st);
       if ((rc = gemm_h16(d, r.scw, r.scb, y, nullptr, N * HW, r.cout, r.cin, EPI_BIAS_F32, dt, st))) return rc;
@@ -204,7 +228,7 @@ int run_resnet(latte_vae* v, const Resnet& r, float** s, float** s2, half_t* b, 
       const int sc_variant = 1;
       if ((rc = launch_gemm(g, EPI_GATE_RES_F32, dt, sc_variant, st))) return rc;
       kprof_mark(VC_ATTN, st);
-      if (r.scw_lo && ((vae_split_mask(v) >> 20) & 1)) {   // + hi * (weight residual)
+      if (r.scw_lo && mask.shortcut_weight()) {   // + hi * (weight residual)
         g.A = d; g.W = r.scw_lo;
         if ((rc = launch_gemm(g, EPI_GATE_RES_F32, dt, sc_variant, st))) return rc;
         kprof_mark(VC_ATTN, st);
@@ -216,49 +240,55 @@ int run_resnet(latte_vae* v, const Resnet& r, float** s, float** s2, half_t* b, 
     }
   }
   if ((rc = launch_groupnorm(x, 1, c, r.n1w, r.n1b, v->gn_partial, v->gn_stats, N, HW, r.cin, 1, dt, st, 1e-6f, groupnorm_max_slabs(), lo))) return rc;
-  if ((rc = launch_conv3x3(c, r.c1w, r.c1b, nullptr, nullptr, v->zeros, N, H, W, r.cin, r.cout, 0, dt, st, nullptr, v->tbuf))) return rc;
-  if (lo && (rc = launch_conv3x3(lo, r.c1w, v->zero_bias, nullptr, nullptr, v->zeros, N, H, W, r.cin, r.cout, 0, dt, st, v->tbuf, v->tbuf))) return rc;
-  if (wlo && (rc = launch_conv3x3(c, r.c1w_lo, v->zero_bias, nullptr, nullptr, v->zeros, N, H, W, r.cin, r.cout, 0, dt, st, v->tbuf, v->tbuf))) return rc;
+  if ((rc = split_conv(v, c, lo, r.c1w, wlo ? r.c1w_lo : nullptr, r.c1b, N, H, W, r.cin, r.cout, 0, nullptr, v->tbuf, 0, 0, st))) return rc;
   if ((rc = launch_groupnorm(v->tbuf, 1, c, r.n2w, r.n2b, v->gn_partial, v->gn_stats, N, HW, r.cout, 1, dt, st, 1e-6f, groupnorm_max_slabs(), lo))) return rc;
-  if (r.cin != r.cout) {
-    float* y = *s2;
-    if ((rc = launch_conv3x3(c, r.c2w, r.c2b, nullptr, nullptr, v->zeros, N, H, W, r.cout, r.cout, 0, dt, st, y, y))) return rc;
-    if (lo && (rc = launch_conv3x3(lo, r.c2w, v->zero_bias, nullptr, nullptr, v->zeros, N, H, W, r.cout, r.cout, 0, dt, st, y, y))) return rc;
-    if (wlo && (rc = launch_conv3x3(c, r.c2w_lo, v->zero_bias, nullptr, nullptr, v->zeros, N, H, W, r.cout, r.cout, 0, dt, st, y, y))) return rc;
-    std::swap(*s, *s2);
-    return LATTE_OK;
-  }
-  if ((rc = launch_conv3x3(c, r.c2w, r.c2b, nullptr, nullptr, v->zeros, N, H, W, r.cout, r.cout, 0, dt, st, x, x))) return rc;
-  if (lo && (rc = launch_conv3x3(lo, r.c2w, v->zero_bias, nullptr, nullptr, v->zeros, N, H, W, r.cout, r.cout, 0, dt, st, x, x))) return rc;
-  if (wlo) return launch_conv3x3(c, r.c2w_lo, v->zero_bias, nullptr, nullptr, v->zeros, N, H, W, r.cout, r.cout, 0, dt, st, x, x);
+  float* y = r.cin != r.cout ? *s2 : x;   // conv2 adds onto the shortcut's result, or onto the stream in place
+  if ((rc = split_conv(v, c, lo, r.c2w, wlo ? r.c2w_lo : nullptr, r.c2b, N, H, W, r.cout, r.cout, 0, y, y, 0, 0, st))) return rc;
+  if (r.cin != r.cout) std::swap(*s, *s2);
   return LATTE_OK;
 }
 
 // TemporalResnetBlock + AlphaBlender on the fp32 stream of ONE video [T, H, W, C]: the frames are the rows of an "image"
 // [T][H W], so the Conv3d (3,1,1) is the implicit-GEMM conv kernel with 3 taps along the rows and GroupNorm sees T H W pixels
-int run_tresnet(latte_vae* v, const TResnet& t, float* x, half_t* c, half_t* clo, int T, int H, int W, hipStream_t st, int stage) {
+int run_tresnet(latte_vae* v, const TResnet& t, float* x, half_t* c, half_t* clo, int T, int H, int W, hipStream_t st, int stage, SplitMask mask) {
   // The two Conv3d run as SPLIT-OPERAND convolutions: activation = hi + lo and weight = hi + lo in f16 (lo = the rounding
   // residual), three MFMA passes hi*hi + lo*hi + hi*lo accumulated in the fp32 output -- the temporal branch then adds ~1e-6 of
   // error instead of one more f16 roundoff per block (with single-pass convolutions the decode measured 1.04e-3 against the
   // fp32 restatement, above the 1e-3 bar; a 3-tap convolution costs a third of a 3x3 one, so three passes cost one)
   int rc;
   const int HW = H * W, dt = v->dtype, C = t.c;
-  if (!((vae_split_mask(v) >> (5 + stage)) & 1)) {   // single-pass temporal convolutions at this stage (split_mask bit 5 + stage clear)
-    if ((rc = launch_groupnorm(x, 1, c, t.n1w, t.n1b, v->gn_partial, v->gn_stats, 1, T * HW, C, 1, dt, st, 1e-5f, groupnorm_max_slabs() * T, nullptr))) return rc;
-    if ((rc = launch_conv3x3(c, t.c1w, t.c1b, nullptr, nullptr, v->zeros, 1, T, HW, C, C, 0, dt, st, nullptr, v->tbuf, 1))) return rc;
-    if ((rc = launch_groupnorm(v->tbuf, 1, c, t.n2w, t.n2b, v->gn_partial, v->gn_stats, 1, T * HW, C, 1, dt, st, 1e-5f, groupnorm_max_slabs() * T, nullptr))) return rc;
-    return launch_conv3x3(c, t.c2w, t.c2b_eff, nullptr, nullptr, v->zeros, 1, T, HW, C, C, 0, dt, st, x, x, 1);
-  }
+  const bool split = mask.temporal(stage);   // clear: single-pass temporal convolutions at this stage
+  if (!split) clo = nullptr;
   if ((rc = launch_groupnorm(x, 1, c, t.n1w, t.n1b, v->gn_partial, v->gn_stats, 1, T * HW, C, 1, dt, st, 1e-5f, groupnorm_max_slabs() * T, clo))) return rc;
-  if ((rc = launch_conv3x3(c, t.c1w, t.c1b, nullptr, nullptr, v->zeros, 1, T, HW, C, C, 0, dt, st, nullptr, v->tbuf, 1))) return rc;
-  if ((rc = launch_conv3x3(clo, t.c1w, v->zero_bias, nullptr, nullptr, v->zeros, 1, T, HW, C, C, 0, dt, st, v->tbuf, v->tbuf, 1))) return rc;
-  if ((rc = launch_conv3x3(c, t.c1w_lo, v->zero_bias, nullptr, nullptr, v->zeros, 1, T, HW, C, C, 0, dt, st, v->tbuf, v->tbuf, 1))) return rc;
+  if ((rc = split_conv(v, c, clo, t.c1w, split ? t.c1w_lo : nullptr, t.c1b, 1, T, HW, C, C, 0, nullptr, v->tbuf, 1, 0, st))) return rc;
   if ((rc = launch_groupnorm(v->tbuf, 1, c, t.n2w, t.n2b, v->gn_partial, v->gn_stats, 1, T * HW, C, 1, dt, st, 1e-5f, groupnorm_max_slabs() * T, clo))) return rc;
   // out = x_spatial + sigmoid(mix) * (conv2 + bias): weights and bias were folded with the blend factor
-  if ((rc = launch_conv3x3(c, t.c2w, t.c2b_eff, nullptr, nullptr, v->zeros, 1, T, HW, C, C, 0, dt, st, x, x, 1))) return rc;
-  if ((rc = launch_conv3x3(clo, t.c2w, v->zero_bias, nullptr, nullptr, v->zeros, 1, T, HW, C, C, 0, dt, st, x, x, 1))) return rc;
-  return launch_conv3x3(c, t.c2w_lo, v->zero_bias, nullptr, nullptr, v->zeros, 1, T, HW, C, C, 0, dt, st, x, x, 1);
+  return split_conv(v, c, clo, t.c2w, split ? t.c2w_lo : nullptr, t.c2b_eff, 1, T, HW, C, C, 0, x, x, 1, 0, st);
 }
+
+// softmax rows sum to 1, so  to_out(P (V0 + 1 bv^T)) = to_out(P V0) + (Wo bv + bo): the value bias is folded into the output bias
+// (once after a weight load) and V^T is produced directly by a GEMM (no transpose kernel)
+int fold_attention_bias(latte_vae* v, hipStream_t st) {
+  const int top = v->ch[3];
+  return launch_small_linear(IN_PLAIN, v->av_b, nullptr, v->ao_w_f32, v->ao_b, nullptr, nullptr, v->ao_b_eff, 1, top, top, top, st);
+}
+
+// The stage-trace test hooks (latte_debug_vae_trace / _encode_trace): the stages of a call are numbered as they come and stage `stop_after`
+// ends it with a copy of that activation (fp32, dims d0..d3) in `out`; who: the hook's error prefix
+struct StageTrace {
+  int stop_after; float* out; int64_t* numel; int* dims; const char* who;
+  int stage_no = 0;
+  bool hit(const float* src, int d0, int d1, int d2, int d3, hipStream_t st, int& rc) {
+    if (stage_no++ != stop_after) return false;
+    const int64_t n = (int64_t)d0 * d1 * d2 * d3;
+    rc = LATTE_OK;
+    if (hipMemcpyAsync(out, src, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, st) != hipSuccess)
+      rc = fail(LATTE_ERR_HIP, std::string(who) + ": copy failed");
+    *numel = n;
+    dims[0] = d0; dims[1] = d1; dims[2] = d2; dims[3] = d3;
+    return true;
+  }
+};
 
 int vae_create_impl(int latent_size, int max_frames, int compute_dtype, bool temporal, latte_vae_t** out);
 int vae_create_encoder_impl(int image_size, int max_frames, int compute_dtype, latte_vae_t** out);
@@ -336,6 +366,22 @@ int run_mid_attention(latte_vae* v, float* a, half_t* b, half_t* c, half_t* d, i
   return LATTE_OK;
 }
 
+// The scratch both kinds of handle need, behind their weights: big = elements of the largest NHWC map, L = h * w of the latent (the
+// attention's tokens); *per_latent = [max_frames, ch, h, w] fp32 (the decoder's post_quant_conv output / the encoder's moments)
+int alloc_workspace(latte_vae* v, size_t big, size_t L, float** per_latent, int ch) {
+  int rc;
+  for (int i = 0; i < 3; ++i) if ((rc = v->arena.alloc(&v->buf[i], big))) return rc;
+  for (int i = 0; i < 2; ++i) if ((rc = v->arena.alloc(&v->sbuf[i], big))) return rc;
+  if ((rc = v->arena.alloc(&v->tbuf, big)) || (rc = v->arena.alloc(&v->ones, 512))) return rc;
+  const std::vector<float> one(512, 1.0f);
+  LATTE_HIP(hipMemcpy(v->ones, one.data(), sizeof(float) * 512, hipMemcpyHostToDevice));
+  if ((rc = v->arena.alloc(&v->zeros, 64)) || (rc = v->arena.alloc(per_latent, (size_t)v->max_frames * ch * L)) ||
+      (rc = v->arena.alloc(&v->scores, L * L)) || (rc = v->arena.alloc(&v->gn_partial, (size_t)v->max_frames * groupnorm_max_slabs() * 64)) ||
+      (rc = v->arena.alloc(&v->gn_stats, (size_t)v->max_frames * 64)))
+    return rc;
+  return v->weights.alloc_stage(v->arena, true);
+}
+
 int vae_create_impl(int latent_size, int max_frames, int compute_dtype, bool temporal, latte_vae_t** out) {
   if (!out || latent_size <= 0 || max_frames <= 0) return fail(LATTE_ERR_INVALID, "vae_create: bad arguments");
   if (compute_dtype != LATTE_DTYPE_F16)
@@ -398,21 +444,7 @@ int vae_create_impl(int latent_size, int max_frames, int compute_dtype, bool tem
 
   // workspace: the largest NHWC map is [N, 8h, 8w, 256] (output of up_blocks.2's upsampler)
   const size_t big = (size_t)max_frames * (8 * latent_size) * (8 * latent_size) * 256;
-  for (int i = 0; i < 3; ++i) TRY(v->arena.alloc(&v->buf[i], big));
-  for (int i = 0; i < 2; ++i) TRY(v->arena.alloc(&v->sbuf[i], big));
-  TRY(v->arena.alloc(&v->tbuf, big));
-  TRY(v->arena.alloc(&v->ones, 512));
-  {
-    std::vector<float> one(512, 1.0f);
-    LATTE_HIP(hipMemcpy(v->ones, one.data(), sizeof(float) * 512, hipMemcpyHostToDevice));
-  }
-  TRY(v->arena.alloc(&v->zeros, 64));
-  TRY(v->arena.alloc(&v->pq_out, (size_t)max_frames * latent_size * latent_size * 4));
-  const size_t L = (size_t)latent_size * latent_size;
-  TRY(v->arena.alloc(&v->scores, L * L));
-  TRY(v->arena.alloc(&v->gn_partial, (size_t)max_frames * groupnorm_max_slabs() * 64));
-  TRY(v->arena.alloc(&v->gn_stats, (size_t)max_frames * 64));
-  TRY(v->weights.alloc_stage(v->arena, true));
+  TRY(alloc_workspace(v, big, (size_t)latent_size * latent_size, &v->pq_out, 4));
 #undef TRY
   *out = v;
   return LATTE_OK;
@@ -466,21 +498,7 @@ int vae_create_encoder_impl(int image_size, int max_frames, int compute_dtype, l
 
   // workspace: the largest NHWC map is [N, H, W, 128] at the full image size (conv_in, down block 0)
   const size_t big = (size_t)max_frames * image_size * image_size * v->ch[0];
-  for (int i = 0; i < 3; ++i) TRY(v->arena.alloc(&v->buf[i], big));
-  for (int i = 0; i < 2; ++i) TRY(v->arena.alloc(&v->sbuf[i], big));
-  TRY(v->arena.alloc(&v->tbuf, big));
-  TRY(v->arena.alloc(&v->ones, 512));
-  {
-    std::vector<float> one(512, 1.0f);
-    LATTE_HIP(hipMemcpy(v->ones, one.data(), sizeof(float) * 512, hipMemcpyHostToDevice));
-  }
-  TRY(v->arena.alloc(&v->zeros, 64));
-  const size_t L = (size_t)v->h * v->h;
-  TRY(v->arena.alloc(&v->moments, (size_t)max_frames * 8 * L));
-  TRY(v->arena.alloc(&v->scores, L * L));
-  TRY(v->arena.alloc(&v->gn_partial, (size_t)max_frames * groupnorm_max_slabs() * 64));
-  TRY(v->arena.alloc(&v->gn_stats, (size_t)max_frames * 64));
-  TRY(v->weights.alloc_stage(v->arena, true));
+  TRY(alloc_workspace(v, big, (size_t)v->h * v->h, &v->moments, 8));
 #undef TRY
   *out = v;
   return LATTE_OK;
@@ -539,22 +557,8 @@ static int vae_decode_impl(latte_vae_t* v, const float* z, int n_frames, float z
 // GroupNorm apply, mid-block attention + 1x1 shortcut GEMMs, small kernels).  Synchronises the stream.
 int latte_vae_profile_decode(latte_vae_t* v, const float* z, int n_frames, float z_scale, int out_mode, void* out, float* ms_out,
                              int* launches_out, int n, void* stream) {
-  if (!ms_out || !launches_out || n < VC_NUM_CLASSES) return fail(LATTE_ERR_INVALID, "vae_profile_decode: bad arguments");
-  KProf prof;
-  g_kprof = &prof;
-  kprof_mark(VC_START, (hipStream_t)stream);
-  int rc = vae_decode_impl(v, z, n_frames, z_scale, out_mode, out, stream, -1, nullptr, nullptr, nullptr);
-  g_kprof = nullptr;
-  if (!rc && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = fail(LATTE_ERR_HIP, "vae_profile_decode: device error");
-  for (int i = 0; i < n; ++i) { ms_out[i] = 0.f; launches_out[i] = 0; }
-  for (size_t i = 1; !rc && i < prof.ev.size(); ++i) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, prof.ev[i - 1], prof.ev[i]) != hipSuccess) { rc = fail(LATTE_ERR_HIP, "vae_profile_decode: event"); break; }
-    const int c = prof.cls[i];
-    if (c >= 0 && c < n) { ms_out[c] += ms; launches_out[c] += 1; }
-  }
-  for (auto ev : prof.ev) (void)hipEventDestroy(ev);
-  return rc;
+  return profile_vae_call("vae_profile_decode", ms_out, launches_out, n, (hipStream_t)stream,
+                          [&] { return vae_decode_impl(v, z, n_frames, z_scale, out_mode, out, stream, -1, nullptr, nullptr, nullptr); });
 }
 
 int latte_vae_decode(latte_vae_t* v, const float* z, int n_frames, float z_scale, int out_mode, void* out, void* stream) {
@@ -580,10 +584,9 @@ static int vae_decode_impl(latte_vae_t* v, const float* z, int n_frames, float z
   hipStream_t st = (hipStream_t)stream;
   const int N = n_frames, dt = v->dtype, top = v->ch[3];
   int H = v->h, W = v->h;
+  const SplitMask mask = vae_split_mask(v->temporal ? VAE_SPLIT_DEFAULT_TEMPORAL : VAE_SPLIT_DEFAULT_SPATIAL);
   if (!v->bias_folded) {
-    // softmax rows sum to 1, so  to_out(P (V0 + 1 bv^T)) = to_out(P V0) + (Wo bv + bo): the value bias is folded into
-    // the output bias and V^T is produced directly by a GEMM (no transpose kernel)
-    if ((rc = launch_small_linear(IN_PLAIN, v->av_b, nullptr, v->ao_w_f32, v->ao_b, nullptr, nullptr, v->ao_b_eff, 1, top, top, top, st))) return rc;
+    if ((rc = fold_attention_bias(v, st))) return rc;
     if (v->temporal) {   // AlphaBlender folded into conv2 of every temporal resnet: out = x_spatial + sigmoid(mix) (conv2 + b)
       auto fold = [&](TResnet& t) -> int {
         int r2 = launch_pack_conv_t(t.c2w_f32, t.c2w, t.c, t.c, t.mix, dt, st, t.c2w_lo);
@@ -596,47 +599,38 @@ static int vae_decode_impl(latte_vae_t* v, const float* z, int n_frames, float z
   }
   half_t *b = v->buf[0], *c = v->buf[1], *d = v->buf[2];
   float *a = v->sbuf[0], *a2 = v->sbuf[1];   // the fp32 residual stream and its ping-pong partner
-  int stage_no = 0, cur_c = top;
+  int cur_c = top;
   // stage numbering: 0 conv_in | 1 mid.resnet0 | 2 mid.attention | 3 mid.resnet1 | then per up block: 3 resnets (+ upsampler)
-  auto traced = [&](int& rc_out) -> bool {
-    if (stage_no++ != stop_after) return false;
-    const int64_t n = (int64_t)N * H * W * cur_c;
-    rc_out = LATTE_OK;
-    if (hipMemcpyAsync(trace_out, a, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, st) != hipSuccess)
-      rc_out = fail(LATTE_ERR_HIP, "vae_trace: copy failed");
-    *trace_numel = n;
-    trace_dims[0] = N; trace_dims[1] = H; trace_dims[2] = W; trace_dims[3] = cur_c;
-    return true;
-  };
+  StageTrace tr{stop_after, trace_out, trace_numel, trace_dims, "vae_trace"};
+  auto traced = [&](int& rc_out) { return tr.hit(a, N, H, W, cur_c, st, rc_out); };
   if ((rc = launch_post_quant(z, v->pq_w, v->pq_b, v->pq_out, N, H * W, z_scale, st))) return rc;
   if ((rc = launch_conv_in(v->pq_out, v->ci_wt, v->ci_b, a, N, H, W, top, st))) return rc;
   if (traced(rc)) return rc;
-  if ((rc = run_resnet(v, v->mid[0], &a, &a2, b, c, d, N, H, W, st, 0))) return rc;
-  if (v->temporal && (rc = run_tresnet(v, v->tmid[0], a, c, d, N, H, W, st, 0))) return rc;
+  if ((rc = run_resnet(v, v->mid[0], &a, &a2, b, c, d, N, H, W, st, 0, mask))) return rc;
+  if (v->temporal && (rc = run_tresnet(v, v->tmid[0], a, c, d, N, H, W, st, 0, mask))) return rc;
   if (traced(rc)) return rc;
   if ((rc = run_mid_attention(v, a, b, c, d, N, H, W, st))) return rc;
   if (traced(rc)) return rc;
-  if ((rc = run_resnet(v, v->mid[1], &a, &a2, b, c, d, N, H, W, st, 0))) return rc;
-  if (v->temporal && (rc = run_tresnet(v, v->tmid[1], a, c, d, N, H, W, st, 0))) return rc;
+  if ((rc = run_resnet(v, v->mid[1], &a, &a2, b, c, d, N, H, W, st, 0, mask))) return rc;
+  if (v->temporal && (rc = run_tresnet(v, v->tmid[1], a, c, d, N, H, W, st, 0, mask))) return rc;
   if (traced(rc)) return rc;
   for (int i = 0; i < 4; ++i) {
     for (int r = 0; r < 3; ++r) {
-      if ((rc = run_resnet(v, v->up[i][r], &a, &a2, b, c, d, N, H, W, st, 1 + i))) return rc;
-      if (v->temporal && (rc = run_tresnet(v, v->tup[i][r], a, c, d, N, H, W, st, 1 + i))) return rc;
+      if ((rc = run_resnet(v, v->up[i][r], &a, &a2, b, c, d, N, H, W, st, 1 + i, mask))) return rc;
+      if (v->temporal && (rc = run_tresnet(v, v->tup[i][r], a, c, d, N, H, W, st, 1 + i, mask))) return rc;
       cur_c = v->up[i][r].cout;
       if (traced(rc)) return rc;
     }
     if (i < 3) {  // Upsample2D: nearest x2 folded into the conv's gather (on a half copy of the stream), fp32 result
       const int cch = v->ch[3 - i];
-      const bool ups_lo = (vae_split_mask(v) >> (12 + i)) & 1;   // the half copy as hi + lo, a second pass on lo
+      const bool ups_lo = mask.resample(i);   // the half copy as hi + lo, a second pass on lo
       if (ups_lo) rc = launch_convert_f32_to_h16_split(a, d, c, (int64_t)N * H * W * cch, dt, st);
       else rc = launch_convert_f32_to_h16(a, d, (int64_t)N * H * W * cch, dt, st);
       if (rc) return rc;
       kprof_mark(VC_SMALL, st);
-      if ((rc = launch_conv3x3(d, v->upc_w[i], v->upc_b[i], nullptr, nullptr, v->zeros, N, H, W, cch, cch, 1, dt, st, nullptr, a2))) return rc;
-      if (ups_lo && (rc = launch_conv3x3(c, v->upc_w[i], v->zero_bias, nullptr, nullptr, v->zeros, N, H, W, cch, cch, 1, dt, st, a2, a2))) return rc;
-      if (v->upc_w_lo[i] && ((vae_split_mask(v) >> (21 + i)) & 1) &&
-          (rc = launch_conv3x3(d, v->upc_w_lo[i], v->zero_bias, nullptr, nullptr, v->zeros, N, H, W, cch, cch, 1, dt, st, a2, a2))) return rc;
+      // (a null upc_w_lo[i] or a clear bit 21 + i: no pass on the weight residual)
+      if ((rc = split_conv(v, d, ups_lo ? c : nullptr, v->upc_w[i], mask.resample_weight(i) ? v->upc_w_lo[i] : nullptr, v->upc_b[i], N, H, W, cch, cch,
+                           1, nullptr, a2, 0, 0, st))) return rc;
       std::swap(a, a2);
       H *= 2;
       W *= 2;
@@ -644,7 +638,7 @@ static int vae_decode_impl(latte_vae_t* v, const float* z, int n_frames, float z
     }
   }
   if (stop_after >= 0) return fail(LATTE_ERR_INVALID, "vae_trace: stage index beyond the last traced stage");
-  half_t* co_lo = ((vae_split_mask(v) >> 11) & 1) ? b : nullptr;   // conv_out reads the GroupNorm output as hi + lo (its weights are fp32)
+  half_t* co_lo = mask.conv_out() ? b : nullptr;   // conv_out reads the GroupNorm output as hi + lo (its weights are fp32)
   if ((rc = launch_groupnorm(a, 1, c, v->no_w, v->no_b, v->gn_partial, v->gn_stats, N, H * W, v->ch[0], 1, dt, st, 1e-6f, groupnorm_max_slabs(), co_lo))) return rc;
   if (!v->temporal) return launch_conv_out(c, v->co_w, v->co_b, out, N, H, W, v->ch[0], out_mode, dt, st, co_lo);
   // conv_out to fp32 NCHW frames, then time_conv_out over the frames of the chunk
@@ -670,70 +664,54 @@ static int vae_encode_impl(latte_vae_t* v, const void* x, int n_frames, int in_m
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int N = n_frames, dt = v->dtype, top = v->ch[3];
-  if (!v->bias_folded) {   // the attention's value bias (see vae_decode_impl) and quant_conv into conv_out
-    if ((rc = launch_small_linear(IN_PLAIN, v->av_b, nullptr, v->ao_w_f32, v->ao_b, nullptr, nullptr, v->ao_b_eff, 1, top, top, top, st))) return rc;
+  const SplitMask mask = vae_split_mask(VAE_SPLIT_DEFAULT_ENCODER);
+  if (!v->bias_folded) {   // the attention's value bias and quant_conv into conv_out
+    if ((rc = fold_attention_bias(v, st))) return rc;
     if ((rc = launch_fold_quant_conv(v->eco_raw, v->eco_rb, v->eq_w, v->eq_b, v->eco_w, v->eco_b, 9 * top, st))) return rc;
     v->bias_folded = true;
   }
-  v->enc_split = encode_split_mask();   // once per call (vae_split_mask reads it for run_resnet)
-  const int split = v->enc_split;
   half_t *b = v->buf[0], *c = v->buf[1], *d = v->buf[2];
   float *a = v->sbuf[0], *a2 = v->sbuf[1];
-  int H = v->img, W = v->img, stage_no = 0, cur_c = v->ch[0];
+  int H = v->img, W = v->img, cur_c = v->ch[0];
   // stage numbering: 0 conv_in | per down block i: resnets 0, 1 (+ down-sampler, i < 3) -> 1..11 | 12 mid.resnet0 | 13 mid.attention |
   // 14 mid.resnet1 | 15 the moments
-  auto traced = [&](int& rc_out) -> bool {
-    if (stage_no++ != stop_after) return false;
-    const int64_t n = (int64_t)N * H * W * cur_c;
-    rc_out = LATTE_OK;
-    if (hipMemcpyAsync(trace_out, a, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, st) != hipSuccess)
-      rc_out = fail(LATTE_ERR_HIP, "vae_encode_trace: copy failed");
-    *trace_numel = n;
-    trace_dims[0] = N; trace_dims[1] = H; trace_dims[2] = W; trace_dims[3] = cur_c;
-    return true;
-  };
+  StageTrace tr{stop_after, trace_out, trace_numel, trace_dims, "vae_encode_trace"};
+  auto traced = [&](int& rc_out) { return tr.hit(a, N, H, W, cur_c, st, rc_out); };
   if ((rc = launch_enc_conv_in(x, in_mode, v->ci_wt, v->ci_b, a, N, H, W, st))) return rc;
   if (traced(rc)) return rc;
   for (int i = 0; i < 4; ++i) {
     for (int r = 0; r < 2; ++r) {
-      if ((rc = run_resnet(v, v->down[i][r], &a, &a2, b, c, d, N, H, W, st, 1 + i))) return rc;
+      if ((rc = run_resnet(v, v->down[i][r], &a, &a2, b, c, d, N, H, W, st, 1 + i, mask))) return rc;
       cur_c = v->down[i][r].cout;
       if (traced(rc)) return rc;
     }
     if (i < 3) {   // Downsample2D: pad (0, 1, 0, 1) + stride 2 in the conv's gather, on a half copy of the stream (split: hi d + lo c)
-      const bool dn_lo = (split >> (12 + i)) & 1;
+      const bool dn_lo = mask.resample(i);
       if (dn_lo) rc = launch_convert_f32_to_h16_split(a, d, c, (int64_t)N * H * W * cur_c, dt, st);
       else rc = launch_convert_f32_to_h16(a, d, (int64_t)N * H * W * cur_c, dt, st);
       if (rc) return rc;
       kprof_mark(VC_SMALL, st);
-      if ((rc = launch_conv3x3(d, v->dnc_w[i], v->dnc_b[i], nullptr, nullptr, v->zeros, N, H, W, cur_c, cur_c, 0, dt, st, nullptr, a2, 0, 1))) return rc;
-      if (dn_lo && (rc = launch_conv3x3(c, v->dnc_w[i], v->zero_bias, nullptr, nullptr, v->zeros, N, H, W, cur_c, cur_c, 0, dt, st, a2, a2, 0, 1))) return rc;
-      if (((split >> (21 + i)) & 1) &&
-          (rc = launch_conv3x3(d, v->dnc_w_lo[i], v->zero_bias, nullptr, nullptr, v->zeros, N, H, W, cur_c, cur_c, 0, dt, st, a2, a2, 0, 1))) return rc;
+      if ((rc = split_conv(v, d, dn_lo ? c : nullptr, v->dnc_w[i], mask.resample_weight(i) ? v->dnc_w_lo[i] : nullptr, v->dnc_b[i], N, H, W, cur_c, cur_c,
+                           0, nullptr, a2, 0, 1, st))) return rc;
       std::swap(a, a2);
       H /= 2;
       W /= 2;
       if (traced(rc)) return rc;
     }
   }
-  if ((rc = run_resnet(v, v->mid[0], &a, &a2, b, c, d, N, H, W, st, 0))) return rc;
+  if ((rc = run_resnet(v, v->mid[0], &a, &a2, b, c, d, N, H, W, st, 0, mask))) return rc;
   if (traced(rc)) return rc;
   if ((rc = run_mid_attention(v, a, b, c, d, N, H, W, st))) return rc;
   if (traced(rc)) return rc;
-  if ((rc = run_resnet(v, v->mid[1], &a, &a2, b, c, d, N, H, W, st, 0))) return rc;
+  if ((rc = run_resnet(v, v->mid[1], &a, &a2, b, c, d, N, H, W, st, 0, mask))) return rc;
   if (traced(rc)) return rc;
-  half_t* co_lo = ((split >> 11) & 1) ? b : nullptr;   // conv_out reads the GroupNorm output as hi + lo (its weights are fp32)
+  half_t* co_lo = mask.conv_out() ? b : nullptr;   // conv_out reads the GroupNorm output as hi + lo (its weights are fp32)
   if ((rc = launch_groupnorm(a, 1, c, v->no_w, v->no_b, v->gn_partial, v->gn_stats, N, H * W, top, 1, dt, st, 1e-6f, groupnorm_max_slabs(), co_lo))) return rc;
   float* mom = (out_mode == 0 && stop_after < 0) ? out : v->moments;
   if ((rc = launch_enc_conv_out(c, co_lo, v->eco_w, v->eco_b, mom, N, H, W, top, dt, st))) return rc;
   if (stop_after >= 0) {
-    if (stage_no != stop_after) return fail(LATTE_ERR_INVALID, "vae_encode_trace: stage index beyond the last traced stage (15, the moments)");
-    const int64_t n = (int64_t)N * 8 * H * W;
-    if (hipMemcpyAsync(trace_out, mom, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, st) != hipSuccess)
-      return fail(LATTE_ERR_HIP, "vae_encode_trace: copy failed");
-    *trace_numel = n;
-    trace_dims[0] = N; trace_dims[1] = 8; trace_dims[2] = H; trace_dims[3] = W;
-    return LATTE_OK;
+    if (tr.hit(mom, N, 8, H, W, st, rc)) return rc;
+    return fail(LATTE_ERR_INVALID, "vae_encode_trace: stage index beyond the last traced stage (15, the moments)");
   }
   if (out_mode == 0) return LATTE_OK;
   return launch_posterior(mom, noise, N, H * W, scale, out_mode, out, st);
@@ -751,22 +729,9 @@ int latte_vae_posterior(const float* moments, const float* noise, int n, int hw,
 
 int latte_vae_profile_encode(latte_vae_t* v, const void* x, int n_frames, int in_mode, const float* noise, float scale, int out_mode, float* out,
                              float* ms_out, int* launches_out, int n, void* stream) {
-  if (!ms_out || !launches_out || n < VC_NUM_CLASSES) return fail(LATTE_ERR_INVALID, "vae_profile_encode: bad arguments");
-  KProf prof;
-  g_kprof = &prof;
-  kprof_mark(VC_START, (hipStream_t)stream);
-  int rc = vae_encode_impl(v, x, n_frames, in_mode, noise, scale, out_mode, out, stream, -1, nullptr, nullptr, nullptr);
-  g_kprof = nullptr;
-  if (!rc && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = fail(LATTE_ERR_HIP, "vae_profile_encode: device error");
-  for (int i = 0; i < n; ++i) { ms_out[i] = 0.f; launches_out[i] = 0; }
-  for (size_t i = 1; !rc && i < prof.ev.size(); ++i) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, prof.ev[i - 1], prof.ev[i]) != hipSuccess) { rc = fail(LATTE_ERR_HIP, "vae_profile_encode: event"); break; }
-    const int c = prof.cls[i];
-    if (c >= 0 && c < n) { ms_out[c] += ms; launches_out[c] += 1; }
-  }
-  for (auto ev : prof.ev) (void)hipEventDestroy(ev);
-  return rc;
+  return profile_vae_call("vae_profile_encode", ms_out, launches_out, n, (hipStream_t)stream, [&] {
+    return vae_encode_impl(v, x, n_frames, in_mode, noise, scale, out_mode, out, stream, -1, nullptr, nullptr, nullptr);
+  });
 }
 
 /* test hook (include/latte_amd_debug.h): run the encoder up to and including stage `stop_after` */
