@@ -281,11 +281,21 @@ int latte_trainer_backward_stage(latte_trainer_t* e, int stage, void* stream);
  * "fuse_small" (default 1, round 6b): the step's tiny launches folded (csrc/train_fin.hip) -- one finalize launch per block
  * stage, the gated residual's backward on the LayerNorm backward's pass, gated add + next LayerNorm in one forward pass, fc1 / qkv
  * bias gradients on the weight-gradient launch, one weight-pack launch; 0 = the separate launches (A/B tests); refused while a
- * step is in flight (between latte_trainer_begin and the last backward stage).  Gradients agree with the separate path to 2e-4. */
+ * step is in flight (between latte_trainer_begin and the last backward stage).  Gradients agree with the separate path to 2e-4.
+ * "grad_accumulate" (default 0): 1 makes every kernel that writes into the bound gradient buffer ADD to what is there, in its own
+ * store (gradient accumulation, train.py:222-236: micro-batch 1 of a window runs with 0 -- no clear needed --, the others with 1;
+ * each micro-batch leaves the loss-scaled domain by the current scale as it is written, and a non-finite value of any micro-batch
+ * survives the sum, so the skip rule of latte_trainer_optimizer_step holds unchanged).  "loss_divisor" (default 1, in [1, 65536]):
+ * d loss.mean() is divided by it (`loss / gradient_accumulation_steps`); the reported terms stay undivided.  Both are refused
+ * while a step is in flight; with both at their defaults the step is bit-identical to a trainer that never heard of them. */
 int latte_trainer_set_option(latte_trainer_t* e, const char* name, double value);
 /* out8 (host) = {loss scale, applied updates since it changed, applied updates in total, skipped updates, last call skipped (0/1),
  * dynamic (0/1), growth interval, largest scale}.  Synchronises the device: for logging and tests, not for the step path. */
 int latte_trainer_scaler_state(latte_trainer_t* e, double* out8);
+/* The inverse: in8 (host, the same eight fields) goes back to the device -- what a resumed run needs besides the five flat buffers:
+ * the live loss scale and its growth count, the count of applied updates (AdamW's bias-correction step), the skip counters and the
+ * policy.  Scales must be powers of two in [1, 2^24], counters integers in [0, 2^24].  Synchronises; refused while a step is in flight. */
+int latte_trainer_set_scaler_state(latte_trainer_t* e, const double* in8);
 int latte_trainer_optimizer_step(latte_trainer_t* e, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                                  float clip_max_norm, int clip, float ema_decay, float* norm_out, void* stream);
 

@@ -98,6 +98,7 @@ PROTOTYPES = {
     "latte_trainer_optimizer_step": (c_int, [c_void, c_f32, c_f32, c_f32, c_f32, c_f32, c_int, c_f32, c_int, c_f32, c_void, c_void]),
     "latte_trainer_set_option": (c_int, [c_void, c_char, ctypes.c_double]),
     "latte_trainer_scaler_state": (c_int, [c_void, ctypes.POINTER(ctypes.c_double)]),
+    "latte_trainer_set_scaler_state": (c_int, [c_void, ctypes.POINTER(ctypes.c_double)]),
     "latte_profile_forward": (c_int, [c_void, c_void, c_void, c_void, c_int, c_void, c_void, c_void, c_int, c_void]),
     "latte_profile_forward_ex": (c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_void, c_void, c_void, c_int, c_void]),
     "latte_t2v_create": (c_int, [ctypes.POINTER(T2VConfig), c_int, ctypes.POINTER(c_void)]),

@@ -304,7 +304,9 @@ int launch_ln_bwd(const half_t* dy, const float* x, const float* scale, int mod_
 int launch_gelu_fwd(const half_t* u, half_t* h, size_t n, int dtype, hipStream_t st);
 int launch_gelu_bwd(const half_t* u, const half_t* dh, half_t* du, size_t n, int dtype, hipStream_t st);
 int colsum_chunks(int M);
-int launch_colsum_half(const half_t* in, int M, int C, float* partial, float* out, int accumulate, int dtype, hipStream_t st);
+// (inv_scale_dev on the writers below: optional device loss scale; what is written or ADDED to `out` is the result x 1 / scale)
+int launch_colsum_half(const half_t* in, int M, int C, float* partial, float* out, int accumulate, int dtype, hipStream_t st,
+                       const float* inv_scale_dev = nullptr);
 // inv_scale_dev: optional device float; the sum is multiplied by 1 / *inv_scale_dev (the loss scale, a power of two) on the way out
 int launch_split_reduce(const float* partial, int splits, size_t stride, size_t n, float* out, int accumulate, hipStream_t st,
                         const float* inv_scale_dev = nullptr);
@@ -324,6 +326,7 @@ struct StageFinArgs {
   float* bias_out[4];
   int bias_blk[5];           // (filled by the launcher)
   const float* scaler;       // device loss scale or nullptr: dW, db and the bias sums leave the scaled domain
+  int accumulate;            // 1: dW, db and the bias sums are ADDED to what the gradient buffer holds (gradient accumulation)
 };
 int launch_stage_finalize(const StageFinArgs& a, hipStream_t st);
 int adaln_dc_splits(int nmod);
@@ -331,24 +334,28 @@ int launch_adaln_dc(const float* dmod, int nmod, int B, const float* w_blocks, l
                     int D, float* ws, float* dc, hipStream_t st);
 int narrow_blocks(int M);
 int launch_narrow_outer(const float* nar, int P, const void* wide, int wide_half, int D, int M, float* dW, long so_p, long so_k,
-                        float* nsum_out, float* wsum_out, float* ws, int dtype, const float* inv_scale_dev, hipStream_t st);
+                        float* nsum_out, float* wsum_out, float* ws, int dtype, const float* inv_scale_dev, hipStream_t st,
+                        int accumulate = 0);
 int launch_narrow_dx(const float* nar, int P, const float* W, int D, int M, half_t* out, int dtype, hipStream_t st);
 struct PackDesc { const float* w; half_t* wn; half_t* wt; int N, K; };
 struct PackPlan { int tiles_per_block; int tile0[4]; };
 int launch_pack_weights(const PackDesc* descs_dev, int blocks, const PackPlan& pl, int dtype, hipStream_t st);
 int launch_naive_gemm(const float* A, long sam, long sak, const float* B, long sbk, long sbn, float* C, long scm, long scn, int M, int N,
-                      int K, float alpha, int accumulate, hipStream_t st, int splits = 1, float* ws = nullptr);
+                      int K, float alpha, int accumulate, hipStream_t st, int splits = 1, float* ws = nullptr,
+                      const float* inv_scale_dev = nullptr);
 int launch_tfreq(const int64_t* t, float* out, int B, hipStream_t st);
 int launch_gather_i64(const int64_t* table, const int64_t* idx, int64_t* out, int n, hipStream_t st);
 int launch_unpatchify_bwd(const float* dout, float* dtok, int BF, int G, int p, int Cout, hipStream_t st);
 int launch_im2col_patch(const float* x, float* pix, int BF, int G, int p, int C, hipStream_t st);
-int launch_embedding_bwd(const float* dc, const int64_t* idx, float* dtable, int B, int D, hipStream_t st);
+int launch_embedding_bwd(const float* dc, const int64_t* idx, float* dtable, int B, int D, hipStream_t st,
+                         const float* inv_scale_dev = nullptr);
 int launch_silu_bwd(const float* dout, const float* pre, float* din, size_t n, int accumulate, hipStream_t st);
 int launch_add_rows(float* dst, const float* src, size_t n, hipStream_t st);
-int launch_rows_sum(const float* in, int B, long stride, int N, float* out, int accumulate, hipStream_t st);
+int launch_rows_sum(const float* in, int B, long stride, int N, float* out, int accumulate, hipStream_t st,
+                    const float* inv_scale_dev = nullptr);
 int launch_loss_grad(const float* tables, int n_steps, int mean_type, int var_type, const float* x_start, const float* x_t,
                      const float* noise, const float* model_out, const int64_t* t, int batch, int frames, int channels, int hw,
-                     float vb_scale, float* dmodel_out, hipStream_t st);
+                     float vb_scale, float* dmodel_out, hipStream_t st, float loss_divisor = 1.0f);
 int sumsq_blocks();
 int launch_grad_norm(const float* g, size_t n, double* partial, float max_norm, int clip, float* stats, float* scaler, hipStream_t st);
 int launch_adamw_ema(float* p, float* g, float* m, float* v, float* ema, size_t n, float lr, float b1, float b2, float eps, float wd,

@@ -510,7 +510,8 @@ __global__ void __launch_bounds__(256) pack_weight_kernel(const float* __restric
 // the K range [z k_chunk, (z + 1) k_chunk) and ASSIGNS its partial product to C + z * c_split_stride (reduce afterwards).
 __global__ void __launch_bounds__(256) naive_gemm_kernel(const float* __restrict__ A, long sam, long sak, const float* __restrict__ B,
                                                          long sbk, long sbn, float* __restrict__ C, long scm, long scn, int M, int N,
-                                                         int K, float alpha, int accumulate, int k_chunk, long c_split_stride) {
+                                                         int K, float alpha, int accumulate, int k_chunk, long c_split_stride,
+                                                         const float* __restrict__ inv_scale) {
   const int n = blockIdx.x * 64 + (threadIdx.x & 63);
   const int m = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (n >= N || m >= M) return;
@@ -531,7 +532,8 @@ __global__ void __launch_bounds__(256) naive_gemm_kernel(const float* __restrict
     s3 += a[(size_t)(k + 3) * sak] * b[(size_t)(k + 3) * sbk];
   }
   for (; k < k1; ++k) s0 += a[(size_t)k * sak] * b[(size_t)k * sbk];
-  const float r = alpha * ((s0 + s1) + (s2 + s3));
+  float r = alpha * ((s0 + s1) + (s2 + s3));
+  if (inv_scale) r *= 1.0f / inv_scale[0];   // the product -- not the accumulated-into value -- leaves the loss-scaled domain (exact)
   float* c = C + (size_t)m * scm + (size_t)n * scn;
   *c = (accumulate && k_chunk == 0) ? *c + r : r;
 }
@@ -576,11 +578,16 @@ __global__ void im2col_patch_kernel(const float* __restrict__ x, float* __restri
     pix[i] = x[((bf * C + c) * H + gh * p + pp) * H + gw * p + q];
   }
 }
-// dtable[idx[b]][:] += dc[b][:]  (serial over b: a label may repeat)
+// dtable[idx[b]][:] += dc[b][:]  (serial over b: a label may repeat);  inv_scale: optional device loss scale (dc x 1 / scale)
 __global__ void embedding_bwd_kernel(const float* __restrict__ dc, const int64_t* __restrict__ idx, float* __restrict__ dtable, int B,
-                                     int D) {
+                                     int D, const float* __restrict__ inv_scale) {
   const int col = blockIdx.x * 256 + threadIdx.x;
   if (col >= D) return;
+  if (inv_scale) {
+    const float f = 1.0f / inv_scale[0];
+    for (int b = 0; b < B; ++b) dtable[(size_t)idx[b] * D + col] += dc[(size_t)b * D + col] * f;
+    return;
+  }
   for (int b = 0; b < B; ++b) dtable[(size_t)idx[b] * D + col] += dc[(size_t)b * D + col];
 }
 // din[i] = dout[i] * silu'(pre[i]),  silu'(x) = s (1 + x (1 - s)),  s = sigmoid(x)
@@ -596,13 +603,15 @@ __global__ void silu_bwd_kernel(const float* __restrict__ dout, const float* __r
 __global__ void add_rows_kernel(float* __restrict__ dst, const float* __restrict__ src, size_t n) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] += src[i];
 }
-// out[col] (+)= sum_b in[b * stride + col]
-__global__ void rows_sum_kernel(const float* __restrict__ in, int B, long stride, int N, float* __restrict__ out, int accumulate) {
+// out[col] (+)= sum_b in[b * stride + col];  inv_scale: optional device loss scale (the sum x 1 / scale)
+__global__ void rows_sum_kernel(const float* __restrict__ in, int B, long stride, int N, float* __restrict__ out, int accumulate,
+                                const float* __restrict__ inv_scale) {
   const int col = blockIdx.x * 256 + threadIdx.x;
   if (col >= N) return;
-  float a = accumulate ? out[col] : 0.f;
+  float a = 0.f;
   for (int b = 0; b < B; ++b) a += in[(size_t)b * stride + col];
-  out[col] = a;
+  if (inv_scale) a *= 1.0f / inv_scale[0];
+  out[col] = accumulate ? out[col] + a : a;
 }
 
 // ---------------------------------------------------------------------------------------------- loss gradient
@@ -621,7 +630,7 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict_
                                                         const float* __restrict__ x0, const float* __restrict__ xt,
                                                         const float* __restrict__ noise, const float* __restrict__ mo,
                                                         const int64_t* __restrict__ t, int batch, int frames, int C, int hw,
-                                                        float vb_scale, float* __restrict__ dmo) {
+                                                        float vb_scale, float loss_divisor, float* __restrict__ dmo) {
   const int b = blockIdx.y;
   const int ti = (int)t[b];
   const float coef1 = tab[DT_COEF1 * n_steps + ti], coef2 = tab[DT_COEF2 * n_steps + ti];
@@ -629,8 +638,9 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict_
   const float srec = tab[DT_SQRT_RECIP * n_steps + ti], srecm1 = tab[DT_SQRT_RECIPM1 * n_steps + ti];
   const size_t chw = (size_t)C * hw, per = (size_t)frames * chw;
   const int Cm = var_type == 0 ? 2 * C : C;
-  const float wmse = 2.0f / ((float)per * (float)batch);
-  const float wvb = vb_scale / ((float)per * (float)batch * 0.6931471805599453f);
+  // loss_divisor: the mean is taken over batch * loss_divisor samples (train.py:222 `loss / gradient_accumulation_steps`; 1: exact no-op)
+  const float wmse = 2.0f / ((float)per * ((float)batch * loss_divisor));
+  const float wvb = vb_scale / ((float)per * ((float)batch * loss_divisor) * 0.6931471805599453f);
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < per; e += (size_t)gridDim.x * 256) {
     const size_t f = e / chw, r = e % chw;
     const size_t i = (size_t)b * per + e;
@@ -919,7 +929,8 @@ int launch_gelu_bwd(const half_t* u, const half_t* dh, half_t* du, size_t n, int
 
 int colsum_chunks(int M) { return (M + CS_ROWS - 1) / CS_ROWS; }
 // out[col] (+)= sum_m in[m][col];  partial: float [colsum_chunks(M)][C]
-int launch_colsum_half(const half_t* in, int M, int C, float* partial, float* out, int accumulate, int dtype, hipStream_t st) {
+int launch_colsum_half(const half_t* in, int M, int C, float* partial, float* out, int accumulate, int dtype, hipStream_t st,
+                       const float* inv_scale_dev) {
   if (C % 8) return fail(LATTE_ERR_INVALID, "colsum: C % 8 != 0");
   const int chunks = colsum_chunks(M);
 #define CALL(DT) hipLaunchKernelGGL(colsum_half_kernel<DT>, dim3((C + 127) / 128, chunks), dim3(256), 0, st, in, M, C, partial)
@@ -927,7 +938,7 @@ int launch_colsum_half(const half_t* in, int M, int C, float* partial, float* ou
 #undef CALL
   if (out)   // nullptr: the chunk partials [colsum_chunks(M)][C] are reduced by the stage's finalize kernel
     hipLaunchKernelGGL(split_reduce_kernel, dim3(blocks_for((size_t)C)), dim3(256), 0, st, partial, chunks, (size_t)C, (size_t)C, out, accumulate,
-                       (const float*)nullptr);
+                       inv_scale_dev);
   LATTE_HIP(hipGetLastError());
   return LATTE_OK;
 }
@@ -955,18 +966,18 @@ int launch_pack_weight(const float* w, half_t* wn, half_t* wt, int N, int K, int
 // splits > 1: the contraction is cut into `splits` ranges, partial products go to `ws` (splits * M * N floats, dense [M][N]) and are
 // reduced into C (which must then be dense row-major: scm = N, scn = 1)
 int launch_naive_gemm(const float* A, long sam, long sak, const float* B, long sbk, long sbn, float* C, long scm, long scn, int M, int N,
-                      int K, float alpha, int accumulate, hipStream_t st, int splits, float* ws) {
+                      int K, float alpha, int accumulate, hipStream_t st, int splits, float* ws, const float* inv_scale_dev) {
   if (splits > 1) {
     if (!ws || scm != N || scn != 1) return fail(LATTE_ERR_INVALID, "naive_gemm: split needs a workspace and a dense output");
     const int chunk = (K + splits - 1) / splits;
     const int ns = (K + chunk - 1) / chunk;
     hipLaunchKernelGGL(naive_gemm_kernel, dim3((N + 63) / 64, (M + 3) / 4, ns), dim3(256), 0, st, A, sam, sak, B, sbk, sbn, ws, (long)N, 1L, M,
-                       N, K, alpha, 0, chunk, (long)M * N);
+                       N, K, alpha, 0, chunk, (long)M * N, (const float*)nullptr);
     hipLaunchKernelGGL(split_reduce_kernel, dim3(blocks_for((size_t)M * N)), dim3(256), 0, st, ws, ns, (size_t)M * N, (size_t)M * N, C,
-                       accumulate, (const float*)nullptr);
+                       accumulate, inv_scale_dev);
   } else {
     hipLaunchKernelGGL(naive_gemm_kernel, dim3((N + 63) / 64, (M + 3) / 4, 1), dim3(256), 0, st, A, sam, sak, B, sbk, sbn, C, scm, scn, M, N,
-                       K, alpha, accumulate, 0, 0L);
+                       K, alpha, accumulate, 0, 0L, inv_scale_dev);
   }
   LATTE_HIP(hipGetLastError());
   return LATTE_OK;
@@ -992,8 +1003,8 @@ int launch_im2col_patch(const float* x, float* pix, int BF, int G, int p, int C,
   LATTE_HIP(hipGetLastError());
   return LATTE_OK;
 }
-int launch_embedding_bwd(const float* dc, const int64_t* idx, float* dtable, int B, int D, hipStream_t st) {
-  hipLaunchKernelGGL(embedding_bwd_kernel, dim3((D + 255) / 256), dim3(256), 0, st, dc, idx, dtable, B, D);
+int launch_embedding_bwd(const float* dc, const int64_t* idx, float* dtable, int B, int D, hipStream_t st, const float* inv_scale_dev) {
+  hipLaunchKernelGGL(embedding_bwd_kernel, dim3((D + 255) / 256), dim3(256), 0, st, dc, idx, dtable, B, D, inv_scale_dev);
   LATTE_HIP(hipGetLastError());
   return LATTE_OK;
 }
@@ -1007,18 +1018,18 @@ int launch_add_rows(float* dst, const float* src, size_t n, hipStream_t st) {
   LATTE_HIP(hipGetLastError());
   return LATTE_OK;
 }
-int launch_rows_sum(const float* in, int B, long stride, int N, float* out, int accumulate, hipStream_t st) {
-  hipLaunchKernelGGL(rows_sum_kernel, dim3((N + 255) / 256), dim3(256), 0, st, in, B, stride, N, out, accumulate);
+int launch_rows_sum(const float* in, int B, long stride, int N, float* out, int accumulate, hipStream_t st, const float* inv_scale_dev) {
+  hipLaunchKernelGGL(rows_sum_kernel, dim3((N + 255) / 256), dim3(256), 0, st, in, B, stride, N, out, accumulate, inv_scale_dev);
   LATTE_HIP(hipGetLastError());
   return LATTE_OK;
 }
 
 int launch_loss_grad(const float* tables, int n_steps, int mean_type, int var_type, const float* x_start, const float* x_t,
                      const float* noise, const float* model_out, const int64_t* t, int batch, int frames, int channels, int hw,
-                     float vb_scale, float* dmodel_out, hipStream_t st) {
+                     float vb_scale, float* dmodel_out, hipStream_t st, float loss_divisor) {
   const size_t per = (size_t)frames * channels * hw;
   hipLaunchKernelGGL(loss_grad_kernel, dim3(blocks_for(per, 256), batch), dim3(256), 0, st, tables, n_steps, mean_type, var_type, x_start,
-                     x_t, noise, model_out, t, batch, frames, channels, hw, vb_scale, dmodel_out);
+                     x_t, noise, model_out, t, batch, frames, channels, hw, vb_scale, loss_divisor, dmodel_out);
   LATTE_HIP(hipGetLastError());
   return LATTE_OK;
 }

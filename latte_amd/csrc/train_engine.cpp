@@ -55,6 +55,14 @@ struct latte_trainer {
   // row-run / column partials of a stage stay in their own buffers until its end, the adaLN linear's input gradient is one batched
   // product at the last stage, the loss-scale pass of the block slices rides on the kernels that write them, one weight-pack launch
   int fuse_small = 1;
+  // Gradient accumulation ("grad_accumulate" / "loss_divisor" options).  grad_accumulate = 1: every kernel that writes into the bound
+  // gradient buffer ADDS to what is there, in its own store -- no second pass, no scratch copy.  Loss scaling needs nothing new: each
+  // micro-batch is unscaled by the CURRENT scale as it is written (in accumulate mode by the writing kernels themselves -- the
+  // per-stage scale pass of the assign mode would rescale the earlier micro-batches' sum -- x 1 / scale, a power of two: the same
+  // bits), the scale changes only inside the optimiser step, and a non-finite value of any micro-batch survives the sum, so the
+  // existing rule applies unchanged: a non-finite gradient norm skips the update and halves the scale.
+  int grad_accumulate = 0;
+  float loss_divisor = 1.0f;     // d loss.mean() / loss_divisor (train.py:222 `loss / gradient_accumulation_steps`); terms stay undivided
   float *pg1 = nullptr, *pl1 = nullptr, *pg2 = nullptr, *pg2b = nullptr, *pl2 = nullptr, *pc_fc1 = nullptr, *pc_qkv = nullptr, *dc_ws = nullptr, *no_ws = nullptr;
   PackDesc* pack_descs = nullptr;
   PackPlan pack_plan{};
@@ -118,8 +126,11 @@ int gemm_gelu(latte_trainer* e, int epi, const half_t* A, const half_t* W, const
   return launch_gemm_pw(g, epi, e->dt, 1, st);
 }
 
+bool scaling_active(const latte_trainer* e);
+const float* acc_scale(const latte_trainer* e);
 // dW[N, K] = dY[M, N]^T X[M, K] on the transposed-operand GEMM (gemm_tn.hip: no transposed copies), the contraction split so
 // that about four workgroups per CU are in flight; the partial products are reduced in a fixed order; result ASSIGNED to dW
+// ("grad_accumulate": ADDED by the reduction's own store, unscaled there)
 // (unscale: the reduction also takes the result out of the loss-scaled domain, x 1 / scaler[0])
 // cs_partial / cs_rows: the column sums of dY per split ([*cs_rows][N]: the bias gradient's partial rows) ride on the launch
 int wgrad(latte_trainer* e, const half_t* dY, const half_t* X, int M, int N, int K, float* dW, hipStream_t st, bool unscale = false,
@@ -129,7 +140,8 @@ int wgrad(latte_trainer* e, const half_t* dY, const half_t* X, int M, int N, int
   if ((int64_t)splits * N * K > e->wg_ws_floats) return fail(LATTE_ERR_STATE, "wgrad: workspace too small");
   if (cs_rows) *cs_rows = splits;
   if ((rc = launch_gemm_tn(dY, X, e->wg_ws, M, N, K, chunk, e->dt, st, cs_partial))) return rc;
-  return launch_split_reduce(e->wg_ws, splits, (size_t)N * K, (size_t)N * K, dW, 0, st, unscale ? e->scaler : nullptr);
+  return launch_split_reduce(e->wg_ws, splits, (size_t)N * K, (size_t)N * K, dW, e->grad_accumulate, st,
+                             unscale ? e->scaler : acc_scale(e));
 }
 
 // loss-scale state -> device.  what: 0 = everything incl. the counters (create), 1 = a new scale (restarts the growth count),
@@ -152,6 +164,8 @@ int upload_scaler(latte_trainer* e, int what) {
   return LATTE_OK;
 }
 bool scaling_active(const latte_trainer* e) { return e->loss_scale != 1.0f || e->dynamic_scale; }
+// accumulate mode: the gradient writers unscale what they add themselves (device loss scale), nullptr otherwise
+const float* acc_scale(const latte_trainer* e) { return e->grad_accumulate && scaling_active(e) ? e->scaler : nullptr; }
 
 }  // namespace
 
@@ -445,7 +459,7 @@ int latte_trainer_begin(latte_trainer_t* e, const latte_schedule_t* s, int loss_
   if ((rc = latte_training_losses(s, loss_type, x_start, e->x_t, noise, e->model_out, t, B, F, e->Cin, hw, e->loss_ws,
                                   e->loss_ws_floats - 3 * e->max_batch, terms_out + B, terms_out + 2 * B, terms_out, stream))) return rc;
   if ((rc = launch_loss_grad(tab, s->num_timesteps, s->mean_type, s->var_type, x_start, e->x_t, noise, e->model_out, t, B, F, e->Cin, hw,
-                             vb_scale, e->dmodel_out, st))) return rc;
+                             vb_scale, e->dmodel_out, st, e->loss_divisor))) return rc;
   if (scaling_active(e) && (rc = launch_scale_f32_dev(e->dmodel_out, e->scaler, 0, (size_t)B * F * e->Cout * hw, st))) return rc;
 
   LATTE_HIP(hipMemsetAsync(e->dc, 0, sizeof(float) * (size_t)B * D, st));   // d SiLU(c), summed over the adaLN linears by the stages
@@ -465,8 +479,10 @@ static int adaln_bwd(latte_trainer_t* e, int i, hipStream_t st) {
   const int N = fin ? 2 * D : 6 * D;
   const float* dm = e->dmod + (size_t)i * 6 * D;
   int rc;
-  if ((rc = launch_rows_sum(dm, B, nmod, N, G_(e, p + "bias"), 0, st))) return rc;
-  if ((rc = launch_naive_gemm(dm, 1, nmod, e->csilu, D, 1, G_(e, p + "weight"), D, 1, N, D, B, 1.0f, 0, st))) return rc;          // dW[n, k]
+  const int acc = e->grad_accumulate;
+  const float* gs = acc_scale(e);
+  if ((rc = launch_rows_sum(dm, B, nmod, N, G_(e, p + "bias"), acc, st, gs))) return rc;
+  if ((rc = launch_naive_gemm(dm, 1, nmod, e->csilu, D, 1, G_(e, p + "weight"), D, 1, N, D, B, 1.0f, acc, st, 1, nullptr, gs))) return rc;   // dW[n, k]
   if ((rc = launch_naive_gemm(dm, nmod, 1, P_(e, p + "weight"), D, 1, e->dtmp, D, 1, B, D, N, 1.0f, 0, st, 48, e->ng_ws))) return rc;  // d csilu
   return launch_add_rows(e->dc, e->dtmp, (size_t)B * D, st);
 }
@@ -494,8 +510,8 @@ int latte_trainer_stage_range(const latte_trainer_t* e, int stage, int64_t* offs
 static int backward_stage_impl(latte_trainer_t* e, int stage, void* stream);
 int latte_trainer_backward_stage(latte_trainer_t* e, int stage, void* stream) {
   int rc = backward_stage_impl(e, stage, stream);
-  // (fuse_small: the block stages' slices were unscaled by the kernels that wrote them)
-  if (!rc && scaling_active(e) && !(e->fuse_small && stage >= 1 && stage <= e->cfg.depth)) {   // the slice this stage finalised leaves the loss-scaled domain
+  // (fuse_small: the block stages' slices were unscaled by the kernels that wrote them; accumulate mode: every slice was)
+  if (!rc && scaling_active(e) && !e->grad_accumulate && !(e->fuse_small && stage >= 1 && stage <= e->cfg.depth)) {   // the slice this stage finalised leaves the loss-scaled domain
     int64_t off = 0, n = 0;
     if ((rc = latte_trainer_stage_range(e, stage, &off, &n))) return rc;
     rc = launch_scale_f32_dev(e->Gr + off, e->scaler, 1, (size_t)n, (hipStream_t)stream);
@@ -526,6 +542,17 @@ int latte_trainer_set_option(latte_trainer_t* e, const char* name, double value)
     e->fuse_small = value != 0.0 ? 1 : 0;
     return LATTE_OK;
   }
+  if (std::string(name) == "grad_accumulate") {   // 0: the gradient writers assign (default), 1: they add (struct latte_trainer)
+    if (e->next_stage <= e->cfg.depth + 1) return fail(LATTE_ERR_STATE, "grad_accumulate: a step is in flight");
+    e->grad_accumulate = value != 0.0 ? 1 : 0;
+    return LATTE_OK;
+  }
+  if (std::string(name) == "loss_divisor") {
+    if (e->next_stage <= e->cfg.depth + 1) return fail(LATTE_ERR_STATE, "loss_divisor: a step is in flight");
+    if (!(value >= 1.0) || value > 65536.0) return fail(LATTE_ERR_INVALID, "loss_divisor must be in [1, 65536]");
+    e->loss_divisor = (float)value;
+    return LATTE_OK;
+  }
   if (std::string(name) == "fuse_gelu") {   // 0: separate GELU passes (rounds 2 - 5), 1: inside the GEMM epilogues (default)
     e->fuse_gelu = value != 0.0 ? 1 : 0;
     return LATTE_OK;
@@ -543,6 +570,8 @@ static int backward_stage_impl(latte_trainer_t* e, int stage, void* stream) {
   const int D = e->D, T = e->T, F = e->F, Hm = e->Hm, B = e->cur_batch, dt = e->dt, nmod = e->nmod;
   const int M = B * F * T, rps = F * T;
   const int64_t* y = e->cur_y;
+  const int acc = e->grad_accumulate;
+  const float* gs = acc_scale(e);
   if (stage == 0) {
   float* xl = e->xs[2 * c.depth];
   const float* fm = e->mod + (size_t)c.depth * 6 * D;
@@ -553,14 +582,14 @@ static int backward_stage_impl(latte_trainer_t* e, int stage, void* stream) {
     // reductions, and its input gradient straight to half (train_fin.hip)
     if ((rc = launch_ln_modulate(xl, xl, e->xnh, fm, fm + D, nmod, M, D, rps, nullptr, T, F, dt, st))) return rc;
     if ((rc = launch_narrow_outer(e->dtok, e->P, e->xnh, 1, D, M, G_(e, "final_layer.linear.weight"), D, 1, G_(e, "final_layer.linear.bias"),
-                                  nullptr, e->no_ws, dt, nullptr, st))) return rc;
+                                  nullptr, e->no_ws, dt, gs, st, acc))) return rc;
     if ((rc = launch_narrow_dx(e->dtok, e->P, P_(e, "final_layer.linear.weight"), D, M, e->dxnH, dt, st))) return rc;
   } else {
-  if ((rc = launch_naive_gemm(e->ones, 0, 1, e->dtok, e->P, 1, G_(e, "final_layer.linear.bias"), e->P, 1, 1, e->P, M, 1.0f, 0, st, 64, e->ng_ws)))
+  if ((rc = launch_naive_gemm(e->ones, 0, 1, e->dtok, e->P, 1, G_(e, "final_layer.linear.bias"), e->P, 1, 1, e->P, M, 1.0f, acc, st, 64, e->ng_ws, gs)))
     return rc;
   if ((rc = launch_ln_modulate(xl, xl, e->xnh, fm, fm + D, nmod, M, D, rps, nullptr, T, F, dt, st))) return rc;
   if ((rc = launch_convert_h16_to_f32(e->xnh, e->f32a, (int64_t)M * D, dt, st))) return rc;
-  if ((rc = launch_naive_gemm(e->dtok, 1, e->P, e->f32a, D, 1, G_(e, "final_layer.linear.weight"), D, 1, e->P, D, M, 1.0f, 0, st, 64, e->ng_ws)))
+  if ((rc = launch_naive_gemm(e->dtok, 1, e->P, e->f32a, D, 1, G_(e, "final_layer.linear.weight"), D, 1, e->P, D, M, 1.0f, acc, st, 64, e->ng_ws, gs)))
     return rc;
   if ((rc = launch_naive_gemm(e->dtok, e->P, 1, P_(e, "final_layer.linear.weight"), D, 1, e->f32b, D, 1, M, D, e->P, 1.0f, 0, st))) return rc;
   if ((rc = launch_convert_f32_to_h16(e->f32b, e->dxnH, (int64_t)M * D, dt, st))) return rc;
@@ -578,7 +607,8 @@ static int backward_stage_impl(latte_trainer_t* e, int stage, void* stream) {
       a.n_mod = 2; a.rows_per_sample = rps / (4 * train_rows_per_run(rps)); a.B = B; a.D = D;
       a.dmod = dm; a.dmod_stride = nmod; a.csilu = e->csilu;
       a.dW = G_(e, "final_layer.adaLN_modulation.1.weight"); a.db = G_(e, "final_layer.adaLN_modulation.1.bias");
-      a.n_bias = 0; a.scaler = nullptr;   // this stage's slice is unscaled by the pass behind the stage
+      a.n_bias = 0; a.scaler = gs;   // assign mode: this stage's slice is unscaled by the pass behind the stage
+      a.accumulate = acc;
       return launch_stage_finalize(a, st);
     }
     if ((rc = launch_ln_bwd(e->dxnH, xl, fm + D, nmod, nullptr, e->dx, e->part_rows, dm, dm + D, nmod, M, D, rps, dt, st))) return rc;
@@ -644,11 +674,12 @@ static int backward_stage_impl(latte_trainer_t* e, int stage, void* stream) {
       a.bias_src[2] = e->pc_fc1;   a.bias_rows[2] = fc1_rows;   a.bias_stride[2] = Hm;    a.bias_cols[2] = Hm;    a.bias_out[2] = G_(e, p + "mlp.fc1.bias");
       a.bias_src[3] = pg2 + D;      a.bias_rows[3] = B * rb; a.bias_stride[3] = 2 * D; a.bias_cols[3] = D;     a.bias_out[3] = G_(e, p + "mlp.fc2.bias");
       a.scaler = us ? e->scaler : nullptr;
+      a.accumulate = acc;
       return launch_stage_finalize(a, st);
     }
     // ---- MLP branch: x2 = x1 + g2 * (fc2(gelu(fc1(xn2))))
     if ((rc = launch_gate_bwd(e->dx, b.y2, mb + 5 * D, nmod, e->dyD, e->part_rows, dm + 5 * D, nmod, M, D, rps, dt, st))) return rc;
-    if ((rc = launch_colsum_half(e->dyD, M, D, e->part_cols, G_(e, p + "mlp.fc2.bias"), 0, dt, st))) return rc;
+    if ((rc = launch_colsum_half(e->dyD, M, D, e->part_cols, G_(e, p + "mlp.fc2.bias"), acc, dt, st, gs))) return rc;
     if ((rc = wgrad(e, e->dyD, b.h, M, D, Hm, G_(e, p + "mlp.fc2.weight"), st))) return rc;
     if (gelu_fusable(e, M, Hm, D)) {   // du = (dy W2) gelu'(u) in the GEMM's epilogue (the product is not rounded to half in between)
       if ((rc = gemm_gelu(e, EPI_DGELU_H16, e->dyD, b.fc2_wt, e->zeros, e->dhH, b.u, M, Hm, D, st))) return rc;
@@ -656,20 +687,20 @@ static int backward_stage_impl(latte_trainer_t* e, int stage, void* stream) {
       if ((rc = gemm_half(e, e->dyD, b.fc2_wt, e->zeros, e->dhH, M, Hm, D, st))) return rc;
       if ((rc = launch_gelu_bwd(b.u, e->dhH, e->dhH, (size_t)M * Hm, dt, st))) return rc;
     }
-    if ((rc = launch_colsum_half(e->dhH, M, Hm, e->part_cols, G_(e, p + "mlp.fc1.bias"), 0, dt, st))) return rc;
+    if ((rc = launch_colsum_half(e->dhH, M, Hm, e->part_cols, G_(e, p + "mlp.fc1.bias"), acc, dt, st, gs))) return rc;
     if ((rc = wgrad(e, e->dhH, b.xn2, M, Hm, D, G_(e, p + "mlp.fc1.weight"), st))) return rc;
     if ((rc = gemm_half(e, e->dhH, b.fc1_wt, e->zeros, e->dxnH, M, D, Hm, st))) return rc;
     if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i + 1], mb + 4 * D, nmod, e->dx, e->dx, e->part_rows, dm + 3 * D, dm + 4 * D, nmod, M, D, rps, dt,
                             st))) return rc;
     // ---- attention branch: x1 = x0 + g1 * proj(attn(qkv(xn1)))
     if ((rc = launch_gate_bwd(e->dx, b.y1, mb + 2 * D, nmod, e->dyD, e->part_rows, dm + 2 * D, nmod, M, D, rps, dt, st))) return rc;
-    if ((rc = launch_colsum_half(e->dyD, M, D, e->part_cols, G_(e, p + "attn.proj.bias"), 0, dt, st))) return rc;
+    if ((rc = launch_colsum_half(e->dyD, M, D, e->part_cols, G_(e, p + "attn.proj.bias"), acc, dt, st, gs))) return rc;
     if ((rc = wgrad(e, e->dyD, b.att, M, D, D, G_(e, p + "attn.proj.weight"), st))) return rc;
     if ((rc = gemm_half(e, e->dyD, b.proj_wt, e->zeros, e->dxnH, M, D, D, st))) return rc;   // d(attention output)
     if (spatial) rc = launch_attention_bwd(b.qkv, b.att, e->dxnH, e->dqkvH, e->attn_stats, B * F, T, c.num_heads, e->hd, F, rps, T, 1, dt, st);
     else         rc = launch_attention_bwd(b.qkv, b.att, e->dxnH, e->dqkvH, e->attn_stats, B * T, F, c.num_heads, e->hd, T, rps, 1, T, dt, st);
     if (rc) return rc;
-    if ((rc = launch_colsum_half(e->dqkvH, M, 3 * D, e->part_cols, G_(e, p + "attn.qkv.bias"), 0, dt, st))) return rc;
+    if ((rc = launch_colsum_half(e->dqkvH, M, 3 * D, e->part_cols, G_(e, p + "attn.qkv.bias"), acc, dt, st, gs))) return rc;
     if ((rc = wgrad(e, e->dqkvH, b.xn1, M, 3 * D, D, G_(e, p + "attn.qkv.weight"), st))) return rc;
     if ((rc = gemm_half(e, e->dqkvH, b.qkv_wt, e->zeros, e->dxnH, M, D, 3 * D, st))) return rc;
     if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i], mb + D, nmod, e->dx, e->dx, e->part_rows, dm, dm + D, nmod, M, D, rps, dt, st))) return rc;
@@ -679,12 +710,12 @@ static int backward_stage_impl(latte_trainer_t* e, int stage, void* stream) {
   if (e->fuse_small && e->KPE <= 32) {   // dW[k][j] = sum_m dx[m][k] pix[m][j], db[k] = sum_m dx[m][k]: one launch + reductions
     if ((rc = launch_im2col_patch(e->x_t, e->pix, B * F, e->G, c.patch_size, e->Cin, st))) return rc;
     if ((rc = launch_narrow_outer(e->pix, e->KPE, e->dx, 0, D, M, G_(e, "x_embedder.proj.weight"), 1, e->KPE, nullptr,
-                                  G_(e, "x_embedder.proj.bias"), e->no_ws, dt, nullptr, st))) return rc;
+                                  G_(e, "x_embedder.proj.bias"), e->no_ws, dt, gs, st, acc))) return rc;
   } else {
-  if ((rc = launch_naive_gemm(e->ones, 0, 1, e->dx, D, 1, G_(e, "x_embedder.proj.bias"), D, 1, 1, D, M, 1.0f, 0, st, 64, e->ng_ws))) return rc;
+  if ((rc = launch_naive_gemm(e->ones, 0, 1, e->dx, D, 1, G_(e, "x_embedder.proj.bias"), D, 1, 1, D, M, 1.0f, acc, st, 64, e->ng_ws, gs))) return rc;
   if ((rc = launch_im2col_patch(e->x_t, e->pix, B * F, e->G, c.patch_size, e->Cin, st))) return rc;
-  if ((rc = launch_naive_gemm(e->dx, 1, D, e->pix, e->KPE, 1, G_(e, "x_embedder.proj.weight"), e->KPE, 1, D, e->KPE, M, 1.0f, 0, st, 64,
-                              e->ng_ws))) return rc;
+  if ((rc = launch_naive_gemm(e->dx, 1, D, e->pix, e->KPE, 1, G_(e, "x_embedder.proj.weight"), e->KPE, 1, D, e->KPE, M, 1.0f, acc, st, 64,
+                              e->ng_ws, gs))) return rc;
   }
   // ---- conditioning tail: d SiLU(c) (summed by the stages) -> c = temb (+ y_emb) -> t_embedder MLP
   if (e->fuse_small) {   // d SiLU(c) = dmod W over every adaLN linear of the model at once (the stages left their dmod rows)
@@ -697,19 +728,20 @@ static int backward_stage_impl(latte_trainer_t* e, int stage, void* stream) {
   if ((rc = launch_silu_bwd(e->dc, e->cvec, e->dtmp, (size_t)B * D, 0, st))) return rc;     // dtmp = dc (gradient of c = temb + y_emb)
   if (c.extras == 2) {
     // the scatter accumulates (a label may repeat inside the batch): clear the slice first, so that forward_backward ASSIGNS this
-    // gradient like every other one (two calls without an optimiser step in between must not double it)
+    // gradient like every other one (two calls without an optimiser step in between must not double it).  Accumulate mode: no
+    // clear -- the scatter's own add IS the accumulation (rows of labels this micro-batch does not hold keep their sum)
     float* gy = G_(e, "y_embedder.embedding_table.weight");
-    LATTE_HIP(hipMemsetAsync(gy, 0, (size_t)(c.num_classes + 1) * D * sizeof(float), st));
-    if ((rc = launch_embedding_bwd(e->dtmp, y, gy, B, D, st))) return rc;
+    if (!acc) LATTE_HIP(hipMemsetAsync(gy, 0, (size_t)(c.num_classes + 1) * D * sizeof(float), st));
+    if ((rc = launch_embedding_bwd(e->dtmp, y, gy, B, D, st, gs))) return rc;
   }
   // temb = W2 SiLU(temb_pre) + b2
-  if ((rc = launch_rows_sum(e->dtmp, B, D, D, G_(e, "t_embedder.mlp.2.bias"), 0, st))) return rc;
-  if ((rc = launch_naive_gemm(e->dtmp, 1, D, e->temb_act, D, 1, G_(e, "t_embedder.mlp.2.weight"), D, 1, D, D, B, 1.0f, 0, st))) return rc;
+  if ((rc = launch_rows_sum(e->dtmp, B, D, D, G_(e, "t_embedder.mlp.2.bias"), acc, st, gs))) return rc;
+  if ((rc = launch_naive_gemm(e->dtmp, 1, D, e->temb_act, D, 1, G_(e, "t_embedder.mlp.2.weight"), D, 1, D, D, B, 1.0f, acc, st, 1, nullptr, gs))) return rc;
   if ((rc = launch_naive_gemm(e->dtmp, D, 1, P_(e, "t_embedder.mlp.2.weight"), D, 1, e->dtmp2, D, 1, B, D, D, 1.0f, 0, st))) return rc;
   if ((rc = launch_silu_bwd(e->dtmp2, e->temb_pre, e->dtmp2, (size_t)B * D, 0, st))) return rc;
   // temb_pre = W0 freq(t) + b0
-  if ((rc = launch_rows_sum(e->dtmp2, B, D, D, G_(e, "t_embedder.mlp.0.bias"), 0, st))) return rc;
-  if ((rc = launch_naive_gemm(e->dtmp2, 1, D, e->tfreq, 256, 1, G_(e, "t_embedder.mlp.0.weight"), 256, 1, D, 256, B, 1.0f, 0, st))) return rc;
+  if ((rc = launch_rows_sum(e->dtmp2, B, D, D, G_(e, "t_embedder.mlp.0.bias"), acc, st, gs))) return rc;
+  if ((rc = launch_naive_gemm(e->dtmp2, 1, D, e->tfreq, 256, 1, G_(e, "t_embedder.mlp.0.weight"), 256, 1, D, 256, B, 1.0f, acc, st, 1, nullptr, gs))) return rc;
   return LATTE_OK;
 }
 
@@ -744,6 +776,30 @@ int latte_trainer_scaler_state(latte_trainer_t* e, double* out8) {
   LATTE_HIP(hipDeviceSynchronize());
   LATTE_HIP(hipMemcpy(h, e->scaler, sizeof(h), hipMemcpyDeviceToHost));
   for (int i = 0; i < 8; ++i) out8[i] = h[i];
+  return LATTE_OK;
+}
+
+// The inverse of latte_trainer_scaler_state: the same eight fields back to the device (a resumed run: the live loss scale, its growth
+// count, AdamW's bias-correction count = applied updates, the skip counters, the policy).  Not while a step is in flight.
+int latte_trainer_set_scaler_state(latte_trainer_t* e, const double* in8) {
+  if (!e || !in8) return fail(LATTE_ERR_INVALID, "trainer_set_scaler_state: null argument");
+  if (e->next_stage <= e->cfg.depth + 1) return fail(LATTE_ERR_STATE, "trainer_set_scaler_state: a step is in flight");
+  int ex = 0;
+  if (!(in8[0] >= 1.0) || in8[0] > 16777216.0 || std::frexp(in8[0], &ex) != 0.5 || !(in8[7] >= in8[0]) || in8[7] > 16777216.0 ||
+      std::frexp(in8[7], &ex) != 0.5)
+    return fail(LATTE_ERR_INVALID, "trainer_set_scaler_state: loss scale and largest scale must be powers of two in [1, 2^24], scale <= largest");
+  for (int i = 1; i <= 4; ++i)
+    if (!(in8[i] >= 0.0) || in8[i] > 16777216.0 || in8[i] != std::floor(in8[i]))
+      return fail(LATTE_ERR_INVALID, "trainer_set_scaler_state: counters must be integers in [0, 2^24] (what a float counts exactly)");
+  if (!(in8[6] >= 1.0) || in8[6] > 1e7) return fail(LATTE_ERR_INVALID, "trainer_set_scaler_state: growth interval must be in [1, 1e7]");
+  float h[8];
+  for (int i = 0; i < 8; ++i) h[i] = (float)in8[i];
+  h[5] = in8[5] != 0.0 ? 1.0f : 0.0f;
+  e->loss_scale = h[0];
+  e->dynamic_scale = (int)h[5];
+  e->growth_interval = h[6];
+  LATTE_HIP(hipDeviceSynchronize());
+  LATTE_HIP(hipMemcpy(e->scaler, h, sizeof(h), hipMemcpyHostToDevice));
   return LATTE_OK;
 }
 

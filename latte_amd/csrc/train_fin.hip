@@ -73,7 +73,7 @@ __global__ void __launch_bounds__(1024) stage_finalize_kernel(StageFinArgs a) {
         float s = 0.f;
         for (int b = 0; b < nb; ++b) s += dm_s[b][tx];
         float* o = a.db + chunk * D + col;
-        *o = bs ? *o + s * inv : s * inv;
+        *o = (bs || a.accumulate) ? *o + s * inv : s * inv;
       }
       const int nq = D >> 2;
       for (int i = threadIdx.x; i < 64 * nq; i += 1024) {
@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(1024) stage_finalize_kernel(StageFinArgs a) {
         }
         float4* w = (float4*)(a.dW + ((size_t)chunk * D + cg * 64 + j) * D) + q;
         o.x *= inv; o.y *= inv; o.z *= inv; o.w *= inv;
-        if (bs) {
+        if (bs || a.accumulate) {
           const float4 p = *w;
           o.x += p.x; o.y += p.y; o.z += p.z; o.w += p.w;
         }
@@ -119,7 +119,7 @@ __global__ void __launch_bounds__(1024) stage_finalize_kernel(StageFinArgs a) {
     float t = 0.f;
 #pragma unroll
     for (int k = 0; k < 16; ++k) t += red[0][k][tx];
-    a.bias_out[s][col] = t * inv;
+    a.bias_out[s][col] = a.accumulate ? a.bias_out[s][col] + t * inv : t * inv;
   }
 }
 
@@ -336,11 +336,12 @@ int launch_stage_finalize(const StageFinArgs& a, hipStream_t st) {
 
 constexpr int NO_ROWS_PER_BLOCK = 128;
 int narrow_blocks(int M) { return (M + NO_ROWS_PER_BLOCK - 1) / NO_ROWS_PER_BLOCK; }
-// dW[p so_p + k so_k] = sum_m nar[m][p] wide[m][k] (assigned), optional bias gradients nsum_out[p] = sum_m nar[m][p],
+// dW[p so_p + k so_k] = sum_m nar[m][p] wide[m][k] (assigned; accumulate != 0: added by the reductions' own stores), optional bias gradients nsum_out[p] = sum_m nar[m][p],
 // wsum_out[k] = sum_m wide[m][k];  wide: fp32 (wide_half == 0) or the engine's half type;  ws: float [narrow_blocks(M)][P D + P + D];
 // inv_scale_dev: optional device loss scale (results x 1 / scale)
 int launch_narrow_outer(const float* nar, int P, const void* wide, int wide_half, int D, int M, float* dW, long so_p, long so_k,
-                        float* nsum_out, float* wsum_out, float* ws, int dtype, const float* inv_scale_dev, hipStream_t st) {
+                        float* nsum_out, float* wsum_out, float* ws, int dtype, const float* inv_scale_dev, hipStream_t st,
+                        int accumulate) {
   if (P < 1 || P > NO_PMAX || D % 4 || D > FIN_DMAX) return fail(LATTE_ERR_INVALID, "narrow_outer: need 1 <= P <= 32, D % 4 == 0, D <= 1280");
   const int nb = narrow_blocks(M), threads = (D / 4 + 63) / 64 * 64;
   float* part = ws;
@@ -362,9 +363,9 @@ int launch_narrow_outer(const float* nar, int P, const void* wide, int wide_half
 #undef NO_CASE
   LATTE_HIP(hipGetLastError());
   int rc;
-  if ((rc = launch_split_reduce(part, nb, (size_t)P * D, (size_t)P * D, dW, 0, st, inv_scale_dev))) return rc;
-  if (nsum_out && (rc = launch_split_reduce(pn, nb, (size_t)P, (size_t)P, nsum_out, 0, st, inv_scale_dev))) return rc;
-  if (wsum_out && (rc = launch_split_reduce(pw, nb, (size_t)D, (size_t)D, wsum_out, 0, st, inv_scale_dev))) return rc;
+  if ((rc = launch_split_reduce(part, nb, (size_t)P * D, (size_t)P * D, dW, accumulate, st, inv_scale_dev))) return rc;
+  if (nsum_out && (rc = launch_split_reduce(pn, nb, (size_t)P, (size_t)P, nsum_out, accumulate, st, inv_scale_dev))) return rc;
+  if (wsum_out && (rc = launch_split_reduce(pw, nb, (size_t)D, (size_t)D, wsum_out, accumulate, st, inv_scale_dev))) return rc;
   return LATTE_OK;
 }
 // out[m][k] = half(sum_p nar[m][p] W[p][k])

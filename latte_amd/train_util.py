@@ -1,0 +1,63 @@
+"""Host-side pieces of the training driver (tools/train.py) that need no GPU: the learning-rate schedule, the data index of a
+micro-batch, which checkpoint a resumed run continues from, and the random-state record that rides beside a checkpoint."""
+import os
+import re
+
+import torch
+
+STATE_SUFFIX = ".state.pt"     # <step>.pt is the reference's {"model", "ema"}; <step>.state.pt holds the rest of the run
+
+
+def scheduled_lr(base_lr, step, warmup_steps=0, scheduler="constant"):
+    """diffusers' ``get_scheduler(name, optimizer, num_warmup_steps)`` (train.py:169-173) for optimiser step ``step`` (from 1):
+    "constant" ignores the warm-up, "constant_with_warmup" is linear from 0 over ``warmup_steps`` -- lr * k / W for k <= W, lr after."""
+    if scheduler == "constant":
+        return float(base_lr)
+    if scheduler == "constant_with_warmup":
+        w = int(warmup_steps or 0)
+        return float(base_lr) * min(1.0, step / w) if w > 0 else float(base_lr)
+    raise ValueError(f"lr_scheduler must be 'constant' or 'constant_with_warmup', got {scheduler!r}")
+
+
+def data_seed(seed, step, micro, accum, rank, world):
+    """Seed of the data generator of micro-batch ``micro`` (0 .. accum-1) of optimiser step ``step`` on ``rank``: micro-batches are
+    numbered step * accum + micro, ranks interleave inside one -- distinct for every (step, micro, rank), and step * world + rank
+    (what a run without accumulation always used) for accum = 1."""
+    if not (0 <= micro < accum and 0 <= rank < world):
+        raise ValueError("need 0 <= micro < accum and 0 <= rank < world")
+    return int(seed) * 1000003 + (int(step) * int(accum) + int(micro)) * int(world) + int(rank)
+
+
+def checkpoint_step(path):
+    """0100000.pt -> 100000 (train.py:195-196); None for anything that is not a numbered checkpoint (the state files beside them)."""
+    m = re.fullmatch(r"(\d+)\.pt", os.path.basename(str(path)))
+    return int(m.group(1)) if m else None
+
+
+def latest_checkpoint(ckpt_dir):
+    """The numerically highest <step>.pt under ``ckpt_dir`` (train.py:180-192), or None."""
+    if not os.path.isdir(ckpt_dir):
+        return None
+    found = [(checkpoint_step(f), f) for f in os.listdir(ckpt_dir)]
+    found = [(s, f) for s, f in found if s is not None]
+    return os.path.join(ckpt_dir, max(found)[1]) if found else None
+
+
+def state_path(ckpt_path, rank=0):
+    """The run-state file beside a checkpoint: rank 0's holds the optimiser state too, the other ranks' only their random state."""
+    stem = str(ckpt_path)[:-len(".pt")]
+    return stem + (STATE_SUFFIX if rank == 0 else f".rng{rank}.pt")
+
+
+def rng_state(device=None):
+    """torch's CPU and (current) device generator states of this process."""
+    st = {"cpu": torch.get_rng_state()}
+    if device is not None and torch.cuda.is_available():
+        st["device"] = torch.cuda.get_rng_state(device)
+    return st
+
+
+def set_rng_state(st, device=None):
+    torch.set_rng_state(st["cpu"].cpu().to(torch.uint8))
+    if "device" in st and device is not None and torch.cuda.is_available():
+        torch.cuda.set_rng_state(st["device"].cpu().to(torch.uint8), device)

@@ -59,11 +59,18 @@ class LatteTrainer:
     step, no host synchronisation (``scaler_state()`` reads the counters back for logging).  ``train_steps`` is the TRAINING-step
     counter of train.py:195-236 (clipping starts at ``start_clip_iter``, checkpoints are numbered by it, a continued run sets it to
     the checkpoint's step); AdamW's bias correction uses the engine's own count of applied updates, which starts at 0 with the
-    fresh moments -- as ``torch.optim.AdamW`` does in the reference."""
+    fresh moments -- as ``torch.optim.AdamW`` does in the reference.
+    gradient_accumulation_steps = A (train.py:222-236, accelerate's ``accumulate``): ``train_step`` runs ONE micro-batch; micro-batch 1
+    of a window assigns the gradient buffer (no clear), micro-batches 2 .. A add to it inside the kernels that write it, the loss
+    gradient is divided by A (the reported terms are not), and clip + AdamW + EMA run after the A-th -- ``train_steps`` counts those
+    optimiser steps.  Data parallel: only the window's last micro-batch takes the staged backward with its per-stage all-reduce (of
+    the ACCUMULATED slice, final only then); the earlier ones run without a collective, as under DDP's ``no_sync``.
+    ``training_state()`` / ``load_training_state()`` carry everything a run is made of (parameters, EMA, AdamW moments, the eight
+    loss-scale / update counters, ``train_steps``, a partial window) so that a resumed run continues bit for bit."""
 
     def __init__(self, model, diffusion, max_batch, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_max_norm=0.1,
                  start_clip_iter=20000, ema_decay=0.9999, class_dropout_prob=0.1, compute_dtype="f16", process_group=None,
-                 loss_scale=None, dynamic_loss_scale=None):
+                 loss_scale=None, dynamic_loss_scale=None, gradient_accumulation_steps=1):
         if not isinstance(model, Latte):
             raise LatteError("LatteTrainer needs a latte_amd.Latte model")
         if not isinstance(diffusion, SpacedDiffusion):
@@ -83,6 +90,11 @@ class LatteTrainer:
         self.process_group = process_group
         self.always_staged = False     # test hook: take the staged (bucketed) backward path without a process group
         self.train_steps = 0
+        self.gradient_accumulation_steps = int(gradient_accumulation_steps)
+        if self.gradient_accumulation_steps < 1:
+            raise LatteError("gradient_accumulation_steps must be >= 1")
+        self.micro_step = 0            # micro-batches of the current window already in the gradient buffer
+        self._accumulating = False     # the engine's "grad_accumulate" option as last set
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise LatteError("move the model to the GPU first (model.to('cuda'))")
@@ -97,6 +109,8 @@ class LatteTrainer:
             check(lib.latte_trainer_set_option(h, b"loss_scale", float(loss_scale)))
         if dynamic_loss_scale is not None:
             check(lib.latte_trainer_set_option(h, b"dynamic_loss_scale", float(bool(dynamic_loss_scale))))
+        if self.gradient_accumulation_steps != 1:
+            check(lib.latte_trainer_set_option(h, b"loss_divisor", float(self.gradient_accumulation_steps)))
         self.compute_dtype = compute_dtype
         n = lib.latte_trainer_num_params(h)
         self.layout = [(lib.latte_trainer_param_key(h, i).decode(), int(lib.latte_trainer_param_offset(h, i)),
@@ -130,7 +144,8 @@ class LatteTrainer:
         """Engine options of the trainer (latte_trainer_set_option): "loss_scale", "dynamic_loss_scale", "loss_scale_growth_interval",
         "fuse_gelu" (0: separate GELU passes, 1: inside the fc1 / fc2-gradient GEMMs -- the default), "fuse_small" (0: the
         separate finalize / column-sum / adaLN / gate-backward launches of rounds 2 - 6, 1: folded -- the default, csrc/train_fin.hip;
-        not while a step is in flight)."""
+        not while a step is in flight), "grad_accumulate" / "loss_divisor" (what ``gradient_accumulation_steps`` drives; see
+        include/latte_amd.h)."""
         check(load_library().latte_trainer_set_option(self._h, name.encode(), float(value)))
 
     def __del__(self):
@@ -240,8 +255,30 @@ class LatteTrainer:
             average_gradients(self.grads, self.process_group)
             self._reduced = True
 
+    def _set_accumulate(self, on):
+        if on != self._accumulating:
+            check(load_library().latte_trainer_set_option(self._h, b"grad_accumulate", float(on)))
+            self._accumulating = on
+
+    def backward_micro_batch(self, x_start, t, noise, y=None, drop_mask=None):
+        """The next micro-batch of the accumulation window: ``forward_backward`` in assign mode for the first, in accumulate mode
+        for the others; the window's last one takes the staged, all-reducing backward when there is a process group.
+        -> (forward_backward's dict, True when the window is complete and ``optimizer_step`` is due)."""
+        if self.micro_step >= self.gradient_accumulation_steps:
+            raise LatteError("the accumulation window is complete: optimizer_step() is due")
+        last = self.micro_step == self.gradient_accumulation_steps - 1
+        self._set_accumulate(self.micro_step > 0)
+        out = self.forward_backward(x_start, t, noise, y, drop_mask,
+                                    overlap_all_reduce=last and (_world(self.process_group) > 1 or self.always_staged))
+        self.micro_step += 1
+        if last:
+            self.all_reduce_gradients()
+        return out, last
+
     def optimizer_step(self):
-        """clip_grad_norm_ + AdamW + update_ema; -> gradient norm (0-d tensor, device)."""
+        """clip_grad_norm_ + AdamW + update_ema; -> gradient norm (0-d tensor, device).  Ends the accumulation window."""
+        self.micro_step = 0
+        self._set_accumulate(False)     # a plain forward_backward assigns again
         self.train_steps += 1
         clip = int(self.train_steps - 1 >= self.start_clip_iter)                  # train.py:228-231
         with torch.cuda.device(self.device):
@@ -262,8 +299,53 @@ class LatteTrainer:
         keys = ("loss_scale", "good_steps", "applied_updates", "skipped_updates", "last_skipped", "dynamic", "growth_interval", "max_scale")
         return dict(zip(keys, [float(v) for v in out]))
 
+    def set_scaler_state(self, state):
+        """Puts the eight values of ``scaler_state()`` back (latte_trainer_set_scaler_state)."""
+        import ctypes
+        keys = ("loss_scale", "good_steps", "applied_updates", "skipped_updates", "last_skipped", "dynamic", "growth_interval", "max_scale")
+        check(load_library().latte_trainer_set_scaler_state(self._h, (ctypes.c_double * 8)(*[float(state[k]) for k in keys])))
+
+    # ------------------------------------------------------------------ the whole state of a run
+    def _keyed(self, flat):
+        named = dict(self.model.named_parameters())
+        return {k: flat[off:off + numel].view(named[k].shape).clone() for k, off, numel in self.layout}
+
+    def training_state(self):
+        """Everything a run continues from: ``model`` / ``ema`` (the reference's checkpoint entries, train.py:257-262), ``opt``
+        (AdamW's ``exp_avg`` / ``exp_avg_sq``, state-dict keyed), ``scaler`` (the eight counters), ``train_steps``, ``micro_step``
+        and, inside a window (``micro_step != 0``), the partial gradient buffer ``grads``."""
+        st = {"model": self.model_state_dict(), "ema": self.ema_state_dict(),
+              "opt": {"exp_avg": self._keyed(self.exp_avg), "exp_avg_sq": self._keyed(self.exp_avg_sq)},
+              "scaler": self.scaler_state(), "train_steps": int(self.train_steps), "micro_step": int(self.micro_step),
+              "gradient_accumulation_steps": int(self.gradient_accumulation_steps)}
+        if self.micro_step:
+            st["grads"] = self._keyed(self.grads)
+        return st
+
+    def load_training_state(self, state):
+        """The inverse of ``training_state()``: buffers, counters and window position back, the packed weights re-synced."""
+        micro = int(state.get("micro_step", 0))
+        if micro and int(state.get("gradient_accumulation_steps", self.gradient_accumulation_steps)) != self.gradient_accumulation_steps:
+            raise LatteError("the state was saved inside an accumulation window of another gradient_accumulation_steps")
+        if micro and "grads" not in state:
+            raise LatteError("the state was saved inside an accumulation window but holds no gradients")
+        with torch.no_grad():
+            for k, off, numel in self.layout:
+                self.exp_avg[off:off + numel].copy_(state["opt"]["exp_avg"][k].reshape(-1).float())
+                self.exp_avg_sq[off:off + numel].copy_(state["opt"]["exp_avg_sq"][k].reshape(-1).float())
+                if micro:
+                    self.grads[off:off + numel].copy_(state["grads"][k].reshape(-1).float())
+            if not micro:
+                self.grads.zero_()
+        self.load_state_dict(state["model"], state["ema"])
+        self.set_scaler_state(state["scaler"])
+        self.train_steps, self.micro_step = int(state["train_steps"]), micro
+        if hasattr(self.model, "mark_weights_dirty"):
+            self.model.mark_weights_dirty()
+
     def train_step(self, x_start, y=None, t=None, noise=None, drop_mask=None):
-        """train.py:197-236 for one micro-batch (gradient_accumulation_steps = 1)."""
+        """train.py:197-236 for one micro-batch; the optimiser step runs after the ``gradient_accumulation_steps``-th of a window
+        (``out["updated"]``; ``out["grad_norm"]`` only then)."""
         B = x_start.shape[0]
         if t is None:
             t = torch.randint(0, self.diffusion.num_timesteps, (B,), device=self.device)       # train.py:223
@@ -271,7 +353,8 @@ class LatteTrainer:
             noise = torch.randn_like(x_start, dtype=torch.float32, device=self.device)          # gd:733-734
         if drop_mask is None and self.model.extras == 2 and self.class_dropout_prob > 0:
             drop_mask = torch.rand(B, device=self.device) < self.class_dropout_prob              # latte.py:142-143
-        out = self.forward_backward(x_start, t, noise, y, drop_mask, overlap_all_reduce=_world(self.process_group) > 1 or self.always_staged)
-        self.all_reduce_gradients()
-        out["grad_norm"] = self.optimizer_step()
+        out, last = self.backward_micro_batch(x_start, t, noise, y, drop_mask)
+        out["updated"] = last
+        if last:
+            out["grad_norm"] = self.optimizer_step()
         return out

@@ -5,8 +5,11 @@
 
 One process per GPU (train.py:55-66), the model replicated, `local_batch_size` latent clips per rank and step; per step
 `LatteTrainer.train_step` = q_sample + forward + training_losses + backward (gradient slices all-reduced over RCCL bucket by bucket
-under the backward) + clip_grad_norm_ + AdamW + update_ema (train.py:197-236).  Checkpoints are the reference's
-`{"model": state_dict, "ema": state_dict}` (train.py:257-262) and load back through `find_model` / `--pretrained`.
+under the backward) + clip_grad_norm_ + AdamW + update_ema (train.py:197-236).  `gradient_accumulation_steps: A` draws A
+micro-batches per optimiser step (steps, logs and checkpoints count optimiser steps).  Checkpoints are the reference's
+`{"model": state_dict, "ema": state_dict}` (train.py:257-262) and load back through `find_model` / `pretrained:`; beside each,
+`<step>.state.pt` holds the rest of the run (AdamW moments, loss-scale / update counters, step, random states; ranks > 0 write
+`<step>.rng<rank>.pt`), and `resume_from_checkpoint: True` continues from the highest-numbered pair bit for bit.
 `data_path` holds one of
   - uint8 frame clips (.npy [F, H, W, 3], H == W == image_size): every batch is encoded on the GPU as the reference does
     (train.py:204-211, `vae.encode(x).latent_dist.sample().mul_(0.18215)`) through `AutoencoderKL.encode_video_uint8`, the VAE
@@ -34,6 +37,8 @@ sys.path.insert(0, ROOT)
 
 import latte_amd  # noqa: E402
 from latte_amd import parallel  # noqa: E402
+from latte_amd.train_util import (checkpoint_step, data_seed, latest_checkpoint, rng_state, scheduled_lr, set_rng_state,  # noqa: E402
+                                  state_path)
 
 
 def clip_label(path):
@@ -43,8 +48,9 @@ def clip_label(path):
 
 class RawClips:
     """Raw uint8 clips [T, Hs, Ws, 3] of any length and size, memory-mapped: per item the reference's temporal window, frame indices and
-    flip coin (datasets/ucf101_datasets.py:198-216, video_transforms.py:386-427) from a generator seeded by (seed, step, rank)."""
+    flip coin (datasets/ucf101_datasets.py:198-216, video_transforms.py:386-427) from a generator seeded by (seed, step, micro, rank)."""
     frames = True
+    accum = 1             # micro-batches per optimiser step (main sets it)
 
     def __init__(self, path, args, rank, world, seed):
         self.files = sorted(glob.glob(os.path.join(path, "*.npy")))
@@ -59,11 +65,11 @@ class RawClips:
             raise SystemExit(f"{self.files[i]}: raw clips are uint8 [T, Hs, Ws, 3], got {a.dtype} {a.shape}")
         return a
 
-    def batch(self, step, n):
+    def batch(self, step, n, micro=0):
         """-> ([(frames uint8 [num_frames, Hs, Ws, 3], flip)] * n, labels)"""
         import random
         from latte_amd import video_transforms
-        s = self.seed * 1000003 + step * self.world + self.rank
+        s = data_seed(self.seed, step, micro, self.accum, self.rank, self.world)
         g = torch.Generator("cpu").manual_seed(s)
         transform, temporal_sample = video_transforms.get_transform(self.args, rng=random.Random(s))
         items, ys = [], []
@@ -79,6 +85,7 @@ class RawClips:
 
 class LatentClips:
     """Rank-sharded, seeded access to the latent clips (DistributedSampler(shuffle=True, seed=global_seed), train.py:136-151)."""
+    accum = 1             # micro-batches per optimiser step (main sets it)
 
     def __init__(self, path, frames, latent, rank, world, seed, num_classes):
         self.synthetic = path in (None, "", "synthetic")
@@ -95,8 +102,8 @@ class LatentClips:
                 self.shape = (frames, 8 * latent, 8 * latent, 3)
                 self.frames = True
 
-    def batch(self, step, n):
-        g = torch.Generator("cpu").manual_seed(self.seed * 1000003 + step * self.world + self.rank)
+    def batch(self, step, n, micro=0):
+        g = torch.Generator("cpu").manual_seed(data_seed(self.seed, step, micro, self.accum, self.rank, self.world))
         if self.synthetic:
             x = torch.randn(n, *self.shape, generator=g)
             y = torch.randint(0, max(self.num_classes, 1), (n,), generator=g)
@@ -124,8 +131,8 @@ def main():
     assert torch.cuda.is_available(), "tools/train.py needs MI355X GPUs"
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
-    if int(args.get("gradient_accumulation_steps") or 1) != 1:
-        raise SystemExit("gradient_accumulation_steps must be 1")
+    accum = int(args.get("gradient_accumulation_steps") or 1)
+    base_lr, warmup, lr_sched = float(args.learning_rate), int(args.get("lr_warmup_steps") or 0), str(args.get("lr_scheduler") or "constant")
     seed = int(args.global_seed)
     torch.manual_seed(seed)                                   # identical replicas (DDP broadcasts rank 0's weights, train.py:125)
     assert args.image_size % 8 == 0, "Image size must be divisible by 8 (for the VAE encoder)."   # train.py:88
@@ -139,14 +146,12 @@ def main():
         model.load_state_dict({**own, **{k: v for k, v in sd.items() if k in own}})          # train.py:109-122
     diffusion = latte_amd.create_diffusion(timestep_respacing="")                                # train.py:92
     trainer = latte_amd.LatteTrainer(model, diffusion, max_batch=nb, lr=float(args.learning_rate), clip_max_norm=float(args.clip_max_norm),
-                                     start_clip_iter=int(args.start_clip_iter))
+                                     start_clip_iter=int(args.start_clip_iter), gradient_accumulation_steps=accum)
     # Replicas were initialised from the shared seed; from here every rank draws its own timesteps, noise and label-dropout
     # masks, as the reference does (train.py:62 `seed = args.global_seed + rank`): a global batch covers world * nb independent
     # draws, not nb draws replicated world times.
     torch.manual_seed(seed + rank)
-    if args.get("resume_from_checkpoint"):
-        raise SystemExit("resume_from_checkpoint (the reference's accelerate-style state resume, train.py:176-192) is not supported: "
-                         "continue from a checkpoint with `pretrained: <results_dir>/checkpoints/<step>.pt`")
+    out_dir = a.out or args.results_dir
     first_step = 0
     if args.get("pretrained"):
         # train.py:195-196: the step counter continues from the checkpoint's file name (0100000.pt -> 100000), so gradient clipping
@@ -157,6 +162,30 @@ def main():
         if stem.isdigit():
             first_step = int(stem)
             trainer.train_steps = first_step
+    if args.get("resume_from_checkpoint"):
+        # train.py:176-192: the highest-numbered checkpoint of THIS run's results_dir -- with the state file beside it the whole run
+        # comes back: parameters, EMA, AdamW moments, bias-correction count, loss scale and its growth count, step, random streams
+        ck = latest_checkpoint(os.path.join(out_dir, "checkpoints"))
+        if ck is None:
+            if rank == 0:
+                print(f"resume_from_checkpoint: no checkpoint under {out_dir}/checkpoints yet, starting a new run", flush=True)
+        else:
+            if not os.path.isfile(state_path(ck)):
+                raise SystemExit(f"resume_from_checkpoint: {ck} has no {os.path.basename(state_path(ck))} beside it (written by an older "
+                                 "version?); continue from its weights alone with `pretrained:`")
+            both = torch.load(ck, map_location="cpu")
+            rest = torch.load(state_path(ck), map_location="cpu")
+            trainer.load_training_state({**rest, "model": both["model"], "ema": both["ema"]})
+            first_step = int(rest["train_steps"])
+            if checkpoint_step(ck) != first_step:
+                raise SystemExit(f"resume_from_checkpoint: {ck} holds the state of step {first_step}")
+            mine = rest if rank == 0 else (torch.load(state_path(ck, rank), map_location="cpu") if os.path.isfile(state_path(ck, rank)) else None)
+            if mine is not None:
+                set_rng_state(mine["rng"], device)
+            sc = trainer.scaler_state()
+            if rank == 0:
+                print(f"Resumed from {ck}: step {first_step}, loss scale {sc['loss_scale']:g}, applied updates {int(sc['applied_updates'])}, "
+                      f"skipped updates {int(sc['skipped_updates'])}", flush=True)
     raw = args.get("frame_interval") not in (None, "") and args.get("data_path") not in (None, "", "synthetic")
     if raw:                                                   # raw clips through the dataset's frame pipeline (datasets/__init__.py:13-76)
         from latte_amd import video_transforms
@@ -169,7 +198,7 @@ def main():
         if not args.get("pretrained_model_path"):
             raise SystemExit("data_path holds uint8 frame clips: set pretrained_model_path (its vae/ subfolder is the SD-VAE to encode with)")
         vae = latte_amd.AutoencoderKL.from_pretrained(args.pretrained_model_path, subfolder="vae", with_encoder=True).to(device)
-    out_dir = a.out or args.results_dir
+    data.accum = accum
     max_steps = a.max_steps or int(args.max_train_steps)
     log_every = a.log_every or int(args.log_every)
     ckpt_every = a.ckpt_every or int(args.ckpt_every)
@@ -179,17 +208,19 @@ def main():
     parallel.barrier()
     running, t0, log_steps = 0.0, time.time(), 0
     stuck_logs = 0      # consecutive log lines whose whole interval was skipped updates at the floor scale (or with scaling off)
-    seen_skips = 0.0
+    seen_skips = trainer.scaler_state()["skipped_updates"]
     for step in range(first_step + 1, max_steps + 1):
-        x, y = data.batch(step, nb)
-        if vae is not None:                                   # train.py:204-211, posterior noise from this step's seeded generator
-            gen = torch.Generator(device).manual_seed(seed * 1000003 + step * world + rank)
-            if raw:                                           # per item (sizes differ): one upload, one transform launch, the encode
-                x = torch.cat([vae.encode_video_raw(fr.to(device).unsqueeze(0), raw_transform, flip=[fl], generator=gen) for fr, fl in x])
-            else:
-                x = vae.encode_video_uint8(x.to(device), generator=gen)
-        out = trainer.train_step(x.to(device), y=y.to(device) if int(args.extras) == 2 else None)
-        running += float(out["loss"].mean())                  # (the reference's loss.item(), train.py:239)
+        trainer.lr = scheduled_lr(base_lr, step, warmup, lr_sched)     # get_scheduler(...).step(), train.py:169-173,233 (host side only)
+        for micro in range(accum):                            # the optimiser step runs inside the last train_step of the window
+            x, y = data.batch(step, nb, micro)
+            if vae is not None:                               # train.py:204-211, posterior noise from this micro-batch's seeded generator
+                gen = torch.Generator(device).manual_seed(data_seed(seed, step, micro, accum, rank, world))
+                if raw:                                       # per item (sizes differ): one upload, one transform launch, the encode
+                    x = torch.cat([vae.encode_video_raw(fr.to(device).unsqueeze(0), raw_transform, flip=[fl], generator=gen) for fr, fl in x])
+                else:
+                    x = vae.encode_video_uint8(x.to(device), generator=gen)
+            out = trainer.train_step(x.to(device), y=y.to(device) if int(args.extras) == 2 else None)
+            running += float(out["loss"].mean()) / accum      # (the reference's loss.item(), train.py:239; undivided terms)
         log_steps += 1
         if step % log_every == 0:
             torch.cuda.synchronize()
@@ -209,7 +240,7 @@ def main():
             stuck_logs = stuck_logs + 1 if stuck else 0
             if rank == 0:
                 print(f"(step={step:07d}) Train Loss: {float(avg):.4f}, Gradient Norm: {float(out['grad_norm']):.4f}, "
-                      f"Train Steps/Sec: {sps:.2f}, samples/s: {sps * nb * world:.1f}, loss scale: {sc['loss_scale']:g}, "
+                      f"Train Steps/Sec: {sps:.2f}, samples/s: {sps * nb * accum * world:.1f}, loss scale: {sc['loss_scale']:g}, "
                       f"skipped updates: {int(sc['skipped_updates'])} (+{int(new_skips)})", flush=True)
                 if new_skips and not stuck:
                     print(f"  warning: {int(new_skips)} of the last {log_steps} updates were skipped (non-finite gradient norm)", flush=True)
@@ -219,11 +250,17 @@ def main():
                                    + " -- the model has diverged or an f16 activation overflows; lower the learning rate or train with compute_dtype='bf16'")
             running, t0, log_steps = 0.0, time.time(), 0
         if step % ckpt_every == 0 or step == max_steps:
+            # <step>.pt stays the reference's two entries; the rest of the run goes beside it (read back by resume_from_checkpoint):
+            # every rank its random state, rank 0 also the AdamW moments and the counters
+            path = os.path.join(out_dir, "checkpoints", f"{step:07d}.pt")
+            mine = {"rng": rng_state(device), "train_steps": step}
             if rank == 0:
-                path = os.path.join(out_dir, "checkpoints", f"{step:07d}.pt")
-                torch.save({"model": {k: v.cpu() for k, v in trainer.model_state_dict().items()},
-                            "ema": {k: v.cpu() for k, v in trainer.ema_state_dict().items()}}, path)
+                st = trainer.training_state()
+                torch.save({"model": {k: v.cpu() for k, v in st["model"].items()}, "ema": {k: v.cpu() for k, v in st["ema"].items()}}, path)
                 print(f"Saved checkpoint to {path}", flush=True)
+                mine.update({k: v for k, v in st.items() if k not in ("model", "ema", "opt")})
+                mine["opt"] = {m: {k: v.cpu() for k, v in st["opt"][m].items()} for m in st["opt"]}
+            torch.save(mine, state_path(path, rank))
             parallel.barrier()
     if world > 1:
         torch.distributed.destroy_process_group()
