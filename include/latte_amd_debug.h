@@ -126,6 +126,57 @@ int latte_debug_ln_bwd(const void* dy, const float* x, const float* scale, int m
 int latte_debug_gate_bwd(const float* dx, const void* y, const float* gate, int gate_stride, void* dy, float* partial,
                          int64_t partial_floats, float* dgate, int out_stride, int M, int D, int rows_per_sample, int bias_partial,
                          int dtype, void* stream);
+/* The training step's gradient writers (csrc/train.hip, csrc/train_fin.hip), one launch sequence each exactly as the trainer makes it.
+ * Common to all: accumulate 0 assigns `out`, 1 adds to what it holds (gradient accumulation); inv_scale_dev is a device pointer to ONE
+ * float, the loss scale (a power of two), or NULL: the SUM -- not the accumulated-into value -- is multiplied by 1 / scale on the way out.
+ *   split_reduce   out[i] (+)= sum_s partial[s * stride + i], i < n, slabs added in order (16-byte kernel for n >= 4096, n % 4 ==
+ *                  stride % 4 == 0 and 16-byte aligned buffers, else the scalar kernel: the same sum in the same order)
+ *   colsum_half    out[c] (+)= sum_m in[m][c] of a half [M, C] matrix (C % 8 == 0); workspace: >= ceil(M / 512) * C floats, receives the
+ *                  per-512-row chunk sums; out == NULL: they stay there unreduced (what the fused stage's finalize kernel reads)
+ *   rows_sum       out[c] (+)= sum_b in[b * stride + c], c < N
+ *   naive_gemm     C[m scm + n scn] (+)= alpha sum_k A[m sam + k sak] B[k sbk + n sbn] (fp32, any strides); splits > 1: the contraction is
+ *                  cut into ranges whose products go to ws (>= splits * M * N floats) and are reduced into a dense C (scm == N, scn == 1)
+ *   embedding_bwd  dtable[idx[b]][:] += dc[b][:] (/ scale), b in order (always adds; idx: int64 [B])
+ *   silu_bwd       din[i] (+)= dout[i] silu'(pre[i]); din may be dout */
+int latte_debug_split_reduce(const float* partial, int splits, int64_t stride, int64_t n, float* out, int accumulate,
+                             const float* inv_scale_dev, void* stream);
+int latte_debug_colsum_half(const void* in, int M, int C, float* workspace, int64_t workspace_floats, float* out_or_null, int accumulate,
+                            int dtype, const float* inv_scale_dev, void* stream);
+int latte_debug_rows_sum(const float* in, int B, int64_t stride, int N, float* out, int accumulate, const float* inv_scale_dev, void* stream);
+int latte_debug_naive_gemm(const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk, int64_t sbn, float* C, int64_t scm,
+                           int64_t scn, int M, int N, int K, float alpha, int accumulate, int splits, float* ws, int64_t ws_floats,
+                           const float* inv_scale_dev, void* stream);
+int latte_debug_embedding_bwd(const float* dc, const int64_t* idx, float* dtable, int B, int D, const float* inv_scale_dev, void* stream);
+int latte_debug_silu_bwd(const float* dout, const float* pre, float* din, int64_t n, int accumulate, void* stream);
+/* The fused finalize launch of one block stage (csrc/train_fin.hip, StageFinArgs of csrc/common.h passed flat; the pointer and int
+ * arrays are HOST arrays of n_mod (<= 6) and n_bias (<= 4) entries):  per modulation chunk c, mod_src[c] holds row-run partials
+ * [B rows_per_sample][mod_nsum[c]][D] of which row mod_which[c] is summed per sample -> dmod[b][c D + col] (assigned, stays in the
+ * loss-scaled domain), db[c D + col] (+)= sum_b dmod / scale, dW[c D + n][k] (+)= sum_b dmod[b][c D + n] csilu[b][k] / scale;  per bias
+ * sum s, bias_out[s][col] (+)= sum_r bias_src[s][r bias_stride[s] + col] / scale, col < bias_cols[s], r < bias_rows[s].  D % 64 == 0,
+ * D <= 1280. */
+int latte_debug_stage_finalize(const float* const* mod_src, const int* mod_nsum, const int* mod_which, int n_mod, int rows_per_sample,
+                               int B, int D, float* dmod, int dmod_stride, const float* csilu, float* dW, float* db, int n_bias,
+                               const float* const* bias_src, const int* bias_rows, const int* bias_stride, const int* bias_cols,
+                               float* const* bias_out, const float* scaler_dev, int accumulate, void* stream);
+/* dc[b][k] = sum_n dmod[b][n] W(n)[k] (assigned), W = the concatenated adaLN weights: `depth` matrices of rows6 rows at w_blocks +
+ * i * blk_stride, then the final layer's nmod - depth * rows6 rows at w_final; D % 64 == 0; ws: >= ceil(nmod / 1024) * B * D floats. */
+int latte_debug_adaln_dc(const float* dmod, int nmod, int B, const float* w_blocks, int64_t blk_stride, int depth, int rows6,
+                         const float* w_final, int D, float* ws, int64_t ws_floats, float* dc, void* stream);
+/* Narrow-operand products (final linear / patch embed): dW[p so_p + k so_k] (+)= sum_m nar[m][p] wide[m][k] / scale, nsum_out[p] (+)= sum_m
+ * nar[m][p] / scale, wsum_out[k] (+)= sum_m wide[m][k] / scale (either may be NULL); nar fp32 [M, P], wide [M, D] fp32 (wide_half 0) or half
+ * of `dtype`; 1 <= P <= 32, D % 4 == 0, D <= 1280; ws: >= ceil(M / 128) * (P D + P + D) floats.
+ * narrow_dx: out[m][k] = half(sum_p nar[m][p] W[p][k]), W fp32 [P, D]. */
+int latte_debug_narrow_outer(const float* nar, int P, const void* wide, int wide_half, int D, int M, float* dW, int64_t so_p, int64_t so_k,
+                             float* nsum_out, float* wsum_out, float* ws, int64_t ws_floats, int dtype, const float* inv_scale_dev,
+                             int accumulate, void* stream);
+int latte_debug_narrow_dx(const float* nar, int P, const float* W, int D, int M, void* out, int dtype, void* stream);
+/* The half operand copies of fp32 [N, K] weights: wn = half [N, K], wt = half [K, N].  pack_weights: every linear of every block in one
+ * launch -- HOST arrays w_ptrs / wn_ptrs / wt_ptrs [blocks * 4] (block-major), the four linears' shapes N[4], K[4] shared by all blocks;
+ * builds the device table and the tile plan as the trainer does, synchronises and frees the table.  pack_weight: one matrix, one launch
+ * (wn or wt may be NULL). */
+int latte_debug_pack_weights(const float* const* w_ptrs, const int* N, const int* K, void* const* wn_ptrs, void* const* wt_ptrs, int blocks,
+                             int dtype, void* stream);
+int latte_debug_pack_weight(const float* w, void* wn, void* wt, int N, int K, int dtype, void* stream);
 /* d mean_b(terms["loss"]) / d model_output of GaussianDiffusion.training_losses (gaussian_diffusion.py:719-795) for the schedule's
  * model types: loss_type 0 MSE, 1 RESCALED_MSE; x_start / x_t / noise [batch, frames, channels, hw], model_out and dmodel_out
  * [batch, frames, channels (x 2 when the schedule learns sigma), hw] fp32; t: int64 [batch] timestep indices. */

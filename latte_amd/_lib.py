@@ -180,6 +180,21 @@ PROTOTYPES = {
                                    c_void, c_int, c_void, c_void, c_void, c_i64, c_int, c_void]),
     "latte_debug_gate_bwd": (c_int, [c_void, c_void, c_void, c_int, c_void, c_void, c_i64, c_void, c_int, c_int, c_int, c_int, c_int,
                                      c_int, c_void]),
+    "latte_debug_split_reduce": (c_int, [c_void, c_int, c_i64, c_i64, c_void, c_int, c_void, c_void]),
+    "latte_debug_colsum_half": (c_int, [c_void, c_int, c_int, c_void, c_i64, c_void, c_int, c_int, c_void, c_void]),
+    "latte_debug_rows_sum": (c_int, [c_void, c_int, c_i64, c_int, c_void, c_int, c_void, c_void]),
+    "latte_debug_naive_gemm": (c_int, [c_void, c_i64, c_i64, c_void, c_i64, c_i64, c_void, c_i64, c_i64, c_int, c_int, c_int, c_f32,
+                                       c_int, c_int, c_void, c_i64, c_void, c_void]),
+    "latte_debug_embedding_bwd": (c_int, [c_void, c_void, c_void, c_int, c_int, c_void, c_void]),
+    "latte_debug_silu_bwd": (c_int, [c_void, c_void, c_void, c_i64, c_int, c_void]),
+    "latte_debug_stage_finalize": (c_int, [c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void, c_int, c_void, c_void, c_void,
+                                           c_int, c_void, c_void, c_void, c_void, c_void, c_void, c_int, c_void]),
+    "latte_debug_adaln_dc": (c_int, [c_void, c_int, c_int, c_void, c_i64, c_int, c_int, c_void, c_int, c_void, c_i64, c_void, c_void]),
+    "latte_debug_narrow_outer": (c_int, [c_void, c_int, c_void, c_int, c_int, c_int, c_void, c_i64, c_i64, c_void, c_void, c_void, c_i64,
+                                         c_int, c_void, c_int, c_void]),
+    "latte_debug_narrow_dx": (c_int, [c_void, c_int, c_void, c_int, c_int, c_void, c_int, c_void]),
+    "latte_debug_pack_weights": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_void]),
+    "latte_debug_pack_weight": (c_int, [c_void, c_void, c_void, c_int, c_int, c_int, c_void]),
     "latte_debug_loss_grad": (c_int, [c_void, c_int, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void,
                                       c_void]),
     "latte_debug_fill_normal": (c_int, [c_void, c_i64, c_u64, c_u64, c_void]),

@@ -332,6 +332,134 @@ int latte_debug_gate_bwd(const float* dx, const void* y, const float* gate, int 
                          (hipStream_t)stream, bias_partial);
 }
 
+// ---- the training step's gradient writers: argument checks + the trainer's own launchers, unchanged
+static bool bad_mode(int accumulate) { return accumulate != 0 && accumulate != 1; }
+
+int latte_debug_split_reduce(const float* partial, int splits, int64_t stride, int64_t n, float* out, int accumulate,
+                             const float* inv_scale_dev, void* stream) {
+  if (!partial || !out || splits < 1 || n < 1 || stride < n || bad_mode(accumulate))
+    return fail(LATTE_ERR_INVALID, "split_reduce: need splits >= 1, 1 <= n <= stride, accumulate 0 or 1");
+  return launch_split_reduce(partial, splits, (size_t)stride, (size_t)n, out, accumulate, (hipStream_t)stream, inv_scale_dev);
+}
+
+int latte_debug_colsum_half(const void* in, int M, int C, float* workspace, int64_t workspace_floats, float* out_or_null, int accumulate,
+                            int dtype, const float* inv_scale_dev, void* stream) {
+  if (!in || !workspace || M < 1 || C < 1 || bad_mode(accumulate)) return fail(LATTE_ERR_INVALID, "colsum_half: bad arguments");
+  if ((int64_t)colsum_chunks(M) * C > workspace_floats) return fail(LATTE_ERR_INVALID, "colsum_half: workspace too small");
+  return launch_colsum_half((const half_t*)in, M, C, workspace, out_or_null, accumulate, dtype, (hipStream_t)stream, inv_scale_dev);
+}
+
+int latte_debug_rows_sum(const float* in, int B, int64_t stride, int N, float* out, int accumulate, const float* inv_scale_dev, void* stream) {
+  if (!in || !out || B < 1 || N < 1 || stride < N || bad_mode(accumulate))
+    return fail(LATTE_ERR_INVALID, "rows_sum: need B >= 1, 1 <= N <= stride, accumulate 0 or 1");
+  return launch_rows_sum(in, B, (long)stride, N, out, accumulate, (hipStream_t)stream, inv_scale_dev);
+}
+
+int latte_debug_naive_gemm(const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk, int64_t sbn, float* C, int64_t scm,
+                           int64_t scn, int M, int N, int K, float alpha, int accumulate, int splits, float* ws, int64_t ws_floats,
+                           const float* inv_scale_dev, void* stream) {
+  if (!A || !B || !C || M < 1 || N < 1 || K < 1 || splits < 1 || bad_mode(accumulate) || sam < 0 || sak < 0 || sbk < 0 || sbn < 0 ||
+      scm < 0 || scn < 0)
+    return fail(LATTE_ERR_INVALID, "naive_gemm: bad arguments");
+  if (splits > 1 && ws && (int64_t)splits * M * N > ws_floats) return fail(LATTE_ERR_INVALID, "naive_gemm: workspace too small");
+  return launch_naive_gemm(A, (long)sam, (long)sak, B, (long)sbk, (long)sbn, C, (long)scm, (long)scn, M, N, K, alpha, accumulate,
+                           (hipStream_t)stream, splits, ws, inv_scale_dev);
+}
+
+int latte_debug_embedding_bwd(const float* dc, const int64_t* idx, float* dtable, int B, int D, const float* inv_scale_dev, void* stream) {
+  if (!dc || !idx || !dtable || B < 1 || D < 1) return fail(LATTE_ERR_INVALID, "embedding_bwd: bad arguments");
+  return launch_embedding_bwd(dc, idx, dtable, B, D, (hipStream_t)stream, inv_scale_dev);
+}
+
+int latte_debug_silu_bwd(const float* dout, const float* pre, float* din, int64_t n, int accumulate, void* stream) {
+  if (!dout || !pre || !din || n < 1 || bad_mode(accumulate)) return fail(LATTE_ERR_INVALID, "silu_bwd: bad arguments");
+  return launch_silu_bwd(dout, pre, din, (size_t)n, accumulate, (hipStream_t)stream);
+}
+
+int latte_debug_stage_finalize(const float* const* mod_src, const int* mod_nsum, const int* mod_which, int n_mod, int rows_per_sample,
+                               int B, int D, float* dmod, int dmod_stride, const float* csilu, float* dW, float* db, int n_bias,
+                               const float* const* bias_src, const int* bias_rows, const int* bias_stride, const int* bias_cols,
+                               float* const* bias_out, const float* scaler_dev, int accumulate, void* stream) {
+  if (n_mod < 0 || n_mod > 6 || n_bias < 0 || n_bias > 4)
+    return fail(LATTE_ERR_INVALID, "stage_finalize: at most 6 modulation chunks and 4 bias sums");
+  if (B < 1 || D < 1 || rows_per_sample < 1 || bad_mode(accumulate) || (n_mod && (!mod_src || !mod_nsum || !mod_which || !dmod || !csilu ||
+      !dW || !db || dmod_stride < n_mod * D)) || (n_bias && (!bias_src || !bias_rows || !bias_stride || !bias_cols || !bias_out)))
+    return fail(LATTE_ERR_INVALID, "stage_finalize: bad arguments");
+  StageFinArgs a{};
+  for (int c = 0; c < n_mod; ++c) {
+    if (!mod_src[c] || mod_nsum[c] < 1 || mod_which[c] < 0 || mod_which[c] >= mod_nsum[c])
+      return fail(LATTE_ERR_INVALID, "stage_finalize: modulation chunk needs a source and 0 <= which < nsum");
+    a.mod_src[c] = mod_src[c]; a.mod_nsum[c] = mod_nsum[c]; a.mod_which[c] = mod_which[c];
+  }
+  for (int s = 0; s < n_bias; ++s) {
+    if (!bias_src[s] || !bias_out[s] || bias_rows[s] < 1 || bias_cols[s] < 1 || bias_stride[s] < bias_cols[s])
+      return fail(LATTE_ERR_INVALID, "stage_finalize: bias sum needs buffers, rows >= 1 and 1 <= cols <= stride");
+    a.bias_src[s] = bias_src[s]; a.bias_rows[s] = bias_rows[s]; a.bias_stride[s] = bias_stride[s]; a.bias_cols[s] = bias_cols[s];
+    a.bias_out[s] = bias_out[s];
+  }
+  a.n_mod = n_mod; a.rows_per_sample = rows_per_sample; a.B = B; a.D = D; a.dmod = dmod; a.dmod_stride = dmod_stride; a.csilu = csilu;
+  a.dW = dW; a.db = db; a.n_bias = n_bias; a.scaler = scaler_dev; a.accumulate = accumulate;
+  return launch_stage_finalize(a, (hipStream_t)stream);
+}
+
+int latte_debug_adaln_dc(const float* dmod, int nmod, int B, const float* w_blocks, int64_t blk_stride, int depth, int rows6,
+                         const float* w_final, int D, float* ws, int64_t ws_floats, float* dc, void* stream) {
+  if (!dmod || !w_blocks || !w_final || !ws || !dc || B < 1 || D < 1 || depth < 0 || rows6 < 1 || nmod < 1 ||
+      (int64_t)depth * rows6 > nmod || blk_stride < (int64_t)rows6 * D)
+    return fail(LATTE_ERR_INVALID, "adaln_dc: need depth * rows6 <= nmod and blk_stride >= rows6 * D");
+  if ((int64_t)adaln_dc_splits(nmod) * B * D > ws_floats) return fail(LATTE_ERR_INVALID, "adaln_dc: workspace too small");
+  return launch_adaln_dc(dmod, nmod, B, w_blocks, (long)blk_stride, depth, rows6, w_final, D, ws, dc, (hipStream_t)stream);
+}
+
+int latte_debug_narrow_outer(const float* nar, int P, const void* wide, int wide_half, int D, int M, float* dW, int64_t so_p, int64_t so_k,
+                             float* nsum_out, float* wsum_out, float* ws, int64_t ws_floats, int dtype, const float* inv_scale_dev,
+                             int accumulate, void* stream) {
+  if (!nar || !wide || !dW || !ws || M < 1 || P < 1 || D < 1 || bad_mode(accumulate) ||
+      !((so_p == D && so_k == 1) || (so_p == 1 && so_k == P)))
+    return fail(LATTE_ERR_INVALID, "narrow_outer: bad arguments (output layouts: (so_p, so_k) = (D, 1) or (1, P))");
+  if ((int64_t)narrow_blocks(M) * ((int64_t)P * D + P + D) > ws_floats) return fail(LATTE_ERR_INVALID, "narrow_outer: workspace too small");
+  return launch_narrow_outer(nar, P, wide, wide_half, D, M, dW, (long)so_p, (long)so_k, nsum_out, wsum_out, ws, dtype, inv_scale_dev,
+                             (hipStream_t)stream, accumulate);
+}
+
+int latte_debug_narrow_dx(const float* nar, int P, const float* W, int D, int M, void* out, int dtype, void* stream) {
+  if (!nar || !W || !out || M < 1) return fail(LATTE_ERR_INVALID, "narrow_dx: bad arguments");
+  return launch_narrow_dx(nar, P, W, D, M, (half_t*)out, dtype, (hipStream_t)stream);
+}
+
+int latte_debug_pack_weights(const float* const* w_ptrs, const int* N, const int* K, void* const* wn_ptrs, void* const* wt_ptrs, int blocks,
+                             int dtype, void* stream) {
+  if (!w_ptrs || !N || !K || !wn_ptrs || !wt_ptrs || blocks < 1) return fail(LATTE_ERR_INVALID, "pack_weights: bad arguments");
+  PackPlan pl{};
+  int t0 = 0;
+  for (int j = 0; j < 4; ++j) {   // tiles of the four linears of one block, as latte_trainer_create lays them out
+    if (N[j] < 1 || K[j] < 1) return fail(LATTE_ERR_INVALID, "pack_weights: bad shape");
+    pl.tile0[j] = t0;
+    t0 += ((N[j] + 31) / 32) * ((K[j] + 31) / 32);
+  }
+  pl.tiles_per_block = t0;
+  std::vector<PackDesc> h((size_t)blocks * 4);
+  for (int i = 0; i < blocks * 4; ++i) {
+    if (!w_ptrs[i] || !wn_ptrs[i] || !wt_ptrs[i]) return fail(LATTE_ERR_INVALID, "pack_weights: null tensor");
+    h[i] = PackDesc{w_ptrs[i], (half_t*)wn_ptrs[i], (half_t*)wt_ptrs[i], N[i & 3], K[i & 3]};
+  }
+  hipStream_t st = (hipStream_t)stream;
+  PackDesc* descs = nullptr;
+  LATTE_HIP(hipMalloc((void**)&descs, h.size() * sizeof(PackDesc)));
+  int rc = LATTE_OK;
+  if (hipMemcpy(descs, h.data(), h.size() * sizeof(PackDesc), hipMemcpyHostToDevice) != hipSuccess)
+    rc = fail(LATTE_ERR_HIP, "pack_weights: table upload failed");
+  if (!rc) rc = launch_pack_weights(descs, blocks, pl, dtype, st);
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(descs);
+  return rc;
+}
+
+int latte_debug_pack_weight(const float* w, void* wn, void* wt, int N, int K, int dtype, void* stream) {
+  if (!w || N < 1 || K < 1) return fail(LATTE_ERR_INVALID, "pack_weight: bad arguments");
+  return launch_pack_weight(w, (half_t*)wn, (half_t*)wt, N, K, dtype, (hipStream_t)stream);
+}
+
 int latte_debug_loss_grad(const latte_schedule* s, int loss_type, const float* x_start, const float* x_t, const float* noise,
                           const float* model_out, const int64_t* t, int batch, int frames, int channels, int hw, float* dmodel_out,
                           void* stream) {

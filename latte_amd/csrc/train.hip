@@ -441,10 +441,10 @@ __global__ void split_reduce_kernel(const float* __restrict__ partial, int split
                                     int accumulate, const float* __restrict__ inv_scale) {
   const float f = inv_scale ? 1.0f / inv_scale[0] : 1.0f;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-    float a = (accumulate && !inv_scale) ? out[i] : 0.f;
+    float a = 0.f;   // the slabs are summed on their own in every mode: adding is the same sum with or without a loss scale
     for (int s = 0; s < splits; ++s) a += partial[(size_t)s * stride + i];
-    if (inv_scale) a = accumulate ? out[i] + a * f : a * f;
-    out[i] = a;
+    a *= f;
+    out[i] = accumulate ? out[i] + a : a;
   }
 }
 // the same sum in the same (slab) order on 16-byte accesses, four slabs in flight per step (n, stride multiples of 4, 16-byte
@@ -454,7 +454,7 @@ __global__ void __launch_bounds__(256) split_reduce4_kernel(const float4* __rest
                                                             const float* __restrict__ inv_scale) {
   const float f = inv_scale ? 1.0f / inv_scale[0] : 1.0f;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    float4 a = (accumulate && !inv_scale) ? out[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
     int s = 0;
     for (; s + 4 <= splits; s += 4) {
       const float4 p0 = partial[(size_t)s * stride4 + i], p1 = partial[(size_t)(s + 1) * stride4 + i];
@@ -466,12 +466,10 @@ __global__ void __launch_bounds__(256) split_reduce4_kernel(const float4* __rest
       const float4 p = partial[(size_t)s * stride4 + i];
       a.x += p.x; a.y += p.y; a.z += p.z; a.w += p.w;
     }
-    if (inv_scale) {   // the sum leaves the loss-scaled domain (power of two: exact)
-      a.x *= f; a.y *= f; a.z *= f; a.w *= f;
-      if (accumulate) {
-        const float4 o = out[i];
-        a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
-      }
+    a.x *= f; a.y *= f; a.z *= f; a.w *= f;   // the sum leaves the loss-scaled domain (power of two: exact; 1 without a scale)
+    if (accumulate) {
+      const float4 o = out[i];
+      a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
     }
     out[i] = a;
   }

@@ -17,6 +17,9 @@ from test_training_step import GTOL, rel      # the per-tensor relative-L2 bound
 # Accumulation adds fp32 micro-batch gradients in fp32: no operand is rounded that the single-batch step does not round, so the
 # bound of the single-batch gradients holds for the sum.
 TOL = GTOL["f16"]
+# The bf16 trainer runs without a loss scale: its second micro-batch takes the writers' add-without-unscale branch.  Same argument,
+# bf16's bound of the single-batch step.
+TOLS = {"f16": TOL, "bf16": GTOL["bf16"]}
 
 
 @functools.lru_cache(maxsize=None)
@@ -46,7 +49,7 @@ def micro(inputs, i, n=2):
     return tuple(None if v is None else v[i * n:(i + 1) * n] for v in inputs)
 
 
-def trainer(extras, accum=None, fuse_small=1, **kw):
+def trainer(extras, accum=None, fuse_small=1, dt="f16", **kw):
     import latte_amd
     mkw, _, sd, _, _, _ = case(extras)
     model = latte_amd.Latte(**mkw)
@@ -54,20 +57,20 @@ def trainer(extras, accum=None, fuse_small=1, **kw):
     if accum is not None:
         kw["gradient_accumulation_steps"] = accum
     kw.setdefault("start_clip_iter", 10 ** 9)
-    tr = latte_amd.LatteTrainer(model.to("cuda"), latte_amd.create_diffusion(""), max_batch=2, compute_dtype="f16", **kw)
+    tr = latte_amd.LatteTrainer(model.to("cuda"), latte_amd.create_diffusion(""), max_batch=2, compute_dtype=dt, **kw)
     if not fuse_small:
         tr.set_option("fuse_small", 0)
     return tr, model
 
 
 @functools.lru_cache(maxsize=None)
-def whole_batch(extras, fuse_small):
+def whole_batch(extras, fuse_small, dt="f16"):
     """The engine's own gradient of the batch of 4 in ONE assigning forward_backward (the path without accumulation), once per case."""
     import latte_amd
     kw, _, sd, (x0, noise, t, y, drop), _, _ = case(extras)
     model = latte_amd.Latte(**kw)
     model.load_state_dict(sd)
-    tr = latte_amd.LatteTrainer(model.to("cuda"), latte_amd.create_diffusion(""), max_batch=4, compute_dtype="f16", start_clip_iter=10 ** 9)
+    tr = latte_amd.LatteTrainer(model.to("cuda"), latte_amd.create_diffusion(""), max_batch=4, compute_dtype=dt, start_clip_iter=10 ** 9)
     tr.set_option("fuse_small", fuse_small)
     tr.forward_backward(x0, t, noise, y, drop)
     torch.cuda.synchronize()
@@ -86,7 +89,7 @@ def window(tr, inputs):
     return outs
 
 
-def check_against_oracle(tr, grads_ref, label):
+def check_against_oracle(tr, grads_ref, label, tol=TOL):
     got = {k: v.cpu() for k, v in tr.grad_dict().items()}
     assert set(got) == set(grads_ref)
     worst = {k: rel(got[k], grads_ref[k]) for k in grads_ref}
@@ -96,24 +99,26 @@ def check_against_oracle(tr, grads_ref, label):
               "t_embedder.mlp.0.weight", "t_embedder.mlp.2.bias"):
         assert k in worst, k                  # the writers most easily left in assign mode are among the compared tensors
         print("   ", k, worst[k])
-    bad = {k: round(v, 6) for k, v in worst.items() if not v < TOL}
+    bad = {k: round(v, 6) for k, v in worst.items() if not v < tol}
     assert not bad, bad
     return got
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("extras,fuse_small", [(2, 1), (2, 0), (1, 1), (1, 0)])
-def test_accumulated_gradients_match_the_oracle_on_the_whole_batch(extras, fuse_small):
+@pytest.mark.parametrize("extras,fuse_small,dt", [(e, f, dt) for dt in ("f16", "bf16") for e, f in ((2, 1), (2, 0), (1, 1), (1, 0))],
+                         ids=[f"{e}-{f}" + ("" if dt == "f16" else "-bf16") for dt in ("f16", "bf16") for e, f in ((2, 1), (2, 0), (1, 1), (1, 0))])
+def test_accumulated_gradients_match_the_oracle_on_the_whole_batch(extras, fuse_small, dt):
     _, _, _, inputs, terms, grads_ref = case(extras)
     sizes = sorted(g.numel() for g in grads_ref.values())
     assert sizes[0] < 4096 <= sizes[-1]                      # both reductions of the partial products write gradients here
-    tr, _ = trainer(extras, accum=2, fuse_small=fuse_small)
+    tr, _ = trainer(extras, accum=2, fuse_small=fuse_small, dt=dt)
+    assert (tr.scaler_state()["loss_scale"] > 1.0) == (dt == "f16")   # bf16: no loss scale, the writers add without unscaling
     outs = window(tr, inputs)
-    got = check_against_oracle(tr, grads_ref, f"extras {extras} fuse_small {fuse_small}")
+    got = check_against_oracle(tr, grads_ref, f"extras {extras} fuse_small {fuse_small} {dt}", TOLS[dt])
     # Against the engine's own whole-batch step the operand roundings are the same (every row is computed alike in a batch of 2 and
     # of 4, the loss weight 2 / (per * 2 * 2) is the whole batch's exactly); only the order of fp32 sums over the 256 rows differs:
     # sqrt(256) * 2^-24 = 1e-6 of the summed magnitudes, which exceed the result's norm by up to 1.6 x here -> 2e-6.
-    one = whole_batch(extras, fuse_small)
+    one = whole_batch(extras, fuse_small, dt)
     order = {k: rel(got[k], one[k]) for k in one}
     print("    against the single whole-batch step: worst", max(order, key=order.get), max(order.values()))
     assert max(order.values()) < 2e-6, {k: v for k, v in order.items() if not v < 2e-6}
@@ -129,17 +134,17 @@ def test_accumulated_gradients_match_the_oracle_on_the_whole_batch(extras, fuse_
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("fuse_small", [1, 0])
-def test_first_micro_batch_assigns_over_a_stale_buffer(fuse_small):
+@pytest.mark.parametrize("fuse_small,dt", [(1, "f16"), (0, "f16"), (1, "bf16"), (0, "bf16")], ids=["1", "0", "1-bf16", "0-bf16"])
+def test_first_micro_batch_assigns_over_a_stale_buffer(fuse_small, dt):
     """Micro-batch 1 of a window runs in assign mode: whatever the gradient buffer held does not leak into the window."""
     _, _, _, inputs, _, grads_ref = case(2)
-    clean, _ = trainer(2, accum=2, fuse_small=fuse_small)
+    clean, _ = trainer(2, accum=2, fuse_small=fuse_small, dt=dt)
     window(clean, inputs)
-    dirty, _ = trainer(2, accum=2, fuse_small=fuse_small)
+    dirty, _ = trainer(2, accum=2, fuse_small=fuse_small, dt=dt)
     for k, off, numel in dirty.layout:
         dirty.grads[off:off + numel].fill_(1.0e6)
     window(dirty, inputs)
-    check_against_oracle(dirty, grads_ref, f"stale buffer, fuse_small {fuse_small}")
+    check_against_oracle(dirty, grads_ref, f"stale buffer, fuse_small {fuse_small} {dt}", TOLS[dt])
     for k, off, numel in dirty.layout:
         assert torch.equal(dirty.grads[off:off + numel], clean.grads[off:off + numel]), k
 
