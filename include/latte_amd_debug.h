@@ -62,6 +62,43 @@ int latte_debug_qkv_attention_fusable(int D, int heads, int F, int T, int mode, 
 int latte_debug_gemm_tn_plan(int M, int N, int K, int* rows_per_split);
 int latte_debug_attention(const void* qkv, void* out, int num_seq, int L, int heads, int hd, int U,
                           int64_t sample_stride, int64_t seq_stride, int64_t row_stride, int dtype, void* stream);
+/* Text cross-attention of LatteT2V (attn2, latte_t2v.py:740-760; csrc/attention.hip: launch_cross_attention): queries from q viewed as
+ * [rows, q_ld] (column head * hd + d, q_ld >= D = heads * hd, q_ld % 8 == 0), keys / values of sample s = seq / U at rows [s Lk, (s + 1) Lk)
+ * of kv [num_samples Lk, 2 D] = [K | V], kbias_or_null: additive score bias fp32 [num_samples, Lk]; out [rows, D].  Sequences are addressed
+ * as in latte_debug_attention.  Lk <= 128 and L >= 128 run the whole-panel kernel, everything else (and everything under
+ * latte_debug_set_choice("xattn_flash", 1)) the CROSS form of the generic flash kernel. */
+int latte_debug_cross_attention(const void* q, int q_ld, const void* kv, const float* kbias_or_null, void* out, int num_seq, int L, int Lk,
+                                int heads, int hd, int U, int64_t sample_stride, int64_t seq_stride, int64_t row_stride, int dtype,
+                                void* stream);
+/* The denoiser's fp32 bookend kernels (csrc/pointwise.hip), one launch each exactly as the engines make it, behind the argument checks
+ * the launchers leave to their callers (refused with LATTE_ERR_INVALID):
+ *   small_linear        out[b out_stride + n] = bias[n] + sum_k f(b, k) W[n, k] (+ add_table[add_idx[b]][n] when add_table != NULL), in_mode
+ *                       0: f = in[b, k], 1: f = SiLU(in[b, k]), 2: f = the timestep sinusoid [cos | sin] of t[b] (int64; latte.py:97-117);
+ *                       K % 128 == 0, K <= 1152, out_stride >= N
+ *   patch_embed         out[tok, :] = Wt^T pixels(tok) + bias + pos[tok % T, :], x fp32 [BF, C, H, H], Wt [C p p, D], T = (H / p)^2 tokens
+ *                       per frame; D % 128 == 0, H % p == 0, 16 C p p floats of dynamic LDS within the 64 KiB default
+ *   final_layer         out [M / T, Cout, H, H] = unpatchify(LN(x[m, :]) (1 + scale[s]) + shift[s]) Wt + bias), s = m / rows_per_sample, shift /
+ *                       scale rows mod_stride floats apart, Wt [D, p p Cout]; D in 128 * {1, 2, 3, 4, 6, 8, 9}, H % p == 0, T == (H / p)^2,
+ *                       M % T == 0, rows_per_sample > 0, mod_stride even
+ *   text_proj           out[b, n] = bias[n] + sum_k SiLU(text[b, k]) W[n, k]; K % 128 == 0
+ *   gated_split_reduce  x[m, n] += gate[(m / rows_per_sample) gate_stride + n] ((sum_s ws[s stride + m N + n]) + bias[n]), slabs added in
+ *                       order; N % 4 == 0, stride >= M N, stride % 4 == 0
+ *   adaln_single        mod[b][j][:] = tables[j][:] + t6[b][(j % 6)][:] for j < 6 nblk, then the two head rows head_table[r][:] + temb[b][:]
+ *   cond_rows           out[(i, b), :] = SiLU(temb[i, :] (+ ytab[y[b], :] when ytab != NULL)), i < n_steps, b < bu
+ *   mask_bias           bias[i] = (1 - mask[i]) * -10000 */
+int latte_debug_small_linear(int in_mode, const float* in, const int64_t* t, const float* W, const float* bias, const float* add_table,
+                             const int64_t* add_idx, float* out, int B, int N, int K, int out_stride, void* stream);
+int latte_debug_patch_embed(const float* x, const float* Wt, const float* bias, const float* pos, float* out, int BF, int C, int H, int p,
+                            int D, void* stream);
+int latte_debug_final_layer(const float* x, const float* shift, const float* scale, int mod_stride, const float* Wt, const float* bias,
+                            float* out, int M, int D, int rows_per_sample, int T, int p, int Cout, int H, void* stream);
+int latte_debug_text_proj(const float* text, const float* W, const float* bias, float* out, int B, int N, int K, void* stream);
+int latte_debug_gated_split_reduce(float* x, const float* ws, int splits, int64_t stride, const float* bias, const float* gate,
+                                   int gate_stride, int rows_per_sample, int M, int N, void* stream);
+int latte_debug_adaln_single(const float* tables, const float* head_table, const float* t6, const float* temb, float* mod, int B, int nblk,
+                             int D, void* stream);
+int latte_debug_cond_rows(const float* temb, const float* ytab, const int64_t* y, float* out, int n_steps, int bu, int D, void* stream);
+int latte_debug_mask_bias(const float* mask, float* bias, int64_t n, void* stream);
 /* latte_debug_attention with the f16 + fp8-remainder output of guided calls: out [rows, D] (bit for bit the plain call's output) and
  * out8 [rows, D] bytes = e4m3(clamp((value - out) * 2^12, +-448)); f16 only, every kernel of the un-fused path (L <= 16, generic flash,
  * 128 < L <= 256, L > 256). */

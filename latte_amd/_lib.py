@@ -163,6 +163,18 @@ PROTOTYPES = {
     "latte_debug_gemm_tn_plan": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int)]),
     "latte_debug_attention": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_int,
                                       c_void]),
+    "latte_debug_cross_attention": (c_int, [c_void, c_int, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64,
+                                            c_i64, c_int, c_void]),
+    "latte_debug_small_linear": (c_int, [c_int, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int,
+                                         c_void]),
+    "latte_debug_patch_embed": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_void]),
+    "latte_debug_final_layer": (c_int, [c_void, c_void, c_void, c_int, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_int, c_void]),
+    "latte_debug_text_proj": (c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_void]),
+    "latte_debug_gated_split_reduce": (c_int, [c_void, c_void, c_int, c_i64, c_void, c_void, c_int, c_int, c_int, c_int, c_void]),
+    "latte_debug_adaln_single": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_void]),
+    "latte_debug_cond_rows": (c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_void]),
+    "latte_debug_mask_bias": (c_int, [c_void, c_void, c_i64, c_void]),
     "latte_debug_qkv_attention": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                           c_int, c_void]),
     "latte_debug_qkv_attention_trace": (c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int,

@@ -243,6 +243,80 @@ int latte_debug_attention_split8(const void* qkv, void* out, void* out8, int num
   return launch_attention(a, dtype, (hipStream_t)stream);
 }
 
+// ---- text cross-attention and the denoiser's fp32 bookend kernels: argument checks + the engines' own launchers, unchanged
+int latte_debug_cross_attention(const void* q, int q_ld, const void* kv, const float* kbias_or_null, void* out, int num_seq, int L, int Lk,
+                                int heads, int hd, int U, int64_t sample_stride, int64_t seq_stride, int64_t row_stride, int dtype,
+                                void* stream) {
+  if (!q || !kv || !out || num_seq < 1 || L < 1 || Lk < 1 || heads < 1 || U < 1 || sample_stride < 0 || seq_stride < 0 || row_stride < 1)
+    return fail(LATTE_ERR_INVALID, "cross_attention: bad arguments");
+  if (hd != 64 && hd != 72) return fail(LATTE_ERR_INVALID, "cross_attention: head_dim must be 64 or 72");
+  if (q_ld < heads * hd || q_ld % 8) return fail(LATTE_ERR_INVALID, "cross_attention: need q_ld >= heads * hd and q_ld % 8 == 0");
+  AttnArgs a{};
+  a.qkv = (const half_t*)q; a.out = (half_t*)out; a.num_seq = num_seq; a.L = L; a.heads = heads; a.hd = hd; a.D = heads * hd; a.U = U;
+  a.sample_stride = sample_stride; a.seq_stride = seq_stride; a.row_stride = row_stride; a.scale = 1.0f / sqrtf((float)hd);
+  a.kv = (const half_t*)kv; a.kbias = kbias_or_null; a.Lk = Lk; a.q_ld = q_ld;
+  return launch_cross_attention(a, dtype, (hipStream_t)stream);
+}
+
+int latte_debug_small_linear(int in_mode, const float* in, const int64_t* t, const float* W, const float* bias, const float* add_table,
+                             const int64_t* add_idx, float* out, int B, int N, int K, int out_stride, void* stream) {
+  if (!W || !bias || !out || B < 1 || N < 1 || K < 1 || out_stride < N || (in_mode == IN_TFREQ ? !t : !in) || (add_table && !add_idx))
+    return fail(LATTE_ERR_INVALID, "small_linear: bad arguments (out_stride >= N, t in mode 2, in otherwise, add_idx with add_table)");
+  return launch_small_linear(in_mode, in, t, W, bias, add_table, add_idx, out, B, N, K, out_stride, (hipStream_t)stream);
+}
+
+int latte_debug_patch_embed(const float* x, const float* Wt, const float* bias, const float* pos, float* out, int BF, int C, int H, int p,
+                            int D, void* stream) {
+  if (!x || !Wt || !bias || !pos || !out || BF < 1 || C < 1 || H < 1 || p < 1 || D < 1)
+    return fail(LATTE_ERR_INVALID, "patch_embed: bad arguments");
+  if (D % 128) return fail(LATTE_ERR_INVALID, "patch_embed: D must be a multiple of 128");
+  if (H % p) return fail(LATTE_ERR_INVALID, "patch_embed: H must be a multiple of the patch size");
+  if ((int64_t)16 * C * p * p * (int64_t)sizeof(float) > 65536)
+    return fail(LATTE_ERR_INVALID, "patch_embed: 16 tokens x C p p floats exceed the default dynamic LDS limit (64 KiB)");
+  return launch_patch_embed(x, Wt, bias, pos, out, BF, C, H, p, D, (hipStream_t)stream);
+}
+
+int latte_debug_final_layer(const float* x, const float* shift, const float* scale, int mod_stride, const float* Wt, const float* bias,
+                            float* out, int M, int D, int rows_per_sample, int T, int p, int Cout, int H, void* stream) {
+  if (!x || !shift || !scale || !Wt || !bias || !out || M < 1 || D < 1 || T < 1 || p < 1 || Cout < 1 || H < 1 || mod_stride < 0)
+    return fail(LATTE_ERR_INVALID, "final_layer: bad arguments");
+  if (D % 128) return fail(LATTE_ERR_INVALID, "final_layer: D must be a multiple of 128");
+  if (H % p) return fail(LATTE_ERR_INVALID, "final_layer: H must be a multiple of the patch size");
+  if (rows_per_sample <= 0) return fail(LATTE_ERR_INVALID, "final_layer: rows_per_sample must be positive");
+  if (T != (H / p) * (H / p) || M % T || mod_stride % 2)
+    return fail(LATTE_ERR_INVALID, "final_layer: need T == (H / p)^2, whole frames (M % T == 0) and an even mod_stride");
+  return launch_final_layer(x, shift, scale, mod_stride, Wt, bias, out, M, D, rows_per_sample, T, p, Cout, H, (hipStream_t)stream);
+}
+
+int latte_debug_text_proj(const float* text, const float* W, const float* bias, float* out, int B, int N, int K, void* stream) {
+  if (!text || !W || !bias || !out || B < 1 || N < 1 || K < 1) return fail(LATTE_ERR_INVALID, "text_proj: bad arguments");
+  return launch_text_proj(text, W, bias, out, B, N, K, (hipStream_t)stream);
+}
+
+int latte_debug_gated_split_reduce(float* x, const float* ws, int splits, int64_t stride, const float* bias, const float* gate,
+                                   int gate_stride, int rows_per_sample, int M, int N, void* stream) {
+  if (!x || !ws || !bias || !gate || M < 1 || N < 1 || rows_per_sample <= 0 || gate_stride < 0 || gate_stride % 4 || stride % 4 ||
+      stride < (int64_t)M * N)
+    return fail(LATTE_ERR_INVALID, "gated_split_reduce: need rows_per_sample > 0, stride >= M * N, stride and gate_stride multiples of 4");
+  return launch_gated_split_reduce(x, ws, splits, (size_t)stride, bias, gate, gate_stride, rows_per_sample, M, N, (hipStream_t)stream);
+}
+
+int latte_debug_adaln_single(const float* tables, const float* head_table, const float* t6, const float* temb, float* mod, int B, int nblk,
+                             int D, void* stream) {
+  if (!tables || !head_table || !t6 || !temb || !mod || B < 1 || nblk < 1 || D < 1) return fail(LATTE_ERR_INVALID, "adaln_single: bad arguments");
+  return launch_adaln_single(tables, head_table, t6, temb, mod, B, nblk, D, (hipStream_t)stream);
+}
+
+int latte_debug_cond_rows(const float* temb, const float* ytab, const int64_t* y, float* out, int n_steps, int bu, int D, void* stream) {
+  if (!temb || !out || n_steps < 1 || bu < 1 || D < 1 || (ytab && !y)) return fail(LATTE_ERR_INVALID, "cond_rows: bad arguments");
+  return launch_cond_rows(temb, ytab, y, out, n_steps, bu, D, (hipStream_t)stream);
+}
+
+int latte_debug_mask_bias(const float* mask, float* bias, int64_t n, void* stream) {
+  if (!mask || !bias || n < 1) return fail(LATTE_ERR_INVALID, "mask_bias: bad arguments");
+  return launch_mask_bias(mask, bias, (size_t)n, (hipStream_t)stream);
+}
+
 int latte_debug_qkv_attention(const void* xn, const void* w, const float* bias, void* out, void* dbg_qkv, int B, int F, int T, int D,
                               int heads, int mode, int flags, int dtype, void* stream) {
   return latte_debug_qkv_attention_trace(xn, w, bias, out, dbg_qkv, nullptr, B, F, T, D, heads, mode, flags, dtype, stream);
