@@ -185,6 +185,47 @@ int latte_debug_naive_gemm(const float* A, int64_t sam, int64_t sak, const float
                            const float* inv_scale_dev, void* stream);
 int latte_debug_embedding_bwd(const float* dc, const int64_t* idx, float* dtable, int B, int D, const float* inv_scale_dev, void* stream);
 int latte_debug_silu_bwd(const float* dout, const float* pre, float* din, int64_t n, int accumulate, void* stream);
+/* The optimiser step (csrc/train.hip), the two launches latte_trainer_optimizer_step makes, each alone:
+ *   grad_norm   stats[0] = sqrt(sum g[i]^2) (fp64 sum; partial: double [latte_debug_sumsq_blocks()] scratch), stats[1] = the coefficient
+ *               AdamW multiplies every gradient with: clip ? min(max_norm / (norm + 1e-6), 1) : 1, and 0 with stats[2] = 1 when the norm is
+ *               not finite (the update is skipped); stats: float [4].  scaler_or_null: the trainer's eight floats {loss scale, applied
+ *               steps since it changed, applied updates, skipped updates, this call skipped, dynamic on / off, growth interval, largest
+ *               scale}, advanced by the call as described above gradnorm_finalize_kernel
+ *   adamw_ema   torch.optim.AdamW's single-tensor update of p with g * stats[1] (weight decay p *= 1 - lr wd first), then ema = ema decay +
+ *               p (1 - decay) (ema_or_null == NULL: none), then g = 0; stats_or_null[2] != 0: p, m, v, ema untouched, g zeroed.  step >= 1:
+ *               the bias corrections' step; step == 0: it is read from step_dev_or_null[0] (a device float, the trainer's count of applied
+ *               updates) -- refused when that is NULL, as is step < 0.  16-byte accesses when all five buffers are 16-byte aligned. */
+int latte_debug_sumsq_blocks(void);
+int latte_debug_grad_norm(const float* g, int64_t n, double* partial, float max_norm, int clip, float* stats, float* scaler_or_null,
+                          void* stream);
+int latte_debug_adamw_ema(float* p, float* g, float* m, float* v, float* ema_or_null, int64_t n, float lr, float b1, float b2, float eps,
+                          float wd, int step, float ema_decay, const float* stats_or_null, const float* step_dev_or_null, void* stream);
+/* The trainer's layout and pointwise helpers (csrc/train.hip, csrc/pointwise.hip), one launch each as the trainer makes it; n >= 1:
+ *   gated_add       x_out[m, :] = x_in[m, :] + gate[(m / rows_per_sample) gate_stride + :] * y[m, :] (y half [M, D]; latte.py:179-180);
+ *                   D % 4 == 0, gate_stride % 4 == 0, gate_stride >= D, x_in / x_out / gate 16-byte aligned
+ *   gelu            bwd 0: out = gelu_tanh(u) (dh_or_null unused); bwd 1: out = dh * gelu_tanh'(u), out may be dh (latte.py:170 and its
+ *                   autograd; the un-fused form, trainer option fuse_gelu 0); half buffers of n elements, n % 4 == 0
+ *   tfreq           out[b, :] = [cos(t[b] f_i) | sin(t[b] f_i)], f_i = exp(-ln(10000) i / 128), i < 128 (latte.py:97-117; t int64 [B])
+ *   gather_i64      out[i] = table[idx[i]] (the spaced schedule's timestep map)
+ *   unpatchify_bwd  dtok[(bf G + gh) G + gw][(i p + j) Cout + c] = dout[bf][c][gh p + i][gw p + j] (inverse of latte.py:297-310)
+ *   im2col_patch    pix[(bf G + gh) G + gw][(c p + i) p + j] = x[bf][c][gh p + i][gw p + j] (the Conv2d(k = s = p) patch of a token)
+ *   add_rows        dst[i] += src[i]
+ *   scale_f32_dev   p[i] *= s_dev[0] (inverse 0) or p[i] *= 1 / s_dev[0] (inverse 1), s_dev a device float holding a power of two
+ *   silu_rows       out[i] = SiLU(in[i]), out may be in
+ *   transpose_f32   out[c rows + r] = in[r cols + c], not in place
+ *   widen           out[i] = fp32(in[i]) of a half buffer */
+int latte_debug_gated_add(const float* x_in, const void* y, const float* gate, int gate_stride, float* x_out, int M, int D,
+                          int rows_per_sample, int dtype, void* stream);
+int latte_debug_gelu(const void* u, const void* dh_or_null, void* out, int64_t n, int bwd, int dtype, void* stream);
+int latte_debug_tfreq(const int64_t* t, float* out, int B, void* stream);
+int latte_debug_gather_i64(const int64_t* table, const int64_t* idx, int64_t* out, int n, void* stream);
+int latte_debug_unpatchify_bwd(const float* dout, float* dtok, int BF, int G, int p, int Cout, void* stream);
+int latte_debug_im2col_patch(const float* x, float* pix, int BF, int G, int p, int C, void* stream);
+int latte_debug_add_rows(float* dst, const float* src, int64_t n, void* stream);
+int latte_debug_scale_f32_dev(float* p, const float* s_dev, int inverse, int64_t n, void* stream);
+int latte_debug_silu_rows(const float* in, float* out, int64_t n, void* stream);
+int latte_debug_transpose_f32(const float* in, float* out, int rows, int cols, void* stream);
+int latte_debug_widen(const void* in, float* out, int64_t n, int dtype, void* stream);
 /* The fused finalize launch of one block stage (csrc/train_fin.hip, StageFinArgs of csrc/common.h passed flat; the pointer and int
  * arrays are HOST arrays of n_mod (<= 6) and n_bias (<= 4) entries):  per modulation chunk c, mod_src[c] holds row-run partials
  * [B rows_per_sample][mod_nsum[c]][D] of which row mod_which[c] is summed per sample -> dmod[b][c D + col] (assigned, stays in the

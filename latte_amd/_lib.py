@@ -199,6 +199,21 @@ PROTOTYPES = {
                                        c_int, c_int, c_void, c_i64, c_void, c_void]),
     "latte_debug_embedding_bwd": (c_int, [c_void, c_void, c_void, c_int, c_int, c_void, c_void]),
     "latte_debug_silu_bwd": (c_int, [c_void, c_void, c_void, c_i64, c_int, c_void]),
+    "latte_debug_sumsq_blocks": (c_int, []),
+    "latte_debug_grad_norm": (c_int, [c_void, c_i64, c_void, c_f32, c_int, c_void, c_void, c_void]),
+    "latte_debug_adamw_ema": (c_int, [c_void, c_void, c_void, c_void, c_void, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_int, c_f32,
+                                      c_void, c_void, c_void]),
+    "latte_debug_gated_add": (c_int, [c_void, c_void, c_void, c_int, c_void, c_int, c_int, c_int, c_int, c_void]),
+    "latte_debug_gelu": (c_int, [c_void, c_void, c_void, c_i64, c_int, c_int, c_void]),
+    "latte_debug_tfreq": (c_int, [c_void, c_void, c_int, c_void]),
+    "latte_debug_gather_i64": (c_int, [c_void, c_void, c_void, c_int, c_void]),
+    "latte_debug_unpatchify_bwd": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_void]),
+    "latte_debug_im2col_patch": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_void]),
+    "latte_debug_add_rows": (c_int, [c_void, c_void, c_i64, c_void]),
+    "latte_debug_scale_f32_dev": (c_int, [c_void, c_void, c_int, c_i64, c_void]),
+    "latte_debug_silu_rows": (c_int, [c_void, c_void, c_i64, c_void]),
+    "latte_debug_transpose_f32": (c_int, [c_void, c_void, c_int, c_int, c_void]),
+    "latte_debug_widen": (c_int, [c_void, c_void, c_i64, c_int, c_void]),
     "latte_debug_stage_finalize": (c_int, [c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void, c_int, c_void, c_void, c_void,
                                            c_int, c_void, c_void, c_void, c_void, c_void, c_void, c_int, c_void]),
     "latte_debug_adaln_dc": (c_int, [c_void, c_int, c_int, c_void, c_i64, c_int, c_int, c_void, c_int, c_void, c_i64, c_void, c_void]),

@@ -450,6 +450,92 @@ int latte_debug_silu_bwd(const float* dout, const float* pre, float* din, int64_
   return launch_silu_bwd(dout, pre, din, (size_t)n, accumulate, (hipStream_t)stream);
 }
 
+// ---- the optimiser step and the trainer's layout / pointwise helpers
+static bool misaligned(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) != 0; }
+static bool bad_dtype(int dtype) { return dtype != LATTE_DTYPE_BF16 && dtype != LATTE_DTYPE_F16; }
+
+int latte_debug_sumsq_blocks(void) { return sumsq_blocks(); }
+
+int latte_debug_grad_norm(const float* g, int64_t n, double* partial, float max_norm, int clip, float* stats, float* scaler_or_null,
+                          void* stream) {
+  if (!g || !partial || !stats || n < 1 || bad_mode(clip) || misaligned(g, 4) || misaligned(partial, 8))
+    return fail(LATTE_ERR_INVALID, "grad_norm: bad arguments");
+  return launch_grad_norm(g, (size_t)n, partial, max_norm, clip, stats, scaler_or_null, (hipStream_t)stream);
+}
+
+int latte_debug_adamw_ema(float* p, float* g, float* m, float* v, float* ema_or_null, int64_t n, float lr, float b1, float b2, float eps,
+                          float wd, int step, float ema_decay, const float* stats_or_null, const float* step_dev_or_null, void* stream) {
+  if (!p || !g || !m || !v || n < 1) return fail(LATTE_ERR_INVALID, "adamw_ema: bad arguments");
+  if (step < 0 || (step == 0 && !step_dev_or_null))
+    return fail(LATTE_ERR_INVALID, "adamw_ema: step counts from 1 (0: the device-side count, which must then be given)");
+  return launch_adamw_ema(p, g, m, v, ema_or_null, (size_t)n, lr, b1, b2, eps, wd, step, ema_decay, stats_or_null, step_dev_or_null,
+                          (hipStream_t)stream);
+}
+
+int latte_debug_gated_add(const float* x_in, const void* y, const float* gate, int gate_stride, float* x_out, int M, int D,
+                          int rows_per_sample, int dtype, void* stream) {
+  if (!x_in || !y || !gate || !x_out || M < 1 || D < 1 || rows_per_sample < 1 || gate_stride < D || gate_stride % 4 || misaligned(x_in, 16) ||
+      misaligned(x_out, 16) || misaligned(gate, 16) || misaligned(y, 8))
+    return fail(LATTE_ERR_INVALID, "gated_add: bad arguments (rows_per_sample > 0, gate_stride >= D and % 4 == 0, 16-byte aligned rows)");
+  return launch_gated_add(x_in, (const half_t*)y, gate, gate_stride, x_out, M, D, rows_per_sample, dtype, (hipStream_t)stream);
+}
+
+int latte_debug_gelu(const void* u, const void* dh_or_null, void* out, int64_t n, int bwd, int dtype, void* stream) {
+  if (!u || !out || n < 1 || n % 4 || bad_mode(bwd) || (bwd && !dh_or_null) || misaligned(u, 8) || misaligned(out, 8) ||
+      misaligned(dh_or_null, 8))
+    return fail(LATTE_ERR_INVALID, "gelu: bad arguments (n % 4 == 0, dh in the backward form, 8-byte aligned buffers)");
+  if (bwd) return launch_gelu_bwd((const half_t*)u, (const half_t*)dh_or_null, (half_t*)out, (size_t)n, dtype, (hipStream_t)stream);
+  return launch_gelu_fwd((const half_t*)u, (half_t*)out, (size_t)n, dtype, (hipStream_t)stream);
+}
+
+int latte_debug_tfreq(const int64_t* t, float* out, int B, void* stream) {
+  if (!t || !out || B < 1) return fail(LATTE_ERR_INVALID, "tfreq: bad arguments");
+  return launch_tfreq(t, out, B, (hipStream_t)stream);
+}
+
+int latte_debug_gather_i64(const int64_t* table, const int64_t* idx, int64_t* out, int n, void* stream) {
+  if (!table || !idx || !out || n < 1) return fail(LATTE_ERR_INVALID, "gather_i64: bad arguments");
+  return launch_gather_i64(table, idx, out, n, (hipStream_t)stream);
+}
+
+static bool bad_patch_shape(int BF, int G, int p, int C) {
+  return BF < 1 || G < 1 || p < 1 || C < 1 || (int64_t)p * p * C > 0x7fffffff || (int64_t)G * p > 0x7fffffff;
+}
+int latte_debug_unpatchify_bwd(const float* dout, float* dtok, int BF, int G, int p, int Cout, void* stream) {
+  if (!dout || !dtok || bad_patch_shape(BF, G, p, Cout)) return fail(LATTE_ERR_INVALID, "unpatchify_bwd: bad arguments");
+  return launch_unpatchify_bwd(dout, dtok, BF, G, p, Cout, (hipStream_t)stream);
+}
+
+int latte_debug_im2col_patch(const float* x, float* pix, int BF, int G, int p, int C, void* stream) {
+  if (!x || !pix || bad_patch_shape(BF, G, p, C)) return fail(LATTE_ERR_INVALID, "im2col_patch: bad arguments");
+  return launch_im2col_patch(x, pix, BF, G, p, C, (hipStream_t)stream);
+}
+
+int latte_debug_add_rows(float* dst, const float* src, int64_t n, void* stream) {
+  if (!dst || !src || n < 1) return fail(LATTE_ERR_INVALID, "add_rows: bad arguments");
+  return launch_add_rows(dst, src, (size_t)n, (hipStream_t)stream);
+}
+
+int latte_debug_scale_f32_dev(float* p, const float* s_dev, int inverse, int64_t n, void* stream) {
+  if (!p || !s_dev || n < 1 || bad_mode(inverse)) return fail(LATTE_ERR_INVALID, "scale_f32_dev: bad arguments");
+  return launch_scale_f32_dev(p, s_dev, inverse, (size_t)n, (hipStream_t)stream);
+}
+
+int latte_debug_silu_rows(const float* in, float* out, int64_t n, void* stream) {
+  if (!in || !out || n < 1) return fail(LATTE_ERR_INVALID, "silu_rows: bad arguments");
+  return launch_silu_rows(in, out, (size_t)n, (hipStream_t)stream);
+}
+
+int latte_debug_transpose_f32(const float* in, float* out, int rows, int cols, void* stream) {
+  if (!in || !out || rows < 1 || cols < 1 || in == out) return fail(LATTE_ERR_INVALID, "transpose_f32: bad arguments (not in place)");
+  return launch_transpose_f32(in, out, rows, cols, (hipStream_t)stream);
+}
+
+int latte_debug_widen(const void* in, float* out, int64_t n, int dtype, void* stream) {
+  if (!in || !out || n < 1 || bad_dtype(dtype)) return fail(LATTE_ERR_INVALID, "widen: bad arguments");
+  return launch_convert_h16_to_f32((const half_t*)in, out, n, dtype, (hipStream_t)stream);
+}
+
 int latte_debug_stage_finalize(const float* const* mod_src, const int* mod_nsum, const int* mod_which, int n_mod, int rows_per_sample,
                                int B, int D, float* dmod, int dmod_stride, const float* csilu, float* dW, float* db, int n_bias,
                                const float* const* bias_src, const int* bias_rows, const int* bias_stride, const int* bias_cols,

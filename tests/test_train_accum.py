@@ -4,6 +4,7 @@ batch (the mean over 4 is half the sum of the two micro-batch means), at the tin
 tests/test_training_step.py.  Its tensors cover both reductions of the weight-gradient partials: x_embedder.proj.weight
 (128 x 16 = 2048 elements) and every bias take the scalar kernel, the block weights (>= 16384) the 16-byte one."""
 import functools
+import math
 
 import pytest
 import torch
@@ -210,3 +211,99 @@ def test_accumulated_update_matches_the_oracle():
         assert float((msd[k] - new_sd[k]).abs().max()) < 3e-7, k
         assert float((esd[k] - ema[k]).abs().max()) < 3e-7, k
     assert tr.micro_step == 0 and tr.train_steps == 1
+
+
+# ------------------------------------------------------------------------------------------------ the optimiser's trajectory
+TRAJ = dict(lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, wd=0.05, decay=0.9999)
+TRAJ_SCALES = (1.0, 0.7, 1.5, 1.2, 0.45, 2.0)       # gradient norm of each step in units of 2 x clip_max_norm: the fifth is not clipped
+TRAJ_INF_STEP = 2                                   # the third step's gradient holds one inf
+
+
+def follow_adamw(tr, seed=7):
+    """Six optimiser steps of `tr` (params / grads / exp_avg / exp_avg_sq / ema flat fp32 buffers, clip_max_norm, optimizer_step(),
+    scaler_state()) on injected gradients against torch.optim.AdamW + clip_grad_norm_ + update_ema on float64 CPU copies; see
+    test_six_optimiser_steps_follow_torch_adamw.  -> worst err / bound per buffer."""
+    import numpy as np
+    from test_optimizer_kernels import U32, adamw_ref, scaler_model
+    f32 = lambda x: float(np.float32(x))
+    h = {k: f32(v) for k, v in TRAJ.items()}
+    n = tr.params.numel()
+    gen = torch.Generator("cpu").manual_seed(seed)
+    base = 1e-3
+    tr.clip_max_norm = f32(0.5 * base * n ** 0.5)
+    p64 = torch.nn.Parameter(tr.params.detach().double().cpu().clone())
+    ema64 = tr.ema.detach().double().cpu().clone()
+    opt = torch.optim.AdamW([p64], lr=h["lr"], betas=(h["b1"], h["b2"]), eps=h["eps"], weight_decay=h["wd"])
+    zero = torch.zeros(n, dtype=torch.float64)
+    E = dict(p=zero.clone(), m=zero.clone(), v=zero.clone(), ema=zero.clone())
+    sc = list(tr.scaler_state().values())
+    applied, worst = 0, {}
+    for i, s in enumerate(TRAJ_SCALES):
+        g32 = torch.randn(n, generator=gen) * (base * s)
+        if i == TRAJ_INF_STEP:
+            g32[n // 3] = float("inf")
+        tr.grads.copy_(g32)
+        p64.grad = g32.double()
+        norm = float(torch.nn.utils.clip_grad_norm_([p64], tr.clip_max_norm))
+        ok = math.isfinite(norm)
+        if ok:
+            st = opt.state.get(p64, {})
+            m0, v0 = st.get("exp_avg", zero).clone(), st.get("exp_avg_sq", zero).clone()
+            p0, e0, gc = p64.detach().clone(), ema64.clone(), p64.grad.clone()
+            opt.step()
+            ema64.mul_(h["decay"]).add_(p64.detach(), alpha=1 - h["decay"])
+            applied += 1
+            # the step's own bounds at the reference state, then what the errors carried into it become (docstring)
+            _, L = adamw_ref(p0, gc, m0, v0, e0, h, applied, 1.0)
+            m1, v1 = opt.state[p64]["exp_avg"], opt.state[p64]["exp_avg_sq"]
+            bc1, bc2 = 1 - h["b1"] ** applied, 1 - h["b2"] ** applied
+            denom = v1.sqrt() / math.sqrt(bc2) + h["eps"]
+            upd = h["lr"] / bc1 * m1 / denom
+            cm = 4 * U32 * (1 - h["b1"]) * gc.abs()                # the clip coefficient's 4 roundings, through g'
+            cv = 8 * U32 * (1 - h["b2"]) * gc * gc
+            in_m, in_v = h["b1"] * E["m"] + cm, h["b2"] * E["v"] + cv
+            Ep = (1 - h["lr"] * h["wd"]) * E["p"] + L["p"] + h["lr"] / bc1 * in_m / denom + upd.abs() * in_v / (2 * v1)
+            E = dict(m=in_m + L["m"], v=in_v + L["v"], p=Ep, ema=h["decay"] * E["ema"] + L["ema"] + (1 - h["decay"]) * (Ep - L["p"]))
+        p64.grad = None
+        before = [t.clone() for t in (tr.params, tr.ema, tr.exp_avg, tr.exp_avg_sq)]
+        gn = tr.optimizer_step()
+        if not ok:
+            assert all(torch.equal(a, b) for a, b in zip(before, (tr.params, tr.ema, tr.exp_avg, tr.exp_avg_sq))), "the skipped step moved a buffer"
+        sc = scaler_model(sc, ok)
+        assert list(tr.scaler_state().values()) == sc, f"step {i + 1}: counters {tr.scaler_state()} against {sc}"
+        assert math.isfinite(float(gn)) == ok and float(tr.grads.abs().max()) == 0.0
+        if ok:
+            assert abs(float(gn) - norm) <= 2 * U32 * norm
+        st = opt.state.get(p64, {})
+        for k, got, want in (("p", tr.params, p64.detach()), ("ema", tr.ema, ema64), ("m", tr.exp_avg, st.get("exp_avg", zero)),
+                             ("v", tr.exp_avg_sq, st.get("exp_avg_sq", zero))):
+            err = (got.detach().double().cpu() - want).abs()
+            bad = ~(err <= E[k])
+            assert not bool(bad.any()), (f"step {i + 1} ({applied} applied): {k}: {int(bad.sum())} of {n} elements out of bound, worst err / bound "
+                                         f"{float((err / E[k].clamp_min(1e-300)).max()):.3g}")
+            if ok:
+                worst[k] = max(worst.get(k, 0.0), float((err / E[k]).max()))
+    assert applied == len(TRAJ_SCALES) - 1 and sc[2] == applied and sc[3] == 1.0
+    return worst
+
+
+@pytest.mark.gpu
+def test_six_optimiser_steps_follow_torch_adamw():
+    """weight_decay 0.05, clipping from the first step at half the norm of the first gradient; six steps on gradients written straight
+    into tr.grads (seeded, another draw and another norm per step -- the fifth stays below the clip norm), the third with one inf.  The
+    reference is torch.optim.AdamW ITSELF on a float64 CPU copy of the flat parameter buffer, fed by clip_grad_norm_, followed by
+    update_ema; its step() is not called at the skipped step, so its bias corrections count 5 -- an engine that counted the skipped
+    call would sit at 6 and miss the parameters by about 1 / 6 of a step's update from the fourth step on.  After EVERY step: params,
+    ema, exp_avg, exp_avg_sq within the accumulated bound, the eight scaler counters equal to the state machine's model.
+
+    Accumulation (first order).  L_x is the one-step bound of test_optimizer_kernels.adamw_ref at the reference's state, E_x the bound
+    carried into the step.  The engine's clip coefficient passes 4 fp32 roundings the reference does not (the norm to fp32, + 1e-6
+    and the constant itself, the divide): c_m = 4 u (1 - b1) |g'| on m', c_v = 8 u (1 - b2) g'^2 on v'.  Then
+        E_m' = b1 E_m + c_m + L_m                      E_v' = b2 E_v + c_v + L_v
+        E_p' = (1 - lr wd) E_p + L_p + (lr / bc1) (b1 E_m + c_m) / denom + |upd| (b2 E_v + c_v) / (2 v')
+        E_ema' = d E_ema + L_ema + (1 - d) (E_p' - L_p)
+    (d upd / d m' = (lr / bc1) / denom; |d upd / d v'| <= |upd| / (2 v'); L_ema already holds (1 - d) L_p).  A skipped step carries every
+    E over unchanged, and the buffers must not move at all."""
+    tr, model = trainer(2, weight_decay=TRAJ["wd"], start_clip_iter=0, lr=TRAJ["lr"], ema_decay=TRAJ["decay"])
+    worst = follow_adamw(tr)
+    print("optimiser trajectory: worst err / accumulated bound " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
