@@ -434,6 +434,20 @@ int latte_t2v_set_text(latte_t2v_t* e, const float* encoder_hidden_states, const
 int latte_t2v_guided_ddim_loop(latte_t2v_t* e, float* x, int samples, int n_steps, const int64_t* timesteps,
                                const double* alpha_t, const double* alpha_prev, float guidance_scale,
                                int enable_temporal_attentions, void* stream);
+/* The same guided loop for every sampler whose update is a linear combination of the latents, the newest guided model output, up to
+ * three remembered outputs and fresh noise (latte_amd/schedulers.py: Euler, Euler-ancestral, Heun, DPM-Solver++ multistep build the
+ * table with engine_plan()).  plan: HOST doubles [n_evals][LATTE_T2V_PLAN_COLS], one row per denoiser evaluation, narrowed to fp32 at
+ * launch like the DDIM loop's coefficients:
+ *   timestep (integral), in_scale, m_x, m_eps, c_x, c0, c1, c2, c3, c_noise, push (0 / 1), reserved (0)
+ * Per row: the transformer on in_scale * x at that timestep, eps = uncond + s (text - uncond) on the first C channels, then
+ *   m0 = m_x x + m_eps eps;   x = c_x x + c0 m0 + c1 h1 + c2 h2 + c3 h3 + c_noise noise[row];   push: (h1, h2, h3) <- (m0, h1, h2)
+ * noise: DEVICE [n_evals][samples * C * F * H * W] fp32 (only the rows with c_noise != 0 are read), or NULL when no row has one.
+ * Preconditions as latte_t2v_guided_ddim_loop; LATTE_ERR_INVALID also for a non-finite entry, a non-integral or negative timestep,
+ * c_noise != 0 without noise, and a c_j (j >= 1) that is non-zero before j rows with push have run.  Nothing is launched when a
+ * check fails. */
+#define LATTE_T2V_PLAN_COLS 12
+int latte_t2v_guided_linear_loop(latte_t2v_t* e, float* x, int samples, int n_evals, const double* plan, const float* noise,
+                                 float guidance_scale, int enable_temporal_attentions, void* stream);
 
 /* ------------------------------------------------------------------ T5 v1.1 text encoder
  * transformers.T5EncoderModel (feed_forward_proj "gated-gelu"): the text_encoder of Latte-1 text-to-video (T5-v1.1-XXL: d_model 4096,

@@ -99,6 +99,17 @@ int latte_debug_adaln_single(const float* tables, const float* head_table, const
                              int D, void* stream);
 int latte_debug_cond_rows(const float* temb, const float* ytab, const int64_t* y, float* out, int n_steps, int bu, int D, void* stream);
 int latte_debug_mask_bias(const float* mask, float* bias, int64_t n, void* stream);
+/* One launch of the guided linear sampler step (csrc/pointwise.hip: t2v_guided_linear_step_kernel) as latte_t2v_guided_linear_loop
+ * makes it: x [b, C, F, hw] in place, model_out the guidance pair's output in frame layout [(2 b) F, Cout, hw] ([negative | prompt],
+ * Cout >= C, only the first C channels are read),
+ *   eps = un + scale (tx - un);  m0 = m_x x + m_eps eps;  x' = c_x x + c0 m0 + c1 h1 + c2 h2 + c3 h3 + c_noise noise;
+ *   x = x';  x_in = in_scale_next x' unless x_in == x;  push != 0: hist_write = m0.
+ * h1 / h2 / h3 / noise may be NULL where their coefficient is 0 (refused otherwise), hist_write may be one of h1..h3 and is needed
+ * only with push.  hw % 4 == 0 and 16-byte aligned buffers take the 16-byte kernel, everything else the scalar one. */
+int latte_debug_t2v_linear_step(float* x, float* x_in, const float* model_out, const float* h1, const float* h2, const float* h3,
+                                const float* noise, float* hist_write, int b, int C, int Cout, int F, int hw, float scale, float m_x,
+                                float m_eps, float c_x, float c0, float c1, float c2, float c3, float c_noise, float in_scale_next,
+                                int push, void* stream);
 /* latte_debug_attention with the f16 + fp8-remainder output of guided calls: out [rows, D] (bit for bit the plain call's output) and
  * out8 [rows, D] bytes = e4m3(clamp((value - out) * 2^12, +-448)); f16 only, every kernel of the un-fused path (L <= 16, generic flash,
  * 128 < L <= 256, L > 256). */

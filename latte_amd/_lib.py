@@ -43,6 +43,7 @@ class VideoPlan(ctypes.Structure):
                                      "reg_y", "reg_x", "reg_h", "reg_w")] + [("scale_h", c_f32), ("scale_w", c_f32)]
 
 
+T2V_PLAN_COLS = 12   # LATTE_T2V_PLAN_COLS of include/latte_amd.h
 DTYPES = {"bf16": 0, "bfloat16": 0, "f16": 1, "fp16": 1, "float16": 1}
 
 # name -> (restype, argtypes); mirrors include/latte_amd.h and include/latte_amd_debug.h
@@ -111,6 +112,7 @@ PROTOTYPES = {
     "latte_t2v_forward": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_void, c_void]),
     "latte_t2v_set_text": (c_int, [c_void, c_void, c_void, c_int, c_int, c_void]),
     "latte_t2v_guided_ddim_loop": (c_int, [c_void, c_void, c_int, c_int, c_void, c_void, c_void, c_f32, c_int, c_void]),
+    "latte_t2v_guided_linear_loop": (c_int, [c_void, c_void, c_int, c_int, c_void, c_void, c_f32, c_int, c_void]),
     "latte_bench_gemm": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_f32), c_void]),
     "latte_vae_create": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_void)]),
     "latte_vae_create_temporal": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_void)]),
@@ -175,6 +177,7 @@ PROTOTYPES = {
     "latte_debug_adaln_single": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_void]),
     "latte_debug_cond_rows": (c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_void]),
     "latte_debug_mask_bias": (c_int, [c_void, c_void, c_i64, c_void]),
+    "latte_debug_t2v_linear_step": (c_int, [c_void] * 8 + [c_int] * 5 + [c_f32] * 10 + [c_int, c_void]),
     "latte_debug_qkv_attention": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                           c_int, c_void]),
     "latte_debug_qkv_attention_trace": (c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int,

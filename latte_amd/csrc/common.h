@@ -233,6 +233,19 @@ int launch_scale_f32_dev(float* p, const float* s_dev, int inverse, size_t n, hi
 // eps = u + s (c - u) on the first C channels (learned sigma dropped), x0 = (x - c1 eps) / c2, x' = c3 x0 + c4 eps.
 int launch_t2v_guided_ddim(float* x, const float* model_out, int b, int C, int Cout, int F, int hw, float scale, float c1, float c2,
                            float c3, float c4, hipStream_t st);
+// One guided step of ANY sampler whose update is linear in {latents, newest guided output, remembered outputs, fresh noise} (Euler,
+// Euler-ancestral, Heun, DPM-Solver++ multistep: latte_t2v_guided_linear_loop), on x [b, C, F, HW] in place; model_out as above:
+//   eps = u + s (c - u);  m0 = m_x x + m_eps eps;  x' = c_x x + c0 m0 + c1 h1 + c2 h2 + c3 h3 + c_noise noise
+//   x = x';  x_in = in_scale_next x' (the next denoiser call's input; nothing written when x_in == x);  push: hw = m0
+// A history / noise pointer whose coefficient is 0 is never dereferenced (may be NULL); hw may be one of h1..h3 (every thread reads
+// its elements before it writes them).  HW % 4 == 0 with 16-byte aligned buffers: 16-byte accesses, else the scalar kernel.
+struct T2VLinearStep {
+  float scale, m_x, m_eps, c_x, c0, c1, c2, c3, c_noise, in_scale_next;
+  int push;
+};
+int launch_t2v_guided_linear_step(float* x, float* x_in, const float* model_out, const float* h1, const float* h2, const float* h3,
+                                  const float* noise, float* hw, int b, int C, int Cout, int F, int HW, const T2VLinearStep& s,
+                                  hipStream_t st);
 int launch_mask_bias(const float* mask, float* bias, size_t n, hipStream_t st);   // bias = (1 - mask) * -10000
 int launch_cfg_combine(float* out, int half_batch, int F, int Cout, int HW, float cfg_scale, hipStream_t st);
 int launch_convert_f32_to_h16(const float* in, half_t* out, int64_t n, int dtype, hipStream_t st);

@@ -680,6 +680,63 @@ __global__ void t2v_guided_ddim_kernel(float* __restrict__ x, const float* __res
   }
 }
 
+// V consecutive floats of one (sample, channel, frame) row: one 16-byte access for V = 4
+template <int V>
+__device__ __forceinline__ void ld_row(float (&d)[V], const float* p) {
+  if constexpr (V == 4) {
+    const float4 v = *(const float4*)p;
+    d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+  } else {
+    d[0] = *p;
+  }
+}
+template <int V>
+__device__ __forceinline__ void st_row(float* p, const float (&d)[V]) {
+  if constexpr (V == 4) *(float4*)p = make_float4(d[0], d[1], d[2], d[3]);
+  else *p = d[0];
+}
+
+// The guided step of every linear sampler (common.h: T2VLinearStep), indexed exactly as t2v_guided_ddim_kernel; V = 4 needs hw % 4 == 0
+// (the four elements of a thread then lie in one row) and 16-byte aligned buffers.  x / x_in and the history pointers carry no
+// __restrict__: x_in may be x, hwr may be one of h1..h3 -- every thread reads its elements before it writes them.
+template <int V>
+__global__ void t2v_guided_linear_step_kernel(float* x, float* x_in, const float* __restrict__ mo, const float* h1, const float* h2,
+                                              const float* h3, const float* __restrict__ noise, float* hwr, int b, int C, int Cout, int F,
+                                              int hw, T2VLinearStep s) {
+#pragma clang fp contract(off)
+  const size_t total = (size_t)b * C * F * hw / V;
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (size_t)gridDim.x * blockDim.x) {
+    const size_t i = q * V;
+    const size_t r = i % hw, f = (i / hw) % F, c = (i / ((size_t)hw * F)) % C, bb = i / ((size_t)hw * F * C);
+    float un[V], tx[V], xv[V], a1[V], a2[V], a3[V], nz[V], m0[V], xn[V];
+    ld_row<V>(un, mo + (((bb * F + f) * Cout) + c) * hw + r);                // negative-prompt half
+    ld_row<V>(tx, mo + ((((bb + b) * F + f) * Cout) + c) * hw + r);          // prompt half
+    ld_row<V>(xv, x + i);
+    if (s.c1 != 0.0f) ld_row<V>(a1, h1 + i);
+    if (s.c2 != 0.0f) ld_row<V>(a2, h2 + i);
+    if (s.c3 != 0.0f) ld_row<V>(a3, h3 + i);
+    if (s.c_noise != 0.0f) ld_row<V>(nz, noise + i);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const float eps = un[j] + s.scale * (tx[j] - un[j]);                   // pipeline_latte.py:748-749
+      m0[j] = s.m_x * xv[j] + s.m_eps * eps;
+      float v = s.c_x * xv[j] + s.c0 * m0[j];
+      if (s.c1 != 0.0f) v = v + s.c1 * a1[j];
+      if (s.c2 != 0.0f) v = v + s.c2 * a2[j];
+      if (s.c3 != 0.0f) v = v + s.c3 * a3[j];
+      if (s.c_noise != 0.0f) v = v + s.c_noise * nz[j];
+      xn[j] = v;
+    }
+    st_row<V>(x + i, xn);
+    if (x_in != x) {
+#pragma unroll
+      for (int j = 0; j < V; ++j) xv[j] = s.in_scale_next * xn[j];
+      st_row<V>(x_in + i, xv);
+    }
+    if (s.push) st_row<V>(hwr + i, m0);
+  }
+}
+
 __global__ void training_combine_kernel(const float* __restrict__ mse, const float* __restrict__ vb, int has_vb, int kl_only,
                                         float vb_scale, int batch, float* mse_out, float* vb_out, float* loss_out) {
 #pragma clang fp contract(off)
@@ -855,6 +912,23 @@ int launch_t2v_guided_ddim(float* x, const float* model_out, int b, int C, int C
   const size_t total = (size_t)b * C * F * hw;
   hipLaunchKernelGGL(t2v_guided_ddim_kernel, dim3(grid_for(total, 256)), dim3(256), 0, st, x, model_out, b, C, Cout, F, hw, scale, c1,
                      c2, c3, c4);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+
+int launch_t2v_guided_linear_step(float* x, float* x_in, const float* model_out, const float* h1, const float* h2, const float* h3,
+                                  const float* noise, float* hw, int b, int C, int Cout, int F, int HW, const T2VLinearStep& s,
+                                  hipStream_t st) {
+  const size_t total = (size_t)b * C * F * HW;
+  auto aligned = [](const void* p) { return ((uintptr_t)p & 15) == 0; };   // a null (unused) pointer counts as aligned
+  const bool vec = HW % 4 == 0 && aligned(x) && aligned(x_in) && aligned(model_out) && aligned(h1) && aligned(h2) && aligned(h3) &&
+                   aligned(noise) && aligned(hw);
+  if (vec)
+    hipLaunchKernelGGL(t2v_guided_linear_step_kernel<4>, dim3(grid_for(total / 4, 256)), dim3(256), 0, st, x, x_in, model_out, h1, h2, h3,
+                       noise, hw, b, C, Cout, F, HW, s);
+  else
+    hipLaunchKernelGGL(t2v_guided_linear_step_kernel<1>, dim3(grid_for(total, 256)), dim3(256), 0, st, x, x_in, model_out, h1, h2, h3,
+                       noise, hw, b, C, Cout, F, HW, s);
   LATTE_HIP(hipGetLastError());
   return LATTE_OK;
 }

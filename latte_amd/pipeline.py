@@ -6,8 +6,9 @@ What runs where: the transformer call of every step (``latte_amd.LatteT2V``, the
 ``transformers`` T5 in the reference) or are bypassed with ``prompt_embeds`` / ``negative_prompt_embeds``; the scheduler is
 any object with the diffusers interface (``latte_amd.schedulers.DDIMScheduler`` is a self-contained stand-in).  With that
 scheduler at eta = 0 the whole guided loop (:700-760) runs inside the engine (``latte_t2v_guided_ddim_loop``: text context
-computed once, guidance combine + learned-sigma drop + DDIM update fused into one kernel per step); with any other
-scheduler object the guidance combine, the learned-sigma drop and the scheduler update are the reference's own few
+computed once, guidance combine + learned-sigma drop + DDIM update fused into one kernel per step), and so does the chain of a
+scheduler that exposes ``engine_plan()`` (Euler, Euler-ancestral, Heun, DPM-Solver++ of ``latte_amd.schedulers``:
+``latte_t2v_guided_linear_loop``); with any other scheduler object the guidance combine, the learned-sigma drop and the scheduler update are the reference's own few
 elementwise lines (:747-758) on device tensors around the engine denoiser.  ``enable_vae_temporal_decoder=True`` decodes through
 ``latte_amd.AutoencoderKLTemporalDecoder`` in chunks of 14 frames (:779-798), else per frame (:765-777).
 """
@@ -123,6 +124,17 @@ class LattePipeline:
         a_p = [float(sch.alphas_cumprod[t - ratio]) if t - ratio >= 0 else float(sch.final_alpha_cumprod) for t in ts]
         return ts, a_t, a_p
 
+    def _fused_plan(self, do_cfg, callback, latent_channels):
+        """The scheduler's ``engine_plan()`` table when the chain can run inside the engine as latte_t2v_guided_linear_loop: guidance
+        on, no per-step callback, the engine transformer, a scheduler that describes its update as such a table (Euler,
+        Euler-ancestral, Heun, DPM-Solver++ of latte_amd.schedulers).  Else None: the step-by-step loop."""
+        from .t2v import LatteT2V
+        sch, tr = self.scheduler, self.transformer
+        if not (do_cfg and callback is None and getattr(self, "allow_fused_loop", True) and isinstance(tr, LatteT2V)
+                and tr.config.out_channels in (latent_channels, 2 * latent_channels) and hasattr(sch, "engine_plan")):
+            return None
+        return sch.engine_plan()
+
     def prepare_latents(self, batch_size, num_channels_latents, video_length, height, width, device, generator, latents=None):
         shape = (batch_size, num_channels_latents, video_length, height // self.vae_scale_factor, width // self.vae_scale_factor)
         if latents is None:
@@ -205,6 +217,17 @@ class LattePipeline:
             self.transformer.set_text(prompt_embeds)
             latents = self.transformer.guided_ddim_loop(latents, fused[0], fused[1], fused[2], guidance_scale,
                                                         enable_temporal_attentions)
+            steps = []
+        plan = self._fused_plan(do_cfg, callback, latent_channels) if fused is None else None
+        if plan is not None:
+            # the same chain for every sampler with a linear update: one table, one engine call.  A stochastic sampler's noise is
+            # drawn up front by the calls its step() would make, in order, so both loops consume the generator alike
+            noise = None
+            from .schedulers import P_CN, draw_noise
+            if (plan[:, P_CN] != 0.0).any():
+                noise = torch.stack([draw_noise(latents.shape, generator, device, latents.dtype) for _ in range(plan.shape[0])])
+            self.transformer.set_text(prompt_embeds)
+            latents = self.transformer.guided_linear_loop(latents, plan, noise, guidance_scale, enable_temporal_attentions)
             steps = []
         for i, t in enumerate(steps):
             latent_model_input = torch.cat([latents] * 2) if do_cfg else latents

@@ -199,3 +199,25 @@ class LatteT2V:
                                                             ap.ctypes.data, float(guidance_scale),
                                                             int(bool(enable_temporal_attentions)), stream_ptr()))
         return x
+
+    def guided_linear_loop(self, latents, plan, noise, guidance_scale, enable_temporal_attentions=True):
+        """The classifier-free-guidance loop of any sampler with a linear update (``engine_plan()`` of latte_amd.schedulers: Euler,
+        Euler-ancestral, Heun, DPM-Solver++) inside the engine on ``latents`` [b, C, F, H, W]; ``set_text`` must hold the 2 b rows
+        [negative | prompt].  ``plan``: [n_evals, 12] float64 (host); ``noise``: [n_evals, b, C, F, H, W] or None."""
+        import numpy as np
+        dev = self._device
+        x = latents.to(device=dev, dtype=torch.float32).contiguous().clone()
+        plan = np.ascontiguousarray(np.asarray(plan, dtype=np.float64))
+        if plan.ndim != 2 or plan.shape[1] != _lib.T2V_PLAN_COLS or plan.shape[0] == 0:
+            raise LatteError(f"guided_linear_loop: plan must be [n_evals, {_lib.T2V_PLAN_COLS}]")
+        if noise is not None:
+            noise = noise.to(device=dev, dtype=torch.float32).contiguous()
+            if noise.numel() != plan.shape[0] * x.numel():
+                raise LatteError("guided_linear_loop: noise must hold one latent-shaped slab per evaluation")
+        if self._h is None:
+            raise LatteError("guided_linear_loop: call set_text first")
+        with torch.cuda.device(dev):
+            check(load_library().latte_t2v_guided_linear_loop(self._h, ptr(x), x.shape[0], plan.shape[0], plan.ctypes.data, ptr(noise),
+                                                              float(guidance_scale), int(bool(enable_temporal_attentions)),
+                                                              stream_ptr()))
+        return x

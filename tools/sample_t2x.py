@@ -1,6 +1,6 @@
 """sample/sample_t2x.py of the reference on the MI355X engine: Latte-1 text-to-video.
 
-  python tools/sample_t2x.py --config configs/t2v_sample.yaml [--random] [--steps N] [--layers L]
+  python tools/sample_t2x.py --config configs/t2v_sample.yaml [--random] [--steps N] [--layers L] [--sample-method NAME]
 
 With a real checkpoint directory (`pretrained_model_path` holding transformer/, vae/, tokenizer/, text_encoder/) the flow is
 the reference's (sample_t2x.py:21-140): the T5 tokenizer from `transformers`, the T5 encoder on the engine
@@ -8,8 +8,10 @@ the reference's (sample_t2x.py:21-140): the T5 tokenizer from `transformers`, th
 `LattePipeline(...)`, one video per prompt.  Offline there are no weights: `--random` builds randomly initialised models, the text
 encoder among them (`--t5-layers` of the XXL shape), and a deterministic stand-in tokenizer (`latte_amd.t5.HashTokenizer`), so the
 run goes prompt string -> ids -> T5 -> denoiser -> VAE -> mp4 on the device path and times it.  Videos are written as .mp4
-(Motion-JPEG samples, latte_amd.video_io).  Only the DDIM scheduler has a self-contained stand-in (latte_amd/schedulers.py); any diffusers
-scheduler object can be passed to LattePipeline instead.
+(Motion-JPEG samples, latte_amd.video_io).  `sample_method` picks one of the five self-contained schedulers of latte_amd/schedulers.py
+(DDIM, EulerDiscrete, EulerAncestralDiscrete, HeunDiscrete, DPMSolverMultistep), each of which runs its whole guided chain inside the
+engine; the reference's other five names are refused (INTEGRATION.md says why), and any diffusers scheduler object can be passed to
+LattePipeline instead.
 """
 import argparse
 import os
@@ -22,7 +24,29 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import latte_amd  # noqa: E402
-from latte_amd.schedulers import DDIMScheduler  # noqa: E402
+from latte_amd import schedulers  # noqa: E402
+
+# sample_t2x.py:43-114: sample_method -> scheduler class
+SAMPLE_METHODS = {
+    "DDIM": schedulers.DDIMScheduler,
+    "EulerDiscrete": schedulers.EulerDiscreteScheduler,
+    "EulerAncestralDiscrete": schedulers.EulerAncestralDiscreteScheduler,
+    "HeunDiscrete": schedulers.HeunDiscreteScheduler,
+    "DPMSolverMultistep": schedulers.DPMSolverMultistepScheduler,
+}
+REFUSED_METHODS = ("DDPM", "PNDM", "DPMSolverSinglestep", "DEISMultistep", "KDPM2AncestralDiscrete")
+
+
+def make_scheduler(args):
+    name = args.sample_method
+    if name not in SAMPLE_METHODS:
+        known = "one of the reference's methods without an offline stand-in" if name in REFUSED_METHODS else "not a sample_method"
+        raise SystemExit(f"sample_method {name!r} is {known}; the methods that run are {', '.join(SAMPLE_METHODS)} "
+                         "(or pass a diffusers scheduler object to LattePipeline)")
+    kw = dict(beta_start=args.beta_start, beta_end=args.beta_end, beta_schedule=args.beta_schedule)
+    if name == "DDIM":
+        kw["clip_sample"] = False
+    return SAMPLE_METHODS[name](**kw)
 
 
 def main():
@@ -31,18 +55,19 @@ def main():
     ap.add_argument("--random", action="store_true", help="random weights and a stand-in tokenizer (no checkpoints offline)")
     ap.add_argument("--t5-layers", type=int, default=24, help="--random: depth of the randomly initialised T5 encoder (XXL shape)")
     ap.add_argument("--steps", type=int, default=None)
+    ap.add_argument("--sample-method", default=None, help="overrides the config's sample_method: " + ", ".join(SAMPLE_METHODS))
     ap.add_argument("--layers", type=int, default=28)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     args = latte_amd.load_config(a.config)
+    if a.sample_method:
+        args.sample_method = a.sample_method
     torch.set_grad_enabled(False)
     assert torch.cuda.is_available(), "sample_t2x needs an MI355X"
     device = "cuda"
     cdt = "f16"                       # sample_t2x.py:29 .to(device, dtype=torch.float16): the only operand type of latte_amd.LatteT2V
     latent = args.image_size[0] // 8
-    if args.sample_method != "DDIM":
-        raise SystemExit("only the DDIM scheduler has an offline stand-in; pass a diffusers scheduler to LattePipeline otherwise")
-    scheduler = DDIMScheduler(beta_start=args.beta_start, beta_end=args.beta_end, beta_schedule=args.beta_schedule, clip_sample=False)
+    scheduler = make_scheduler(args)
     tokenizer = text_encoder = None
     if a.random:
         from latte_amd.random_init import t2v_state_dict, t5_state_dict, vae_decoder_state_dict
