@@ -260,6 +260,32 @@ int latte_trainer_begin(latte_trainer_t* e, const latte_schedule_t* s, int loss_
 int latte_trainer_num_stages(const latte_trainer_t* e);
 int latte_trainer_stage_range(const latte_trainer_t* e, int stage, int64_t* offset, int64_t* numel);
 int latte_trainer_backward_stage(latte_trainer_t* e, int stage, void* stream);
+/* Joint image-video training (train_with_img.py:214-241, models/latte_img.py:361-399, `use_image_num: N` of the *_img_train.yaml
+ * configs): every sample carries F video frames and N single image frames.  LatteIMG has exactly Latte's parameters, its image
+ * frames never meet the video frames (spatial blocks treat every frame alone, temporal blocks see x[:, :F]) and mean_flat runs over
+ * all F + N frames of a sample, whose t they share, so for loss, mse and vb
+ *     terms_b = (F terms_video_b + sum_n terms_image_{b,n}) / (F + N)
+ *     grad loss.mean() = F / (F + N) grad mean_b(loss_video_b) + N / (F + N) grad mean_{b,n}(loss_image_{b,n})
+ * and a joint micro-batch is the plain step on the video frames plus an IMAGE PASS: the same network on batch * N one-frame
+ * pseudo-samples (t_b, label y_image[b][n]) with the temporal blocks off -- only the even blocks and the final layer run, no
+ * temp_embed, the odd blocks' gradient slices are not touched -- whose gradient writers add to what the video pass wrote.
+ * latte_trainer_create_joint: a trainer whose per-sample buffers hold max_batch * max_image_num pseudo-samples; max_image_num = 0 is
+ * latte_trainer_create; max_image_num > num_frames (the image pass runs in the video pass's row buffers) and tokens per frame % 64
+ * != 0 are refused.  Through the plain entry points such a trainer computes what one of latte_trainer_create does, bit for bit.
+ * latte_trainer_begin_joint: x_start / noise / model_out_copy [batch, F + N, C(_out), H, W], y_image int64 [batch, N] after label
+ * dropout (ignored without a label table); runs the video pass completely (forward and every stage) in the current assign /
+ * accumulate mode with loss weight F / (F + N) (it multiplies into "loss_divisor"), then the image pass's forward in accumulate
+ * mode with weight N / (F + N), and writes the combined terms_out [3][batch] (undivided, as ever).  The image pass's stages are the
+ * caller's: latte_trainer_backward_stage(k), k = 0 .. num_stages - 1; after stage k the slice latte_trainer_stage_range(k) is
+ * final (the odd blocks' stages launch nothing).  `y` and `y_image` must stay alive until the last stage.
+ * latte_trainer_forward_backward_joint = latte_trainer_begin_joint + every stage. */
+int latte_trainer_create_joint(const latte_model_config_t* cfg, int max_batch, int max_image_num, latte_trainer_t** out);
+int latte_trainer_begin_joint(latte_trainer_t* e, const latte_schedule_t* s, int loss_type, const float* x_start, const float* noise,
+                              const int64_t* t, const int64_t* y, const int64_t* y_image, int batch, int use_image_num, float* terms_out,
+                              float* model_out_copy, void* stream);
+int latte_trainer_forward_backward_joint(latte_trainer_t* e, const latte_schedule_t* s, int loss_type, const float* x_start,
+                                         const float* noise, const int64_t* t, const int64_t* y, const int64_t* y_image, int batch,
+                                         int use_image_num, float* terms_out, float* model_out_copy, void* stream);
 /* clip_grad_norm_ (utils.py:72-117: total 2-norm, g *= min(max_norm / (norm + 1e-6), 1) when clip != 0) + AdamW + update_ema
  * (utils.py:191-200) on the bound buffers.  `step` = 0 (what LatteTrainer passes): AdamW's bias correction uses the trainer's own count
  * of APPLIED updates (what torch.optim.AdamW does: a fresh optimiser state starts at 1 even when the training-step counter continues

@@ -230,6 +230,14 @@ int latte_debug_gated_add(const float* x_in, const void* y, const float* gate, i
 int latte_debug_gelu(const void* u, const void* dh_or_null, void* out, int64_t n, int bwd, int dtype, void* stream);
 int latte_debug_tfreq(const int64_t* t, float* out, int B, void* stream);
 int latte_debug_gather_i64(const int64_t* table, const int64_t* idx, int64_t* out, int n, void* stream);
+/* joint image-video micro-batch (latte_trainer_begin_joint): x / noise [B, F + N, per] -> x_video / noise_video [B, F, per] and
+ * x_image / noise_image [B N, per], t_image[b N + n] = t[b] (exact copies);  terms_out[k][b] = (F terms_video[k][b] +
+ * sum_n terms_image[k][b N + n]) / (F + N) for k < 3 (summed in double, rounded once) and, when out_joint is not NULL, out_joint
+ * [B, F + N, per] gathered back from out_video [B, F, per] / out_image [B N, per] */
+int latte_debug_joint_split(const float* x, const float* noise, const int64_t* t, float* x_video, float* noise_video, float* x_image,
+                            float* noise_image, int64_t* t_image, int B, int F, int N, int64_t per, void* stream);
+int latte_debug_joint_merge(const float* terms_video, const float* terms_image, float* terms_out, const float* out_video, const float* out_image,
+                            float* out_joint, int B, int F, int N, int64_t per, void* stream);
 int latte_debug_unpatchify_bwd(const float* dout, float* dtok, int BF, int G, int p, int Cout, void* stream);
 int latte_debug_im2col_patch(const float* x, float* pix, int BF, int G, int p, int C, void* stream);
 int latte_debug_add_rows(float* dst, const float* src, int64_t n, void* stream);

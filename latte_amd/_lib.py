@@ -93,6 +93,10 @@ PROTOTYPES = {
     "latte_trainer_sync_weights": (c_int, [c_void, c_void]),
     "latte_trainer_forward_backward": (c_int, [c_void, c_void, c_int, c_void, c_void, c_void, c_void, c_int, c_void, c_void, c_void]),
     "latte_trainer_begin": (c_int, [c_void, c_void, c_int, c_void, c_void, c_void, c_void, c_int, c_void, c_void, c_void]),
+    "latte_trainer_create_joint": (c_int, [ctypes.POINTER(ModelConfig), c_int, c_int, ctypes.POINTER(c_void)]),
+    "latte_trainer_forward_backward_joint": (c_int, [c_void, c_void, c_int, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_void, c_void,
+                                                     c_void]),
+    "latte_trainer_begin_joint": (c_int, [c_void, c_void, c_int, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_void, c_void, c_void]),
     "latte_trainer_num_stages": (c_int, [c_void]),
     "latte_trainer_stage_range": (c_int, [c_void, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "latte_trainer_backward_stage": (c_int, [c_void, c_int, c_void]),
@@ -210,6 +214,8 @@ PROTOTYPES = {
     "latte_debug_gelu": (c_int, [c_void, c_void, c_void, c_i64, c_int, c_int, c_void]),
     "latte_debug_tfreq": (c_int, [c_void, c_void, c_int, c_void]),
     "latte_debug_gather_i64": (c_int, [c_void, c_void, c_void, c_int, c_void]),
+    "latte_debug_joint_split": (c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_i64, c_void]),
+    "latte_debug_joint_merge": (c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_i64, c_void]),
     "latte_debug_unpatchify_bwd": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_void]),
     "latte_debug_im2col_patch": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_void]),
     "latte_debug_add_rows": (c_int, [c_void, c_void, c_i64, c_void]),

@@ -358,6 +358,11 @@ int launch_naive_gemm(const float* A, long sam, long sak, const float* B, long s
                       const float* inv_scale_dev = nullptr);
 int launch_tfreq(const int64_t* t, float* out, int B, hipStream_t st);
 int launch_gather_i64(const int64_t* table, const int64_t* idx, int64_t* out, int n, hipStream_t st);
+// joint image-video micro-batch (train.hip): [B][F + N][per] <-> the video pass's [B][F][per] and the image pass's [B N][per]
+int launch_joint_split(const float* x, const float* nz, const int64_t* t, float* xv, float* nv, float* xi, float* ni, int64_t* t_img, int B,
+                       int F, int N, size_t per, hipStream_t st);
+int launch_joint_merge(const float* terms_v, const float* terms_i, float* terms_out, const float* mo_v, const float* mo_i, float* mo_out, int B,
+                       int F, int N, size_t per, hipStream_t st);
 int launch_unpatchify_bwd(const float* dout, float* dtok, int BF, int G, int p, int Cout, hipStream_t st);
 int launch_im2col_patch(const float* x, float* pix, int BF, int G, int p, int C, hipStream_t st);
 int launch_embedding_bwd(const float* dc, const int64_t* idx, float* dtable, int B, int D, hipStream_t st,

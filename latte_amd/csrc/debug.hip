@@ -509,6 +509,20 @@ int latte_debug_gather_i64(const int64_t* table, const int64_t* idx, int64_t* ou
   return launch_gather_i64(table, idx, out, n, (hipStream_t)stream);
 }
 
+int latte_debug_joint_split(const float* x, const float* noise, const int64_t* t, float* x_video, float* noise_video, float* x_image,
+                            float* noise_image, int64_t* t_image, int B, int F, int N, int64_t per, void* stream) {
+  if (!x || !noise || !t || !x_video || !noise_video || !x_image || !noise_image || !t_image || B < 1 || F < 1 || N < 1 || per < 1)
+    return fail(LATTE_ERR_INVALID, "joint_split: bad arguments");
+  return launch_joint_split(x, noise, t, x_video, noise_video, x_image, noise_image, t_image, B, F, N, (size_t)per, (hipStream_t)stream);
+}
+
+int latte_debug_joint_merge(const float* terms_video, const float* terms_image, float* terms_out, const float* out_video, const float* out_image,
+                            float* out_joint, int B, int F, int N, int64_t per, void* stream) {
+  if (!terms_video || !terms_image || !terms_out || B < 1 || F < 1 || N < 1 || (out_joint && (!out_video || !out_image || per < 1)))
+    return fail(LATTE_ERR_INVALID, "joint_merge: bad arguments");
+  return launch_joint_merge(terms_video, terms_image, terms_out, out_video, out_image, out_joint, B, F, N, (size_t)per, (hipStream_t)stream);
+}
+
 static bool bad_patch_shape(int BF, int G, int p, int C) {
   return BF < 1 || G < 1 || p < 1 || C < 1 || (int64_t)p * p * C > 0x7fffffff || (int64_t)G * p > 0x7fffffff;
 }

@@ -16,7 +16,9 @@
 // Row-wise kernels use one wave per token row (lane owns the float4 chunks {lane + 64 c} of the row, as ln_modulate_kernel);
 // per-sample column reductions (dshift / dscale / dgate) are two-stage and deterministic: a wave walks a run of consecutive
 // rows of ONE sample and writes one partial row, a finalize kernel adds the partial rows in a fixed order.
+#include <algorithm>
 #include <cmath>
+#include <initializer_list>
 
 #include "common.h"
 #include "mfma_util.h"
@@ -549,6 +551,61 @@ __global__ void gather_i64_kernel(const int64_t* __restrict__ table, const int64
   if (i < n) out[i] = table[idx[i]];
 }
 
+// ---------------------------------------------------------------------------------------------- joint image-video micro-batch
+// (train_with_img.py:214-241, latte_img.py:361-399: F video frames and N image frames per sample; the step runs them as a video
+// pass over [B, F] and a spatial-only image pass over B N one-frame pseudo-samples)
+// x / nz [B][F + N][per] -> the packed video regions xv / nv [B][F][per] and image regions xi / ni [B N][1][per];
+// t_img[b N + n] = t[b].  V: floats per thread step (4: per % 4 == 0 and 16-byte aligned buffers)
+template <int V>
+__global__ void __launch_bounds__(256) joint_split_kernel(const float* __restrict__ x, const float* __restrict__ nz, const int64_t* __restrict__ t,
+                                                          float* __restrict__ xv, float* __restrict__ nv, float* __restrict__ xi,
+                                                          float* __restrict__ ni, int64_t* __restrict__ t_img, int B, int F, int N, size_t per) {
+  const size_t pv = per / V, total = (size_t)B * (F + N) * pv;
+  const size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i0 < (size_t)B * N) t_img[i0] = t[i0 / N];
+  for (size_t i = i0; i < total; i += (size_t)gridDim.x * 256) {
+    const size_t fr = i / pv, r = i - fr * pv;
+    const size_t b = fr / (F + N);
+    const int f = (int)(fr - b * (F + N));
+    const size_t dst = (f < F ? (b * F + f) : (b * N + (f - F))) * pv + r;
+    float* ox = f < F ? xv : xi;
+    float* on = f < F ? nv : ni;
+    if constexpr (V == 4) {
+      ((float4*)ox)[dst] = ((const float4*)x)[i];
+      ((float4*)on)[dst] = ((const float4*)nz)[i];
+    } else {
+      ox[dst] = x[i];
+      on[dst] = nz[i];
+    }
+  }
+}
+// terms_out[k][b] = (F tv[k][b] + sum_n ti[k][b N + n]) / (F + N), k < 3 (mean_flat over the F + N frames of a sample: every frame has
+// the same number of elements), summed in double and rounded once;  mo_out [B][F + N][per] <- mo_v [B][F][per], mo_i [B N][per]
+// (mo_out == nullptr: terms only)
+template <int V>
+__global__ void __launch_bounds__(256) joint_merge_kernel(const float* __restrict__ tv, const float* __restrict__ ti, float* __restrict__ terms_out,
+                                                          const float* __restrict__ mo_v, const float* __restrict__ mo_i,
+                                                          float* __restrict__ mo_out, int B, int F, int N, size_t per) {
+  const size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i0 < (size_t)3 * B) {
+    const int k = (int)(i0 / B), b = (int)(i0 - (size_t)k * B);
+    double s = (double)F * (double)tv[(size_t)k * B + b];
+    for (int n = 0; n < N; ++n) s += (double)ti[((size_t)k * B + b) * N + n];
+    terms_out[i0] = (float)(s / (double)(F + N));
+  }
+  if (!mo_out) return;
+  const size_t pv = per / V, total = (size_t)B * (F + N) * pv;
+  for (size_t i = i0; i < total; i += (size_t)gridDim.x * 256) {
+    const size_t fr = i / pv, r = i - fr * pv;
+    const size_t b = fr / (F + N);
+    const int f = (int)(fr - b * (F + N));
+    const size_t src = (f < F ? (b * F + f) : (b * N + (f - F))) * pv + r;
+    const float* in = f < F ? mo_v : mo_i;
+    if constexpr (V == 4) ((float4*)mo_out)[i] = ((const float4*)in)[src];
+    else mo_out[i] = in[src];
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- token <-> latent layout helpers
 // dtok[m][(p q c)] = dout[bf][c][gh p_ + p][gw p_ + q]   (inverse of unpatchify, latte.py:297-310), m = bf * T + gh * G + gw
 __global__ void unpatchify_bwd_kernel(const float* __restrict__ dout, float* __restrict__ dtok, int BF, int G, int p, int Cout) {
@@ -987,6 +1044,37 @@ int launch_tfreq(const int64_t* t, float* out, int B, hipStream_t st) {
 }
 int launch_gather_i64(const int64_t* table, const int64_t* idx, int64_t* out, int n, hipStream_t st) {
   hipLaunchKernelGGL(gather_i64_kernel, dim3((n + 255) / 256), dim3(256), 0, st, table, idx, out, n);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+
+static bool joint_vec4(size_t per, std::initializer_list<const void*> ptrs) {
+  if (per % 4) return false;
+  for (const void* p : ptrs)
+    if ((uintptr_t)p & 15) return false;
+  return true;
+}
+int launch_joint_split(const float* x, const float* nz, const int64_t* t, float* xv, float* nv, float* xi, float* ni, int64_t* t_img, int B,
+                       int F, int N, size_t per, hipStream_t st) {
+  if (B < 1 || F < 1 || N < 1 || per < 1) return fail(LATTE_ERR_INVALID, "joint_split: need B, F, N, per >= 1");
+  if (joint_vec4(per, {x, nz, xv, nv, xi, ni}))
+    hipLaunchKernelGGL(joint_split_kernel<4>, dim3(blocks_for((size_t)B * (F + N) * (per / 4))), dim3(256), 0, st, x, nz, t, xv, nv, xi, ni, t_img,
+                       B, F, N, per);
+  else
+    hipLaunchKernelGGL(joint_split_kernel<1>, dim3(blocks_for((size_t)B * (F + N) * per)), dim3(256), 0, st, x, nz, t, xv, nv, xi, ni, t_img, B, F,
+                       N, per);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+int launch_joint_merge(const float* terms_v, const float* terms_i, float* terms_out, const float* mo_v, const float* mo_i, float* mo_out, int B,
+                       int F, int N, size_t per, hipStream_t st) {
+  if (B < 1 || F < 1 || N < 1 || (mo_out && per < 1)) return fail(LATTE_ERR_INVALID, "joint_merge: need B, F, N, per >= 1");
+  if (mo_out && joint_vec4(per, {mo_v, mo_i, mo_out}))
+    hipLaunchKernelGGL(joint_merge_kernel<4>, dim3(blocks_for(std::max((size_t)B * (F + N) * (per / 4), (size_t)3 * B))), dim3(256), 0, st, terms_v,
+                       terms_i, terms_out, mo_v, mo_i, mo_out, B, F, N, per);
+  else
+    hipLaunchKernelGGL(joint_merge_kernel<1>, dim3(blocks_for(mo_out ? std::max((size_t)B * (F + N) * per, (size_t)3 * B) : (size_t)3 * B)),
+                       dim3(256), 0, st, terms_v, terms_i, terms_out, mo_v, mo_i, mo_out, B, F, N, per);
   LATTE_HIP(hipGetLastError());
   return LATTE_OK;
 }

@@ -90,6 +90,18 @@ struct latte_trainer {
   half_t *dyD = nullptr, *dhH = nullptr, *dxnH = nullptr, *dqkvH = nullptr, *xnh = nullptr;
   int64_t wg_ws_floats = 0, ng_ws_floats = 0, loss_ws_floats = 0;
   bool weights_synced = false;
+  // Joint image-video micro-batch (latte_trainer_begin_joint; train_with_img.py:214-241, latte_img.py:361-399).  The image frames of a
+  // sample never meet its video frames (spatial blocks treat every frame alone, temporal blocks see x[:, :F] only) and mean_flat runs
+  // over all F + N frames, so loss.mean() = F / (F + N) mean_b(loss_video_b) + N / (F + N) mean_{b,n}(loss_image_{b,n}): the step is the
+  // video pass below plus an image pass over B N one-frame pseudo-samples in spatial-only mode.  The RUN MODE of a pass: frames per
+  // sample (run_F), temporal blocks on / off (off: odd blocks skipped in the forward and in their backward stage, no temp_embed,
+  // the xs[] / xn1 chain follows the even blocks), and the pass's loss weight (multiplies loss_divisor).
+  int max_image = 0;
+  int run_F = 0, run_temporal = 1;
+  float run_weight = 1.0f;
+  int joint_saved_acc = -1;      // >= 0: an image pass is in flight (always in accumulate mode); the caller's grad_accumulate, restored after its last stage
+  float *jx_v = nullptr, *jn_v = nullptr, *jx_i = nullptr, *jn_i = nullptr, *jmo = nullptr, *jterms = nullptr;
+  int64_t* jt_i = nullptr;
   int cur_batch = 0, next_stage = 1 << 30;   // step in flight: batch, labels (caller keeps them alive), next backward stage
   const int64_t* cur_y = nullptr;
   DeviceArena arena;
@@ -172,7 +184,15 @@ const float* acc_scale(const latte_trainer* e) { return e->grad_accumulate && sc
 extern "C" {
 
 int latte_trainer_create(const latte_model_config_t* cfg, int max_batch, latte_trainer_t** out) {
-  if (!cfg || !out || max_batch <= 0) return fail(LATTE_ERR_INVALID, "trainer_create: bad arguments");
+  return latte_trainer_create_joint(cfg, max_batch, 0, out);
+}
+
+// max_image_num > 0: the per-sample buffers hold max_batch * max_image_num pseudo-samples of the image pass (the row buffers already
+// do: B N T <= B F T), plus the packed regions of the joint micro-batch
+int latte_trainer_create_joint(const latte_model_config_t* cfg, int max_batch, int max_image_num, latte_trainer_t** out) {
+  if (!cfg || !out || max_batch <= 0 || max_image_num < 0) return fail(LATTE_ERR_INVALID, "trainer_create: bad arguments");
+  if (max_image_num > cfg->num_frames)
+    return fail(LATTE_ERR_INVALID, "trainer: use_image_num must not exceed num_frames (the image pass runs in the video pass's row buffers)");
   const auto& c = *cfg;
   if (c.extras != 1 && c.extras != 2) return fail(LATTE_ERR_INVALID, "trainer: extras must be 1 or 2 (train.py:213-218 refuses text-to-video training)");
   if (c.hidden_size % 128 || c.hidden_size > 1280 || c.depth % 2 || c.hidden_size % c.num_heads)
@@ -184,6 +204,8 @@ int latte_trainer_create(const latte_model_config_t* cfg, int max_batch, latte_t
   auto* e = new latte_trainer();
   e->cfg = c;
   e->max_batch = max_batch;
+  e->max_image = max_image_num;
+  e->run_F = c.num_frames;
   e->D = c.hidden_size; e->F = c.num_frames; e->G = c.input_size / c.patch_size; e->T = e->G * e->G;
   e->Cin = c.in_channels; e->Cout = c.learn_sigma ? 2 * c.in_channels : c.in_channels; e->H = c.input_size;
   e->P = c.patch_size * c.patch_size * e->Cout; e->KPE = c.in_channels * c.patch_size * c.patch_size;
@@ -192,6 +214,10 @@ int latte_trainer_create(const latte_model_config_t* cfg, int max_batch, latte_t
   e->dynamic_scale = c.compute_dtype == LATTE_DTYPE_F16 ? 1 : 0;
   e->nmod = c.depth * 6 * e->D + 2 * e->D;
   if ((e->F * e->T) % 64) { delete e; return fail(LATTE_ERR_INVALID, "trainer: frames * tokens per sample must be a multiple of 64"); }
+  if (max_image_num > 0 && e->T % 64) {
+    delete e;
+    return fail(LATTE_ERR_INVALID, "trainer: joint image-video training needs tokens per frame to be a multiple of 64 (an image is a sample of one frame)");
+  }
   e->rows_max = (int64_t)max_batch * e->F * e->T;
   e->rows_pad = (e->rows_max + 255) / 256 * 256;
   e->ld = (e->rows_max + 63) / 64 * 64;
@@ -235,7 +261,7 @@ int latte_trainer_create(const latte_model_config_t* cfg, int max_batch, latte_t
     A(&b.qkv_w, (size_t)3 * D * D); A(&b.qkv_wt, (size_t)3 * D * D); A(&b.proj_w, (size_t)D * D); A(&b.proj_wt, (size_t)D * D);
     A(&b.fc1_w, (size_t)Hm * D); A(&b.fc1_wt, (size_t)Hm * D); A(&b.fc2_w, (size_t)Hm * D); A(&b.fc2_wt, (size_t)Hm * D);
   }
-  const size_t Bm = (size_t)max_batch;
+  const size_t Bm = (size_t)max_batch * std::max(1, max_image_num);   // samples of a pass: the image pass has batch * use_image_num
   A(&e->tfreq, Bm * 256); A(&e->temb_pre, Bm * D); A(&e->temb_act, Bm * D); A(&e->cvec, Bm * D); A(&e->csilu, Bm * D);
   A(&e->mod, Bm * e->nmod); A(&e->dmod, Bm * e->nmod); A(&e->dc, Bm * D); A(&e->dtmp, Bm * D); A(&e->dtmp2, Bm * D);
   A(&e->t_orig, Bm);
@@ -275,11 +301,17 @@ int latte_trainer_create(const latte_model_config_t* cfg, int max_batch, latte_t
     e->wg_ws_floats = worst;
     A(&e->wg_ws, (size_t)worst);
   }
-  e->ng_ws_floats = 64LL * std::max<int64_t>((int64_t)e->P * D, (int64_t)max_batch * D) + 64LL * D * e->KPE + 64LL * D;
+  e->ng_ws_floats = 64LL * std::max<int64_t>((int64_t)e->P * D, (int64_t)Bm * D) + 64LL * D * e->KPE + 64LL * D;
   A(&e->ng_ws, (size_t)e->ng_ws_floats);
   A(&e->attn_stats, (size_t)e->rows_max * c.num_heads * 3 + 16);
-  e->loss_ws_floats = latte_training_workspace_floats(max_batch, (int64_t)e->F * e->Cin * e->H * e->H) + 3 * max_batch;
+  e->loss_ws_floats = std::max(latte_training_workspace_floats(max_batch, (int64_t)e->F * e->Cin * e->H * e->H),
+                               latte_training_workspace_floats((int)Bm, (int64_t)e->Cin * e->H * e->H)) + 3 * max_batch;
   A(&e->loss_ws, (size_t)e->loss_ws_floats);
+  if (max_image_num > 0) {
+    const size_t per = (size_t)e->Cin * e->H * e->H, mb = (size_t)max_batch;
+    A(&e->jx_v, mb * e->F * per); A(&e->jn_v, mb * e->F * per); A(&e->jx_i, Bm * per); A(&e->jn_i, Bm * per);
+    A(&e->jmo, mb * e->F * e->Cout * e->H * e->H); A(&e->jterms, 3 * mb + 3 * Bm); A(&e->jt_i, Bm);
+  }
   A(&e->stats, 4);
   A(&e->scaler, 8);
   A(&e->sumsq, (size_t)sumsq_blocks());
@@ -358,11 +390,16 @@ int latte_trainer_sync_weights(latte_trainer_t* e, void* stream) {
 
 // Forward with saved activations + loss terms + d loss / d model_output; the backward follows in stages (below).
 // terms_out: device float [3][batch] = loss, mse, vb;  model_out_copy: optional device copy of the model output
-int latte_trainer_begin(latte_trainer_t* e, const latte_schedule_t* s, int loss_type, const float* x_start, const float* noise,
-                        const int64_t* t, const int64_t* y, int batch, float* terms_out, float* model_out_copy, void* stream) {
+}  // extern "C"
+
+namespace {
+// one pass in the trainer's current run mode (run_F frames per sample, temporal blocks on / off, loss weight); batch_cap: samples the
+// per-sample buffers hold in that mode
+int begin_impl(latte_trainer_t* e, const latte_schedule_t* s, int loss_type, const float* x_start, const float* noise, const int64_t* t,
+               const int64_t* y, int batch, int batch_cap, float* terms_out, float* model_out_copy, void* stream) {
   if (!e || !s || !x_start || !noise || !t || !terms_out) return fail(LATTE_ERR_INVALID, "train step: null argument");
   if (!e->Pm) return fail(LATTE_ERR_STATE, "train step: bind the parameter buffers first");
-  if (batch <= 0 || batch > e->max_batch) return fail(LATTE_ERR_STATE, "train step: batch exceeds max_batch");
+  if (batch <= 0 || batch > batch_cap) return fail(LATTE_ERR_STATE, "train step: batch exceeds max_batch");
   if (loss_type != 0 && loss_type != 1) return fail(LATTE_ERR_INVALID, "train step: loss_type must be 0 (MSE) or 1 (RESCALED_MSE); the KL losses train no mean head (gaussian_diffusion.py:741-752)");
   if (s->mean_type != 0) return fail(LATTE_ERR_INVALID, "train step: only the epsilon-prediction models of train.py:92 are supported");
   if ((s->var_type == 0) != (e->cfg.learn_sigma != 0)) return fail(LATTE_ERR_INVALID, "train step: schedule / model disagree on learn_sigma");
@@ -371,7 +408,8 @@ int latte_trainer_begin(latte_trainer_t* e, const latte_schedule_t* s, int loss_
   hipStream_t st = (hipStream_t)stream;
   int rc;
   if (!e->weights_synced && (rc = latte_trainer_sync_weights(e, stream))) return rc;
-  const int D = e->D, T = e->T, F = e->F, Hm = e->Hm, B = batch, dt = e->dt, nmod = e->nmod;
+  const int D = e->D, T = e->T, F = e->run_F, Hm = e->Hm, B = batch, dt = e->dt, nmod = e->nmod;
+  const bool temporal = e->run_temporal != 0;
   const int M = B * F * T, rps = F * T;
   const int hw = e->H * e->H;
   const float* tab = nullptr;
@@ -409,12 +447,14 @@ int latte_trainer_begin(latte_trainer_t* e, const latte_schedule_t* s, int loss_
     return rc;
   for (int i = 0; i < c.depth; ++i) {
     const bool spatial = (i % 2) == 0;
+    if (!temporal && !spatial) continue;
+    const int nx = temporal ? i + 1 : i + 2;   // the next block that runs: its input snapshot is xs[2 nx] (depth is even: nx <= depth)
     const std::string p = "blocks." + std::to_string(i) + ".";
     BlockBuf& b = e->blk[i];
     const float* mb = e->mod + (size_t)i * 6 * D;
     float* x0 = e->xs[2 * i];
     float* x1 = e->xs[2 * i + 1];
-    float* x2 = e->xs[2 * i + 2];
+    float* x2 = e->xs[2 * nx];
     // (fuse_small: blocks 1 .. depth-1 got xn1 -- and the temporal embedding -- from the previous block's closing gated add)
     if ((!e->fuse_small || i == 0) &&
         (rc = launch_ln_modulate(x0, x0, b.xn1, mb, mb + D, nmod, M, D, rps, i == 1 ? e->temp : nullptr, T, F, dt, st))) return rc;
@@ -440,10 +480,10 @@ int latte_trainer_begin(latte_trainer_t* e, const latte_schedule_t* s, int loss_
       if ((rc = launch_gelu_fwd(b.u, b.h, (size_t)M * Hm, dt, st))) return rc;
     }
     if ((rc = gemm_half(e, b.h, b.fc2_w, P_(e, p + "mlp.fc2.bias"), b.y2, M, D, Hm, st))) return rc;
-    if (e->fuse_small && i + 1 < c.depth) {   // x2 = x1 + g2 y2 (+ temp_embed in front of block 1) and the NEXT block's xn1
-      const float* nb = e->mod + (size_t)(i + 1) * 6 * D;
-      if ((rc = launch_gated_add_ln(x1, b.y2, mb + 5 * D, nmod, x2, e->blk[i + 1].xn1, nb, nb + D, nmod, M, D, rps,
-                                    i + 1 == 1 ? e->temp : nullptr, T, F, dt, st))) return rc;
+    if (e->fuse_small && nx < c.depth) {   // x2 = x1 + g2 y2 (+ temp_embed in front of block 1) and the NEXT running block's xn1
+      const float* nb = e->mod + (size_t)nx * 6 * D;
+      if ((rc = launch_gated_add_ln(x1, b.y2, mb + 5 * D, nmod, x2, e->blk[nx].xn1, nb, nb + D, nmod, M, D, rps,
+                                    nx == 1 ? e->temp : nullptr, T, F, dt, st))) return rc;
     } else if ((rc = launch_gated_add(x1, b.y2, mb + 5 * D, nmod, x2, M, D, rps, dt, st))) return rc;
   }
   float* xl = e->xs[2 * c.depth];
@@ -459,14 +499,73 @@ int latte_trainer_begin(latte_trainer_t* e, const latte_schedule_t* s, int loss_
   if ((rc = latte_training_losses(s, loss_type, x_start, e->x_t, noise, e->model_out, t, B, F, e->Cin, hw, e->loss_ws,
                                   e->loss_ws_floats - 3 * e->max_batch, terms_out + B, terms_out + 2 * B, terms_out, stream))) return rc;
   if ((rc = launch_loss_grad(tab, s->num_timesteps, s->mean_type, s->var_type, x_start, e->x_t, noise, e->model_out, t, B, F, e->Cin, hw,
-                             vb_scale, e->dmodel_out, st, e->loss_divisor))) return rc;
+                             vb_scale, e->dmodel_out, st, e->loss_divisor * e->run_weight))) return rc;
   if (scaling_active(e) && (rc = launch_scale_f32_dev(e->dmodel_out, e->scaler, 0, (size_t)B * F * e->Cout * hw, st))) return rc;
 
   LATTE_HIP(hipMemsetAsync(e->dc, 0, sizeof(float) * (size_t)B * D, st));   // d SiLU(c), summed over the adaLN linears by the stages
+  // temporal blocks off: their stages write no dmod rows, and the last stage contracts ALL rows with the adaLN weights -- what the
+  // previous pass left there must not reach the t / y embedders' gradients
+  if (!temporal) LATTE_HIP(hipMemsetAsync(e->dmod, 0, sizeof(float) * (size_t)B * nmod, st));
   e->cur_batch = B;
   e->cur_y = y;
   e->next_stage = 0;
   return LATTE_OK;
+}
+
+// the trainer back in the plain run mode (an image pass that was abandoned half way included)
+void plain_mode(latte_trainer_t* e) {
+  if (e->joint_saved_acc >= 0) e->grad_accumulate = e->joint_saved_acc;
+  e->joint_saved_acc = -1;
+  e->run_F = e->F;
+  e->run_temporal = 1;
+  e->run_weight = 1.0f;
+}
+}  // namespace
+
+extern "C" {
+
+int latte_trainer_begin(latte_trainer_t* e, const latte_schedule_t* s, int loss_type, const float* x_start, const float* noise,
+                        const int64_t* t, const int64_t* y, int batch, float* terms_out, float* model_out_copy, void* stream) {
+  if (!e) return fail(LATTE_ERR_INVALID, "train step: null argument");
+  plain_mode(e);
+  return begin_impl(e, s, loss_type, x_start, noise, t, y, batch, e->max_batch, terms_out, model_out_copy, stream);
+}
+
+// One joint micro-batch: x_start / noise / model_out_copy [batch, F + N, C, H, W], y_image int64 [batch, N] after label dropout.
+// The video pass runs here completely (forward and every stage, in the caller's assign / accumulate mode), then the image pass's
+// forward in accumulate mode; ITS stages are the caller's (latte_trainer_backward_stage: after stage k the slice is final).
+int latte_trainer_begin_joint(latte_trainer_t* e, const latte_schedule_t* s, int loss_type, const float* x_start, const float* noise,
+                              const int64_t* t, const int64_t* y, const int64_t* y_image, int batch, int use_image_num, float* terms_out,
+                              float* model_out_copy, void* stream) {
+  if (!e || !s || !x_start || !noise || !t || !terms_out) return fail(LATTE_ERR_INVALID, "joint train step: null argument");
+  if (use_image_num < 1 || use_image_num > e->max_image)
+    return fail(LATTE_ERR_INVALID, "joint train step: use_image_num must be in [1, max_image_num of latte_trainer_create_joint]");
+  if (batch <= 0 || batch > e->max_batch) return fail(LATTE_ERR_STATE, "train step: batch exceeds max_batch");
+  if (e->cfg.extras == 2 && (!y || !y_image)) return fail(LATTE_ERR_INVALID, "joint train step: class-conditional model needs y and y_image");
+  hipStream_t st = (hipStream_t)stream;
+  const int B = batch, F = e->F, N = use_image_num;
+  const size_t per = (size_t)e->Cin * e->H * e->H, per_out = (size_t)e->Cout * e->H * e->H;
+  float* tv = e->jterms;
+  float* ti = e->jterms + 3 * (size_t)e->max_batch;
+  int rc;
+  plain_mode(e);
+  if ((rc = launch_joint_split(x_start, noise, t, e->jx_v, e->jn_v, e->jx_i, e->jn_i, e->jt_i, B, F, N, per, st))) return rc;
+  // ---- video pass: the plain step with the weight F / (F + N) on its loss
+  e->run_weight = (float)(F + N) / (float)F;
+  rc = begin_impl(e, s, loss_type, e->jx_v, e->jn_v, t, y, B, e->max_batch, tv, model_out_copy ? e->jmo : nullptr, stream);
+  for (int k = 0; !rc && k < latte_trainer_num_stages(e); ++k) rc = latte_trainer_backward_stage(e, k, stream);
+  if (rc) { plain_mode(e); return rc; }
+  // ---- image pass: B N one-frame samples, spatial blocks only, gradients ADDED (unscaled by their writers)
+  e->joint_saved_acc = e->grad_accumulate;
+  e->grad_accumulate = 1;
+  e->run_F = 1;
+  e->run_temporal = 0;
+  e->run_weight = (float)(F + N) / (float)N;
+  rc = begin_impl(e, s, loss_type, e->jx_i, e->jn_i, e->jt_i, e->cfg.extras == 2 ? y_image : nullptr, B * N, e->max_batch * e->max_image, ti,
+                  nullptr, stream);
+  if (!rc) rc = launch_joint_merge(tv, ti, terms_out, e->jmo, e->model_out, model_out_copy, B, F, N, per_out, st);
+  if (rc) { plain_mode(e); e->next_stage = 1 << 30; }
+  return rc;
 }
 
 // adaLN linear of block i (i == depth: the final layer's): bias / weight gradients from the finished dmod rows, and its
@@ -515,6 +614,10 @@ int latte_trainer_backward_stage(latte_trainer_t* e, int stage, void* stream) {
     int64_t off = 0, n = 0;
     if ((rc = latte_trainer_stage_range(e, stage, &off, &n))) return rc;
     rc = launch_scale_f32_dev(e->Gr + off, e->scaler, 1, (size_t)n, (hipStream_t)stream);
+  }
+  if (e && e->joint_saved_acc >= 0 && (rc || stage == e->cfg.depth + 1)) {   // the image pass of a joint micro-batch is over
+    plain_mode(e);
+    if (rc) e->next_stage = 1 << 30;
   }
   return rc;
 }
@@ -567,9 +670,13 @@ static int backward_stage_impl(latte_trainer_t* e, int stage, void* stream) {
   const auto& c = e->cfg;
   hipStream_t st = (hipStream_t)stream;
   int rc;
-  const int D = e->D, T = e->T, F = e->F, Hm = e->Hm, B = e->cur_batch, dt = e->dt, nmod = e->nmod;
+  const int D = e->D, T = e->T, F = e->run_F, Hm = e->Hm, B = e->cur_batch, dt = e->dt, nmod = e->nmod;
+  const bool temporal = e->run_temporal != 0;
   const int M = B * F * T, rps = F * T;
   const int64_t* y = e->cur_y;
+  // the MLP gate's partial rows of block i wait in one of two buffers for its stage's finalize launch, which follows the pass that
+  // fills the NEXT running block's: consecutive running blocks alternate (temporal off: blocks 0, 2, 4, ...)
+  auto pg2_of = [&](int i) { return ((temporal ? i : i >> 1) & 1) ? e->pg2b : e->pg2; };
   const int acc = e->grad_accumulate;
   const float* gs = acc_scale(e);
   if (stage == 0) {
@@ -598,9 +705,9 @@ static int backward_stage_impl(latte_trainer_t* e, int stage, void* stream) {
     float* dm = e->dmod + (size_t)c.depth * 6 * D;
     if (e->fuse_small) {   // shift / scale gradients of the final modulation and its adaLN linear's bias / weight gradients in one launch
       {   // ... and the gated residual's backward of the last block's MLP branch on the same pass over dx (its stage starts at the wgrad)
-        const int il = c.depth - 1;
+        const int il = temporal ? c.depth - 1 : c.depth - 2;   // the last block that ran
         if ((rc = launch_ln_bwd(e->dxnH, xl, fm + D, nmod, nullptr, e->dx, e->pl1, nullptr, nullptr, nmod, M, D, rps, dt, st, e->blk[il].y2,
-                                e->mod + (size_t)il * 6 * D + 5 * D, nmod, e->dyD, (il & 1) ? e->pg2b : e->pg2))) return rc;
+                                e->mod + (size_t)il * 6 * D + 5 * D, nmod, e->dyD, pg2_of(il)))) return rc;
       }
       StageFinArgs a{};
       a.mod_src[0] = a.mod_src[1] = e->pl1; a.mod_nsum[0] = a.mod_nsum[1] = 2; a.mod_which[0] = 0; a.mod_which[1] = 1;
@@ -618,6 +725,8 @@ static int backward_stage_impl(latte_trainer_t* e, int stage, void* stream) {
   if (stage <= c.depth) {
     const int i = c.depth - stage;
     const bool spatial = (i % 2) == 0;
+    if (!temporal && !spatial) return LATTE_OK;   // the block did not run: its gradient slice, dx and the waiting partial rows stay
+    const int ip = temporal ? i - 1 : i - 2;      // the running block in front of this one
     const std::string p = "blocks." + std::to_string(i) + ".";
     BlockBuf& b = e->blk[i];
     const float* mb = e->mod + (size_t)i * 6 * D;
@@ -626,7 +735,7 @@ static int backward_stage_impl(latte_trainer_t* e, int stage, void* stream) {
       const bool us = scaling_active(e);
       // ---- MLP branch: x2 = x1 + g2 * (fc2(gelu(fc1(xn2)))).  dy = g2 dx and the gate / bias partial rows were left by the LayerNorm
       // backward that produced dx (the previous stage's last pass); the partial rows wait for this stage's finalize launch
-      float* pg2 = (i & 1) ? e->pg2b : e->pg2;
+      float* pg2 = pg2_of(i);
       if ((rc = wgrad(e, e->dyD, b.h, M, D, Hm, G_(e, p + "mlp.fc2.weight"), st, us))) return rc;
       if (gelu_fusable(e, M, Hm, D)) {
         if ((rc = gemm_gelu(e, EPI_DGELU_H16, e->dyD, b.fc2_wt, e->zeros, e->dhH, b.u, M, Hm, D, st))) return rc;
@@ -653,9 +762,9 @@ static int backward_stage_impl(latte_trainer_t* e, int stage, void* stream) {
       if ((rc = wgrad(e, e->dqkvH, b.xn1, M, 3 * D, D, G_(e, p + "attn.qkv.weight"), st, us, cs_qkv ? e->pc_qkv : nullptr,
                       cs_qkv ? &qkv_rows : nullptr))) return rc;
       if ((rc = gemm_half(e, e->dqkvH, b.qkv_wt, e->zeros, e->dxnH, M, D, 3 * D, st))) return rc;
-      if (i > 0) {   // LN1's backward + the gate backward of block i - 1's MLP branch (the next stage's first step)
+      if (ip >= 0) {   // LN1's backward + the gate backward of the previous running block's MLP branch (the next stage's first step)
         if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i], mb + D, nmod, e->dx, e->dx, e->pl1, nullptr, nullptr, nmod, M, D, rps, dt, st,
-                                e->blk[i - 1].y2, e->mod + (size_t)(i - 1) * 6 * D + 5 * D, nmod, e->dyD, ((i - 1) & 1) ? e->pg2b : e->pg2)))
+                                e->blk[ip].y2, e->mod + (size_t)ip * 6 * D + 5 * D, nmod, e->dyD, pg2_of(ip))))
           return rc;
       } else if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i], mb + D, nmod, e->dx, e->dx, e->pl1, nullptr, nullptr, nmod, M, D, rps, dt, st)))
         return rc;
@@ -749,6 +858,14 @@ static int backward_stage_impl(latte_trainer_t* e, int stage, void* stream) {
 int latte_trainer_forward_backward(latte_trainer_t* e, const latte_schedule_t* s, int loss_type, const float* x_start, const float* noise,
                                    const int64_t* t, const int64_t* y, int batch, float* terms_out, float* model_out_copy, void* stream) {
   int rc = latte_trainer_begin(e, s, loss_type, x_start, noise, t, y, batch, terms_out, model_out_copy, stream);
+  for (int k = 0; !rc && k < latte_trainer_num_stages(e); ++k) rc = latte_trainer_backward_stage(e, k, stream);
+  return rc;
+}
+
+int latte_trainer_forward_backward_joint(latte_trainer_t* e, const latte_schedule_t* s, int loss_type, const float* x_start, const float* noise,
+                                         const int64_t* t, const int64_t* y, const int64_t* y_image, int batch, int use_image_num,
+                                         float* terms_out, float* model_out_copy, void* stream) {
+  int rc = latte_trainer_begin_joint(e, s, loss_type, x_start, noise, t, y, y_image, batch, use_image_num, terms_out, model_out_copy, stream);
   for (int k = 0; !rc && k < latte_trainer_num_stages(e); ++k) rc = latte_trainer_backward_stage(e, k, stream);
   return rc;
 }

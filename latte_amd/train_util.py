@@ -28,6 +28,31 @@ def data_seed(seed, step, micro, accum, rank, world):
     return int(seed) * 1000003 + (int(step) * int(accum) + int(micro)) * int(world) + int(rank)
 
 
+def latte_preset_name(name):
+    """The model preset a training config's ``model:`` names: ``LatteIMG-XL/2`` (train_with_img.py, models/latte_img.py) has exactly the
+    parameters of ``Latte-XL/2`` and its checkpoints are sampled with that preset, so the joint trainer runs on the plain model:
+    "LatteIMG-<size>" -> "Latte-<size>"; every other name as it is (``get_models`` itself keeps refusing the LatteIMG names)."""
+    name = str(name)
+    return "Latte-" + name[len("LatteIMG-"):] if name.startswith("LatteIMG-") else name
+
+
+def joint_loss_weights(num_frames, use_image_num):
+    """(video, image) weights of the two passes of a joint micro-batch in its loss: mean_flat runs over all F + N frames of a sample,
+    so the video pass carries F / (F + N) and the image pass N / (F + N)."""
+    f, n = int(num_frames), int(use_image_num)
+    if f < 1 or n < 0:
+        raise ValueError("need num_frames >= 1 and use_image_num >= 0")
+    return f / (f + n), n / (f + n)
+
+
+def draw_image_frames(num_files, samples, use_image_num, generator):
+    """Indices [samples, use_image_num] of the single frames that join each sample of a micro-batch, drawn with replacement from
+    ``num_files`` files by the caller's seeded generator (data_seed): a resumed run redraws the same ones."""
+    if num_files < 1 or samples < 1 or use_image_num < 1:
+        raise ValueError("need num_files, samples and use_image_num >= 1")
+    return torch.randint(0, int(num_files), (int(samples), int(use_image_num)), generator=generator)
+
+
 def checkpoint_step(path):
     """0100000.pt -> 100000 (train.py:195-196); None for anything that is not a numbered checkpoint (the state files beside them)."""
     m = re.fullmatch(r"(\d+)\.pt", os.path.basename(str(path)))

@@ -66,11 +66,17 @@ class LatteTrainer:
     optimiser steps.  Data parallel: only the window's last micro-batch takes the staged backward with its per-stage all-reduce (of
     the ACCUMULATED slice, final only then); the earlier ones run without a collective, as under DDP's ``no_sync``.
     ``training_state()`` / ``load_training_state()`` carry everything a run is made of (parameters, EMA, AdamW moments, the eight
-    loss-scale / update counters, ``train_steps``, a partial window) so that a resumed run continues bit for bit."""
+    loss-scale / update counters, ``train_steps``, a partial window) so that a resumed run continues bit for bit.
+    use_image_num = N > 0: joint image-video training (train_with_img.py:214-241, models/latte_img.py, the ``*_img_train.yaml``
+    configs): ``x_start`` is [B, F + N, C, H, W] -- F video frames and N single images per sample -- and class-conditional models take
+    ``y_image`` [B, N] besides ``y``.  LatteIMG has exactly Latte's parameters and its image frames meet neither the video frames nor
+    the temporal blocks, so the engine runs a joint micro-batch as the video step plus one spatial-only image pass over B N one-frame
+    samples whose gradient writers add (include/latte_amd.h); the checkpoint is sampled with the plain ``Latte-*`` presets.  A joint
+    micro-batch is ONE micro-batch of an accumulation window.  N <= num_frames; with N = 0 nothing changes."""
 
     def __init__(self, model, diffusion, max_batch, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_max_norm=0.1,
                  start_clip_iter=20000, ema_decay=0.9999, class_dropout_prob=0.1, compute_dtype="f16", process_group=None,
-                 loss_scale=None, dynamic_loss_scale=None, gradient_accumulation_steps=1):
+                 loss_scale=None, dynamic_loss_scale=None, gradient_accumulation_steps=1, use_image_num=0):
         if not isinstance(model, Latte):
             raise LatteError("LatteTrainer needs a latte_amd.Latte model")
         if not isinstance(diffusion, SpacedDiffusion):
@@ -84,6 +90,14 @@ class LatteTrainer:
         _lib.require_gpu()
         self.model, self.diffusion = model, diffusion
         self.max_batch = int(max_batch)
+        self.use_image_num = int(use_image_num)
+        if self.use_image_num < 0:
+            raise LatteError("use_image_num must be >= 0")
+        if self.use_image_num > model.num_frames:
+            raise LatteError(f"use_image_num {self.use_image_num} exceeds num_frames {model.num_frames}: the image pass runs in the "
+                             "video pass's row buffers")
+        if self.use_image_num and ((model.input_size // model.patch_size) ** 2) % 64:
+            raise LatteError("joint image-video training needs (input_size / patch_size)^2 to be a multiple of 64")
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), tuple(betas), float(eps), float(weight_decay)
         self.clip_max_norm, self.start_clip_iter, self.ema_decay = float(clip_max_norm), int(start_clip_iter), float(ema_decay)
         self.class_dropout_prob = float(class_dropout_prob)
@@ -103,7 +117,10 @@ class LatteTrainer:
         cfg = model.engine_config(compute_dtype)
         h = _lib.c_void()
         with torch.cuda.device(dev):
-            check(lib.latte_trainer_create(cfg, self.max_batch, h))
+            if self.use_image_num:
+                check(lib.latte_trainer_create_joint(cfg, self.max_batch, self.use_image_num, h))
+            else:
+                check(lib.latte_trainer_create(cfg, self.max_batch, h))
         self._h = h
         if loss_scale is not None:
             check(lib.latte_trainer_set_option(h, b"loss_scale", float(loss_scale)))
@@ -192,9 +209,29 @@ class LatteTrainer:
             check(load_library().latte_trainer_sync_weights(self._h, stream_ptr()))
 
     # ------------------------------------------------------------------ one iteration of train.py:197-236
-    def forward_backward(self, x_start, t, noise, y=None, drop_mask=None, return_model_out=False, overlap_all_reduce=False):
+    def _image_labels(self, y_image, B, image_drop_mask):
+        """y_image: [B, N] tensor or the reference's list of B tensors of N labels (train_with_img.py:218-221) -> int64 [B, N] on the
+        device after the images' label dropout: ONE coin per sample for all of its images (latte_img.py:341-342 reshapes a sample's
+        image labels to [1, N] and token_drop draws rand(labels.shape[0]))."""
+        if y_image is None:
+            raise LatteError("class-conditional model with use_image_num: y_image (the images' labels) required")
+        if isinstance(y_image, (list, tuple)):
+            y_image = torch.stack([torch.as_tensor(v).reshape(-1) for v in y_image])
+        yi = y_image.to(device=self.device, dtype=torch.int64)
+        if tuple(yi.shape) != (B, self.use_image_num):
+            raise LatteError(f"y_image must be [batch, use_image_num] = [{B}, {self.use_image_num}], got {list(yi.shape)}")
+        if image_drop_mask is not None:
+            yi = torch.where(image_drop_mask.to(self.device).reshape(B, 1), torch.full_like(yi, self.model.num_classes), yi)
+        if int(yi.min()) < 0 or int(yi.max()) > self.model.num_classes:
+            raise IndexError("label out of range")
+        return yi.contiguous()
+
+    def forward_backward(self, x_start, t, noise, y=None, drop_mask=None, return_model_out=False, overlap_all_reduce=False,
+                         y_image=None, image_drop_mask=None):
         """q_sample + forward + training_losses + backward; gradients of ``terms['loss'].mean()`` land in ``self.grads``
         (overlap_all_reduce: already averaged over the process group, bucket by bucket under the backward).
+        A trainer with ``use_image_num`` = N takes the joint micro-batch [B, F + N, C, H, W] (and ``y_image`` / ``image_drop_mask``);
+        a micro-batch of F frames still takes the plain step.
         -> dict(loss, mse, vb [, model_out])."""
         self._reduced = False
         d = self.diffusion
@@ -202,6 +239,10 @@ class LatteTrainer:
         B = x0.shape[0]
         if B > self.max_batch:
             raise LatteError(f"batch {B} exceeds max_batch {self.max_batch}")
+        F, N = self.model.num_frames, self.use_image_num
+        if N and (x0.dim() != 5 or x0.shape[1] not in (F, F + N)):
+            raise LatteError(f"x_start must be [batch, {F + N} (or {F}: video only), C, H, W], got {list(x0.shape)}")
+        joint = N > 0 and x0.shape[1] == F + N
         nz = noise.to(device=self.device, dtype=torch.float32).contiguous()
         if nz.shape != x0.shape:
             raise AssertionError("noise.shape == x_start.shape")
@@ -221,13 +262,20 @@ class LatteTrainer:
         lib = load_library()
         args = (self._h, d._h, _LOSS[d.loss_type], ptr(x0), ptr(nz), ptr(t64), ptr(yy) if yy is not None else None, B, ptr(terms),
                 ptr(mo) if mo is not None else None, stream_ptr())
+        run, begin = lib.latte_trainer_forward_backward, lib.latte_trainer_begin
+        if joint:
+            yi = self._image_labels(y_image, B, image_drop_mask) if self.model.extras == 2 else None
+            self._y_image = yi                                     # alive until the last stage
+            args = args[:7] + (ptr(yi), B, N) + args[8:]
+            run, begin = lib.latte_trainer_forward_backward_joint, lib.latte_trainer_begin_joint
         with torch.cuda.device(self.device):
             if not overlap_all_reduce:
-                check(lib.latte_trainer_forward_backward(*args))
+                check(run(*args))
             else:
                 # bucketed data parallelism: as soon as a stage's gradient slice is final its all-reduce is enqueued (RCCL runs it
                 # on its own stream behind the kernels already launched) while the next stages' kernels follow on this stream
-                check(lib.latte_trainer_begin(*args))
+                # (a joint micro-batch: the video pass ran inside begin, these are the image pass's stages -- final slices)
+                check(begin(*args))
                 handles = []
                 for k in range(lib.latte_trainer_num_stages(self._h)):
                     check(lib.latte_trainer_backward_stage(self._h, k, stream_ptr()))
@@ -260,7 +308,7 @@ class LatteTrainer:
             check(load_library().latte_trainer_set_option(self._h, b"grad_accumulate", float(on)))
             self._accumulating = on
 
-    def backward_micro_batch(self, x_start, t, noise, y=None, drop_mask=None):
+    def backward_micro_batch(self, x_start, t, noise, y=None, drop_mask=None, y_image=None, image_drop_mask=None):
         """The next micro-batch of the accumulation window: ``forward_backward`` in assign mode for the first, in accumulate mode
         for the others; the window's last one takes the staged, all-reducing backward when there is a process group.
         -> (forward_backward's dict, True when the window is complete and ``optimizer_step`` is due)."""
@@ -269,7 +317,8 @@ class LatteTrainer:
         last = self.micro_step == self.gradient_accumulation_steps - 1
         self._set_accumulate(self.micro_step > 0)
         out = self.forward_backward(x_start, t, noise, y, drop_mask,
-                                    overlap_all_reduce=last and (_world(self.process_group) > 1 or self.always_staged))
+                                    overlap_all_reduce=last and (_world(self.process_group) > 1 or self.always_staged),
+                                    y_image=y_image, image_drop_mask=image_drop_mask)
         self.micro_step += 1
         if last:
             self.all_reduce_gradients()
@@ -343,7 +392,7 @@ class LatteTrainer:
         if hasattr(self.model, "mark_weights_dirty"):
             self.model.mark_weights_dirty()
 
-    def train_step(self, x_start, y=None, t=None, noise=None, drop_mask=None):
+    def train_step(self, x_start, y=None, t=None, noise=None, drop_mask=None, y_image=None, image_drop_mask=None):
         """train.py:197-236 for one micro-batch; the optimiser step runs after the ``gradient_accumulation_steps``-th of a window
         (``out["updated"]``; ``out["grad_norm"]`` only then)."""
         B = x_start.shape[0]
@@ -353,7 +402,10 @@ class LatteTrainer:
             noise = torch.randn_like(x_start, dtype=torch.float32, device=self.device)          # gd:733-734
         if drop_mask is None and self.model.extras == 2 and self.class_dropout_prob > 0:
             drop_mask = torch.rand(B, device=self.device) < self.class_dropout_prob              # latte.py:142-143
-        out, last = self.backward_micro_batch(x_start, t, noise, y, drop_mask)
+        if (image_drop_mask is None and y_image is not None and self.use_image_num and self.model.extras == 2
+                and self.class_dropout_prob > 0):
+            image_drop_mask = torch.rand(B, device=self.device) < self.class_dropout_prob        # latte_img.py:341-342: one coin per sample
+        out, last = self.backward_micro_batch(x_start, t, noise, y, drop_mask, y_image, image_drop_mask)
         out["updated"] = last
         if last:
             out["grad_norm"] = self.optimizer_step()

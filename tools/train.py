@@ -22,6 +22,11 @@ micro-batches per optimiser step (steps, logs and checkpoints count optimiser st
     and step a `TemporalRandomCrop(num_frames * frame_interval)` window and the flip coin from a seeded generator, the `num_frames` frames
     of `frame_indices` gathered on the host, one upload, one `latte_amd.video_transforms` launch for `dataset`'s pipeline
     (ffs | ucf101 | taichi | sky), then the encode above -- nothing of the augmentation is frozen into the stored data.
+Joint image-video training (train_with_img.py, the `*_img_train.yaml` configs): `use_image_num: N` appends N single frames to every
+clip and `model: LatteIMG-*` is mapped to the `Latte-*` preset of the same size (identical parameters; the checkpoint is sampled with
+it).  `frame_data_path` is a directory of single frames -- .npy latents [4, h, w] (scaled by 0.18215) or uint8 [H, W, 3] at the
+training image size, encoded with the VAE like the frame clips; label = file-name prefix, as for clips -- N of them drawn per sample
+from the micro-batch's seeded generator (a resumed run redraws the same ones); with `data_path: synthetic` they are synthetic too.
 """
 import argparse
 import glob
@@ -37,8 +42,8 @@ sys.path.insert(0, ROOT)
 
 import latte_amd  # noqa: E402
 from latte_amd import parallel  # noqa: E402
-from latte_amd.train_util import (checkpoint_step, data_seed, latest_checkpoint, rng_state, scheduled_lr, set_rng_state,  # noqa: E402
-                                  state_path)
+from latte_amd.train_util import (checkpoint_step, data_seed, draw_image_frames, latest_checkpoint, latte_preset_name,  # noqa: E402
+                                  rng_state, scheduled_lr, set_rng_state, state_path)
 
 
 def clip_label(path):
@@ -118,6 +123,37 @@ class LatentClips:
         return torch.stack(xs), torch.tensor(ys)
 
 
+class ImageFrames:
+    """The single frames of joint image-video training (`frame_data_path`, `use_image_num`): N per sample, drawn from the micro-batch's
+    seeded generator (its seed offset keeps the draw apart from the clips')."""
+    accum = 1             # micro-batches per optimiser step (main sets it)
+
+    def __init__(self, path, images, latent, rank, world, seed, num_classes):
+        self.synthetic = path in (None, "", "synthetic")
+        self.images, self.latent = int(images), int(latent)
+        self.rank, self.world, self.seed, self.num_classes = rank, world, seed, num_classes
+        self.files = [] if self.synthetic else sorted(glob.glob(os.path.join(path, "*.npy")))
+        if not self.synthetic and not self.files:
+            raise SystemExit(f"no .npy frames under {path}")
+        self.frames = bool(self.files) and np.load(self.files[0], mmap_mode="r").dtype == np.uint8
+        self.shape = (8 * latent, 8 * latent, 3) if self.frames else (4, latent, latent)
+
+    def batch(self, step, n, micro=0):
+        """-> (x [n, N, 4, h, w] float latents or [n, N, H, W, 3] uint8 frames, labels [n, N])"""
+        g = torch.Generator("cpu").manual_seed(data_seed(self.seed, step, micro, self.accum, self.rank, self.world) + 500009)
+        if self.synthetic:
+            x = torch.randn(n, self.images, *self.shape, generator=g)
+            return x, torch.randint(0, max(self.num_classes, 1), (n, self.images), generator=g)
+        idx = draw_image_frames(len(self.files), n, self.images, g)
+        xs = []
+        for i in idx.reshape(-1).tolist():
+            a = np.load(self.files[i])
+            assert a.shape == self.shape, f"{self.files[i]}: expected {self.shape}, got {a.shape}"
+            xs.append(torch.from_numpy(a) if self.frames else torch.from_numpy(a).float())
+        ys = torch.tensor([clip_label(self.files[i]) for i in idx.reshape(-1).tolist()]).reshape(n, self.images)
+        return torch.stack(xs).reshape(n, self.images, *self.shape), ys
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True)
@@ -139,6 +175,8 @@ def main():
     args.latent_size = args.image_size // 8
     nb = int(args.local_batch_size)
     args.max_batch = nb
+    use_image_num = int(args.get("use_image_num") or 0)
+    args.model = latte_preset_name(args.model)                # LatteIMG-* trains on the Latte-* preset of the same size
     model = latte_amd.get_models(args).to(device)
     if args.get("pretrained"):
         sd = latte_amd.find_model(args.pretrained)
@@ -146,7 +184,8 @@ def main():
         model.load_state_dict({**own, **{k: v for k, v in sd.items() if k in own}})          # train.py:109-122
     diffusion = latte_amd.create_diffusion(timestep_respacing="")                                # train.py:92
     trainer = latte_amd.LatteTrainer(model, diffusion, max_batch=nb, lr=float(args.learning_rate), clip_max_norm=float(args.clip_max_norm),
-                                     start_clip_iter=int(args.start_clip_iter), gradient_accumulation_steps=accum)
+                                     start_clip_iter=int(args.start_clip_iter), gradient_accumulation_steps=accum,
+                                     use_image_num=use_image_num)
     # Replicas were initialised from the shared seed; from here every rank draws its own timesteps, noise and label-dropout
     # masks, as the reference does (train.py:62 `seed = args.global_seed + rank`): a global batch covers world * nb independent
     # draws, not nb draws replicated world times.
@@ -193,8 +232,15 @@ def main():
         raw_transform, _ = video_transforms.get_transform(args)
     else:
         data = LatentClips(args.get("data_path"), int(args.num_frames), args.latent_size, rank, world, seed, int(args.get("num_classes") or 0))
+    images = None
+    if use_image_num:
+        frame_path = "synthetic" if args.get("data_path") in (None, "", "synthetic") else args.get("frame_data_path")
+        if not frame_path:
+            raise SystemExit("use_image_num: set frame_data_path (a directory of single frames)")
+        images = ImageFrames(frame_path, use_image_num, args.latent_size, rank, world, seed, int(args.get("num_classes") or 0))
+        images.accum = accum
     vae = None
-    if data.frames:                                           # train.py:94 (+ the encoder): frames -> latents on the GPU every step
+    if data.frames or (images is not None and images.frames):                                           # train.py:94 (+ the encoder): frames -> latents on the GPU every step
         if not args.get("pretrained_model_path"):
             raise SystemExit("data_path holds uint8 frame clips: set pretrained_model_path (its vae/ subfolder is the SD-VAE to encode with)")
         vae = latte_amd.AutoencoderKL.from_pretrained(args.pretrained_model_path, subfolder="vae", with_encoder=True).to(device)
@@ -217,9 +263,16 @@ def main():
                 gen = torch.Generator(device).manual_seed(data_seed(seed, step, micro, accum, rank, world))
                 if raw:                                       # per item (sizes differ): one upload, one transform launch, the encode
                     x = torch.cat([vae.encode_video_raw(fr.to(device).unsqueeze(0), raw_transform, flip=[fl], generator=gen) for fr, fl in x])
-                else:
+                elif data.frames:
                     x = vae.encode_video_uint8(x.to(device), generator=gen)
-            out = trainer.train_step(x.to(device), y=y.to(device) if int(args.extras) == 2 else None)
+            y_image = None
+            if images is not None:                            # train_with_img.py:214-221: N single frames behind every clip
+                xi, y_image = images.batch(step, nb, micro)
+                if images.frames:
+                    xi = vae.encode_video_uint8(xi.to(device), generator=gen)
+                x = torch.cat([x.to(device).float(), xi.to(device).float()], dim=1)
+                y_image = y_image.to(device) if int(args.extras) == 2 else None
+            out = trainer.train_step(x.to(device), y=y.to(device) if int(args.extras) == 2 else None, y_image=y_image)
             running += float(out["loss"].mean()) / accum      # (the reference's loss.item(), train.py:239; undivided terms)
         log_steps += 1
         if step % log_every == 0:
