@@ -352,7 +352,7 @@ int latte_debug_dma_probe(const void* src, long long* out, int mode, int waves, 
  *                     encoder reads the same layout (bit 0 mid block, 1 + i down block i, 12 + i / 21 + i the down-sampler of block i, 11
  *                     conv_out).  A decode / encode call reads the choice once, when it starts, and runs entirely on that mask
  * Anything else is refused (LATTE_ERR_INVALID).  Replaces the LATTE_* environment variables round 3 read at every launch; the
- * measurement ablations whose results are garbage (attention variants 7-10, 16-19) exist only in a LATTE_DEBUG_BUILD=1 library. */
+ * measurement ablations whose results are garbage (attention variants 7-10, 16-19) were removed; profiles/ keeps their logs. */
 int latte_debug_set_choice(const char* name, int value);
 
 /* T5 encoder kernels (csrc/t5.hip) one at a time.  A "pair" is two f16 arrays hi / lo of one shape: value = hi + lo / 2048.

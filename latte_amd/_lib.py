@@ -259,7 +259,7 @@ def load_library():
     global _lib
     if _lib is not None:
         return _lib
-    path = os.environ.get("LATTE_AMD_LIB") or LIB_PATH     # LATTE_AMD_LIB: the measurement build (latte_amd/build.py), tools only
+    path = os.environ.get("LATTE_AMD_LIB") or LIB_PATH     # LATTE_AMD_LIB: a compiler-flag A/B build (latte_amd/build.py: LATTE_BUILD_TAG), tools only
     if not os.path.exists(path):
         raise LatteError(
             f"{path} not found: build it with `python -m latte_amd.build` (hipcc, gfx950). "

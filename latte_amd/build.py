@@ -10,21 +10,16 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-DEBUG_BUILD = bool(os.environ.get("LATTE_DEBUG_BUILD"))
-# the measurement build (ablation instantiations, the kernels that were measured and not kept) lives beside the product library and is only
-# ever loaded when LATTE_AMD_LIB names it (tools/, never tests or bench defaults)
-OBJ = os.path.join(HERE, "build_dbg" if DEBUG_BUILD else "build")
+OBJ = os.path.join(HERE, "build")
 LIBDIR = os.path.join(HERE, "lib")
-LIB = os.path.join(LIBDIR, "liblatte_amd_dbg.so" if DEBUG_BUILD else "liblatte_amd.so")
+LIB = os.path.join(LIBDIR, "liblatte_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
 SOURCES = ["gemm.hip", "gemm_pw.hip", "gemm_tn.hip", "train.hip", "train_fin.hip", "train_attn.hip", "attention.hip", "qkv_attn.hip", "pointwise.hip", "debug.hip", "vae.hip", "t5.hip", "video.hip", "engine.cpp", "train_engine.cpp", "vae_engine.cpp", "t2v_engine.cpp", "t5_engine.cpp", "weight_store.cpp", "schedule.cpp"]
 COMMON = ["--offload-arch=" + ARCH, "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
-if DEBUG_BUILD:   # measurement build: main-loop / epilogue ablation instantiations of the GEMM
-    COMMON.append("-DLATTE_GEMM_ABLATE")
 # compiler-flag A/B builds (measurement only): LATTE_BUILD_TAG=<tag> LATTE_EXTRA_HIPFLAGS="<flags>" builds lib/liblatte_amd_<tag>.so
-# from objects under build_<tag>/ with the extra flags on the .hip files; loaded through LATTE_AMD_LIB like the measurement build
+# from objects under build_<tag>/ with the extra flags on the .hip files; loaded through LATTE_AMD_LIB (tools/flag_ab_probe.py)
 BUILD_TAG = os.environ.get("LATTE_BUILD_TAG", "")
 EXTRA_HIP = os.environ.get("LATTE_EXTRA_HIPFLAGS", "").split() if BUILD_TAG else []
 if BUILD_TAG:

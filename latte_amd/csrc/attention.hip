@@ -416,7 +416,7 @@ __global__ void __launch_bounds__(256, 2) attn_full_kernel(AttnArgs a) {
 // Online softmax across blocks: running max on the raw scores (the scale is positive), alpha = exp2((m_old - m_new) c).
 // The V^T fragments come from the transpose read in its inline-assembly form: in front of the builtin hipcc drains every LDS
 // DMA in flight (mfma_util.h: lds_tr16_asm), which would serialise the ring again.
-template <int HD, int DT, int ABL = 0, bool LO8 = false>
+template <int HD, int DT, bool LO8 = false>
 __global__ void __launch_bounds__(512) attn_stream_kernel(AttnArgs a) {
   constexpr int KS = (HD + 31) / 32, DF = (HD + 15) / 16, NCH = HD / 8;
   constexpr int RP = 160, KB = 128, NKT = KB / 16;     // keys per block, 16-key tiles per block
@@ -499,15 +499,6 @@ __global__ void __launch_bounds__(512) attn_stream_kernel(AttnArgs a) {
                                          (__attribute__((address_space(3))) void*)(dst + (wave * 5 + j) * 1024), 16, 0, 0);
     }
   };
-  // (ABL 11, measurement build: the five pieces of block kb + 2 spread over the MFMA phases of block kb instead of issued together behind the
-  // barrier -- both waves of a SIMD are then not held at their DMA issues at the same time)
-  auto stage_piece = [&](int kb, int slot, int j) __attribute__((always_inline)) {
-    char* dst = smem_attn + slot * BLK;
-    const char* blk = (const char*)(qkv_h + (size_t)(base + (int64_t)kb * KB * a.row_stride) * ld);
-    const unsigned off = (ragged && kb == nkb - 1) ? lane_offset(j, kb) : voff[j];
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(blk + off),
-                                     (__attribute__((address_space(3))) void*)(dst + (wave * 5 + j) * 1024), 16, 0, 0);
-  };
   stage(0, 0);
   if (nkb > 1) stage(1, 1);
 
@@ -534,9 +525,6 @@ __global__ void __launch_bounds__(512) attn_stream_kernel(AttnArgs a) {
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
       if (kt + 2 < NKT) load_k(kt + 2, kf[(kt + 2) & 3]);
-      if constexpr (ABL == 11) {
-        if ((kt & 1) == 1 && kb + 2 < nkb) stage_piece(kb + 2, (kb + 2) % 3, kt >> 1);   // pieces 0..3 behind key tiles 1, 3, 5, 7
-      }
       __builtin_amdgcn_sched_barrier(0);
       st[0][kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
       st[1][kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -574,25 +562,6 @@ __global__ void __launch_bounds__(512) attn_stream_kernel(AttnArgs a) {
       typedef float f32x2 __attribute__((ext_vector_type(2)));
       const f32x2 c2 = {c, c}, nm2 = {nm, nm};
       f32x2 ls2 = {0.f, 0.f};
-      float ls;
-      if constexpr (ABL == 10) {   // single-issue fp32 forms only (no v_pk_*_f32 beside the partner wave's MFMAs)
-        float l0 = 0.f, l1 = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-          for (int r = 0; r < 4; r += 2) {
-            float e0, e1, p0, p1;
-            asm("v_fma_f32 %0, %1, %2, %3" : "=v"(e0) : "v"(st[gq][kt][r]), "v"(c), "v"(nm));
-            asm("v_fma_f32 %0, %1, %2, %3" : "=v"(e1) : "v"(st[gq][kt][r + 1]), "v"(c), "v"(nm));
-            p0 = __builtin_amdgcn_exp2f(e0);
-            p1 = __builtin_amdgcn_exp2f(e1);
-            st[gq][kt][r] = p0;
-            st[gq][kt][r + 1] = p1;
-            l0 += p0;
-            l0 += p1;
-          }
-        ls = l0 + l1;
-      } else {
 #pragma unroll
       for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
@@ -603,8 +572,7 @@ __global__ void __launch_bounds__(512) attn_stream_kernel(AttnArgs a) {
           st[gq][kt][r + 1] = p.y;
           ls2 += p;
         }
-      ls = ls2.x + ls2.y;
-      }
+      float ls = ls2.x + ls2.y;
       ls += __shfl_xor(ls, 16, 64);
       ls += __shfl_xor(ls, 32, 64);
       l_run[gq] = l_run[gq] * alpha + ls;
@@ -618,7 +586,6 @@ __global__ void __launch_bounds__(512) attn_stream_kernel(AttnArgs a) {
       }
     }
   };
-  auto softmax_sel = [&](int kb) __attribute__((always_inline)) { if constexpr (ABL != 8) softmax(kb); };   // (ABL: measurement ablations, results garbage)
   // O^T += V^T P^T of block kb (MFMA phase 2); k-slot (8g + i) <-> key 32 ks2 + (i < 4 ? 4g + i : 16 + 4g + i - 4).  V^T
   // fragments one 32-key step ahead; the reads are inline assembly, so their completion is counted here: 2 DF reads per step
   auto weighted_sum = [&](int kb) __attribute__((always_inline)) {
@@ -643,9 +610,6 @@ __global__ void __launch_bounds__(512) attn_stream_kernel(AttnArgs a) {
       } else {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       }
-      if constexpr (ABL == 11) {
-        if (ks2 == 1 && kb + 2 < nkb) stage_piece(kb + 2, (kb + 2) % 3, 4);
-      }
       __builtin_amdgcn_sched_barrier(0);
       u32x4 pb[2];
 #pragma unroll
@@ -665,22 +629,15 @@ __global__ void __launch_bounds__(512) attn_stream_kernel(AttnArgs a) {
 
   // Interval kb: own DMA of block kb landed (block kb + 1 may stay in flight), then everybody's; the barrier also retires every
   // read of block kb - 1, whose slot takes block kb + 2.  (Running waves 4-7 one phase behind waves 0-3 -- softmax of block
-  // kb - 1 under the other wave's score MFMAs -- was built and measured: 250 against 242 us, no gain; ABL: measurement ablations.)
+  // kb - 1 under the other wave's score MFMAs -- was built and measured: 250 against 242 us, no gain.)
   for (int kb = 0; kb < nkb; ++kb) {
-    if constexpr (ABL != 9) {
-      if (kb + 1 < nkb) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
-    if constexpr (ABL != 7 && ABL != 11) {
-      if (kb + 2 < nkb) stage(kb + 2, (kb + 2) % 3);
-    }
-    if constexpr (ABL == 11) {   // (a wave without queries still has to bring its pieces)
-      if (!wave_active && kb + 2 < nkb) stage(kb + 2, (kb + 2) % 3);
-    }
+    if (kb + 1 < nkb) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    if (kb + 2 < nkb) stage(kb + 2, (kb + 2) % 3);
     if (wave_active) {
       scores(kb);
-      softmax_sel(kb);
+      softmax(kb);
       weighted_sum(kb);
     }
   }
@@ -761,7 +718,7 @@ constexpr int STREAM64_LDS = S64_NS * (S64_KIMG + S64_VIMG) + 256;
 
 // NG = 32-query groups per wave: 2 = the one-wave-per-SIMD form described above (4 waves); 1 = the SAME pipeline on 8 waves x 32 queries, two
 // waves per SIMD (everything fits the architectural registers: the S MFMAs are the compiler's) -- `attn_variant` 13.
-template <int HD, int DT, bool LO8 = false, int ABL = 0, int NG = 2>
+template <int HD, int DT, bool LO8 = false, int NG = 2>
 __global__ void __launch_bounds__(512 / NG) attn_stream64_kernel(AttnArgs a) {
   constexpr int NWV = 8 / NG;                    // waves
   constexpr int NPC = 19, NPW = (NPC + NWV - 1) / NWV;   // DMA pieces per issue group (9 K + 10 V), per wave
@@ -911,7 +868,7 @@ __global__ void __launch_bounds__(512 / NG) attn_stream64_kernel(AttnArgs a) {
       for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
-          if (ABL != 7 && dma != nullptr && g == 0) {   // (the prologue call passes nullptr: compile-time after inlining)
+          if (dma != nullptr && g == 0) {   // (the prologue call passes nullptr: compile-time after inlining)
             if constexpr (NG == 2) {
               if (ks == 1 && t == 0) stage_piece(*dma, 0);   // pieces 0, 1 of the group behind 4 / 12 MFMAs of the phase
               if (ks == 3 && t == 0) stage_piece(*dma, 1);
@@ -1017,13 +974,12 @@ __global__ void __launch_bounds__(512 / NG) attn_stream64_kernel(AttnArgs a) {
   // MASKED = block i+1 may be ragged: the steady-state instance (MORE, not MASKED) has no branch between its MFMAs.
   auto iteration = [&](int i, auto more, auto masked) __attribute__((always_inline)) {
     constexpr bool MORE = decltype(more)::value;
-    if constexpr (ABL != 9) {   // G(i) landed; G(i+1), G(i+2) may stay in flight
-      if constexpr (NG == 2) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    }
-    if constexpr (ABL != 9) __builtin_amdgcn_s_barrier();
+    // G(i) landed; G(i+1), G(i+2) may stay in flight
+    if constexpr (NG == 2) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
     if (!wave_active) {
-      if constexpr (ABL != 7) stage_group(i + 4, i + 3);
+      stage_group(i + 4, i + 3);
       return;
     }
     const Group gr = make_group(i + 4, i + 3);
@@ -1042,12 +998,10 @@ __global__ void __launch_bounds__(512 / NG) attn_stream64_kernel(AttnArgs a) {
     }
     if constexpr (MORE) {
       scores(i + 1, &gr);
-      if constexpr (ABL != 8) softmax_max(i + 1, masked);
+      softmax_max(i + 1, masked);
     } else {
-      if constexpr (ABL != 7) {
-        stage_piece(gr, 0);
-        if constexpr (NG == 2) stage_piece(gr, 1);
-      }
+      stage_piece(gr, 0);
+      if constexpr (NG == 2) stage_piece(gr, 1);
     }
 #pragma unroll
     for (int step = 0; step < 2 * NT; ++step) {
@@ -1060,12 +1014,10 @@ __global__ void __launch_bounds__(512 / NG) attn_stream64_kernel(AttnArgs a) {
       } else {
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vlo[cur][0]), "+v"(vlo[cur][1]), "+v"(vlo[cur][2]), "+v"(vhi[cur][0]), "+v"(vhi[cur][1]), "+v"(vhi[cur][2]) :: "memory");
       }
-      if constexpr (ABL != 7) {   // the group's remaining pieces between the k-steps
-        if constexpr (NG == 2) {
-          if (step < 3) stage_piece(gr, 2 + step);
-        } else {
-          if (step == 0 || step == 2) stage_piece(gr, 1 + step / 2);
-        }
+      if constexpr (NG == 2) {   // the group's remaining pieces between the k-steps
+        if (step < 3) stage_piece(gr, 2 + step);
+      } else {
+        if (step == 0 || step == 2) stage_piece(gr, 1 + step / 2);
       }
       const int t = step >> 1, s2 = step & 1;
 #pragma unroll
@@ -1077,7 +1029,7 @@ __global__ void __launch_bounds__(512 / NG) attn_stream64_kernel(AttnArgs a) {
           o[g][d] = mfma32<DT>(vfrag, pb, o[g][d]);
         }
       }
-      if constexpr (MORE && ABL != 8) {
+      if constexpr (MORE) {
         if (s2 == 1) softmax_exp(t);   // P(i)'s tile t has been read: P(i+1)'s tile t takes its registers
       }
     }
@@ -1369,6 +1321,33 @@ __global__ void __launch_bounds__(256) attn_small_kernel(AttnArgs a) {
   }
 }
 
+// the self-attention kernel of one (head_dim, dtype, output form); small / stream / full as launch_attention decided them
+template <int HD, int DT, bool LO8>
+int launch_self(const AttnArgs& a, bool small, bool stream, bool full, dim3 grid, dim3 block, hipStream_t st) {
+  constexpr int FULL_LDS = 2 * 256 * 160, STREAM_LDS = 3 * 2 * 128 * 160;
+  if (stream) {
+    if constexpr (HD == 72 && !LO8) {   // the 32 x 32 x 16 streaming kernel ("attn_variant" 12 / 13)
+      if (a.variant == 13) return launch_lds<attn_stream64_kernel<72, DT, false, 1>>(grid, dim3(512), STREAM64_LDS, st, a);
+      if (a.variant == 12) return launch_lds<attn_stream64_kernel<72, DT>>(grid, dim3(256), STREAM64_LDS, st, a);
+    }
+    return launch_lds<attn_stream_kernel<HD, DT, LO8>>(grid, block, STREAM_LDS, st, a);
+  }
+  if (full) return launch_lds<attn_full_kernel<HD, DT, LO8>>(grid, block, FULL_LDS, st, a);
+  if (small) hipLaunchKernelGGL((attn_small_kernel<HD, DT, LO8>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((attn_flash_kernel<HD, DT, false, LO8>), grid, block, 0, st, a);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+
+template <int HD, int DT>
+int launch_cross(const AttnArgs& a, bool panel, dim3 grid, dim3 block, hipStream_t st) {
+  constexpr int CROSS_LDS = 2 * 128 * 160 + 128 * 4;
+  if (panel) return launch_lds<attn_cross_kernel<HD, DT>>(grid, block, CROSS_LDS, st, a);
+  hipLaunchKernelGGL((attn_flash_kernel<HD, DT, true>), grid, block, 0, st, a);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+
 }  // namespace
 
 int launch_attention(const AttnArgs& a_in, int dtype, hipStream_t st) {
@@ -1379,105 +1358,29 @@ int launch_attention(const AttnArgs& a_in, int dtype, hipStream_t st) {
   AttnArgs a = a_in;
   // kernel-choice override of the A/B tests (latte_debug_set_choice("attn_variant", v), include/latte_amd_debug.h): 1 = the generic
   // flash kernel for every L > 16, 5 = the streaming kernel for 128 < L <= 256 as well.  Every choice computes the same function;
-  // the measurement ablations that do not (7-9: no softmax / no waits / no staging) exist in the LATTE_DEBUG_BUILD library only.
+  // the measurement ablations that did not (7-9: no softmax / no waits / no staging) are gone and set_debug_choice refuses them.
   if (const int ov = debug_choice(DBG_ATTN_VARIANT)) a.variant = ov;
   const bool full = a.L > 128 && a.L <= 256 && a.variant != 1 && a.variant != 5;
   // L > 256: the streaming kernel (8 waves, 256 queries, ring of 128-key blocks); its per-lane source offsets are 32-bit: 128 rows
   // of a block must span less than 2 GiB, otherwise the generic flash kernel runs
   const bool stream_ok = (int64_t)a.row_stride * 3 * a.D * 2 * 128 < (1ll << 31);
   const bool stream = stream_ok && ((a.L > 256 && a.variant != 1) || (a.L > 128 && a.variant == 5));
-  constexpr int FULL_LDS = 2 * 256 * 160, STREAM_LDS = 3 * 2 * 128 * 160;
   dim3 block(stream ? 512 : 256);
   dim3 grid = small ? dim3((a.num_seq * a.heads + 3) / 4)
                     : (full && !stream ? dim3(a.num_seq * a.heads)
                             : (stream ? dim3(a.num_seq * a.heads * ((a.L + 255) / 256)) : dim3(a.num_seq * a.heads * ((a.L + 63) / 64))));
-#ifdef LATTE_GEMM_ABLATE
-#define ATTN_STREAM_ABLATIONS(HD, DT)                                                                         \
-      if (((a.variant >= 7 && a.variant <= 10) || a.variant == 16) && HD == 72 && DT == LATTE_DTYPE_F16) {                            \
-        static std::atomic<uint64_t> attr_done_a[5];                                                          \
-        const void* fn_ = a.variant == 7 ? (const void*)attn_stream_kernel<72, LATTE_DTYPE_F16, 7>            \
-                          : a.variant == 8 ? (const void*)attn_stream_kernel<72, LATTE_DTYPE_F16, 8>          \
-                          : a.variant == 9 ? (const void*)attn_stream_kernel<72, LATTE_DTYPE_F16, 9>          \
-                          : a.variant == 10 ? (const void*)attn_stream_kernel<72, LATTE_DTYPE_F16, 10>        \
-                                           : (const void*)attn_stream_kernel<72, LATTE_DTYPE_F16, 11>;        \
-        if (int rc_ = ensure_dynamic_lds(fn_, STREAM_LDS, attr_done_a[a.variant == 16 ? 4 : a.variant - 7])) return rc_;            \
-        void* args_[] = {(void*)&a};                                                                          \
-        LATTE_HIP(hipLaunchKernel(fn_, grid, block, args_, STREAM_LDS, st));                                  \
-      } else
-#define ATTN_STREAM64_ABLATIONS(DT)                                                                           \
-      if (a.variant >= 17 && a.variant <= 19 && DT == LATTE_DTYPE_F16) {                                      \
-        static std::atomic<uint64_t> attr_done_b[3];                                                          \
-        const void* fn_ = a.variant == 17 ? (const void*)attn_stream64_kernel<72, LATTE_DTYPE_F16, false, 7>  \
-                          : a.variant == 18 ? (const void*)attn_stream64_kernel<72, LATTE_DTYPE_F16, false, 8>\
-                                            : (const void*)attn_stream64_kernel<72, LATTE_DTYPE_F16, false, 9>;\
-        if (int rc_ = ensure_dynamic_lds(fn_, STREAM64_LDS, attr_done_b[a.variant - 17])) return rc_;         \
-        void* args_[] = {(void*)&a};                                                                          \
-        LATTE_HIP(hipLaunchKernel(fn_, grid, dim3(256), args_, STREAM64_LDS, st));                            \
-      } else
-#else
-#define ATTN_STREAM_ABLATIONS(HD, DT)
-#define ATTN_STREAM64_ABLATIONS(DT)
-#endif
-#define ATTN_LAUNCH(HD, DT)                                                                                   \
-  do {                                                                                                        \
-    if (small)                                                                                                \
-      hipLaunchKernelGGL((attn_small_kernel<HD, DT>), grid, block, 0, st, a);                                 \
-    else if (stream) {                                                                                        \
-      static std::atomic<uint64_t> attr_done_s{0};                                                            \
-      if (int rc_ = ensure_dynamic_lds((const void*)attn_stream_kernel<HD, DT>, STREAM_LDS, attr_done_s)) return rc_; \
-      ATTN_STREAM_ABLATIONS(HD, DT)                                                                           \
-      ATTN_STREAM64_ABLATIONS(DT)                                                                             \
-      if (HD == 72 && a.variant == 13) {                                                                      \
-        static std::atomic<uint64_t> attr_done_s64b{0};                                                       \
-        if (int rc_ = ensure_dynamic_lds((const void*)attn_stream64_kernel<72, DT, false, 0, 1>, STREAM64_LDS, attr_done_s64b)) return rc_; \
-        hipLaunchKernelGGL((attn_stream64_kernel<72, DT, false, 0, 1>), grid, dim3(512), STREAM64_LDS, st, a); \
-      } else if (HD == 72 && a.variant == 12) {                                                               \
-        static std::atomic<uint64_t> attr_done_s64{0};                                                        \
-        if (int rc_ = ensure_dynamic_lds((const void*)attn_stream64_kernel<72, DT>, STREAM64_LDS, attr_done_s64)) return rc_; \
-        hipLaunchKernelGGL((attn_stream64_kernel<72, DT>), grid, dim3(256), STREAM64_LDS, st, a);             \
-      } else                                                                                                  \
-      hipLaunchKernelGGL((attn_stream_kernel<HD, DT>), grid, block, STREAM_LDS, st, a);                       \
-    } else if (full) {                                                                                          \
-      static std::atomic<uint64_t> attr_done{0};                                                              \
-      if (int rc_ = ensure_dynamic_lds((const void*)attn_full_kernel<HD, DT>, FULL_LDS, attr_done)) return rc_; \
-      hipLaunchKernelGGL((attn_full_kernel<HD, DT>), grid, block, FULL_LDS, st, a);                           \
-    } else                                                                                                    \
-      hipLaunchKernelGGL((attn_flash_kernel<HD, DT>), grid, block, 0, st, a);                                 \
-  } while (0)
   if (a.out8) {   // f16 + fp8 remainder output (guided calls; AttnArgs::out8)
     if (dtype != LATTE_DTYPE_F16) return fail(LATTE_ERR_INVALID, "attention: the fp8-remainder output is f16 only");
-#define ATTN_LAUNCH8(HD)                                                                                                        \
-  do {                                                                                                                        \
-    if (small)                                                                                                                \
-      hipLaunchKernelGGL((attn_small_kernel<HD, LATTE_DTYPE_F16, true>), grid, block, 0, st, a);                              \
-    else if (stream) {                                                                                                        \
-      static std::atomic<uint64_t> attr_done_s8{0};                                                                           \
-      if (int rc_ = ensure_dynamic_lds((const void*)attn_stream_kernel<HD, LATTE_DTYPE_F16, 0, true>, STREAM_LDS, attr_done_s8)) return rc_; \
-      hipLaunchKernelGGL((attn_stream_kernel<HD, LATTE_DTYPE_F16, 0, true>), grid, block, STREAM_LDS, st, a);                 \
-    } else if (full) {                                                                                                        \
-      static std::atomic<uint64_t> attr_done8{0};                                                                             \
-      if (int rc_ = ensure_dynamic_lds((const void*)attn_full_kernel<HD, LATTE_DTYPE_F16, true>, FULL_LDS, attr_done8)) return rc_; \
-      hipLaunchKernelGGL((attn_full_kernel<HD, LATTE_DTYPE_F16, true>), grid, block, FULL_LDS, st, a);                        \
-    } else                                                                                                                    \
-      hipLaunchKernelGGL((attn_flash_kernel<HD, LATTE_DTYPE_F16, false, true>), grid, block, 0, st, a);                       \
-  } while (0)
-    if (a.hd == 64) ATTN_LAUNCH8(64); else ATTN_LAUNCH8(72);
-#undef ATTN_LAUNCH8
-    LATTE_HIP(hipGetLastError());
-    return LATTE_OK;
+    return a.hd == 64 ? launch_self<64, LATTE_DTYPE_F16, true>(a, small, stream, full, grid, block, st)
+                      : launch_self<72, LATTE_DTYPE_F16, true>(a, small, stream, full, grid, block, st);
   }
-  if (dtype == LATTE_DTYPE_BF16) {
-    if (a.hd == 64) ATTN_LAUNCH(64, LATTE_DTYPE_BF16); else ATTN_LAUNCH(72, LATTE_DTYPE_BF16);
-  } else if (dtype == LATTE_DTYPE_F16) {
-    if (a.hd == 64) ATTN_LAUNCH(64, LATTE_DTYPE_F16); else ATTN_LAUNCH(72, LATTE_DTYPE_F16);
-  } else {
-    return fail(LATTE_ERR_INVALID, "attention: unknown dtype");
-  }
-#undef ATTN_LAUNCH
-#undef ATTN_STREAM_ABLATIONS
-#undef ATTN_STREAM64_ABLATIONS
-  LATTE_HIP(hipGetLastError());
-  return LATTE_OK;
+  if (dtype == LATTE_DTYPE_BF16)
+    return a.hd == 64 ? launch_self<64, LATTE_DTYPE_BF16, false>(a, small, stream, full, grid, block, st)
+                      : launch_self<72, LATTE_DTYPE_BF16, false>(a, small, stream, full, grid, block, st);
+  if (dtype == LATTE_DTYPE_F16)
+    return a.hd == 64 ? launch_self<64, LATTE_DTYPE_F16, false>(a, small, stream, full, grid, block, st)
+                      : launch_self<72, LATTE_DTYPE_F16, false>(a, small, stream, full, grid, block, st);
+  return fail(LATTE_ERR_INVALID, "attention: unknown dtype");
 }
 
 int launch_cross_attention(const AttnArgs& a, int dtype, hipStream_t st) {
@@ -1486,27 +1389,12 @@ int launch_cross_attention(const AttnArgs& a, int dtype, hipStream_t st) {
   // Lk <= 128 keys (Latte-1: 120) and at least half a 256-query block per sequence: the whole-panel kernel; latte_debug_set_choice("xattn_flash", 1)
   // keeps the generic flash kernel (tests, A/B)
   const bool panel = a.Lk <= 128 && a.L >= 128 && debug_choice(DBG_XATTN_FLASH) != 1;
-  constexpr int CROSS_LDS = 2 * 128 * 160 + 128 * 4;
   dim3 block(panel ? 512 : 256), grid(panel ? a.num_seq * a.heads * ((a.L + 255) / 256) : a.num_seq * a.heads * ((a.L + 63) / 64));
-#define XATTN_LAUNCH(HD, DT)                                                                                  \
-  do {                                                                                                        \
-    if (panel) {                                                                                              \
-      static std::atomic<uint64_t> attr_done_x{0};                                                            \
-      if (int rc_ = ensure_dynamic_lds((const void*)attn_cross_kernel<HD, DT>, CROSS_LDS, attr_done_x)) return rc_; \
-      hipLaunchKernelGGL((attn_cross_kernel<HD, DT>), grid, block, CROSS_LDS, st, a);                         \
-    } else                                                                                                    \
-      hipLaunchKernelGGL((attn_flash_kernel<HD, DT, true>), grid, block, 0, st, a);                           \
-  } while (0)
-  if (dtype == LATTE_DTYPE_BF16) {
-    if (a.hd == 64) XATTN_LAUNCH(64, LATTE_DTYPE_BF16); else XATTN_LAUNCH(72, LATTE_DTYPE_BF16);
-  } else if (dtype == LATTE_DTYPE_F16) {
-    if (a.hd == 64) XATTN_LAUNCH(64, LATTE_DTYPE_F16); else XATTN_LAUNCH(72, LATTE_DTYPE_F16);
-  } else {
-    return fail(LATTE_ERR_INVALID, "cross attention: unknown dtype");
-  }
-#undef XATTN_LAUNCH
-  LATTE_HIP(hipGetLastError());
-  return LATTE_OK;
+  if (dtype == LATTE_DTYPE_BF16)
+    return a.hd == 64 ? launch_cross<64, LATTE_DTYPE_BF16>(a, panel, grid, block, st) : launch_cross<72, LATTE_DTYPE_BF16>(a, panel, grid, block, st);
+  if (dtype == LATTE_DTYPE_F16)
+    return a.hd == 64 ? launch_cross<64, LATTE_DTYPE_F16>(a, panel, grid, block, st) : launch_cross<72, LATTE_DTYPE_F16>(a, panel, grid, block, st);
+  return fail(LATTE_ERR_INVALID, "cross attention: unknown dtype");
 }
 
 }  // namespace latte

@@ -53,6 +53,20 @@ inline int ensure_dynamic_lds(const void* fn, int bytes, std::atomic<uint64_t>& 
   }
   return LATTE_OK;
 }
+// Launch of a kernel that opts in to more dynamic LDS than the 64 KB default: one opt-in flag per kernel instantiation, so every launch site
+// of a kernel shares it (and must ask for the same attribute value).  lds_attr is the attribute value, lds_bytes what this launch takes.
+template <auto Kernel, typename... Args>
+int launch_lds_max(dim3 grid, dim3 block, int lds_attr, int lds_bytes, hipStream_t st, const Args&... args) {
+  static std::atomic<uint64_t> attr_done{0};
+  if (int rc = ensure_dynamic_lds((const void*)Kernel, lds_attr, attr_done)) return rc;
+  hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, st, args...);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+template <auto Kernel, typename... Args>
+int launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t st, const Args&... args) {
+  return launch_lds_max<Kernel>(grid, block, lds_bytes, lds_bytes, st, args...);
+}
 
 // 16-bit storage element (bf16 or f16 bit pattern depending on the engine's compute dtype)
 typedef uint16_t half_t;
@@ -68,17 +82,8 @@ enum GemmEpi : int {
   EPI_BIAS_GELU_H16 = 1,  // out(half) = gelu_tanh(acc + bias)
   EPI_GATE_RES_F32 = 2,   // res(fp32)[m,n] += gate[sample(m)][n] * (acc + bias)
   EPI_BIAS_F32 = 3,       // out(fp32) = acc + bias
-  EPI_ABLATE_NOSTORE = 4, // measurement only: bias add, nothing written (persistent kernel only)
+  // (4 and 6-12 were the epilogues of the removed measurement build; the values below are passed as integers and keep theirs)
   EPI_BIAS_RES_H16 = 5,   // out(half) = acc + bias + res(half)[m,n]   (plain kernel only; VAE attention out-proj)
-  // measurement only, persistent kernel only, nothing written: main-loop ablations (results are garbage)
-  EPI_ABLATE_NODMA = 6,     // no operand DMA inside the K loop
-  EPI_ABLATE_NOLDSREAD = 7, // fragments read from LDS once, then reused
-  EPI_ABLATE_NOMFMA = 8,    // DMA + fragment reads, no MFMA
-  EPI_ABLATE_HOTSRC = 9,    // every K tile's DMA reads K tile 0 again (cache-hot source)
-  EPI_ABLATE_DMA_A = 10,    // only the A operand is DMA'd in the loop
-  EPI_ABLATE_DMA_B = 11,    // only the B operand is DMA'd in the loop
-  EPI_ABLATE_TRACE = 12,    // full loop, no stores; workgroup 0 writes per-wave phase times (s_memtime ticks) to `out`:
-                            // int64 [8 waves][8] = {L, barrier-1 wait, C issue, vmcnt wait, barrier-2 wait, DMA issue, total, K tiles}
   // training step (round 6; rolling 12-wave kernel only, gemm_pw.hip -- launch_gemm_pw): the GELU passes of the MLP inside the GEMMs
   EPI_BIAS_GELU_DUAL_H16 = 13,  // out(half) = u = acc + bias AND aux(half) = gelu_tanh(u) (of the ROUNDED u: what a separate GELU pass reads)
   EPI_DGELU_H16 = 14,           // out(half) = (acc + bias) * gelu_tanh'(aux(half)[m,n])     (the fc2 input-gradient GEMM: du = dh gelu'(u))
@@ -95,7 +100,7 @@ struct GemmArgs {
   int rows_per_sample;
   int stagger;        // persistent kernel: number of start cohorts (0/1 = none); cohort c sleeps c/stagger of a tile time
   int group_m;        // persistent kernel: tile rows walked together by the grouped tile order (0 = 8)
-  int rmw_mode;       // measurement build only: look-ahead depth + 16 * non-temporal loads of the read-modify-write epilogue
+  int rmw_mode;       // unused slot (read by the removed measurement build only): keeps the kernel-argument offsets
   int tag;            // call site of a gated-residual GEMM (0 = attention out-projection, 1 = fc2): separate kernel symbols
   int k_chunk;        // plain kernels (variants 1-3) only: > 0 splits the contraction, grid.y = ceil(K / k_chunk) partial products
   long split_stride;  // ... written to (float*)out + blockIdx.y * split_stride (use EPI_BIAS_F32 with a zero bias)

@@ -134,12 +134,8 @@ extern "C" {
 // out: int64 [8 waves][2] = {ticks spent issuing, ticks until landed}, each summed over `reps` bursts of 16 instructions.
 int latte_debug_dma_probe(const void* src_1gib_window, long long* out, int mode, int waves, int reps, void* stream) {
   if (waves < 1 || waves > 8) return fail(LATTE_ERR_INVALID, "dma_probe: waves must be 1..8");
-  static std::atomic<uint64_t> attr_done{0};
-  if (int rc_ = ensure_dynamic_lds((const void*)dma_probe_kernel, 8 * 16384, attr_done)) return rc_;
-  hipLaunchKernelGGL(dma_probe_kernel, dim3(256), dim3(64 * waves), 8 * 16384, (hipStream_t)stream, (const char*)src_1gib_window,
-                     out, mode, reps);
-  LATTE_HIP(hipGetLastError());
-  return LATTE_OK;
+  return launch_lds<dma_probe_kernel>(dim3(256), dim3(64 * waves), 8 * 16384, (hipStream_t)stream, (const char*)src_1gib_window, out, mode,
+                                      reps);
 }
 
 int latte_debug_gemm(const void* A, const void* W, const float* bias, void* out, const float* gate, int M, int N, int K,

@@ -32,9 +32,6 @@ int set_debug_choice(const char* name, int value) {
       bool ok = value == 0;
       for (int k = 0; k < 4; ++k) ok = ok || (allowed[i][k] != 0 && value == allowed[i][k]);
       ok = ok || (i == DBG_VAE_SPLIT && (value >> 24) == 1);   // (1 << 24) | pass mask (vae_engine.cpp: vae_split_mask)
-#ifdef LATTE_GEMM_ABLATE
-      ok = ok || (i == DBG_ATTN_VARIANT && value >= 7 && value <= 19);   // measurement build: attn_stream ablations (results garbage)
-#endif
       if (!ok) return -1;
       g_debug_choice[i].store(value, std::memory_order_relaxed);
       return 0;
@@ -568,9 +565,6 @@ int latte_engine_set_option(latte_engine_t* e, const char* name, int64_t value) 
   for (int gi = 0; gi < 4; ++gi) {
     static const char* names[4] = {"gemm_variant_qkv", "gemm_variant_proj", "gemm_variant_fc1", "gemm_variant_fc2"};
     if (k == names[gi]) {
-#ifdef LATTE_GEMM_ABLATE   // measurement build: 17 = the two-accumulator-set kernel of the gated GEMMs (gemm_pw.hip)
-      if (value == 17 && (gi == 1 || gi == 3)) { e->gemm_variant_of[gi] = 17; return LATTE_OK; }
-#endif
       if (value < 0 || (value > 13 && value != 18 && value != 19)) return fail(LATTE_ERR_INVALID, "gemm_variant_*: must be 0..13, 18 or 19");
       e->gemm_variant_of[gi] = (int)value;
       return LATTE_OK;

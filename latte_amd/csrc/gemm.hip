@@ -15,8 +15,6 @@
 //    and float4 bias / gate loads in the epilogue;
 //  * XCD-aware, grouped block->tile mapping so that co-resident tiles of one XCD share A/W panels in
 //    that XCD's private L2.
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 #include "common.h"
@@ -31,9 +29,7 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& g, const f32x4& a
   const float4 b4 = *(const float4*)(g.bias + n);
   float v0 = a[0] + b4.x, v1 = a[1] + b4.y, v2 = a[2] + b4.z, v3 = a[3] + b4.w;
   const size_t o = (size_t)m * g.N + n;
-  if constexpr (EPI == EPI_ABLATE_NOSTORE || EPI >= EPI_ABLATE_NODMA) {
-    asm volatile("" ::"v"(v0), "v"(v1), "v"(v2), "v"(v3));
-  } else if constexpr (EPI == EPI_BIAS_RES_H16) {
+  if constexpr (EPI == EPI_BIAS_RES_H16) {
     const u32x2 r2 = *(const u32x2*)(g.res + o);
     if constexpr (DT == LATTE_DTYPE_BF16) {
       v0 += __builtin_bit_cast(float, r2[0] << 16); v1 += __builtin_bit_cast(float, r2[0] & 0xffff0000u);
@@ -362,25 +358,14 @@ int launch_n144(const GemmArgs& a, int epi, hipStream_t st) {
   if (a.N % 144 != 0 || a.K % 64 != 0 || a.k_chunk != 0)
     return fail(LATTE_ERR_INVALID, "gemm (144-wide tile): need N % 144 == 0, K % 64 == 0, no K split");
   dim3 grid(((a.M + BM - 1) / BM) * (a.N / 144)), block(PRODUCER ? 1024 : 768);
-#define LATTE_GEMM_CASE(E)                                                                           \
-  case E: {                                                                                          \
-    auto kern = gemm_n144_kernel<E, DT, PRODUCER, BM>;                                               \
-    static std::atomic<uint64_t> attr_done{0};                                                       \
-    if (int rc_ = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_;                 \
-    hipLaunchKernelGGL(kern, grid, block, LDS, st, a);                                               \
-    break;                                                                                           \
-  }
   switch (epi) {
-    LATTE_GEMM_CASE(EPI_BIAS_H16)
-    LATTE_GEMM_CASE(EPI_BIAS_GELU_H16)
-    LATTE_GEMM_CASE(EPI_GATE_RES_F32)
-    LATTE_GEMM_CASE(EPI_BIAS_F32)
+    case EPI_BIAS_H16: return launch_lds<gemm_n144_kernel<EPI_BIAS_H16, DT, PRODUCER, BM>>(grid, block, LDS, st, a);
+    case EPI_BIAS_GELU_H16: return launch_lds<gemm_n144_kernel<EPI_BIAS_GELU_H16, DT, PRODUCER, BM>>(grid, block, LDS, st, a);
+    case EPI_GATE_RES_F32: return launch_lds<gemm_n144_kernel<EPI_GATE_RES_F32, DT, PRODUCER, BM>>(grid, block, LDS, st, a);
+    case EPI_BIAS_F32: return launch_lds<gemm_n144_kernel<EPI_BIAS_F32, DT, PRODUCER, BM>>(grid, block, LDS, st, a);
     default:
       return fail(LATTE_ERR_INVALID, "gemm (144-wide tile): unknown epilogue");
   }
-#undef LATTE_GEMM_CASE
-  LATTE_HIP(hipGetLastError());
-  return LATTE_OK;
 }
 
 template <int BM, int BN, int WGM, int WGN, int DT>
@@ -390,26 +375,15 @@ int launch_cfg(const GemmArgs& a, int epi, hipStream_t st) {
   const int splits = a.k_chunk > 0 ? (a.K + a.k_chunk - 1) / a.k_chunk : 1;
   if (a.k_chunk % 64) return fail(LATTE_ERR_INVALID, "gemm: k_chunk must be a multiple of 64");
   dim3 grid(tiles, splits), block(WGM * WGN * 64);
-#define LATTE_GEMM_CASE(E)                                                                           \
-  case E: {                                                                                          \
-    auto kern = gemm_kernel<BM, BN, WGM, WGN, E, DT>;                                                \
-    static std::atomic<uint64_t> attr_done{0};                                                       \
-    if (int rc_ = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_;                 \
-    hipLaunchKernelGGL(kern, grid, block, LDS, st, a);                                               \
-    break;                                                                                           \
-  }
   switch (epi) {
-    LATTE_GEMM_CASE(EPI_BIAS_H16)
-    LATTE_GEMM_CASE(EPI_BIAS_GELU_H16)
-    LATTE_GEMM_CASE(EPI_GATE_RES_F32)
-    LATTE_GEMM_CASE(EPI_BIAS_F32)
-    LATTE_GEMM_CASE(EPI_BIAS_RES_H16)
+    case EPI_BIAS_H16: return launch_lds<gemm_kernel<BM, BN, WGM, WGN, EPI_BIAS_H16, DT>>(grid, block, LDS, st, a);
+    case EPI_BIAS_GELU_H16: return launch_lds<gemm_kernel<BM, BN, WGM, WGN, EPI_BIAS_GELU_H16, DT>>(grid, block, LDS, st, a);
+    case EPI_GATE_RES_F32: return launch_lds<gemm_kernel<BM, BN, WGM, WGN, EPI_GATE_RES_F32, DT>>(grid, block, LDS, st, a);
+    case EPI_BIAS_F32: return launch_lds<gemm_kernel<BM, BN, WGM, WGN, EPI_BIAS_F32, DT>>(grid, block, LDS, st, a);
+    case EPI_BIAS_RES_H16: return launch_lds<gemm_kernel<BM, BN, WGM, WGN, EPI_BIAS_RES_H16, DT>>(grid, block, LDS, st, a);
     default:
       return fail(LATTE_ERR_INVALID, "gemm: unknown epilogue");
   }
-#undef LATTE_GEMM_CASE
-  LATTE_HIP(hipGetLastError());
-  return LATTE_OK;
 }
 
 
@@ -578,11 +552,11 @@ __global__ void __launch_bounds__(512) gemm_pp_kernel(GemmArgs g) {
 // Tile sequence of a workgroup: XCD x (= blockIdx & 7) owns a contiguous chunk of the grouped tile
 // order (tile_coords' order); slot s (= blockIdx >> 3) takes positions s, s + G/8, ... of that chunk, so
 // the 32 workgroups of one XCD work on a compact patch of tiles at any time (shared A / W panels in L2).
-// RMW_AHEAD / RMW_NT: the gated fp32 read-modify-write epilogue keeps RMW_AHEAD residual fragments (1 KB per wave each)
-// in flight ahead of the stores; RMW_NT loads them with the non-temporal policy (they are read exactly once).
+// The gated fp32 read-modify-write epilogue keeps RMW_AHEAD = 2 residual fragments (1 KB per wave each) in flight ahead of the
+// stores (deeper look-ahead and non-temporal loads were measured and not kept: DESIGN.md Appendix A).
 // TAG only separates the instantiations of the two gated-residual call sites (0 = attention out-projection, 1 = fc2), which
 // share every other template argument, so that a kernel trace lists them as two kernels.
-template <int BN, int EPI, int DT, int RMW_AHEAD = 2, int RMW_NT = 0, int TAG = 0>
+template <int BN, int EPI, int DT, int TAG = 0>
 __global__ void __launch_bounds__(512) gemm_pps_kernel(GemmArgs g) {
   constexpr int BM = 256, NW = 8;
   constexpr int WTN = BN / 4, FN = WTN / 16;
@@ -590,7 +564,7 @@ __global__ void __launch_bounds__(512) gemm_pps_kernel(GemmArgs g) {
   constexpr int A_INSTR = BM / 8 / NW, B_INSTR = BN / 8 / NW;
   constexpr int AH_INSTR = 128 / 8 / 4;
   constexpr int BG_INSTR = BN / 8 / 4;
-  constexpr int GROUP_M = 8;
+  constexpr int GROUP_M = 8, RMW_AHEAD = 2;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
@@ -764,14 +738,7 @@ __global__ void __launch_bounds__(512) gemm_pps_kernel(GemmArgs g) {
             const int mc = min(mbase + (f / FN) * 16, g.M - 1);      // clamped row: the load is unconditional
             return outp + (size_t)mc * g.N + ncol + (f % FN) * 16;
           };
-          auto load_res = [&](int f) -> float4 {
-            if constexpr (RMW_NT) {
-              const f32x4 v = __builtin_nontemporal_load((const f32x4*)frag_ptr(f));
-              return make_float4(v[0], v[1], v[2], v[3]);
-            } else {
-              return *(const float4*)frag_ptr(f);
-            }
-          };
+          auto load_res = [&](int f) -> float4 { return *(const float4*)frag_ptr(f); };
           float4 qa[RMW_AHEAD];
 #pragma unroll
           for (int a = 0; a < RMW_AHEAD; ++a) qa[a] = load_res(a);
@@ -818,19 +785,6 @@ __global__ void __launch_bounds__(512) gemm_pps_kernel(GemmArgs g) {
   // (Tiles with rows >= M, and waves whose columns lie beyond N, take the plain vmcnt(0) path.)
   int it = 0;
   bool counted = false;   // the DMA needed by this iteration was issued before an epilogue that loaded and used data
-  // main-loop ablations (measurement only)
-  constexpr bool NO_DMA = EPI == EPI_ABLATE_NODMA, NO_LDSR = EPI == EPI_ABLATE_NOLDSREAD, NO_MFMA = EPI == EPI_ABLATE_NOMFMA;
-  u32x4 hold_b[NO_LDSR ? 2 : 1][NO_LDSR ? FN : 1], hold_a[NO_LDSR ? 2 : 1][NO_LDSR ? 8 : 1];
-  constexpr bool DO_A = EPI != EPI_ABLATE_DMA_B, DO_B = EPI != EPI_ABLATE_DMA_A;
-  constexpr bool TRACE = EPI == EPI_ABLATE_TRACE;
-  long long tacc[6] = {0, 0, 0, 0, 0, 0}, tprev = 0, tstart = 0;
-  if constexpr (TRACE) tstart = tprev = (long long)__builtin_readcyclecounter();
-#define LATTE_TS(IDX)                                                \
-  if constexpr (TRACE) {                                             \
-    const long long now_ = (long long)__builtin_readcyclecounter();  \
-    tacc[IDX] += now_ - tprev;                                       \
-    tprev = now_;                                                    \
-  }
   for (;;) {
     const int npos = pos + per;
     const bool has_next = npos < cnt;
@@ -843,99 +797,61 @@ __global__ void __launch_bounds__(512) gemm_pps_kernel(GemmArgs g) {
       //  and the barrier that releases the other group)
       const bool last = kt + 1 == nk;
       const bool in_tile = kt + 2 < nk;
-      const bool do_dma = !NO_DMA && (in_tile || has_next);
+      const bool do_dma = in_tile || has_next;
       const int stm = in_tile ? tm : ntm, stn = in_tile ? tn : ntn;
-      const int skt = EPI == EPI_ABLATE_HOTSRC ? 0 : in_tile ? kt + 2 : kt + 2 - nk;
+      const int skt = in_tile ? kt + 2 : kt + 2 - nk;
       const char* sbuf = smem + (it & 1) * STAGE;
       u32x4 bf[2][FN], af[2][8];
-      if (!NO_LDSR || it == 0) {
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
+      for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
-          for (int j = 0; j < FN; ++j) bf[ks][j] = *(const u32x4*)(sbuf + ((b_off + j * 2048) ^ (ks << 6)));
+        for (int j = 0; j < FN; ++j) bf[ks][j] = *(const u32x4*)(sbuf + ((b_off + j * 2048) ^ (ks << 6)));
 #pragma unroll
-          for (int i = 0; i < 8; ++i) af[ks][i] = *(const u32x4*)(sbuf + ((a_off + i * 2048) ^ (ks << 6)));
-        }
-      }
-
-      if constexpr (NO_LDSR) {   // ablation: keep the first K tile's fragments
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-          for (int j = 0; j < FN; ++j) { if (it == 0) hold_b[ks][j] = bf[ks][j]; else bf[ks][j] = hold_b[ks][j]; }
-#pragma unroll
-          for (int i = 0; i < 8; ++i) { if (it == 0) hold_a[ks][i] = af[ks][i]; else af[ks][i] = hold_a[ks][i]; }
-        }
+        for (int i = 0; i < 8; ++i) af[ks][i] = *(const u32x4*)(sbuf + ((a_off + i * 2048) ^ (ks << 6)));
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      LATTE_TS(0)
       __builtin_amdgcn_s_barrier();
-      LATTE_TS(1)
       __builtin_amdgcn_s_setprio(1);
-      if constexpr (NO_MFMA) {
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
+      for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-          for (int j = 0; j < FN; ++j) asm volatile("" ::"v"(bf[ks][j]));
+        for (int i = 0; i < 8; ++i)
 #pragma unroll
-          for (int i = 0; i < 8; ++i) asm volatile("" ::"v"(af[ks][i]));
-        }
-      } else {
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-          for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < FN; ++j) acc[i][j] = mfma16<DT>(bf[ks][j], af[ks][i], acc[i][j]);
-      }
+          for (int j = 0; j < FN; ++j) acc[i][j] = mfma16<DT>(bf[ks][j], af[ks][i], acc[i][j]);
       __builtin_amdgcn_s_setprio(0);
-      LATTE_TS(2)
       // DMA(u+1) must have landed.  After a tile boundary it provably has: the epilogue began with global loads
       // (bias / residual) that were issued AFTER DMA(u) and DMA(u+1) and were consumed before its first store, and
       // vmcnt retires in issue order -- so no wait here, and the epilogue's stores keep draining under this tile.
       if (!counted) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       counted = false;
-      LATTE_TS(3)
       // K tile u+2 (same tile, or the next tile's K tile kt + 2 - nk) into the stage just consumed.
       // Group 1's own A rows may be overwritten as soon as its L(u) is done, but the issue (4 buffer loads per wave,
       // which stall when the address unit's queue is full) must not sit between its last MFMA and the barrier that
       // releases group 0's compute segment.  So it follows the barrier -- except at a tile boundary, where it has to
       // precede the epilogue (in-order vmcnt argument above).
       if (grp == 1 && last) {
-        if (do_dma && DO_A) dma_a_half(stm, skt, it & 1);
+        if (do_dma) dma_a_half(stm, skt, it & 1);
         asm volatile("" ::: "memory");   // the epilogue's loads must stay BEHIND the DMA issue
         epilogue(tm, tn);
       }
       __builtin_amdgcn_s_barrier();
-      LATTE_TS(4)
       if (grp == 1 && !last) {
-        if (do_dma && DO_A) dma_a_half(stm, skt, it & 1);
+        if (do_dma) dma_a_half(stm, skt, it & 1);
       }
       if (grp == 0) {
         if (do_dma) {
-          if (DO_A) dma_a_half(stm, skt, it & 1);
-          if (DO_B) dma_b_all(stn, skt, it & 1);
+          dma_a_half(stm, skt, it & 1);
+          dma_b_all(stn, skt, it & 1);
         }
         asm volatile("" ::: "memory");
         if (last) epilogue(tm, tn);
       }
       if (last) counted = do_dma && full_rows && (tn * BN + wn * WTN < g.N);
-      LATTE_TS(5)
     }
     if (!has_next) break;
     pos = npos; tm = ntm; tn = ntn;
   }
   if (grp == 0) __builtin_amdgcn_s_barrier();  // balance group 1's extra barrier
-#undef LATTE_TS
-  if constexpr (TRACE) {   // phase times of workgroup 0 (tools/gpu_first_light.py gemm_trace)
-    if (blockIdx.x == 0 && lane == 0) {
-      long long* o = (long long*)g.out + wave * 8;
-#pragma unroll
-      for (int i = 0; i < 6; ++i) o[i] = tacc[i];
-      o[6] = (long long)__builtin_readcyclecounter() - tstart;
-      o[7] = it;
-    }
-  }
 }
 
 
@@ -953,65 +869,16 @@ int launch_pps(const GemmArgs& a, int epi, hipStream_t st) {
   }
   const int nblk = tiles >= 256 ? 256 : (tiles + 7) / 8 * 8;   // one workgroup per CU, multiple of the 8 XCDs
   dim3 grid(nblk), block(512);
-#define LATTE_GEMM_CASE(E)                                                                           \
-  case E: {                                                                                          \
-    auto kern = gemm_pps_kernel<BN, E, DT>;                                                          \
-    static std::atomic<uint64_t> attr_done{0};                                                       \
-    if (int rc_ = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_;                 \
-    hipLaunchKernelGGL(kern, grid, block, LDS, st, a);                                               \
-    break;                                                                                           \
-  }
-#ifdef LATTE_GEMM_ABLATE
-  // measurement build: look-ahead depth / cache policy of the read-modify-write epilogue (GemmArgs::rmw_mode = depth + 16 * nt)
-  if constexpr (BN == 192 && DT == LATTE_DTYPE_BF16) {
-    if (epi == EPI_GATE_RES_F32 && a.rmw_mode) {
-#define LATTE_RMW_CASE(AH, NT)                                                                        \
-  case AH + 16 * NT: {                                                                                \
-    auto kern = gemm_pps_kernel<BN, EPI_GATE_RES_F32, DT, AH, NT>;                                    \
-    static std::atomic<uint64_t> attr_done{0};                                                        \
-    if (int rc_ = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_;                  \
-    hipLaunchKernelGGL(kern, grid, block, LDS, st, a);                                                \
-    LATTE_HIP(hipGetLastError());                                                                     \
-    return LATTE_OK;                                                                                  \
-  }
-      switch (a.rmw_mode) {
-        LATTE_RMW_CASE(3, 0) LATTE_RMW_CASE(4, 0) LATTE_RMW_CASE(6, 0) LATTE_RMW_CASE(8, 0) LATTE_RMW_CASE(12, 0)
-        LATTE_RMW_CASE(2, 1) LATTE_RMW_CASE(4, 1) LATTE_RMW_CASE(6, 1) LATTE_RMW_CASE(8, 1)
-        default: break;
-      }
-#undef LATTE_RMW_CASE
-    }
-  }
-#endif
-  if (epi == EPI_GATE_RES_F32 && a.tag == 1) {   // fc2: its own kernel symbol
-    auto kern = gemm_pps_kernel<BN, EPI_GATE_RES_F32, DT, 2, 0, 1>;
-    static std::atomic<uint64_t> attr_done{0};
-    if (int rc_ = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_;
-    hipLaunchKernelGGL(kern, grid, block, LDS, st, a);
-    LATTE_HIP(hipGetLastError());
-    return LATTE_OK;
-  }
+  if (epi == EPI_GATE_RES_F32 && a.tag == 1)   // fc2: its own kernel symbol
+    return launch_lds<gemm_pps_kernel<BN, EPI_GATE_RES_F32, DT, 1>>(grid, block, LDS, st, a);
   switch (epi) {
-    LATTE_GEMM_CASE(EPI_BIAS_H16)
-    LATTE_GEMM_CASE(EPI_BIAS_GELU_H16)
-    LATTE_GEMM_CASE(EPI_GATE_RES_F32)
-    LATTE_GEMM_CASE(EPI_BIAS_F32)
-#ifdef LATTE_GEMM_ABLATE   // measurement build only (LATTE_DEBUG_BUILD=1 python -m latte_amd.build): main-loop ablations
-    LATTE_GEMM_CASE(EPI_ABLATE_NOSTORE)
-    LATTE_GEMM_CASE(EPI_ABLATE_NODMA)
-    LATTE_GEMM_CASE(EPI_ABLATE_NOLDSREAD)
-    LATTE_GEMM_CASE(EPI_ABLATE_NOMFMA)
-    LATTE_GEMM_CASE(EPI_ABLATE_HOTSRC)
-    LATTE_GEMM_CASE(EPI_ABLATE_DMA_A)
-    LATTE_GEMM_CASE(EPI_ABLATE_DMA_B)
-    LATTE_GEMM_CASE(EPI_ABLATE_TRACE)
-#endif
+    case EPI_BIAS_H16: return launch_lds<gemm_pps_kernel<BN, EPI_BIAS_H16, DT>>(grid, block, LDS, st, a);
+    case EPI_BIAS_GELU_H16: return launch_lds<gemm_pps_kernel<BN, EPI_BIAS_GELU_H16, DT>>(grid, block, LDS, st, a);
+    case EPI_GATE_RES_F32: return launch_lds<gemm_pps_kernel<BN, EPI_GATE_RES_F32, DT>>(grid, block, LDS, st, a);
+    case EPI_BIAS_F32: return launch_lds<gemm_pps_kernel<BN, EPI_BIAS_F32, DT>>(grid, block, LDS, st, a);
     default:
       return fail(LATTE_ERR_INVALID, "gemm: unknown epilogue");
   }
-#undef LATTE_GEMM_CASE
-  LATTE_HIP(hipGetLastError());
-  return LATTE_OK;
 }
 
 template <int BN, int DT>
@@ -1021,277 +888,16 @@ int launch_pp(const GemmArgs& a, int epi, hipStream_t st) {
   const int splits = a.k_chunk > 0 ? (a.K + a.k_chunk - 1) / a.k_chunk : 1;
   if (a.k_chunk % 64) return fail(LATTE_ERR_INVALID, "gemm: k_chunk must be a multiple of 64");
   dim3 grid(tiles, splits), block(512);
-#define LATTE_GEMM_CASE(E)                                                                           \
-  case E: {                                                                                          \
-    auto kern = gemm_pp_kernel<BN, E, DT>;                                                           \
-    static std::atomic<uint64_t> attr_done{0};                                                       \
-    if (int rc_ = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_;                 \
-    hipLaunchKernelGGL(kern, grid, block, LDS, st, a);                                               \
-    break;                                                                                           \
-  }
   switch (epi) {
-    LATTE_GEMM_CASE(EPI_BIAS_H16)
-    LATTE_GEMM_CASE(EPI_BIAS_GELU_H16)
-    LATTE_GEMM_CASE(EPI_GATE_RES_F32)
-    LATTE_GEMM_CASE(EPI_BIAS_F32)
+    case EPI_BIAS_H16: return launch_lds<gemm_pp_kernel<BN, EPI_BIAS_H16, DT>>(grid, block, LDS, st, a);
+    case EPI_BIAS_GELU_H16: return launch_lds<gemm_pp_kernel<BN, EPI_BIAS_GELU_H16, DT>>(grid, block, LDS, st, a);
+    case EPI_GATE_RES_F32: return launch_lds<gemm_pp_kernel<BN, EPI_GATE_RES_F32, DT>>(grid, block, LDS, st, a);
+    case EPI_BIAS_F32: return launch_lds<gemm_pp_kernel<BN, EPI_BIAS_F32, DT>>(grid, block, LDS, st, a);
     default:
       return fail(LATTE_ERR_INVALID, "gemm: unknown epilogue");
   }
-#undef LATTE_GEMM_CASE
-  LATTE_HIP(hipGetLastError());
-  return LATTE_OK;
 }
 
-#ifdef LATTE_GEMM_ABLATE
-// ------------------------------------------------------------------------------------------------
-// Measurement build only (variant 14): ONE MFMA wave per SIMD.  256 x 256 tile, four waves (2 x 2, wave tile 128 x 128:
-// 64 accumulator fragments = the 256 AGPRs, two fragment sets of 16 ds_read_b128 = 128 VGPRs), persistent over the same
-// XCD-chunked tile order as the ping-pong kernel, K tiles of 64 in two 64 KB LDS stages.  Per K tile and wave:
-//     A: MFMAs of the first half (fragment set 0)   ||  ds_reads of set 1
-//     lgkmcnt(0), own DMA of K tile t + 1 landed, ONE barrier (everybody done reading stage t & 1, everybody's t + 1 landed)
-//     B: MFMAs of the second half (set 1)           ||  DMA of K tile t + 2 into stage t & 1  ||  ds_reads of set 0 of K tile t + 1
-// The (tile, K tile) sequence is flat: the first two K tiles of the next output tile are in flight / landed when a tile's
-// epilogue starts, and the epilogue's stores are issued AFTER that DMA, so the first barrier of the next tile waits with a
-// counted vmcnt (the stores) instead of draining them.  DESIGN.md section 8: the question is whether a lone wave with a full
-// register file covers its own LDS latency, which the 168-register waves of the 12-wave kernel do not.
-template <int EPI, int DT>
-__global__ void __launch_bounds__(256) gemm_w4_kernel(GemmArgs g) {
-  constexpr int BM = 256, BN = 256, NW = 4, FM = 8, FN = 8;
-  constexpr int A_BYTES = BM * 128, STAGE = (BM + BN) * 128;
-  constexpr bool LDS_EPI = EPI == EPI_BIAS_H16 || EPI == EPI_BIAS_GELU_H16;
-  constexpr int EPI_STORES = LDS_EPI ? 32 : 0;   // global store instructions of one epilogue (LDS_EPI form)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int K = g.K, nk = K / 64;
-  const unsigned row_bytes = (unsigned)K * 2u;
-
-  const int tiles_m = (g.M + BM - 1) / BM, tiles_n = g.N / BN, nwg = tiles_m * tiles_n;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per = gridDim.x >> 3;
-  const int q = nwg >> 3, r = nwg & 7;
-  const int chunk0 = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  const int cnt = q + (xcd < r ? 1 : 0);
-  if (slot >= cnt) return;
-  const int group_m = g.group_m > 0 ? g.group_m : 8;
-  auto decode = [&](int wg, int& tm, int& tn) {
-    const int per_group = group_m * tiles_n;
-    const int group = wg / per_group;
-    const int first_m = group * group_m;
-    const int gsz = min(tiles_m - first_m, group_m);
-    const int in_group = wg - group * per_group;
-    tm = first_m + in_group % gsz;
-    tn = in_group / gsz;
-  };
-  const __amdgpu_buffer_rsrc_t rsA =
-      __builtin_amdgcn_make_buffer_rsrc((void*)g.A, 0, (unsigned)tiles_m * BM * row_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)g.W, 0, (unsigned)g.N * row_bytes, 0x00020000);
-  const int lrow = lane >> 3, cpos = lane & 7;
-  const unsigned off_lane = (unsigned)lrow * row_bytes + (unsigned)((cpos ^ (((wave * 8 + lrow) >> 1) & 7)) * 16);
-  unsigned step32 = 32u * row_bytes;
-  asm volatile("" : "+s"(step32));
-  // K tile kt of output tile (tm_, tn_) into stage stg: row-groups wave + 4 j of A and of W, 16 one-KB pieces per wave
-  auto dma = [&](int tm_, int tn_, int kt, int stg) __attribute__((always_inline)) {
-    char* sA = smem + stg * STAGE + wave * 1024;
-    const unsigned soA = (unsigned)(tm_ * BM + wave * 8) * row_bytes + (unsigned)kt * 128u;
-    const unsigned soB = (unsigned)(tn_ * BN + wave * 8) * row_bytes + (unsigned)kt * 128u;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      bload_lds16(rsA, sA + j * NW * 1024, off_lane, soA + (unsigned)j * step32);
-      bload_lds16(rsB, sA + A_BYTES + j * NW * 1024, off_lane, soB + (unsigned)j * step32);
-    }
-  };
-  const int sw = (lane >> 1) & 7;
-  const int chunkb = ((lane >> 4) ^ sw) * 16;
-  const int a_off = (wm * 128 + (lane & 15)) * 128 + chunkb;
-  const int b_off = A_BYTES + (wn * 128 + (lane & 15)) * 128 + chunkb;
-  u32x4 fa[2][FM], fb[2][FN];
-  auto read_set = [&](int set, int stg, int ks) __attribute__((always_inline)) {
-    const char* sbuf = smem + stg * STAGE;
-#pragma unroll
-    for (int i = 0; i < FM; ++i) fa[set][i] = *(const u32x4*)(sbuf + ((a_off + i * 2048) ^ (ks << 6)));
-#pragma unroll
-    for (int j = 0; j < FN; ++j) fb[set][j] = *(const u32x4*)(sbuf + ((b_off + j * 2048) ^ (ks << 6)));
-  };
-  f32x4 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  auto mma_set = [&](int set) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j) acc[i][j] = mfma16<DT>(fb[set][j], fa[set][i], acc[i][j]);
-  };
-
-  // the bias of the wave's 128 columns goes global -> LDS by one DMA piece (1 KB: the 128 floats + the next 128, unused) into a
-  // wave-private slot, double-buffered by tile parity, issued BEFORE the operand DMA of the tile's last K step: no register
-  // holds it through the K loop and no load sits behind the DMA in the in-order vmcnt queue when the epilogue starts
-  const __amdgpu_buffer_rsrc_t rsBias = __builtin_amdgcn_make_buffer_rsrc((void*)g.bias, 0, (unsigned)g.N * 4u, 0x00020000);
-  char* const bias_lds = smem + 2 * STAGE + NW * 4096 + wave * 2048;
-  auto dma_bias = [&](int tn_, int par) __attribute__((always_inline)) {
-    bload_lds16(rsBias, bias_lds + par * 1024, (unsigned)lane * 16u, (unsigned)(tn_ * BN + wn * 128) * 4u);
-  };
-  int bias_par = 0;
-  auto epilogue = [&](int tm_, int tn_) __attribute__((always_inline)) {
-    int le = lane;
-    asm volatile("" : "+v"(le));
-    const int fr = le & 15, gq = le >> 4;
-    const int ncol0 = tn_ * BN + wn * 128, mrow0 = tm_ * BM + wm * 128;
-    if constexpr (LDS_EPI) {
-      // wave-private 4 KB patch [32 rows][128 B] behind the two stages: every global store writes 8 complete 128-byte row pieces
-      char* patch = smem + 2 * STAGE + wave * 4096;
-#pragma unroll
-      for (int jh = 0; jh < 2; ++jh) {
-        float4 b4[4];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) b4[jj] = *(const float4*)(bias_lds + bias_par * 1024 + (jh * 64 + jj * 16 + gq * 4) * 4);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-#pragma unroll
-          for (int ii = 0; ii < 2; ++ii) {
-            const int i = 2 * c + ii, row = ii * 16 + fr;
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-              const int j = jh * 4 + jj;
-              float v0 = acc[i][j][0] + b4[jj].x, v1 = acc[i][j][1] + b4[jj].y, v2 = acc[i][j][2] + b4[jj].z, v3 = acc[i][j][3] + b4[jj].w;
-              if constexpr (EPI == EPI_BIAS_GELU_H16) {
-                v0 = gelu_tanh(v0); v1 = gelu_tanh(v1); v2 = gelu_tanh(v2); v3 = gelu_tanh(v3);
-              }
-              const u32x2 pk = {pack2<DT>(v0, v1), pack2<DT>(v2, v3)};
-              const int piece = jj * 2 + (gq >> 1);
-              *(u32x2*)(patch + row * 128 + ((piece ^ ((row >> 1) & 7)) << 4) + ((gq & 1) << 3)) = pk;
-              acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            }
-          }
-#pragma unroll
-          for (int kq = 0; kq < 4; ++kq) {
-            const int row = kq * 8 + (le >> 3), piece = le & 7;
-            const u32x4 v = *(const u32x4*)(patch + row * 128 + ((piece ^ ((row >> 1) & 7)) << 4));
-            const int m = mrow0 + c * 32 + row;
-            if (m < g.M) *(u32x4*)((half_t*)g.out + (size_t)m * g.N + ncol0 + jh * 64 + piece * 8) = v;
-          }
-        }
-      }
-    } else {
-      const int ncol = ncol0 + gq * 4;
-#pragma unroll
-      for (int i = 0; i < FM; ++i) {
-        const int m = mrow0 + i * 16 + fr;
-        const float* gate_row = nullptr;
-        if constexpr (EPI == EPI_GATE_RES_F32) gate_row = g.gate + (size_t)(min(m, g.M - 1) / g.rows_per_sample) * g.gate_stride;
-#pragma unroll
-        for (int j = 0; j < FN; ++j) {
-          if (m < g.M) epilogue_store<EPI, DT>(g, acc[i][j], m, ncol + j * 16, gate_row);
-          acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-      }
-    }
-  };
-
-  // flat walk over (tile, K tile) steps: the K loop below multiplies step (tile, kt); n1 = the step after it (landing / landed),
-  // n2 = the one after that (issued in this step's second half); both cross into the workgroup's next tile on their own
-  int pos = slot, tm, tn;
-  decode(chunk0 + pos, tm, tn);
-  // next step; when the walk ends p = -1 and the coordinates stay where they were (a valid K tile: the DMA / reads of the last two
-  // steps run unconditionally -- a branch would split the scheduling region the interleave below is written for -- and are unused)
-  auto advance = [&](int& p, int& a, int& b, int& k) __attribute__((always_inline)) {
-    if (k + 1 < nk) { ++k; return; }
-    if (p + per >= cnt) { p = -1; return; }
-    k = 0;
-    p += per;
-    decode(chunk0 + p, a, b);
-  };
-  int pos1 = pos, tm1 = tm, tn1 = tn, kt1 = 0;
-  if constexpr (LDS_EPI) dma_bias(tn, 0);
-  dma(tm, tn, 0, 0);
-  advance(pos1, tm1, tn1, kt1);                       // step 1 (nk >= 2: same tile, kt 1)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  dma(tm1, tn1, kt1, 1);
-  read_set(0, 0, 0);
-  int pos2 = pos1, tm2 = tm1, tn2 = tn1, kt2 = kt1;
-  advance(pos2, tm2, tn2, kt2);                       // step 2
-  int stg = 0;
-  bool after_stores = false;
-  for (;;) {
-    int posN = -1, tmN = 0, tnN = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-      const bool opens_next = kt == nk - 1 && pos1 >= 0;     // n1 is K tile 0 of the workgroup's next tile
-      if (LDS_EPI && opens_next) dma_bias(tn1, bias_par ^ 1);
-      // ---- A: first half of the K tile (set 0), fragment set 1 arriving under it: one read per two MFMAs, then MFMAs alone
-      __builtin_amdgcn_sched_barrier(0);
-      read_set(1, stg, 1);
-      mma_set(0);
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 32, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (after_stores) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(EPI_STORES) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      after_stores = false;
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      // ---- B: second half (set 1), the DMA of step + 2 into the stage just released, set 0 of step + 1
-      dma(tm2, tn2, kt2, stg);
-      read_set(0, stg ^ 1, 0);
-      mma_set(1);
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (opens_next) { posN = pos1; tmN = tm1; tnN = tn1; }
-      pos1 = pos2; tm1 = tm2; tn1 = tn2; kt1 = kt2;
-      if (pos2 >= 0) advance(pos2, tm2, tn2, kt2);
-      stg ^= 1;
-    }
-    epilogue(tm, tn);
-    after_stores = EPI_STORES > 0;
-    bias_par ^= 1;
-    if (posN < 0) break;
-    pos = posN; tm = tmN; tn = tnN;
-  }
-}
-
-template <int DT>
-int launch_w4(const GemmArgs& a, int epi, hipStream_t st) {
-  constexpr int LDS = 2 * 512 * 128 + 4 * 4096 + 4 * 2048;
-  if (a.N % 256 || a.K % 64 || a.K < 128 || a.k_chunk) return fail(LATTE_ERR_INVALID, "gemm w4: needs N % 256 == 0, K % 64 == 0, K >= 128, no split K");
-  const int tiles = ((a.M + 255) / 256) * (a.N / 256);
-  const int nblk = tiles >= 256 ? 256 : (tiles + 7) / 8 * 8;
-  dim3 grid(nblk), block(256);
-#define LATTE_GEMM_CASE(E)                                                                           \
-  case E: {                                                                                          \
-    auto kern = gemm_w4_kernel<E, DT>;                                                               \
-    static std::atomic<uint64_t> attr_done{0};                                                       \
-    if (int rc_ = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_;                 \
-    hipLaunchKernelGGL(kern, grid, block, LDS, st, a);                                               \
-    break;                                                                                           \
-  }
-  switch (epi) {
-    LATTE_GEMM_CASE(EPI_BIAS_H16)
-    LATTE_GEMM_CASE(EPI_BIAS_GELU_H16)
-    LATTE_GEMM_CASE(EPI_GATE_RES_F32)
-    LATTE_GEMM_CASE(EPI_BIAS_F32)
-    LATTE_GEMM_CASE(EPI_ABLATE_NOSTORE)
-    default:
-      return fail(LATTE_ERR_INVALID, "gemm w4: unknown epilogue");
-  }
-#undef LATTE_GEMM_CASE
-  LATTE_HIP(hipGetLastError());
-  return LATTE_OK;
-}
-#endif   // LATTE_GEMM_ABLATE
 
 template <int DT>
 int launch_dt(const GemmArgs& a, int epi, int variant, hipStream_t st) {
@@ -1311,10 +917,6 @@ int launch_dt(const GemmArgs& a, int epi, int variant, hipStream_t st) {
       if (epi == EPI_GATE_RES_F32 && a.rows_per_sample % 256 != 0) return launch_n144<DT, 1, 256>(a, epi, st);
       return launch_n144<DT, 0, 256>(a, epi, st);
     case 19: return launch_n144<DT, 1, 256>(a, epi, st);
-#ifdef LATTE_GEMM_ABLATE   // measurement build: one consumer wave per SIMD (4 waves x 512 registers, wave tile 128 x 128) on the plain template
-    case 14: return launch_w4<DT>(a, epi, st);
-    case 15: return launch_cfg<256, 256, 2, 2, DT>(a, epi, st);   // the same wave layout on the plain two-stage template
-#endif
     default: return fail(LATTE_ERR_INVALID, "gemm: unknown tile variant");
   }
 }
@@ -1325,8 +927,8 @@ int gemm_tile_m(int variant) { return variant == 1 || variant == 12 || variant =
 
 int gemm_tile_n(int variant) {
   switch (variant) {
-    case 3: case 6: case 9: case 14: case 15: return 256;
-    case 5: case 8: case 10: case 11: case 17: return 192;
+    case 3: case 6: case 9: return 256;
+    case 5: case 8: case 10: case 11: return 192;
     case 12: case 13: case 18: case 19: return 144;
     default: return 128;
   }
@@ -1394,21 +996,6 @@ int launch_gemm(const GemmArgs& a_in, int epi, int dtype, int variant, hipStream
   // grouped tile order of the persistent kernel: the gated-residual GEMMs (192-wide tiles: an A K-tile is 32 KB, a W K-tile
   // 24 KB) walk 4 tile rows together instead of 8 (fc2 in the XL/2 forward at B = 8: 341 -> 333 us, round-2 sweep)
   if (a.group_m == 0 && epi == EPI_GATE_RES_F32) a.group_m = 4;
-#ifdef LATTE_GEMM_ABLATE
-  if (const char* m = getenv("LATTE_RMW_MODE")) a.rmw_mode = atoi(m);
-  if (const char* m = getenv("LATTE_PWR_ABL")) { if (epi == EPI_GATE_RES_F32) a.rmw_mode = atoi(m); }   // ladder rungs of the rolling kernel (gemm_pw.hip)
-  if (const char* m = getenv("LATTE_RMW_VARIANT")) { if (epi == EPI_GATE_RES_F32 && variant == 0) variant = atoi(m); }
-  if (const char* m = getenv("LATTE_GROUP_M")) {   // "epi:value[,epi:value]" e.g. "2:5" = gated-residual GEMMs walk 5 tile rows together
-    for (const char* q = m; q && *q;) {
-      const int e_ = atoi(q);
-      const char* c_ = strchr(q, ':');
-      if (!c_) break;
-      if (e_ == epi) a.group_m = atoi(c_ + 1);
-      q = strchr(c_, ',');
-      if (q) ++q;
-    }
-  }
-#endif
   if (a.A4) {   // fp4 correction pass (GemmArgs::A4 / W4 + row scales): rolling 12-wave kernel, any K % 64 == 0 (rows are padded to K % 256 == 0)
     if (!gemm_lo4_ok(a.M, a.N, a.K)) return fail(LATTE_ERR_INVALID, "gemm: the fp4 correction pass needs N % 192 == 0, K % 64 == 0, K >= 128");
     return launch_gemm_pw(a, epi, dtype, 1, st);
@@ -1419,9 +1006,6 @@ int launch_gemm(const GemmArgs& a_in, int epi, int dtype, int variant, hipStream
   }
   if (variant == 0) variant = gemm_resolve_variant(a.M, a.N, a.K, epi);
   if (variant == 10 || variant == 11) return launch_gemm_pw(a, epi, dtype, variant == 11, st);
-#ifdef LATTE_GEMM_ABLATE
-  if (variant == 17) return launch_gemm_pw(a, epi, dtype, 3, st);   // two-accumulator-set kernel (gemm_pw.hip; measured: loses)
-#endif
   const int bn = gemm_tile_n(variant);
   const int nq = variant >= 7 && variant <= 9 ? bn / 4 : bn;   // persistent kernels: partial last tile column in whole wave widths
   if (a.K % 64 != 0 || a.N % nq != 0 || a.M <= 0)

@@ -354,18 +354,13 @@ int launch_gemm_tn(const half_t* dY, const half_t* X, float* partial, int M, int
   if (gemm_tn8_ok(M, N, K)) {
     constexpr int LDS8 = 2 * 4 * 64 * 256;
     dim3 grid8(((N + 255) / 256) * ((K + 255) / 256) * splits), block8(512);   // 1-D: the kernel maps workgroups to (split, tile)
-#define LATTE_TN8_CASE(DT, CS)                                                                      \
-  {                                                                                                 \
-    static std::atomic<uint64_t> done{0};                                                           \
-    if (int rc = ensure_dynamic_lds((const void*)gemm_tn8_kernel<DT, CS>, LDS8, done)) return rc;   \
-    hipLaunchKernelGGL((gemm_tn8_kernel<DT, CS>), grid8, block8, LDS8, st, a);                      \
-  }
-    if (dtype == LATTE_DTYPE_BF16) { if (colsum_partial) LATTE_TN8_CASE(LATTE_DTYPE_BF16, true) else LATTE_TN8_CASE(LATTE_DTYPE_BF16, false) }
-    else if (dtype == LATTE_DTYPE_F16) { if (colsum_partial) LATTE_TN8_CASE(LATTE_DTYPE_F16, true) else LATTE_TN8_CASE(LATTE_DTYPE_F16, false) }
-    else return fail(LATTE_ERR_INVALID, "gemm_tn: unknown dtype");
-#undef LATTE_TN8_CASE
-    LATTE_HIP(hipGetLastError());
-    return LATTE_OK;
+    if (dtype == LATTE_DTYPE_BF16)
+      return colsum_partial ? launch_lds<gemm_tn8_kernel<LATTE_DTYPE_BF16, true>>(grid8, block8, LDS8, st, a)
+                            : launch_lds<gemm_tn8_kernel<LATTE_DTYPE_BF16, false>>(grid8, block8, LDS8, st, a);
+    if (dtype == LATTE_DTYPE_F16)
+      return colsum_partial ? launch_lds<gemm_tn8_kernel<LATTE_DTYPE_F16, true>>(grid8, block8, LDS8, st, a)
+                            : launch_lds<gemm_tn8_kernel<LATTE_DTYPE_F16, false>>(grid8, block8, LDS8, st, a);
+    return fail(LATTE_ERR_INVALID, "gemm_tn: unknown dtype");
   }
   // 128 x 128 tile on 4 waves, two workgroups per CU.  Measured against it (training step, Latte-B/2, batch 5, same box): one
   // 256 x 128 / 8-wave workgroup per CU (a quarter fewer ds_write_b128 bytes per MFMA) 28.1 against 26.4 ms, one 128 x 256 /
@@ -373,19 +368,14 @@ int launch_gemm_tn(const half_t* dY, const half_t* X, float* partial, int M, int
   // wait sit under the other's MFMAs), one bigger workgroup marches in lock step.
   const int tile_n = gemm_tn_tile_n();
   dim3 grid(((N + tile_n - 1) / tile_n) * (K / 128), splits), block(tile_n * 2);
-  const int lds = 2 * (64 * (tile_n == 128 ? 288 : 544) + 64 * TN_PITCH);
-#define LATTE_TN_CASE(DT, WN)                                                                       \
-  {                                                                                                 \
-    static std::atomic<uint64_t> done{0};                                                           \
-    if (int rc = ensure_dynamic_lds((const void*)gemm_tn_kernel<DT, WN>, lds, done)) return rc;     \
-    hipLaunchKernelGGL((gemm_tn_kernel<DT, WN>), grid, block, lds, st, a);                          \
-  }
-  if (dtype == LATTE_DTYPE_BF16) { if (tile_n == 256) LATTE_TN_CASE(LATTE_DTYPE_BF16, 4) else LATTE_TN_CASE(LATTE_DTYPE_BF16, 2) }
-  else if (dtype == LATTE_DTYPE_F16) { if (tile_n == 256) LATTE_TN_CASE(LATTE_DTYPE_F16, 4) else LATTE_TN_CASE(LATTE_DTYPE_F16, 2) }
-  else return fail(LATTE_ERR_INVALID, "gemm_tn: unknown dtype");
-#undef LATTE_TN_CASE
-  LATTE_HIP(hipGetLastError());
-  return LATTE_OK;
+  const int lds = 2 * (64 * (tile_n == 128 ? 288 : 544) + 64 * TN_PITCH);   // one value per WN: each kernel's opt-in is what it launches with
+  if (dtype == LATTE_DTYPE_BF16)
+    return tile_n == 256 ? launch_lds<gemm_tn_kernel<LATTE_DTYPE_BF16, 4>>(grid, block, lds, st, a)
+                         : launch_lds<gemm_tn_kernel<LATTE_DTYPE_BF16, 2>>(grid, block, lds, st, a);
+  if (dtype == LATTE_DTYPE_F16)
+    return tile_n == 256 ? launch_lds<gemm_tn_kernel<LATTE_DTYPE_F16, 4>>(grid, block, lds, st, a)
+                         : launch_lds<gemm_tn_kernel<LATTE_DTYPE_F16, 2>>(grid, block, lds, st, a);
+  return fail(LATTE_ERR_INVALID, "gemm_tn: unknown dtype");
 }
 
 }  // namespace latte

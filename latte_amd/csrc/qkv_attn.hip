@@ -555,12 +555,7 @@ __global__ void __launch_bounds__(512) qkv_attn_kernel(QkvAttnArgs a) {
 
 template <int HD, int DT, int MODE, int FLAGS, int SPLIT = 0>
 int launch_one(const QkvAttnArgs& a, dim3 grid, hipStream_t st) {
-  auto kern = qkv_attn_kernel<HD, DT, MODE, FLAGS, SPLIT>;
-  static std::atomic<uint64_t> done{0};
-  if (int rc = ensure_dynamic_lds((const void*)kern, FUSED_LDS, done)) return rc;
-  hipLaunchKernelGGL(kern, grid, dim3(512), FUSED_LDS, st, a);
-  LATTE_HIP(hipGetLastError());
-  return LATTE_OK;
+  return launch_lds<qkv_attn_kernel<HD, DT, MODE, FLAGS, SPLIT>>(grid, dim3(512), FUSED_LDS, st, a);
 }
 
 template <int HD, int DT>

@@ -325,13 +325,9 @@ int launch_stage_finalize(const StageFinArgs& a, hipStream_t st) {
   const int blocks = a.n_mod * (a.D / 64) + b.bias_blk[a.n_bias];
   if (blocks <= 0) return LATTE_OK;
   const int lds = (FIN_SB * 16 * 64 + FIN_SB * 64 + FIN_SB * a.D) * (int)sizeof(float);
-  static std::atomic<uint64_t> done{0};
   // (the opt-in is remembered per device: ask for the largest image the kernel can need, not this launch's)
   constexpr int LDS_MAX = (FIN_SB * 16 * 64 + FIN_SB * 64 + FIN_SB * FIN_DMAX) * (int)sizeof(float);
-  if (int rc = ensure_dynamic_lds((const void*)stage_finalize_kernel, LDS_MAX, done)) return rc;
-  hipLaunchKernelGGL(stage_finalize_kernel, dim3(blocks), dim3(1024), lds, st, b);
-  LATTE_HIP(hipGetLastError());
-  return LATTE_OK;
+  return launch_lds_max<stage_finalize_kernel>(dim3(blocks), dim3(1024), LDS_MAX, lds, st, b);
 }
 
 constexpr int NO_ROWS_PER_BLOCK = 128;
@@ -349,20 +345,18 @@ int launch_narrow_outer(const float* nar, int P, const void* wide, int wide_half
   float* pw = pn + (size_t)nb * P;
   const int lds = (NO_ROWS * D + NO_ROWS * NO_PMAX) * (int)sizeof(float);
   constexpr int lds_max = (NO_ROWS * FIN_DMAX + NO_ROWS * NO_PMAX) * (int)sizeof(float);   // the per-device opt-in covers every D
-#define NO_CASE(WT, DT)                                                                                                          \
-  {                                                                                                                              \
-    static std::atomic<uint64_t> done{0};                                                                                        \
-    if (int rc = ensure_dynamic_lds((const void*)narrow_outer_kernel<WT, DT>, lds_max, done)) return rc;                          \
-    hipLaunchKernelGGL((narrow_outer_kernel<WT, DT>), dim3(nb), dim3(threads), lds, st, nar, P, (const WT*)wide, D, M,            \
-                       NO_ROWS_PER_BLOCK, part, so_p, so_k, nsum_out ? pn : nullptr, wsum_out ? pw : nullptr);                   \
-  }
-  if (!wide_half) NO_CASE(float, LATTE_DTYPE_F16)
-  else if (dtype == LATTE_DTYPE_BF16) NO_CASE(half_t, LATTE_DTYPE_BF16)
-  else if (dtype == LATTE_DTYPE_F16) NO_CASE(half_t, LATTE_DTYPE_F16)
-  else return fail(LATTE_ERR_INVALID, "narrow_outer: unknown dtype");
-#undef NO_CASE
-  LATTE_HIP(hipGetLastError());
+  float* const pn_out = nsum_out ? pn : nullptr;
+  float* const pw_out = wsum_out ? pw : nullptr;
+  const dim3 grid(nb), block(threads);
   int rc;
+  if (!wide_half)
+    rc = launch_lds_max<narrow_outer_kernel<float, LATTE_DTYPE_F16>>(grid, block, lds_max, lds, st, nar, P, (const float*)wide, D, M, NO_ROWS_PER_BLOCK, part, so_p, so_k, pn_out, pw_out);
+  else if (dtype == LATTE_DTYPE_BF16)
+    rc = launch_lds_max<narrow_outer_kernel<half_t, LATTE_DTYPE_BF16>>(grid, block, lds_max, lds, st, nar, P, (const half_t*)wide, D, M, NO_ROWS_PER_BLOCK, part, so_p, so_k, pn_out, pw_out);
+  else if (dtype == LATTE_DTYPE_F16)
+    rc = launch_lds_max<narrow_outer_kernel<half_t, LATTE_DTYPE_F16>>(grid, block, lds_max, lds, st, nar, P, (const half_t*)wide, D, M, NO_ROWS_PER_BLOCK, part, so_p, so_k, pn_out, pw_out);
+  else return fail(LATTE_ERR_INVALID, "narrow_outer: unknown dtype");
+  if (rc) return rc;
   if ((rc = launch_split_reduce(part, nb, (size_t)P * D, (size_t)P * D, dW, accumulate, st, inv_scale_dev))) return rc;
   if (nsum_out && (rc = launch_split_reduce(pn, nb, (size_t)P, (size_t)P, nsum_out, accumulate, st, inv_scale_dev))) return rc;
   if (wsum_out && (rc = launch_split_reduce(pw, nb, (size_t)D, (size_t)D, wsum_out, accumulate, st, inv_scale_dev))) return rc;

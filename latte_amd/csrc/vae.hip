@@ -1245,45 +1245,21 @@ int launch_conv3x3(const half_t* in, const half_t* w, const float* bias, const h
   // 11.5 -> 12.2 ms; temporal decoder chunk 117 -> 137 ms, profiles/r6_vae_persistent_conv_ab.log): it runs only when conv_kernel 4 asks for it
   if (pp_ok && debug_choice(DBG_CONV_KERNEL) == 4) {
     const int nblk = pp_tiles >= 256 ? 256 : (pp_tiles + 7) / 8 * 8;
-    if (bn == 256) {
-      constexpr int LDS_PP = 2 * (256 + 256) * 128;
-      static std::atomic<uint64_t> attr_a{0};
-      if (int rc_ = ensure_dynamic_lds((const void*)conv3x3_pps_kernel<256, LATTE_DTYPE_F16>, LDS_PP, attr_a)) return rc_;
-      hipLaunchKernelGGL((conv3x3_pps_kernel<256, LATTE_DTYPE_F16>), dim3(nblk), dim3(512), LDS_PP, st, a);
-    } else {
-      constexpr int LDS_PP = 2 * (256 + 128) * 128;
-      static std::atomic<uint64_t> attr_b{0};
-      if (int rc_ = ensure_dynamic_lds((const void*)conv3x3_pps_kernel<128, LATTE_DTYPE_F16>, LDS_PP, attr_b)) return rc_;
-      hipLaunchKernelGGL((conv3x3_pps_kernel<128, LATTE_DTYPE_F16>), dim3(nblk), dim3(512), LDS_PP, st, a);
-    }
+    const int rc = bn == 256 ? launch_lds<conv3x3_pps_kernel<256, LATTE_DTYPE_F16>>(dim3(nblk), dim3(512), 2 * (256 + 256) * 128, st, a)
+                             : launch_lds<conv3x3_pps_kernel<128, LATTE_DTYPE_F16>>(dim3(nblk), dim3(512), 2 * (256 + 128) * 128, st, a);
     kprof_mark(VC_CONV3, st);
-    LATTE_HIP(hipGetLastError());
-    return LATTE_OK;
+    return rc;
   }
   if (pp_ok && debug_choice(DBG_CONV_KERNEL) != 1 && (pp_tiles >= 192 || debug_choice(DBG_CONV_KERNEL) >= 2)) {
-    if (bn == 256) {
-      constexpr int LDS_PP = 2 * (256 + 256) * 128;
-      static std::atomic<uint64_t> attr_a{0};
-      if (int rc_ = ensure_dynamic_lds((const void*)conv3x3_pp_kernel<256, LATTE_DTYPE_F16>, LDS_PP, attr_a)) return rc_;
-      hipLaunchKernelGGL((conv3x3_pp_kernel<256, LATTE_DTYPE_F16>), dim3(pp_tiles), dim3(512), LDS_PP, st, a);
-    } else {
-      constexpr int LDS_PP = 2 * (256 + 128) * 128;
-      static std::atomic<uint64_t> attr_b{0};
-      if (int rc_ = ensure_dynamic_lds((const void*)conv3x3_pp_kernel<128, LATTE_DTYPE_F16>, LDS_PP, attr_b)) return rc_;
-      hipLaunchKernelGGL((conv3x3_pp_kernel<128, LATTE_DTYPE_F16>), dim3(pp_tiles), dim3(512), LDS_PP, st, a);
-    }
+    const int rc = bn == 256 ? launch_lds<conv3x3_pp_kernel<256, LATTE_DTYPE_F16>>(dim3(pp_tiles), dim3(512), 2 * (256 + 256) * 128, st, a)
+                             : launch_lds<conv3x3_pp_kernel<128, LATTE_DTYPE_F16>>(dim3(pp_tiles), dim3(512), 2 * (256 + 128) * 128, st, a);
     kprof_mark(VC_CONV3, st);
-    LATTE_HIP(hipGetLastError());
-    return LATTE_OK;
+    return rc;
   }
   const int tiles = ((M + 127) / 128) * (Cout / 128);
-  constexpr int LDS = 2 * 256 * 128;
-  static std::atomic<uint64_t> attr_f16{0};
-  if (int rc_ = ensure_dynamic_lds((const void*)conv3x3_kernel<LATTE_DTYPE_F16>, LDS, attr_f16)) return rc_;
-  hipLaunchKernelGGL(conv3x3_kernel<LATTE_DTYPE_F16>, dim3(tiles), dim3(256), LDS, st, a);
+  const int rc = launch_lds<conv3x3_kernel<LATTE_DTYPE_F16>>(dim3(tiles), dim3(256), 2 * 256 * 128, st, a);
   kprof_mark(VC_CONV3, st);
-  LATTE_HIP(hipGetLastError());
-  return LATTE_OK;
+  return rc;
 }
 
 int launch_groupnorm(const void* x, int x_is_f32, half_t* y, const float* gamma, const float* beta, float* partial, float* stats,

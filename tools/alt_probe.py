@@ -1,11 +1,10 @@
-"""Gated GEMMs with the epilogue burst hidden under the K loop (variant 17, the two-accumulator-set kernel of gemm_pw.hip; round 5
-also ran variant 16, the alternating-groups form, with this script) against the rolling 12-wave kernel (variant 11) on the MI355X:
-bit-identity, stand-alone launch time on random operands, per-launch time INSIDE the XL/2 forward (HIP events of
-latte_profile_forward), interleaved settings in one process.  Needs the measurement build:
-    LATTE_DEBUG_BUILD=1 python -m latte_amd.build;  LATTE_AMD_LIB=latte_amd/lib/liblatte_amd_dbg.so python tools/alt_probe.py [check]
-    [standalone] [inmodel] [trace] [B=8,2] [dtype=f16] [variants=11,17]
-Result (profiles/r5_gated_overlap_*.log): same bits, the burst is hidden, the launch is slower -- a halved tile moves 1.43 x the operand
-bytes per MFMA through the LDS-DMA path, which is what bounds these kernels."""
+"""Gated GEMMs: other kernel variants against the rolling 12-wave kernel (variant 11) on the MI355X: bit-identity, stand-alone launch
+time on random operands, per-launch time INSIDE the XL/2 forward (HIP events of latte_profile_forward), interleaved settings in one
+process.
+    python tools/alt_probe.py [check] [standalone] [inmodel] [B=8,2] [dtype=f16] [variants=11,8,10]
+Written in round 5 for variants 16 / 17, the two forms of the gated GEMM with its epilogue burst hidden under the K loop.  Their code
+and the phase-trace mode that went with it were removed with the measurement build; profiles/r5_gated_overlap_*.log is the record (same
+bits, the burst is hidden, the launch is slower -- a halved tile moves 1.43 x the operand bytes per MFMA through the LDS-DMA path)."""
 import os
 import sys
 import time
@@ -22,7 +21,8 @@ what = [a for a in args if "=" not in a] or ["check", "standalone", "inmodel"]
 kv = dict(a.split("=") for a in args if "=" in a)
 DT = {"bf16": 0, "f16": 1}[kv.get("dtype", "f16")]
 TD = {0: torch.bfloat16, 1: torch.float16}[DT]
-VARIANTS = [int(v) for v in kv.get("variants", "11,17").split(",")]
+VARIANTS = [int(v) for v in kv.get("variants", "11,8,10").split(",")]
+OTHERS = [v for v in VARIANTS if v != 11]   # (8 / 10 / 11 share K order and epilogue arithmetic: same bits)
 
 
 def log(*a):
@@ -40,24 +40,25 @@ def do_check():
         gate = torch.randn((M + rps - 1) // rps, 2 * N, generator=g).to(dev)
         out0 = torch.randn(Mp, N, generator=g).to(dev)
         outs = {}
-        for variant in (11, 17, 1017):
+        for variant in [11] + OTHERS + [1000 + v for v in OTHERS]:
             out = out0.clone()
             check(lib.latte_debug_gemm(ptr(A), ptr(W), ptr(bias), ptr(out), ptr(gate), M, N, K, 2 * N, rps, 2, DT, variant, stream_ptr()))
             torch.cuda.synchronize()
             outs[variant] = out
         want = out0[:M] + gate[torch.arange(M, device=dev) // rps, :N] * (A.float()[:M] @ W.float().t() + bias)
-        for v in (17,):
+        for v in OTHERS:
             err = float((outs[v][:M] - want).norm() / want.norm())
             same = torch.equal(outs[v], outs[11]) and torch.equal(outs[1000 + v], outs[11])
             pad_ok = torch.equal(outs[v][M:], out0[M:])
             log(f"check v{v} M={M} N={N} K={K} rps={rps}: rel err {err:.2e}, bit-identical to v11: {same}, pad rows untouched: {pad_ok}")
         # second launch on the result (stale-state screen): res += again
-        out = outs[17].clone()
         ref = outs[11].clone()
-        check(lib.latte_debug_gemm(ptr(A), ptr(W), ptr(bias), ptr(out), ptr(gate), M, N, K, 2 * N, rps, 2, DT, 17, stream_ptr()))
         check(lib.latte_debug_gemm(ptr(A), ptr(W), ptr(bias), ptr(ref), ptr(gate), M, N, K, 2 * N, rps, 2, DT, 11, stream_ptr()))
-        torch.cuda.synchronize()
-        log(f"      second launch identical: {torch.equal(out, ref)}")
+        for v in OTHERS:
+            out = outs[v].clone()
+            check(lib.latte_debug_gemm(ptr(A), ptr(W), ptr(bias), ptr(out), ptr(gate), M, N, K, 2 * N, rps, 2, DT, v, stream_ptr()))
+            torch.cuda.synchronize()
+            log(f"      second launch of v{v} identical: {torch.equal(out, ref)}")
 
 
 def do_standalone():
@@ -89,7 +90,9 @@ def do_inmodel():
         t = torch.full((B,), 500, device=dev, dtype=torch.int64)
         res = {}
         outs = {}
-        settings = [("v11/v11", 0, 0), ("v17/v11", 17, 0), ("v11/v17", 0, 17), ("v17/v17", 17, 17)]
+        settings = [("v11/v11", 0, 0)]
+        for v in OTHERS:
+            settings += [(f"v{v}/v11", v, 0), (f"v11/v{v}", 0, v), (f"v{v}/v{v}", v, v)]
         for rep in range(4):
             for name, vp, vf in settings:
                 m.set_engine_option("gemm_variant_proj", vp, B)
@@ -118,32 +121,7 @@ def do_inmodel():
         torch.cuda.empty_cache()
 
 
-def do_trace():
-    """Measurement build (LATTE_AMD_LIB=latte_amd/lib/liblatte_amd_dbg.so): per-wave phase times of workgroup 0, shader clocks per K step.
-    v11 consumers: h0 | h1 head + lgkm | barrier | h1 rest | epilogue | refill;  v16 consumers: the same four K-step phases, then
-    epilogue-slice work | (barrier waits of the epilogue phase + fragment fill);  producers: DMA issue | vmcnt wait | barrier | - | - | bookkeeping."""
-    for (M, N, K, var) in [(32768, 1152, 1152, 11), (32768, 1152, 4608, 11)]:
-        A = torch.randn(M, K, device=dev).to(TD)
-        W = (torch.randn(N, K, device=dev) / K ** 0.5).to(TD)
-        bias = torch.randn(N, device=dev)
-        out = torch.zeros(M * N, dtype=torch.float32, device=dev)
-        gate = torch.randn(2 * N, device=dev)
-        for rep in range(3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            check(lib.latte_debug_gemm(ptr(A), ptr(W), ptr(bias), ptr(out), ptr(gate), M, N, K, 0, M, 12, DT, var, stream_ptr()))
-            e1.record()
-            torch.cuda.synchronize()
-        us = e0.elapsed_time(e1) * 1e3
-        t = out.view(torch.int64)[:96].cpu().view(12, 8)
-        log(f"trace v{var} M={M} N={N} K={K}: launch {us:.1f} us (no stores); ticks per K step of the wave's own count")
-        for w in range(12):
-            kt = max(int(t[w, 7]), 1)
-            row = " ".join(f"[{i}] {float(t[w, i]) / kt:7.1f}" for i in range(6))
-            log(f"   wave {w:2d} ({'grp %d' % (w >> 2) if w < 8 else 'producer'}): {row} | {int(t[w, 6]) / us:.0f} ticks/us, {kt} K steps, {float(t[w, 6]) / kt:.1f} ticks/K step")
-
-
 t0 = time.time()
 for w in what:
-    {"check": do_check, "standalone": do_standalone, "inmodel": do_inmodel, "trace": do_trace}[w]()
+    {"check": do_check, "standalone": do_standalone, "inmodel": do_inmodel}[w]()
 log(f"alt_probe done in {time.time() - t0:.1f} s")

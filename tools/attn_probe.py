@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Interleaved A/B of the self-attention kernels on one shape (both in ONE process, alternating, so clock drift and box variance
 cancel): latte_debug_set_choice("attn_variant", v) switches per launch.  Default shape = Latte-1 T2V spatial attention (32 sequences x 1024 tokens,
-16 heads x 72).  Variants: 0 default choice, 1 generic flash kernel, 4 256-key block kernel, 5 streaming kernel also for
-128 < L <= 256, 7 / 8 / 9 streaming kernel without DMA issue in the loop / without softmax / without barrier (results garbage).
+16 heads x 72).  Variants: 0 default choice, 1 generic flash kernel, 5 streaming kernel also for 128 < L <= 256, 12 / 13 the
+32 x 32 x 16 streaming kernel (head dim 72) with two / one query groups per wave.
 --sync: synchronise after every warm-up launch (the FIRST launch of a kernel that needs scratch memory, e.g. the block kernel,
 faulted on this pool when it was queued behind a running 120 KB-LDS kernel; with a synchronise in between it never did)."""
 import argparse
@@ -21,7 +21,7 @@ def main():
     ap.add_argument("--L", type=int, default=1024)
     ap.add_argument("--heads", type=int, default=16)
     ap.add_argument("--hd", type=int, default=72)
-    ap.add_argument("--variants", default="0,4")
+    ap.add_argument("--variants", default="0,1")
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--iters", type=int, default=40)
     ap.add_argument("--sync", action="store_true", help="synchronize after every warm-up launch (fault localisation)")
@@ -35,7 +35,7 @@ def main():
     flop = 4.0 * a.seqs * a.heads * a.L * a.L * a.hd
 
     def run(v):
-        assert lib.latte_debug_set_choice(b"attn_variant", int(v)) == 0, f"variant {v} is not offered by this build (7-9: LATTE_DEBUG_BUILD=1)"
+        assert lib.latte_debug_set_choice(b"attn_variant", int(v)) == 0, f"variant {v} is not offered"
         rc = lib.latte_debug_attention(qkv.data_ptr(), out.data_ptr(), a.seqs, a.L, a.heads, a.hd, 1, a.L, a.L, 1, 1, st)
         assert rc == 0, rc
 

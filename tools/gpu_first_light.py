@@ -202,86 +202,16 @@ def gemm_bench():
 
 
 def gemm_epi_ablation():
-    """Same shape, different epilogues on the persistent kernel: 0 bf16 out, 1 GELU bf16, 2 gated fp32 RMW, 3 fp32 out, 4 no store."""
+    """Same shape, different epilogues on the persistent kernel: 0 bf16 out, 1 GELU bf16, 2 gated fp32 RMW, 3 fp32 out."""
     ms = _lib.c_f32()
     for (M, N, K, variant) in [(32768, 4608, 1152, 9), (32768, 4608, 1152, 8), (32768, 3456, 1152, 8), (32768, 1152, 4608, 8),
                                (32768, 1152, 1152, 8)]:
         row = []
-        for epi in (0, 1, 2, 3, 4):
+        for epi in (0, 1, 2, 3):
             check(lib.latte_bench_gemm(M, N, K, epi, 0, variant, 20, ctypes.byref(ms), stream_ptr()))
             tf = 2.0 * M * N * K / (ms.value * 1e-3) / 1e12
             row.append(f"epi{epi}: {ms.value*1e3:6.1f}us {tf:5.0f}TF")
         log(f"epi_ablation v{variant} M={M} N={N} K={K}: " + " | ".join(row))
-
-
-def gemm_loop_ablation():
-    """Main-loop ablations of the persistent kernel (no stores in all of them): 4 = full loop, 6 = no DMA in the loop,
-    7 = no LDS fragment reads, 8 = no MFMA, 9 = DMA from a cache-hot source, 10 / 11 = only A / only B DMA'd."""
-    ms = _lib.c_f32()
-    for (M, N, K, variant) in [(8192, 4096, 4096, 9), (32768, 4608, 1152, 9), (32768, 1152, 4608, 8), (8192, 4608, 4096, 8)]:
-        row = []
-        check(lib.latte_bench_gemm(M, N, K, 4, 0, variant, 20, ctypes.byref(ms), stream_ptr()))   # warm-up (clocks)
-        for epi in (4, 6, 7, 8, 9, 10, 11):
-            check(lib.latte_bench_gemm(M, N, K, epi, 0, variant, 20, ctypes.byref(ms), stream_ptr()))
-            tf = 2.0 * M * N * K / (ms.value * 1e-3) / 1e12
-            row.append(f"epi{epi}: {ms.value*1e3:6.1f}us {tf:5.0f}TF")
-        log(f"loop_ablation v{variant} M={M} N={N} K={K}: " + " | ".join(row))
-
-
-def gemm_trace():
-    """Per-wave phase times of the persistent kernel's main loop (workgroup 0), s_memtime ticks."""
-    names = ["L(reads)", "bar1 wait", "C issue", "vmcnt", "bar2 wait", "DMA issue"]
-    for (M, N, K, v) in [(32768, 4608, 1152, 9), (32768, 1152, 4608, 8)]:
-        Mp = (M + 255) // 256 * 256
-        A = torch.randn(Mp, K, device=dev).to(torch.bfloat16)
-        W = (torch.randn(N, K, device=dev) / K ** 0.5).to(torch.bfloat16)
-        bias = torch.randn(N, device=dev)
-        out = torch.zeros(Mp * N, dtype=torch.float32, device=dev)
-        gate = torch.randn(2 * N, device=dev)
-        for rep in range(3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            check(lib.latte_debug_gemm(ptr(A), ptr(W), ptr(bias), ptr(out), ptr(gate), M, N, K, 0, M, 12, 0, v, stream_ptr()))
-            e1.record()
-            torch.cuda.synchronize()
-        us = e0.elapsed_time(e1) * 1e3
-        t = out.view(torch.int64)[:64].cpu().view(8, 8)
-        log(f"trace v{v} M={M} N={N} K={K}: launch {us:.1f} us; wave rows: per-K-tile ticks; total ticks, K tiles")
-        for w in range(8):
-            kt = int(t[w, 7])
-            row = " ".join(f"{names[i]} {float(t[w, i]) / kt:7.1f}" for i in range(6))
-            log(f"   wave {w} (grp {w >> 2}): {row} | total {int(t[w, 6])} ticks = {int(t[w, 6]) / us:.1f} ticks/us, {kt} K tiles, {float(t[w, 6]) / kt:.1f} ticks/K tile")
-
-
-def gemm_trace_pw():
-    """Measurement build: per-wave phase times of the producer-wave kernel (variant 10, workgroup 0), s_memtime ticks.
-    Consumers: L(reads) | barrier-1 wait | C (MFMAs + second-half reads) | epilogue g1 | barrier-2 wait | epilogue g0.
-    Producers: DMA issue | vmcnt wait (even interval) | barrier | vmcnt wait (odd, incl. issue) | barrier | bookkeeping."""
-    names = {10: (["L(reads)", "bar1 wait", "C", "epi(g1)", "bar2 wait", "epi(g0)"],
-                  ["DMA issue", "vmcnt even", "bar even", "vmcnt odd", "bar odd", "bookkeep"]),
-             11: (["h0", "h1 head+lgkm", "barrier", "h1 rest", "epilogue", "refill"],
-                  ["DMA issue", "vmcnt wait", "barrier", "-", "-", "bookkeep"])}
-    for (M, N, K, var) in [(32768, 1152, 4608, 10), (32768, 1152, 4608, 11), (32768, 1152, 1152, 11), (32768, 4608, 1152, 11)]:
-        cn, pn = names[var]
-        A = torch.randn(M, K, device=dev).to(torch.bfloat16)
-        W = (torch.randn(N, K, device=dev) / K ** 0.5).to(torch.bfloat16)
-        bias = torch.randn(N, device=dev)
-        out = torch.zeros(M * N, dtype=torch.float32, device=dev)
-        gate = torch.randn(2 * N, device=dev)
-        for rep in range(3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            check(lib.latte_debug_gemm(ptr(A), ptr(W), ptr(bias), ptr(out), ptr(gate), M, N, K, 0, M, 12, 0, var, stream_ptr()))
-            e1.record()
-            torch.cuda.synchronize()
-        us = e0.elapsed_time(e1) * 1e3
-        t = out.view(torch.int64)[:96].cpu().view(12, 8)
-        log(f"trace v{var} M={M} N={N} K={K}: launch {us:.1f} us; per-K-tile ticks")
-        for w in range(12):
-            kt = max(int(t[w, 7]), 1)
-            nm = cn if w < 8 else pn
-            row = " ".join(f"{nm[i]} {float(t[w, i]) / kt:7.1f}" for i in range(6))
-            log(f"   wave {w:2d} ({'grp %d' % (w >> 2) if w < 8 else 'producer'}): {row} | {int(t[w, 6]) / us:.0f} ticks/us, {kt} K tiles, {float(t[w, 6]) / kt:.1f} ticks/K tile")
 
 
 def dma_probe():
@@ -340,43 +270,6 @@ def gemm_in_model():
         torch.cuda.empty_cache()
 
 
-def rmw_ahead():
-    """Measurement build (LATTE_DEBUG_BUILD=1): look-ahead depth / non-temporal loads of the synchronous read-modify-write
-    epilogue (LATTE_RMW_MODE = depth + 16 * nt), stand-alone with an output larger than the Infinity Cache (M = 65536:
-    the residual is HBM-cold, as inside the model) and inside the XL/2 forward at B = 8."""
-    ms = _lib.c_f32()
-    modes = [0, 3, 4, 6, 8, 12, 18, 20, 22, 24]
-    for (N, K, nm, tag) in [(1152, 1152, "proj", 0), (1152, 4608, "fc2", 1)]:
-        for M in (65536, 32768):
-            row = []
-            for mode in modes + [0]:
-                os.environ["LATTE_RMW_MODE"] = str(mode)
-                check(lib.latte_bench_gemm(M, N, K, 2, 0, 8 + 1000 * tag, 20, ctypes.byref(ms), stream_ptr()))
-                row.append(f"m{mode}: {ms.value*1e3:6.1f}")
-            log(f"rmw_ahead {nm} M={M} (us): " + " | ".join(row))
-    from latte_amd.models import Latte_models
-    B = 8
-    m = Latte_models["Latte-XL/2"](compute_dtype="bf16", max_batch=B, input_size=32, num_frames=16, extras=1)
-    with torch.no_grad():
-        for n_, p_ in m.named_parameters():
-            if float(p_.abs().max()) == 0.0:
-                p_.normal_(0, 0.02)
-    m = m.to(dev)
-    x = torch.randn(B, 16, 4, 32, 32, device=dev)
-    t = torch.full((B,), 500, device=dev, dtype=torch.int64)
-    os.environ["LATTE_RMW_VARIANT"] = "8"
-    for mode in modes + [0]:
-        os.environ["LATTE_RMW_MODE"] = str(mode)
-        m.profile_forward(x, t)
-        pr = [m.profile_forward(x, t) for _ in range(3)]
-        row = " ".join(f"{k}: {min(p[k][0] for p in pr) / max(pr[0][k][1], 1) * 1e3:6.1f}us" for k in
-                       ("gemm_proj", "gemm_fc2", "gemm_qkv", "gemm_fc1", "ln_modulate"))
-        tot = min(sum(v_[0] for v_ in p.values()) for p in pr)
-        log(f"rmw_ahead in-model B={B} mode {mode}: {row} | forward {tot:.3f} ms")
-    os.environ["LATTE_RMW_MODE"] = "0"
-    del os.environ["LATTE_RMW_VARIANT"]
-
-
 def attn_variants():
     """Attention kernels on the model shapes: XL/2 spatial (L = 256) through attn_full / the block kernel / the generic flash
     kernel, Latte-1 spatial (L = 1024, B = 2) through the block kernel / flash, temporal (L = 16)."""
@@ -413,31 +306,6 @@ def attn_variants():
     log(f"attn_variants XL/2 temporal L=16 B=8: {us:.1f}us, {8*16*256*4*1152*2/us/1e6:.2f} TB/s algorithmic")
     us, tf, _ = run(8, 16, 256, "temporal_adjacent", None)
     log(f"attn_variants XL/2 temporal L=16 B=8, frames of a token in adjacent rows: {us:.1f}us, {8*16*256*4*1152*2/us/1e6:.2f} TB/s algorithmic")
-
-
-def group_m_sweep():
-    """Measurement build: tile rows walked together by the persistent GEMM (LATTE_GROUP_M=epi:value), inside the XL/2 forward."""
-    from latte_amd.models import Latte_models
-    B = 8
-    m = Latte_models["Latte-XL/2"](compute_dtype="bf16", max_batch=B, input_size=32, num_frames=16, extras=1)
-    with torch.no_grad():
-        for n_, p_ in m.named_parameters():
-            if float(p_.abs().max()) == 0.0:
-                p_.normal_(0, 0.02)
-    m = m.to(dev)
-    x = torch.randn(B, 16, 4, 32, 32, device=dev)
-    t = torch.full((B,), 500, device=dev, dtype=torch.int64)
-    for spec in ("", "2:5", "2:6", "2:4", "2:3", "2:16", "0:4,1:4", "0:6,1:6", "0:16,1:16", "0:2,1:2", ""):
-        if spec:
-            os.environ["LATTE_GROUP_M"] = spec
-        else:
-            os.environ.pop("LATTE_GROUP_M", None)
-        m.profile_forward(x, t)
-        pr = [m.profile_forward(x, t) for _ in range(3)]
-        row = " ".join(f"{k}: {min(p[k][0] for p in pr) / max(pr[0][k][1], 1) * 1e3:6.1f}us" for k in
-                       ("gemm_qkv", "gemm_proj", "gemm_fc1", "gemm_fc2"))
-        log(f"group_m '{spec}': {row} | forward {min(sum(v_[0] for v_ in p.values()) for p in pr):.3f} ms")
-    os.environ.pop("LATTE_GROUP_M", None)
 
 
 def gemm_stagger():
