@@ -306,6 +306,42 @@ int latte_debug_conv3x3_f32(const void* in, const float* w, const float* bias, c
 int latte_debug_groupnorm_f32(const float* x, void* y, const float* gamma, const float* beta, int N, int HW, int C, int silu,
                               int dtype, void* stream);
 
+/* launch_groupnorm (csrc/vae.hip) with its three defaulted arguments exposed: x half or (x_is_f32) fp32 NHWC [N, HW, C], C in {128, 256,
+ * 512}, y half; y_lo (may be NULL) receives the f16 rounding residual of y (the split-operand convolutions' second input); eps is the
+ * variance floor (1e-6 SD-VAE, 1e-5 the temporal decoder's blocks); the statistics pass uses min(max(HW / 256, 1), max_slabs) slabs.
+ * stats_out (may be NULL): fp32 [N][32][2] = (mean, rstd) per sample and group, copied from the launcher's statistics buffer.
+ * Refused: max_slabs < 1; max_slabs > groupnorm_max_slabs() (256) unless N == 1 -- the temporal form, one sample of T HW pixels -- and
+ * then at most 64 times it; a C the kernels are not built for; buffers that are not 16-byte aligned; a dtype other than f16. */
+int latte_debug_groupnorm_ex(const void* x, int x_is_f32, void* y, void* y_lo_or_null, const float* gamma, const float* beta, int N, int HW,
+                             int C, int silu, float eps, int max_slabs, float* stats_out_or_null, int dtype, void* stream);
+/* The decoder's small kernels (csrc/vae.hip), one launcher each; every half buffer is f16.
+ * latte_debug_vae_post_quant: z fp32 NCHW [N, 4, hw] * z_scale -> post_quant_conv (w [4, 4], b [4]) -> out fp32 NHWC [N, hw, 4].
+ * latte_debug_vae_conv_in: x fp32 NHWC [N, H, W, 4], w fp32 [Cout, 4, 3, 3] (packed here), bias [Cout] -> out fp32 NHWC [N, H, W, Cout];
+ *   Cout must be even and at least 2 (the kernel stores channel pairs).
+ * latte_debug_vae_conv_out: x half NHWC [N, H, W, C] (x_lo: its f16 rounding residual, or NULL), w fp32 [3, C, 3, 3] (packed here), bias [3]
+ *   -> out_mode 0: fp32 NCHW [N, 3, H, W]; 1: uint8 NHWC [N, H, W, 3] = ((v * 0.5 + 0.5) * 255 + 0.5).clamp(0, 255) truncated
+ *   (sample.py:122).  C % 8 == 0 and 27 C floats within 64 KiB of LDS; C == 128 with W % 16 == 0 runs conv_out_c128_kernel, every other
+ *   shape conv_out_kernel.
+ * latte_debug_vae_softmax_rows: p half [rows, L] = softmax(scale * s fp32 [rows, L]) per row; L % 64 == 0, 64 <= L <= 4096.
+ * latte_debug_vae_time_conv_out: Conv3d(3, 3, (3, 1, 1), padding (1, 0, 0)) over the T frames of one video: in fp32 [T, 3, HW], w [3, 3, 3]
+ *   = [co][ci][tap], bias [3] -> out_mode 0: fp32 [T, 3, HW]; 1: uint8 [T, HW, 3] (the formula above).
+ * latte_debug_vae_pack_conv_t: w fp32 [Cout, Cin, 3] -> out half [Cout][3 Cin] (k = tap Cin + ci), times sigmoid(*mix) when mix != NULL;
+ *   out_lo (may be NULL): the f16 rounding residual.
+ * latte_debug_vae_scale_by_sigmoid: out[i] = in[i] * sigmoid(*mix), n fp32 values (mix is a device pointer, not NULL).
+ * latte_debug_vae_pack_conv_w: w fp32 [Cout, Cin, 3, 3] -> out half [Cout][9 Cin] (k = (ky 3 + kx) Cin + ci); out_lo as above.
+ * latte_debug_convert_split: out = f16(in), out_lo = f16(in - out), n values (launch_convert_f32_to_h16_split).
+ * Each refuses NULL buffers (other than the ones marked optional) and non-positive sizes; out_mode must be 0 or 1. */
+int latte_debug_vae_post_quant(const float* z, const float* w, const float* b, float* out, int N, int hw, float z_scale, void* stream);
+int latte_debug_vae_conv_in(const float* x, const float* w, const float* bias, float* out, int N, int H, int W, int Cout, void* stream);
+int latte_debug_vae_conv_out(const void* x, const void* x_lo_or_null, const float* w, const float* bias, void* out, int N, int H, int W, int C,
+                             int out_mode, void* stream);
+int latte_debug_vae_softmax_rows(const float* s, void* p, int rows, int L, float scale, void* stream);
+int latte_debug_vae_time_conv_out(const float* in, const float* w, const float* bias, void* out, int T, int HW, int out_mode, void* stream);
+int latte_debug_vae_pack_conv_t(const float* w, const float* mix_or_null, void* out, void* out_lo_or_null, int Cout, int Cin, void* stream);
+int latte_debug_vae_scale_by_sigmoid(const float* in, float* out, int n, const float* mix, void* stream);
+int latte_debug_vae_pack_conv_w(const float* w, void* out, void* out_lo_or_null, int Cout, int Cin, void* stream);
+int latte_debug_convert_split(const float* in, void* out, void* out_lo, int64_t n, void* stream);
+
 /* Runs the VAE decoder (include/latte_amd.h) up to and including stage `stop_after` and returns that stage's NHWC
  * activation (the fp32 residual stream) (trace_dims = N, H, W, C).  Stages: 0 conv_in, 1 mid.resnets.0, 2 mid.attentions.0,
  * 3 mid.resnets.1, then for up block i: three resnets and (i < 3) the upsampler -> 4..18.  Localises a divergence. */

@@ -249,6 +249,17 @@ PROTOTYPES = {
                                         c_void]),
     "latte_debug_groupnorm_f32": (c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_void]),
     "latte_debug_groupnorm": (c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_void]),
+    "latte_debug_groupnorm_ex": (c_int, [c_void, c_int, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_f32, c_int, c_void,
+                                         c_int, c_void]),
+    "latte_debug_vae_post_quant": (c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_f32, c_void]),
+    "latte_debug_vae_conv_in": (c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void]),
+    "latte_debug_vae_conv_out": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_void]),
+    "latte_debug_vae_softmax_rows": (c_int, [c_void, c_void, c_int, c_int, c_f32, c_void]),
+    "latte_debug_vae_time_conv_out": (c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_void]),
+    "latte_debug_vae_pack_conv_t": (c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_void]),
+    "latte_debug_vae_scale_by_sigmoid": (c_int, [c_void, c_void, c_int, c_void, c_void]),
+    "latte_debug_vae_pack_conv_w": (c_int, [c_void, c_void, c_void, c_int, c_int, c_void]),
+    "latte_debug_convert_split": (c_int, [c_void, c_void, c_void, c_i64, c_void]),
 }
 
 _lib = None

@@ -777,6 +777,103 @@ int latte_debug_groupnorm(const void* x, void* y, const float* gamma, const floa
   return rc;
 }
 
+// ---- the VAE's GroupNorm with its defaulted arguments, and the small kernels of csrc/vae.hip: argument checks + the engines' own
+// launchers, unchanged (f16 half buffers throughout: the VAE launchers refuse bf16)
+int latte_debug_groupnorm_ex(const void* x, int x_is_f32, void* y, void* y_lo_or_null, const float* gamma, const float* beta, int N, int HW,
+                             int C, int silu, float eps, int max_slabs, float* stats_out_or_null, int dtype, void* stream) {
+  if (!x || !y || !gamma || !beta || N < 1 || HW < 1 || bad_mode(x_is_f32) || bad_mode(silu) || !(eps > 0.0f) || misaligned(x, 16) ||
+      misaligned(y, 16) || misaligned(y_lo_or_null, 16) || misaligned(gamma, 16) || misaligned(beta, 16) || (int64_t)N * HW > 0x7fffffff)
+    return fail(LATTE_ERR_INVALID, "groupnorm_ex: bad arguments (x_is_f32 and silu 0 or 1, eps > 0, 16-byte aligned buffers)");
+  if (C != 128 && C != 256 && C != 512) return fail(LATTE_ERR_INVALID, "groupnorm_ex: C must be 128, 256 or 512");
+  if (dtype != LATTE_DTYPE_F16) return fail(LATTE_ERR_INVALID, "groupnorm_ex: the VAE kernels are built for f16 operands only");
+  if (max_slabs < 1) return fail(LATTE_ERR_INVALID, "groupnorm_ex: max_slabs must be at least 1");
+  if (max_slabs > groupnorm_max_slabs() * 64 || (max_slabs > groupnorm_max_slabs() && N != 1))
+    return fail(LATTE_ERR_INVALID, "groupnorm_ex: max_slabs beyond groupnorm_max_slabs() is the one-sample form (N == 1), at most 64 times it");
+  hipStream_t st = (hipStream_t)stream;
+  float *partial = nullptr, *stats = nullptr;
+  LATTE_HIP(hipMalloc((void**)&partial, (size_t)N * max_slabs * 64 * 4));
+  LATTE_HIP(hipMalloc((void**)&stats, (size_t)N * 64 * 4));
+  int rc = launch_groupnorm(x, x_is_f32, (half_t*)y, gamma, beta, partial, stats, N, HW, C, silu, dtype, st, eps, max_slabs, (half_t*)y_lo_or_null);
+  if (!rc && stats_out_or_null &&
+      hipMemcpyAsync(stats_out_or_null, stats, (size_t)N * 64 * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
+    rc = fail(LATTE_ERR_HIP, "groupnorm_ex: statistics copy failed");
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(partial);
+  (void)hipFree(stats);
+  return rc;
+}
+
+int latte_debug_vae_post_quant(const float* z, const float* w, const float* b, float* out, int N, int hw, float z_scale, void* stream) {
+  if (!z || !w || !b || !out || N < 1 || hw < 1 || (int64_t)N * hw > 0x7fffffff / 4 || misaligned(out, 16))
+    return fail(LATTE_ERR_INVALID, "vae_post_quant: bad arguments (out 16-byte aligned)");
+  return launch_post_quant(z, w, b, out, N, hw, z_scale, (hipStream_t)stream);
+}
+
+int latte_debug_vae_conv_in(const float* x, const float* w, const float* bias, float* out, int N, int H, int W, int Cout, void* stream) {
+  if (!x || !w || !bias || !out || N < 1 || H < 1 || W < 1 || (int64_t)N * H * W > 0x7fffffff || misaligned(out, 8))
+    return fail(LATTE_ERR_INVALID, "vae_conv_in: bad arguments");
+  if (Cout < 2 || Cout % 2) return fail(LATTE_ERR_INVALID, "vae_conv_in: Cout must be even and at least 2");
+  hipStream_t st = (hipStream_t)stream;
+  float* wt = nullptr;
+  LATTE_HIP(hipMalloc((void**)&wt, (size_t)36 * Cout * 4));
+  int rc = launch_pack_small_w(w, wt, Cout, 4, 1, st);
+  if (!rc) rc = launch_conv_in(x, wt, bias, out, N, H, W, Cout, st);
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(wt);
+  return rc;
+}
+
+int latte_debug_vae_conv_out(const void* x, const void* x_lo_or_null, const float* w, const float* bias, void* out, int N, int H, int W, int C,
+                             int out_mode, void* stream) {
+  if (!x || !w || !bias || !out || N < 1 || H < 1 || W < 1 || (int64_t)N * H * W > 0x7fffffff / 3 || misaligned(x, 16) ||
+      misaligned(x_lo_or_null, 16))
+    return fail(LATTE_ERR_INVALID, "vae_conv_out: bad arguments (x and x_lo 16-byte aligned)");
+  if (C < 8 || C % 8) return fail(LATTE_ERR_INVALID, "vae_conv_out: C must be a positive multiple of 8");
+  if ((int64_t)27 * C * (int64_t)sizeof(float) > 65536)
+    return fail(LATTE_ERR_INVALID, "vae_conv_out: 27 C floats of weights exceed the default dynamic LDS limit (64 KiB)");
+  if (bad_mode(out_mode)) return fail(LATTE_ERR_INVALID, "vae_conv_out: out_mode must be 0 (fp32 NCHW) or 1 (uint8 NHWC)");
+  hipStream_t st = (hipStream_t)stream;
+  float* wt = nullptr;
+  LATTE_HIP(hipMalloc((void**)&wt, (size_t)27 * C * 4));
+  int rc = launch_pack_small_w(w, wt, 3, C, 0, st);
+  if (!rc) rc = launch_conv_out((const half_t*)x, wt, bias, out, N, H, W, C, out_mode, LATTE_DTYPE_F16, st, (const half_t*)x_lo_or_null);
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(wt);
+  return rc;
+}
+
+int latte_debug_vae_softmax_rows(const float* s, void* p, int rows, int L, float scale, void* stream) {
+  if (!s || !p || rows < 1) return fail(LATTE_ERR_INVALID, "vae_softmax_rows: bad arguments");
+  if (L < 64 || L % 64 || L > 4096) return fail(LATTE_ERR_INVALID, "vae_softmax_rows: need L % 64 == 0 and 64 <= L <= 4096");
+  return launch_softmax_rows(s, (half_t*)p, rows, L, scale, LATTE_DTYPE_F16, (hipStream_t)stream);
+}
+
+int latte_debug_vae_time_conv_out(const float* in, const float* w, const float* bias, void* out, int T, int HW, int out_mode, void* stream) {
+  if (!in || !w || !bias || !out || T < 1 || HW < 1) return fail(LATTE_ERR_INVALID, "vae_time_conv_out: bad arguments");
+  if (bad_mode(out_mode)) return fail(LATTE_ERR_INVALID, "vae_time_conv_out: out_mode must be 0 (fp32 NCHW) or 1 (uint8 NHWC)");
+  return launch_time_conv_out(in, w, bias, out, T, HW, out_mode, (hipStream_t)stream);
+}
+
+int latte_debug_vae_pack_conv_t(const float* w, const float* mix_or_null, void* out, void* out_lo_or_null, int Cout, int Cin, void* stream) {
+  if (!w || !out || Cout < 1 || Cin < 1) return fail(LATTE_ERR_INVALID, "vae_pack_conv_t: bad arguments");
+  return launch_pack_conv_t(w, (half_t*)out, Cout, Cin, mix_or_null, LATTE_DTYPE_F16, (hipStream_t)stream, (half_t*)out_lo_or_null);
+}
+
+int latte_debug_vae_scale_by_sigmoid(const float* in, float* out, int n, const float* mix, void* stream) {
+  if (!in || !out || !mix || n < 1) return fail(LATTE_ERR_INVALID, "vae_scale_by_sigmoid: bad arguments");
+  return launch_scale_by_sigmoid(in, out, n, mix, (hipStream_t)stream);
+}
+
+int latte_debug_vae_pack_conv_w(const float* w, void* out, void* out_lo_or_null, int Cout, int Cin, void* stream) {
+  if (!w || !out || Cout < 1 || Cin < 1) return fail(LATTE_ERR_INVALID, "vae_pack_conv_w: bad arguments");
+  return launch_pack_conv_w(w, (half_t*)out, Cout, Cin, LATTE_DTYPE_F16, (hipStream_t)stream, (half_t*)out_lo_or_null);
+}
+
+int latte_debug_convert_split(const float* in, void* out, void* out_lo, int64_t n, void* stream) {
+  if (!in || !out || !out_lo || n < 1) return fail(LATTE_ERR_INVALID, "convert_split: bad arguments");
+  return launch_convert_f32_to_h16_split(in, (half_t*)out, (half_t*)out_lo, n, LATTE_DTYPE_F16, (hipStream_t)stream);
+}
+
 int latte_debug_set_choice(const char* name, int value) {
   if (set_debug_choice(name, value) != 0)
     return fail(LATTE_ERR_INVALID, std::string("latte_debug_set_choice: unknown name or value not offered by this build: ") + (name ? name : "(null)"));

@@ -257,6 +257,92 @@ def test_vae_stagewise_vs_oracle(lib, cd, tol):
     assert max(errs) < tol, errs
 
 
+ATTN = "decoder.mid_block.attentions.0."
+
+
+def attention_inputs():
+    """weights of vo.init_state_dict with to_v.bias and to_out.0.bias redrawn N(0, 1) (a missed bias fold is then as large as the
+    contribution itself) and two frames of a 16 x 16 latent.  The four projection matrices are rounded to f16 values first: with
+    unrounded ones the engine's f16 weight pack alone puts a correct engine at 2.3 x the yardstick below (CPU restatement with and
+    without f16 weights: 1.69e-4 against 7.2e-5), which would say nothing about run_mid_attention; the weight pack is covered by the
+    whole-decode tests."""
+    sd = vo.init_state_dict(seed=12)
+    g = torch.Generator().manual_seed(13)
+    sd[ATTN + "to_v.bias"] = torch.randn(512, generator=g)
+    sd[ATTN + "to_out.0.bias"] = torch.randn(512, generator=g)
+    for k in ("to_q", "to_k", "to_v", "to_out.0"):     # f16-representable projection weights: the engine packs them to f16 at load, which
+        sd[ATTN + k + ".weight"] = sd[ATTN + k + ".weight"].half().float()   # is then exact, so the six activation roundings are all there is
+    return sd, torch.randn(2, 4, 16, 16, generator=g)
+
+
+def attention_contribution(sd, x, half_roundings=False):
+    """The mid-block attention's own contribution (its output before the residual is added) from the NHWC activation x [N, H, W, 512]:
+    GroupNorm (eps 1e-6), one head of 512, softmax, out-projection, in x's precision.  half_roundings: round to f16 exactly where
+    run_mid_attention (csrc/vae_engine.cpp) does -- the normed input, q, k, V0^T (the value bias is folded into the output bias
+    there: to_out(P (V0 + 1 bv^T)) = to_out(P V0) + Wo bv + bo), P and the attention output."""
+    r = (lambda t: t.half().to(t.dtype)) if half_roundings else (lambda t: t)
+    w = lambda k: sd[ATTN + k].to(x.dtype)
+    n, hh, ww, c = x.shape
+    h = F.group_norm(x.permute(0, 3, 1, 2), 32, w("group_norm.weight"), w("group_norm.bias"), 1e-6)
+    h = r(h.reshape(n, c, hh * ww).transpose(1, 2))
+    q, k = r(F.linear(h, w("to_q.weight"), w("to_q.bias"))), r(F.linear(h, w("to_k.weight"), w("to_k.bias")))
+    v0 = r(F.linear(h, w("to_v.weight")))
+    p = r(torch.softmax(q @ k.transpose(1, 2) * (c ** -0.5), dim=-1))
+    o = r(p @ v0)
+    b_eff = w("to_out.0.weight") @ w("to_v.bias") + w("to_out.0.bias")
+    return F.linear(o, w("to_out.0.weight"), b_eff).reshape(n, hh, ww, c)
+
+
+def test_attention_contribution_restatement_is_the_oracle_attention():
+    """the helper above, without roundings, is the oracle's attention minus its residual (so the bias fold it restates is right)"""
+    sd, _ = attention_inputs()
+    x = torch.randn(2, 16, 16, 512, generator=torch.Generator().manual_seed(1)).double()
+    sd64 = {k: v.double() for k, v in sd.items()}
+    want = vo._attention(sd64, ATTN, x.permute(0, 3, 1, 2)) - x.permute(0, 3, 1, 2)
+    assert rel_l2(attention_contribution(sd, x).permute(0, 3, 1, 2), want) < 1e-12
+    nobias = dict(sd)
+    nobias[ATTN + "to_v.bias"] = torch.zeros(512)
+    assert rel_l2(attention_contribution(nobias, x), attention_contribution(sd, x)) > 0.3     # a missed fold of the value bias is large
+
+
+@pytest.mark.gpu
+def test_vae_mid_attention_contribution(lib):
+    """Stage 2 of the trace is the residual stream PLUS the attention's contribution, held to 1e-3 of the stream; here the contribution
+    alone (stage 2 - stage 1) is compared with the fp64 attention of the engine's own stage-1 activation.  The tolerance is measured
+    against a yardstick, not derived: a CPU restatement that rounds to f16 where run_mid_attention does has some relative L2 error
+    against fp64; the engine must stay within twice that (summation order and the fast exponential are small next to six f16
+    roundings).  Every frame's contribution must equal, bit for bit, that frame decoded alone."""
+    import ctypes
+    from latte_amd._lib import check, ptr, stream_ptr
+    from latte_amd.vae import AutoencoderKL
+    sd, z = attention_inputs()
+    vae = AutoencoderKL(latent_size=16, max_frames=2, compute_dtype="f16")
+    vae.load_state_dict(sd)
+    vae.to("cuda")
+    eng = vae._engine(2, 16)
+    numel, dims = ctypes.c_int64(), (ctypes.c_int * 4)()
+
+    def stage(zz, k):
+        buf = torch.empty(zz.shape[0] * 16 * 16 * 512, device="cuda")
+        check(lib.latte_debug_vae_trace(eng, ptr(zz), zz.shape[0], 1.0, k, ptr(buf), ctypes.byref(numel), dims, stream_ptr()))
+        torch.cuda.synchronize()
+        assert list(dims) == [zz.shape[0], 16, 16, 512] and numel.value == buf.numel()
+        return buf.view(zz.shape[0], 16, 16, 512)
+    zd = z.cuda()
+    s1, s2 = stage(zd, 1), stage(zd, 2)
+    got = (s2.double() - s1.double()).cpu()
+    x = s1.cpu()
+    want = attention_contribution(sd, x.double())
+    yard = rel_l2(attention_contribution(sd, x, half_roundings=True).double(), want)
+    err = rel_l2(got, want)
+    print(f"mid attention contribution: engine rel-L2 vs fp64 {err:.3e}, f16-rounded CPU restatement {yard:.3e}, ratio {err / yard:.2f}; "
+          f"|contribution| / |stream| {float(want.norm() / x.double().norm()):.3f}")
+    assert err <= 2.0 * yard
+    for f in range(2):
+        a1, a2 = stage(zd[f:f + 1], 1), stage(zd[f:f + 1], 2)
+        assert torch.equal(a1[0], s1[f]) and torch.equal(a2[0], s2[f])
+
+
 @pytest.mark.gpu
 def test_vae_full_size_decode_vs_oracle(lib):
     """The headline size: frames of a 32x32 latent -> 256x256 against the oracle (2 frames: ~10-20 s of CPU conv),
