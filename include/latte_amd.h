@@ -217,6 +217,36 @@ int latte_training_losses(const latte_schedule_t* s, int loss_type, const float*
                           const float* model_out, const int64_t* t, int batch, int frames, int channels, int hw, float* workspace,
                           int64_t workspace_floats, float* mse_out, float* vb_out, float* loss_out, void* stream);
 
+/* ------------------------------------------------------------------ likelihood evaluation (bits per dimension)
+ * GaussianDiffusion.calc_bpd_loop (gaussian_diffusion.py:813-866): the variational bound of a batch of clips, term by term.
+ * One RESPACED index is shared by the batch (:836); tensors are [batch, frames, channels, hw] fp32 on the device, model_out with
+ * 2 * channels when the schedule's variance is learned (the layout latte_sampler_step reads).
+ *   latte_prior_bpd     _prior_bpd (:797-811): KL(q(x_T | x_0) || N(0, I)) / ln 2 per sample -> out[batch].
+ *   latte_bpd_terms     one column of the loop from x_0, x_t, the noise that made x_t and the model's output on
+ *                       (x_t, timestep_map[index]), per sample b, written at [b * out_stride]:
+ *                         vb         _vb_terms_bpd (:686-717): p_mean_variance (:254-336) for the schedule's ModelMeanType /
+ *                                    ModelVarType, pred_xstart clamped to [-1, 1] BEFORE the posterior mean when clip_denoised
+ *                                    (:316-330), KL against the true posterior in bits; the discretized decoder NLL at index 0
+ *                         xstart_mse mean_flat((pred_xstart - x_0)^2)                                              (:850)
+ *                         mse        mean_flat((eps - noise)^2), eps = _predict_eps_from_xstart(x_t, pred_xstart)  (:345-348,:851-852)
+ *                       pred_xstart_out (may be NULL) receives the [batch, frames, channels, hw] prediction.
+ *                       workspace: latte_bpd_workspace_floats(batch, frames * channels * hw) floats.  The sums are taken in a fixed
+ *                       order without atomics: equal inputs give equal bits, and a sample's numbers do not depend on the batch.
+ *   latte_bpd_loop      the whole loop inside the engine for respaced steps start_index ... end_index DESCENDING (:835): per step
+ *                       noise (:837), q_sample (:838), the unguided Latte.forward on (x_t, timestep_map[i]) with the chain
+ *                       conditioning latte_sample_loop_ex uses, then the terms.  vb / xstart_mse / mse are [batch, n_steps] with
+ *                       n_steps = start_index - end_index + 1; column k is the k-th executed step, so a full chain has the
+ *                       reference's column order (t = T-1 first, :854).  noise: [n_steps][batch, frames, channels, hw] or NULL
+ *                       = one draw per step from the engine's Philox stream (option "seed"), as the sampling loop draws.
+ *                       Class-conditional (y: int64[batch]) and unconditional models.  Stream-ordered, no synchronisation. */
+int latte_prior_bpd(const latte_schedule_t* s, const float* x_start, int batch, int64_t numel_per_sample, float* out, void* stream);
+int64_t latte_bpd_workspace_floats(int batch, int64_t numel_per_sample);
+int latte_bpd_terms(const latte_schedule_t* s, int index, int clip_denoised, const float* x_start, const float* x_t, const float* noise,
+                    const float* model_out, int batch, int frames, int channels, int hw, float* workspace, int64_t workspace_floats,
+                    float* vb_out, float* xstart_mse_out, float* mse_out, int64_t out_stride, float* pred_xstart_out, void* stream);
+int latte_bpd_loop(latte_engine_t* e, const latte_schedule_t* s, int clip_denoised, const float* x_start, const int64_t* y, int batch,
+                   int start_index, int end_index, const float* noise, float* vb, float* xstart_mse, float* mse, void* stream);
+
 /* ------------------------------------------------------------------ training step
  * Replaces the body of the reference's optimisation loop, train.py:197-236, for the class-conditional / unconditional Latte
  * (train.py:213-218 refuses text-to-video training):

@@ -81,6 +81,11 @@ PROTOTYPES = {
     "latte_training_workspace_floats": (c_i64, [c_int, c_i64]),
     "latte_training_losses": (c_int, [c_void, c_int, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void,
                                       c_i64, c_void, c_void, c_void, c_void]),
+    "latte_prior_bpd": (c_int, [c_void, c_void, c_int, c_i64, c_void, c_void]),
+    "latte_bpd_workspace_floats": (c_i64, [c_int, c_i64]),
+    "latte_bpd_terms": (c_int, [c_void, c_int, c_int, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void, c_i64,
+                                c_void, c_void, c_void, c_i64, c_void, c_void]),
+    "latte_bpd_loop": (c_int, [c_void, c_void, c_int, c_void, c_void, c_int, c_int, c_int, c_void, c_void, c_void, c_void, c_void]),
     "latte_trainer_create": (c_int, [ctypes.POINTER(ModelConfig), c_int, ctypes.POINTER(c_void)]),
     "latte_trainer_destroy": (None, [c_void]),
     "latte_trainer_num_params": (c_int, [c_void]),

@@ -421,4 +421,15 @@ int training_terms_blocks(size_t per_sample);
 int launch_training_combine(const float* mse, const float* vb, int has_vb, int kl_only, float vb_scale, int batch, float* mse_out,
                             float* vb_out, float* loss_out, hipStream_t st);
 
+
+// ---- likelihood evaluation (gaussian_diffusion.py:813-866 calc_bpd_loop): one respaced index for the batch
+int launch_q_sample_scalar(float sqrt_ab, float sqrt_one_minus_ab, const float* x_start, const float* noise, size_t total, float* x_t,
+                           hipStream_t st);
+// per-sample vb (KL, or the decoder NLL when c.nonzero == 0, in bits), xstart_mse, mse -> out[b * out_stride];
+// partial: [batch][blocks][3] scratch, blocks = training_terms_blocks(per_sample); pred_xstart_out may be nullptr
+int launch_bpd_terms(const SamplerCoefs& c, const float* x_start, const float* x_t, const float* noise, const float* model_out, int batch,
+                     int frames, int channels, int hw, float* partial, int blocks_per_sample, float* vb, float* xstart_mse, float* mse,
+                     int64_t out_stride, float* pred_xstart_out, hipStream_t st);
+int launch_prior_bpd(float mean_coef, float log_variance, const float* x_start, int batch, size_t per_sample, float* out, hipStream_t st);
+
 }  // namespace latte

@@ -118,6 +118,8 @@ struct latte_engine {
   std::vector<int64_t> temb_own_map;     // the timestep_map temb_own currently holds (empty: none); a chain run in several
                                          // latte_sample_loop segments computes its table once
   int64_t temb_table_cap = 0, temb_own_cap = 0, temb_cap = 0, cond_cap = 0, mod_all_cap = 0;
+  float *bpd_xt = nullptr, *bpd_ws = nullptr;   // latte_bpd_loop: x_t of the step, the reduction's per-block slots
+  int64_t bpd_xt_cap = 0, bpd_ws_cap = 0;
   WeightSlots weights;
   DeviceArena arena;
   uint64_t seed = 0, rng_offset = 0;
@@ -387,6 +389,62 @@ int compute_temb_table(latte_engine* e, const latte_schedule_t* s, float* out, h
                                   e->temb_work + (size_t)r0 * D, rows, D, 256, D, st))) return rc;
     if ((rc = launch_small_linear(IN_SILU, e->temb_work + (size_t)r0 * D, nullptr, e->t2_w, e->t2_b, nullptr, nullptr,
                                   out + (size_t)r0 * D, rows, D, D, D, st))) return rc;
+  }
+  return LATTE_OK;
+}
+
+// ---- conditioning of a whole chain (latte_sample_loop_ex, latte_bpd_loop): it depends on (timestep, label) only, never on x.
+struct ChainCond {
+  const float* temb;   // [num_timesteps, D] timestep-embedding table, own or installed
+  int bu;              // conditioning rows per step: 1 for an unconditional model, else the batch
+  int chunk_steps;     // steps whose rows fit mod_all at once
+};
+
+// Picks the timestep-embedding table (computing the engine's own when none is installed for this timestep_map) and sizes the row
+// buffers.  The conditioning rows of the chain are produced in chunks of <= 256 rows (= 256 / bu steps), right before the steps
+// that use them: the adaLN outputs are 783 KB per row at XL/2 (nmod = 195 840 fp32), so the whole chain at once would
+// be 3.1 GB for 250 guided steps at B = 16.  The adaLN weights are streamed once per 64 rows either way.
+int chain_prepare(latte_engine* e, const latte_schedule_t* s, int bu, int n_run, hipStream_t st, ChainCond* cc) {
+  const int n = s->num_timesteps, D = e->D;
+  int rc;
+  cc->bu = bu;
+  if (e->temb_table_n == n && e->temb_table_map == s->timestep_map) {   // installed for exactly this timestep_map
+    cc->temb = e->temb_table;
+  } else {
+    if (e->temb_own_map != s->timestep_map) {
+      e->temb_own_map.clear();
+      if ((rc = grow(e, &e->temb_own, &e->temb_own_cap, (int64_t)n * D))) return rc;
+      if ((rc = compute_temb_table(e, s, e->temb_own, st))) return rc;
+      e->temb_own_map = s->timestep_map;
+    }
+    cc->temb = e->temb_own;
+  }
+  cc->chunk_steps = std::max(1, 256 / bu);
+  const int64_t rows_chunk = (int64_t)std::min(cc->chunk_steps, n_run) * bu;
+  if ((rc = grow(e, &e->cond_rows, &e->cond_cap, rows_chunk * D))) return rc;
+  if ((rc = grow(e, &e->mod_all, &e->mod_all_cap, rows_chunk * e->nmod))) return rc;
+  if (e->cfg.extras == 78 && (rc = grow(e, &e->cond_rows_t, &e->cond_t_cap, rows_chunk * D))) return rc;
+  return LATTE_OK;
+}
+
+// conditioning of respaced steps [lo, lo + cnt) into mod_all: rows ordered by index ascending, row (i - lo) * bu + b
+int chain_conditioning(latte_engine* e, const ChainCond& cc, const int64_t* y, int lo, int cnt, hipStream_t st) {
+  const int D = e->D, ex = e->cfg.extras, bu = cc.bu;
+  const float* temb = cc.temb;
+  const size_t fo = (size_t)e->cfg.depth * 6 * D;
+  const int64_t rows_all = (int64_t)cnt * bu;
+  int r2;
+  if ((r2 = launch_cond_rows(temb + (size_t)lo * D, ex == 2 ? e->ytab : ex == 78 ? e->txt_proj : nullptr,
+                             ex == 78 ? e->iota : y, e->cond_rows, cnt, bu, D, st))) return r2;
+  if (ex == 78 &&   // t-only rows for the final layer (latte.py:372-373)
+      (r2 = launch_cond_rows(temb + (size_t)lo * D, nullptr, nullptr, e->cond_rows_t, cnt, bu, D, st))) return r2;
+  for (int64_t r0 = 0; r0 < rows_all; r0 += 64) {
+    const int rows = (int)std::min<int64_t>(64, rows_all - r0);
+    if ((r2 = launch_small_linear(IN_PLAIN, e->cond_rows + (size_t)r0 * D, nullptr, e->ada_w, e->ada_b, nullptr, nullptr,
+                                  e->mod_all + (size_t)r0 * e->nmod, rows, e->nmod, D, e->nmod, st))) return r2;
+    if (ex == 78 &&
+        (r2 = launch_small_linear(IN_PLAIN, e->cond_rows_t + (size_t)r0 * D, nullptr, e->ada_w + fo * D, e->ada_b + fo, nullptr,
+                                  nullptr, e->mod_all + (size_t)r0 * e->nmod + fo, rows, 2 * D, D, e->nmod, st))) return r2;
   }
   return LATTE_OK;
 }
@@ -757,59 +815,22 @@ int latte_sample_loop_ex(latte_engine_t* e, const latte_schedule_t* s, int metho
   //   mod[i, b, :] = all 28 adaLN_modulation + the final layer's, = Linear(SiLU(c))   latte.py:172-178,192-198
   // Unconditional models have one row per step shared by every sample (row stride 0).  The adaLN weights (0.9 GB
   // fp32) are then streamed once per 64 rows instead of once per denoising step.
-  const int D = e->D;
   const int n_run = start_index - end_index + 1;
   const int ex = e->cfg.extras;
   const int bu = ex == 1 ? 1 : batch;
   if (ex == 2 && y == nullptr) return fail(LATTE_ERR_INVALID, "sample_loop: class-conditional model needs y");
   if (ex == 78 && e->txt_rows != batch)
     return fail(LATTE_ERR_STATE, "sample_loop: text-conditioned model needs latte_engine_set_text_embedding with one row per sample first");
-  const float* temb = nullptr;
-  if (e->temb_table_n == n && e->temb_table_map == s->timestep_map) {   // installed for exactly this timestep_map
-    temb = e->temb_table;
-  } else {
-    if (e->temb_own_map != s->timestep_map) {
-      e->temb_own_map.clear();
-      if ((rc = grow(e, &e->temb_own, &e->temb_own_cap, (int64_t)n * D))) return rc;
-      if ((rc = compute_temb_table(e, s, e->temb_own, st))) return rc;
-      e->temb_own_map = s->timestep_map;
-    }
-    temb = e->temb_own;
-  }
-  // The conditioning rows of the chain are produced in chunks of <= 256 rows (= 256 / bu steps), right before the steps
-  // that use them: the adaLN outputs are 783 KB per row at XL/2 (nmod = 195 840 fp32), so the whole chain at once would
-  // be 3.1 GB for 250 guided steps at B = 16.  The adaLN weights are streamed once per 64 rows either way.
-  const int chunk_steps = std::max(1, 256 / bu);
-  const int64_t rows_chunk = (int64_t)std::min(chunk_steps, n_run) * bu;
-  if ((rc = grow(e, &e->cond_rows, &e->cond_cap, rows_chunk * D))) return rc;
-  if ((rc = grow(e, &e->mod_all, &e->mod_all_cap, rows_chunk * e->nmod))) return rc;
-  if (ex == 78 && (rc = grow(e, &e->cond_rows_t, &e->cond_t_cap, rows_chunk * D))) return rc;
-  const size_t fo = (size_t)e->cfg.depth * 6 * D;
-  // conditioning of respaced steps [lo, lo + cnt): rows ordered by index ascending, row (i - lo) * bu + b
-  auto chain_conditioning = [&](int lo, int cnt) -> int {
-    const int64_t rows_all = (int64_t)cnt * bu;
-    int r2;
-    if ((r2 = launch_cond_rows(temb + (size_t)lo * D, ex == 2 ? e->ytab : ex == 78 ? e->txt_proj : nullptr,
-                               ex == 78 ? e->iota : y, e->cond_rows, cnt, bu, D, st))) return r2;
-    if (ex == 78 &&   // t-only rows for the final layer (latte.py:372-373)
-        (r2 = launch_cond_rows(temb + (size_t)lo * D, nullptr, nullptr, e->cond_rows_t, cnt, bu, D, st))) return r2;
-    for (int64_t r0 = 0; r0 < rows_all; r0 += 64) {
-      const int rows = (int)std::min<int64_t>(64, rows_all - r0);
-      if ((r2 = launch_small_linear(IN_PLAIN, e->cond_rows + (size_t)r0 * D, nullptr, e->ada_w, e->ada_b, nullptr, nullptr,
-                                    e->mod_all + (size_t)r0 * e->nmod, rows, e->nmod, D, e->nmod, st))) return r2;
-      if (ex == 78 &&
-          (r2 = launch_small_linear(IN_PLAIN, e->cond_rows_t + (size_t)r0 * D, nullptr, e->ada_w + fo * D, e->ada_b + fo, nullptr,
-                                    nullptr, e->mod_all + (size_t)r0 * e->nmod + fo, rows, 2 * D, D, e->nmod, st))) return r2;
-    }
-    return LATTE_OK;
-  };
+  ChainCond cc;
+  if ((rc = chain_prepare(e, s, bu, n_run, st, &cc))) return rc;
+  const int chunk_steps = cc.chunk_steps;
   const size_t numel = (size_t)batch * e->F * e->Cin * e->H * e->H;
   int k = 0;
   int chunk_lo = start_index + 1;   // first respaced index covered by the rows currently in mod_all
   for (int i = start_index; i >= end_index; --i, ++k) {
     if (i < chunk_lo) {   // next chunk: steps i, i - 1, ..., down to max(end_index, i - chunk_steps + 1)
       chunk_lo = std::max(end_index, i - chunk_steps + 1);
-      if ((rc = chain_conditioning(chunk_lo, i - chunk_lo + 1))) return rc;
+      if ((rc = chain_conditioning(e, cc, y, chunk_lo, i - chunk_lo + 1, st))) return rc;
     }
     const float* mod_i = e->mod_all + (size_t)(i - chunk_lo) * bu * e->nmod;
     if ((rc = run_forward(e, x, nullptr, y, batch, use_cfg, e->model_out, st, nullptr, mod_i, bu == 1 ? 0 : e->nmod))) return rc;
@@ -915,6 +936,88 @@ int latte_training_losses(const latte_schedule_t* s, int loss_type, const float*
 int64_t latte_training_workspace_floats(int batch, int64_t numel_per_sample) {
   if (batch <= 0 || numel_per_sample <= 0) return 0;
   return (int64_t)batch * training_terms_blocks((size_t)numel_per_sample) * 2 + 2 * (int64_t)batch;
+}
+
+// ---- likelihood evaluation (gaussian_diffusion.py:813-866 calc_bpd_loop, :686-717 _vb_terms_bpd, :797-811 _prior_bpd)
+int64_t latte_bpd_workspace_floats(int batch, int64_t numel_per_sample) {
+  if (batch <= 0 || numel_per_sample <= 0) return 0;
+  return (int64_t)batch * training_terms_blocks((size_t)numel_per_sample) * 3;
+}
+
+int latte_prior_bpd(const latte_schedule_t* s, const float* x_start, int batch, int64_t numel_per_sample, float* out, void* stream) {
+  if (!s || !x_start || !out) return fail(LATTE_ERR_INVALID, "prior_bpd: null argument");
+  if (batch <= 0 || numel_per_sample <= 0) return fail(LATTE_ERR_INVALID, "prior_bpd: batch and numel_per_sample must be positive");
+  const int last = s->num_timesteps - 1;   // gd:806
+  return launch_prior_bpd((float)s->sqrt_alphas_cumprod[last], (float)std::log(1.0 - s->alphas_cumprod[last]) /* gd:183 */, x_start,
+                          batch, (size_t)numel_per_sample, out, (hipStream_t)stream);
+}
+
+int latte_bpd_terms(const latte_schedule_t* s, int index, int clip_denoised, const float* x_start, const float* x_t, const float* noise,
+                    const float* model_out, int batch, int frames, int channels, int hw, float* workspace, int64_t workspace_floats,
+                    float* vb_out, float* xstart_mse_out, float* mse_out, int64_t out_stride, float* pred_xstart_out, void* stream) {
+  if (!s || !x_start || !x_t || !noise || !model_out || !workspace || !vb_out || !xstart_mse_out || !mse_out)
+    return fail(LATTE_ERR_INVALID, "bpd_terms: null argument");
+  if (batch <= 0 || frames <= 0 || channels <= 0 || hw <= 0 || out_stride <= 0)
+    return fail(LATTE_ERR_INVALID, "bpd_terms: batch, frames, channels, hw and out_stride must be positive");
+  if (index < 0 || index >= s->num_timesteps) return fail(LATTE_ERR_INVALID, "bpd_terms: index out of range");
+  if (s->num_timesteps < 2) return fail(LATTE_ERR_INVALID, "bpd_terms: needs >= 2 timesteps (posterior_log_variance_clipped)");
+  const size_t per = (size_t)frames * channels * hw;
+  if (workspace_floats < latte_bpd_workspace_floats(batch, (int64_t)per))
+    return fail(LATTE_ERR_INVALID, "bpd_terms: workspace too small (latte_bpd_workspace_floats)");
+  const SamplerCoefs c = make_coefs(s, LATTE_METHOD_DDPM, index, 0.0f, clip_denoised);
+  return launch_bpd_terms(c, x_start, x_t, noise, model_out, batch, frames, channels, hw, workspace, training_terms_blocks(per), vb_out,
+                          xstart_mse_out, mse_out, out_stride, pred_xstart_out, (hipStream_t)stream);
+}
+
+int latte_bpd_loop(latte_engine_t* e, const latte_schedule_t* s, int clip_denoised, const float* x_start, const int64_t* y, int batch,
+                   int start_index, int end_index, const float* noise, float* vb, float* xstart_mse, float* mse, void* stream) {
+  if (!e || !s || !x_start || !vb || !xstart_mse || !mse) return fail(LATTE_ERR_INVALID, "bpd_loop: null argument");
+  int rc = latte_engine_check_weights(e);
+  if (rc) return rc;
+  const int n = s->num_timesteps;
+  if (start_index >= n || end_index < 0 || start_index < end_index) return fail(LATTE_ERR_INVALID, "bpd_loop: bad index range");
+  if (n < 2) return fail(LATTE_ERR_INVALID, "bpd_loop: needs >= 2 timesteps (posterior_log_variance_clipped)");
+  if (batch <= 0 || batch > e->max_batch) return fail(LATTE_ERR_STATE, "bpd_loop: batch exceeds max_batch");
+  if ((s->var_type == 0) != (e->Cout == 2 * e->Cin))
+    return fail(LATTE_ERR_INVALID, "bpd_loop: the model's learn_sigma and the diffusion's learn_sigma disagree "
+                                   "(model output channels vs ModelVarType, gd:290 / :338)");
+  const int ex = e->cfg.extras;
+  if (ex == 2 && y == nullptr) return fail(LATTE_ERR_INVALID, "bpd_loop: class-conditional model needs y");
+  if (ex == 78) return fail(LATTE_ERR_INVALID, "bpd_loop: serves the class-conditional and unconditional models only");
+  hipStream_t st = (hipStream_t)stream;
+  const int n_run = start_index - end_index + 1;
+  const int bu = ex == 1 ? 1 : batch;
+  const size_t per = (size_t)e->F * e->Cin * e->H * e->H;
+  const size_t numel = (size_t)batch * per;
+  const int blocks = training_terms_blocks(per);
+  ChainCond cc;
+  if ((rc = chain_prepare(e, s, bu, n_run, st, &cc))) return rc;
+  if ((rc = grow(e, &e->bpd_xt, &e->bpd_xt_cap, (int64_t)e->max_batch * (int64_t)per))) return rc;
+  if ((rc = grow(e, &e->bpd_ws, &e->bpd_ws_cap, latte_bpd_workspace_floats(e->max_batch, (int64_t)per)))) return rc;
+  int k = 0;
+  int chunk_lo = start_index + 1;   // first respaced index covered by the rows currently in mod_all
+  for (int i = start_index; i >= end_index; --i, ++k) {   // gd:835: t = T-1 first
+    if (i < chunk_lo) {
+      chunk_lo = std::max(end_index, i - cc.chunk_steps + 1);
+      if ((rc = chain_conditioning(e, cc, y, chunk_lo, i - chunk_lo + 1, st))) return rc;
+    }
+    const float* nz = nullptr;
+    if (noise) {
+      nz = noise + (size_t)k * numel;
+    } else {                        // gd:837: one draw per step, from the engine's stream
+      if ((rc = launch_fill_normal(e->noise_buf, numel, e->seed, e->rng_offset, st))) return rc;
+      e->rng_offset += numel;
+      nz = e->noise_buf;
+    }
+    if ((rc = launch_q_sample_scalar((float)s->sqrt_alphas_cumprod[i], (float)s->sqrt_one_minus_alphas_cumprod[i], x_start, nz, numel,
+                                     e->bpd_xt, st))) return rc;                       // gd:838
+    const float* mod_i = e->mod_all + (size_t)(i - chunk_lo) * bu * e->nmod;
+    if ((rc = run_forward(e, e->bpd_xt, nullptr, y, batch, false, e->model_out, st, nullptr, mod_i, bu == 1 ? 0 : e->nmod))) return rc;
+    const SamplerCoefs c = make_coefs(s, LATTE_METHOD_DDPM, i, 0.0f, clip_denoised);
+    if ((rc = launch_bpd_terms(c, x_start, e->bpd_xt, nz, e->model_out, batch, e->F, e->Cin, e->H * e->H, e->bpd_ws, blocks, vb + k,
+                               xstart_mse + k, mse + k, n_run, nullptr, st))) return rc;   // gd:841-852
+  }
+  return LATTE_OK;
 }
 
 int latte_profile_forward(latte_engine_t* e, const float* x, const int64_t* t, const int64_t* y, int batch, float* out,

@@ -580,6 +580,33 @@ __device__ __forceinline__ float approx_std_normal_cdf(float x) {      // diffus
   return 0.5f * (1.0f + tanhf(c * (x + 0.044715f * (x * x * x))));
 }
 
+// The per-element pieces of _vb_terms_bpd, shared by the training-loss kernel and the likelihood kernels below.
+__device__ __forceinline__ float learned_range_log_var(float v, float max_log, float min_log) {   // gd:291-296
+#pragma clang fp contract(off)
+  const float frac = (v + 1.0f) / 2.0f;
+  return frac * max_log + (1.0f - frac) * min_log;
+}
+
+__device__ __forceinline__ float normal_kl(float mean1, float logvar1, float mean2, float logvar2) {   // diffusion_utils.py:10-36
+#pragma clang fp contract(off)
+  const float dm = mean1 - mean2;
+  return 0.5f * (-1.0f + logvar2 - logvar1 + expf(logvar1 - logvar2) + (dm * dm) * expf(-logvar2));
+}
+
+// -discretized_gaussian_log_likelihood(x, means, log_scales = 0.5 * log_variance), diffusion_utils.py:62-88
+__device__ __forceinline__ float discretized_nll(float xs, float mean, float lv) {
+#pragma clang fp contract(off)
+  const float centered = xs - mean;
+  const float inv_stdv = expf(-(0.5f * lv));
+  const float cdf_plus = approx_std_normal_cdf(inv_stdv * (centered + 0.00392156862745098f));
+  const float cdf_min = approx_std_normal_cdf(inv_stdv * (centered - 0.00392156862745098f));
+  const float log_cdf_plus = logf(fmaxf(cdf_plus, 1e-12f));
+  const float log_one_minus = logf(fmaxf(1.0f - cdf_min, 1e-12f));
+  const float log_delta = logf(fmaxf(cdf_plus - cdf_min, 1e-12f));
+  const float lp = xs < -0.999f ? log_cdf_plus : (xs > 0.999f ? log_one_minus : log_delta);
+  return -lp;
+}
+
 constexpr int TT_THREADS = 256;
 __global__ void __launch_bounds__(TT_THREADS) training_terms_kernel(const float* __restrict__ tab, int n_steps, int mean_type,
                                                                     int var_type, const float* __restrict__ x0,
@@ -608,32 +635,11 @@ __global__ void __launch_bounds__(TT_THREADS) training_terms_kernel(const float*
     // q(x_{t-1} | x_t, x_0), gd:232-241
     const float true_mean = coef1 * xs + coef2 * xv;
     // p_mean_variance with clip_denoised = False, gd:289-336
-    float lv;
-    if (var_type == 0) {
-      const float v = mo[o + chw];
-      const float frac = (v + 1.0f) / 2.0f;
-      lv = frac * lb + (1.0f - frac) * plv;
-    } else {
-      lv = flv;
-    }
+    const float lv = var_type == 0 ? learned_range_log_var(mo[o + chw], lb, plv) : flv;
     const float x0p = mean_type == 1 ? pred : srec * xv - srecm1 * pred;
     const float mean = coef1 * x0p + coef2 * xv;
-    float term;
-    if (ti != 0) {                                                     // KL(q || p), diffusion_utils.py:29-36
-      const float dm = true_mean - mean;
-      term = 0.5f * (-1.0f + lv - plv + expf(plv - lv) + (dm * dm) * expf(-lv));
-    } else {                                                           // decoder NLL, diffusion_utils.py:62-88
-      const float centered = xs - mean;
-      const float inv_stdv = expf(-(0.5f * lv));
-      const float cdf_plus = approx_std_normal_cdf(inv_stdv * (centered + 0.00392156862745098f));
-      const float cdf_min = approx_std_normal_cdf(inv_stdv * (centered - 0.00392156862745098f));
-      const float log_cdf_plus = logf(fmaxf(cdf_plus, 1e-12f));
-      const float log_one_minus = logf(fmaxf(1.0f - cdf_min, 1e-12f));
-      const float log_delta = logf(fmaxf(cdf_plus - cdf_min, 1e-12f));
-      const float lp = xs < -0.999f ? log_cdf_plus : (xs > 0.999f ? log_one_minus : log_delta);
-      term = -lp;
-    }
-    s_vb += term;
+    // KL(q || p), or the decoder NLL at the first timestep (gd:714-716)
+    s_vb += ti != 0 ? normal_kl(true_mean, plv, mean, lv) : discretized_nll(xs, mean, lv);
   }
   // deterministic block reduction (fixed tree), then one slot per (sample, block)
   __shared__ float red[2][TT_THREADS];
@@ -663,6 +669,98 @@ __global__ void training_finalize_kernel(const float* __restrict__ partial, int 
   }
   mse[b] = (float)(a / per_sample);                                    // mean_flat
   vb[b] = (float)(c / per_sample) / 0.6931471805599453f;               // mean_flat(.) / np.log(2.0), fp32 division
+}
+
+// ------------------------------------------------------------------------------------------------
+// Likelihood evaluation (gaussian_diffusion.py:813-866 calc_bpd_loop; :686-717 _vb_terms_bpd WITH clip_denoised; :797-811
+// _prior_bpd; :345-348 _predict_eps_from_xstart).  One respaced index for the whole batch, so the coefficients are the host's
+// fp32 casts of the fp64 tables (SamplerCoefs, as the sampler update takes them); arithmetic op for op, no FMA contraction.
+// Reduction: every block of a sample sums a fixed strided subset in a fixed tree, the finalize pass adds the blocks' slots in
+// index order -- no atomics, and the block count depends on the sample's size alone, so a sample's numbers do not depend on
+// the batch around it.
+constexpr int BPD_SLOTS = 3;   // vb, xstart_mse, mse
+__device__ __forceinline__ void bpd_block_reduce(float (&acc)[BPD_SLOTS], float* __restrict__ slot) {
+  __shared__ float red[BPD_SLOTS][TT_THREADS];
+#pragma unroll
+  for (int k = 0; k < BPD_SLOTS; ++k) red[k][threadIdx.x] = acc[k];
+  __syncthreads();
+  for (int w = TT_THREADS / 2; w > 0; w >>= 1) {
+    if (threadIdx.x < w) {
+#pragma unroll
+      for (int k = 0; k < BPD_SLOTS; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < BPD_SLOTS; ++k) slot[k] = red[k][0];
+  }
+}
+
+__global__ void __launch_bounds__(TT_THREADS) bpd_terms_kernel(SamplerCoefs c, const float* __restrict__ x0,
+                                                               const float* __restrict__ xt, const float* __restrict__ noise,
+                                                               const float* __restrict__ mo, int frames, int C, int hw,
+                                                               float* __restrict__ partial, float* __restrict__ x0_out) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.y;
+  const size_t chw = (size_t)C * hw, per = (size_t)frames * chw;
+  const int Cm = c.var_type == 0 ? 2 * C : C;
+  float acc[BPD_SLOTS] = {0.f, 0.f, 0.f};
+  for (size_t e = (size_t)blockIdx.x * TT_THREADS + threadIdx.x; e < per; e += (size_t)gridDim.x * TT_THREADS) {
+    const size_t f = e / chw, r = e % chw;
+    const size_t i = (size_t)b * per + e;
+    const size_t o = (((size_t)b * frames + f) * Cm) * hw + r;
+    const float pred = mo[o];
+    const float xs = x0[i], xv = xt[i];
+    const float true_mean = c.coef1 * xs + c.coef2 * xv;               // q(x_{t-1} | x_t, x_0), gd:232-241
+    // p_mean_variance, gd:289-336
+    const float lv = c.var_type == 0 ? learned_range_log_var(mo[o + chw], c.max_log, c.min_log) : c.fixed_log_var;
+    float x0p = c.mean_type == 1 ? pred : c.sqrt_recip * xv - c.sqrt_recipm1 * pred;
+    if (c.clip) x0p = fminf(fmaxf(x0p, -1.0f), 1.0f);                  // process_xstart, gd:316-321
+    const float mean = c.coef1 * x0p + c.coef2 * xv;
+    acc[0] += c.nonzero != 0.0f ? normal_kl(true_mean, c.min_log, mean, lv) : discretized_nll(xs, mean, lv);
+    const float dx = x0p - xs;                                         // gd:850
+    acc[1] += dx * dx;
+    const float eps = (c.sqrt_recip * xv - x0p) / c.sqrt_recipm1;      // gd:345-348, from the (clipped) prediction
+    const float de = eps - noise[i];                                   // gd:852
+    acc[2] += de * de;
+    if (x0_out != nullptr) x0_out[i] = x0p;
+  }
+  bpd_block_reduce(acc, partial + ((size_t)b * gridDim.x + blockIdx.x) * BPD_SLOTS);
+}
+
+// out_k[b * out_stride] = mean_flat of slot k (out1 / out2 may be nullptr); slot 0 (the bound's term) in bits
+__global__ void bpd_finalize_kernel(const float* __restrict__ partial, int blocks, int slots, double per_sample, float* out0,
+                                    float* out1, float* out2, int64_t out_stride) {
+  const int b = blockIdx.x, k = threadIdx.x;
+  if (k >= slots) return;
+  double a = 0.0;
+  for (int j = 0; j < blocks; ++j) a += (double)partial[((size_t)b * blocks + j) * slots + k];
+  const float m = (float)(a / per_sample);                             // mean_flat
+  if (k == 0) out0[(size_t)b * out_stride] = m / 0.6931471805599453f;  // / np.log(2.0), fp32 division
+  if (k == 1 && out1 != nullptr) out1[(size_t)b * out_stride] = m;
+  if (k == 2 && out2 != nullptr) out2[(size_t)b * out_stride] = m;
+}
+
+// _prior_bpd: KL(q(x_T | x_0) || N(0, I)) in bits; mean_c = sqrt(ab[T-1]), logvar = log(1 - ab[T-1])  (gd:203-213, :805-811).
+// One workgroup per sample strides over it: fixed order, nothing shared between samples, no scratch.
+__global__ void __launch_bounds__(TT_THREADS) prior_bpd_kernel(float mean_c, float logvar, const float* __restrict__ x0, size_t per,
+                                                               float* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x;
+  float acc[BPD_SLOTS] = {0.f, 0.f, 0.f};
+  for (size_t e = threadIdx.x; e < per; e += TT_THREADS) acc[0] += normal_kl(mean_c * x0[(size_t)b * per + e], logvar, 0.0f, 0.0f);
+  __shared__ float total[BPD_SLOTS];
+  bpd_block_reduce(acc, total);
+  if (threadIdx.x == 0) out[b] = (float)((double)total[0] / (double)per) / 0.6931471805599453f;
+}
+
+// q_sample with one index for the batch: x_t = sqrt(ab[i]) x_0 + sqrt(1 - ab[i]) noise  (gd:226-229)
+__global__ void q_sample_scalar_kernel(float a, float b, const float* __restrict__ x0, const float* __restrict__ noise, size_t total,
+                                       float* __restrict__ xt) {
+#pragma clang fp contract(off)
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+    xt[i] = a * x0[i] + b * noise[i];
 }
 
 __global__ void t2v_guided_ddim_kernel(float* __restrict__ x, const float* __restrict__ mo, int b, int C, int Cout, int F, int hw,
@@ -953,6 +1051,31 @@ int launch_training_terms(const float* tables, int n_steps, int mean_type, int v
                      var_type, x_start, x_t, noise, model_out, t, frames, channels, hw, partial);
   hipLaunchKernelGGL(training_finalize_kernel, dim3(batch), dim3(1), 0, st, partial, blocks_per_sample,
                      (double)frames * channels * hw, mse, vb);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+
+int launch_q_sample_scalar(float sqrt_ab, float sqrt_one_minus_ab, const float* x_start, const float* noise, size_t total, float* x_t,
+                           hipStream_t st) {
+  hipLaunchKernelGGL(q_sample_scalar_kernel, dim3(grid_for(total, 256)), dim3(256), 0, st, sqrt_ab, sqrt_one_minus_ab, x_start, noise,
+                     total, x_t);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+
+int launch_bpd_terms(const SamplerCoefs& c, const float* x_start, const float* x_t, const float* noise, const float* model_out, int batch,
+                     int frames, int channels, int hw, float* partial, int blocks_per_sample, float* vb, float* xstart_mse, float* mse,
+                     int64_t out_stride, float* pred_xstart_out, hipStream_t st) {
+  hipLaunchKernelGGL(bpd_terms_kernel, dim3(blocks_per_sample, batch), dim3(TT_THREADS), 0, st, c, x_start, x_t, noise, model_out, frames,
+                     channels, hw, partial, pred_xstart_out);
+  hipLaunchKernelGGL(bpd_finalize_kernel, dim3(batch), dim3(64), 0, st, partial, blocks_per_sample, BPD_SLOTS,
+                     (double)frames * channels * hw, vb, xstart_mse, mse, out_stride);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+
+int launch_prior_bpd(float mean_coef, float log_variance, const float* x_start, int batch, size_t per_sample, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(prior_bpd_kernel, dim3(batch), dim3(TT_THREADS), 0, st, mean_coef, log_variance, x_start, per_sample, out);
   LATTE_HIP(hipGetLastError());
   return LATTE_OK;
 }

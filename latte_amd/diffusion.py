@@ -295,6 +295,90 @@ class SpacedDiffusion:
             terms["vb"] = vb
         return terms
 
+    # ------------------------------------------------------------------ likelihood evaluation (gd:686-717, :797-866)
+    def _prior_bpd(self, x_start):
+        """``GaussianDiffusion._prior_bpd`` (gd:797-811): KL(q(x_T | x_0) || N(0, I)) in bits per dimension, [N]."""
+        _lib.require_gpu()
+        x0 = x_start.float().contiguous()
+        out = torch.empty(x0.shape[0], device=x0.device, dtype=torch.float32)
+        with torch.cuda.device(x0.device):
+            check(load_library().latte_prior_bpd(self._h, ptr(x0), x0.shape[0], x0[0].numel(), ptr(out), stream_ptr()))
+        return out
+
+    def _bpd_terms(self, x0, x_t, noise, model_output, index, clip_denoised, tables=None, column=0, want_xstart=False):
+        """One column of ``calc_bpd_loop`` on the engine (``latte_bpd_terms``): vb, xstart_mse, mse of respaced ``index`` into
+        ``tables`` ([N, T] each) at ``column``, or into fresh [N] tensors."""
+        B, F, C = x0.shape[:3]
+        want = (B, F, C * 2 if self.learn_sigma else C, *x0.shape[3:])              # gd:290 / :338
+        if tuple(model_output.shape) != want:
+            raise AssertionError(f"model output shape {tuple(model_output.shape)} != {want}")
+        mo = model_output.detach().to(device=x0.device, dtype=torch.float32).contiguous()
+        if tables is None:
+            tables = tuple(torch.empty(B, 1, device=x0.device, dtype=torch.float32) for _ in range(3))
+            column = 0
+        stride = tables[0].shape[1]
+        hw = int(np.prod(x0.shape[3:]))
+        lib = load_library()
+        nws = int(lib.latte_bpd_workspace_floats(B, x0[0].numel()))
+        ws = torch.empty(nws, device=x0.device, dtype=torch.float32)
+        pred = torch.empty_like(x0) if want_xstart else None
+        with torch.cuda.device(x0.device):
+            check(lib.latte_bpd_terms(self._h, int(index), int(bool(clip_denoised)), ptr(x0), ptr(x_t), ptr(noise), ptr(mo), B, F, C, hw,
+                                      ptr(ws), nws, ptr(tables[0][:, column:]), ptr(tables[1][:, column:]), ptr(tables[2][:, column:]),
+                                      stride, ptr(pred), stream_ptr()))
+        return tables, pred
+
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """``GaussianDiffusion._vb_terms_bpd`` (gd:686-717) for one timestep index shared by the batch, as ``calc_bpd_loop``
+        calls it: {"output": KL (decoder NLL at t == 0) in bits [N], "pred_xstart"}.  The noise that made ``x_t`` is not an
+        argument of the reference method; the eps-MSE column of the kernel is computed against zeros here and dropped."""
+        _lib.require_gpu()
+        index = self._uniform_index(t)
+        x0 = x_start.float().contiguous()
+        xt = x_t.to(device=x0.device, dtype=torch.float32).contiguous()
+        out = self._call_model(model, xt, index, model_kwargs or {})
+        tables, pred = self._bpd_terms(x0, xt, torch.zeros_like(x0), out, index, clip_denoised, want_xstart=True)
+        return {"output": tables[0][:, 0], "pred_xstart": pred}
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, noise=None):
+        """``GaussianDiffusion.calc_bpd_loop`` (gd:813-866): {"total_bpd", "prior_bpd" [N]; "vb", "xstart_mse", "mse" [N, T]},
+        column 0 = t = T-1.  ``noise`` ([T, N, ...], row k for the k-th executed step) replaces the per-step draws of gd:837.
+        With ``model`` the ``forward`` of a ``latte_amd.Latte`` the loop is ONE ``latte_bpd_loop`` call (its draws then come from
+        the engine's Philox stream, option "seed"); any other callable is driven step by step with ``torch.randn_like`` draws."""
+        _lib.require_gpu()
+        model_kwargs = dict(model_kwargs or {})
+        x0 = x_start.float().contiguous()
+        if x0.dim() != 5:
+            raise LatteError("x_start must be [N, F, C, H, W]")
+        n = self.num_timesteps
+        B = x0.shape[0]
+        nz_all = None
+        if noise is not None:
+            if tuple(noise.shape) != (n,) + tuple(x0.shape):
+                raise AssertionError("noise.shape == (num_timesteps,) + x_start.shape")
+            nz_all = noise.to(device=x0.device, dtype=torch.float32).contiguous()
+        tables = tuple(torch.empty(B, n, device=x0.device, dtype=torch.float32) for _ in range(3))
+        owner, uses_cfg = self._engine_model(model)
+        if owner is not None and not uses_cfg and owner.extras != 78 and set(model_kwargs) <= {"y", "use_fp16"}:
+            # ---- whole loop inside the engine
+            x0, _, y64 = owner._prep(x0, torch.zeros(B, dtype=torch.int64), model_kwargs.get("y"))
+            eng = owner.engine(B)
+            with torch.cuda.device(x0.device):
+                check(load_library().latte_bpd_loop(eng, self._h, int(bool(clip_denoised)), ptr(x0), ptr(y64), B, n - 1, 0, ptr(nz_all),
+                                                    ptr(tables[0]), ptr(tables[1]), ptr(tables[2]), stream_ptr()))
+        else:
+            # ---- generic model callable, step by step (gd:835-852)
+            for k, i in enumerate(range(n - 1, -1, -1)):
+                nz = nz_all[k] if nz_all is not None else torch.randn_like(x0)
+                t = torch.full((B,), i, device=x0.device, dtype=torch.int64)
+                x_t = self.q_sample(x0, t, nz)
+                out = self._call_model(model, x_t, i, model_kwargs)
+                self._bpd_terms(x0, x_t, nz, out, i, clip_denoised, tables, k)
+        vb, xstart_mse, mse = tables
+        prior_bpd = self._prior_bpd(x0)
+        total_bpd = vb.sum(dim=1) + prior_bpd                                       # gd:859
+        return {"total_bpd": total_bpd, "prior_bpd": prior_bpd, "vb": vb, "xstart_mse": xstart_mse, "mse": mse}
+
 
 def create_diffusion(timestep_respacing, noise_schedule="linear", use_kl=False, sigma_small=False,
                      predict_xstart=False, learn_sigma=True, rescale_learned_sigmas=False, diffusion_steps=1000):
