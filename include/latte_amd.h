@@ -53,7 +53,7 @@ void latte_schedule_destroy(latte_schedule_t* s);
 int latte_schedule_num_timesteps(const latte_schedule_t* s);
 /* SpacedDiffusion.timestep_map (respace.py:75,86): respaced index -> original timestep */
 int latte_schedule_timestep_map(const latte_schedule_t* s, int64_t* out, int n);
-/* name in {betas, alphas_cumprod, alphas_cumprod_prev, sqrt_recip_alphas_cumprod,
+/* name in {betas, alphas_cumprod, alphas_cumprod_prev, alphas_cumprod_next, sqrt_recip_alphas_cumprod,
  * sqrt_recipm1_alphas_cumprod, posterior_variance, posterior_log_variance_clipped,
  * posterior_mean_coef1, posterior_mean_coef2, log_betas, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod} */
 int latte_schedule_table(const latte_schedule_t* s, const char* name, double* out, int n);
@@ -157,10 +157,14 @@ int latte_forward_with_cfg(latte_engine_t* e, const float* x, const int64_t* t, 
 /* ------------------------------------------------------------------ sampler update
  * Replaces gaussian_diffusion.py:254-336 p_mean_variance (EPSILON + LEARNED_RANGE, as built by
  * create_diffusion) followed by :380-421 p_sample (method 0 = "ddpm") or :517-564 ddim_sample
- * (method 1 = "ddim").  `index` is the respaced step i.  model_out:[B,F,2C,H,W]; noise may be NULL
- * when no noise term is needed (ddim eta == 0, or index == 0).  Outputs may alias x. */
+ * (method 1 = "ddim") or :566-602 ddim_reverse_sample (method 2 = "ddim_reverse": the deterministic step from level
+ * `index` UP to level index + 1 with alphas_cumprod_next, whose last entry is 0 -- index num_timesteps-1 returns the
+ * re-derived eps itself; eta must be 0 (:580, LATTE_ERR_INVALID otherwise) and noise is ignored).  `index` is the
+ * respaced step i.  model_out:[B,F,2C,H,W]; noise may be NULL when no noise term is needed (ddim eta == 0, or
+ * index == 0).  Outputs may alias x. */
 #define LATTE_METHOD_DDPM 0
 #define LATTE_METHOD_DDIM 1
+#define LATTE_METHOD_DDIM_REVERSE 2
 int latte_sampler_step(const latte_schedule_t* s, int method, int index, float eta, int clip_denoised,
                        const float* x, const float* model_out, const float* noise,
                        int batch, int frames, int channels, int hw /* H*W */,
@@ -170,8 +174,8 @@ int latte_sampler_step(const latte_schedule_t* s, int method, int index, float e
  *     pred_xstart_out, apply the function, and pass its result as pred_xstart_in (it replaces the prediction BEFORE the
  *     clamp);
  *   cond_fn (:345-375; the hook sees ORIGINAL timesteps, respace.py:100-104): pass cond_grad = cond_fn(x, t).  DDPM
- *     adds variance * gradient to the mean (condition_mean), DDIM shifts eps by sqrt(1 - alpha_bar) * gradient and
- *     re-derives pred_xstart from it (condition_score).
+ *     adds variance * gradient to the mean (condition_mean), DDIM and the reverse step shift eps by
+ *     sqrt(1 - alpha_bar) * gradient and re-derive pred_xstart from it (condition_score, :589-590).
  * Either pointer may be NULL. */
 int latte_sampler_step_ex(const latte_schedule_t* s, int method, int index, float eta, int clip_denoised,
                           const float* x, const float* model_out, const float* noise, const float* pred_xstart_in,
@@ -197,6 +201,19 @@ int latte_sample_loop(latte_engine_t* e, const latte_schedule_t* s, int method, 
 int latte_sample_loop_ex(latte_engine_t* e, const latte_schedule_t* s, int method, float eta, int clip_denoised, int guided,
                          float cfg_scale, float* x, const int64_t* y, int batch, int start_index, int end_index,
                          const float* noise, float* trail_sample, float* trail_x0, void* stream);
+
+/* ------------------------------------------------------------------ DDIM inversion
+ * GaussianDiffusion.ddim_reverse_sample (gaussian_diffusion.py:566-602) stepped over respaced indices start_index ... end_index
+ * ASCENDING, 0 <= start_index <= end_index < num_timesteps; the full chain is 0 ... num_timesteps-1 (the reference has no loop of
+ * its own: this is `for i in range(T)` around its step).  Index i evaluates the model on (x, timestep_map[i]) -- the level being
+ * LEFT -- and carries x from level i to level i + 1; level num_timesteps is pure noise (alphas_cumprod_next ends in 0), one level
+ * above where ddim_sample_loop starts.  x:[B,F,C,H,W] fp32 updated in place.  The forward runs on the chain conditioning of
+ * latte_sample_loop_ex; guided != 0 drives Latte.forward_with_cfg on the doubled batch for any cfg_scale, combined inside the
+ * update kernel as there.  trail_sample / trail_x0: NULL or [n_steps][B,F,C,H,W] receiving every step's {"sample","pred_xstart"}
+ * in execution order.  Deterministic: no noise is read and the engine's Philox offset is not touched.  Same preconditions and
+ * error codes as latte_sample_loop_ex; nothing is launched when one fails.  Stream-ordered, no synchronisation. */
+int latte_invert_loop(latte_engine_t* e, const latte_schedule_t* s, int clip_denoised, int guided, float cfg_scale, float* x,
+                      const int64_t* y, int batch, int start_index, int end_index, float* trail_sample, float* trail_x0, void* stream);
 
 /* ------------------------------------------------------------------ training path, forward evaluation
  * SURVEY.md section 8(f) rank 3, first slice: the loss VALUES of GaussianDiffusion.training_losses

@@ -10,8 +10,8 @@ from .config import Config, load_config  # noqa: F401
 from .diffusion import SpacedDiffusion, create_diffusion  # noqa: F401
 from .models import Latte, Latte_models, find_model, get_models  # noqa: F401
 from .pipeline import LattePipeline  # noqa: F401
-from .schedulers import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,  # noqa: F401
-                         EulerDiscreteScheduler, HeunDiscreteScheduler)
+from .schedulers import (DDIMInverseScheduler, DDIMScheduler, DPMSolverMultistepScheduler,  # noqa: F401
+                         EulerAncestralDiscreteScheduler, EulerDiscreteScheduler, HeunDiscreteScheduler)
 from .t2v import LatteT2V  # noqa: F401
 from .t5 import T5EncoderModel  # noqa: F401
 from .training import LatteTrainer  # noqa: F401

@@ -77,6 +77,7 @@ PROTOTYPES = {
                                   c_void, c_void, c_void, c_void]),
     "latte_sample_loop_ex": (c_int, [c_void, c_void, c_int, c_f32, c_int, c_int, c_f32, c_void, c_void, c_int, c_int, c_int,
                                      c_void, c_void, c_void, c_void]),
+    "latte_invert_loop": (c_int, [c_void, c_void, c_int, c_int, c_f32, c_void, c_void, c_int, c_int, c_int, c_void, c_void, c_void]),
     "latte_q_sample": (c_int, [c_void, c_void, c_void, c_void, c_int, c_i64, c_void, c_void]),
     "latte_training_workspace_floats": (c_i64, [c_int, c_i64]),
     "latte_training_losses": (c_int, [c_void, c_int, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void,

@@ -12,7 +12,7 @@
 struct latte_schedule {
   int num_timesteps = 0;
   std::vector<int64_t> timestep_map;
-  std::vector<double> betas, alphas_cumprod, alphas_cumprod_prev, sqrt_recip_alphas_cumprod,
+  std::vector<double> betas, alphas_cumprod, alphas_cumprod_prev, alphas_cumprod_next, sqrt_recip_alphas_cumprod,
       sqrt_recipm1_alphas_cumprod, posterior_variance, posterior_log_variance_clipped, posterior_mean_coef1,
       posterior_mean_coef2, log_betas, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod;
   // what the model predicts (gd ModelMeanType / ModelVarType as create_diffusion sets them, diffusion/__init__.py:32-45)
@@ -395,6 +395,7 @@ int launch_attention_bwd(const half_t* qkv, const half_t* o, const half_t* dout,
 struct SamplerCoefs {  // fp32 values of the fp64 tables at the step (gaussian_diffusion.py:869-881)
   float min_log, max_log, sqrt_recip, sqrt_recipm1, coef1, coef2;
   float sqrt_ab_prev, dir_coef, sigma;  // ddim: sqrt(ab_prev), sqrt(1-ab_prev-sigma^2), sigma
+                                        // ddim reverse (gd:597-600): sqrt(ab_next), sqrt(1-ab_next), 0
   float nonzero;                        // 0 when index == 0
   float cfg_scale;                      // > 1: model_out is a raw doubled batch, combine here
   float sqrt_one_minus_ab;              // condition_score: (1 - alpha_bar).sqrt() in fp32 (gd:368)

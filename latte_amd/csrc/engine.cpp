@@ -465,6 +465,12 @@ SamplerCoefs make_coefs(const latte_schedule_t* s, int method, int i, float eta,
   c.sigma = sigma;
   c.sqrt_ab_prev = std::sqrt(abp);
   c.dir_coef = std::sqrt((1.0f - abp) - sigma * sigma);  // gd:558: sqrt(1 - abp - sigma**2)
+  if (method == LATTE_METHOD_DDIM_REVERSE) {   // gd:597-600 on the extracted fp32 alpha_bar_next; the update is the DDIM one
+    const float abn = (float)s->alphas_cumprod_next[i];
+    c.sigma = 0.0f;
+    c.sqrt_ab_prev = std::sqrt(abn);
+    c.dir_coef = std::sqrt(1.0f - abn);
+  }
   c.nonzero = i == 0 ? 0.0f : 1.0f;
   c.cfg_scale = 1.0f;
   c.sqrt_one_minus_ab = std::sqrt(1.0f - ab);   // gd:368 on the fp32 alpha_bar
@@ -769,12 +775,15 @@ int latte_sampler_step_ex(const latte_schedule_t* s, int method, int index, floa
   if (!s || !x || !model_out) return fail(LATTE_ERR_INVALID, "sampler_step: null argument");
   if (predict_only ? !pred_xstart_out : !sample_out) return fail(LATTE_ERR_INVALID, "sampler_step: null output");
   if (index < 0 || index >= s->num_timesteps) return fail(LATTE_ERR_INVALID, "sampler_step: index out of range");
-  if (method != LATTE_METHOD_DDPM && method != LATTE_METHOD_DDIM) return fail(LATTE_ERR_INVALID, "sampler_step: bad method");
+  if (method != LATTE_METHOD_DDPM && method != LATTE_METHOD_DDIM && method != LATTE_METHOD_DDIM_REVERSE)
+    return fail(LATTE_ERR_INVALID, "sampler_step: bad method");
+  if (method == LATTE_METHOD_DDIM_REVERSE && eta != 0.0f)
+    return fail(LATTE_ERR_INVALID, "sampler_step: Reverse ODE only for deterministic path (eta must be 0, gd:580)");
   if (s->num_timesteps < 2) return fail(LATTE_ERR_INVALID, "sampler_step: learned-range variance needs >= 2 timesteps");
   SamplerCoefs c = make_coefs(s, method, index, eta, clip_denoised);
   if (!predict_only && method == LATTE_METHOD_DDPM && index != 0 && noise == nullptr)
     return fail(LATTE_ERR_INVALID, "sampler_step: DDPM needs noise for index > 0");
-  const bool need_noise = (method == LATTE_METHOD_DDPM) ? (index != 0) : (c.sigma != 0.0f && index != 0);
+  const bool need_noise = (method == LATTE_METHOD_DDPM) ? (index != 0) : (c.sigma != 0.0f && index != 0);   // never for the reverse step
   return launch_sampler_update(c, x, model_out, need_noise ? noise : nullptr, batch, frames, channels, hw, 0, sample_out,
                                pred_xstart_out, (hipStream_t)stream, pred_xstart_in, cond_grad, predict_only);
 }
@@ -849,6 +858,51 @@ int latte_sample_loop_ex(latte_engine_t* e, const latte_schedule_t* s, int metho
     }
     float* x0 = trail_x0 ? trail_x0 + (size_t)k * numel : nullptr;
     if ((rc = launch_sampler_update(c, x, e->model_out, nz, batch, e->F, e->Cin, e->H * e->H, use_cfg ? 1 : 0, x, x0, st))) return rc;
+    if (trail_sample)
+      LATTE_HIP(hipMemcpyAsync(trail_sample + (size_t)k * numel, x, sizeof(float) * numel, hipMemcpyDeviceToDevice, st));
+  }
+  return LATTE_OK;
+}
+
+// ---- DDIM inversion (gaussian_diffusion.py:566-602 ddim_reverse_sample, stepped over ascending indices)
+int latte_invert_loop(latte_engine_t* e, const latte_schedule_t* s, int clip_denoised, int guided, float cfg_scale, float* x,
+                      const int64_t* y, int batch, int start_index, int end_index, float* trail_sample, float* trail_x0, void* stream) {
+  if (!e || !s || !x) return fail(LATTE_ERR_INVALID, "invert_loop: null argument");
+  int rc = latte_engine_check_weights(e);
+  if (rc) return rc;
+  const int n = s->num_timesteps;
+  if (start_index < 0 || end_index >= n || start_index > end_index) return fail(LATTE_ERR_INVALID, "invert_loop: bad index range");
+  if (n < 2) return fail(LATTE_ERR_INVALID, "invert_loop: learned-range variance needs >= 2 timesteps");
+  if (batch <= 0 || batch > e->max_batch) return fail(LATTE_ERR_STATE, "invert_loop: batch exceeds max_batch");
+  if ((s->var_type == 0) != (e->Cout == 2 * e->Cin))
+    return fail(LATTE_ERR_INVALID, "invert_loop: the model's learn_sigma and the diffusion's learn_sigma disagree "
+                                   "(model output channels vs ModelVarType, gd:290 / :338)");
+  const bool use_cfg = guided != 0;   // forward_with_cfg semantics for ANY scale, as latte_sample_loop_ex
+  if (use_cfg && (batch % 2)) return fail(LATTE_ERR_INVALID, "invert_loop: guidance needs the doubled batch");
+  hipStream_t st = (hipStream_t)stream;
+  const int n_run = end_index - start_index + 1;
+  const int ex = e->cfg.extras;
+  const int bu = ex == 1 ? 1 : batch;
+  if (ex == 2 && y == nullptr) return fail(LATTE_ERR_INVALID, "invert_loop: class-conditional model needs y");
+  if (ex == 78 && e->txt_rows != batch)
+    return fail(LATTE_ERR_STATE, "invert_loop: text-conditioned model needs latte_engine_set_text_embedding with one row per sample first");
+  ChainCond cc;
+  if ((rc = chain_prepare(e, s, bu, n_run, st, &cc))) return rc;
+  const size_t numel = (size_t)batch * e->F * e->Cin * e->H * e->H;
+  int k = 0;
+  int chunk_lo = 0, chunk_hi = -1;   // respaced indices covered by the rows currently in mod_all
+  for (int i = start_index; i <= end_index; ++i, ++k) {   // index i carries level i to level i + 1
+    if (i > chunk_hi) {   // next chunk: steps i, i + 1, ..., up to min(end_index, i + chunk_steps - 1)
+      chunk_lo = i;
+      chunk_hi = std::min(end_index, i + cc.chunk_steps - 1);
+      if ((rc = chain_conditioning(e, cc, y, chunk_lo, chunk_hi - chunk_lo + 1, st))) return rc;
+    }
+    const float* mod_i = e->mod_all + (size_t)(i - chunk_lo) * bu * e->nmod;
+    if ((rc = run_forward(e, x, nullptr, y, batch, use_cfg, e->model_out, st, nullptr, mod_i, bu == 1 ? 0 : e->nmod))) return rc;
+    SamplerCoefs c = make_coefs(s, LATTE_METHOD_DDIM_REVERSE, i, 0.0f, clip_denoised);
+    c.cfg_scale = cfg_scale;
+    float* x0 = trail_x0 ? trail_x0 + (size_t)k * numel : nullptr;
+    if ((rc = launch_sampler_update(c, x, e->model_out, nullptr, batch, e->F, e->Cin, e->H * e->H, use_cfg ? 1 : 0, x, x0, st))) return rc;
     if (trail_sample)
       LATTE_HIP(hipMemcpyAsync(trail_sample + (size_t)k * numel, x, sizeof(float) * numel, hipMemcpyDeviceToDevice, st));
   }

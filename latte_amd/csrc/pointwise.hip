@@ -5,7 +5,7 @@
 //  patch_embed   : Conv2d(k=s=p) as a [C p p]-deep dot + bias + pos_embed        latte.py:233,330-331
 //  final_layer   : LN + modulate + Linear(D, p*p*Cout) + unpatchify              latte.py:197-201,297-310,374-376
 //  cfg_combine   : classifier-free guidance on the first 4 channels              latte.py:394-398
-//  sampler_update: p_mean_variance + p_sample / ddim_sample                      gaussian_diffusion.py:254-336,380-421,517-564
+//  sampler_update: p_mean_variance + p_sample / ddim_sample / ddim_reverse_sample gaussian_diffusion.py:254-336,380-421,517-602
 #include "common.h"
 #include "mfma_util.h"
 
@@ -541,7 +541,8 @@ __global__ void sampler_update_kernel(SamplerCoefs c, const float* __restrict__ 
       if (grad != nullptr) mean = mean + expf(log_var) * grad[i];      // condition_mean, gd:354-355 (variance = exp(log_var), gd:297)
       const float nz = noise != nullptr ? noise[i] : 0.0f;
       s = mean + (c.nonzero * expf(0.5f * log_var)) * nz;              // gd:420
-    } else {
+    } else {                                                           // ddim_sample, and ddim_reverse_sample (gd:589-600): the
+      // same operations with sqrt(ab_next), sqrt(1 - ab_next) in sqrt_ab_prev / dir_coef (make_coefs) and noise == nullptr
       if (grad != nullptr) {                                           // condition_score, gd:366-373
         float e = (c.sqrt_recip * xv - x0) / c.sqrt_recipm1;
         e = e - c.sqrt_one_minus_ab * grad[i];

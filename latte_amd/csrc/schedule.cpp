@@ -136,12 +136,14 @@ int latte_schedule_create(int diffusion_steps, const char* timestep_respacing, c
   auto& B = s->betas;
   s->alphas_cumprod.resize(n);
   s->alphas_cumprod_prev.resize(n);
+  s->alphas_cumprod_next.resize(n);
   double cp = 1.0;
   for (int i = 0; i < n; ++i) {
     s->alphas_cumprod_prev[i] = cp;
     cp = cp * (1.0 - B[i]);
     s->alphas_cumprod[i] = cp;
   }
+  for (int i = 0; i < n; ++i) s->alphas_cumprod_next[i] = i + 1 < n ? s->alphas_cumprod[i + 1] : 0.0;   // gd:174
   s->sqrt_recip_alphas_cumprod.resize(n);
   s->sqrt_recipm1_alphas_cumprod.resize(n);
   s->posterior_variance.resize(n);
@@ -197,6 +199,7 @@ int latte_schedule_table(const latte_schedule_t* s, const char* name, double* ou
   if (k == "betas") v = &s->betas;
   else if (k == "alphas_cumprod") v = &s->alphas_cumprod;
   else if (k == "alphas_cumprod_prev") v = &s->alphas_cumprod_prev;
+  else if (k == "alphas_cumprod_next") v = &s->alphas_cumprod_next;
   else if (k == "sqrt_recip_alphas_cumprod") v = &s->sqrt_recip_alphas_cumprod;
   else if (k == "sqrt_recipm1_alphas_cumprod") v = &s->sqrt_recipm1_alphas_cumprod;
   else if (k == "posterior_variance") v = &s->posterior_variance;

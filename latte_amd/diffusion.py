@@ -5,8 +5,8 @@
 * per-step update: ``latte_sampler_step`` (one fused HIP kernel instead of ~25 elementwise ops and
   8-12 host->device coefficient copies per step, gaussian_diffusion.py:869-881);
 * whole loop: when the model callable is a ``latte_amd.Latte`` method the loop runs inside the
-  engine (``latte_sample_loop``); any other callable following the model-callable protocol is driven
-  step by step with the same update kernel.
+  engine (``latte_sample_loop``; ``latte_invert_loop`` for DDIM inversion); any other callable following
+  the model-callable protocol is driven step by step with the same update kernel.
 """
 import ctypes
 
@@ -17,12 +17,12 @@ from . import _lib
 from ._lib import LatteError, check, load_library, ptr, stream_ptr
 from .models import Latte
 
-_TABLES = ["betas", "alphas_cumprod", "alphas_cumprod_prev", "sqrt_recip_alphas_cumprod",
+_TABLES = ["betas", "alphas_cumprod", "alphas_cumprod_prev", "alphas_cumprod_next", "sqrt_recip_alphas_cumprod",
            "sqrt_recipm1_alphas_cumprod", "posterior_variance", "posterior_log_variance_clipped",
            "posterior_mean_coef1", "posterior_mean_coef2", "log_betas", "sqrt_alphas_cumprod",
            "sqrt_one_minus_alphas_cumprod"]
 _LOSS = {"mse": 0, "rescaled_mse": 1, "kl": 2, "rescaled_kl": 3}
-_METHOD = {"ddpm": 0, "ddim": 1}
+_METHOD = {"ddpm": 0, "ddim": 1, "ddim_reverse": 2}
 
 
 class SpacedDiffusion:
@@ -90,9 +90,10 @@ class SpacedDiffusion:
 
     def _step(self, method, model_output, x, index, noise, eta, clip_denoised, denoised_fn=None, cond_fn=None,
               model_kwargs=None):
-        """p_mean_variance + p_sample / ddim_sample of one step on the engine (gd:254-336, :380-421, :517-564), with the
-        two caller hooks: ``denoised_fn`` on the x_start prediction before the clamp (gd:316-321) and ``cond_fn(x, t)``
-        with ORIGINAL timesteps (rs:100-104; condition_mean for DDPM, condition_score for DDIM)."""
+        """p_mean_variance + p_sample / ddim_sample / ddim_reverse_sample of one step on the engine (gd:254-336, :380-421,
+        :517-602), with the two caller hooks: ``denoised_fn`` on the x_start prediction before the clamp (gd:316-321) and
+        ``cond_fn(x, t)`` with ORIGINAL timesteps (rs:100-104; condition_mean for DDPM, condition_score for DDIM and its
+        reverse)."""
         _lib.require_gpu()
         B, F, C = x.shape[:3]
         want = (B, F, C * 2 if self.learn_sigma else C, *x.shape[3:])              # gd:290 / :338
@@ -142,6 +143,14 @@ class SpacedDiffusion:
         return self._step("ddim", out, x, index, torch.randn_like(x.float()), eta, clip_denoised, denoised_fn, cond_fn,
                           model_kwargs)
 
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0):
+        """``GaussianDiffusion.ddim_reverse_sample`` (gd:566-602): the deterministic DDIM step from level ``t`` UP to level
+        ``t + 1`` -> {"sample", "pred_xstart"}.  One timestep index shared by the batch, as ``_vb_terms_bpd`` takes it."""
+        assert eta == 0.0, "Reverse ODE only for deterministic path"                  # gd:580
+        index = self._uniform_index(t)
+        out = self._call_model(model, x, index, model_kwargs or {})
+        return self._step("ddim_reverse", out, x, index, None, 0.0, clip_denoised, denoised_fn, cond_fn, model_kwargs)
+
     @staticmethod
     def _uniform_index(t):
         tv = t.tolist()
@@ -151,9 +160,21 @@ class SpacedDiffusion:
         return int(tv[0])
 
     # ------------------------------------------------------------------ loops (gd:423-515, :604-684)
+    def _index_range(self, start_index, end_index, ascending):
+        """The inclusive respaced index range of a partial chain; None = the end of the full chain on that side."""
+        n = self.num_timesteps
+        first, last = (0, n - 1) if ascending else (n - 1, 0)
+        start = first if start_index is None else int(start_index)
+        end = last if end_index is None else int(end_index)
+        lo, hi = (start, end) if ascending else (end, start)
+        if not 0 <= lo <= hi < n:
+            raise LatteError(f"bad index range {start} ... {end} for {n} timesteps")
+        return start, end
+
     def _loop(self, method, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress,
-              eta, progressive):
+              eta, progressive, start_index=None, end_index=None):
         _lib.require_gpu()
+        start, end = self._index_range(start_index, end_index, ascending=False)
         model_kwargs = dict(model_kwargs or {})
         device = self._device(model, device)
         assert isinstance(shape, (tuple, list))
@@ -177,9 +198,9 @@ class SpacedDiffusion:
             numel_bytes = x32.numel() * 4
             seg = max(1, min(n, self.SEGMENT_BYTES // max(numel_bytes, 1)))
             lib = load_library()
-            i = n - 1
-            while i >= 0:
-                lo = max(0, i - seg + 1)
+            i = start
+            while i >= end:
+                lo = max(end, i - seg + 1)
                 cnt = i - lo + 1
                 nz = torch.stack([torch.randn_like(x32) for _ in range(cnt)]) if needs_noise else None
                 trail_s = trail_0 = None
@@ -200,7 +221,7 @@ class SpacedDiffusion:
                 yield {"sample": x32, "pred_xstart": None}
             return
         # ---- generic model callable, step by step
-        indices = list(range(n))[::-1]
+        indices = list(range(end, start + 1))[::-1]
         if progress:
             from tqdm.auto import tqdm
             indices = tqdm(indices)
@@ -230,10 +251,86 @@ class SpacedDiffusion:
         return final["sample"]
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                         model_kwargs=None, device=None, progress=False, eta=0.0):
+                         model_kwargs=None, device=None, progress=False, eta=0.0, start_index=None, end_index=None):
+        """``GaussianDiffusion.ddim_sample_loop`` (gd:604-635).  ``start_index`` / ``end_index`` (not in the reference; default
+        the full chain T-1 ... 0) run the respaced steps start ... end descending on ``noise`` taken as level ``start``: the
+        way back from a ``ddim_reverse_sample_loop`` that ended at ``end_index = start - 1``."""
         final = None
         for final in self._loop("ddim", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
-                                progress, eta, False):
+                                progress, eta, False, start_index, end_index):
+            pass
+        return final["sample"]
+
+    # ------------------------------------------------------------------ DDIM inversion (gd:566-602)
+    def _reverse_loop(self, model, x, clip_denoised, denoised_fn, cond_fn, model_kwargs, progress, start_index, end_index,
+                      progressive):
+        _lib.require_gpu()
+        model_kwargs = dict(model_kwargs or {})
+        start, end = self._index_range(start_index, end_index, ascending=True)
+        img = x.to(dtype=torch.float32).contiguous().clone()
+        if img.dim() != 5:
+            raise LatteError("x must be [N, F, C, H, W]")
+        owner, uses_cfg = self._engine_model(model)
+        known = {"y", "use_fp16", "cfg_scale", "text_embedding"}
+        if owner is not None and set(model_kwargs) <= known and denoised_fn is None and cond_fn is None:
+            # ---- whole range inside the engine (the dispatch rule of _loop); only progressive trails split it
+            B = img.shape[0]
+            x32, _, y64 = owner._prep(img, torch.zeros(B, dtype=torch.int64), model_kwargs.get("y"))
+            cfg_scale = float(model_kwargs.get("cfg_scale", 7.0)) if uses_cfg else 1.0
+            eng = owner.engine(B, guided=uses_cfg)
+            owner._set_text(model_kwargs.get("text_embedding"), B, guided=uses_cfg)
+            seg = end - start + 1
+            if progressive:
+                seg = max(1, min(seg, self.SEGMENT_BYTES // max(x32.numel() * 4, 1)))
+            lib = load_library()
+            i = start
+            while i <= end:
+                hi = min(end, i + seg - 1)
+                cnt = hi - i + 1
+                trail_s = trail_0 = None
+                if progressive:
+                    trail_s = torch.empty((cnt,) + tuple(x32.shape), device=x32.device, dtype=torch.float32)
+                    trail_0 = torch.empty_like(trail_s)
+                with torch.cuda.device(x32.device):
+                    check(lib.latte_invert_loop(eng, self._h, int(bool(clip_denoised)), int(uses_cfg), cfg_scale, ptr(x32),
+                                                ptr(y64), B, i, hi, ptr(trail_s), ptr(trail_0), stream_ptr()))
+                    if progressive:
+                        torch.cuda.current_stream().synchronize()      # the segment's trails are handed out next, as in _loop
+                for k in range(cnt if progressive else 0):
+                    yield {"sample": trail_s[k], "pred_xstart": trail_0[k]}
+                i = hi + 1
+            if not progressive:
+                yield {"sample": x32, "pred_xstart": None}
+            return
+        # ---- generic model callable, step by step
+        indices = list(range(start, end + 1))
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        for i in indices:
+            out = self._call_model(model, img, i, model_kwargs)
+            r = self._step("ddim_reverse", out, img, i, None, 0.0, clip_denoised, denoised_fn, cond_fn, model_kwargs)
+            yield r
+            img = r["sample"]
+
+    def ddim_reverse_sample_loop_progressive(self, model, x, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                             model_kwargs=None, progress=False, start_index=0, end_index=None):
+        """``ddim_reverse_sample_loop`` yielding every step's {"sample", "pred_xstart"} in execution order."""
+        yield from self._reverse_loop(model, x, clip_denoised, denoised_fn, cond_fn, model_kwargs, progress, start_index,
+                                      end_index, True)
+
+    def ddim_reverse_sample_loop(self, model, x, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                                 progress=False, start_index=0, end_index=None):
+        """DDIM inversion of a clip ``x`` [N, F, C, H, W]: the reference has no such loop; this is the obvious
+        ``for i in range(T)`` around its ``ddim_reverse_sample`` (gd:566-602), over the respaced indices ``start_index`` ...
+        ``end_index`` ascending (default 0 ... T-1).  Index ``i`` evaluates the model at level ``i`` and carries ``x`` to level
+        ``i + 1``; level T is pure noise, ONE level above where ``ddim_sample_loop`` starts (it takes its input as level T-1),
+        so the way back from ``end_index = k - 1`` is ``ddim_sample_loop(..., noise=x_k, start_index=k)``.  With
+        ``model.forward`` / ``model.forward_with_cfg`` of a ``latte_amd.Latte``, known kwargs and no hooks, the whole range is
+        ONE ``latte_invert_loop`` call; any other callable is driven step by step.  Returns the inverted latent."""
+        final = None
+        for final in self._reverse_loop(model, x, clip_denoised, denoised_fn, cond_fn, model_kwargs, progress, start_index,
+                                        end_index, False):
             pass
         return final["sample"]
 

@@ -124,12 +124,12 @@ class LattePipeline:
         a_p = [float(sch.alphas_cumprod[t - ratio]) if t - ratio >= 0 else float(sch.final_alpha_cumprod) for t in ts]
         return ts, a_t, a_p
 
-    def _fused_plan(self, do_cfg, callback, latent_channels):
+    def _fused_plan(self, do_cfg, callback, latent_channels, scheduler=None):
         """The scheduler's ``engine_plan()`` table when the chain can run inside the engine as latte_t2v_guided_linear_loop: guidance
         on, no per-step callback, the engine transformer, a scheduler that describes its update as such a table (Euler,
         Euler-ancestral, Heun, DPM-Solver++ of latte_amd.schedulers).  Else None: the step-by-step loop."""
         from .t2v import LatteT2V
-        sch, tr = self.scheduler, self.transformer
+        sch, tr = scheduler or self.scheduler, self.transformer
         if not (do_cfg and callback is None and getattr(self, "allow_fused_loop", True) and isinstance(tr, LatteT2V)
                 and tr.config.out_channels in (latent_channels, 2 * latent_channels) and hasattr(sch, "engine_plan")):
             return None
@@ -168,6 +168,54 @@ class LattePipeline:
         video = torch.cat(video)
         video = video.reshape(b, f, *video.shape[1:]).permute(0, 1, 3, 4, 2)
         return ((video / 2.0 + 0.5).clamp(0, 1) * 255).to(dtype=torch.uint8).cpu().contiguous()
+
+    # ------------------------------------------------------------------ DDIM inversion (no counterpart in pipeline_latte.py)
+    @torch.no_grad()
+    def invert(self, prompt=None, latents=None, num_inference_steps=50, guidance_scale=1.0, negative_prompt="", prompt_embeds=None,
+               negative_prompt_embeds=None, enable_temporal_attentions=True, clean_caption=True, mask_feature=True):
+        """DDIM inversion of clean ``latents`` [B, 4, F, h, w] under a prompt: ``DDIMInverseScheduler`` (``self.inverse_scheduler``,
+        default ``DDIMInverseScheduler()``) for ``num_inference_steps`` evaluations -> latents at level abar[u_{n-1}], where
+        ``__call__(latents=..., num_inference_steps=n)`` with the DDIM scheduler starts.  Guidance above 1 runs the whole chain
+        inside the engine (``latte_t2v_guided_linear_loop``); otherwise ``LatteT2V.forward`` is stepped from Python without a
+        guidance pair.  The prompt is encoded and the text context installed as in ``__call__``."""
+        from .schedulers import DDIMInverseScheduler
+        if latents is None:
+            raise ValueError("invert needs the clean `latents` [B, 4, F, h, w] of the clip")
+        if prompt is None and prompt_embeds is None:
+            raise ValueError("Provide either `prompt` or `prompt_embeds`.")
+        cfg = self.transformer.config
+        device = self._device
+        latents = latents.to(device=device, dtype=torch.float32)
+        if latents.dim() != 5 or latents.shape[1] != cfg.in_channels:
+            raise ValueError(f"latents must be [B, {cfg.in_channels}, F, h, w], got {tuple(latents.shape)}")
+        prompts = 1 if isinstance(prompt, str) else len(prompt) if prompt is not None else prompt_embeds.shape[0]
+        if prompts != latents.shape[0]:
+            raise ValueError(f"one prompt per clip: {prompts} prompts for {latents.shape[0]} clips")
+        do_cfg = guidance_scale > 1.0
+        prompt_embeds, negative_prompt_embeds = self.encode_prompt(
+            prompt, do_cfg, negative_prompt=negative_prompt, device=device, prompt_embeds=prompt_embeds,
+            negative_prompt_embeds=negative_prompt_embeds, clean_caption=clean_caption, mask_feature=mask_feature)
+        if do_cfg:
+            prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0)
+        sch = getattr(self, "inverse_scheduler", None) or DDIMInverseScheduler()
+        sch.set_timesteps(num_inference_steps, device=device)
+        plan = self._fused_plan(do_cfg, None, cfg.in_channels, scheduler=sch)
+        if plan is not None:
+            self.transformer.set_text(prompt_embeds)
+            return self.transformer.guided_linear_loop(latents, plan, None, guidance_scale, enable_temporal_attentions)
+        added_cond_kwargs = {"resolution": None, "aspect_ratio": None}
+        for t in sch.timesteps:
+            x_in = sch.scale_model_input(torch.cat([latents] * 2) if do_cfg else latents, t)
+            current = t.reshape(-1)[:1].to(device).expand(x_in.shape[0])
+            noise_pred = self.transformer(x_in, encoder_hidden_states=prompt_embeds, timestep=current, added_cond_kwargs=added_cond_kwargs,
+                                          enable_temporal_attentions=enable_temporal_attentions, return_dict=False)[0]
+            if do_cfg:
+                uncond, text = noise_pred.chunk(2)
+                noise_pred = uncond + guidance_scale * (text - uncond)
+            if cfg.out_channels // 2 == cfg.in_channels:
+                noise_pred = noise_pred.chunk(2, dim=1)[0]
+            latents = sch.step(noise_pred, t, latents, return_dict=False)[0]
+        return latents
 
     # ------------------------------------------------------------------ pipeline_latte.py:516-771
     @torch.no_grad()

@@ -13,7 +13,8 @@ The other four classes -- ``EulerDiscreteScheduler``, ``EulerAncestralDiscreteSc
 published updates (Karras et al. 2022, algorithms 1-2; Lu et al. 2022, DPM-Solver++ 2M) the same way: memory-derived, NOT pinned
 against diffusers.  Each one also describes its chain as a table, ``engine_plan()``: one row of ``PLAN_COLS`` doubles per denoiser
 evaluation (include/latte_amd.h: latte_t2v_guided_linear_loop), which is what lets ``LattePipeline`` run the whole guided chain
-inside the engine.  ``timestep_spacing`` is "leading" (the DDIM stand-in's) or "trailing"; "linspace" is refused: it gives fractional
+inside the engine.  ``DDIMInverseScheduler`` walks the DDIM chain the other way (``LattePipeline.invert``) as the same kind of table.
+``timestep_spacing`` is "leading" (the DDIM stand-in's) or "trailing"; "linspace" is refused: it gives fractional
 timesteps and interpolated sigmas, and the engine's timestep input is int64 (``LatteT2V.forward`` truncates).
 
 Notation: abar_i = alphas_cumprod at the i-th timestep of the set, abar = 1 after the last one.  The k-diffusion family (Euler,
@@ -294,3 +295,39 @@ class DPMSolverMultistepScheduler(_LinearScheduler):
             r0 = (lam[i] - lam[i - 1]) / h
             m0 = m0 + float(0.5 / r0) * (m0 - m1)
         return float(sg[i + 1] / sg[i]) * x - float(al[i + 1] * np.expm1(-h)) * m0
+
+
+class DDIMInverseScheduler(_LinearScheduler):
+    """DDIM inversion for text-to-video: the algebraic inverse of this project's ``DDIMScheduler`` chain at eta = 0, with its
+    constructor keys (``set_alpha_to_one`` among them).  ``set_timesteps(n)`` gives the sampling set of ``n`` steps in ASCENDING
+    order u_0 < ... < u_{n-1}.  Evaluation j runs the denoiser at u_j and carries x from level a_from to level a_to = abar[u_j], where
+    a_from = ``final_alpha_cumprod`` (1, or abar[0] with ``set_alpha_to_one=False``) for j = 0 and abar[u_{j-1}] after it:
+
+        x' = sqrt(a_to / a_from) x + (sqrt(1 - a_to) - sqrt(a_to (1 - a_from) / a_from)) eps
+
+    which undoes the DDIM step from a_to down to a_from for the same eps.  After n evaluations x is at level abar[u_{n-1}], where a
+    DDIM run of the same n starts.  One ``engine_plan()`` row per evaluation (m_eps = 1, c_x, c0; no history, no noise), so
+    ``latte_t2v_guided_linear_loop`` runs the chain unchanged.
+
+    Memory-derived and NOT pinned against diffusers.  The denoiser sees the timestep of the level being ENTERED (u_j with x still at
+    the level below it) -- the convention of diffusers-style inversion; the class-conditional engine's ``ddim_reverse_sample`` follows the
+    reference instead and evaluates at the level being LEFT."""
+
+    def __init__(self, set_alpha_to_one=True, clip_sample=False, **kw):
+        if clip_sample:
+            raise ValueError("DDIMInverseScheduler has no clip_sample: a clamped x_0 prediction has no inverse")
+        super().__init__(**kw)
+        self.final_alpha_cumprod = 1.0 if set_alpha_to_one else float(self.alphas_cumprod[0])
+
+    def _build(self, ts):
+        up = [int(t) for t in ts[::-1]]                                    # ascending
+        self._eval_timesteps = up
+        rows, a_from = [], self.final_alpha_cumprod
+        for t in up:
+            a_to = float(self.alphas_cumprod[t])
+            rows.append(self._row(t, c_x=(a_to / a_from) ** 0.5, c0=(1.0 - a_to) ** 0.5 - (a_to * (1.0 - a_from) / a_from) ** 0.5))
+            a_from = a_to
+        self._rows = np.array(rows)
+
+    def _update(self, i, eps, x, generator):
+        return float(self._rows[i, P_CX]) * x + float(self._rows[i, P_C0]) * eps
