@@ -109,7 +109,9 @@ void latte_engine_destroy(latte_engine_t* e);
  * Operands whose shape has no split form stay plain: latte_engine_get_option("guided_split_active") reports the bits the last
  * guided forward really used),
  * "seed" (Philox seed of the engine's own noise stream, used by latte_sample_loop when no noise
- * pointer is supplied; the reference draws torch.randn_like, gaussian_diffusion.py:413,555). */
+ * pointer is supplied; the reference draws torch.randn_like, gaussian_diffusion.py:413,555),
+ * "train_timesteps" (default 1000: the number of timesteps the model was trained on, diffusion_steps of create_diffusion;
+ * latte_sample_plan_loop refuses a plan row at or above it -- nothing else reads it). */
 int latte_engine_set_option(latte_engine_t* e, const char* name, int64_t value);
 /* Reads an option back (same names), or one of the read-only facts "guided_split_active" (bits of "guided_split" the last guided
  * forward ran with) and "guided_split_failed" (1 after an allocation for the split operands failed: guided calls then run plain). */
@@ -214,6 +216,31 @@ int latte_sample_loop_ex(latte_engine_t* e, const latte_schedule_t* s, int metho
  * error codes as latte_sample_loop_ex; nothing is launched when one fails.  Stream-ordered, no synchronisation. */
 int latte_invert_loop(latte_engine_t* e, const latte_schedule_t* s, int clip_denoised, int guided, float cfg_scale, float* x,
                       const int64_t* y, int batch, int start_index, int end_index, float* trail_sample, float* trail_x0, void* stream);
+
+/* ------------------------------------------------------------------ linear samplers as a plan (Euler, Euler-ancestral, Heun, DPM-Solver++)
+ * The class-conditional / unconditional / text-embedding engine's counterpart of latte_t2v_guided_linear_loop (below): a whole chain of
+ * any sampler whose update is a linear combination of the latents, the newest eps, up to three remembered outputs and fresh noise, as
+ * ONE call.  plan: HOST doubles [n_evals][LATTE_PLAN_COLS] (latte_amd/schedulers.py: engine_plan()), narrowed to fp32 at launch:
+ *   timestep (integral, ORIGINAL -- no latte_schedule_t is involved), in_scale, m_x, m_eps, c_x, c0, c1, c2, c3, c_noise, push (0 / 1),
+ *   reserved (0)
+ * Per row: Latte.forward (guided != 0: Latte.forward_with_cfg on the doubled batch, first half duplicated, for ANY cfg_scale) on
+ * in_scale * x at the row's timestep, eps = the first C output channels (guided: uncond + cfg_scale (cond - uncond), rows b and
+ * b + batch / 2 alike; the learned-sigma channels are dropped), then
+ *   m0 = m_x x + m_eps eps;   x = c_x x + c0 m0 + c1 h1 + c2 h2 + c3 h3 + c_noise noise[row];   push: (h1, h2, h3) <- (m0, h1, h2)
+ * x: [batch, F, C, H, W] fp32 in place.  The conditioning of the chain (t_embedder of every row's timestep, then the adaLN outputs in
+ * chunks of <= 256 rows) is computed as latte_sample_loop_ex computes it; timesteps may repeat (Heun).
+ * noise: DEVICE [n_evals][batch * F * C * H * W] fp32 (only rows with c_noise != 0 are read), or NULL = those rows draw from the
+ * engine's Philox stream (option "seed"), as latte_sample_loop_ex does.  trail_sample: NULL or [n_evals][...] receiving x after every row.
+ * LATTE_ERR_INVALID for a non-finite entry, a non-integral or negative timestep, a timestep at or above the trained range (option
+ * "train_timesteps", default 1000), push outside {0, 1} or a non-zero reserved column, a c_j (j >= 1) that is non-zero before j rows
+ * with push have run, an odd guided batch, a class-conditional model without y, n_evals > LATTE_PLAN_MAX_EVALS and H * W % 4 != 0;
+ * LATTE_ERR_STATE for batch > max_batch and for a text-embedding model without latte_engine_set_text_embedding of `batch` rows.  Every
+ * check runs before the first launch: x is untouched when one fails.  The ring of remembered outputs and the scaled model input are
+ * taken from the engine's arena by the first call only.  Stream-ordered; the plan is consumed before the call returns. */
+#define LATTE_PLAN_COLS 12   /* same columns as LATTE_T2V_PLAN_COLS */
+#define LATTE_PLAN_MAX_EVALS 4096
+int latte_sample_plan_loop(latte_engine_t* e, int guided, float cfg_scale, float* x, const int64_t* y, int batch, int n_evals,
+                           const double* plan, const float* noise, float* trail_sample, void* stream);
 
 /* ------------------------------------------------------------------ training path, forward evaluation
  * SURVEY.md section 8(f) rank 3, first slice: the loss VALUES of GaussianDiffusion.training_losses

@@ -110,6 +110,16 @@ int latte_debug_t2v_linear_step(float* x, float* x_in, const float* model_out, c
                                 const float* noise, float* hist_write, int b, int C, int Cout, int F, int hw, float scale, float m_x,
                                 float m_eps, float c_x, float c0, float c1, float c2, float c3, float c_noise, float in_scale_next,
                                 int push, void* stream);
+/* One launch of the step kernel of latte_sample_plan_loop (csrc/pointwise.hip: linear_step_kernel): the formula above on the
+ * class-conditional / unconditional engine's layout -- x [B, F, C, hw] in place, model_out [B, F, Cout, hw] with Cout = C or 2 C (only the
+ * first C channels are read).  guided != 0: B is the doubled batch of forward_with_cfg and eps of rows b and b + B / 2 is
+ * uncond + scale (cond - uncond), cond = row b of model_out's first half, uncond = the same row of its second half; every one of the B
+ * rows is updated.  guided == 0: eps is the row's own output, scale is unused.  NULL / aliasing rules as above.  16-byte accesses only:
+ * hw % 4 != 0, a misaligned buffer, an odd guided B or another Cout is refused. */
+int latte_debug_linear_step(float* x, float* x_in, const float* model_out, const float* h1, const float* h2, const float* h3,
+                            const float* noise, float* hist_write, int B, int C, int Cout, int F, int hw, int guided, float scale, float m_x,
+                            float m_eps, float c_x, float c0, float c1, float c2, float c3, float c_noise, float in_scale_next, int push,
+                            void* stream);
 /* latte_debug_attention with the f16 + fp8-remainder output of guided calls: out [rows, D] (bit for bit the plain call's output) and
  * out8 [rows, D] bytes = e4m3(clamp((value - out) * 2^12, +-448)); f16 only, every kernel of the un-fused path (L <= 16, generic flash,
  * 128 < L <= 256, L > 256). */

@@ -44,6 +44,7 @@ class VideoPlan(ctypes.Structure):
 
 
 T2V_PLAN_COLS = 12   # LATTE_T2V_PLAN_COLS of include/latte_amd.h
+PLAN_COLS = 12       # LATTE_PLAN_COLS
 DTYPES = {"bf16": 0, "bfloat16": 0, "f16": 1, "fp16": 1, "float16": 1}
 
 # name -> (restype, argtypes); mirrors include/latte_amd.h and include/latte_amd_debug.h
@@ -78,6 +79,7 @@ PROTOTYPES = {
     "latte_sample_loop_ex": (c_int, [c_void, c_void, c_int, c_f32, c_int, c_int, c_f32, c_void, c_void, c_int, c_int, c_int,
                                      c_void, c_void, c_void, c_void]),
     "latte_invert_loop": (c_int, [c_void, c_void, c_int, c_int, c_f32, c_void, c_void, c_int, c_int, c_int, c_void, c_void, c_void]),
+    "latte_sample_plan_loop": (c_int, [c_void, c_int, c_f32, c_void, c_void, c_int, c_int, c_void, c_void, c_void, c_void]),
     "latte_q_sample": (c_int, [c_void, c_void, c_void, c_void, c_int, c_i64, c_void, c_void]),
     "latte_training_workspace_floats": (c_i64, [c_int, c_i64]),
     "latte_training_losses": (c_int, [c_void, c_int, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void,
@@ -188,6 +190,7 @@ PROTOTYPES = {
     "latte_debug_cond_rows": (c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_void]),
     "latte_debug_mask_bias": (c_int, [c_void, c_void, c_i64, c_void]),
     "latte_debug_t2v_linear_step": (c_int, [c_void] * 8 + [c_int] * 5 + [c_f32] * 10 + [c_int, c_void]),
+    "latte_debug_linear_step": (c_int, [c_void] * 8 + [c_int] * 6 + [c_f32] * 10 + [c_int, c_void]),
     "latte_debug_qkv_attention": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                           c_int, c_void]),
     "latte_debug_qkv_attention_trace": (c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int,

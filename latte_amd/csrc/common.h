@@ -251,6 +251,14 @@ struct T2VLinearStep {
 int launch_t2v_guided_linear_step(float* x, float* x_in, const float* model_out, const float* h1, const float* h2, const float* h3,
                                   const float* noise, float* hw, int b, int C, int Cout, int F, int HW, const T2VLinearStep& s,
                                   hipStream_t st);
+// The same step in the class-conditional / unconditional engine's layout (latte_sample_plan_loop): x [B, F, C, HW] in place, model_out
+// [B, F, Cout, HW] with Cout = C or 2 C (the variance channels are never read).  guided: the doubled batch of forward_with_cfg
+// (latte.py:379-398) -- eps of rows b and b + B / 2 is uncond + scale (cond - uncond), cond = row b % (B / 2) of model_out, uncond = row
+// b % (B / 2) + B / 2, the order of sampler_update_kernel's raw_cfg path; every one of the B rows is updated.  Not guided: eps is the row's
+// own output and `scale` is unused.  Pointer rules as above; 16-byte accesses only: HW % 4 != 0 or a misaligned buffer is refused.
+int launch_linear_step(float* x, float* x_in, const float* model_out, const float* h1, const float* h2, const float* h3,
+                       const float* noise, float* hw, int B, int C, int Cout, int F, int HW, int guided, const T2VLinearStep& s,
+                       hipStream_t st);
 int launch_mask_bias(const float* mask, float* bias, size_t n, hipStream_t st);   // bias = (1 - mask) * -10000
 int launch_cfg_combine(float* out, int half_batch, int F, int Cout, int HW, float cfg_scale, hipStream_t st);
 int launch_convert_f32_to_h16(const float* in, half_t* out, int64_t n, int dtype, hipStream_t st);

@@ -324,6 +324,17 @@ int latte_debug_t2v_linear_step(float* x, float* x_in, const float* model_out, c
   return launch_t2v_guided_linear_step(x, x_in, model_out, h1, h2, h3, noise, hist_write, b, C, Cout, F, hw, s, (hipStream_t)stream);
 }
 
+int latte_debug_linear_step(float* x, float* x_in, const float* model_out, const float* h1, const float* h2, const float* h3,
+                            const float* noise, float* hist_write, int B, int C, int Cout, int F, int hw, int guided, float scale, float m_x,
+                            float m_eps, float c_x, float c0, float c1, float c2, float c3, float c_noise, float in_scale_next, int push,
+                            void* stream) {
+  if (!x || !x_in || !model_out) return fail(LATTE_ERR_INVALID, "linear_step: bad arguments");
+  if ((c1 != 0.0f && !h1) || (c2 != 0.0f && !h2) || (c3 != 0.0f && !h3) || (c_noise != 0.0f && !noise) || (push && !hist_write))
+    return fail(LATTE_ERR_INVALID, "linear_step: a buffer with a non-zero coefficient (or the pushed slot) is NULL");
+  const T2VLinearStep s{scale, m_x, m_eps, c_x, c0, c1, c2, c3, c_noise, in_scale_next, push ? 1 : 0};
+  return launch_linear_step(x, x_in, model_out, h1, h2, h3, noise, hist_write, B, C, Cout, F, hw, guided ? 1 : 0, s, (hipStream_t)stream);
+}
+
 int latte_debug_qkv_attention(const void* xn, const void* w, const float* bias, void* out, void* dbg_qkv, int B, int F, int T, int D,
                               int heads, int mode, int flags, int dtype, void* stream) {
   return latte_debug_qkv_attention_trace(xn, w, bias, out, dbg_qkv, nullptr, B, F, T, D, heads, mode, flags, dtype, stream);

@@ -120,6 +120,11 @@ struct latte_engine {
   int64_t temb_table_cap = 0, temb_own_cap = 0, temb_cap = 0, cond_cap = 0, mod_all_cap = 0;
   float *bpd_xt = nullptr, *bpd_ws = nullptr;   // latte_bpd_loop: x_t of the step, the reduction's per-block slots
   int64_t bpd_xt_cap = 0, bpd_ws_cap = 0;
+  // latte_sample_plan_loop (taken from the arena by its first call): the ring of three remembered outputs and the scaled model input,
+  // max_batch latents each; t_embedder of every row of the plan, in chain order
+  float *plan_hist[3] = {nullptr, nullptr, nullptr}, *plan_xin = nullptr, *plan_temb = nullptr;
+  int64_t plan_temb_cap = 0;
+  int train_timesteps = 1000;   // latte_sample_plan_loop refuses timesteps at or above it (diffusion_steps of create_diffusion)
   WeightSlots weights;
   DeviceArena arena;
   uint64_t seed = 0, rng_offset = 0;
@@ -372,14 +377,15 @@ int grow(latte_engine* e, float** p, int64_t* cap, int64_t need) {
 
 // Timestep-embedding table of a schedule: row i = t_embedder(timestep_map[i]) (latte.py:84-123, respace.py:125-130).
 // This is the [steps, D] fp32 table rank 0 broadcasts over RCCL in the multi-GPU driver (1.15 MB for 250 x 1152).
-int compute_temb_table(latte_engine* e, const latte_schedule_t* s, float* out, hipStream_t st) {
-  const int n = s->num_timesteps, D = e->D;
+// `ts`: n HOST timesteps (row i = t_embedder(ts[i]); repeats allowed).
+int compute_temb_rows(latte_engine* e, const int64_t* ts, int n, float* out, hipStream_t st) {
+  const int D = e->D;
   int rc;
   if (e->tmap_cap < n) {
     if ((rc = e->arena.alloc(&e->tmap_dev, (size_t)n, false))) return rc;
     e->tmap_cap = n;
   }
-  LATTE_HIP(hipMemcpyAsync(e->tmap_dev, s->timestep_map.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, st));
+  LATTE_HIP(hipMemcpyAsync(e->tmap_dev, ts, sizeof(int64_t) * n, hipMemcpyHostToDevice, st));
   LATTE_HIP(hipStreamSynchronize(st));   // the host vector may be freed by the caller
   if ((rc = grow(e, &e->temb_work, &e->temb_cap, (int64_t)n * D))) return rc;
   constexpr int CH = 64;   // rows per launch: the kernel keeps a weight row in registers and loops over the rows
@@ -392,6 +398,9 @@ int compute_temb_table(latte_engine* e, const latte_schedule_t* s, float* out, h
   }
   return LATTE_OK;
 }
+int compute_temb_table(latte_engine* e, const latte_schedule_t* s, float* out, hipStream_t st) {
+  return compute_temb_rows(e, s->timestep_map.data(), s->num_timesteps, out, st);
+}
 
 // ---- conditioning of a whole chain (latte_sample_loop_ex, latte_bpd_loop): it depends on (timestep, label) only, never on x.
 struct ChainCond {
@@ -399,6 +408,18 @@ struct ChainCond {
   int bu;              // conditioning rows per step: 1 for an unconditional model, else the batch
   int chunk_steps;     // steps whose rows fit mod_all at once
 };
+
+// chunk size and row buffers of a chain of n_run steps with cc->bu rows each
+int chain_row_buffers(latte_engine* e, int n_run, ChainCond* cc) {
+  const int D = e->D, bu = cc->bu;
+  int rc;
+  cc->chunk_steps = std::max(1, 256 / bu);
+  const int64_t rows_chunk = (int64_t)std::min(cc->chunk_steps, n_run) * bu;
+  if ((rc = grow(e, &e->cond_rows, &e->cond_cap, rows_chunk * D))) return rc;
+  if ((rc = grow(e, &e->mod_all, &e->mod_all_cap, rows_chunk * e->nmod))) return rc;
+  if (e->cfg.extras == 78 && (rc = grow(e, &e->cond_rows_t, &e->cond_t_cap, rows_chunk * D))) return rc;
+  return LATTE_OK;
+}
 
 // Picks the timestep-embedding table (computing the engine's own when none is installed for this timestep_map) and sizes the row
 // buffers.  The conditioning rows of the chain are produced in chunks of <= 256 rows (= 256 / bu steps), right before the steps
@@ -419,12 +440,7 @@ int chain_prepare(latte_engine* e, const latte_schedule_t* s, int bu, int n_run,
     }
     cc->temb = e->temb_own;
   }
-  cc->chunk_steps = std::max(1, 256 / bu);
-  const int64_t rows_chunk = (int64_t)std::min(cc->chunk_steps, n_run) * bu;
-  if ((rc = grow(e, &e->cond_rows, &e->cond_cap, rows_chunk * D))) return rc;
-  if ((rc = grow(e, &e->mod_all, &e->mod_all_cap, rows_chunk * e->nmod))) return rc;
-  if (e->cfg.extras == 78 && (rc = grow(e, &e->cond_rows_t, &e->cond_t_cap, rows_chunk * D))) return rc;
-  return LATTE_OK;
+  return chain_row_buffers(e, n_run, cc);
 }
 
 // conditioning of respaced steps [lo, lo + cnt) into mod_all: rows ordered by index ascending, row (i - lo) * bu + b
@@ -656,6 +672,11 @@ int latte_engine_set_option(latte_engine_t* e, const char* name, int64_t value) 
     e->rng_offset = 0;
     return LATTE_OK;
   }
+  if (k == "train_timesteps") {
+    if (value < 1 || value > (1 << 30)) return fail(LATTE_ERR_INVALID, "train_timesteps: the number of trained timesteps, >= 1");
+    e->train_timesteps = (int)value;
+    return LATTE_OK;
+  }
   return fail(LATTE_ERR_INVALID, "set_option: unknown option '" + k + "'");
 }
 
@@ -673,6 +694,7 @@ int latte_engine_get_option(const latte_engine_t* e, const char* name, int64_t* 
   else if (k == "guided_split_active") *value = e->guided_split_active;
   else if (k == "guided_split_failed") *value = e->split_failed ? 1 : 0;
   else if (k == "seed") *value = (int64_t)e->seed;
+  else if (k == "train_timesteps") *value = e->train_timesteps;
   else return fail(LATTE_ERR_INVALID, "get_option: unknown option '" + k + "'");
   return LATTE_OK;
 }
@@ -903,6 +925,103 @@ int latte_invert_loop(latte_engine_t* e, const latte_schedule_t* s, int clip_den
     c.cfg_scale = cfg_scale;
     float* x0 = trail_x0 ? trail_x0 + (size_t)k * numel : nullptr;
     if ((rc = launch_sampler_update(c, x, e->model_out, nullptr, batch, e->F, e->Cin, e->H * e->H, use_cfg ? 1 : 0, x, x0, st))) return rc;
+    if (trail_sample)
+      LATTE_HIP(hipMemcpyAsync(trail_sample + (size_t)k * numel, x, sizeof(float) * numel, hipMemcpyDeviceToDevice, st));
+  }
+  return LATTE_OK;
+}
+
+// ---- linear samplers as a plan (include/latte_amd.h; the table is latte_amd/schedulers.py: engine_plan())
+int latte_sample_plan_loop(latte_engine_t* e, int guided, float cfg_scale, float* x, const int64_t* y, int batch, int n_evals,
+                           const double* plan, const float* noise, float* trail_sample, void* stream) {
+  if (!e || !x || !plan || batch <= 0 || n_evals <= 0) return fail(LATTE_ERR_INVALID, "sample_plan_loop: bad arguments");
+  int rc = latte_engine_check_weights(e);
+  if (rc) return rc;
+  if (batch > e->max_batch) return fail(LATTE_ERR_STATE, "sample_plan_loop: batch exceeds max_batch");
+  const bool use_cfg = guided != 0;   // forward_with_cfg semantics for ANY scale, as latte_sample_loop_ex
+  if (use_cfg && (batch % 2)) return fail(LATTE_ERR_INVALID, "sample_plan_loop: guidance needs the doubled batch");
+  const int ex = e->cfg.extras;
+  if (ex == 2 && y == nullptr) return fail(LATTE_ERR_INVALID, "sample_plan_loop: class-conditional model needs y");
+  if (ex == 78 && e->txt_rows != batch)
+    return fail(LATTE_ERR_STATE, "sample_plan_loop: text-conditioned model needs latte_engine_set_text_embedding with one row per sample first");
+  if (n_evals > LATTE_PLAN_MAX_EVALS)
+    return fail(LATTE_ERR_INVALID, "sample_plan_loop: more than " + std::to_string(LATTE_PLAN_MAX_EVALS) + " evaluations");
+  const int HW = e->H * e->H;
+  if (HW % 4) return fail(LATTE_ERR_INVALID, "sample_plan_loop: H * W must be a multiple of 4 (16-byte accesses of the step kernel)");
+  // ---- the whole table is checked before anything is launched
+  enum { P_T = 0, P_IN, P_MX, P_MEPS, P_CX, P_C0, P_C1, P_C2, P_C3, P_CN, P_PUSH, P_RSV };
+  std::vector<int64_t> ts(n_evals);
+  bool scaled = false;
+  int pushed = 0;
+  for (int k = 0; k < n_evals; ++k) {
+    const double* r = plan + (size_t)k * LATTE_PLAN_COLS;
+    for (int j = 0; j < LATTE_PLAN_COLS; ++j)
+      if (!std::isfinite(r[j])) return fail(LATTE_ERR_INVALID, "sample_plan_loop: non-finite plan entry in row " + std::to_string(k));
+    if (r[P_T] < 0.0 || r[P_T] >= 9.0e15 || r[P_T] != std::floor(r[P_T]))
+      return fail(LATTE_ERR_INVALID, "sample_plan_loop: timestep of row " + std::to_string(k) + " is not a non-negative integer");
+    if (r[P_T] >= (double)e->train_timesteps)
+      return fail(LATTE_ERR_INVALID, "sample_plan_loop: timestep of row " + std::to_string(k) + " is outside the trained range [0, " +
+                                         std::to_string(e->train_timesteps) + ")");
+    if ((r[P_PUSH] != 0.0 && r[P_PUSH] != 1.0) || r[P_RSV] != 0.0)
+      return fail(LATTE_ERR_INVALID, "sample_plan_loop: push must be 0 or 1 and the reserved column 0 (row " + std::to_string(k) + ")");
+    for (int j = 1; j <= 3; ++j)
+      if (r[P_C0 + j] != 0.0 && pushed < j)
+        return fail(LATTE_ERR_INVALID, "sample_plan_loop: row " + std::to_string(k) + " reads history slot " + std::to_string(j) +
+                                           " before " + std::to_string(j) + " rows with push have run");
+    ts[k] = (int64_t)r[P_T];
+    scaled = scaled || r[P_IN] != 1.0;
+    pushed += r[P_PUSH] != 0.0;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t per = (size_t)e->F * e->Cin * HW;
+  const size_t numel = (size_t)batch * per;
+  if (!e->plan_xin) {   // first use: the ring and the scaled model input
+    for (auto& h : e->plan_hist)
+      if (!h && (rc = e->arena.alloc(&h, (size_t)e->max_batch * per, false))) return rc;
+    if ((rc = e->arena.alloc(&e->plan_xin, (size_t)e->max_batch * per, false))) return rc;
+  }
+  // ---- conditioning: t_embedder of every row (chain order), then the adaLN outputs chunk by chunk right before the rows that use them
+  if ((rc = grow(e, &e->plan_temb, &e->plan_temb_cap, (int64_t)n_evals * e->D))) return rc;
+  if ((rc = compute_temb_rows(e, ts.data(), n_evals, e->plan_temb, st))) return rc;
+  ChainCond cc;
+  cc.temb = e->plan_temb;
+  cc.bu = ex == 1 ? 1 : batch;
+  if ((rc = chain_row_buffers(e, n_evals, &cc))) return rc;
+  const int bu = cc.bu;
+  // what the denoiser reads: x itself when every in_scale is 1, else in_scale * x kept beside it by the step kernel
+  float* x_in = scaled ? e->plan_xin : x;
+  if (scaled) {
+    LATTE_HIP(hipMemcpyAsync(x_in, x, sizeof(float) * numel, hipMemcpyDeviceToDevice, st));
+    if ((rc = launch_scale_f32(x_in, (float)plan[P_IN], numel, st))) return rc;
+  }
+  int newest = 0;   // ring: h_j = plan_hist[(newest - (j - 1) + 3) % 3]; a push writes the oldest slot, which becomes h1
+  int chunk_lo = 0, chunk_hi = -1;   // rows covered by what mod_all currently holds
+  for (int k = 0; k < n_evals; ++k) {
+    const double* r = plan + (size_t)k * LATTE_PLAN_COLS;
+    if (k > chunk_hi) {
+      chunk_lo = k;
+      chunk_hi = std::min(n_evals - 1, k + cc.chunk_steps - 1);
+      if ((rc = chain_conditioning(e, cc, y, chunk_lo, chunk_hi - chunk_lo + 1, st))) return rc;
+    }
+    const float* mod_k = e->mod_all + (size_t)(k - chunk_lo) * bu * e->nmod;
+    if ((rc = run_forward(e, x_in, nullptr, y, batch, use_cfg, e->model_out, st, nullptr, mod_k, bu == 1 ? 0 : e->nmod))) return rc;
+    const float* nz = nullptr;
+    if (r[P_CN] != 0.0) {
+      if (noise) {
+        nz = noise + (size_t)k * numel;
+      } else {
+        if ((rc = launch_fill_normal(e->noise_buf, numel, e->seed, e->rng_offset, st))) return rc;
+        e->rng_offset += numel;
+        nz = e->noise_buf;
+      }
+    }
+    const bool last = k + 1 == n_evals;
+    const T2VLinearStep s{cfg_scale, (float)r[P_MX], (float)r[P_MEPS], (float)r[P_CX], (float)r[P_C0], (float)r[P_C1], (float)r[P_C2],
+                          (float)r[P_C3], (float)r[P_CN], last ? 1.0f : (float)r[LATTE_PLAN_COLS + P_IN], r[P_PUSH] != 0.0 ? 1 : 0};
+    if ((rc = launch_linear_step(x, last ? x : x_in, e->model_out, e->plan_hist[newest], e->plan_hist[(newest + 2) % 3],
+                                 e->plan_hist[(newest + 1) % 3], nz, e->plan_hist[(newest + 1) % 3], batch, e->Cin, e->Cout, e->F, HW,
+                                 use_cfg ? 1 : 0, s, st))) return rc;
+    if (s.push) newest = (newest + 1) % 3;
     if (trail_sample)
       LATTE_HIP(hipMemcpyAsync(trail_sample + (size_t)k * numel, x, sizeof(float) * numel, hipMemcpyDeviceToDevice, st));
   }

@@ -836,6 +836,54 @@ __global__ void t2v_guided_linear_step_kernel(float* x, float* x_in, const float
   }
 }
 
+// The same step on the class-conditional / unconditional engine's layout (common.h: launch_linear_step): x [B, F, C, hw], model output
+// [B, F, Cout, hw].  Four consecutive floats of one (sample, frame, channel) row per thread (hw % 4 == 0), 16-byte accesses; the aliasing
+// rules of the kernel above: x_in may be x, hwr may be one of h1..h3, every thread reads its elements before it writes them.
+template <bool GUIDED>
+__global__ void linear_step_kernel(float* x, float* x_in, const float* __restrict__ mo, const float* h1, const float* h2, const float* h3,
+                                   const float* __restrict__ noise, float* hwr, int B, int C, int Cout, int F, int hw, T2VLinearStep s) {
+#pragma clang fp contract(off)
+  constexpr int V = 4;
+  const size_t total = (size_t)B * F * C * hw / V;
+  const size_t hb = (size_t)(B >> 1);
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (size_t)gridDim.x * blockDim.x) {
+    const size_t i = q * V;
+    const size_t r = i % hw, c = (i / hw) % C, bf = i / ((size_t)hw * C);
+    float e0[V], e1[V], xv[V], a1[V], a2[V], a3[V], nz[V], m0[V], xn[V];
+    if constexpr (GUIDED) {
+      const size_t bc = (bf / F) % hb, f = bf % F;
+      ld_row<V>(e0, mo + (((bc * F + f) * Cout) + c) * hw + r);              // cond: the first half of the doubled batch (latte.py:395)
+      ld_row<V>(e1, mo + ((((bc + hb) * F + f) * Cout) + c) * hw + r);       // uncond: the second half
+    } else {
+      ld_row<V>(e0, mo + ((bf * Cout) + c) * hw + r);
+    }
+    ld_row<V>(xv, x + i);
+    if (s.c1 != 0.0f) ld_row<V>(a1, h1 + i);
+    if (s.c2 != 0.0f) ld_row<V>(a2, h2 + i);
+    if (s.c3 != 0.0f) ld_row<V>(a3, h3 + i);
+    if (s.c_noise != 0.0f) ld_row<V>(nz, noise + i);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      float eps = e0[j];
+      if constexpr (GUIDED) eps = e1[j] + s.scale * (e0[j] - e1[j]);         // latte.py:396: uncond + s (cond - uncond)
+      m0[j] = s.m_x * xv[j] + s.m_eps * eps;
+      float v = s.c_x * xv[j] + s.c0 * m0[j];
+      if (s.c1 != 0.0f) v = v + s.c1 * a1[j];
+      if (s.c2 != 0.0f) v = v + s.c2 * a2[j];
+      if (s.c3 != 0.0f) v = v + s.c3 * a3[j];
+      if (s.c_noise != 0.0f) v = v + s.c_noise * nz[j];
+      xn[j] = v;
+    }
+    st_row<V>(x + i, xn);
+    if (x_in != x) {
+#pragma unroll
+      for (int j = 0; j < V; ++j) xv[j] = s.in_scale_next * xn[j];
+      st_row<V>(x_in + i, xv);
+    }
+    if (s.push) st_row<V>(hwr + i, m0);
+  }
+}
+
 __global__ void training_combine_kernel(const float* __restrict__ mse, const float* __restrict__ vb, int has_vb, int kl_only,
                                         float vb_scale, int batch, float* mse_out, float* vb_out, float* loss_out) {
 #pragma clang fp contract(off)
@@ -1028,6 +1076,25 @@ int launch_t2v_guided_linear_step(float* x, float* x_in, const float* model_out,
   else
     hipLaunchKernelGGL(t2v_guided_linear_step_kernel<1>, dim3(grid_for(total, 256)), dim3(256), 0, st, x, x_in, model_out, h1, h2, h3,
                        noise, hw, b, C, Cout, F, HW, s);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+
+int launch_linear_step(float* x, float* x_in, const float* model_out, const float* h1, const float* h2, const float* h3,
+                       const float* noise, float* hw, int B, int C, int Cout, int F, int HW, int guided, const T2VLinearStep& s,
+                       hipStream_t st) {
+  if (B < 1 || C < 1 || F < 1 || HW < 1 || (Cout != C && Cout != 2 * C)) return fail(LATTE_ERR_INVALID, "linear_step: bad shape (Cout must be C or 2 C)");
+  if (guided && (B % 2)) return fail(LATTE_ERR_INVALID, "linear_step: guidance needs the doubled batch");
+  auto aligned = [](const void* p) { return ((uintptr_t)p & 15) == 0; };   // a null (unused) pointer counts as aligned
+  if (HW % 4 != 0 || !(aligned(x) && aligned(x_in) && aligned(model_out) && aligned(h1) && aligned(h2) && aligned(h3) && aligned(noise) && aligned(hw)))
+    return fail(LATTE_ERR_INVALID, "linear_step: HW must be a multiple of 4 and every buffer 16-byte aligned");
+  const size_t total = (size_t)B * F * C * HW;
+  if (guided)
+    hipLaunchKernelGGL(linear_step_kernel<true>, dim3(grid_for(total / 4, 256)), dim3(256), 0, st, x, x_in, model_out, h1, h2, h3, noise, hw,
+                       B, C, Cout, F, HW, s);
+  else
+    hipLaunchKernelGGL(linear_step_kernel<false>, dim3(grid_for(total / 4, 256)), dim3(256), 0, st, x, x_in, model_out, h1, h2, h3, noise, hw,
+                       B, C, Cout, F, HW, s);
   LATTE_HIP(hipGetLastError());
   return LATTE_OK;
 }

@@ -6,7 +6,9 @@
   8-12 host->device coefficient copies per step, gaussian_diffusion.py:869-881);
 * whole loop: when the model callable is a ``latte_amd.Latte`` method the loop runs inside the
   engine (``latte_sample_loop``; ``latte_invert_loop`` for DDIM inversion); any other callable following
-  the model-callable protocol is driven step by step with the same update kernel.
+  the model-callable protocol is driven step by step with the same update kernel;
+* ``linear_sample_loop`` (not in the reference): Euler, Euler-ancestral, Heun and DPM-Solver++(2M) on the diffusion's own
+  timesteps, as ONE ``latte_sample_plan_loop`` call for a ``latte_amd.Latte`` method.
 """
 import ctypes
 
@@ -16,6 +18,8 @@ import torch
 from . import _lib
 from ._lib import LatteError, check, load_library, ptr, stream_ptr
 from .models import Latte
+from .schedulers import (DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler,
+                         HeunDiscreteScheduler)
 
 _TABLES = ["betas", "alphas_cumprod", "alphas_cumprod_prev", "alphas_cumprod_next", "sqrt_recip_alphas_cumprod",
            "sqrt_recipm1_alphas_cumprod", "posterior_variance", "posterior_log_variance_clipped",
@@ -23,6 +27,8 @@ _TABLES = ["betas", "alphas_cumprod", "alphas_cumprod_prev", "alphas_cumprod_nex
            "sqrt_one_minus_alphas_cumprod"]
 _LOSS = {"mse": 0, "rescaled_mse": 1, "kl": 2, "rescaled_kl": 3}
 _METHOD = {"ddpm": 0, "ddim": 1, "ddim_reverse": 2}
+LINEAR_METHODS = {"euler": EulerDiscreteScheduler, "euler_a": EulerAncestralDiscreteScheduler, "heun": HeunDiscreteScheduler,
+                  "dpmsolver++": DPMSolverMultistepScheduler}
 
 
 class SpacedDiffusion:
@@ -258,6 +264,97 @@ class SpacedDiffusion:
         final = None
         for final in self._loop("ddim", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
                                 progress, eta, False, start_index, end_index):
+            pass
+        return final["sample"]
+
+    # ------------------------------------------------------------------ linear samplers (not in the reference)
+    def linear_scheduler(self, method="dpmsolver++"):
+        """The ``latte_amd.schedulers`` object of ``method`` ("euler" | "euler_a" | "heun" | "dpmsolver++") set to THIS diffusion's
+        timesteps: ``timestep_map`` descending with ``alphas_cumprod`` at them, so ``create_diffusion("20")`` means 20 steps (39
+        evaluations for Heun) as it does for ``ddim_sample_loop``.  Host only."""
+        if self.predict_xstart:
+            raise LatteError("linear_sample_loop: the linear samplers take an eps-prediction model (predict_xstart=False)")
+        if method not in LINEAR_METHODS:
+            raise LatteError(f"linear_sample_loop: method must be one of {sorted(LINEAR_METHODS)}, got {method!r}")
+        sch = LINEAR_METHODS[method](num_train_timesteps=self.original_num_steps)
+        sch.set_timesteps(timesteps=self.timestep_map[::-1], alphas_cumprod_at=self.alphas_cumprod[::-1])
+        return sch
+
+    def _linear_loop(self, model, shape, noise, method, model_kwargs, device, progress, step_noise, progressive):
+        sch = self.linear_scheduler(method)
+        plan = np.ascontiguousarray(sch.engine_plan(), dtype=np.float64)
+        n_evals = plan.shape[0]
+        model_kwargs = dict(model_kwargs or {})
+        assert isinstance(shape, (tuple, list))
+        owner, uses_cfg = self._engine_model(model)
+        if device is None and owner is None and noise is not None:
+            device = noise.device
+        device = self._device(model, device)
+        img = noise if noise is not None else torch.randn(*shape, device=device)
+        img = img.to(device=device, dtype=torch.float32).contiguous() * float(sch.init_noise_sigma)
+        if img.dim() != 5:
+            raise LatteError("shape must be [N, F, C, H, W]")
+        nz = None
+        if step_noise is not None:
+            if tuple(step_noise.shape) != (n_evals,) + tuple(img.shape):
+                raise LatteError(f"step_noise must be [{n_evals}, ...latents]: one slab per denoiser evaluation of {method!r}")
+            nz = step_noise.to(device=device, dtype=torch.float32).contiguous()
+        known = {"y", "use_fp16", "cfg_scale", "text_embedding"}
+        if owner is not None and set(model_kwargs) <= known:
+            # ---- whole chain inside the engine: one call
+            _lib.require_gpu()
+            B = img.shape[0]
+            x32, _, y64 = owner._prep(img, torch.zeros(B, dtype=torch.int64), model_kwargs.get("y"))
+            cfg_scale = float(model_kwargs.get("cfg_scale", 7.0)) if uses_cfg else 1.0
+            eng = owner.engine(B, guided=uses_cfg)
+            owner._set_text(model_kwargs.get("text_embedding"), B, guided=uses_cfg)
+            lib = load_library()
+            check(lib.latte_engine_set_option(eng, b"train_timesteps", self.original_num_steps))
+            trail = torch.empty((n_evals,) + tuple(x32.shape), device=x32.device, dtype=torch.float32) if progressive else None
+            with torch.cuda.device(x32.device):
+                check(lib.latte_sample_plan_loop(eng, int(uses_cfg), cfg_scale, ptr(x32), ptr(y64), B, n_evals, plan.ctypes.data,
+                                                 ptr(nz), ptr(trail), stream_ptr()))
+                if nz is not None or progressive:
+                    torch.cuda.current_stream().synchronize()      # the noise may be released / the trail is handed out next
+            for k in range(n_evals if progressive else 0):
+                yield {"sample": trail[k], "pred_xstart": None}
+            if not progressive:
+                yield {"sample": x32, "pred_xstart": None}
+            return
+        # ---- generic model callable, step by step: the scheduler's own scale_model_input / step around it
+        C = img.shape[2]
+        steps = list(enumerate(sch.timesteps.tolist()))
+        if progress:
+            from tqdm.auto import tqdm
+            steps = tqdm(steps)
+        for k, t in steps:
+            tt = torch.full((img.shape[0],), t, device=img.device, dtype=torch.int64)   # ORIGINAL timesteps: no _WrappedModel here
+            out = model(sch.scale_model_input(img, t), tt, **model_kwargs)
+            if isinstance(out, tuple):
+                out = out[0]
+            if out.shape[2] not in (C, 2 * C):
+                raise AssertionError(f"model output has {out.shape[2]} channels for {C}-channel latents")
+            eps = out[:, :, :C].float()                            # the learned-sigma half is dropped; forward_with_cfg already guided it
+            img = sch.step(eps, t, img, return_dict=False, noise=None if nz is None else nz[k])[0]
+            yield {"sample": img, "pred_xstart": None}
+
+    def linear_sample_loop_progressive(self, model, shape, noise=None, method="dpmsolver++", model_kwargs=None, device=None,
+                                       progress=False, step_noise=None):
+        """``linear_sample_loop`` yielding {"sample", "pred_xstart": None} after every denoiser evaluation."""
+        yield from self._linear_loop(model, shape, noise, method, model_kwargs, device, progress, step_noise, True)
+
+    def linear_sample_loop(self, model, shape, noise=None, method="dpmsolver++", model_kwargs=None, device=None, progress=False,
+                           step_noise=None):
+        """Sampling with a linear multistep / Runge-Kutta sampler in place of DDIM / DDPM: ``method`` "euler", "euler_a" (ancestral),
+        "heun" or "dpmsolver++" (2M) from ``latte_amd.schedulers``, on this diffusion's own ``timestep_map`` (``linear_scheduler``).  The
+        initial latents are ``noise * init_noise_sigma``; the model sees ORIGINAL timesteps; the learned-sigma half of its output is
+        dropped and nothing is clipped.  With ``model.forward`` / ``model.forward_with_cfg`` of a ``latte_amd.Latte`` and known kwargs
+        the chain is ONE ``latte_sample_plan_loop`` call; any other callable is driven through the scheduler's ``scale_model_input`` /
+        ``step``.  ``step_noise`` [n_evals, ...latents] gives the draws of the stochastic steps ("euler_a") to either path; without it
+        the engine path draws from the engine's Philox stream (option "seed"), the step-by-step path from ``torch.randn``.  Run over the
+        same timesteps, "euler" is ``ddim_sample_loop(eta=0, clip_denoised=False)``.  No hooks (``denoised_fn`` / ``cond_fn``)."""
+        final = None
+        for final in self._linear_loop(model, shape, noise, method, model_kwargs, device, progress, step_noise, False):
             pass
         return final["sample"]
 

@@ -121,10 +121,38 @@ class _LinearScheduler:
             raise ValueError("timesteps leave the trained range (steps_offset too large)")
         return ts
 
-    def set_timesteps(self, num_inference_steps, device=None):
-        ts = self._spaced(num_inference_steps)
+    def _own_timesteps(self, timesteps, alphas_cumprod_at):
+        """The checked (timesteps, abar at them) of ``set_timesteps(timesteps=..., alphas_cumprod_at=...)``."""
+        if timesteps is None or alphas_cumprod_at is None:
+            raise ValueError("timesteps= and alphas_cumprod_at= go together")
+        ts = np.asarray(timesteps)
+        ab = np.asarray(alphas_cumprod_at, dtype=np.float64)
+        if ts.ndim != 1 or ts.size < 1 or not np.all(ts == np.floor(ts)) or ts.min() < 0:
+            raise ValueError("timesteps must be a non-empty list of non-negative integers")
+        ts = ts.astype(np.int64)
+        if ab.shape != ts.shape:
+            raise ValueError(f"alphas_cumprod_at has {ab.size} entries for {ts.size} timesteps")
+        if np.any(np.diff(ts) >= 0):
+            raise ValueError("timesteps must be distinct and descending")
+        if not np.all(np.isfinite(ab)) or np.any(ab <= 0.0) or np.any(ab > 1.0):
+            raise ValueError("alphas_cumprod_at must lie in (0, 1]")
+        return ts, ab
+
+    def set_timesteps(self, num_inference_steps=None, device=None, *, timesteps=None, alphas_cumprod_at=None):
+        """``set_timesteps(n)``: n timesteps of the trained range by ``timestep_spacing``.  ``set_timesteps(timesteps=ts,
+        alphas_cumprod_at=ab)``: the chain on a caller's own timesteps -- descending distinct integers with abar AT them (a respaced
+        diffusion's ``timestep_map`` and ``alphas_cumprod``; the gaps need not be uniform, the scheduler's own beta table is not consulted);
+        it ends at abar = 1 behind the last one all the same."""
+        if timesteps is not None or alphas_cumprod_at is not None:
+            ts, abar = self._own_timesteps(timesteps, alphas_cumprod_at)
+            if num_inference_steps is not None and num_inference_steps != len(ts):
+                raise ValueError(f"num_inference_steps = {num_inference_steps} for {len(ts)} timesteps")
+            num_inference_steps = len(ts)
+        else:
+            ts = self._spaced(num_inference_steps)
+            abar = self.alphas_cumprod[ts]
         self.num_inference_steps = num_inference_steps
-        self._abar = np.append(self.alphas_cumprod[ts], 1.0)              # abar_0 .. abar_{n-1}, then 1 behind the last timestep
+        self._abar = np.append(abar, 1.0)                                 # abar_0 .. abar_{n-1}, then 1 behind the last timestep
         self._sigmas = np.sqrt((1.0 - self._abar) / self._abar)           # ... and sigma = 0 there
         self._step_index = 0
         self._build(ts)
@@ -155,12 +183,14 @@ class _LinearScheduler:
         s = float(self._rows[min(self._step_index, len(self._rows) - 1), P_IN])
         return sample if s == 1.0 else sample * s
 
-    def step(self, model_output, timestep, sample, generator=None, return_dict=True):
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True, noise=None):
         """One evaluation's update (``_update``: the class's published formula, host fp64 scalars as Python floats times the
-        tensors); advances the internal step index that ``set_timesteps`` resets."""
+        tensors); advances the internal step index that ``set_timesteps`` resets.  ``noise`` (not in diffusers): the draw of a
+        stochastic step, given by the caller in place of ``generator``."""
         self._need_chain()
         if self._step_index >= len(self._rows):
             raise IndexError("step called more often than the chain has evaluations; call set_timesteps to start a new chain")
+        self._given_noise = noise
         prev = self._update(self._step_index, model_output, sample, generator)
         self._step_index += 1
         return (prev,) if not return_dict else type("SchedulerOutput", (), {"prev_sample": prev})()
@@ -205,7 +235,7 @@ class EulerAncestralDiscreteScheduler(EulerDiscreteScheduler):
 
     def _update(self, i, eps, x, generator):
         up, down = self._up_down(i)
-        noise = draw_noise(eps.shape, generator, eps.device, eps.dtype)
+        noise = self._given_noise if self._given_noise is not None else draw_noise(eps.shape, generator, eps.device, eps.dtype)
         return x + (down - float(self._sigmas[i])) * eps + up * noise
 
 
@@ -323,8 +353,7 @@ class DDIMInverseScheduler(_LinearScheduler):
         up = [int(t) for t in ts[::-1]]                                    # ascending
         self._eval_timesteps = up
         rows, a_from = [], self.final_alpha_cumprod
-        for t in up:
-            a_to = float(self.alphas_cumprod[t])
+        for t, a_to in zip(up, self._abar[-2::-1].tolist()):               # abar at the set's timesteps, ascending too
             rows.append(self._row(t, c_x=(a_to / a_from) ** 0.5, c0=(1.0 - a_to) ** 0.5 - (a_to * (1.0 - a_from) / a_from) ** 0.5))
             a_from = a_to
         self._rows = np.array(rows)

@@ -67,6 +67,9 @@ def main(args, cli):
     if args.sample_method == "ddim":                                       # :100-107
         samples = diffusion.ddim_sample_loop(sample_fn, z.shape, z, clip_denoised=False, model_kwargs=model_kwargs,
                                              progress=True, device=device)
+    elif args.sample_method in latte_amd.LINEAR_METHODS:                   # euler | euler_a | heun | dpmsolver++ (not in the reference)
+        samples = diffusion.linear_sample_loop(sample_fn, z.shape, z, method=args.sample_method, model_kwargs=model_kwargs,
+                                               progress=True, device=device)
     else:
         samples = diffusion.p_sample_loop(sample_fn, z.shape, z, clip_denoised=False, model_kwargs=model_kwargs,
                                           progress=True, device=device)

@@ -101,8 +101,11 @@ def main():
         else:
             kw = dict(y=None)
             fn = model.forward
-        loop = diffusion.ddim_sample_loop if args.sample_method == "ddim" else diffusion.p_sample_loop
-        samples = loop(fn, z.shape, z, clip_denoised=False, model_kwargs=kw, progress=False, device=device)
+        if args.sample_method in latte_amd.LINEAR_METHODS:         # euler | euler_a | heun | dpmsolver++ (not in the reference)
+            samples = diffusion.linear_sample_loop(fn, z.shape, z, method=args.sample_method, model_kwargs=kw, device=device)
+        else:
+            loop = diffusion.ddim_sample_loop if args.sample_method == "ddim" else diffusion.p_sample_loop
+            samples = loop(fn, z.shape, z, clip_denoised=False, model_kwargs=kw, progress=False, device=device)
         if using_cfg:
             samples, _ = samples.chunk(2, dim=0)                   # sample_ddp.py:159-160
         if vae is not None:
