@@ -87,6 +87,10 @@ void latte_engine_destroy(latte_engine_t* e);
  * "gemm_variant_qkv" / "_proj" / "_fc1" / "_fc2" (the same, for one of the four GEMMs of the block only; tuning hook),
  * "gated_split_k" (small batches: 0 = the rule -- a gated GEMM with >= 64 K tiles whose tiles fill at most half of the
  * CUs, and which the 128x144 tile does not take, runs as 2..4 partial products + one reduction into the residual stream; 1 = never; 2..4 = force that many),
+ * "gated_rmw_shape" (how the rolling 12-wave kernel requests the fp32 residual of a gated GEMM: 0 = one 16 x 16 accumulator
+ * fragment, 16 rows x 64 B, per instruction; 1 = the default: the whole 128-byte line of a wave's span as 8 rows x 128 B; same bits),
+ * "fc2_temp_embed" (1 = the default: x + temp_embed of latte.py:357-358 is added by the first block's fc2 epilogue where fc2 runs on the
+ * rolling 12-wave kernel; 0 = by the second block's first LayerNorm pass, as for every other fc2 kernel; same bits),
  * "fuse_qkv_attn" (bit 0: spatial blocks, bit 1: temporal blocks run the QKV projection and the attention core of
  * latte.py:48-70 as ONE kernel with q / k / v held in LDS -- csrc/qkv_attn.hip -- wherever the shape allows it: 256 tokens per
  * frame / 16 frames, head_dim 64 | 72; default 3, 0 = the separate qkv GEMM + attention kernels; values 0..31: bits 2, 3, 4 switch

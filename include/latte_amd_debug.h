@@ -397,6 +397,8 @@ int latte_debug_dma_probe(const void* src, long long* out, int mode, int waves, 
  *                     same stages run three passes (hi*hi + lo*hi + hi*lo) instead of one (csrc/vae_engine.cpp: vae_split_mask); the SD-VAE
  *                     encoder reads the same layout (bit 0 mid block, 1 + i down block i, 12 + i / 21 + i the down-sampler of block i, 11
  *                     conv_out).  A decode / encode call reads the choice once, when it starts, and runs entirely on that mask
+ *   "gated_rmw_shape" latte_debug_gemm / _lo8 / _lo4 with epi 2 on the rolling 12-wave kernel: 1 = fragment-wise residual accesses (16 rows x 64 B
+ *                     per instruction), 2 = line-wise (8 rows x 128 B on the whole line of a wave's span): the engine option of the same name + 1
  * Anything else is refused (LATTE_ERR_INVALID).  Replaces the LATTE_* environment variables round 3 read at every launch; the
  * measurement ablations whose results are garbage (attention variants 7-10, 16-19) were removed; profiles/ keeps their logs. */
 int latte_debug_set_choice(const char* name, int value);

@@ -100,7 +100,8 @@ struct GemmArgs {
   int rows_per_sample;
   int stagger;        // persistent kernel: number of start cohorts (0/1 = none); cohort c sleeps c/stagger of a tile time
   int group_m;        // persistent kernel: tile rows walked together by the grouped tile order (0 = 8)
-  int rmw_mode;       // unused slot (read by the removed measurement build only): keeps the kernel-argument offsets
+  int rmw_mode;       // rolling 12-wave kernel, EPI_GATE_RES_F32: access shape of the residual read-modify-write, 0 = one 16 x 16 fragment
+                      // (16 rows x 64 B) per instruction, 1 = the whole line of a wave's span as 8 rows x 128 B (gemm_pw.hip); same bits
   int tag;            // call site of a gated-residual GEMM (0 = attention out-projection, 1 = fc2): separate kernel symbols
   int k_chunk;        // plain kernels (variants 1-3) only: > 0 splits the contraction, grid.y = ceil(K / k_chunk) partial products
   long split_stride;  // ... written to (float*)out + blockIdx.y * split_stride (use EPI_BIAS_F32 with a zero bias)
@@ -119,10 +120,17 @@ struct GemmArgs {
   const uint8_t* A4s;
   const uint8_t* W4s;
   half_t* aux;        // EPI_BIAS_GELU_DUAL_H16: second output [Mpad, N]; EPI_DGELU_H16: the pre-activation u [Mpad, N] (read only)
+  // EPI_GATE_RES_F32 on the rolling 12-wave kernel only (launch_gemm refuses it elsewhere): a second fp32 addend per element behind the
+  // gated update,  res = (res + gate * (acc + bias)) + te[(m / te_T) % te_F][n]  -- the temporal position embedding, which the first
+  // spatial block's fc2 adds while it holds every element of the residual stream in a register (latte.py:357-358).
+  const float* te;    // [te_F, N]
+  int te_T, te_F;
 };
 // constant block scales of the correction pass: A8 holds the rounding remainder of a half operand (|lo| <= 2^-11 |x|), W8 weights of
 // |w| < 7; the MFMA multiplies the products back by 2^-(LO8_A_SHIFT + LO8_W_SHIFT) (E8M0 scale bytes 127 - shift)
 constexpr int LO8_A_SHIFT = 12, LO8_W_SHIFT = 6;
+// GemmArgs::rmw_mode of the denoiser's gated GEMMs unless the engine option "gated_rmw_shape" says otherwise
+constexpr int GATED_RMW_SHAPE_DEFAULT = 1;
 inline int lo4_pitch(int K) { return (K + 255) / 256 * 128; }   // bytes per row of an fp4 correction operand
 bool gemm_lo8_ok(int M, int N, int K);   // the shape takes the fp8 correction pass (whole 192-wide tile columns, K % 128 == 0, 32-bit offsets)
 bool gemm_lo4_ok(int M, int N, int K);   // the shape takes the fp4 correction pass (whole 192-wide tile columns, K % 64 == 0, 32-bit offsets)
@@ -227,7 +235,7 @@ int launch_fill_f32(float* p, float v, size_t n, hipStream_t st);
 // Kernel-choice overrides of the A/B tests (latte_debug_set_choice, include/latte_amd_debug.h; engine.cpp).  Process-global, 0 = the
 // library's own choice.  Every value selects another implementation of the SAME function; nothing here can change a result beyond
 // rounding.  (Round 3 read environment variables at every launch instead, among them ablations with garbage results.)
-enum DebugChoice { DBG_ATTN_VARIANT = 0, DBG_XATTN_FLASH, DBG_TN_KERNEL, DBG_TN_WN, DBG_ATTN_BWD_TILES, DBG_CONV_KERNEL, DBG_VAE_SPLIT, DBG_NUM_CHOICES };
+enum DebugChoice { DBG_ATTN_VARIANT = 0, DBG_XATTN_FLASH, DBG_TN_KERNEL, DBG_TN_WN, DBG_ATTN_BWD_TILES, DBG_CONV_KERNEL, DBG_VAE_SPLIT, DBG_GATED_RMW_SHAPE, DBG_NUM_CHOICES };
 int debug_choice(DebugChoice c);
 int set_debug_choice(const char* name, int value);   // 0 = ok, -1 = unknown name / value not offered by this build
 

@@ -145,6 +145,9 @@ int latte_debug_gemm(const void* A, const void* W, const float* bias, void* out,
   g.M = M; g.N = N; g.K = K; g.gate_stride = gate_stride; g.rows_per_sample = rows_per_sample;
   if (epi == EPI_BIAS_RES_H16) g.res = (const half_t*)gate;   // epi 5: `gate` carries the half residual [Mpad, N]
   if (variant >= 1000) { g.tag = variant / 1000; variant %= 1000; }   // + 1000 * call-site tag (GemmArgs::tag)
+  // latte_debug_set_choice("gated_rmw_shape", 1 | 2): the fragment-wise | line-wise residual accesses of the rolling kernel's gated epilogue
+  const int shape = debug_choice(DBG_GATED_RMW_SHAPE);
+  g.rmw_mode = shape ? shape - 1 : GATED_RMW_SHAPE_DEFAULT;
   return launch_gemm(g, epi, dtype, variant, (hipStream_t)stream);
 }
 
@@ -164,6 +167,8 @@ int latte_debug_gemm_lo8(const void* A, const void* W, const void* A8, const voi
   g.A = (const half_t*)A; g.W = (const half_t*)W; g.bias = bias; g.out = out; g.gate = gate;
   g.M = M; g.N = N; g.K = K; g.gate_stride = gate_stride; g.rows_per_sample = rows_per_sample;
   g.A8 = (const uint8_t*)A8; g.W8 = (const uint8_t*)W8;
+  const int shape = debug_choice(DBG_GATED_RMW_SHAPE);
+  g.rmw_mode = shape ? shape - 1 : GATED_RMW_SHAPE_DEFAULT;
   return launch_gemm(g, epi, dtype, 0, (hipStream_t)stream);
 }
 
@@ -175,6 +180,8 @@ int latte_debug_gemm_lo4(const void* A, const void* W, const void* A4, const voi
   g.A = (const half_t*)A; g.W = (const half_t*)W; g.bias = bias; g.out = out; g.gate = gate;
   g.M = M; g.N = N; g.K = K; g.gate_stride = gate_stride; g.rows_per_sample = rows_per_sample;
   g.A4 = (const uint8_t*)A4; g.A4s = (const uint8_t*)A4s; g.W4 = (const uint8_t*)W4; g.W4s = (const uint8_t*)W4s;
+  const int shape = debug_choice(DBG_GATED_RMW_SHAPE);
+  g.rmw_mode = shape ? shape - 1 : GATED_RMW_SHAPE_DEFAULT;
   return launch_gemm(g, epi, dtype, 0, (hipStream_t)stream);
 }
 

@@ -25,8 +25,8 @@ static thread_local std::string g_last_error;
 static std::atomic<int> g_debug_choice[DBG_NUM_CHOICES];
 int debug_choice(DebugChoice c) { return g_debug_choice[c].load(std::memory_order_relaxed); }
 int set_debug_choice(const char* name, int value) {
-  static const char* const names[DBG_NUM_CHOICES] = {"attn_variant", "xattn_flash", "tn_kernel", "tn_wn", "attn_bwd_tiles", "conv_kernel", "vae_split"};
-  static const int allowed[DBG_NUM_CHOICES][4] = {{1, 5, 12, 13}, {1, 0, 0, 0}, {4, 0, 0, 0}, {4, 0, 0, 0}, {1, 2, 0, 0}, {1, 2, 3, 4}, {0, 0, 0, 0}};
+  static const char* const names[DBG_NUM_CHOICES] = {"attn_variant", "xattn_flash", "tn_kernel", "tn_wn", "attn_bwd_tiles", "conv_kernel", "vae_split", "gated_rmw_shape"};
+  static const int allowed[DBG_NUM_CHOICES][4] = {{1, 5, 12, 13}, {1, 0, 0, 0}, {4, 0, 0, 0}, {4, 0, 0, 0}, {1, 2, 0, 0}, {1, 2, 3, 4}, {0, 0, 0, 0}, {1, 2, 0, 0}};
   for (int i = 0; i < DBG_NUM_CHOICES; ++i) {
     if (name && std::string(name) == names[i]) {
       bool ok = value == 0;
@@ -71,6 +71,9 @@ struct latte_engine {
                                            // (qkv_attn.hip) wherever the shape allows it (T == 256 / F == 16); 0 = the un-fused pair;
                                            // bits 2, 3: QkvAttnArgs::flags (schedule variants, same results)
   int gated_split_k = 0;                   // gated GEMMs of small batches: 0 = rule of gated_gemm, 1 = never split, 2..4 = force
+  int gated_rmw_shape = GATED_RMW_SHAPE_DEFAULT;   // GemmArgs::rmw_mode of the out-projection and fc2: 0 = fragment-wise, 1 = line-wise residual accesses
+  int fc2_temp_embed = 1;                  // the first block's fc2 adds temp_embed in its epilogue where its kernel can (GemmArgs::te); 0 = the
+                                           // second block's first LayerNorm pass adds it (an extra write of the residual stream); same bits
   // Guided calls (forward_with_cfg, latte.py:379-398): eps_u + s (eps_c - eps_u) amplifies the part of the operand rounding that differs
   // between the two halves (s = 7: 7 c - 6 u).  At trained-scale gates the f16 forward of XL/2 then sits AT north_star's 1e-3 (0.6 - 1.2e-3
   // over gate_std x timestep x seed, two of twelve draws above: profiles/r5_gate_parity_guided.json); the per-rounding-point attribution
@@ -161,6 +164,11 @@ int gated_split_choice(const latte_engine* e, int M, int N, int K, int variant) 
   for (int s = 4; s >= 2; --s)
     if (tiles * s <= 256 && nk % s == 0 && nk / s >= 32 && (int64_t)s * M * N <= SPLIT_WS_FLOATS) return s;
   return 1;
+}
+// the gated GEMM of this shape runs on the rolling 12-wave kernel, whose epilogue can add the temporal embedding (GemmArgs::te)
+bool gated_gemm_takes_te(const latte_engine* e, int M, int N, int K, int variant) {
+  if (gated_split_choice(e, M, N, K, variant) != 1) return false;
+  return (variant ? variant : gemm_resolve_variant(M, N, K, EPI_GATE_RES_F32)) == 11;
 }
 int gated_gemm(latte_engine* e, const GemmArgs& g, int dt, int variant, hipStream_t st) {
   if (g.A8) return launch_gemm(g, EPI_GATE_RES_F32, dt, 0, st);   // fp8 correction pass: the rolling 12-wave kernel carries it
@@ -290,12 +298,15 @@ int run_forward(latte_engine* e, const float* x, const int64_t* t, const int64_t
     const BlockW& w = e->blocks[i];
     const float* mb = modp + (size_t)i * 6 * D;  // chunk(6): shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
     bool split_proj = false;   // this block's attention output leaves the fused kernel as a split pair
-    // x + temp_embed once, after the first spatial block (latte.py:357-358)
-    const float* te = (i == 1) ? e->temp : nullptr;
+    // x + temp_embed once, after the first spatial block (latte.py:357-358): in that block's fc2 epilogue where fc2 runs on the
+    // rolling 12-wave kernel (every element of x is in a register there), else in this LayerNorm pass, which then rewrites x
+    const int fc2_variant = e->gemm_variant_of[3] ? e->gemm_variant_of[3] : e->gemm_variant;
+    const bool te_in_fc2 = e->fc2_temp_embed && c.depth > 1 && gated_gemm_takes_te(e, M, D, e->Hm, fc2_variant);
+    const float* te = (i == 1 && !te_in_fc2) ? e->temp : nullptr;
     if ((rc = launch_ln_modulate(e->xres, e->xres, e->xn, mb, mb + D, mstride, M, D, rps, te, T, F, dt, st))) return rc;
     tm.mark(C_LN);
     GemmArgs g{};
-    g.M = M; g.rows_per_sample = rps; g.gate_stride = mstride;
+    g.M = M; g.rows_per_sample = rps; g.gate_stride = mstride; g.rmw_mode = e->gated_rmw_shape;
     const half_t* attn_out = e->xn;
     if (((e->fuse_qkv_attn >> (spatial ? 0 : 1)) & 1) && qkv_attention_fusable(D, c.num_heads, e->hd, F, T, spatial ? 0 : 1, M)) {
       // qkv projection + attention core in one kernel (q / k / v of a head only in LDS); the output goes to the (otherwise idle)
@@ -348,8 +359,8 @@ int run_forward(latte_engine* e, const float* x, const int64_t* t, const int64_t
     g.A8 = nullptr; g.W8 = nullptr; g.A4 = nullptr; g.A4s = nullptr; g.W4 = nullptr; g.W4s = nullptr;
     tm.mark(C_FC1);
     g.A = e->hbuf; g.W = w.fc2_w; g.bias = w.fc2_b; g.out = e->xres; g.gate = mb + 5 * D; g.N = D; g.K = e->Hm; g.tag = 1;
-
-    if ((rc = gated_gemm(e, g, dt, e->gemm_variant_of[3] ? e->gemm_variant_of[3] : e->gemm_variant, st))) return rc;
+    if (i == 0 && te_in_fc2) { g.te = e->temp; g.te_T = T; g.te_F = F; }
+    if ((rc = gated_gemm(e, g, dt, fc2_variant, st))) return rc;
     tm.mark(C_FC2);
   }
   // --- final layer (latte.py:197-201) + unpatchify (:297-310)
@@ -655,6 +666,16 @@ int latte_engine_set_option(latte_engine_t* e, const char* name, int64_t value) 
     e->gated_split_k = (int)value;
     return LATTE_OK;
   }
+  if (k == "gated_rmw_shape") {
+    if (value < 0 || value > 1) return fail(LATTE_ERR_INVALID, "gated_rmw_shape: 0 (fragment-wise) or 1 (line-wise residual accesses of the gated GEMMs)");
+    e->gated_rmw_shape = (int)value;
+    return LATTE_OK;
+  }
+  if (k == "fc2_temp_embed") {
+    if (value < 0 || value > 1) return fail(LATTE_ERR_INVALID, "fc2_temp_embed: 0 (LayerNorm pass adds temp_embed) or 1 (the first block's fc2 epilogue does)");
+    e->fc2_temp_embed = (int)value;
+    return LATTE_OK;
+  }
   if (k == "fuse_qkv_attn") {
     if (value < 0 || value > 31)
       return fail(LATTE_ERR_INVALID, "fuse_qkv_attn: bit 0 = spatial blocks, bit 1 = temporal blocks, bits 2-4 = schedule features off (0..31)");
@@ -689,6 +710,8 @@ int latte_engine_get_option(const latte_engine_t* e, const char* name, int64_t* 
   else if (k == "gemm_variant_fc1") *value = e->gemm_variant_of[2];
   else if (k == "gemm_variant_fc2") *value = e->gemm_variant_of[3];
   else if (k == "gated_split_k") *value = e->gated_split_k;
+  else if (k == "gated_rmw_shape") *value = e->gated_rmw_shape;
+  else if (k == "fc2_temp_embed") *value = e->fc2_temp_embed;
   else if (k == "fuse_qkv_attn") *value = e->fuse_qkv_attn;
   else if (k == "guided_split") *value = e->guided_split;
   else if (k == "guided_split_active") *value = e->guided_split_active;

@@ -1005,6 +1005,8 @@ int launch_gemm(const GemmArgs& a_in, int epi, int dtype, int variant, hipStream
     return launch_gemm_pw(a, epi, dtype, 1, st);
   }
   if (variant == 0) variant = gemm_resolve_variant(a.M, a.N, a.K, epi);
+  if (a.te && !(variant == 11 && epi == EPI_GATE_RES_F32))   // a missing form is an error, never a dropped addend
+    return fail(LATTE_ERR_INVALID, "gemm: GemmArgs::te exists in the rolling 12-wave kernel's gated epilogue only (variant 11)");
   if (variant == 10 || variant == 11) return launch_gemm_pw(a, epi, dtype, variant == 11, st);
   const int bn = gemm_tile_n(variant);
   const int nq = variant >= 7 && variant <= 9 ? bn / 4 : bn;   // persistent kernels: partial last tile column in whole wave widths

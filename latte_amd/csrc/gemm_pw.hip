@@ -66,6 +66,14 @@ __device__ __forceinline__ void mfma8_ip(f32x4& c, const u32x8& a, const u32x8& 
   asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]" : "+v"(c) : "v"(a), "v"(b), "v"(sa), "v"(sb));
 }
 
+// `src` of lane l ^ 8 for the lanes of the 4-lane banks in BANKS (bit b = lanes 4 b ... 4 b + 3 of every row of 16), `old` elsewhere:
+// a DPP rotation by 8 inside each row of 16 lanes.  (Written per scalar: with the element of a vector as the builtin's operand
+// the compiler kept one exchange of four.)
+template <int BANKS>
+__device__ __forceinline__ float ror8(float old, float src) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), 0x128, 0xf, BANKS, false));
+}
+
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 template <int EPI, int DT, int TAG>
@@ -332,7 +340,9 @@ __global__ void __launch_bounds__(768) gemm_pw_kernel(GemmArgs g) {
 // fp8 correction operands A8 / W8 (GemmArgs) -- a 128-byte row piece of an fp8 operand is K = 128, so a correction K tile has the
 // byte geometry, the LDS image, the swizzle and the DMA pieces of a half-precision one; the producers only switch descriptor and row
 // pitch, the consumers run lo_tile() (24 MFMAs of 16 passes on the same fragment reads) instead of ktile() (48 of 8 passes).
-template <int EPI, int DT, int TAG, int LO = 0>
+// RS: access shape of the gated epilogue's residual traffic (GemmArgs::rmw_mode): 0 = one 16 x 16 fragment per instruction,
+// 1 = the whole 128-byte line of the wave's span in 8-row instructions (see the epilogue).  TAG = 2: fc2 + temporal embedding.
+template <int EPI, int DT, int TAG, int LO = 0, int RS = 0>
 __global__ void __launch_bounds__(768) gemm_pwr_kernel(GemmArgs g) {
   constexpr int BM = 256, BN = 192, FN = 3, WTN = 48;
   constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128;
@@ -543,7 +553,75 @@ __global__ void __launch_bounds__(768) gemm_pwr_kernel(GemmArgs g) {
       }
       return;
     }
-    if constexpr (EPI == EPI_GATE_RES_F32) {
+    // TAG == 2: the temporal position embedding of row m's frame (GemmArgs::te), added BEHIND the gated update -- the two
+    // fp32 operations of the former pair [this epilogue | x + temp_embed inside the next LayerNorm pass], in that order
+    auto te_ptr = [&](int m_clamped, int n) -> const float* {
+      return g.te + (size_t)((m_clamped / g.te_T) % g.te_F) * g.N + n;
+    };
+    // (TAG = 2 exists fragment-wise only: with the embedding's addresses the line-wise form spilled 24 B per lane; it is one launch per forward.)
+    static_assert(!(TAG == 2 && RS == 1), "the temporal-embedding epilogue has the fragment-wise form only");
+    if constexpr (EPI == EPI_GATE_RES_F32 && RS == 1) {
+      // Line-wise residual accesses (GemmArgs::rmw_mode = 1; tools/rmw_shape_probe.hip, profiles/r7_rmw_shape_probe.log).  A wave's
+      // 48 columns are 192 B of a row = one whole 128-byte line + half of a line shared with the neighbouring wave (the half comes
+      // first in the odd waves).  The two fragments that make up the whole line swap halves between lanes l and l ^ 8 (one DPP
+      // row rotation by 8 per register), after which lane (fr, gq) holds columns 16 (fr >> 3) + 4 gq ... + 3 of the line for the
+      // rows (fr & 7) and 8 + (fr & 7) of the fragment row: two instructions of 8 rows x 128 B instead of two of 16 rows x 64 B.
+      // The third fragment keeps the fragment-wise access.  Only acc + bias travels: every element is still
+      // fma(gate, acc + bias, res) in fp32, so the bits are those of the fragment-wise form.
+      if ((g.rows_per_sample % BM) == 0) {
+        float* const outp = (float*)g.out;
+        const bool odd = wn & 1;
+        const int gq = le >> 4;
+        const int n0 = tn_ * BN + wn * WTN;
+        const int nline = n0 + (odd ? 16 : 0) + ((fr >> 3) * 4 + gq) * 4;
+        const int nhalf = n0 + (odd ? 0 : 32) + gq * 4;
+        const int mline = tm_ * BM + grp * 128 + (fr & 7);
+        const float* gs = g.gate + (size_t)((tm_ * BM) / g.rows_per_sample) * g.gate_stride;
+        const float4 gl = *(const float4*)(gs + nline), gh = *(const float4*)(gs + nhalf);
+        float4 b4[FN];
+#pragma unroll
+        for (int j = 0; j < FN; ++j) b4[j] = *(const float4*)(g.bias + ncol + j * 16);
+        constexpr int NQ = 8 * 3, AHEAD = 2;   // access q: fragment row q / 3; q % 3 = rows 0-7 | rows 8-15 of the line, the half line
+        auto row_of = [&](int q) -> int { return (q % 3 == 2 ? mbase : mline + (q % 3) * 8) + (q / 3) * 16; };
+        auto col_of = [&](int q) -> int { return q % 3 == 2 ? nhalf : nline; };
+        float4 qa[AHEAD];
+        auto load = [&](int q) {
+          const int mc = min(row_of(q), g.M - 1);
+          qa[q % AHEAD] = *(const float4*)(outp + (size_t)mc * g.N + col_of(q));
+        };
+#pragma unroll
+        for (int a = 0; a < AHEAD; ++a) load(a);
+        f32x4 t[3];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+          float4 rr = qa[q % AHEAD];
+          if (q + AHEAD < NQ) load(q + AHEAD);
+          asm volatile("" ::: "memory");
+          const int i = q / 3, k = q % 3;
+          if (k == 0) {
+            f32x4 s[FN];
+#pragma unroll
+            for (int j = 0; j < FN; ++j) {
+              s[j] = (f32x4){acc[i][j][0] + b4[j].x, acc[i][j][1] + b4[j].y, acc[i][j][2] + b4[j].z, acc[i][j][3] + b4[j].w};
+              acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
+            const f32x4 l0 = odd ? s[1] : s[0], l1 = odd ? s[2] : s[1];
+            t[2] = odd ? s[0] : s[2];
+            // lanes 8-15 of every 16 take the line's second fragment of lane - 8, lanes 0-7 its first fragment of lane + 8
+            t[0] = (f32x4){ror8<0xC>(l0[0], l1[0]), ror8<0xC>(l0[1], l1[1]), ror8<0xC>(l0[2], l1[2]), ror8<0xC>(l0[3], l1[3])};
+            t[1] = (f32x4){ror8<0x3>(l1[0], l0[0]), ror8<0x3>(l1[1], l0[1]), ror8<0x3>(l1[2], l0[2]), ror8<0x3>(l1[3], l0[3])};
+          }
+          const float4 gg = k == 2 ? gh : gl;
+          rr.x = __builtin_fmaf(gg.x, t[k][0], rr.x);
+          rr.y = __builtin_fmaf(gg.y, t[k][1], rr.y);
+          rr.z = __builtin_fmaf(gg.z, t[k][2], rr.z);
+          rr.w = __builtin_fmaf(gg.w, t[k][3], rr.w);
+          if (row_of(q) < g.M) *(float4*)(outp + (size_t)row_of(q) * g.N + col_of(q)) = rr;
+        }
+        return;
+      }
+    }
+    if constexpr (EPI == EPI_GATE_RES_F32 && RS == 0) {
       if ((g.rows_per_sample % BM) == 0) {
         float* const outp = (float*)g.out;
         const float* gr = g.gate + (size_t)((tm_ * BM) / g.rows_per_sample) * g.gate_stride + ncol;
@@ -558,19 +636,25 @@ __global__ void __launch_bounds__(768) gemm_pwr_kernel(GemmArgs g) {
           const int mc = min(mbase + (f / FN) * 16, g.M - 1);
           return outp + (size_t)mc * g.N + ncol + (f % FN) * 16;
         };
-        float4 qa[AHEAD];
+        float4 qa[AHEAD], qe[AHEAD];
+        auto load_te = [&](int f) {
+          if constexpr (TAG == 2) qe[f % AHEAD] = *(const float4*)te_ptr(min(mbase + (f / FN) * 16, g.M - 1), ncol + (f % FN) * 16);
+        };
 #pragma unroll
-        for (int a = 0; a < AHEAD; ++a) qa[a] = *(const float4*)frag_ptr(a);
+        for (int a = 0; a < AHEAD; ++a) { qa[a] = *(const float4*)frag_ptr(a); load_te(a); }
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
           float4 rr = qa[f % AHEAD];
-          if (f + AHEAD < NF) qa[f % AHEAD] = *(const float4*)frag_ptr(f + AHEAD);
+          float4 e4 = make_float4(0.f, 0.f, 0.f, 0.f);
+          if constexpr (TAG == 2) e4 = qe[f % AHEAD];
+          if (f + AHEAD < NF) { qa[f % AHEAD] = *(const float4*)frag_ptr(f + AHEAD); load_te(f + AHEAD); }
           asm volatile("" ::: "memory");
           const int i = f / FN, j = f % FN;
           rr.x += g1[j].x * (acc[i][j][0] + b4[j].x);
           rr.y += g1[j].y * (acc[i][j][1] + b4[j].y);
           rr.z += g1[j].z * (acc[i][j][2] + b4[j].z);
           rr.w += g1[j].w * (acc[i][j][3] + b4[j].w);
+          if constexpr (TAG == 2) { rr.x += e4.x; rr.y += e4.y; rr.z += e4.z; rr.w += e4.w; }
           if (mbase + i * 16 < g.M) *(float4*)(outp + (size_t)(mbase + i * 16) * g.N + ncol + j * 16) = rr;
           acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
@@ -592,6 +676,10 @@ __global__ void __launch_bounds__(768) gemm_pwr_kernel(GemmArgs g) {
             float4* dst = (float4*)((float*)g.out + o);
             float4 rr = *dst;
             rr.x += g4.x * v0; rr.y += g4.y * v1; rr.z += g4.z * v2; rr.w += g4.w * v3;
+            if constexpr (TAG == 2) {
+              const float4 e4 = *(const float4*)te_ptr(m, n);
+              rr.x += e4.x; rr.y += e4.y; rr.z += e4.z; rr.w += e4.w;
+            }
             *dst = rr;
           } else if constexpr (EPI == EPI_BIAS_F32) {
             *(float4*)((float*)g.out + o) = make_float4(v0, v1, v2, v3);
@@ -879,9 +967,20 @@ __global__ void __launch_bounds__(768) gemm_pwr_kernel(GemmArgs g) {
 // ------------------------------------------------------------------------------------------------
 
 // roll != 0: the rolling schedule (variant 11), else the two-segment one (variant 10)
+// the rolling kernel's gated-residual instantiations: residual access shape (GemmArgs::rmw_mode) x call site / correction pass
+template <int DT, int TAG, int LO>
+int launch_pwr_gated(const GemmArgs& a, dim3 grid, dim3 block, int lds, hipStream_t st) {
+  if (a.rmw_mode) return launch_lds<gemm_pwr_kernel<EPI_GATE_RES_F32, DT, TAG, LO, 1>>(grid, block, lds, st, a);
+  return launch_lds<gemm_pwr_kernel<EPI_GATE_RES_F32, DT, TAG, LO, 0>>(grid, block, lds, st, a);
+}
+
 template <int EPI, int DT, int TAG>
 int launch_pw_roll(const GemmArgs& a, int roll, dim3 grid, dim3 block, int lds, hipStream_t st) {
-  if (roll) return launch_lds<gemm_pwr_kernel<EPI, DT, TAG>>(grid, block, lds, st, a);
+  if constexpr (EPI == EPI_GATE_RES_F32) {
+    if (roll) return launch_pwr_gated<DT, TAG, 0>(a, grid, block, lds, st);
+  } else {
+    if (roll) return launch_lds<gemm_pwr_kernel<EPI, DT, TAG>>(grid, block, lds, st, a);
+  }
   return launch_lds<gemm_pw_kernel<EPI, DT, TAG>>(grid, block, lds, st, a);
 }
 
@@ -891,14 +990,14 @@ int launch_pw_dt(const GemmArgs& a, int epi, int roll, hipStream_t st) {
   const int tiles = ((a.M + 255) / 256) * (a.N / 192);
   const int nblk = tiles >= 256 ? 256 : (tiles + 7) / 8 * 8;
   dim3 grid(nblk), block(768);
+  if ((a.A4 || a.A8) && a.te) return fail(LATTE_ERR_INVALID, "gemm: GemmArgs::te has no correction-pass form");
   if (a.A4) {   // fp4 correction pass (GemmArgs::A4 / W4 + row scales): the rolling kernel's LO = 2 instantiations
     if (!roll || !a.W4 || !a.A4s || !a.W4s || !(epi == EPI_GATE_RES_F32 || epi == EPI_BIAS_GELU_H16) || DT != LATTE_DTYPE_F16)
       return fail(LATTE_ERR_INVALID, "gemm: the fp4 correction pass needs the rolling kernel, f16 operands, both code images with their row scales, and the gated / GELU epilogue");
     if constexpr (DT == LATTE_DTYPE_F16) {
       const bool half_tail = (a.K & 255) != 0 && (a.K & 255) <= 128;   // the last code tile ends inside its first half: LO = 3
       if (epi == EPI_GATE_RES_F32)
-        return half_tail ? launch_lds<gemm_pwr_kernel<EPI_GATE_RES_F32, DT, 0, 3>>(grid, block, LDS, st, a)
-                         : launch_lds<gemm_pwr_kernel<EPI_GATE_RES_F32, DT, 0, 2>>(grid, block, LDS, st, a);
+        return half_tail ? launch_pwr_gated<DT, 0, 3>(a, grid, block, LDS, st) : launch_pwr_gated<DT, 0, 2>(a, grid, block, LDS, st);
       return half_tail ? launch_lds<gemm_pwr_kernel<EPI_BIAS_GELU_H16, DT, 0, 3>>(grid, block, LDS, st, a)
                        : launch_lds<gemm_pwr_kernel<EPI_BIAS_GELU_H16, DT, 0, 2>>(grid, block, LDS, st, a);
     }
@@ -908,13 +1007,17 @@ int launch_pw_dt(const GemmArgs& a, int epi, int roll, hipStream_t st) {
     if (!roll || !a.W8 || a.K % 128 != 0 || !(epi == EPI_GATE_RES_F32 || epi == EPI_BIAS_GELU_H16) || DT != LATTE_DTYPE_F16)
       return fail(LATTE_ERR_INVALID, "gemm (correction pass): rolling kernel, f16 operands, K % 128 == 0, gated-residual or GELU epilogue only");
     if constexpr (DT == LATTE_DTYPE_F16) {
-      if (epi == EPI_GATE_RES_F32) return launch_lds<gemm_pwr_kernel<EPI_GATE_RES_F32, DT, 0, 1>>(grid, block, LDS, st, a);
+      if (epi == EPI_GATE_RES_F32) return launch_pwr_gated<DT, 0, 1>(a, grid, block, LDS, st);
       return launch_lds<gemm_pwr_kernel<EPI_BIAS_GELU_H16, DT, 0, 1>>(grid, block, LDS, st, a);
     }
     return LATTE_OK;   // (not reached: bf16 was refused above)
   }
   switch (epi) {
     case EPI_GATE_RES_F32:
+      if (a.te) {   // fc2 + temporal embedding (GemmArgs::te): the rolling kernel's TAG = 2 instantiations
+        if (!roll || a.te_T <= 0 || a.te_F <= 0) return fail(LATTE_ERR_INVALID, "gemm (producer-wave kernel): GemmArgs::te needs the rolling kernel and te_T, te_F > 0");
+        return launch_lds<gemm_pwr_kernel<EPI_GATE_RES_F32, DT, 2, 0, 0>>(grid, block, LDS, st, a);
+      }
       if (a.tag == 1) return launch_pw_roll<EPI_GATE_RES_F32, DT, 1>(a, roll, grid, block, LDS, st);
       return launch_pw_roll<EPI_GATE_RES_F32, DT, 0>(a, roll, grid, block, LDS, st);
     case EPI_BIAS_F32: return launch_pw_roll<EPI_BIAS_F32, DT, 0>(a, roll, grid, block, LDS, st);
