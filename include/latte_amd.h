@@ -241,7 +241,7 @@ int latte_invert_loop(latte_engine_t* e, const latte_schedule_t* s, int clip_den
  * LATTE_ERR_STATE for batch > max_batch and for a text-embedding model without latte_engine_set_text_embedding of `batch` rows.  Every
  * check runs before the first launch: x is untouched when one fails.  The ring of remembered outputs and the scaled model input are
  * taken from the engine's arena by the first call only.  Stream-ordered; the plan is consumed before the call returns. */
-#define LATTE_PLAN_COLS 12   /* same columns as LATTE_T2V_PLAN_COLS */
+#define LATTE_PLAN_COLS 12   /* the columns above; their one C++ definition and every check of the table: csrc/plan.h (PlanCol, plan_check) */
 #define LATTE_PLAN_MAX_EVALS 4096
 int latte_sample_plan_loop(latte_engine_t* e, int guided, float cfg_scale, float* x, const int64_t* y, int batch, int n_evals,
                            const double* plan, const float* noise, float* trail_sample, void* stream);
@@ -548,8 +548,8 @@ int latte_t2v_guided_ddim_loop(latte_t2v_t* e, float* x, int samples, int n_step
  * noise: DEVICE [n_evals][samples * C * F * H * W] fp32 (only the rows with c_noise != 0 are read), or NULL when no row has one.
  * Preconditions as latte_t2v_guided_ddim_loop; LATTE_ERR_INVALID also for a non-finite entry, a non-integral or negative timestep,
  * c_noise != 0 without noise, and a c_j (j >= 1) that is non-zero before j rows with push have run.  Nothing is launched when a
- * check fails. */
-#define LATTE_T2V_PLAN_COLS 12
+ * check fails.  The table is the one of latte_sample_plan_loop (csrc/plan.h: PlanCol). */
+#define LATTE_T2V_PLAN_COLS LATTE_PLAN_COLS
 int latte_t2v_guided_linear_loop(latte_t2v_t* e, float* x, int samples, int n_evals, const double* plan, const float* noise,
                                  float guidance_scale, int enable_temporal_attentions, void* stream);
 

@@ -99,7 +99,11 @@ int latte_debug_adaln_single(const float* tables, const float* head_table, const
                              int D, void* stream);
 int latte_debug_cond_rows(const float* temb, const float* ytab, const int64_t* y, float* out, int n_steps, int bu, int D, void* stream);
 int latte_debug_mask_bias(const float* mask, float* bias, int64_t n, void* stream);
-/* One launch of the guided linear sampler step (csrc/pointwise.hip: t2v_guided_linear_step_kernel) as latte_t2v_guided_linear_loop
+/* The table checks of latte_sample_plan_loop and latte_t2v_guided_linear_loop (csrc/plan.h: plan_check) on a HOST plan
+ * [n_evals][LATTE_PLAN_COLS], nothing else: no engine, no GPU.  t_limit: timesteps must be below it, 0 = no bound (text-to-video);
+ * a row with c_noise != 0 is refused unless noise_given or may_draw_noise.  LATTE_OK or LATTE_ERR_INVALID with latte_last_error(). */
+int latte_debug_plan_check(const double* plan, int n_evals, int max_evals, int64_t t_limit, int noise_given, int may_draw_noise);
+/* One launch of the guided linear sampler step (csrc/pointwise.hip: linear_step_kernel<T2VRows, V>) as latte_t2v_guided_linear_loop
  * makes it: x [b, C, F, hw] in place, model_out the guidance pair's output in frame layout [(2 b) F, Cout, hw] ([negative | prompt],
  * Cout >= C, only the first C channels are read),
  *   eps = un + scale (tx - un);  m0 = m_x x + m_eps eps;  x' = c_x x + c0 m0 + c1 h1 + c2 h2 + c3 h3 + c_noise noise;
@@ -110,7 +114,7 @@ int latte_debug_t2v_linear_step(float* x, float* x_in, const float* model_out, c
                                 const float* noise, float* hist_write, int b, int C, int Cout, int F, int hw, float scale, float m_x,
                                 float m_eps, float c_x, float c0, float c1, float c2, float c3, float c_noise, float in_scale_next,
                                 int push, void* stream);
-/* One launch of the step kernel of latte_sample_plan_loop (csrc/pointwise.hip: linear_step_kernel): the formula above on the
+/* One launch of the step kernel of latte_sample_plan_loop (csrc/pointwise.hip: linear_step_kernel<ClassGuidedRows | ClassPlainRows, 4>): the formula above on the
  * class-conditional / unconditional engine's layout -- x [B, F, C, hw] in place, model_out [B, F, Cout, hw] with Cout = C or 2 C (only the
  * first C channels are read).  guided != 0: B is the doubled batch of forward_with_cfg and eps of rows b and b + B / 2 is
  * uncond + scale (cond - uncond), cond = row b of model_out's first half, uncond = the same row of its second half; every one of the B

@@ -43,7 +43,7 @@ class VideoPlan(ctypes.Structure):
                                      "reg_y", "reg_x", "reg_h", "reg_w")] + [("scale_h", c_f32), ("scale_w", c_f32)]
 
 
-T2V_PLAN_COLS = 12   # LATTE_T2V_PLAN_COLS of include/latte_amd.h
+T2V_PLAN_COLS = 12   # LATTE_T2V_PLAN_COLS of include/latte_amd.h (= LATTE_PLAN_COLS)
 PLAN_COLS = 12       # LATTE_PLAN_COLS
 DTYPES = {"bf16": 0, "bfloat16": 0, "f16": 1, "fp16": 1, "float16": 1}
 
@@ -189,6 +189,7 @@ PROTOTYPES = {
     "latte_debug_adaln_single": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_void]),
     "latte_debug_cond_rows": (c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_void]),
     "latte_debug_mask_bias": (c_int, [c_void, c_void, c_i64, c_void]),
+    "latte_debug_plan_check": (c_int, [c_void, c_int, c_int, c_i64, c_int, c_int]),
     "latte_debug_t2v_linear_step": (c_int, [c_void] * 8 + [c_int] * 5 + [c_f32] * 10 + [c_int, c_void]),
     "latte_debug_linear_step": (c_int, [c_void] * 8 + [c_int] * 6 + [c_f32] * 10 + [c_int, c_void]),
     "latte_debug_qkv_attention": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

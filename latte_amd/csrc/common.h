@@ -252,12 +252,12 @@ int launch_t2v_guided_ddim(float* x, const float* model_out, int b, int C, int C
 //   x = x';  x_in = in_scale_next x' (the next denoiser call's input; nothing written when x_in == x);  push: hw = m0
 // A history / noise pointer whose coefficient is 0 is never dereferenced (may be NULL); hw may be one of h1..h3 (every thread reads
 // its elements before it writes them).  HW % 4 == 0 with 16-byte aligned buffers: 16-byte accesses, else the scalar kernel.
-struct T2VLinearStep {
+struct LinearStep {
   float scale, m_x, m_eps, c_x, c0, c1, c2, c3, c_noise, in_scale_next;
   int push;
 };
 int launch_t2v_guided_linear_step(float* x, float* x_in, const float* model_out, const float* h1, const float* h2, const float* h3,
-                                  const float* noise, float* hw, int b, int C, int Cout, int F, int HW, const T2VLinearStep& s,
+                                  const float* noise, float* hw, int b, int C, int Cout, int F, int HW, const LinearStep& s,
                                   hipStream_t st);
 // The same step in the class-conditional / unconditional engine's layout (latte_sample_plan_loop): x [B, F, C, HW] in place, model_out
 // [B, F, Cout, HW] with Cout = C or 2 C (the variance channels are never read).  guided: the doubled batch of forward_with_cfg
@@ -265,7 +265,7 @@ int launch_t2v_guided_linear_step(float* x, float* x_in, const float* model_out,
 // b % (B / 2) + B / 2, the order of sampler_update_kernel's raw_cfg path; every one of the B rows is updated.  Not guided: eps is the row's
 // own output and `scale` is unused.  Pointer rules as above; 16-byte accesses only: HW % 4 != 0 or a misaligned buffer is refused.
 int launch_linear_step(float* x, float* x_in, const float* model_out, const float* h1, const float* h2, const float* h3,
-                       const float* noise, float* hw, int B, int C, int Cout, int F, int HW, int guided, const T2VLinearStep& s,
+                       const float* noise, float* hw, int B, int C, int Cout, int F, int HW, int guided, const LinearStep& s,
                        hipStream_t st);
 int launch_mask_bias(const float* mask, float* bias, size_t n, hipStream_t st);   // bias = (1 - mask) * -10000
 int launch_cfg_combine(float* out, int half_batch, int F, int Cout, int HW, float cfg_scale, hipStream_t st);

@@ -327,7 +327,7 @@ int latte_debug_t2v_linear_step(float* x, float* x_in, const float* model_out, c
   if (!x || !x_in || !model_out || b < 1 || C < 1 || Cout < C || F < 1 || hw < 1) return fail(LATTE_ERR_INVALID, "t2v_linear_step: bad arguments");
   if ((c1 != 0.0f && !h1) || (c2 != 0.0f && !h2) || (c3 != 0.0f && !h3) || (c_noise != 0.0f && !noise) || (push && !hist_write))
     return fail(LATTE_ERR_INVALID, "t2v_linear_step: a buffer with a non-zero coefficient (or the pushed slot) is NULL");
-  const T2VLinearStep s{scale, m_x, m_eps, c_x, c0, c1, c2, c3, c_noise, in_scale_next, push ? 1 : 0};
+  const LinearStep s{scale, m_x, m_eps, c_x, c0, c1, c2, c3, c_noise, in_scale_next, push ? 1 : 0};
   return launch_t2v_guided_linear_step(x, x_in, model_out, h1, h2, h3, noise, hist_write, b, C, Cout, F, hw, s, (hipStream_t)stream);
 }
 
@@ -338,7 +338,7 @@ int latte_debug_linear_step(float* x, float* x_in, const float* model_out, const
   if (!x || !x_in || !model_out) return fail(LATTE_ERR_INVALID, "linear_step: bad arguments");
   if ((c1 != 0.0f && !h1) || (c2 != 0.0f && !h2) || (c3 != 0.0f && !h3) || (c_noise != 0.0f && !noise) || (push && !hist_write))
     return fail(LATTE_ERR_INVALID, "linear_step: a buffer with a non-zero coefficient (or the pushed slot) is NULL");
-  const T2VLinearStep s{scale, m_x, m_eps, c_x, c0, c1, c2, c3, c_noise, in_scale_next, push ? 1 : 0};
+  const LinearStep s{scale, m_x, m_eps, c_x, c0, c1, c2, c3, c_noise, in_scale_next, push ? 1 : 0};
   return launch_linear_step(x, x_in, model_out, h1, h2, h3, noise, hist_write, B, C, Cout, F, hw, guided ? 1 : 0, s, (hipStream_t)stream);
 }
 

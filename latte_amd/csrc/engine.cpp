@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "event_profile.h"
+#include "plan.h"
 #include "weight_store.h"
 
 namespace latte {
@@ -418,6 +419,7 @@ struct ChainCond {
   const float* temb;   // [num_timesteps, D] timestep-embedding table, own or installed
   int bu;              // conditioning rows per step: 1 for an unconditional model, else the batch
   int chunk_steps;     // steps whose rows fit mod_all at once
+  int lo = 0, hi = -1; // table rows whose conditioning mod_all holds right now (chain_mod)
 };
 
 // chunk size and row buffers of a chain of n_run steps with cc->bu rows each
@@ -476,6 +478,65 @@ int chain_conditioning(latte_engine* e, const ChainCond& cc, const int64_t* y, i
   return LATTE_OK;
 }
 
+// The cursor over mod_all: the adaLN rows of table row i of a chain that walks towards row `last` (ascending when last >= i, else
+// descending).  When row i is not resident the chunk is refilled from i in the direction of travel, capped at chunk_steps rows and at
+// `last`.  This is the only place that indexes mod_all for a step.
+int chain_mod(latte_engine* e, ChainCond* cc, const int64_t* y, int i, int last, hipStream_t st, const float** mod, int* stride) {
+  if (i < cc->lo || i > cc->hi) {
+    const int far = last >= i ? std::min(last, i + cc->chunk_steps - 1) : std::max(last, i - cc->chunk_steps + 1);
+    cc->lo = std::min(i, far);
+    cc->hi = std::max(i, far);
+    int rc = chain_conditioning(e, *cc, y, cc->lo, cc->hi - cc->lo + 1, st);
+    if (rc) return rc;
+  }
+  *mod = e->mod_all + (size_t)(i - cc->lo) * cc->bu * e->nmod;
+  *stride = cc->bu == 1 ? 0 : e->nmod;
+  return LATTE_OK;
+}
+
+// ---- what every fused loop shares besides its conditioning
+// rows [lo, hi] of a schedule of n timesteps; `why2` is the entry point's own text for n < 2
+int range_check(const std::string& who, int n, int lo, int hi, const char* why2) {
+  if (hi >= n || lo < 0 || hi < lo) return fail(LATTE_ERR_INVALID, who + ": bad index range");
+  if (n < 2) return fail(LATTE_ERR_INVALID, who + ": " + why2);
+  return LATTE_OK;
+}
+
+// The argument block, in this order: batch, learn_sigma (skipped without a schedule), doubled batch, y, text.
+int chain_check(const std::string& who, const latte_engine* e, const latte_schedule_t* s, int batch, bool guided, const int64_t* y,
+                bool text_allowed) {
+  if (batch <= 0 || batch > e->max_batch) return fail(LATTE_ERR_STATE, who + ": batch exceeds max_batch");
+  if (s && (s->var_type == 0) != (e->Cout == 2 * e->Cin))
+    return fail(LATTE_ERR_INVALID, who + ": the model's learn_sigma and the diffusion's learn_sigma disagree "
+                                         "(model output channels vs ModelVarType, gd:290 / :338)");
+  if (guided && (batch % 2)) return fail(LATTE_ERR_INVALID, who + ": guidance needs the doubled batch");
+  const int ex = e->cfg.extras;
+  if (ex == 2 && y == nullptr) return fail(LATTE_ERR_INVALID, who + ": class-conditional model needs y");
+  if (ex == 78 && !text_allowed) return fail(LATTE_ERR_INVALID, who + ": serves the class-conditional and unconditional models only");
+  if (ex == 78 && e->txt_rows != batch)
+    return fail(LATTE_ERR_STATE, who + ": text-conditioned model needs latte_engine_set_text_embedding with one row per sample first");
+  return LATTE_OK;
+}
+
+// noise of step k: the caller's row k, else one draw from the engine's Philox stream (option "seed"), which advances
+int chain_noise(latte_engine* e, const float* noise, int k, size_t numel, hipStream_t st, const float** nz) {
+  if (noise) {
+    *nz = noise + (size_t)k * numel;
+    return LATTE_OK;
+  }
+  int rc = launch_fill_normal(e->noise_buf, numel, e->seed, e->rng_offset, st);
+  if (rc) return rc;
+  e->rng_offset += numel;
+  *nz = e->noise_buf;
+  return LATTE_OK;
+}
+
+// x after step k into slot k of a trail (NULL: no trail)
+int chain_trail(float* trail, int k, const float* x, size_t numel, hipStream_t st) {
+  if (trail) LATTE_HIP(hipMemcpyAsync(trail + (size_t)k * numel, x, sizeof(float) * numel, hipMemcpyDeviceToDevice, st));
+  return LATTE_OK;
+}
+
 SamplerCoefs make_coefs(const latte_schedule_t* s, int method, int i, float eta, int clip) {
   SamplerCoefs c{};
   c.method = method;
@@ -507,6 +568,49 @@ SamplerCoefs make_coefs(const latte_schedule_t* s, int method, int i, float eta,
   if (s->var_type == 1) c.fixed_log_var = (float)std::log(i == 0 ? s->posterior_variance[1] : s->betas[i]);
   else c.fixed_log_var = (float)s->posterior_log_variance_clipped[i];
   return c;
+}
+
+// DDPM draws at every index but 0, DDIM where sigma != 0 (eta > 0), the reverse (inversion) step never
+bool step_needs_noise(int method, const SamplerCoefs& c, int index) {
+  return method == LATTE_METHOD_DDPM ? index != 0 : (c.sigma != 0.0f && index != 0);
+}
+
+// latte_sample_loop_ex (dir = -1: start_index down to end_index) and latte_invert_loop (dir = +1: start_index up to end_index)
+int sampler_chain(const std::string& who, latte_engine* e, const latte_schedule_t* s, int method, int dir, float eta, int clip_denoised,
+                  int guided, float cfg_scale, float* x, const int64_t* y, int batch, int start_index, int end_index, const float* noise,
+                  float* trail_sample, float* trail_x0, hipStream_t st) {
+  if (!e || !s || !x) return fail(LATTE_ERR_INVALID, who + ": null argument");
+  int rc = latte_engine_check_weights(e);
+  if (rc) return rc;
+  if ((rc = range_check(who, s->num_timesteps, dir > 0 ? start_index : end_index, dir > 0 ? end_index : start_index,
+                        "learned-range variance needs >= 2 timesteps"))) return rc;
+  const bool use_cfg = guided != 0;   // forward_with_cfg semantics for ANY scale (latte.py:379-398 has no threshold)
+  if ((rc = chain_check(who, e, s, batch, use_cfg, y, true))) return rc;
+  // ---- conditioning of the whole chain: it depends on (timestep, label) only, never on x.
+  //   temb[i]      = t_embedder(timestep_map[i])           (own, or the table installed after the RCCL broadcast)
+  //   c[i, b]      = SiLU(temb[i] (+ y_embedder(y[b])))     latte.py:337,348 (+ the SiLU of :173)
+  //   mod[i, b, :] = all 28 adaLN_modulation + the final layer's, = Linear(SiLU(c))   latte.py:172-178,192-198
+  // Unconditional models have one row per step shared by every sample (row stride 0).  The adaLN weights (0.9 GB
+  // fp32) are then streamed once per 64 rows instead of once per denoising step.
+  const int n_run = (end_index - start_index) * dir + 1;
+  ChainCond cc;
+  if ((rc = chain_prepare(e, s, e->cfg.extras == 1 ? 1 : batch, n_run, st, &cc))) return rc;
+  const size_t numel = (size_t)batch * e->F * e->Cin * e->H * e->H;
+  for (int k = 0; k < n_run; ++k) {
+    const int i = start_index + dir * k;
+    const float* mod_i;
+    int mstride;
+    if ((rc = chain_mod(e, &cc, y, i, end_index, st, &mod_i, &mstride))) return rc;
+    if ((rc = run_forward(e, x, nullptr, y, batch, use_cfg, e->model_out, st, nullptr, mod_i, mstride))) return rc;
+    SamplerCoefs c = make_coefs(s, method, i, eta, clip_denoised);
+    c.cfg_scale = cfg_scale;
+    const float* nz = nullptr;
+    if (step_needs_noise(method, c, i) && (rc = chain_noise(e, noise, k, numel, st, &nz))) return rc;
+    float* x0 = trail_x0 ? trail_x0 + (size_t)k * numel : nullptr;
+    if ((rc = launch_sampler_update(c, x, e->model_out, nz, batch, e->F, e->Cin, e->H * e->H, use_cfg ? 1 : 0, x, x0, st))) return rc;
+    if ((rc = chain_trail(trail_sample, k, x, numel, st))) return rc;
+  }
+  return LATTE_OK;
 }
 
 }  // namespace
@@ -828,8 +932,7 @@ int latte_sampler_step_ex(const latte_schedule_t* s, int method, int index, floa
   SamplerCoefs c = make_coefs(s, method, index, eta, clip_denoised);
   if (!predict_only && method == LATTE_METHOD_DDPM && index != 0 && noise == nullptr)
     return fail(LATTE_ERR_INVALID, "sampler_step: DDPM needs noise for index > 0");
-  const bool need_noise = (method == LATTE_METHOD_DDPM) ? (index != 0) : (c.sigma != 0.0f && index != 0);   // never for the reverse step
-  return launch_sampler_update(c, x, model_out, need_noise ? noise : nullptr, batch, frames, channels, hw, 0, sample_out,
+  return launch_sampler_update(c, x, model_out, step_needs_noise(method, c, index) ? noise : nullptr, batch, frames, channels, hw, 0, sample_out,
                                pred_xstart_out, (hipStream_t)stream, pred_xstart_in, cond_grad, predict_only);
 }
 
@@ -850,108 +953,16 @@ int latte_sample_loop(latte_engine_t* e, const latte_schedule_t* s, int method, 
 int latte_sample_loop_ex(latte_engine_t* e, const latte_schedule_t* s, int method, float eta, int clip_denoised, int guided,
                          float cfg_scale, float* x, const int64_t* y, int batch, int start_index, int end_index,
                          const float* noise, float* trail_sample, float* trail_x0, void* stream) {
-  if (!e || !s || !x) return fail(LATTE_ERR_INVALID, "sample_loop: null argument");
-  int rc = latte_engine_check_weights(e);
-  if (rc) return rc;
-  const int n = s->num_timesteps;
-  if (start_index >= n || end_index < 0 || start_index < end_index) return fail(LATTE_ERR_INVALID, "sample_loop: bad index range");
-  if (n < 2) return fail(LATTE_ERR_INVALID, "sample_loop: learned-range variance needs >= 2 timesteps");
-  if (batch <= 0 || batch > e->max_batch) return fail(LATTE_ERR_STATE, "sample_loop: batch exceeds max_batch");
-  if ((s->var_type == 0) != (e->Cout == 2 * e->Cin))
-    return fail(LATTE_ERR_INVALID, "sample_loop: the model's learn_sigma and the diffusion's learn_sigma disagree "
-                                   "(model output channels vs ModelVarType, gd:290 / :338)");
-  const bool use_cfg = guided != 0;   // forward_with_cfg semantics for ANY scale (latte.py:379-398 has no threshold)
-  if (use_cfg && (batch % 2)) return fail(LATTE_ERR_INVALID, "sample_loop: guidance needs the doubled batch");
-  hipStream_t st = (hipStream_t)stream;
-  // ---- conditioning of the whole chain, once: it depends on (timestep, label) only, never on x.
-  //   temb[i]      = t_embedder(timestep_map[i])           (own, or the table installed after the RCCL broadcast)
-  //   c[i, b]      = SiLU(temb[i] (+ y_embedder(y[b])))     latte.py:337,348 (+ the SiLU of :173)
-  //   mod[i, b, :] = all 28 adaLN_modulation + the final layer's, = Linear(SiLU(c))   latte.py:172-178,192-198
-  // Unconditional models have one row per step shared by every sample (row stride 0).  The adaLN weights (0.9 GB
-  // fp32) are then streamed once per 64 rows instead of once per denoising step.
-  const int n_run = start_index - end_index + 1;
-  const int ex = e->cfg.extras;
-  const int bu = ex == 1 ? 1 : batch;
-  if (ex == 2 && y == nullptr) return fail(LATTE_ERR_INVALID, "sample_loop: class-conditional model needs y");
-  if (ex == 78 && e->txt_rows != batch)
-    return fail(LATTE_ERR_STATE, "sample_loop: text-conditioned model needs latte_engine_set_text_embedding with one row per sample first");
-  ChainCond cc;
-  if ((rc = chain_prepare(e, s, bu, n_run, st, &cc))) return rc;
-  const int chunk_steps = cc.chunk_steps;
-  const size_t numel = (size_t)batch * e->F * e->Cin * e->H * e->H;
-  int k = 0;
-  int chunk_lo = start_index + 1;   // first respaced index covered by the rows currently in mod_all
-  for (int i = start_index; i >= end_index; --i, ++k) {
-    if (i < chunk_lo) {   // next chunk: steps i, i - 1, ..., down to max(end_index, i - chunk_steps + 1)
-      chunk_lo = std::max(end_index, i - chunk_steps + 1);
-      if ((rc = chain_conditioning(e, cc, y, chunk_lo, i - chunk_lo + 1, st))) return rc;
-    }
-    const float* mod_i = e->mod_all + (size_t)(i - chunk_lo) * bu * e->nmod;
-    if ((rc = run_forward(e, x, nullptr, y, batch, use_cfg, e->model_out, st, nullptr, mod_i, bu == 1 ? 0 : e->nmod))) return rc;
-    SamplerCoefs c = make_coefs(s, method, i, eta, clip_denoised);
-    c.cfg_scale = cfg_scale;
-    const bool need_noise = (method == LATTE_METHOD_DDPM) ? (i != 0) : (c.sigma != 0.0f && i != 0);
-    const float* nz = nullptr;
-    if (need_noise) {
-      if (noise) {
-        nz = noise + (size_t)k * numel;
-      } else {
-        if ((rc = launch_fill_normal(e->noise_buf, numel, e->seed, e->rng_offset, st))) return rc;
-        e->rng_offset += numel;
-        nz = e->noise_buf;
-      }
-    }
-    float* x0 = trail_x0 ? trail_x0 + (size_t)k * numel : nullptr;
-    if ((rc = launch_sampler_update(c, x, e->model_out, nz, batch, e->F, e->Cin, e->H * e->H, use_cfg ? 1 : 0, x, x0, st))) return rc;
-    if (trail_sample)
-      LATTE_HIP(hipMemcpyAsync(trail_sample + (size_t)k * numel, x, sizeof(float) * numel, hipMemcpyDeviceToDevice, st));
-  }
-  return LATTE_OK;
+  return sampler_chain("sample_loop", e, s, method, -1, eta, clip_denoised, guided, cfg_scale, x, y, batch, start_index, end_index, noise,
+                       trail_sample, trail_x0, (hipStream_t)stream);
 }
 
-// ---- DDIM inversion (gaussian_diffusion.py:566-602 ddim_reverse_sample, stepped over ascending indices)
+// ---- DDIM inversion (gaussian_diffusion.py:566-602 ddim_reverse_sample, stepped over ascending indices: index i carries level i to
+// level i + 1)
 int latte_invert_loop(latte_engine_t* e, const latte_schedule_t* s, int clip_denoised, int guided, float cfg_scale, float* x,
                       const int64_t* y, int batch, int start_index, int end_index, float* trail_sample, float* trail_x0, void* stream) {
-  if (!e || !s || !x) return fail(LATTE_ERR_INVALID, "invert_loop: null argument");
-  int rc = latte_engine_check_weights(e);
-  if (rc) return rc;
-  const int n = s->num_timesteps;
-  if (start_index < 0 || end_index >= n || start_index > end_index) return fail(LATTE_ERR_INVALID, "invert_loop: bad index range");
-  if (n < 2) return fail(LATTE_ERR_INVALID, "invert_loop: learned-range variance needs >= 2 timesteps");
-  if (batch <= 0 || batch > e->max_batch) return fail(LATTE_ERR_STATE, "invert_loop: batch exceeds max_batch");
-  if ((s->var_type == 0) != (e->Cout == 2 * e->Cin))
-    return fail(LATTE_ERR_INVALID, "invert_loop: the model's learn_sigma and the diffusion's learn_sigma disagree "
-                                   "(model output channels vs ModelVarType, gd:290 / :338)");
-  const bool use_cfg = guided != 0;   // forward_with_cfg semantics for ANY scale, as latte_sample_loop_ex
-  if (use_cfg && (batch % 2)) return fail(LATTE_ERR_INVALID, "invert_loop: guidance needs the doubled batch");
-  hipStream_t st = (hipStream_t)stream;
-  const int n_run = end_index - start_index + 1;
-  const int ex = e->cfg.extras;
-  const int bu = ex == 1 ? 1 : batch;
-  if (ex == 2 && y == nullptr) return fail(LATTE_ERR_INVALID, "invert_loop: class-conditional model needs y");
-  if (ex == 78 && e->txt_rows != batch)
-    return fail(LATTE_ERR_STATE, "invert_loop: text-conditioned model needs latte_engine_set_text_embedding with one row per sample first");
-  ChainCond cc;
-  if ((rc = chain_prepare(e, s, bu, n_run, st, &cc))) return rc;
-  const size_t numel = (size_t)batch * e->F * e->Cin * e->H * e->H;
-  int k = 0;
-  int chunk_lo = 0, chunk_hi = -1;   // respaced indices covered by the rows currently in mod_all
-  for (int i = start_index; i <= end_index; ++i, ++k) {   // index i carries level i to level i + 1
-    if (i > chunk_hi) {   // next chunk: steps i, i + 1, ..., up to min(end_index, i + chunk_steps - 1)
-      chunk_lo = i;
-      chunk_hi = std::min(end_index, i + cc.chunk_steps - 1);
-      if ((rc = chain_conditioning(e, cc, y, chunk_lo, chunk_hi - chunk_lo + 1, st))) return rc;
-    }
-    const float* mod_i = e->mod_all + (size_t)(i - chunk_lo) * bu * e->nmod;
-    if ((rc = run_forward(e, x, nullptr, y, batch, use_cfg, e->model_out, st, nullptr, mod_i, bu == 1 ? 0 : e->nmod))) return rc;
-    SamplerCoefs c = make_coefs(s, LATTE_METHOD_DDIM_REVERSE, i, 0.0f, clip_denoised);
-    c.cfg_scale = cfg_scale;
-    float* x0 = trail_x0 ? trail_x0 + (size_t)k * numel : nullptr;
-    if ((rc = launch_sampler_update(c, x, e->model_out, nullptr, batch, e->F, e->Cin, e->H * e->H, use_cfg ? 1 : 0, x, x0, st))) return rc;
-    if (trail_sample)
-      LATTE_HIP(hipMemcpyAsync(trail_sample + (size_t)k * numel, x, sizeof(float) * numel, hipMemcpyDeviceToDevice, st));
-  }
-  return LATTE_OK;
+  return sampler_chain("invert_loop", e, s, LATTE_METHOD_DDIM_REVERSE, +1, 0.0f, clip_denoised, guided, cfg_scale, x, y, batch, start_index,
+                       end_index, nullptr, trail_sample, trail_x0, (hipStream_t)stream);
 }
 
 // ---- linear samplers as a plan (include/latte_amd.h; the table is latte_amd/schedulers.py: engine_plan())
@@ -960,41 +971,13 @@ int latte_sample_plan_loop(latte_engine_t* e, int guided, float cfg_scale, float
   if (!e || !x || !plan || batch <= 0 || n_evals <= 0) return fail(LATTE_ERR_INVALID, "sample_plan_loop: bad arguments");
   int rc = latte_engine_check_weights(e);
   if (rc) return rc;
-  if (batch > e->max_batch) return fail(LATTE_ERR_STATE, "sample_plan_loop: batch exceeds max_batch");
   const bool use_cfg = guided != 0;   // forward_with_cfg semantics for ANY scale, as latte_sample_loop_ex
-  if (use_cfg && (batch % 2)) return fail(LATTE_ERR_INVALID, "sample_plan_loop: guidance needs the doubled batch");
-  const int ex = e->cfg.extras;
-  if (ex == 2 && y == nullptr) return fail(LATTE_ERR_INVALID, "sample_plan_loop: class-conditional model needs y");
-  if (ex == 78 && e->txt_rows != batch)
-    return fail(LATTE_ERR_STATE, "sample_plan_loop: text-conditioned model needs latte_engine_set_text_embedding with one row per sample first");
-  if (n_evals > LATTE_PLAN_MAX_EVALS)
-    return fail(LATTE_ERR_INVALID, "sample_plan_loop: more than " + std::to_string(LATTE_PLAN_MAX_EVALS) + " evaluations");
+  if ((rc = chain_check("sample_plan_loop", e, nullptr, batch, use_cfg, y, true))) return rc;
   const int HW = e->H * e->H;
-  if (HW % 4) return fail(LATTE_ERR_INVALID, "sample_plan_loop: H * W must be a multiple of 4 (16-byte accesses of the step kernel)");
-  // ---- the whole table is checked before anything is launched
-  enum { P_T = 0, P_IN, P_MX, P_MEPS, P_CX, P_C0, P_C1, P_C2, P_C3, P_CN, P_PUSH, P_RSV };
-  std::vector<int64_t> ts(n_evals);
-  bool scaled = false;
-  int pushed = 0;
-  for (int k = 0; k < n_evals; ++k) {
-    const double* r = plan + (size_t)k * LATTE_PLAN_COLS;
-    for (int j = 0; j < LATTE_PLAN_COLS; ++j)
-      if (!std::isfinite(r[j])) return fail(LATTE_ERR_INVALID, "sample_plan_loop: non-finite plan entry in row " + std::to_string(k));
-    if (r[P_T] < 0.0 || r[P_T] >= 9.0e15 || r[P_T] != std::floor(r[P_T]))
-      return fail(LATTE_ERR_INVALID, "sample_plan_loop: timestep of row " + std::to_string(k) + " is not a non-negative integer");
-    if (r[P_T] >= (double)e->train_timesteps)
-      return fail(LATTE_ERR_INVALID, "sample_plan_loop: timestep of row " + std::to_string(k) + " is outside the trained range [0, " +
-                                         std::to_string(e->train_timesteps) + ")");
-    if ((r[P_PUSH] != 0.0 && r[P_PUSH] != 1.0) || r[P_RSV] != 0.0)
-      return fail(LATTE_ERR_INVALID, "sample_plan_loop: push must be 0 or 1 and the reserved column 0 (row " + std::to_string(k) + ")");
-    for (int j = 1; j <= 3; ++j)
-      if (r[P_C0 + j] != 0.0 && pushed < j)
-        return fail(LATTE_ERR_INVALID, "sample_plan_loop: row " + std::to_string(k) + " reads history slot " + std::to_string(j) +
-                                           " before " + std::to_string(j) + " rows with push have run");
-    ts[k] = (int64_t)r[P_T];
-    scaled = scaled || r[P_IN] != 1.0;
-    pushed += r[P_PUSH] != 0.0;
-  }
+  if (n_evals <= LATTE_PLAN_MAX_EVALS && HW % 4)   // plan_check refuses a longer table first
+    return fail(LATTE_ERR_INVALID, "sample_plan_loop: H * W must be a multiple of 4 (16-byte accesses of the step kernel)");
+  PlanInfo info;   // the engine may draw the noise of a row itself
+  if ((rc = plan_check("sample_plan_loop", plan, n_evals, LATTE_PLAN_MAX_EVALS, e->train_timesteps, noise != nullptr, true, &info))) return rc;
   hipStream_t st = (hipStream_t)stream;
   const size_t per = (size_t)e->F * e->Cin * HW;
   const size_t numel = (size_t)batch * per;
@@ -1005,48 +988,30 @@ int latte_sample_plan_loop(latte_engine_t* e, int guided, float cfg_scale, float
   }
   // ---- conditioning: t_embedder of every row (chain order), then the adaLN outputs chunk by chunk right before the rows that use them
   if ((rc = grow(e, &e->plan_temb, &e->plan_temb_cap, (int64_t)n_evals * e->D))) return rc;
-  if ((rc = compute_temb_rows(e, ts.data(), n_evals, e->plan_temb, st))) return rc;
+  if ((rc = compute_temb_rows(e, info.ts.data(), n_evals, e->plan_temb, st))) return rc;
   ChainCond cc;
   cc.temb = e->plan_temb;
-  cc.bu = ex == 1 ? 1 : batch;
+  cc.bu = e->cfg.extras == 1 ? 1 : batch;
   if ((rc = chain_row_buffers(e, n_evals, &cc))) return rc;
-  const int bu = cc.bu;
   // what the denoiser reads: x itself when every in_scale is 1, else in_scale * x kept beside it by the step kernel
-  float* x_in = scaled ? e->plan_xin : x;
-  if (scaled) {
+  float* x_in = info.scaled ? e->plan_xin : x;
+  if (info.scaled) {
     LATTE_HIP(hipMemcpyAsync(x_in, x, sizeof(float) * numel, hipMemcpyDeviceToDevice, st));
     if ((rc = launch_scale_f32(x_in, (float)plan[P_IN], numel, st))) return rc;
   }
-  int newest = 0;   // ring: h_j = plan_hist[(newest - (j - 1) + 3) % 3]; a push writes the oldest slot, which becomes h1
-  int chunk_lo = 0, chunk_hi = -1;   // rows covered by what mod_all currently holds
+  HistRing ring{{e->plan_hist[0], e->plan_hist[1], e->plan_hist[2]}};
   for (int k = 0; k < n_evals; ++k) {
-    const double* r = plan + (size_t)k * LATTE_PLAN_COLS;
-    if (k > chunk_hi) {
-      chunk_lo = k;
-      chunk_hi = std::min(n_evals - 1, k + cc.chunk_steps - 1);
-      if ((rc = chain_conditioning(e, cc, y, chunk_lo, chunk_hi - chunk_lo + 1, st))) return rc;
-    }
-    const float* mod_k = e->mod_all + (size_t)(k - chunk_lo) * bu * e->nmod;
-    if ((rc = run_forward(e, x_in, nullptr, y, batch, use_cfg, e->model_out, st, nullptr, mod_k, bu == 1 ? 0 : e->nmod))) return rc;
+    const float* mod_k;
+    int mstride;
+    if ((rc = chain_mod(e, &cc, y, k, n_evals - 1, st, &mod_k, &mstride))) return rc;
+    if ((rc = run_forward(e, x_in, nullptr, y, batch, use_cfg, e->model_out, st, nullptr, mod_k, mstride))) return rc;
+    const LinearStep s = plan_step(plan, k, n_evals, cfg_scale);
     const float* nz = nullptr;
-    if (r[P_CN] != 0.0) {
-      if (noise) {
-        nz = noise + (size_t)k * numel;
-      } else {
-        if ((rc = launch_fill_normal(e->noise_buf, numel, e->seed, e->rng_offset, st))) return rc;
-        e->rng_offset += numel;
-        nz = e->noise_buf;
-      }
-    }
-    const bool last = k + 1 == n_evals;
-    const T2VLinearStep s{cfg_scale, (float)r[P_MX], (float)r[P_MEPS], (float)r[P_CX], (float)r[P_C0], (float)r[P_C1], (float)r[P_C2],
-                          (float)r[P_C3], (float)r[P_CN], last ? 1.0f : (float)r[LATTE_PLAN_COLS + P_IN], r[P_PUSH] != 0.0 ? 1 : 0};
-    if ((rc = launch_linear_step(x, last ? x : x_in, e->model_out, e->plan_hist[newest], e->plan_hist[(newest + 2) % 3],
-                                 e->plan_hist[(newest + 1) % 3], nz, e->plan_hist[(newest + 1) % 3], batch, e->Cin, e->Cout, e->F, HW,
-                                 use_cfg ? 1 : 0, s, st))) return rc;
-    if (s.push) newest = (newest + 1) % 3;
-    if (trail_sample)
-      LATTE_HIP(hipMemcpyAsync(trail_sample + (size_t)k * numel, x, sizeof(float) * numel, hipMemcpyDeviceToDevice, st));
+    if (plan[(size_t)k * LATTE_PLAN_COLS + P_CN] != 0.0 && (rc = chain_noise(e, noise, k, numel, st, &nz))) return rc;
+    if ((rc = launch_linear_step(x, k + 1 == n_evals ? x : x_in, e->model_out, ring.h1(), ring.h2(), ring.h3(), nz, ring.write(), batch,
+                                 e->Cin, e->Cout, e->F, HW, use_cfg ? 1 : 0, s, st))) return rc;
+    if (s.push) ring.push();
+    if ((rc = chain_trail(trail_sample, k, x, numel, st))) return rc;
   }
   return LATTE_OK;
 }
@@ -1170,45 +1135,27 @@ int latte_bpd_loop(latte_engine_t* e, const latte_schedule_t* s, int clip_denois
   if (!e || !s || !x_start || !vb || !xstart_mse || !mse) return fail(LATTE_ERR_INVALID, "bpd_loop: null argument");
   int rc = latte_engine_check_weights(e);
   if (rc) return rc;
-  const int n = s->num_timesteps;
-  if (start_index >= n || end_index < 0 || start_index < end_index) return fail(LATTE_ERR_INVALID, "bpd_loop: bad index range");
-  if (n < 2) return fail(LATTE_ERR_INVALID, "bpd_loop: needs >= 2 timesteps (posterior_log_variance_clipped)");
-  if (batch <= 0 || batch > e->max_batch) return fail(LATTE_ERR_STATE, "bpd_loop: batch exceeds max_batch");
-  if ((s->var_type == 0) != (e->Cout == 2 * e->Cin))
-    return fail(LATTE_ERR_INVALID, "bpd_loop: the model's learn_sigma and the diffusion's learn_sigma disagree "
-                                   "(model output channels vs ModelVarType, gd:290 / :338)");
-  const int ex = e->cfg.extras;
-  if (ex == 2 && y == nullptr) return fail(LATTE_ERR_INVALID, "bpd_loop: class-conditional model needs y");
-  if (ex == 78) return fail(LATTE_ERR_INVALID, "bpd_loop: serves the class-conditional and unconditional models only");
+  if ((rc = range_check("bpd_loop", s->num_timesteps, end_index, start_index, "needs >= 2 timesteps (posterior_log_variance_clipped)")))
+    return rc;
+  if ((rc = chain_check("bpd_loop", e, s, batch, false, y, false))) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int n_run = start_index - end_index + 1;
-  const int bu = ex == 1 ? 1 : batch;
   const size_t per = (size_t)e->F * e->Cin * e->H * e->H;
   const size_t numel = (size_t)batch * per;
   const int blocks = training_terms_blocks(per);
   ChainCond cc;
-  if ((rc = chain_prepare(e, s, bu, n_run, st, &cc))) return rc;
+  if ((rc = chain_prepare(e, s, e->cfg.extras == 1 ? 1 : batch, n_run, st, &cc))) return rc;
   if ((rc = grow(e, &e->bpd_xt, &e->bpd_xt_cap, (int64_t)e->max_batch * (int64_t)per))) return rc;
   if ((rc = grow(e, &e->bpd_ws, &e->bpd_ws_cap, latte_bpd_workspace_floats(e->max_batch, (int64_t)per)))) return rc;
-  int k = 0;
-  int chunk_lo = start_index + 1;   // first respaced index covered by the rows currently in mod_all
-  for (int i = start_index; i >= end_index; --i, ++k) {   // gd:835: t = T-1 first
-    if (i < chunk_lo) {
-      chunk_lo = std::max(end_index, i - cc.chunk_steps + 1);
-      if ((rc = chain_conditioning(e, cc, y, chunk_lo, i - chunk_lo + 1, st))) return rc;
-    }
-    const float* nz = nullptr;
-    if (noise) {
-      nz = noise + (size_t)k * numel;
-    } else {                        // gd:837: one draw per step, from the engine's stream
-      if ((rc = launch_fill_normal(e->noise_buf, numel, e->seed, e->rng_offset, st))) return rc;
-      e->rng_offset += numel;
-      nz = e->noise_buf;
-    }
+  for (int k = 0; k < n_run; ++k) {   // gd:835: t = T-1 first
+    const int i = start_index - k;
+    const float *mod_i, *nz;
+    int mstride;
+    if ((rc = chain_mod(e, &cc, y, i, end_index, st, &mod_i, &mstride))) return rc;
+    if ((rc = chain_noise(e, noise, k, numel, st, &nz))) return rc;   // gd:837: one draw per step
     if ((rc = launch_q_sample_scalar((float)s->sqrt_alphas_cumprod[i], (float)s->sqrt_one_minus_alphas_cumprod[i], x_start, nz, numel,
                                      e->bpd_xt, st))) return rc;                       // gd:838
-    const float* mod_i = e->mod_all + (size_t)(i - chunk_lo) * bu * e->nmod;
-    if ((rc = run_forward(e, e->bpd_xt, nullptr, y, batch, false, e->model_out, st, nullptr, mod_i, bu == 1 ? 0 : e->nmod))) return rc;
+    if ((rc = run_forward(e, e->bpd_xt, nullptr, y, batch, false, e->model_out, st, nullptr, mod_i, mstride))) return rc;
     const SamplerCoefs c = make_coefs(s, LATTE_METHOD_DDPM, i, 0.0f, clip_denoised);
     if ((rc = launch_bpd_terms(c, x_start, e->bpd_xt, nz, e->model_out, batch, e->F, e->Cin, e->H * e->H, e->bpd_ws, blocks, vb + k,
                                xstart_mse + k, mse + k, n_run, nullptr, st))) return rc;   // gd:841-852

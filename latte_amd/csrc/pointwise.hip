@@ -795,68 +795,51 @@ __device__ __forceinline__ void st_row(float* p, const float (&d)[V]) {
   else *p = d[0];
 }
 
-// The guided step of every linear sampler (common.h: T2VLinearStep), indexed exactly as t2v_guided_ddim_kernel; V = 4 needs hw % 4 == 0
-// (the four elements of a thread then lie in one row) and 16-byte aligned buffers.  x / x_in and the history pointers carry no
-// __restrict__: x_in may be x, hwr may be one of h1..h3 -- every thread reads its elements before it writes them.
-template <int V>
-__global__ void t2v_guided_linear_step_kernel(float* x, float* x_in, const float* __restrict__ mo, const float* h1, const float* h2,
-                                              const float* h3, const float* __restrict__ noise, float* hwr, int b, int C, int Cout, int F,
-                                              int hw, T2VLinearStep s) {
-#pragma clang fp contract(off)
-  const size_t total = (size_t)b * C * F * hw / V;
-  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (size_t)gridDim.x * blockDim.x) {
-    const size_t i = q * V;
+// Where the V elements of x that start at flat index i find their model-output rows: `cd` the conditional row (the only one when not
+// guided), `un` the unconditional one.  n is the launcher's batch argument.
+struct T2VRows {   // x [n, C, F, hw], output of the guidance pair [(2 n) F, Cout, hw], indexed exactly as t2v_guided_ddim_kernel
+  static constexpr bool guided = true;
+  static __device__ __forceinline__ void rows(const float* mo, size_t i, int n, int C, int Cout, int F, int hw, const float*& un,
+                                              const float*& cd) {
     const size_t r = i % hw, f = (i / hw) % F, c = (i / ((size_t)hw * F)) % C, bb = i / ((size_t)hw * F * C);
-    float un[V], tx[V], xv[V], a1[V], a2[V], a3[V], nz[V], m0[V], xn[V];
-    ld_row<V>(un, mo + (((bb * F + f) * Cout) + c) * hw + r);                // negative-prompt half
-    ld_row<V>(tx, mo + ((((bb + b) * F + f) * Cout) + c) * hw + r);          // prompt half
-    ld_row<V>(xv, x + i);
-    if (s.c1 != 0.0f) ld_row<V>(a1, h1 + i);
-    if (s.c2 != 0.0f) ld_row<V>(a2, h2 + i);
-    if (s.c3 != 0.0f) ld_row<V>(a3, h3 + i);
-    if (s.c_noise != 0.0f) ld_row<V>(nz, noise + i);
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-      const float eps = un[j] + s.scale * (tx[j] - un[j]);                   // pipeline_latte.py:748-749
-      m0[j] = s.m_x * xv[j] + s.m_eps * eps;
-      float v = s.c_x * xv[j] + s.c0 * m0[j];
-      if (s.c1 != 0.0f) v = v + s.c1 * a1[j];
-      if (s.c2 != 0.0f) v = v + s.c2 * a2[j];
-      if (s.c3 != 0.0f) v = v + s.c3 * a3[j];
-      if (s.c_noise != 0.0f) v = v + s.c_noise * nz[j];
-      xn[j] = v;
-    }
-    st_row<V>(x + i, xn);
-    if (x_in != x) {
-#pragma unroll
-      for (int j = 0; j < V; ++j) xv[j] = s.in_scale_next * xn[j];
-      st_row<V>(x_in + i, xv);
-    }
-    if (s.push) st_row<V>(hwr + i, m0);
+    un = mo + (((bb * F + f) * Cout) + c) * hw + r;            // negative-prompt half: the first
+    cd = mo + ((((bb + n) * F + f) * Cout) + c) * hw + r;      // prompt half
   }
-}
+};
+struct ClassGuidedRows {   // x [n, F, C, hw], output [n, F, Cout, hw] of the doubled batch; rows b and b + n / 2 read the same pair
+  static constexpr bool guided = true;
+  static __device__ __forceinline__ void rows(const float* mo, size_t i, int n, int C, int Cout, int F, int hw, const float*& un,
+                                              const float*& cd) {
+    const size_t hb = (size_t)(n >> 1);
+    const size_t r = i % hw, c = (i / hw) % C, bf = i / ((size_t)hw * C), bc = (bf / F) % hb, f = bf % F;
+    cd = mo + (((bc * F + f) * Cout) + c) * hw + r;            // cond: the first half of the doubled batch (latte.py:395)
+    un = mo + ((((bc + hb) * F + f) * Cout) + c) * hw + r;     // uncond: the second half
+  }
+};
+struct ClassPlainRows {   // the same layout, every row on its own output
+  static constexpr bool guided = false;
+  static __device__ __forceinline__ void rows(const float* mo, size_t i, int n, int C, int Cout, int F, int hw, const float*& un,
+                                              const float*& cd) {
+    const size_t r = i % hw, c = (i / hw) % C, bf = i / ((size_t)hw * C);
+    un = cd = mo + ((bf * Cout) + c) * hw + r;
+  }
+};
 
-// The same step on the class-conditional / unconditional engine's layout (common.h: launch_linear_step): x [B, F, C, hw], model output
-// [B, F, Cout, hw].  Four consecutive floats of one (sample, frame, channel) row per thread (hw % 4 == 0), 16-byte accesses; the aliasing
-// rules of the kernel above: x_in may be x, hwr may be one of h1..h3, every thread reads its elements before it writes them.
-template <bool GUIDED>
+// The step of every linear sampler (common.h: LinearStep) on n * C * F * hw latents, V consecutive floats of one row per thread; V = 4
+// needs hw % 4 == 0 (the four elements of a thread then lie in one row) and 16-byte aligned buffers.  x / x_in and the history pointers
+// carry no __restrict__: x_in may be x, hwr may be one of h1..h3 -- every thread reads its elements before it writes them.
+template <class Layout, int V>
 __global__ void linear_step_kernel(float* x, float* x_in, const float* __restrict__ mo, const float* h1, const float* h2, const float* h3,
-                                   const float* __restrict__ noise, float* hwr, int B, int C, int Cout, int F, int hw, T2VLinearStep s) {
+                                   const float* __restrict__ noise, float* hwr, int n, int C, int Cout, int F, int hw, LinearStep s) {
 #pragma clang fp contract(off)
-  constexpr int V = 4;
-  const size_t total = (size_t)B * F * C * hw / V;
-  const size_t hb = (size_t)(B >> 1);
+  const size_t total = (size_t)n * C * F * hw / V;
   for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (size_t)gridDim.x * blockDim.x) {
     const size_t i = q * V;
-    const size_t r = i % hw, c = (i / hw) % C, bf = i / ((size_t)hw * C);
-    float e0[V], e1[V], xv[V], a1[V], a2[V], a3[V], nz[V], m0[V], xn[V];
-    if constexpr (GUIDED) {
-      const size_t bc = (bf / F) % hb, f = bf % F;
-      ld_row<V>(e0, mo + (((bc * F + f) * Cout) + c) * hw + r);              // cond: the first half of the doubled batch (latte.py:395)
-      ld_row<V>(e1, mo + ((((bc + hb) * F + f) * Cout) + c) * hw + r);       // uncond: the second half
-    } else {
-      ld_row<V>(e0, mo + ((bf * Cout) + c) * hw + r);
-    }
+    const float *pu, *pc;
+    Layout::rows(mo, i, n, C, Cout, F, hw, pu, pc);
+    float un[V], cd[V], xv[V], a1[V], a2[V], a3[V], nz[V], m0[V], xn[V];
+    ld_row<V>(cd, pc);
+    if constexpr (Layout::guided) ld_row<V>(un, pu);
     ld_row<V>(xv, x + i);
     if (s.c1 != 0.0f) ld_row<V>(a1, h1 + i);
     if (s.c2 != 0.0f) ld_row<V>(a2, h2 + i);
@@ -864,8 +847,8 @@ __global__ void linear_step_kernel(float* x, float* x_in, const float* __restric
     if (s.c_noise != 0.0f) ld_row<V>(nz, noise + i);
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      float eps = e0[j];
-      if constexpr (GUIDED) eps = e1[j] + s.scale * (e0[j] - e1[j]);         // latte.py:396: uncond + s (cond - uncond)
+      float eps = cd[j];
+      if constexpr (Layout::guided) eps = un[j] + s.scale * (cd[j] - un[j]);   // latte.py:396, pipeline_latte.py:748-749
       m0[j] = s.m_x * xv[j] + s.m_eps * eps;
       float v = s.c_x * xv[j] + s.c0 * m0[j];
       if (s.c1 != 0.0f) v = v + s.c1 * a1[j];
@@ -1064,24 +1047,24 @@ int launch_t2v_guided_ddim(float* x, const float* model_out, int b, int C, int C
 }
 
 int launch_t2v_guided_linear_step(float* x, float* x_in, const float* model_out, const float* h1, const float* h2, const float* h3,
-                                  const float* noise, float* hw, int b, int C, int Cout, int F, int HW, const T2VLinearStep& s,
+                                  const float* noise, float* hw, int b, int C, int Cout, int F, int HW, const LinearStep& s,
                                   hipStream_t st) {
   const size_t total = (size_t)b * C * F * HW;
   auto aligned = [](const void* p) { return ((uintptr_t)p & 15) == 0; };   // a null (unused) pointer counts as aligned
   const bool vec = HW % 4 == 0 && aligned(x) && aligned(x_in) && aligned(model_out) && aligned(h1) && aligned(h2) && aligned(h3) &&
                    aligned(noise) && aligned(hw);
   if (vec)
-    hipLaunchKernelGGL(t2v_guided_linear_step_kernel<4>, dim3(grid_for(total / 4, 256)), dim3(256), 0, st, x, x_in, model_out, h1, h2, h3,
+    hipLaunchKernelGGL((linear_step_kernel<T2VRows, 4>), dim3(grid_for(total / 4, 256)), dim3(256), 0, st, x, x_in, model_out, h1, h2, h3,
                        noise, hw, b, C, Cout, F, HW, s);
   else
-    hipLaunchKernelGGL(t2v_guided_linear_step_kernel<1>, dim3(grid_for(total, 256)), dim3(256), 0, st, x, x_in, model_out, h1, h2, h3,
+    hipLaunchKernelGGL((linear_step_kernel<T2VRows, 1>), dim3(grid_for(total, 256)), dim3(256), 0, st, x, x_in, model_out, h1, h2, h3,
                        noise, hw, b, C, Cout, F, HW, s);
   LATTE_HIP(hipGetLastError());
   return LATTE_OK;
 }
 
 int launch_linear_step(float* x, float* x_in, const float* model_out, const float* h1, const float* h2, const float* h3,
-                       const float* noise, float* hw, int B, int C, int Cout, int F, int HW, int guided, const T2VLinearStep& s,
+                       const float* noise, float* hw, int B, int C, int Cout, int F, int HW, int guided, const LinearStep& s,
                        hipStream_t st) {
   if (B < 1 || C < 1 || F < 1 || HW < 1 || (Cout != C && Cout != 2 * C)) return fail(LATTE_ERR_INVALID, "linear_step: bad shape (Cout must be C or 2 C)");
   if (guided && (B % 2)) return fail(LATTE_ERR_INVALID, "linear_step: guidance needs the doubled batch");
@@ -1090,10 +1073,10 @@ int launch_linear_step(float* x, float* x_in, const float* model_out, const floa
     return fail(LATTE_ERR_INVALID, "linear_step: HW must be a multiple of 4 and every buffer 16-byte aligned");
   const size_t total = (size_t)B * F * C * HW;
   if (guided)
-    hipLaunchKernelGGL(linear_step_kernel<true>, dim3(grid_for(total / 4, 256)), dim3(256), 0, st, x, x_in, model_out, h1, h2, h3, noise, hw,
+    hipLaunchKernelGGL((linear_step_kernel<ClassGuidedRows, 4>), dim3(grid_for(total / 4, 256)), dim3(256), 0, st, x, x_in, model_out, h1, h2, h3, noise, hw,
                        B, C, Cout, F, HW, s);
   else
-    hipLaunchKernelGGL(linear_step_kernel<false>, dim3(grid_for(total / 4, 256)), dim3(256), 0, st, x, x_in, model_out, h1, h2, h3, noise, hw,
+    hipLaunchKernelGGL((linear_step_kernel<ClassPlainRows, 4>), dim3(grid_for(total / 4, 256)), dim3(256), 0, st, x, x_in, model_out, h1, h2, h3, noise, hw,
                        B, C, Cout, F, HW, s);
   LATTE_HIP(hipGetLastError());
   return LATTE_OK;

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/latte_amd.h"
+#include "plan.h"
 #include "weight_store.h"
 
 using namespace latte;
@@ -482,54 +483,27 @@ int latte_t2v_guided_linear_loop(latte_t2v_t* e, float* x, int samples, int n_ev
   const auto& c = e->cfg;
   if (c.out_channels != c.in_channels && c.out_channels != 2 * c.in_channels)
     return fail(LATTE_ERR_INVALID, "t2v_guided_linear_loop: out_channels must be C or 2C (learned sigma)");
-  if (n_evals > e->tsteps_cap) return fail(LATTE_ERR_INVALID, "t2v_guided_linear_loop: more than 1024 evaluations");
-  // ---- the whole table is checked before anything is launched
-  enum { P_T = 0, P_IN, P_MX, P_MEPS, P_CX, P_C0, P_C1, P_C2, P_C3, P_CN, P_PUSH, P_RSV };
-  std::vector<int64_t> ts(n_evals);
-  bool scaled = false;
-  int pushed = 0;
-  for (int k = 0; k < n_evals; ++k) {
-    const double* r = plan + (size_t)k * LATTE_T2V_PLAN_COLS;
-    for (int j = 0; j < LATTE_T2V_PLAN_COLS; ++j)
-      if (!std::isfinite(r[j])) return fail(LATTE_ERR_INVALID, "t2v_guided_linear_loop: non-finite plan entry in row " + std::to_string(k));
-    if (r[P_T] < 0.0 || r[P_T] >= 9.0e15 || r[P_T] != std::floor(r[P_T]))
-      return fail(LATTE_ERR_INVALID, "t2v_guided_linear_loop: timestep of row " + std::to_string(k) + " is not a non-negative integer");
-    if ((r[P_PUSH] != 0.0 && r[P_PUSH] != 1.0) || r[P_RSV] != 0.0)
-      return fail(LATTE_ERR_INVALID, "t2v_guided_linear_loop: push must be 0 or 1 and the reserved column 0 (row " + std::to_string(k) + ")");
-    if (r[P_CN] != 0.0 && !noise)
-      return fail(LATTE_ERR_INVALID, "t2v_guided_linear_loop: row " + std::to_string(k) + " has c_noise != 0 but no noise was passed");
-    for (int j = 1; j <= 3; ++j)
-      if (r[P_C0 + j] != 0.0 && pushed < j)
-        return fail(LATTE_ERR_INVALID, "t2v_guided_linear_loop: row " + std::to_string(k) + " reads history slot " + std::to_string(j) +
-                                           " before " + std::to_string(j) + " rows with push have run");
-    ts[k] = (int64_t)r[P_T];
-    scaled = scaled || r[P_IN] != 1.0;
-    pushed += r[P_PUSH] != 0.0;
-  }
+  PlanInfo info;   // no trained-range bound, and this engine draws no noise of its own
+  if ((rc = plan_check("t2v_guided_linear_loop", plan, n_evals, e->tsteps_cap, 0, noise != nullptr, false, &info))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  LATTE_HIP(hipMemcpyAsync(e->tsteps, ts.data(), sizeof(int64_t) * n_evals, hipMemcpyHostToDevice, st));
-  LATTE_HIP(hipStreamSynchronize(st));   // ts goes away
+  LATTE_HIP(hipMemcpyAsync(e->tsteps, info.ts.data(), sizeof(int64_t) * n_evals, hipMemcpyHostToDevice, st));
+  LATTE_HIP(hipStreamSynchronize(st));   // info.ts goes away
   const int HW = e->H * e->H;
   const size_t per_chain = (size_t)samples * c.in_channels * e->F * HW;
   // what the denoiser reads: x itself when every in_scale is 1, else in_scale * x kept beside it by the step kernel
-  float* x_in = scaled ? e->x_scaled : x;
-  if (scaled) {
+  float* x_in = info.scaled ? e->x_scaled : x;
+  if (info.scaled) {
     LATTE_HIP(hipMemcpyAsync(x_in, x, sizeof(float) * per_chain, hipMemcpyDeviceToDevice, st));
     if ((rc = launch_scale_f32(x_in, (float)plan[P_IN], per_chain, st))) return rc;
   }
-  int newest = 0;   // ring: h_j = hist[(newest - (j - 1) + 3) % 3]; a push writes the oldest slot, which becomes h1
+  HistRing ring{{e->hist[0], e->hist[1], e->hist[2]}};
   for (int k = 0; k < n_evals; ++k) {
-    const double* r = plan + (size_t)k * LATTE_T2V_PLAN_COLS;
     if ((rc = t2v_core(e, x_in, e->tsteps + k, true, B, true, enable_temporal_attentions, st))) return rc;
-    const bool last = k + 1 == n_evals;
-    const T2VLinearStep s{guidance_scale, (float)r[P_MX], (float)r[P_MEPS], (float)r[P_CX], (float)r[P_C0], (float)r[P_C1],
-                          (float)r[P_C2], (float)r[P_C3], (float)r[P_CN], last ? 1.0f : (float)r[LATTE_T2V_PLAN_COLS + P_IN],
-                          r[P_PUSH] != 0.0 ? 1 : 0};
-    if ((rc = launch_t2v_guided_linear_step(x, last ? x : x_in, e->out_bf, e->hist[newest], e->hist[(newest + 2) % 3],
-                                            e->hist[(newest + 1) % 3], noise ? noise + (size_t)k * per_chain : nullptr,
-                                            e->hist[(newest + 1) % 3], samples, c.in_channels, c.out_channels, e->F, HW, s, st)))
-      return rc;
-    if (s.push) newest = (newest + 1) % 3;
+    const LinearStep s = plan_step(plan, k, n_evals, guidance_scale);
+    if ((rc = launch_t2v_guided_linear_step(x, k + 1 == n_evals ? x : x_in, e->out_bf, ring.h1(), ring.h2(), ring.h3(),
+                                            noise ? noise + (size_t)k * per_chain : nullptr, ring.write(), samples, c.in_channels,
+                                            c.out_channels, e->F, HW, s, st))) return rc;
+    if (s.push) ring.push();
   }
   return LATTE_OK;
 }

@@ -1,0 +1,198 @@
+"""A/B of two builds of the library on the engine's fused loops: every loop on fixed seeds, sha256 of every returned tensor.
+
+  python tools/chain_ab.py --out profiles/chain_refactor_head.json                                   # the tree's library
+  LATTE_AMD_LIB=<other build>.so python tools/chain_ab.py --out profiles/chain_refactor_parent.json  # another build
+  python tools/chain_ab.py --compare profiles/chain_refactor_parent.json profiles/chain_refactor_head.json
+
+Builds nothing: it loads LATTE_AMD_LIB or latte_amd/lib/liblatte_amd.so.  Models: the tiny_classcond and tiny_uncond golden fixtures
+(f16 operands, max_batch 4) and the tiny text-to-video pipeline of tests/test_t2v_schedulers.py.  Cases:
+  sample loop   DDPM, DDIM eta 0 and eta 0.5 with both trails, noise drawn by the engine (option "seed"); on the class-conditional model
+                guided at batch 4 over 70 steps (bu = 4: the conditioning chunk holds 64), once whole and once as two segments
+  invert loop   the same range, whole and split, both trails
+  bpd loop      given noise and drawn noise, both models
+  plan loop     Euler, Euler-ancestral (drawn noise), Heun, DPM-Solver++ on create_diffusion("6"), guided and plain, with the trail; Heun
+                on create_diffusion("40") (79 rows, guided batch 4).  Euler / Heun scale the model input.
+  T2V           latte_t2v_guided_linear_loop for the four methods and the guided DDIM loop, through LattePipeline
+After every class-engine case the option "seed" is read back and one further engine-drawn DDPM step is hashed, so the Philox offset
+must have advanced identically.  Two runs agree when every hash agrees."""
+import argparse
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import latte_amd  # noqa: E402
+from latte_amd._lib import check, load_library, ptr, stream_ptr  # noqa: E402
+
+DDPM, DDIM = 0, 1
+LINEAR = ["euler", "euler_a", "heun", "dpmsolver++"]
+CFG = 4.0
+
+
+def sha(t):
+    """sha256 of the tensor's bytes; a tensor with a non-finite element is marked, so that a chain that left the fp32 range shows"""
+    torch.cuda.synchronize()
+    t = t.detach().cpu().contiguous()
+    return ("" if bool(torch.isfinite(t).all()) else "nonfinite:") + hashlib.sha256(t.numpy().tobytes()).hexdigest()
+
+
+class ClassEngine:
+    def __init__(self, name):
+        from _util import engine_model, load_golden_model
+        kw, sd, _ = load_golden_model(name)
+        self.name, self.m = name, engine_model(kw, sd, "f16", max_batch=4)
+        self.shape = (kw["num_frames"], 4, kw["input_size"], kw["input_size"])
+        self.classes = kw["num_classes"] if kw["extras"] == 2 else None
+        self.lib = load_library()
+
+    def inputs(self, B, guided, seed):
+        g = torch.Generator("cpu").manual_seed(seed)
+        half = B // 2 if guided else B
+        x = torch.randn((half,) + self.shape, generator=g)
+        y = None
+        if self.classes is not None:
+            y = torch.randint(0, self.classes, (half,), generator=g)
+            if guided:
+                y = torch.cat([y, torch.full_like(y, self.classes)])
+            y = y.cuda()
+        if guided:
+            x = torch.cat([x, x])
+        return x.cuda().contiguous(), y
+
+    def tail(self, rec, B, guided, d, y):
+        """option "seed" + one further engine-drawn DDPM step: the continuation of the noise stream"""
+        rec["seed_after"] = self.m.get_engine_option("seed", batch=B, guided=guided)
+        x = torch.full((B,) + self.shape, 0.25, device="cuda")
+        check(self.lib.latte_sample_loop_ex(self.m.engine(B, guided), d._h, DDPM, 0.0, 1, int(guided), CFG, ptr(x), ptr(y), B, 1, 1, None,
+                                            None, None, stream_ptr()))
+        rec["next_drawn_step"] = sha(x)
+
+    def sample(self, d, method, eta, B, guided, segments, seed, invert=False):
+        x, y = self.inputs(B, guided, seed)
+        self.m.set_engine_option("seed", seed, batch=B, guided=guided)
+        eng, rec = self.m.engine(B, guided), {}
+        n = sum(hi - lo + 1 for lo, hi in segments)
+        trail_s = torch.empty((n,) + tuple(x.shape), device="cuda")
+        trail_0 = torch.empty_like(trail_s)
+        k = 0
+        for lo, hi in segments:          # descending chains run hi ... lo, the inversion lo ... hi
+            if invert:
+                check(self.lib.latte_invert_loop(eng, d._h, 1, int(guided), CFG, ptr(x), ptr(y), B, lo, hi, ptr(trail_s[k:]), ptr(trail_0[k:]),
+                                                 stream_ptr()))
+            else:
+                check(self.lib.latte_sample_loop_ex(eng, d._h, method, eta, 1, int(guided), CFG, ptr(x), ptr(y), B, hi, lo, None,
+                                                    ptr(trail_s[k:]), ptr(trail_0[k:]), stream_ptr()))
+            k += hi - lo + 1
+        rec.update(x=sha(x), trail_sample=sha(trail_s), trail_x0=sha(trail_0))
+        self.tail(rec, B, guided, d, y)
+        return rec
+
+    def bpd(self, d, B, given, seed):
+        x, y = self.inputs(B, False, seed)
+        self.m.set_engine_option("seed", seed, batch=B)
+        noise = None
+        if given:
+            noise = torch.randn((d.num_timesteps,) + tuple(x.shape), generator=torch.Generator("cpu").manual_seed(seed + 1)).cuda()
+        out = d.calc_bpd_loop(self.m.forward, x, clip_denoised=True, model_kwargs={} if y is None else dict(y=y), noise=noise)
+        rec = {k: sha(v) for k, v in out.items()}
+        self.tail(rec, B, False, d, y)
+        return rec
+
+    def plan(self, d, method, B, guided, seed):
+        x, y = self.inputs(B, guided, seed)
+        self.m.set_engine_option("seed", seed, batch=B, guided=guided)
+        mk = {} if y is None else dict(y=y)
+        if guided:
+            mk["cfg_scale"] = CFG
+        fn = self.m.forward_with_cfg if guided else self.m.forward
+        trail = [r["sample"] for r in d.linear_sample_loop_progressive(fn, x.shape, x, method=method, model_kwargs=mk)]
+        rec = {"x": sha(trail[-1]), "trail_sample": sha(torch.stack(trail)), "n_evals": len(trail)}
+        self.tail(rec, B, guided, d, y)
+        return rec
+
+
+def class_cases(out):
+    d80, d10, d6, d40 = (latte_amd.create_diffusion(s) for s in ("80", "10", "6", "40"))
+    cc, un = ClassEngine("tiny_classcond"), ClassEngine("tiny_uncond")
+    whole, split = [(5, 74)], [(40, 74), (5, 39)]                 # 70 steps at bu = 4: two conditioning chunks
+    for tag, method, eta in (("ddpm", DDPM, 0.0), ("ddim_eta0", DDIM, 0.0), ("ddim_eta0.5", DDIM, 0.5)):
+        out[f"sample::{tag}::classcond::guided4::whole"] = cc.sample(d80, method, eta, 4, True, whole, 11)
+        out[f"sample::{tag}::classcond::guided4::split"] = cc.sample(d80, method, eta, 4, True, split, 11)
+        out[f"sample::{tag}::classcond::plain3"] = cc.sample(d10, method, eta, 3, False, [(0, 9)], 12)
+        out[f"sample::{tag}::uncond::plain2"] = un.sample(d10, method, eta, 2, False, [(0, 9)], 13)
+    out["invert::classcond::guided4::whole"] = cc.sample(d80, None, 0.0, 4, True, whole, 14, invert=True)
+    out["invert::classcond::guided4::split"] = cc.sample(d80, None, 0.0, 4, True, [(5, 39), (40, 74)], 14, invert=True)
+    out["invert::uncond::plain2"] = un.sample(d10, None, 0.0, 2, False, [(0, 9)], 15, invert=True)
+    for e in (cc, un):
+        for given in (True, False):
+            out[f"bpd::{e.name}::{'given' if given else 'drawn'}"] = e.bpd(d10, 3, given, 16)
+    for method in LINEAR:
+        out[f"plan::{method}::classcond::guided4"] = cc.plan(d6, method, 4, True, 17)
+        out[f"plan::{method}::classcond::plain3"] = cc.plan(d6, method, 3, False, 18)
+        out[f"plan::{method}::uncond::plain2"] = un.plan(d6, method, 2, False, 19)
+    out["plan::heun::classcond::guided4::40"] = cc.plan(d40, "heun", 4, True, 20)
+
+
+def t2v_cases(out):
+    from latte_amd.schedulers import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler,
+                                      HeunDiscreteScheduler)
+    z = np.load(os.path.join(ROOT, "tests", "golden", "tiny_t2v.npz"))
+    cfg = json.loads(bytes(z["cfg_json"]).decode())
+    sd = {k[4:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("sd::")}
+    m = latte_amd.LatteT2V(num_attention_heads=cfg["num_attention_heads"], attention_head_dim=cfg["attention_head_dim"],
+                           in_channels=cfg["in_channels"], out_channels=cfg["out_channels"], num_layers=cfg["num_layers"],
+                           sample_size=cfg["sample_size"], patch_size=cfg["patch_size"], cross_attention_dim=cfg["cross_attention_dim"],
+                           caption_channels=cfg["caption_channels"], video_length=cfg["video_length"], compute_dtype="f16", max_batch=4)
+    m.load_state_dict(sd)
+    pipe = latte_amd.LattePipeline(transformer=m, scheduler=DDIMScheduler()).to("cuda")
+    g = torch.Generator("cpu").manual_seed(9)
+    pe, ne = (torch.randn(2, 6, cfg["caption_channels"], generator=g) for _ in range(2))
+    lat = torch.randn(2, 4, cfg["video_length"], cfg["sample_size"], cfg["sample_size"], generator=g)
+    classes = {"ddim": DDIMScheduler, "euler": EulerDiscreteScheduler, "euler_a": EulerAncestralDiscreteScheduler,
+               "heun": HeunDiscreteScheduler, "dpmsolver++": DPMSolverMultistepScheduler}
+    for name, cls in classes.items():
+        pipe.scheduler = cls()
+        video = pipe(prompt_embeds=pe, negative_prompt_embeds=ne, num_inference_steps=6, guidance_scale=4.5, latents=lat,
+                     generator=torch.Generator("cpu").manual_seed(21), output_type="latents").video
+        out[f"t2v::{name}"] = {"latents": sha(video)}
+
+
+def compare(a, b):
+    ra, rb = (json.load(open(p))["cases"] for p in (a, b))
+    bad = sorted(k for k in set(ra) | set(rb) if ra.get(k) != rb.get(k))
+    print(f"{len(ra)} / {len(rb)} cases, {len(bad)} differ" + "".join("\n  " + k for k in bad))
+    return 1 if bad or not ra else 0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    ap.add_argument("--compare", nargs=2, metavar="JSON")
+    a = ap.parse_args()
+    if a.compare:
+        raise SystemExit(compare(*a.compare))
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/chain_ab.py needs an MI355X")
+    torch.set_grad_enabled(False)
+    cases = {}
+    class_cases(cases)
+    t2v_cases(cases)
+    result = {"what": "sha256 of every tensor the engine's fused loops return, fixed seeds (tools/chain_ab.py)",
+              "library": "LATTE_AMD_LIB" if os.environ.get("LATTE_AMD_LIB") else "tree", "version": load_library().latte_version().decode(),
+              "device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName, "cases": cases}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(f"{len(cases)} cases -> {a.out}")
+
+
+if __name__ == "__main__":
+    main()
