@@ -338,6 +338,29 @@ int latte_trainer_begin(latte_trainer_t* e, const latte_schedule_t* s, int loss_
 int latte_trainer_num_stages(const latte_trainer_t* e);
 int latte_trainer_stage_range(const latte_trainer_t* e, int stage, int64_t* offset, int64_t* numel);
 int latte_trainer_backward_stage(latte_trainer_t* e, int stage, void* stream);
+/* Custom losses: the same forward and the same staged backward with the loss between them in the CALLER's hands (LatteTrainer.forward
+ * hangs the pair on torch.autograd).  States of a custom pass: idle -> [forward] -> awaiting seed -> [seed] -> backward in flight ->
+ * [stage 0 .. num_stages - 1] -> done (input gradient available) -> idle at the next forward / begin.
+ * latte_trainer_forward: the plain-mode forward with saved activations of model(x, t_model, y).  x fp32 [batch, F, C, H, W], the model
+ * input, ALREADY noised (copied into the trainer: the patch embed's weight gradient reads it at the last stage); t_model int64 [batch]
+ * device, the ORIGINAL timesteps the model sees (timestep_map[t] of a respaced schedule), not respaced indices; y labels after dropout
+ * or NULL (extras == 1), alive until the last stage; model_out fp32 [batch, F, C_out, H, W].  A forward that no seed follows is simply
+ * abandoned: the next latte_trainer_forward / latte_trainer_begin starts over.  Refused (LATTE_ERR_STATE): while a step is in flight
+ * (between a begin / seed and the last stage), on a joint trainer inside its image pass, batch > max_batch, buffers unbound.
+ * latte_trainer_seed: d_model_out fp32, model_out's shape: the caller's gradient of the SUM it wants minimised (for a mean over the
+ * batch: 1 / batch is the caller's).  The trainer divides it by "loss_divisor" and multiplies it by the live loss scale -- exactly
+ * what it does to the built-in loss's gradient -- so accumulation and loss scaling work unchanged; the stages and
+ * latte_trainer_stage_range then run as after latte_trainer_begin, in the current assign / accumulate mode.  One seed per forward:
+ * a second one is refused.  f16 operands: an arbitrary seed is multiplied by 2^14 (the default scale) on its way into f16 operands;
+ * a seed orders of magnitude away from the built-in loss's 2 (pred - target) / numel needs "loss_scale" set accordingly, or bf16.
+ * latte_trainer_input_grad: after the LAST stage of a pass that latte_trainer_seed started and before the next forward / begin /
+ * optimizer step (which re-packs the weights and may change the loss scale; it also abandons a forward that awaits its seed):
+ * dx_out fp32 [batch, F, C, H, W] = d / d x of the seeded sum (divided by "loss_divisor" like every gradient), already out of the
+ * loss-scaled domain.  One pass over the token gradient (csrc/train_fin.hip: patch_embed_dgrad_kernel). */
+int latte_trainer_forward(latte_trainer_t* e, const float* x, const int64_t* t_model, const int64_t* y, int batch, float* model_out,
+                          void* stream);
+int latte_trainer_seed(latte_trainer_t* e, const float* d_model_out, void* stream);
+int latte_trainer_input_grad(latte_trainer_t* e, float* dx_out, void* stream);
 /* Joint image-video training (train_with_img.py:214-241, models/latte_img.py:361-399, `use_image_num: N` of the *_img_train.yaml
  * configs): every sample carries F video frames and N single image frames.  LatteIMG has exactly Latte's parameters, its image
  * frames never meet the video frames (spatial blocks treat every frame alone, temporal blocks see x[:, :F]) and mean_flat runs over

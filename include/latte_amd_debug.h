@@ -281,6 +281,12 @@ int latte_debug_narrow_outer(const float* nar, int P, const void* wide, int wide
                              float* nsum_out, float* wsum_out, float* ws, int64_t ws_floats, int dtype, const float* inv_scale_dev,
                              int accumulate, void* stream);
 int latte_debug_narrow_dx(const float* nar, int P, const float* W, int D, int M, void* out, int dtype, void* stream);
+/* The patch embed's input gradient (latte_trainer_input_grad): out [BF, C, G p, G p] = dx [BF G^2, D] W [D, C p^2] scattered to the
+ * pixels, the inverse of im2col_patch; everything fp32.  inv_scale_dev: optional DEVICE float, the loss scale -- the result is
+ * multiplied by 1 / *inv_scale_dev.  C p^2 a multiple of 4 up to 64 (and D % 4 == 0, D <= 1280, the weight inside 96 KiB of LDS):
+ * one wave per token row, dx and W 16-byte aligned; otherwise a plain product + scatter through a temporary (synchronises). */
+int latte_debug_patch_embed_dgrad(const float* dx, const float* W, float* out, int BF, int G, int p, int C, int D, const float* inv_scale_dev,
+                                  void* stream);
 /* The half operand copies of fp32 [N, K] weights: wn = half [N, K], wt = half [K, N].  pack_weights: every linear of every block in one
  * launch -- HOST arrays w_ptrs / wn_ptrs / wt_ptrs [blocks * 4] (block-major), the four linears' shapes N[4], K[4] shared by all blocks;
  * builds the device table and the tile plan as the trainer does, synchronises and frees the table.  pack_weight: one matrix, one launch

@@ -108,6 +108,9 @@ PROTOTYPES = {
     "latte_trainer_num_stages": (c_int, [c_void]),
     "latte_trainer_stage_range": (c_int, [c_void, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "latte_trainer_backward_stage": (c_int, [c_void, c_int, c_void]),
+    "latte_trainer_forward": (c_int, [c_void, c_void, c_void, c_void, c_int, c_void, c_void]),
+    "latte_trainer_seed": (c_int, [c_void, c_void, c_void]),
+    "latte_trainer_input_grad": (c_int, [c_void, c_void, c_void]),
     "latte_trainer_optimizer_step": (c_int, [c_void, c_f32, c_f32, c_f32, c_f32, c_f32, c_int, c_f32, c_int, c_f32, c_void, c_void]),
     "latte_trainer_set_option": (c_int, [c_void, c_char, ctypes.c_double]),
     "latte_trainer_scaler_state": (c_int, [c_void, ctypes.POINTER(ctypes.c_double)]),
@@ -239,6 +242,7 @@ PROTOTYPES = {
     "latte_debug_narrow_outer": (c_int, [c_void, c_int, c_void, c_int, c_int, c_int, c_void, c_i64, c_i64, c_void, c_void, c_void, c_i64,
                                          c_int, c_void, c_int, c_void]),
     "latte_debug_narrow_dx": (c_int, [c_void, c_int, c_void, c_int, c_int, c_void, c_int, c_void]),
+    "latte_debug_patch_embed_dgrad": (c_int, [c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_void, c_void]),
     "latte_debug_pack_weights": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_void]),
     "latte_debug_pack_weight": (c_int, [c_void, c_void, c_void, c_int, c_int, c_int, c_void]),
     "latte_debug_loss_grad": (c_int, [c_void, c_int, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void,

@@ -371,6 +371,11 @@ int launch_narrow_outer(const float* nar, int P, const void* wide, int wide_half
                         float* nsum_out, float* wsum_out, float* ws, int dtype, const float* inv_scale_dev, hipStream_t st,
                         int accumulate = 0);
 int launch_narrow_dx(const float* nar, int P, const float* W, int D, int M, half_t* out, int dtype, hipStream_t st);
+// custom losses (train_fin.hip): the caller's seed into the backward's domain, the patch embed's input gradient
+int launch_seed_scale(const float* in, float* out, float divisor, const float* scale_dev, size_t n, hipStream_t st);
+bool patch_embed_dgrad_fast(int p, int C, int D);
+int launch_patch_embed_dgrad(const float* dx, const float* W, float* out, int BF, int G, int p, int C, int D, float* ws,
+                             const float* inv_scale_dev, hipStream_t st);
 struct PackDesc { const float* w; half_t* wn; half_t* wt; int N, K; };
 struct PackPlan { int tiles_per_block; int tile0[4]; };
 int launch_pack_weights(const PackDesc* descs_dev, int blocks, const PackPlan& pl, int dtype, hipStream_t st);

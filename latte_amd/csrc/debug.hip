@@ -626,6 +626,19 @@ int latte_debug_narrow_dx(const float* nar, int P, const float* W, int D, int M,
   return launch_narrow_dx(nar, P, W, D, M, (half_t*)out, dtype, (hipStream_t)stream);
 }
 
+int latte_debug_patch_embed_dgrad(const float* dx, const float* W, float* out, int BF, int G, int p, int C, int D, const float* inv_scale_dev,
+                                  void* stream) {
+  if (!dx || !W || !out || bad_patch_shape(BF, G, p, C) || D < 1) return fail(LATTE_ERR_INVALID, "patch_embed_dgrad: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  if (patch_embed_dgrad_fast(p, C, D)) return launch_patch_embed_dgrad(dx, W, out, BF, G, p, C, D, nullptr, inv_scale_dev, st);
+  float* ws = nullptr;   // the wide form's [BF G^2][C p^2] product
+  LATTE_HIP(hipMalloc((void**)&ws, (size_t)BF * G * G * C * p * p * sizeof(float)));
+  const int rc = launch_patch_embed_dgrad(dx, W, out, BF, G, p, C, D, ws, inv_scale_dev, st);
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(ws);
+  return rc;
+}
+
 int latte_debug_pack_weights(const float* const* w_ptrs, const int* N, const int* K, void* const* wn_ptrs, void* const* wt_ptrs, int blocks,
                              int dtype, void* stream) {
   if (!w_ptrs || !N || !K || !wn_ptrs || !wt_ptrs || blocks < 1) return fail(LATTE_ERR_INVALID, "pack_weights: bad arguments");

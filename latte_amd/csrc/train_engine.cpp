@@ -104,6 +104,10 @@ struct latte_trainer {
   int64_t* jt_i = nullptr;
   int cur_batch = 0, next_stage = 1 << 30;   // step in flight: batch, labels (caller keeps them alive), next backward stage
   const int64_t* cur_y = nullptr;
+  // Custom loss (latte_trainer_forward / _seed / _input_grad): 0 = no custom pass, 1 = forward done, awaiting the caller's seed,
+  // 2 = seeded (its stages run, or have run: the token gradient e->dx of the last one is what latte_trainer_input_grad reads)
+  int custom = 0, fwd_batch = 0;
+  const int64_t* fwd_y = nullptr;
   DeviceArena arena;
 };
 
@@ -393,29 +397,16 @@ int latte_trainer_sync_weights(latte_trainer_t* e, void* stream) {
 }  // extern "C"
 
 namespace {
-// one pass in the trainer's current run mode (run_F frames per sample, temporal blocks on / off, loss weight); batch_cap: samples the
-// per-sample buffers hold in that mode
-int begin_impl(latte_trainer_t* e, const latte_schedule_t* s, int loss_type, const float* x_start, const float* noise, const int64_t* t,
-               const int64_t* y, int batch, int batch_cap, float* terms_out, float* model_out_copy, void* stream) {
-  if (!e || !s || !x_start || !noise || !t || !terms_out) return fail(LATTE_ERR_INVALID, "train step: null argument");
-  if (!e->Pm) return fail(LATTE_ERR_STATE, "train step: bind the parameter buffers first");
-  if (batch <= 0 || batch > batch_cap) return fail(LATTE_ERR_STATE, "train step: batch exceeds max_batch");
-  if (loss_type != 0 && loss_type != 1) return fail(LATTE_ERR_INVALID, "train step: loss_type must be 0 (MSE) or 1 (RESCALED_MSE); the KL losses train no mean head (gaussian_diffusion.py:741-752)");
-  if (s->mean_type != 0) return fail(LATTE_ERR_INVALID, "train step: only the epsilon-prediction models of train.py:92 are supported");
-  if ((s->var_type == 0) != (e->cfg.learn_sigma != 0)) return fail(LATTE_ERR_INVALID, "train step: schedule / model disagree on learn_sigma");
-  const auto& c = e->cfg;
-  if (c.extras == 2 && !y) return fail(LATTE_ERR_INVALID, "train step: class-conditional model needs y");
-  hipStream_t st = (hipStream_t)stream;
+// The three parts of a pass in the trainer's current run mode (run_F frames per sample, temporal blocks on / off, loss weight):
+// q_sample + timestep gather, the forward with saved activations, the loss terms + seed.  begin_impl runs them in a row; the custom
+// loss entry points (latte_trainer_forward / _seed) run the middle one and take the seed from the caller.
+
+// ---- x_t = q_sample(x_start, t, noise), original timesteps of the respaced t
+int qsample_part(latte_trainer_t* e, const latte_schedule_t* s, const float* tab, const float* x_start, const float* noise, const int64_t* t,
+                 int B, hipStream_t st) {
   int rc;
-  if (!e->weights_synced && (rc = latte_trainer_sync_weights(e, stream))) return rc;
-  const int D = e->D, T = e->T, F = e->run_F, Hm = e->Hm, B = batch, dt = e->dt, nmod = e->nmod;
-  const bool temporal = e->run_temporal != 0;
-  const int M = B * F * T, rps = F * T;
   const int hw = e->H * e->H;
-  const float* tab = nullptr;
-  if ((rc = schedule_device_tables(s, &tab, st))) return rc;
-  // ---- x_t, original timesteps
-  if ((rc = launch_q_sample(tab, s->num_timesteps, x_start, noise, t, B, (size_t)F * e->Cin * hw, e->x_t, st))) return rc;
+  if ((rc = launch_q_sample(tab, s->num_timesteps, x_start, noise, t, B, (size_t)e->run_F * e->Cin * hw, e->x_t, st))) return rc;
   if (e->tmap_of != s || e->tmap_n != s->num_timesteps) {
     if (e->tmap_n < s->num_timesteps) { if ((rc = e->arena.alloc(&e->tmap_dev, (size_t)s->num_timesteps, false))) return rc; }
     LATTE_HIP(hipMemcpyAsync(e->tmap_dev, s->timestep_map.data(), sizeof(int64_t) * s->num_timesteps, hipMemcpyHostToDevice, st));
@@ -423,8 +414,17 @@ int begin_impl(latte_trainer_t* e, const latte_schedule_t* s, int loss_type, con
     e->tmap_n = s->num_timesteps;
     e->tmap_of = s;
   }
-  if ((rc = launch_gather_i64(e->tmap_dev, t, e->t_orig, B, st))) return rc;
+  return launch_gather_i64(e->tmap_dev, t, e->t_orig, B, st);
+}
 
+// ---- forward of model(e->x_t, e->t_orig, y) with saved activations -> e->model_out (and model_out_copy)
+int forward_part(latte_trainer_t* e, const int64_t* y, int batch, float* model_out_copy, hipStream_t st) {
+  const auto& c = e->cfg;
+  int rc;
+  const int D = e->D, T = e->T, F = e->run_F, Hm = e->Hm, B = batch, dt = e->dt, nmod = e->nmod;
+  const bool temporal = e->run_temporal != 0;
+  const int M = B * F * T, rps = F * T;
+  const int hw = e->H * e->H;
   // ================================================================ forward
   // conditioning (latte.py:119-123,332-348): temb_pre = W0 freq(t) + b0; c = W2 SiLU(temb_pre) + b2 (+ y_emb); mod = adaLN(SiLU(c))
   if ((rc = launch_tfreq(e->t_orig, e->tfreq, B, st))) return rc;
@@ -492,6 +492,42 @@ int begin_impl(latte_trainer_t* e, const latte_schedule_t* s, int loss_type, con
                                e->Cout, e->H, st))) return rc;
   if (model_out_copy)
     LATTE_HIP(hipMemcpyAsync(model_out_copy, e->model_out, sizeof(float) * (size_t)B * F * e->Cout * hw, hipMemcpyDeviceToDevice, st));
+  return LATTE_OK;
+}
+
+// ---- the backward's start state behind a seed in e->dmodel_out
+int arm_backward(latte_trainer_t* e, const int64_t* y, int B, hipStream_t st) {
+  LATTE_HIP(hipMemsetAsync(e->dc, 0, sizeof(float) * (size_t)B * e->D, st));   // d SiLU(c), summed over the adaLN linears by the stages
+  // temporal blocks off: their stages write no dmod rows, and the last stage contracts ALL rows with the adaLN weights -- what the
+  // previous pass left there must not reach the t / y embedders' gradients
+  if (!e->run_temporal) LATTE_HIP(hipMemsetAsync(e->dmod, 0, sizeof(float) * (size_t)B * e->nmod, st));
+  e->cur_batch = B;
+  e->cur_y = y;
+  e->next_stage = 0;
+  return LATTE_OK;
+}
+
+// one pass; batch_cap: samples the per-sample buffers hold in the current run mode
+int begin_impl(latte_trainer_t* e, const latte_schedule_t* s, int loss_type, const float* x_start, const float* noise, const int64_t* t,
+               const int64_t* y, int batch, int batch_cap, float* terms_out, float* model_out_copy, void* stream) {
+  if (!e || !s || !x_start || !noise || !t || !terms_out) return fail(LATTE_ERR_INVALID, "train step: null argument");
+  if (!e->Pm) return fail(LATTE_ERR_STATE, "train step: bind the parameter buffers first");
+  if (batch <= 0 || batch > batch_cap) return fail(LATTE_ERR_STATE, "train step: batch exceeds max_batch");
+  if (loss_type != 0 && loss_type != 1) return fail(LATTE_ERR_INVALID, "train step: loss_type must be 0 (MSE) or 1 (RESCALED_MSE); the KL losses train no mean head (gaussian_diffusion.py:741-752)");
+  if (s->mean_type != 0) return fail(LATTE_ERR_INVALID, "train step: only the epsilon-prediction models of train.py:92 are supported");
+  if ((s->var_type == 0) != (e->cfg.learn_sigma != 0)) return fail(LATTE_ERR_INVALID, "train step: schedule / model disagree on learn_sigma");
+  const auto& c = e->cfg;
+  if (c.extras == 2 && !y) return fail(LATTE_ERR_INVALID, "train step: class-conditional model needs y");
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if (!e->weights_synced && (rc = latte_trainer_sync_weights(e, stream))) return rc;
+  const int F = e->run_F, B = batch;
+  const int hw = e->H * e->H;
+  e->custom = 0;
+  const float* tab = nullptr;
+  if ((rc = schedule_device_tables(s, &tab, st))) return rc;
+  if ((rc = qsample_part(e, s, tab, x_start, noise, t, B, st))) return rc;
+  if ((rc = forward_part(e, y, B, model_out_copy, st))) return rc;
 
   // ================================================================ loss values and d loss / d model_output
   float vb_scale = 1.0f;
@@ -501,15 +537,7 @@ int begin_impl(latte_trainer_t* e, const latte_schedule_t* s, int loss_type, con
   if ((rc = launch_loss_grad(tab, s->num_timesteps, s->mean_type, s->var_type, x_start, e->x_t, noise, e->model_out, t, B, F, e->Cin, hw,
                              vb_scale, e->dmodel_out, st, e->loss_divisor * e->run_weight))) return rc;
   if (scaling_active(e) && (rc = launch_scale_f32_dev(e->dmodel_out, e->scaler, 0, (size_t)B * F * e->Cout * hw, st))) return rc;
-
-  LATTE_HIP(hipMemsetAsync(e->dc, 0, sizeof(float) * (size_t)B * D, st));   // d SiLU(c), summed over the adaLN linears by the stages
-  // temporal blocks off: their stages write no dmod rows, and the last stage contracts ALL rows with the adaLN weights -- what the
-  // previous pass left there must not reach the t / y embedders' gradients
-  if (!temporal) LATTE_HIP(hipMemsetAsync(e->dmod, 0, sizeof(float) * (size_t)B * nmod, st));
-  e->cur_batch = B;
-  e->cur_y = y;
-  e->next_stage = 0;
-  return LATTE_OK;
+  return arm_backward(e, y, B, st);
 }
 
 // the trainer back in the plain run mode (an image pass that was abandoned half way included)
@@ -641,7 +669,7 @@ int latte_trainer_set_option(latte_trainer_t* e, const char* name, double value)
     return upload_scaler(e, 2);
   }
   if (std::string(name) == "fuse_small") {   // 0: the separate finalize / column-sum / adaLN launches of rounds 2 - 6, 1: train_fin.hip (default)
-    if (e->next_stage <= e->cfg.depth + 1) return fail(LATTE_ERR_STATE, "fuse_small: a step is in flight");
+    if (e->next_stage <= e->cfg.depth + 1 || e->custom == 1) return fail(LATTE_ERR_STATE, "fuse_small: a step is in flight");
     e->fuse_small = value != 0.0 ? 1 : 0;
     return LATTE_OK;
   }
@@ -870,12 +898,59 @@ int latte_trainer_forward_backward_joint(latte_trainer_t* e, const latte_schedul
   return rc;
 }
 
+// ---- custom losses: the forward alone, the caller's seed, the input gradient (include/latte_amd.h)
+int latte_trainer_forward(latte_trainer_t* e, const float* x, const int64_t* t_model, const int64_t* y, int batch, float* model_out,
+                          void* stream) {
+  if (!e || !x || !t_model || !model_out) return fail(LATTE_ERR_INVALID, "trainer_forward: null argument");
+  if (!e->Pm) return fail(LATTE_ERR_STATE, "trainer_forward: bind the parameter buffers first");
+  if (e->joint_saved_acc >= 0) return fail(LATTE_ERR_STATE, "trainer_forward: the image pass of a joint micro-batch is in flight");
+  if (e->next_stage <= e->cfg.depth + 1) return fail(LATTE_ERR_STATE, "trainer_forward: a step is in flight");
+  if (batch <= 0 || batch > e->max_batch) return fail(LATTE_ERR_STATE, "trainer_forward: batch exceeds max_batch");
+  if (e->cfg.extras == 2 && !y) return fail(LATTE_ERR_INVALID, "trainer_forward: class-conditional model needs y");
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if (!e->weights_synced && (rc = latte_trainer_sync_weights(e, stream))) return rc;
+  plain_mode(e);
+  e->custom = 0;
+  // the patch embed's weight gradient reads x from e->x_t at the last stage, the forward its timesteps from e->t_orig
+  LATTE_HIP(hipMemcpyAsync(e->x_t, x, sizeof(float) * (size_t)batch * e->F * e->Cin * e->H * e->H, hipMemcpyDeviceToDevice, st));
+  LATTE_HIP(hipMemcpyAsync(e->t_orig, t_model, sizeof(int64_t) * (size_t)batch, hipMemcpyDeviceToDevice, st));
+  if ((rc = forward_part(e, y, batch, model_out, st))) return rc;
+  e->fwd_batch = batch;
+  e->fwd_y = y;
+  e->custom = 1;
+  return LATTE_OK;
+}
+
+int latte_trainer_seed(latte_trainer_t* e, const float* d_model_out, void* stream) {
+  if (!e || !d_model_out) return fail(LATTE_ERR_INVALID, "trainer_seed: null argument");
+  if (e->custom != 1) return fail(LATTE_ERR_STATE, "trainer_seed: one seed per latte_trainer_forward (none is awaiting its seed)");
+  hipStream_t st = (hipStream_t)stream;
+  const int B = e->fwd_batch;
+  int rc;
+  // what launch_loss_grad + the scale pass leave for the built-in loss: the gradient of the sum / loss_divisor, in the loss-scaled domain
+  if ((rc = launch_seed_scale(d_model_out, e->dmodel_out, e->loss_divisor, scaling_active(e) ? e->scaler : nullptr,
+                              (size_t)B * e->F * e->Cout * e->H * e->H, st))) return rc;
+  e->custom = 2;
+  return arm_backward(e, e->fwd_y, B, st);
+}
+
+int latte_trainer_input_grad(latte_trainer_t* e, float* dx_out, void* stream) {
+  if (!e || !dx_out) return fail(LATTE_ERR_INVALID, "trainer_input_grad: null argument");
+  if (e->custom != 2 || e->next_stage != e->cfg.depth + 2)
+    return fail(LATTE_ERR_STATE, "trainer_input_grad: valid after the last backward stage of a pass that latte_trainer_seed started");
+  // e->dx is the gradient of the patch embed's output (block 0's LayerNorm backward left it), e->pix is free after the last stage
+  return launch_patch_embed_dgrad(e->dx, P_(e, "x_embedder.proj.weight"), dx_out, e->cur_batch * e->F, e->G, e->cfg.patch_size, e->Cin, e->D,
+                                  e->pix, scaling_active(e) ? e->scaler : nullptr, (hipStream_t)stream);
+}
+
 // clip_grad_norm_ (utils.py:72-117) + AdamW (train.py:127) + update_ema (utils.py:191-200) on the bound flat buffers, then the
 // half operand copies are re-packed.  norm_out: optional device float[2] = {total gradient norm, applied clip coefficient}.
 int latte_trainer_optimizer_step(latte_trainer_t* e, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                                  float clip_max_norm, int clip, float ema_decay, float* norm_out, void* stream) {
   if (!e || !e->Pm) return fail(LATTE_ERR_STATE, "optimizer_step: bind the parameter buffers first");
   if (step < 0) return fail(LATTE_ERR_INVALID, "optimizer_step: step counts from 1 (0: the trainer's own count of applied updates)");
+  e->custom = 0;   // the weights and perhaps the loss scale change: a forward awaiting its seed is abandoned, the input gradient's time is over
   hipStream_t st = (hipStream_t)stream;
   int rc;
   if ((rc = launch_grad_norm(e->Gr, (size_t)e->total, e->sumsq, clip_max_norm, clip, e->stats, e->scaler, st))) return rc;

@@ -14,7 +14,9 @@
 //   pack_weights_kernel     the half operand copies of every block weight ([N, K] and [K, N]) in one launch from a device table
 //
 // Every reduction runs in a fixed order (deterministic); nothing here is on the inference path.
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
 
 #include "common.h"
 #include "device_util.h"
@@ -314,7 +316,140 @@ __global__ void __launch_bounds__(320) narrow_dx_kernel(const float* __restrict_
   }
 }
 
+// ---------------------------------------------------------------------------------------------- patch embed: input gradient
+// dpix[m][j] = sum_d dx[m][d] W[d][j], j = (c, pp, q) < KPE = C p^2 (x_embedder.proj.weight order), scattered to [BF, C, H, W]: the
+// inverse of im2col_patch.  One wave per token row: lane l owns the 16-byte chunks l, l + 64, ... of the row (all loaded up front),
+// the fp32 weight waits in LDS in the order the lanes read it -- float4 slot ((k 4 + i) KQ + jq) 64 + l holds W[(k 64 + l) 4 + i][4 jq ..],
+// so that a wave's ds_read_b128 covers 64 consecutive slots: no bank conflict --, every lane keeps KPE partial sums, and a
+// reduce-scatter over the lanes (KP - 1 + log2(64 / KP) shuffles) leaves sum j on lane j (64 / KP).
+constexpr int PD_WAVES = 8;
+constexpr int PD_NK = 5;                     // 16-byte chunks per lane: D <= 1280
+constexpr int PD_LDS_MAX = 96 * 1024;
+template <int N, int OFF>
+__device__ __forceinline__ void reduce_scatter(float* a, int lane) {
+  if constexpr (N > 1) {
+    constexpr int h = N / 2;
+    const bool up = (lane & OFF) != 0;       // the upper lane of a pair keeps the upper half of the sums
+#pragma unroll
+    for (int i = 0; i < h; ++i) {
+      const float send = up ? a[i] : a[i + h];
+      const float keep = up ? a[i + h] : a[i];
+      a[i] = keep + __shfl_xor(send, OFF);
+    }
+    if constexpr (OFF > 1) reduce_scatter<h, OFF / 2>(a, lane);
+  } else {
+    a[0] += __shfl_xor(a[0], OFF);
+    if constexpr (OFF > 1) reduce_scatter<1, OFF / 2>(a, lane);
+  }
+}
+// out index of element j of token m
+__device__ __forceinline__ size_t patch_pixel(int m, int j, int G, int p, int C) {
+  const int H = G * p;
+  const int gw = m % G, gh = (m / G) % G, bf = m / (G * G);
+  const int q = j % p, pp = (j / p) % p, c = j / (p * p);
+  return (((size_t)bf * C + c) * H + gh * p + pp) * H + gw * p + q;
+}
+template <int KP>
+__global__ void __launch_bounds__(PD_WAVES * 64) patch_embed_dgrad_kernel(const float* __restrict__ dx, const float* __restrict__ W,
+                                                                          float* __restrict__ out, int M, int G, int p, int C, int D,
+                                                                          const float* __restrict__ inv_scale) {
+  extern __shared__ __attribute__((aligned(16))) float pd_ws[];
+  float4* ws4 = (float4*)pd_ws;
+  const int KPE = C * p * p, KQ = KPE >> 2, nq = D >> 2;
+  for (int g = threadIdx.x; g < D * KQ; g += blockDim.x) {
+    const int d = g / KQ, jq = g - d * KQ;
+    const int i = d & 3, ch = d >> 2;
+    ws4[(((ch >> 6) * 4 + i) * KQ + jq) * 64 + (ch & 63)] = ((const float4*)W)[g];
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float f = inv_scale ? 1.0f / inv_scale[0] : 1.0f;
+  for (int m = blockIdx.x * PD_WAVES + wave; m < M; m += gridDim.x * PD_WAVES) {
+    const float4* row = (const float4*)(dx + (size_t)m * D);
+    float4 x[PD_NK];
+#pragma unroll
+    for (int k = 0; k < PD_NK; ++k) x[k] = k * 64 + lane < nq ? row[k * 64 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float acc[KP];
+#pragma unroll
+    for (int j = 0; j < KP; ++j) acc[j] = 0.f;
+#pragma unroll
+    for (int k = 0; k < PD_NK; ++k) {
+      if (k * 64 + lane < nq) {
+        const float xv[4] = {x[k].x, x[k].y, x[k].z, x[k].w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float4* wr = ws4 + (size_t)((k * 4 + i) * KQ) * 64 + lane;
+#pragma unroll
+          for (int jq = 0; jq < KP / 4; ++jq) {
+            if (jq < KQ) {
+              const float4 w = wr[jq * 64];
+              acc[jq * 4] += xv[i] * w.x; acc[jq * 4 + 1] += xv[i] * w.y; acc[jq * 4 + 2] += xv[i] * w.z; acc[jq * 4 + 3] += xv[i] * w.w;
+            }
+          }
+        }
+      }
+    }
+    reduce_scatter<KP, 32>(acc, lane);
+    constexpr int per = 64 / KP;             // lanes per sum
+    const int j = lane / per;
+    if (lane % per == 0 && j < KPE) out[patch_pixel(m, j, G, p, C)] = acc[0] * f;
+  }
+}
+// the wide form's second half: out[pixel of (m, j)] = pix[m][j] (x 1 / scale)
+__global__ void patch_scatter_kernel(const float* __restrict__ pix, float* __restrict__ out, int BF, int G, int p, int C,
+                                     const float* __restrict__ inv_scale) {
+  const int KPE = C * p * p;
+  const size_t total = (size_t)BF * G * G * KPE;
+  const float f = inv_scale ? 1.0f / inv_scale[0] : 1.0f;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256)
+    out[patch_pixel((int)(i / KPE), (int)(i % KPE), G, p, C)] = pix[i] * f;
+}
+// out[i] = in[i] / divisor (x *scale): the caller's seed of a custom loss into the backward's domain
+__global__ void seed_scale_kernel(const float* __restrict__ in, float* __restrict__ out, float divisor, const float* __restrict__ scale, size_t n) {
+  const float s = scale ? scale[0] : 1.0f;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = in[i] / divisor * s;
+}
+
 }  // namespace
+
+int launch_seed_scale(const float* in, float* out, float divisor, const float* scale_dev, size_t n, hipStream_t st) {
+  const size_t blocks = std::min<size_t>((n + 255) / 256, 4096);
+  hipLaunchKernelGGL(seed_scale_kernel, dim3((unsigned)std::max<size_t>(blocks, 1)), dim3(256), 0, st, in, out, divisor, scale_dev, n);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+
+// fast form: KPE = C p^2 a multiple of 4 up to 64, D a multiple of 4 up to 1280 and the weight inside the LDS budget
+bool patch_embed_dgrad_fast(int p, int C, int D) {
+  const int KPE = C * p * p;
+  return KPE % 4 == 0 && KPE <= 64 && D % 4 == 0 && D <= PD_NK * 256 && (D / 4 + 63) / 64 * 64 * 4 * KPE * (int)sizeof(float) <= PD_LDS_MAX;
+}
+// out [BF, C, G p, G p] = the patch embed's input gradient of dx [BF G^2, D] under W [D, C p^2] (x 1 / *inv_scale_dev);
+// ws: float [BF G^2][C p^2], needed by the wide form only (!patch_embed_dgrad_fast)
+int launch_patch_embed_dgrad(const float* dx, const float* W, float* out, int BF, int G, int p, int C, int D, float* ws,
+                             const float* inv_scale_dev, hipStream_t st) {
+  const int KPE = C * p * p;
+  const int64_t M64 = (int64_t)BF * G * G;
+  if (BF < 1 || G < 1 || p < 1 || C < 1 || D < 1 || M64 * std::max(D, KPE) >= (1ll << 31))
+    return fail(LATTE_ERR_INVALID, "patch_embed_dgrad: bad shape");
+  const int M = (int)M64;
+  if (patch_embed_dgrad_fast(p, C, D)) {
+    if (((uintptr_t)dx | (uintptr_t)W) & 15) return fail(LATTE_ERR_INVALID, "patch_embed_dgrad: dx and W must be 16-byte aligned");
+    const int lds = (D / 4 + 63) / 64 * 64 * 4 * KPE * (int)sizeof(float);
+    const dim3 grid((unsigned)std::min((M + PD_WAVES - 1) / PD_WAVES, 512)), block(PD_WAVES * 64);
+    if (KPE <= 16) return launch_lds_max<patch_embed_dgrad_kernel<16>>(grid, block, PD_LDS_MAX, lds, st, dx, W, out, M, G, p, C, D, inv_scale_dev);
+    if (KPE <= 32) return launch_lds_max<patch_embed_dgrad_kernel<32>>(grid, block, PD_LDS_MAX, lds, st, dx, W, out, M, G, p, C, D, inv_scale_dev);
+    return launch_lds_max<patch_embed_dgrad_kernel<64>>(grid, block, PD_LDS_MAX, lds, st, dx, W, out, M, G, p, C, D, inv_scale_dev);
+  }
+  if (!ws) return fail(LATTE_ERR_INVALID, "patch_embed_dgrad: the wide form needs a workspace");
+  int rc;
+  if ((rc = launch_naive_gemm(dx, D, 1, W, KPE, 1, ws, KPE, 1, M, KPE, D, 1.0f, 0, st))) return rc;
+  const size_t total = (size_t)M * KPE;
+  hipLaunchKernelGGL(patch_scatter_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, st, ws, out, BF, G, p, C,
+                     inv_scale_dev);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
 
 int launch_stage_finalize(const StageFinArgs& a, hipStream_t st) {
   if (a.D % 64 || a.D > FIN_DMAX || a.n_mod < 0 || a.n_mod > 6 || a.n_bias < 0 || a.n_bias > 4)

@@ -28,6 +28,27 @@ def data_seed(seed, step, micro, accum, rank, world):
     return int(seed) * 1000003 + (int(step) * int(accum) + int(micro)) * int(world) + int(rank)
 
 
+def resolve_loss_fn(spec):
+    """The training config's ``loss_fn: "package.module:function"`` -> the callable ``LatteTrainer.train_step(loss_fn=...)`` takes
+    (``loss_fn(model_out, x_start=, x_t=, t=, noise=) -> per-sample loss [B]``).  None / "" -> None: the built-in loss."""
+    if spec in (None, ""):
+        return None
+    if not isinstance(spec, str) or spec.count(":") != 1 or not all(part.strip() for part in spec.split(":")):
+        raise ValueError(f"loss_fn must be 'package.module:function', got {spec!r}")
+    module, name = (part.strip() for part in spec.split(":"))
+    import importlib
+    try:
+        mod = importlib.import_module(module)
+    except ImportError as e:
+        raise ValueError(f"loss_fn {spec!r}: cannot import module {module!r} ({e})") from e
+    if not hasattr(mod, name):
+        raise ValueError(f"loss_fn {spec!r}: module {module!r} has no attribute {name!r}")
+    fn = getattr(mod, name)
+    if not callable(fn):
+        raise ValueError(f"loss_fn {spec!r}: {module}.{name} is not callable ({type(fn).__name__})")
+    return fn
+
+
 def latte_preset_name(name):
     """The model preset a training config's ``model:`` names: ``LatteIMG-XL/2`` (train_with_img.py, models/latte_img.py) has exactly the
     parameters of ``Latte-XL/2`` and its checkpoints are sampled with that preset, so the joint trainer runs on the plain model:

@@ -3,6 +3,7 @@
     trainer = LatteTrainer(model, diffusion, max_batch=5)          # model: latte_amd.Latte, diffusion: create_diffusion("")
     out = trainer.train_step(x_start, y=labels)                     # q_sample + forward + losses + backward + clip + AdamW + EMA
     trainer.ema_state_dict() / model.state_dict()                  # reference checkpoint format (train.py:257-262)
+    out = trainer.forward(x_t, t, y); loss(out).backward(); trainer.optimizer_step()      # any torch loss; x_t.grad when asked for
 
 What runs where: the forward with saved activations, the loss terms and their gradient, the backward (MFMA GEMMs for the
 input / weight gradients, the attention backward, LayerNorm-modulate / GELU / gate backward kernels), gradient norm + clipping,
@@ -41,6 +42,25 @@ def average_gradients(flat_grads, group=None, async_op=False):
     return flat_grads
 
 
+class _EngineDenoiser(torch.autograd.Function):
+    """``LatteTrainer.forward`` as a node of the autograd graph: forward = latte_trainer_forward, backward = latte_trainer_seed + the
+    backward stages (+ latte_trainer_input_grad).  ``anchor`` is a dummy that requires grad, so that the output carries a ``grad_fn``
+    whether or not ``x`` does; nothing goes through ``save_for_backward`` -- the activations live in the engine."""
+
+    @staticmethod
+    def forward(ctx, x, anchor, trainer, t64, yy, generation):
+        mo = trainer._engine_forward(x.detach(), t64, yy)
+        ctx.trainer, ctx.generation, ctx.shape = trainer, generation, tuple(mo.shape)
+        ctx.keep = (t64, yy)                       # the engine reads the labels until the last stage
+        trainer._live = generation
+        return mo
+
+    @staticmethod
+    def backward(ctx, grad):
+        dx = ctx.trainer._engine_backward(ctx.generation, grad, ctx.shape, ctx.needs_input_grad[0])
+        return dx, None, None, None, None, None
+
+
 class LatteTrainer:
     """One data-parallel replica of train.py's model / ema / AdamW triple.
 
@@ -72,7 +92,10 @@ class LatteTrainer:
     ``y_image`` [B, N] besides ``y``.  LatteIMG has exactly Latte's parameters and its image frames meet neither the video frames nor
     the temporal blocks, so the engine runs a joint micro-batch as the video step plus one spatial-only image pass over B N one-frame
     samples whose gradient writers add (include/latte_amd.h); the checkpoint is sampled with the plain ``Latte-*`` presets.  A joint
-    micro-batch is ONE micro-batch of an accumulation window.  N <= num_frames; with N = 0 nothing changes."""
+    micro-batch is ONE micro-batch of an accumulation window.  N <= num_frames; with N = 0 nothing changes.
+    Custom losses: ``forward(x_t, t, y)`` returns the model output as a node of the torch autograd graph -- any torch loss of it calls
+    ``backward()``, which seeds the engine's backward and fills ``x_t.grad`` -- and ``train_step(..., loss_fn=f)`` runs a whole step
+    on ``f(model_out, x_start=, x_t=, t=, noise=) -> [B]``; diffusions with ``use_kl`` / ``predict_xstart`` train only that way."""
 
     def __init__(self, model, diffusion, max_batch, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_max_norm=0.1,
                  start_clip_iter=20000, ema_decay=0.9999, class_dropout_prob=0.1, compute_dtype="f16", process_group=None,
@@ -83,8 +106,6 @@ class LatteTrainer:
             raise LatteError("LatteTrainer needs a latte_amd SpacedDiffusion (create_diffusion)")
         if model.extras not in (1, 2):
             raise LatteError("T2V training are Not supported at this moment!")             # train.py:213-214
-        if diffusion.loss_type not in ("mse", "rescaled_mse"):
-            raise LatteError("the engine trains the MSE loss types (create_diffusion's default and rescale_learned_sigmas)")
         if compute_dtype not in _lib.DTYPES:
             raise LatteError(f"compute_dtype must be one of {sorted(_lib.DTYPES)}")
         _lib.require_gpu()
@@ -108,6 +129,8 @@ class LatteTrainer:
         if self.gradient_accumulation_steps < 1:
             raise LatteError("gradient_accumulation_steps must be >= 1")
         self.micro_step = 0            # micro-batches of the current window already in the gradient buffer
+        self._generation = 0           # custom losses: the live ``forward`` (one graph at a time); 0 = none awaits its backward
+        self._live = None
         self._accumulating = False     # the engine's "grad_accumulate" option as last set
         dev = next(model.parameters()).device
         if dev.type != "cuda":
@@ -154,6 +177,7 @@ class LatteTrainer:
                                                ptr(named["temp_embed"].detach().float().contiguous()), 1, stream_ptr()))
             check(lib.latte_trainer_sync_weights(h, stream_ptr()))
         self._norm = torch.zeros(2, device=dev)
+        self._anchor = torch.zeros((), device=dev, requires_grad=True)   # makes ``forward``'s output a node of the autograd graph
         if hasattr(model, "mark_weights_dirty"):
             model.mark_weights_dirty()
 
@@ -234,7 +258,9 @@ class LatteTrainer:
         a micro-batch of F frames still takes the plain step.
         -> dict(loss, mse, vb [, model_out])."""
         self._reduced = False
+        self._live = None                                                          # a custom ``forward`` awaiting its backward is abandoned
         d = self.diffusion
+        self._builtin_loss_check()
         x0 = x_start.to(device=self.device, dtype=torch.float32).contiguous()
         B = x0.shape[0]
         if B > self.max_batch:
@@ -247,16 +273,7 @@ class LatteTrainer:
         if nz.shape != x0.shape:
             raise AssertionError("noise.shape == x_start.shape")
         t64 = t.to(device=self.device, dtype=torch.int64).contiguous()
-        yy = None
-        if self.model.extras == 2:
-            if y is None:
-                raise LatteError("class-conditional model: labels required")
-            yy = y.to(device=self.device, dtype=torch.int64)
-            if drop_mask is not None:                                              # LabelEmbedder.token_drop, latte.py:138-148
-                yy = torch.where(drop_mask.to(self.device), torch.full_like(yy, self.model.num_classes), yy)
-            if int(yy.min()) < 0 or int(yy.max()) > self.model.num_classes:
-                raise IndexError("label out of range")
-            yy = yy.contiguous()
+        yy = self._labels(y, drop_mask)
         terms = torch.empty(3, B, device=self.device)
         mo = torch.empty(B, x0.shape[1], self.model.out_channels, x0.shape[3], x0.shape[4], device=self.device) if return_model_out else None
         lib = load_library()
@@ -276,25 +293,127 @@ class LatteTrainer:
                 # on its own stream behind the kernels already launched) while the next stages' kernels follow on this stream
                 # (a joint micro-batch: the video pass ran inside begin, these are the image pass's stages -- final slices)
                 check(begin(*args))
-                handles = []
-                for k in range(lib.latte_trainer_num_stages(self._h)):
-                    check(lib.latte_trainer_backward_stage(self._h, k, stream_ptr()))
-                    off, n = _lib.c_i64(), _lib.c_i64()
-                    check(lib.latte_trainer_stage_range(self._h, k, off, n))
-                    h = average_gradients(self.grads[off.value:off.value + n.value], self.process_group, async_op=True)
-                    if h is not None:
-                        handles.append(h)
-                for h in handles:
-                    h.wait()
-                if handles:
-                    self.grads.div_(_world(self.process_group))
-                self._reduced = True
+                self._run_stages(True)
         out = {"loss": terms[0], "mse": terms[1]}
         if d.learn_sigma:
             out["vb"] = terms[2]
         if mo is not None:
             out["model_out"] = mo
         return out
+
+    def _builtin_loss_check(self):
+        d = self.diffusion
+        if d.loss_type not in ("mse", "rescaled_mse"):
+            raise LatteError("the engine's built-in loss is one of the MSE loss types (create_diffusion's default and "
+                             "rescale_learned_sigmas); pass loss_fn= for anything else")
+        if d.predict_xstart:
+            raise LatteError("the engine's built-in loss trains the epsilon-prediction models of train.py:92; pass loss_fn= for a "
+                             "predict_xstart diffusion")
+
+    def _run_stages(self, reduce):
+        """The backward stages behind a begin / seed, in order.  reduce: each stage's finished gradient slice is all-reduced while
+        the next stages run (no-op without a process group) and ``self.grads`` leaves here averaged."""
+        lib = load_library()
+        handles = []
+        for k in range(lib.latte_trainer_num_stages(self._h)):
+            check(lib.latte_trainer_backward_stage(self._h, k, stream_ptr()))
+            if not reduce:
+                continue
+            off, n = _lib.c_i64(), _lib.c_i64()
+            check(lib.latte_trainer_stage_range(self._h, k, off, n))
+            h = average_gradients(self.grads[off.value:off.value + n.value], self.process_group, async_op=True)
+            if h is not None:
+                handles.append(h)
+        for h in handles:
+            h.wait()
+        if handles:
+            self.grads.div_(_world(self.process_group))
+        if reduce:
+            self._reduced = True
+
+    # ------------------------------------------------------------------ custom losses: forward / backward through torch.autograd
+    def _labels(self, y, drop_mask):
+        """-> the labels the engine takes: int64 on the device, after label dropout; None without a label table."""
+        if self.model.extras != 2:
+            return None
+        if y is None:
+            raise LatteError("class-conditional model: labels required")
+        yy = y.to(device=self.device, dtype=torch.int64)
+        if drop_mask is not None:                                                  # LabelEmbedder.token_drop, latte.py:138-148
+            yy = torch.where(drop_mask.to(self.device), torch.full_like(yy, self.model.num_classes), yy)
+        if int(yy.min()) < 0 or int(yy.max()) > self.model.num_classes:
+            raise IndexError("label out of range")
+        return yy.contiguous()
+
+    def forward(self, x, t, y=None, drop_mask=None):
+        """``model(x, t, y)`` on the engine with saved activations: x [B, F, C, H, W] the (noised) model input, t [B] the ORIGINAL
+        timesteps the model sees (``diffusion.timestep_map[t]`` of a respaced index), y labels (``drop_mask``: label dropout applied
+        here).  -> model_out [B, F, C_out, H, W] fp32 with a ``grad_fn``: any torch loss of it can call ``backward()``, which seeds the
+        engine's staged backward with the incoming gradient.  Parameter gradients land in the flat ``self.grads`` (assigned by the
+        window's first micro-batch, added by the others, divided by ``gradient_accumulation_steps``, all-reduced after the last --
+        exactly as ``backward_micro_batch``'s), NOT in ``param.grad``; ``x.grad`` is filled when ``x.requires_grad``.  The backward
+        counts as one micro-batch of the window: ``optimizer_step()`` is due after the ``gradient_accumulation_steps``-th.
+        One graph is alive at a time: a newer ``forward`` (or a built-in step) makes this output's backward a ``LatteError``, as is
+        a second backward.  Under ``torch.no_grad()`` the output is a plain tensor.  The loss-scaled f16 backward multiplies the
+        incoming gradient by the live loss scale (2**14 by default): see DESIGN.md 4.4 before seeding it with a loss whose gradient
+        is orders of magnitude away from the built-in one's."""
+        if self.micro_step >= self.gradient_accumulation_steps:
+            raise LatteError("the accumulation window is complete: optimizer_step() is due")
+        Fr, C, H = self.model.num_frames, self.model.in_channels, self.model.input_size
+        if not torch.is_tensor(x) or x.dim() != 5 or tuple(x.shape[1:]) != (Fr, C, H, H):
+            raise LatteError(f"forward: x must be [batch, {Fr}, {C}, {H}, {H}], got {list(getattr(x, 'shape', []))}"
+                             + (" (a joint F + N micro-batch has no custom-loss path)" if self.use_image_num else ""))
+        B = x.shape[0]
+        if B < 1 or B > self.max_batch:
+            raise LatteError(f"batch {B} exceeds max_batch {self.max_batch}")
+        if x.device != self.device and x.requires_grad:
+            raise LatteError("forward: an input that requires grad must live on the trainer's device")
+        t64 = t.to(device=self.device, dtype=torch.int64).contiguous()
+        if tuple(t64.shape) != (B,):
+            raise LatteError(f"forward: t must be [{B}], got {list(t64.shape)}")
+        yy = self._labels(y, drop_mask)
+        if yy is not None and tuple(yy.shape) != (B,):
+            raise LatteError(f"forward: y must be [{B}], got {list(yy.shape)}")
+        self._reduced = False
+        self._live = None
+        self._set_accumulate(self.micro_step > 0)
+        self._generation += 1
+        if not torch.is_grad_enabled():
+            return self._engine_forward(x.detach(), t64, yy)
+        return _EngineDenoiser.apply(x, self._anchor, self, t64, yy, self._generation)
+
+    def _engine_forward(self, x, t64, yy):
+        x32 = x.to(device=self.device, dtype=torch.float32).contiguous()
+        mo = torch.empty(x32.shape[0], x32.shape[1], self.model.out_channels, x32.shape[3], x32.shape[4], device=self.device)
+        with torch.cuda.device(self.device):
+            check(load_library().latte_trainer_forward(self._h, ptr(x32), ptr(t64), ptr(yy) if yy is not None else None, x32.shape[0],
+                                                       ptr(mo), stream_ptr()))
+        return mo
+
+    def _engine_backward(self, generation, grad, shape, want_dx):
+        if self._live != generation:
+            raise LatteError("backward of a LatteTrainer.forward output that is no longer alive: one graph at a time, one backward per "
+                             "forward (a newer forward or a built-in step came in between, or this is a second backward)")
+        if (not torch.is_tensor(grad) or tuple(grad.shape) != tuple(shape) or grad.dtype != torch.float32 or grad.device != self.device):
+            raise LatteError(f"backward: the gradient of model_out must be float32 {list(shape)} on {self.device}, got "
+                             f"{getattr(grad, 'dtype', None)} {list(getattr(grad, 'shape', []))} on {getattr(grad, 'device', None)}")
+        self._live = None
+        g = grad.contiguous()
+        last = self.micro_step == self.gradient_accumulation_steps - 1
+        lib = load_library()
+        dx = None
+        with torch.cuda.device(self.device):
+            check(lib.latte_trainer_seed(self._h, ptr(g), stream_ptr()))
+            self._run_stages(last and (_world(self.process_group) > 1 or self.always_staged))
+            if want_dx:
+                dx = torch.empty(shape[0], shape[1], self.model.in_channels, shape[3], shape[4], device=self.device)
+                check(lib.latte_trainer_input_grad(self._h, ptr(dx), stream_ptr()))
+                if self.gradient_accumulation_steps != 1:       # the engine's gradients are those of loss / A; x.grad is the loss's own
+                    dx.mul_(float(self.gradient_accumulation_steps))
+        self.micro_step += 1
+        if last:
+            self.all_reduce_gradients()
+        return dx
 
     def all_reduce_gradients(self):
         """DDP's gradient averaging (train.py:125) as ONE collective over the flat gradient buffer: RCCL over xGMI when the
@@ -308,13 +427,37 @@ class LatteTrainer:
             check(load_library().latte_trainer_set_option(self._h, b"grad_accumulate", float(on)))
             self._accumulating = on
 
-    def backward_micro_batch(self, x_start, t, noise, y=None, drop_mask=None, y_image=None, image_drop_mask=None):
+    def backward_micro_batch(self, x_start, t, noise, y=None, drop_mask=None, y_image=None, image_drop_mask=None, loss_fn=None):
         """The next micro-batch of the accumulation window: ``forward_backward`` in assign mode for the first, in accumulate mode
         for the others; the window's last one takes the staged, all-reducing backward when there is a process group.
-        -> (forward_backward's dict, True when the window is complete and ``optimizer_step`` is due)."""
+        loss_fn: a callable ``loss_fn(model_out, x_start=, x_t=, t=, noise=) -> per-sample loss [B]`` in torch replaces the built-in
+        loss: q_sample by the engine's kernel, ``forward``, ``loss_fn(...).mean().backward()`` (t: the respaced indices).
+        -> (forward_backward's dict -- with a loss_fn: {"loss": per-sample loss} --, True when the window is complete and
+        ``optimizer_step`` is due)."""
         if self.micro_step >= self.gradient_accumulation_steps:
             raise LatteError("the accumulation window is complete: optimizer_step() is due")
         last = self.micro_step == self.gradient_accumulation_steps - 1
+        if loss_fn is not None:
+            if not callable(loss_fn):
+                raise LatteError("loss_fn must be callable")
+            if y_image is not None or (torch.is_tensor(x_start) and x_start.dim() == 5 and x_start.shape[1] != self.model.num_frames):
+                raise LatteError("custom losses take video micro-batches of num_frames frames: no joint image-video pass")
+            d = self.diffusion
+            x0 = x_start.to(device=self.device, dtype=torch.float32).contiguous()
+            t64 = t.to(device=self.device, dtype=torch.int64).contiguous()
+            nz = noise.to(device=self.device, dtype=torch.float32).contiguous()
+            x_t = d.q_sample(x0, t64, nz)
+            t_model = torch.tensor(d.timestep_map, device=self.device, dtype=torch.int64)[t64]
+            with torch.enable_grad():
+                out = self.forward(x_t, t_model, y, drop_mask)
+                per_sample = loss_fn(out, x_start=x0, x_t=x_t, t=t64, noise=nz)
+                if not torch.is_tensor(per_sample) or tuple(per_sample.shape) != (x0.shape[0],):
+                    raise LatteError(f"loss_fn must return the per-sample loss [{x0.shape[0]}], got {list(getattr(per_sample, 'shape', []))}")
+                per_sample.mean().backward()
+            if self._live is not None:                                             # no gradient reached the engine: no micro-batch ran
+                self._live = None
+                raise LatteError("loss_fn's result does not depend on model_out")
+            return {"loss": per_sample.detach()}, last
         self._set_accumulate(self.micro_step > 0)
         out = self.forward_backward(x_start, t, noise, y, drop_mask,
                                     overlap_all_reduce=last and (_world(self.process_group) > 1 or self.always_staged),
@@ -392,9 +535,10 @@ class LatteTrainer:
         if hasattr(self.model, "mark_weights_dirty"):
             self.model.mark_weights_dirty()
 
-    def train_step(self, x_start, y=None, t=None, noise=None, drop_mask=None, y_image=None, image_drop_mask=None):
+    def train_step(self, x_start, y=None, t=None, noise=None, drop_mask=None, y_image=None, image_drop_mask=None, loss_fn=None):
         """train.py:197-236 for one micro-batch; the optimiser step runs after the ``gradient_accumulation_steps``-th of a window
-        (``out["updated"]``; ``out["grad_norm"]`` only then)."""
+        (``out["updated"]``; ``out["grad_norm"]`` only then).  loss_fn: the caller's loss in torch instead of the built-in one
+        (``backward_micro_batch``); diffusions with ``use_kl`` / ``predict_xstart`` are accepted only with one."""
         B = x_start.shape[0]
         if t is None:
             t = torch.randint(0, self.diffusion.num_timesteps, (B,), device=self.device)       # train.py:223
@@ -405,7 +549,7 @@ class LatteTrainer:
         if (image_drop_mask is None and y_image is not None and self.use_image_num and self.model.extras == 2
                 and self.class_dropout_prob > 0):
             image_drop_mask = torch.rand(B, device=self.device) < self.class_dropout_prob        # latte_img.py:341-342: one coin per sample
-        out, last = self.backward_micro_batch(x_start, t, noise, y, drop_mask, y_image, image_drop_mask)
+        out, last = self.backward_micro_batch(x_start, t, noise, y, drop_mask, y_image, image_drop_mask, loss_fn=loss_fn)
         out["updated"] = last
         if last:
             out["grad_norm"] = self.optimizer_step()

@@ -9,7 +9,8 @@ chunk per kernel -- its code from its label to the end of its text section (s_en
 function they belong to, assembler comments go, and lines that mention the per-compile __hip_cuid_ symbol are dropped; the two sorted lists of chunks are
 compared.  So a refactor may rename a kernel (a dropped template argument changes the mangling) or change the order in
 which instantiations are emitted; it may not change an instruction or a kernel descriptor.  A refactor of the kernels that claims
-"device code unchanged" shows a table of "same" here; exit status 1 otherwise.  Needs hipcc, no GPU.
+"device code unchanged" shows a table of "same" here -- "same + n new" where a file gained kernels and every kernel it had is still
+there, instruction for instruction --; exit status 1 otherwise.  Needs hipcc, no GPU.
 """
 import io
 import os
@@ -69,8 +70,14 @@ def main(argv):
     print("%-16s %12s %12s  %s" % ("file", "kernels " + rev[:4], "kernels now", "vs " + rev))
     for f in files:
         a, b = out[(old, f)], out[(ROOT, f)]
-        bad += a != b
-        print("%-16s %12d %12d  %s" % (f, len(a), len(b), "same" if a == b else "DIFFERENT"))
+        left = list(b)                   # every old kernel still there unchanged, the rest new: "same + n new"
+        for k in a:
+            if k in left:
+                left.remove(k)
+        added = len(left) if len(left) == len(b) - len(a) and len(b) > len(a) else 0
+        ok = a == b or added
+        bad += not ok
+        print("%-16s %12d %12d  %s" % (f, len(a), len(b), "same" if a == b else ("same + %d new" % added if added else "DIFFERENT")))
     print("%d of %d files match" % (len(files) - bad, len(files)))
     return 1 if bad else 0
 

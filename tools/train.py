@@ -27,6 +27,9 @@ clip and `model: LatteIMG-*` is mapped to the `Latte-*` preset of the same size 
 it).  `frame_data_path` is a directory of single frames -- .npy latents [4, h, w] (scaled by 0.18215) or uint8 [H, W, 3] at the
 training image size, encoded with the VAE like the frame clips; label = file-name prefix, as for clips -- N of them drawn per sample
 from the micro-batch's seeded generator (a resumed run redraws the same ones); with `data_path: synthetic` they are synthetic too.
+`loss_fn: "package.module:function"` replaces the built-in loss by a torch one (`LatteTrainer.train_step(loss_fn=...)`:
+`function(model_out, x_start=, x_t=, t=, noise=) -> per-sample loss [B]`, differentiated through `LatteTrainer.forward`); video
+micro-batches only (not with `use_image_num`).
 """
 import argparse
 import glob
@@ -43,7 +46,7 @@ sys.path.insert(0, ROOT)
 import latte_amd  # noqa: E402
 from latte_amd import parallel  # noqa: E402
 from latte_amd.train_util import (checkpoint_step, data_seed, draw_image_frames, latest_checkpoint, latte_preset_name,  # noqa: E402
-                                  rng_state, scheduled_lr, set_rng_state, state_path)
+                                  resolve_loss_fn, rng_state, scheduled_lr, set_rng_state, state_path)
 
 
 def clip_label(path):
@@ -190,6 +193,12 @@ def main():
     # masks, as the reference does (train.py:62 `seed = args.global_seed + rank`): a global batch covers world * nb independent
     # draws, not nb draws replicated world times.
     torch.manual_seed(seed + rank)
+    loss_fn = resolve_loss_fn(args.get("loss_fn"))
+    if loss_fn is not None:
+        if use_image_num:
+            raise SystemExit("loss_fn: custom losses take video micro-batches only (no use_image_num)")
+        if rank == 0:
+            print(f"Custom loss: {args.get('loss_fn')} ({loss_fn.__module__}.{getattr(loss_fn, '__qualname__', loss_fn)})", flush=True)
     out_dir = a.out or args.results_dir
     first_step = 0
     if args.get("pretrained"):
@@ -272,7 +281,7 @@ def main():
                     xi = vae.encode_video_uint8(xi.to(device), generator=gen)
                 x = torch.cat([x.to(device).float(), xi.to(device).float()], dim=1)
                 y_image = y_image.to(device) if int(args.extras) == 2 else None
-            out = trainer.train_step(x.to(device), y=y.to(device) if int(args.extras) == 2 else None, y_image=y_image)
+            out = trainer.train_step(x.to(device), y=y.to(device) if int(args.extras) == 2 else None, y_image=y_image, loss_fn=loss_fn)
             running += float(out["loss"].mean()) / accum      # (the reference's loss.item(), train.py:239; undivided terms)
         log_steps += 1
         if step % log_every == 0:
