@@ -221,6 +221,36 @@ int latte_sample_loop_ex(latte_engine_t* e, const latte_schedule_t* s, int metho
 int latte_invert_loop(latte_engine_t* e, const latte_schedule_t* s, int clip_denoised, int guided, float cfg_scale, float* x,
                       const int64_t* y, int batch, int start_index, int end_index, float* trail_sample, float* trail_x0, void* stream);
 
+/* ------------------------------------------------------------------ known-region sampling (prediction, interpolation, inpainting)
+ * The replacement scheme of Video Diffusion Models / RePaint on latte_sample_loop_ex's chain (not in the reference): part of the clip is
+ * held fixed and the rest is generated.  known: [B,F,C,H,W] fp32 clean latents; mask: [B,F,H,W] fp32, shared by the channels, 1 = known,
+ * 0 = generated, values between mix linearly.  One blend at level abar is
+ *   kn = sqrt(abar) known + sqrt(1 - abar) z  (known itself at abar = 1);   x <- m == 1 ? kn : (m == 0 ? x : m kn + (1 - m) x)
+ * blend_start != 0: one blend at alphas_cumprod[start_index] before the first evaluation (the first segment of a chain).  Then for every
+ * index i = start_index ... end_index and every repetition u = 1 ... resample: the forward and the step of latte_sample_loop_ex, a blend
+ * at alphas_cumprod_prev[i] (the level the step has just reached; (1, 0) at i == 0, so the known part of the result IS `known`), and,
+ * when u < resample and i > 0, the forward jump x <- sqrt(1 - betas[i]) x + sqrt(betas[i]) z back to level i (RePaint's resampling).
+ * trail_sample / trail_x0: NULL or [n_steps][...], one slot per INDEX: x after the blend of the last repetition, and its pred_xstart.
+ * noise: NULL, or DEVICE slabs of B*F*C*H*W floats consumed in this order: the start blend; then per repetition the step's own noise
+ * (DDPM at i > 0, DDIM where sigma != 0), the blend's (i > 0), the jump's.  latte_known_chain_slabs is the one definition of that count.
+ * NULL: every slab comes from the engine's Philox stream (option "seed") in the same order, the offset advancing by B*F*C*H*W per slab;
+ * the blend draws inside its kernel.  On a guided (doubled) batch known and mask have the batch of x: the caller doubles them as it
+ * doubles z.  LATTE_ERR_INVALID for resample < 1, a method other than DDPM / DDIM, H * W % 4 != 0, a NULL known or mask, plus the checks
+ * of latte_sample_loop_ex; every check runs before the first launch.  Stream-ordered, no synchronisation. */
+int latte_sample_loop_known(latte_engine_t* e, const latte_schedule_t* s, int method, float eta, int clip_denoised, int guided,
+                            float cfg_scale, float* x, const int64_t* y, int batch, int start_index, int end_index, const float* known,
+                            const float* mask, int resample, int blend_start, const float* noise, float* trail_sample, float* trail_x0,
+                            void* stream);
+/* The number of noise slabs latte_sample_loop_known consumes for these arguments.  Host only. */
+int latte_known_chain_slabs(const latte_schedule_t* s, int method, float eta, int start_index, int end_index, int resample,
+                            int blend_start, int64_t* n_slabs);
+/* One blend (formula above) with (a, b) = (sqrt(abar), sqrt(1 - abar)) given; b == 0 reads no noise.  x, known, noise:
+ * [B,F,C,H*W] (frames_inner = 0, the class-conditional engine's layout) or [B,C,F,H*W] (frames_inner = 1, text-to-video); mask [B,F,H*W].
+ * noise == NULL with b != 0: z is drawn in the kernel, bit for bit what the engine's generator writes for a slab at (seed, offset).
+ * hw % 4 != 0 is refused (16-byte accesses). */
+int latte_known_blend(float* x, const float* known, const float* mask, const float* noise, uint64_t seed, uint64_t offset, float a,
+                      float b, int batch, int frames, int channels, int hw, int frames_inner, void* stream);
+
 /* ------------------------------------------------------------------ linear samplers as a plan (Euler, Euler-ancestral, Heun, DPM-Solver++)
  * The class-conditional / unconditional / text-embedding engine's counterpart of latte_t2v_guided_linear_loop (below): a whole chain of
  * any sampler whose update is a linear combination of the latents, the newest eps, up to three remembered outputs and fresh noise, as
@@ -561,6 +591,15 @@ int latte_t2v_set_text(latte_t2v_t* e, const float* encoder_hidden_states, const
 int latte_t2v_guided_ddim_loop(latte_t2v_t* e, float* x, int samples, int n_steps, const int64_t* timesteps,
                                const double* alpha_t, const double* alpha_prev, float guidance_scale,
                                int enable_temporal_attentions, void* stream);
+/* latte_t2v_guided_ddim_loop with a known part held fixed (the scheme of latte_sample_loop_known, without resampling): one blend
+ * (latte_known_blend, frames_inner = 1) at alpha_t[0] before step 0 and one at alpha_prev[k] after step k; the last step blends with
+ * (1, 0) whatever alpha_prev is, so the known part of the result is `known`.  known: [samples, C, F, H, W] fp32 clean latents; mask:
+ * [samples, F, H, W] fp32; noise: DEVICE [n_steps][samples * C * F * H * W] fp32, required (this engine draws none): slab 0 for the
+ * blend before step 0, slab k + 1 for the blend after step k.  Preconditions as latte_t2v_guided_ddim_loop, plus LATTE_ERR_INVALID for
+ * H * W % 4 != 0, a NULL known / mask / noise and an alpha out of range; nothing is launched when a check fails. */
+int latte_t2v_guided_ddim_loop_known(latte_t2v_t* e, float* x, int samples, int n_steps, const int64_t* timesteps,
+                                     const double* alpha_t, const double* alpha_prev, float guidance_scale, const float* known,
+                                     const float* mask, const float* noise, int enable_temporal_attentions, void* stream);
 /* The same guided loop for every sampler whose update is a linear combination of the latents, the newest guided model output, up to
  * three remembered outputs and fresh noise (latte_amd/schedulers.py: Euler, Euler-ancestral, Heun, DPM-Solver++ multistep build the
  * table with engine_plan()).  plan: HOST doubles [n_evals][LATTE_T2V_PLAN_COLS], one row per denoiser evaluation, narrowed to fp32 at

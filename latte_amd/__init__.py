@@ -8,6 +8,7 @@ the Latte-1 text-to-video denoiser and its sampling loop), ``load_config`` (Omeg
 from ._lib import LatteError, load_library  # noqa: F401
 from .config import Config, load_config  # noqa: F401
 from .diffusion import LINEAR_METHODS, SpacedDiffusion, create_diffusion  # noqa: F401
+from .known import known_blend, known_mask  # noqa: F401
 from .models import Latte, Latte_models, find_model, get_models  # noqa: F401
 from .pipeline import LattePipeline  # noqa: F401
 from .schedulers import (DDIMInverseScheduler, DDIMScheduler, DPMSolverMultistepScheduler,  # noqa: F401

@@ -79,6 +79,11 @@ PROTOTYPES = {
     "latte_sample_loop_ex": (c_int, [c_void, c_void, c_int, c_f32, c_int, c_int, c_f32, c_void, c_void, c_int, c_int, c_int,
                                      c_void, c_void, c_void, c_void]),
     "latte_invert_loop": (c_int, [c_void, c_void, c_int, c_int, c_f32, c_void, c_void, c_int, c_int, c_int, c_void, c_void, c_void]),
+    "latte_sample_loop_known": (c_int, [c_void, c_void, c_int, c_f32, c_int, c_int, c_f32, c_void, c_void, c_int, c_int, c_int,
+                                        c_void, c_void, c_int, c_int, c_void, c_void, c_void, c_void]),
+    "latte_known_chain_slabs": (c_int, [c_void, c_int, c_f32, c_int, c_int, c_int, c_int, ctypes.POINTER(c_i64)]),
+    "latte_known_blend": (c_int, [c_void, c_void, c_void, c_void, c_u64, c_u64, c_f32, c_f32, c_int, c_int, c_int, c_int, c_int,
+                                  c_void]),
     "latte_sample_plan_loop": (c_int, [c_void, c_int, c_f32, c_void, c_void, c_int, c_int, c_void, c_void, c_void, c_void]),
     "latte_q_sample": (c_int, [c_void, c_void, c_void, c_void, c_int, c_i64, c_void, c_void]),
     "latte_training_workspace_floats": (c_i64, [c_int, c_i64]),
@@ -127,6 +132,8 @@ PROTOTYPES = {
     "latte_t2v_forward": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_void, c_void]),
     "latte_t2v_set_text": (c_int, [c_void, c_void, c_void, c_int, c_int, c_void]),
     "latte_t2v_guided_ddim_loop": (c_int, [c_void, c_void, c_int, c_int, c_void, c_void, c_void, c_f32, c_int, c_void]),
+    "latte_t2v_guided_ddim_loop_known": (c_int, [c_void, c_void, c_int, c_int, c_void, c_void, c_void, c_f32, c_void, c_void, c_void,
+                                                 c_int, c_void]),
     "latte_t2v_guided_linear_loop": (c_int, [c_void, c_void, c_int, c_int, c_void, c_void, c_f32, c_int, c_void]),
     "latte_bench_gemm": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_f32), c_void]),
     "latte_vae_create": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_void)]),

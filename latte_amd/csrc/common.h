@@ -277,6 +277,11 @@ int launch_convert_h16_to_f32(const half_t* in, float* out, int64_t n, int dtype
 int launch_transpose_f32(const float* in, float* out, int rows, int cols, hipStream_t st);
 // Philox4x32-10 + Box-Muller standard normals; element i depends only on (seed, offset + i).
 int launch_fill_normal(float* out, size_t n, uint64_t seed, uint64_t offset, hipStream_t st);
+// Known-region replacement at level (a, b): x <- m == 1 ? kn : (m == 0 ? x : m kn + (1 - m) x), kn = b == 0 ? known : a known + b z.
+// x, known, z: [B, F, C, HW] (frames_inner = 0) or [B, C, F, HW] (1); mask [B, F, HW].  z == NULL: drawn in the kernel, bit for bit
+// launch_fill_normal(seed, offset).  hw % 4 is refused.
+int launch_known_blend(float* x, const float* known, const float* mask, const float* z, uint64_t seed, uint64_t offset, float a, float b,
+                       int batch, int frames, int channels, int hw, int frames_inner, hipStream_t st);
 
 // ---- VAE decoder kernels (vae.hip) -----------------------------------------------------------------
 // out32 != nullptr: fp32 output  out32 = conv + bias (+ res32)  (the decoder's residual stream is fp32); else half `out` (+ res)

@@ -613,6 +613,91 @@ int sampler_chain(const std::string& who, latte_engine* e, const latte_schedule_
   return LATTE_OK;
 }
 
+// ---- known-region sampling: the noise slabs of a chain, in the order they are consumed.
+// Repetition u (1 ... resample) of index i takes, in this order: the step's own noise, the noise of the blend that follows it, and
+// the noise of the forward jump back to level i.  The chain loop and latte_known_chain_slabs both walk this.
+struct KnownSlabs {
+  bool step, blend, jump;
+  int count() const { return (int)step + (int)blend + (int)jump; }
+};
+KnownSlabs known_slabs(int method, const SamplerCoefs& c, int i, int u, int resample) {
+  return {step_needs_noise(method, c, i), i > 0, u < resample && i > 0};
+}
+// the fp32 (sqrt(abar), sqrt(1 - abar)) of a level, as make_coefs narrows its tables
+void level_coefs(double abar, float* a, float* b) {
+  const float ab = (float)abar;
+  *a = std::sqrt(ab);
+  *b = std::sqrt(1.0f - ab);
+}
+
+int known_method_check(const std::string& who, int method, int resample) {
+  if (method != LATTE_METHOD_DDPM && method != LATTE_METHOD_DDIM) return fail(LATTE_ERR_INVALID, who + ": method must be DDPM or DDIM");
+  if (resample < 1) return fail(LATTE_ERR_INVALID, who + ": resample must be >= 1");
+  return LATTE_OK;
+}
+
+// latte_sample_loop_known: sampler_chain's descending walk with the known part of x replaced after every step
+int known_chain(const std::string& who, latte_engine* e, const latte_schedule_t* s, int method, float eta, int clip_denoised, int guided,
+                float cfg_scale, float* x, const int64_t* y, int batch, int start_index, int end_index, const float* known,
+                const float* mask, int resample, int blend_start, const float* noise, float* trail_sample, float* trail_x0,
+                hipStream_t st) {
+  if (!e || !s || !x) return fail(LATTE_ERR_INVALID, who + ": null argument");
+  int rc = latte_engine_check_weights(e);
+  if (rc) return rc;
+  if ((rc = range_check(who, s->num_timesteps, end_index, start_index, "learned-range variance needs >= 2 timesteps"))) return rc;
+  const bool use_cfg = guided != 0;
+  if ((rc = chain_check(who, e, s, batch, use_cfg, y, true))) return rc;
+  if ((rc = known_method_check(who, method, resample))) return rc;
+  if (!known || !mask) return fail(LATTE_ERR_INVALID, who + ": known and mask are required");
+  const int HW = e->H * e->H;
+  if (HW % 4) return fail(LATTE_ERR_INVALID, who + ": H * W must be a multiple of 4 (16-byte accesses of the blend kernel)");
+  const int n_run = start_index - end_index + 1;
+  ChainCond cc;
+  if ((rc = chain_prepare(e, s, e->cfg.extras == 1 ? 1 : batch, n_run, st, &cc))) return rc;
+  const size_t numel = (size_t)batch * e->F * e->Cin * HW;
+  int slab = 0;   // the next row of the caller's noise
+  // one blend at the level abar; its noise is the caller's next slab, or drawn in the kernel from the engine's stream
+  // (level 0 takes none: alphas_cumprod_prev[0] = 1 gives (1, 0))
+  auto blend = [&](double abar, bool takes_slab) -> int {
+    float a = 1.0f, b = 0.0f;
+    const float* nz = nullptr;
+    const uint64_t off = e->rng_offset;
+    if (takes_slab) {
+      level_coefs(abar, &a, &b);
+      if (noise) nz = noise + (size_t)slab++ * numel;
+      else e->rng_offset += numel;
+    }
+    return launch_known_blend(x, known, mask, nz, e->seed, off, a, b, batch, e->F, e->Cin, HW, 0, st);
+  };
+  if (blend_start && (rc = blend(s->alphas_cumprod[start_index], true))) return rc;
+  for (int k = 0; k < n_run; ++k) {
+    const int i = start_index - k;
+    const float* mod_i;
+    int mstride;
+    if ((rc = chain_mod(e, &cc, y, i, end_index, st, &mod_i, &mstride))) return rc;
+    SamplerCoefs c = make_coefs(s, method, i, eta, clip_denoised);
+    c.cfg_scale = cfg_scale;
+    float* x0 = trail_x0 ? trail_x0 + (size_t)k * numel : nullptr;
+    for (int u = 1; u <= resample; ++u) {
+      const KnownSlabs need = known_slabs(method, c, i, u, resample);
+      if ((rc = run_forward(e, x, nullptr, y, batch, use_cfg, e->model_out, st, nullptr, mod_i, mstride))) return rc;
+      const float* nz = nullptr;
+      if (need.step && (rc = chain_noise(e, noise, slab, numel, st, &nz))) return rc;
+      if (need.step && noise) ++slab;
+      if ((rc = launch_sampler_update(c, x, e->model_out, nz, batch, e->F, e->Cin, HW, use_cfg ? 1 : 0, x, x0, st))) return rc;
+      if ((rc = blend(s->alphas_cumprod_prev[i], need.blend))) return rc;   // (1, 0) at i == 0: the known latents themselves
+      if (need.jump) {   // back to level i: x <- sqrt(1 - beta_i) x + sqrt(beta_i) z, in place
+        if ((rc = chain_noise(e, noise, slab, numel, st, &nz))) return rc;
+        if (noise) ++slab;
+        const float beta = (float)s->betas[i];
+        if ((rc = launch_q_sample_scalar(std::sqrt(1.0f - beta), std::sqrt(beta), x, nz, numel, x, st))) return rc;
+      }
+    }
+    if ((rc = chain_trail(trail_sample, k, x, numel, st))) return rc;
+  }
+  return LATTE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -963,6 +1048,35 @@ int latte_invert_loop(latte_engine_t* e, const latte_schedule_t* s, int clip_den
                       const int64_t* y, int batch, int start_index, int end_index, float* trail_sample, float* trail_x0, void* stream) {
   return sampler_chain("invert_loop", e, s, LATTE_METHOD_DDIM_REVERSE, +1, 0.0f, clip_denoised, guided, cfg_scale, x, y, batch, start_index,
                        end_index, nullptr, trail_sample, trail_x0, (hipStream_t)stream);
+}
+
+// ---- known-region sampling: prediction, interpolation, inpainting by replacement (include/latte_amd.h)
+int latte_sample_loop_known(latte_engine_t* e, const latte_schedule_t* s, int method, float eta, int clip_denoised, int guided,
+                            float cfg_scale, float* x, const int64_t* y, int batch, int start_index, int end_index, const float* known,
+                            const float* mask, int resample, int blend_start, const float* noise, float* trail_sample, float* trail_x0,
+                            void* stream) {
+  return known_chain("sample_loop_known", e, s, method, eta, clip_denoised, guided, cfg_scale, x, y, batch, start_index, end_index, known,
+                     mask, resample, blend_start, noise, trail_sample, trail_x0, (hipStream_t)stream);
+}
+
+int latte_known_chain_slabs(const latte_schedule_t* s, int method, float eta, int start_index, int end_index, int resample,
+                            int blend_start, int64_t* n_slabs) {
+  if (!s || !n_slabs) return fail(LATTE_ERR_INVALID, "known_chain_slabs: null argument");
+  int rc = range_check("known_chain_slabs", s->num_timesteps, end_index, start_index, "learned-range variance needs >= 2 timesteps");
+  if (rc) return rc;
+  if ((rc = known_method_check("known_chain_slabs", method, resample))) return rc;
+  int64_t n = blend_start ? 1 : 0;
+  for (int i = start_index; i >= end_index; --i) {
+    const SamplerCoefs c = make_coefs(s, method, i, eta, 0);
+    for (int u = 1; u <= resample; ++u) n += known_slabs(method, c, i, u, resample).count();
+  }
+  *n_slabs = n;
+  return LATTE_OK;
+}
+
+int latte_known_blend(float* x, const float* known, const float* mask, const float* noise, uint64_t seed, uint64_t offset, float a,
+                      float b, int batch, int frames, int channels, int hw, int frames_inner, void* stream) {
+  return launch_known_blend(x, known, mask, noise, seed, offset, a, b, batch, frames, channels, hw, frames_inner, (hipStream_t)stream);
 }
 
 // ---- linear samplers as a plan (include/latte_amd.h; the table is latte_amd/schedulers.py: engine_plan())

@@ -979,33 +979,77 @@ __device__ __forceinline__ void philox_round(unsigned int (&c)[4], unsigned int 
   c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
 }
 
+// The four standard normals of element quad q of a draw at (seed, offset): quad q covers elements [4q, 4q+4) of THAT draw; the counter
+// is the global element-quad index.  The one definition of the stream: fill_normal_kernel and known_blend_kernel's inline draw.
+__device__ __forceinline__ void philox_normal_quad(unsigned long long seed, unsigned long long offset, size_t q, float (&z)[4]) {
+  const unsigned long long ctr = (offset >> 2) + q;
+  unsigned int c[4] = {(unsigned int)ctr, (unsigned int)(ctr >> 32), (unsigned int)(offset & 3), 0u};
+  unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    philox_round(c, k0, k1);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float r = sqrtf(-2.0f * logf(u1));
+    float sn, cs;
+    sincosf(6.283185307179586f * u2, &sn, &cs);
+    z[2 * h] = r * cs;
+    z[2 * h + 1] = r * sn;
+  }
+}
+
 __global__ void fill_normal_kernel(float* __restrict__ out, size_t n, unsigned long long seed, unsigned long long offset) {
   const size_t quads = (n + 3) / 4;
   for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (size_t)gridDim.x * blockDim.x) {
-    // quad q covers elements [4q, 4q+4) of THIS call; the counter is the global element-quad index
-    const unsigned long long ctr = (offset >> 2) + q;
-    unsigned int c[4] = {(unsigned int)ctr, (unsigned int)(ctr >> 32), (unsigned int)(offset & 3), 0u};
-    unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-      philox_round(c, k0, k1);
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
     float z[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-      const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-      const float r = sqrtf(-2.0f * logf(u1));
-      float sn, cs;
-      sincosf(6.283185307179586f * u2, &sn, &cs);
-      z[2 * h] = r * cs;
-      z[2 * h + 1] = r * sn;
-    }
+    philox_normal_quad(seed, offset, q, z);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (4 * q + j < n) out[4 * q + j] = z[j];
+  }
+}
+
+// Known-region replacement (Video Diffusion Models / RePaint): the known part of x is overwritten with the known clip diffused to a
+// level (a, b) = (sqrt(abar), sqrt(1 - abar)):
+//   kn = b == 0 ? known : a known + b z;      x <- m == 1 ? kn : (m == 0 ? x : m kn + (1 - m) x)
+// m: the mask value of the element's latent pixel, mask [B, F, HW] shared by the channels.  z: the caller's slab, or (z == NULL) drawn
+// here, bit for bit what fill_normal_kernel(seed, offset) writes for the element.  One thread per 16-byte access (hw4 = HW / 4, so a
+// quad never leaves its row): one mask quad and one Philox call per access.  frames_inner = 0: x [B, F, C, HW] (class-conditional
+// engine); 1: x [B, C, F, HW] (text-to-video).  The selects at m == 0 and m == 1 keep x and kn exact there: 0 * inf and the rounding
+// of 1 * kn + 0 * x never enter.  A quad whose four mask values are 0 is neither read nor written.
+__global__ void known_blend_kernel(float* __restrict__ x, const float* __restrict__ known, const float* __restrict__ mask,
+                                   const float* __restrict__ z, float a, float b, size_t quads, int F, int C, int hw4, int frames_inner,
+                                   unsigned long long seed, unsigned long long offset) {
+#pragma clang fp contract(off)
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (size_t)gridDim.x * blockDim.x) {
+    const size_t r4 = q % hw4, row = q / hw4;   // row = (b F + f) C + c, or (b C + c) F + f
+    const size_t bf = frames_inner ? (row / ((size_t)F * C)) * F + row % F : row / C;
+    const float4 m = ((const float4*)mask)[bf * hw4 + r4];
+    if (m.x == 0.0f && m.y == 0.0f && m.z == 0.0f && m.w == 0.0f) continue;
+    const float4 kv = ((const float4*)known)[q];
+    float kn[4] = {kv.x, kv.y, kv.z, kv.w};
+    if (b != 0.0f) {
+      float zz[4];
+      if (z) {
+        const float4 zv = ((const float4*)z)[q];
+        zz[0] = zv.x; zz[1] = zv.y; zz[2] = zv.z; zz[3] = zv.w;
+      } else {
+        philox_normal_quad(seed, offset, q, zz);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) kn[j] = a * kn[j] + b * zz[j];
+    }
+    const float4 xv = ((float4*)x)[q];
+    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ms[4] = {m.x, m.y, m.z, m.w};
+    float o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = ms[j] == 1.0f ? kn[j] : (ms[j] == 0.0f ? xs[j] : ms[j] * kn[j] + (1.0f - ms[j]) * xs[j]);
+    ((float4*)x)[q] = make_float4(o[0], o[1], o[2], o[3]);
   }
 }
 
@@ -1396,6 +1440,18 @@ int launch_pack_w8(const half_t* in, unsigned char* out, int64_t n, int dtype, h
 int launch_fill_normal(float* out, size_t n, uint64_t seed, uint64_t offset, hipStream_t st) {
   hipLaunchKernelGGL(fill_normal_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, st, out, n,
                      (unsigned long long)seed, (unsigned long long)offset);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+
+int launch_known_blend(float* x, const float* known, const float* mask, const float* z, uint64_t seed, uint64_t offset, float a, float b,
+                       int batch, int frames, int channels, int hw, int frames_inner, hipStream_t st) {
+  if (!x || !known || !mask) return fail(LATTE_ERR_INVALID, "known_blend: null argument");
+  if (batch <= 0 || frames <= 0 || channels <= 0 || hw <= 0) return fail(LATTE_ERR_INVALID, "known_blend: bad shape");
+  if (hw % 4) return fail(LATTE_ERR_INVALID, "known_blend: H * W must be a multiple of 4 (16-byte accesses)");
+  const size_t quads = (size_t)batch * frames * channels * (hw / 4);
+  hipLaunchKernelGGL(known_blend_kernel, dim3(grid_for(quads, 256)), dim3(256), 0, st, x, known, mask, z, a, b, quads, frames, channels,
+                     hw / 4, frames_inner ? 1 : 0, (unsigned long long)seed, (unsigned long long)offset);
   LATTE_HIP(hipGetLastError());
   return LATTE_OK;
 }

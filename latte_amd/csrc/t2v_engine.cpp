@@ -470,6 +470,53 @@ int latte_t2v_guided_ddim_loop(latte_t2v_t* e, float* x, int samples, int n_step
   return LATTE_OK;
 }
 
+// The guided DDIM loop with the known part of x replaced at the level each step reaches (include/latte_amd.h)
+int latte_t2v_guided_ddim_loop_known(latte_t2v_t* e, float* x, int samples, int n_steps, const int64_t* timesteps,
+                                     const double* alpha_t, const double* alpha_prev, float guidance_scale, const float* known,
+                                     const float* mask, const float* noise, int enable_temporal_attentions, void* stream) {
+  const char* who = "t2v_guided_ddim_loop_known";
+  if (!e || !x || !timesteps || !alpha_t || !alpha_prev || samples <= 0 || n_steps <= 0)
+    return fail(LATTE_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (!known || !mask || !noise)
+    return fail(LATTE_ERR_INVALID, std::string(who) + ": known, mask and noise [n_steps, ...] are required (this engine draws no noise)");
+  int rc = latte_t2v_check_weights(e);
+  if (rc) return rc;
+  const int B = 2 * samples;
+  if (B > e->max_batch) return fail(LATTE_ERR_STATE, std::string(who) + ": the guidance pair exceeds max_batch of the engine");
+  if (e->txt_batch != B)
+    return fail(LATTE_ERR_STATE, std::string(who) + ": install the text context of the guidance pair first "
+                                 "(latte_t2v_set_text with [negative | prompt] embeddings, 2 * samples rows)");
+  const auto& c = e->cfg;
+  if (c.out_channels != c.in_channels && c.out_channels != 2 * c.in_channels)
+    return fail(LATTE_ERR_INVALID, std::string(who) + ": out_channels must be C or 2C (learned sigma)");
+  const int HW = e->H * e->H;
+  if (HW % 4) return fail(LATTE_ERR_INVALID, std::string(who) + ": H * W must be a multiple of 4 (16-byte accesses of the blend kernel)");
+  if (n_steps > e->tsteps_cap) return fail(LATTE_ERR_INVALID, std::string(who) + ": more than 1024 steps");
+  for (int k = 0; k < n_steps; ++k)
+    if (!(alpha_t[k] > 0.0 && alpha_t[k] < 1.0) || !(alpha_prev[k] > 0.0 && alpha_prev[k] <= 1.0))
+      return fail(LATTE_ERR_INVALID, std::string(who) + ": alpha out of range");
+  hipStream_t st = (hipStream_t)stream;
+  LATTE_HIP(hipMemcpyAsync(e->tsteps, timesteps, sizeof(int64_t) * n_steps, hipMemcpyHostToDevice, st));
+  LATTE_HIP(hipStreamSynchronize(st));   // the caller's host array may go away
+  const size_t numel = (size_t)samples * c.in_channels * e->F * HW;
+  // slab 0: the blend at alpha_t[0] before step 0; slab k + 1: the blend at alpha_prev[k] after step k; the last step blends with (1, 0)
+  auto blend = [&](double abar, const float* nz) {
+    const bool clean = nz == nullptr;
+    return launch_known_blend(x, known, mask, nz, 0, 0, clean ? 1.0f : (float)std::sqrt(abar), clean ? 0.0f : (float)std::sqrt(1.0 - abar),
+                              samples, e->F, c.in_channels, HW, 1, st);
+  };
+  if ((rc = blend(alpha_t[0], noise))) return rc;
+  for (int k = 0; k < n_steps; ++k) {
+    if ((rc = t2v_core(e, x, e->tsteps + k, true, B, true, enable_temporal_attentions, st))) return rc;
+    const double at = alpha_t[k], ap = alpha_prev[k];
+    if ((rc = launch_t2v_guided_ddim(x, e->out_bf, samples, c.in_channels, c.out_channels, e->F, HW, guidance_scale,
+                                     (float)std::sqrt(1.0 - at), (float)std::sqrt(at), (float)std::sqrt(ap),
+                                     (float)std::sqrt(1.0 - ap), st))) return rc;
+    if ((rc = blend(ap, k + 1 < n_steps ? noise + (size_t)(k + 1) * numel : nullptr))) return rc;
+  }
+  return LATTE_OK;
+}
+
 int latte_t2v_guided_linear_loop(latte_t2v_t* e, float* x, int samples, int n_evals, const double* plan, const float* noise,
                                  float guidance_scale, int enable_temporal_attentions, void* stream) {
   if (!e || !x || !plan || samples <= 0 || n_evals <= 0) return fail(LATTE_ERR_INVALID, "t2v_guided_linear_loop: bad arguments");

@@ -8,7 +8,9 @@
   engine (``latte_sample_loop``; ``latte_invert_loop`` for DDIM inversion); any other callable following
   the model-callable protocol is driven step by step with the same update kernel;
 * ``linear_sample_loop`` (not in the reference): Euler, Euler-ancestral, Heun and DPM-Solver++(2M) on the diffusion's own
-  timesteps, as ONE ``latte_sample_plan_loop`` call for a ``latte_amd.Latte`` method.
+  timesteps, as ONE ``latte_sample_plan_loop`` call for a ``latte_amd.Latte`` method;
+* ``known_sample_loop`` (not in the reference): DDIM / DDPM with part of the clip held fixed (prediction, interpolation, inpainting by
+  replacement), as ``latte_sample_loop_known`` calls for a ``latte_amd.Latte`` method.
 """
 import ctypes
 
@@ -17,6 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import LatteError, check, load_library, ptr, stream_ptr
+from .known import known_blend, level_coefs
 from .models import Latte
 from .schedulers import (DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler,
                          HeunDiscreteScheduler)
@@ -338,13 +341,20 @@ class SpacedDiffusion:
             img = sch.step(eps, t, img, return_dict=False, noise=None if nz is None else nz[k])[0]
             yield {"sample": img, "pred_xstart": None}
 
+    @staticmethod
+    def _no_known(known, known_mask):
+        if known is not None or known_mask is not None:
+            raise LatteError("linear_sample_loop: no known-region sampling with the linear samplers -- their samples live at other noise "
+                             "levels (sigma-scaled) and Heun has intermediate states; use known_sample_loop (DDIM / DDPM)")
+
     def linear_sample_loop_progressive(self, model, shape, noise=None, method="dpmsolver++", model_kwargs=None, device=None,
-                                       progress=False, step_noise=None):
+                                       progress=False, step_noise=None, known=None, known_mask=None):
         """``linear_sample_loop`` yielding {"sample", "pred_xstart": None} after every denoiser evaluation."""
+        self._no_known(known, known_mask)
         yield from self._linear_loop(model, shape, noise, method, model_kwargs, device, progress, step_noise, True)
 
     def linear_sample_loop(self, model, shape, noise=None, method="dpmsolver++", model_kwargs=None, device=None, progress=False,
-                           step_noise=None):
+                           step_noise=None, known=None, known_mask=None):
         """Sampling with a linear multistep / Runge-Kutta sampler in place of DDIM / DDPM: ``method`` "euler", "euler_a" (ancestral),
         "heun" or "dpmsolver++" (2M) from ``latte_amd.schedulers``, on this diffusion's own ``timestep_map`` (``linear_scheduler``).  The
         initial latents are ``noise * init_noise_sigma``; the model sees ORIGINAL timesteps; the learned-sigma half of its output is
@@ -352,9 +362,157 @@ class SpacedDiffusion:
         the chain is ONE ``latte_sample_plan_loop`` call; any other callable is driven through the scheduler's ``scale_model_input`` /
         ``step``.  ``step_noise`` [n_evals, ...latents] gives the draws of the stochastic steps ("euler_a") to either path; without it
         the engine path draws from the engine's Philox stream (option "seed"), the step-by-step path from ``torch.randn``.  Run over the
-        same timesteps, "euler" is ``ddim_sample_loop(eta=0, clip_denoised=False)``.  No hooks (``denoised_fn`` / ``cond_fn``)."""
+        same timesteps, "euler" is ``ddim_sample_loop(eta=0, clip_denoised=False)``.  No hooks (``denoised_fn`` / ``cond_fn``), and no
+        known-region sampling: ``known`` / ``known_mask`` raise (``known_sample_loop`` serves DDIM / DDPM)."""
+        self._no_known(known, known_mask)
         final = None
         for final in self._linear_loop(model, shape, noise, method, model_kwargs, device, progress, step_noise, False):
+            pass
+        return final["sample"]
+
+    # ------------------------------------------------------------------ known-region sampling (not in the reference)
+    def known_chain_slabs(self, method="ddim", eta=0.0, resample=1, start_index=None, end_index=None, blend_start=True):
+        """The number of noise slabs (each of the latents' size) a known-region chain consumes: ``latte_known_chain_slabs``, the one
+        definition of the count and the order -- the start blend; then per repetition the step's own noise (DDPM at i > 0, DDIM where
+        sigma != 0), the blend's (i > 0), the forward jump's.  Host only."""
+        if method not in ("ddim", "ddpm"):
+            raise LatteError(f"known_sample_loop: method must be 'ddim' or 'ddpm', got {method!r}")
+        start, end = self._index_range(start_index, end_index, ascending=False)
+        n = _lib.c_i64(0)
+        check(load_library().latte_known_chain_slabs(self._h, _METHOD[method], float(eta), start, end, int(resample), int(bool(blend_start)),
+                                                     ctypes.byref(n)))
+        return int(n.value)
+
+    def _known_loop(self, method, model, shape, known, known_mask, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
+                    progress, eta, resample, start_index, end_index, chain_noise, blend_start, progressive):
+        resample = int(resample)
+        n_slabs = self.known_chain_slabs(method, eta, resample, start_index, end_index, blend_start)   # refuses resample < 1 too
+        _lib.require_gpu()
+        start, end = self._index_range(start_index, end_index, ascending=False)
+        model_kwargs = dict(model_kwargs or {})
+        owner, uses_cfg = self._engine_model(model)
+        if device is None and owner is None:                        # a plain callable: where the start, else the known clip, lives
+            device = noise.device if noise is not None else known.device
+        device = self._device(model, device)
+        assert isinstance(shape, (tuple, list))
+        img = noise if noise is not None else torch.randn(*shape, device=device)
+        img = img.to(device=device, dtype=torch.float32).contiguous().clone()
+        if img.dim() != 5:
+            raise LatteError("shape must be [N, F, C, H, W]")
+        B, F, C, H, W = img.shape
+        if (H * W) % 4:
+            raise LatteError("known_sample_loop: H * W must be a multiple of 4 (16-byte accesses of the blend kernel)")
+        owner, uses_cfg = self._engine_model(model)
+        kn = known.to(device=device, dtype=torch.float32)
+        mk = known_mask.to(device=device, dtype=torch.float32)
+        if kn.shape[0] * 2 == B:                                    # the doubled batch of forward_with_cfg: double them as z is doubled
+            kn = torch.cat([kn, kn])
+        if mk.shape[0] * 2 == B:
+            mk = torch.cat([mk, mk])
+        kn, mk = kn.contiguous(), mk.contiguous()
+        if kn.shape != img.shape:
+            raise LatteError(f"known_sample_loop: known must be {tuple(img.shape)}, got {tuple(kn.shape)}")
+        if tuple(mk.shape) != (B, F, H, W):
+            raise LatteError(f"known_sample_loop: known_mask must be [N, F, H, W] = {(B, F, H, W)}, got {tuple(mk.shape)}")
+        slabs = None
+        if chain_noise is not None:
+            if tuple(chain_noise.shape) != (n_slabs,) + tuple(img.shape):
+                raise LatteError(f"chain_noise must be [{n_slabs}, ...latents]: one slab per draw of the chain (known_chain_slabs)")
+            slabs = chain_noise.to(device=device, dtype=torch.float32).contiguous()
+        taken = 0
+
+        def take(cnt):   # the next cnt slabs: the caller's, else one torch.randn_like each, in slab order
+            nonlocal taken
+            taken += cnt
+            if cnt == 0:
+                return None
+            return slabs[taken - cnt:taken] if slabs is not None else torch.stack([torch.randn_like(img) for _ in range(cnt)])
+
+        lib = load_library()
+        engine_kwargs = {"y", "use_fp16", "cfg_scale", "text_embedding"}
+        if owner is not None and set(model_kwargs) <= engine_kwargs and denoised_fn is None and cond_fn is None:
+            # ---- whole chain inside the engine, in segments of consecutive indices as _loop segments its noise
+            x32, _, y64 = owner._prep(img, torch.zeros(B, dtype=torch.int64), model_kwargs.get("y"))
+            cfg_scale = float(model_kwargs.get("cfg_scale", 7.0)) if uses_cfg else 1.0
+            eng = owner.engine(B, guided=uses_cfg)
+            owner._set_text(model_kwargs.get("text_embedding"), B, guided=uses_cfg)
+            seg = max(1, min(self.num_timesteps, self.SEGMENT_BYTES // max(x32.numel() * 4 * 3 * resample, 1)))
+            i = start
+            while i >= end:
+                lo = max(end, i - seg + 1)
+                cnt = i - lo + 1
+                first = int(bool(blend_start) and i == start)
+                nz = take(self.known_chain_slabs(method, eta, resample, i, lo, first))
+                trail_s = trail_0 = None
+                if progressive:
+                    trail_s = torch.empty((cnt,) + tuple(x32.shape), device=device, dtype=torch.float32)
+                    trail_0 = torch.empty_like(trail_s)
+                with torch.cuda.device(device):
+                    check(lib.latte_sample_loop_known(eng, self._h, _METHOD[method], float(eta), int(bool(clip_denoised)), int(uses_cfg),
+                                                      cfg_scale, ptr(x32), ptr(y64), B, i, lo, ptr(kn), ptr(mk), resample, first, ptr(nz),
+                                                      ptr(trail_s), ptr(trail_0), stream_ptr()))
+                    if nz is not None or progressive:
+                        torch.cuda.current_stream().synchronize()      # the segment's buffers are released / handed out next
+                for k in range(cnt if progressive else 0):
+                    yield {"sample": trail_s[k], "pred_xstart": trail_0[k]}
+                i = lo - 1
+            assert taken == n_slabs
+            if not progressive:
+                yield {"sample": x32, "pred_xstart": None}
+            return
+        # ---- generic model callable, step by step: _step, then latte_known_blend, then the jump
+        def blend(x, abar, draws):
+            a, b = level_coefs(abar) if draws else (1.0, 0.0)
+            z = take(1) if draws else None
+            return known_blend(x, kn, mk, a, b, None if z is None else z[0])
+
+        if blend_start:
+            img = blend(img, self.alphas_cumprod[start], True)
+        indices = list(range(end, start + 1))[::-1]
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        for i in indices:
+            # the step's own draws: what the one-index chain takes besides its blend
+            step_draws = self.known_chain_slabs(method, eta, 1, i, i, False) - int(i > 0)
+            for u in range(1, resample + 1):
+                out = self._call_model(model, img, i, model_kwargs)
+                z = take(step_draws)
+                r = self._step(method, out, img, i, None if z is None else z[0], eta, clip_denoised, denoised_fn, cond_fn, model_kwargs)
+                img = blend(r["sample"], self.alphas_cumprod_prev[i], i > 0)
+                if u < resample and i > 0:                           # back to level i (RePaint's resampling)
+                    beta = np.float32(self.betas[i])
+                    img = float(np.sqrt(np.float32(1.0) - beta)) * img + float(np.sqrt(beta)) * take(1)[0]
+            yield {"sample": img, "pred_xstart": r["pred_xstart"]}
+        assert taken == n_slabs
+
+    def known_sample_loop_progressive(self, model, shape, known, known_mask, method="ddim", noise=None, clip_denoised=True,
+                                      model_kwargs=None, eta=0.0, resample=1, start_index=None, end_index=None, chain_noise=None,
+                                      device=None, progress=False, denoised_fn=None, cond_fn=None, blend_start=True):
+        """``known_sample_loop`` yielding {"sample", "pred_xstart"} after every respaced index (after the blend of its last
+        repetition)."""
+        yield from self._known_loop(method, model, shape, known, known_mask, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
+                                    device, progress, eta, resample, start_index, end_index, chain_noise, blend_start, True)
+
+    def known_sample_loop(self, model, shape, known, known_mask, method="ddim", noise=None, clip_denoised=True, model_kwargs=None,
+                          eta=0.0, resample=1, start_index=None, end_index=None, chain_noise=None, device=None, progress=False,
+                          denoised_fn=None, cond_fn=None, blend_start=True):
+        """Sampling with part of the clip held fixed -- animate a first frame, continue a clip, fill between key frames, repaint a
+        region -- by the replacement scheme of Video Diffusion Models / RePaint, on unchanged weights (not in the reference).  ``known``
+        [N, F, C, H, W]: the clean latents of the known clip; ``known_mask`` [N, F, H, W] (``latte_amd.known_mask``): 1 = known, 0 =
+        generated.  The chain is ``p_sample_loop`` / ``ddim_sample_loop`` (``method``) over ``start_index`` ... ``end_index``; before
+        the first step (``blend_start``) and after every step the known part of the sample is overwritten with ``known`` diffused to
+        the level the sample is at -- ``alphas_cumprod_prev[i]`` after index i, so the known part of the result is ``known`` bit for
+        bit.  ``resample`` > 1 repeats every index that many times with the one-level forward jump ``sqrt(1 - beta_i) x + sqrt(beta_i)
+        z`` between repetitions, which lets the generated part agree with the known part.  With ``forward_with_cfg`` on the doubled
+        batch, ``known`` / ``known_mask`` of half the batch are doubled as ``z`` is.
+        With ``model.forward`` / ``model.forward_with_cfg`` of a ``latte_amd.Latte``, known kwargs and no hooks the chain is ONE
+        ``latte_sample_loop_known`` call per segment; any other callable goes step by step through the step kernel and
+        ``latte_known_blend``.  ``chain_noise`` [known_chain_slabs(...), ...latents] gives every draw to either path, in slab order;
+        without it each slab is one ``torch.randn_like``.  The linear samplers have no known-region form (``linear_sample_loop``)."""
+        final = None
+        for final in self._known_loop(method, model, shape, known, known_mask, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
+                                      device, progress, eta, resample, start_index, end_index, chain_noise, blend_start, False):
             pass
         return final["sample"]
 

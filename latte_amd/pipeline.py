@@ -124,6 +124,63 @@ class LattePipeline:
         a_p = [float(sch.alphas_cumprod[t - ratio]) if t - ratio >= 0 else float(sch.final_alpha_cumprod) for t in ts]
         return ts, a_t, a_p
 
+    def _known_loop(self, latents, known, mask, steps, prompt_embeds, do_cfg, guidance_scale, eta, generator, callback, callback_steps,
+                    enable_temporal_attentions):
+        """The denoising loop with the known part of the latents replaced: ONE
+        ``latte_t2v_guided_ddim_loop_known`` call when guidance is on, there is no callback and ``allow_fused_loop`` is set; else the
+        step-by-step loop with one ``latte_known_blend`` launch before the first step and after every step."""
+        import numpy as np
+        from .known import known_blend
+        from .schedulers import DDIMScheduler, draw_noise
+        from .t2v import LatteT2V
+        sch, tr = self.scheduler, self.transformer
+        if type(sch) is not DDIMScheduler or eta != 0.0 or sch.clip_sample:
+            raise LatteError("known_latents: known-region sampling runs on latte_amd.DDIMScheduler at eta = 0 without clipping only -- the "
+                             "samples of the other schedulers live at other noise levels and Heun has intermediate states")
+        cfg = tr.config
+        device = latents.device
+        b, C, F, H, W = latents.shape
+        known = known.to(device=device, dtype=torch.float32).contiguous()
+        mask = mask.to(device=device, dtype=torch.float32).contiguous()
+        if known.shape != latents.shape or tuple(mask.shape) != (b, F, H, W):
+            raise LatteError(f"known_latents must be {tuple(latents.shape)} and known_mask {(b, F, H, W)}, got {tuple(known.shape)} and "
+                             f"{tuple(mask.shape)}")
+        if (H * W) % 4:
+            raise LatteError("known_latents: h * w must be a multiple of 4 (16-byte accesses of the blend kernel)")
+        ts = [int(t) for t in steps]
+        ratio = sch.num_train_timesteps // sch.num_inference_steps
+        a_t = [float(sch.alphas_cumprod[t]) for t in ts]
+        a_p = [float(sch.alphas_cumprod[t - ratio]) if t - ratio >= 0 else float(sch.final_alpha_cumprod) for t in ts]
+        # slab 0: the blend before step 0; slab k + 1: the blend after step k (the last step takes none)
+        noise = torch.stack([draw_noise(latents.shape, generator, device, latents.dtype) for _ in ts])
+        if (do_cfg and callback is None and isinstance(tr, LatteT2V) and cfg.out_channels in (C, 2 * C)
+                and getattr(self, "allow_fused_loop", True)):
+            tr.set_text(prompt_embeds)
+            return tr.guided_ddim_loop_known(latents, ts, a_t, a_p, guidance_scale, known, mask, noise, enable_temporal_attentions)
+
+        def blend(x, abar, z):   # the engine's coefficients: fp64 square roots narrowed to fp32
+            a, bb = (1.0, 0.0) if z is None else (float(np.float32(np.sqrt(abar))), float(np.float32(np.sqrt(1.0 - abar))))
+            return known_blend(x.to(dtype=torch.float32).contiguous(), known, mask, a, bb, z, frames_inner=True)
+
+        added_cond_kwargs = {"resolution": None, "aspect_ratio": None}
+        latents = blend(latents.clone(), a_t[0], noise[0])
+        for i, t in enumerate(steps):
+            x_in = sch.scale_model_input(torch.cat([latents] * 2) if do_cfg else latents, t)
+            current = t if torch.is_tensor(t) else torch.tensor([t], dtype=torch.int64, device=device)
+            current = current.reshape(-1)[:1].to(device).expand(x_in.shape[0])
+            noise_pred = tr(x_in, encoder_hidden_states=prompt_embeds, timestep=current, added_cond_kwargs=added_cond_kwargs,
+                            enable_temporal_attentions=enable_temporal_attentions, return_dict=False)[0]
+            if do_cfg:
+                uncond, text = noise_pred.chunk(2)
+                noise_pred = uncond + guidance_scale * (text - uncond)
+            if cfg.out_channels // 2 == C:
+                noise_pred = noise_pred.chunk(2, dim=1)[0]
+            latents = sch.step(noise_pred, t, latents, eta=0.0, return_dict=False)[0]
+            latents = blend(latents, a_p[i], noise[i + 1] if i + 1 < len(ts) else None)
+            if callback is not None and i % callback_steps == 0:
+                callback(i, t, latents)
+        return latents
+
     def _fused_plan(self, do_cfg, callback, latent_channels, scheduler=None):
         """The scheduler's ``engine_plan()`` table when the chain can run inside the engine as latte_t2v_guided_linear_loop: guidance
         on, no per-step callback, the engine transformer, a scheduler that describes its update as such a table (Euler,
@@ -223,7 +280,13 @@ class LattePipeline:
                  num_images_per_prompt=1, video_length=None, height=None, width=None, eta=0.0, generator=None, latents=None,
                  prompt_embeds=None, negative_prompt_embeds=None, output_type="pil", return_dict=True, callback=None,
                  callback_steps=1, clean_caption=True, mask_feature=True, enable_temporal_attentions=True,
-                 enable_vae_temporal_decoder=False):
+                 enable_vae_temporal_decoder=False, known_latents=None, known_mask=None):
+        """``known_latents`` [B, 4, F, h, w] with ``known_mask`` [B, F, h, w] (``latte_amd.known_mask``; 1 = known) hold part of the clip
+        fixed and generate the rest (not in the reference): before the first step and after every step the known part of the latents
+        is overwritten with ``known_latents`` diffused to the level the latents are at, the clean ones after the last step.  DDIM
+        scheduler of latte_amd at eta = 0 only; the noise comes from ``generator``, one latent-shaped draw per step, in slab order."""
+        if (known_latents is None) != (known_mask is None):
+            raise LatteError("known_latents and known_mask come together")
         if enable_vae_temporal_decoder and not getattr(self.vae, "_TEMPORAL", False):
             raise LatteError("enable_vae_temporal_decoder=True needs a latte_amd.AutoencoderKLTemporalDecoder as the pipeline's vae "
                              "(sample_t2x.py:31-32 loads it from subfolder 'vae_temporal_decoder')")
@@ -259,14 +322,18 @@ class LattePipeline:
         if "generator" in params:
             extra["generator"] = generator
         added_cond_kwargs = {"resolution": None, "aspect_ratio": None}
-        fused = self._fused_loop(steps, do_cfg, eta, callback, latent_channels)
+        if known_latents is not None:
+            latents = self._known_loop(latents, known_latents, known_mask, steps, prompt_embeds, do_cfg, guidance_scale, eta, generator,
+                                       callback, callback_steps, enable_temporal_attentions)
+            steps = []
+        fused = self._fused_loop(steps, do_cfg, eta, callback, latent_channels) if known_latents is None else None
         if fused is not None:
             # the whole guided DDIM chain inside the engine: no torch op between the first and the last step
             self.transformer.set_text(prompt_embeds)
             latents = self.transformer.guided_ddim_loop(latents, fused[0], fused[1], fused[2], guidance_scale,
                                                         enable_temporal_attentions)
             steps = []
-        plan = self._fused_plan(do_cfg, callback, latent_channels) if fused is None else None
+        plan = self._fused_plan(do_cfg, callback, latent_channels) if fused is None and known_latents is None else None
         if plan is not None:
             # the same chain for every sampler with a linear update: one table, one engine call.  A stochastic sampler's noise is
             # drawn up front by the calls its step() would make, in order, so both loops consume the generator alike
