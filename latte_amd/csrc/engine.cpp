@@ -575,44 +575,6 @@ bool step_needs_noise(int method, const SamplerCoefs& c, int index) {
   return method == LATTE_METHOD_DDPM ? index != 0 : (c.sigma != 0.0f && index != 0);
 }
 
-// latte_sample_loop_ex (dir = -1: start_index down to end_index) and latte_invert_loop (dir = +1: start_index up to end_index)
-int sampler_chain(const std::string& who, latte_engine* e, const latte_schedule_t* s, int method, int dir, float eta, int clip_denoised,
-                  int guided, float cfg_scale, float* x, const int64_t* y, int batch, int start_index, int end_index, const float* noise,
-                  float* trail_sample, float* trail_x0, hipStream_t st) {
-  if (!e || !s || !x) return fail(LATTE_ERR_INVALID, who + ": null argument");
-  int rc = latte_engine_check_weights(e);
-  if (rc) return rc;
-  if ((rc = range_check(who, s->num_timesteps, dir > 0 ? start_index : end_index, dir > 0 ? end_index : start_index,
-                        "learned-range variance needs >= 2 timesteps"))) return rc;
-  const bool use_cfg = guided != 0;   // forward_with_cfg semantics for ANY scale (latte.py:379-398 has no threshold)
-  if ((rc = chain_check(who, e, s, batch, use_cfg, y, true))) return rc;
-  // ---- conditioning of the whole chain: it depends on (timestep, label) only, never on x.
-  //   temb[i]      = t_embedder(timestep_map[i])           (own, or the table installed after the RCCL broadcast)
-  //   c[i, b]      = SiLU(temb[i] (+ y_embedder(y[b])))     latte.py:337,348 (+ the SiLU of :173)
-  //   mod[i, b, :] = all 28 adaLN_modulation + the final layer's, = Linear(SiLU(c))   latte.py:172-178,192-198
-  // Unconditional models have one row per step shared by every sample (row stride 0).  The adaLN weights (0.9 GB
-  // fp32) are then streamed once per 64 rows instead of once per denoising step.
-  const int n_run = (end_index - start_index) * dir + 1;
-  ChainCond cc;
-  if ((rc = chain_prepare(e, s, e->cfg.extras == 1 ? 1 : batch, n_run, st, &cc))) return rc;
-  const size_t numel = (size_t)batch * e->F * e->Cin * e->H * e->H;
-  for (int k = 0; k < n_run; ++k) {
-    const int i = start_index + dir * k;
-    const float* mod_i;
-    int mstride;
-    if ((rc = chain_mod(e, &cc, y, i, end_index, st, &mod_i, &mstride))) return rc;
-    if ((rc = run_forward(e, x, nullptr, y, batch, use_cfg, e->model_out, st, nullptr, mod_i, mstride))) return rc;
-    SamplerCoefs c = make_coefs(s, method, i, eta, clip_denoised);
-    c.cfg_scale = cfg_scale;
-    const float* nz = nullptr;
-    if (step_needs_noise(method, c, i) && (rc = chain_noise(e, noise, k, numel, st, &nz))) return rc;
-    float* x0 = trail_x0 ? trail_x0 + (size_t)k * numel : nullptr;
-    if ((rc = launch_sampler_update(c, x, e->model_out, nz, batch, e->F, e->Cin, e->H * e->H, use_cfg ? 1 : 0, x, x0, st))) return rc;
-    if ((rc = chain_trail(trail_sample, k, x, numel, st))) return rc;
-  }
-  return LATTE_OK;
-}
-
 // ---- known-region sampling: the noise slabs of a chain, in the order they are consumed.
 // Repetition u (1 ... resample) of index i takes, in this order: the step's own noise, the noise of the blend that follows it, and
 // the noise of the forward jump back to level i.  The chain loop and latte_known_chain_slabs both walk this.
@@ -636,26 +598,52 @@ int known_method_check(const std::string& who, int method, int resample) {
   return LATTE_OK;
 }
 
-// latte_sample_loop_known: sampler_chain's descending walk with the known part of x replaced after every step
-int known_chain(const std::string& who, latte_engine* e, const latte_schedule_t* s, int method, float eta, int clip_denoised, int guided,
-                float cfg_scale, float* x, const int64_t* y, int batch, int start_index, int end_index, const float* known,
-                const float* mask, int resample, int blend_start, const float* noise, float* trail_sample, float* trail_x0,
-                hipStream_t st) {
+// The known part of a chain (latte_sample_loop_known): after every step the known part of x is replaced by `known` at the level x is at
+struct KnownRegion {
+  const float *known, *mask;
+  int resample;      // repetitions of every index, the one-level forward jump between them
+  int blend_start;   // blend at the level of start_index before the first step
+};
+
+// The caller's noise rows, two public contracts: a plain chain reads row k at step k (a DDPM step at index 0 has a row and skips it), a
+// known chain reads the next unconsumed slab.  Engine-drawn noise (noise == NULL) never asks.
+struct NoiseCursor {
+  bool by_step;
+  int next = 0;
+  int row(int k) { return by_step ? k : next++; }
+};
+
+// latte_sample_loop_ex (dir = -1: start_index down to end_index), latte_invert_loop (dir = +1: start_index up to end_index) and
+// latte_sample_loop_known (dir = -1 with `kn`: every index `resample` times, the known part of x replaced after every step)
+int sampler_chain(const std::string& who, latte_engine* e, const latte_schedule_t* s, int method, int dir, float eta, int clip_denoised,
+                  int guided, float cfg_scale, float* x, const int64_t* y, int batch, int start_index, int end_index, const KnownRegion* kn,
+                  const float* noise, float* trail_sample, float* trail_x0, hipStream_t st) {
   if (!e || !s || !x) return fail(LATTE_ERR_INVALID, who + ": null argument");
   int rc = latte_engine_check_weights(e);
   if (rc) return rc;
-  if ((rc = range_check(who, s->num_timesteps, end_index, start_index, "learned-range variance needs >= 2 timesteps"))) return rc;
-  const bool use_cfg = guided != 0;
+  if ((rc = range_check(who, s->num_timesteps, dir > 0 ? start_index : end_index, dir > 0 ? end_index : start_index,
+                        "learned-range variance needs >= 2 timesteps"))) return rc;
+  const bool use_cfg = guided != 0;   // forward_with_cfg semantics for ANY scale (latte.py:379-398 has no threshold)
   if ((rc = chain_check(who, e, s, batch, use_cfg, y, true))) return rc;
-  if ((rc = known_method_check(who, method, resample))) return rc;
-  if (!known || !mask) return fail(LATTE_ERR_INVALID, who + ": known and mask are required");
   const int HW = e->H * e->H;
-  if (HW % 4) return fail(LATTE_ERR_INVALID, who + ": H * W must be a multiple of 4 (16-byte accesses of the blend kernel)");
-  const int n_run = start_index - end_index + 1;
+  if (kn) {
+    if ((rc = known_method_check(who, method, kn->resample))) return rc;
+    if (!kn->known || !kn->mask) return fail(LATTE_ERR_INVALID, who + ": known and mask are required");
+    if (HW % 4) return fail(LATTE_ERR_INVALID, who + ": H * W must be a multiple of 4 (16-byte accesses of the blend kernel)");
+    if (dir > 0) return fail(LATTE_ERR_INVALID, who + ": a known region needs a descending chain");
+  }
+  // ---- conditioning of the whole chain: it depends on (timestep, label) only, never on x.
+  //   temb[i]      = t_embedder(timestep_map[i])           (own, or the table installed after the RCCL broadcast)
+  //   c[i, b]      = SiLU(temb[i] (+ y_embedder(y[b])))     latte.py:337,348 (+ the SiLU of :173)
+  //   mod[i, b, :] = all 28 adaLN_modulation + the final layer's, = Linear(SiLU(c))   latte.py:172-178,192-198
+  // Unconditional models have one row per step shared by every sample (row stride 0).  The adaLN weights (0.9 GB
+  // fp32) are then streamed once per 64 rows instead of once per denoising step.
+  const int n_run = (end_index - start_index) * dir + 1;
   ChainCond cc;
   if ((rc = chain_prepare(e, s, e->cfg.extras == 1 ? 1 : batch, n_run, st, &cc))) return rc;
   const size_t numel = (size_t)batch * e->F * e->Cin * HW;
-  int slab = 0;   // the next row of the caller's noise
+  const int reps = kn ? kn->resample : 1;
+  NoiseCursor cur{kn == nullptr};
   // one blend at the level abar; its noise is the caller's next slab, or drawn in the kernel from the engine's stream
   // (level 0 takes none: alphas_cumprod_prev[0] = 1 gives (1, 0))
   auto blend = [&](double abar, bool takes_slab) -> int {
@@ -664,31 +652,30 @@ int known_chain(const std::string& who, latte_engine* e, const latte_schedule_t*
     const uint64_t off = e->rng_offset;
     if (takes_slab) {
       level_coefs(abar, &a, &b);
-      if (noise) nz = noise + (size_t)slab++ * numel;
+      if (noise) nz = noise + (size_t)cur.row(0) * numel;
       else e->rng_offset += numel;
     }
-    return launch_known_blend(x, known, mask, nz, e->seed, off, a, b, batch, e->F, e->Cin, HW, 0, st);
+    return launch_known_blend(x, kn->known, kn->mask, nz, e->seed, off, a, b, batch, e->F, e->Cin, HW, 0, st);
   };
-  if (blend_start && (rc = blend(s->alphas_cumprod[start_index], true))) return rc;
+  if (kn && kn->blend_start && (rc = blend(s->alphas_cumprod[start_index], true))) return rc;
   for (int k = 0; k < n_run; ++k) {
-    const int i = start_index - k;
+    const int i = start_index + dir * k;
     const float* mod_i;
     int mstride;
     if ((rc = chain_mod(e, &cc, y, i, end_index, st, &mod_i, &mstride))) return rc;
     SamplerCoefs c = make_coefs(s, method, i, eta, clip_denoised);
     c.cfg_scale = cfg_scale;
     float* x0 = trail_x0 ? trail_x0 + (size_t)k * numel : nullptr;
-    for (int u = 1; u <= resample; ++u) {
-      const KnownSlabs need = known_slabs(method, c, i, u, resample);
+    for (int u = 1; u <= reps; ++u) {
+      const KnownSlabs need = known_slabs(method, c, i, u, reps);   // a plain chain takes the step's noise only
       if ((rc = run_forward(e, x, nullptr, y, batch, use_cfg, e->model_out, st, nullptr, mod_i, mstride))) return rc;
       const float* nz = nullptr;
-      if (need.step && (rc = chain_noise(e, noise, slab, numel, st, &nz))) return rc;
-      if (need.step && noise) ++slab;
+      if (need.step && (rc = chain_noise(e, noise, cur.row(k), numel, st, &nz))) return rc;
       if ((rc = launch_sampler_update(c, x, e->model_out, nz, batch, e->F, e->Cin, HW, use_cfg ? 1 : 0, x, x0, st))) return rc;
+      if (!kn) continue;
       if ((rc = blend(s->alphas_cumprod_prev[i], need.blend))) return rc;   // (1, 0) at i == 0: the known latents themselves
       if (need.jump) {   // back to level i: x <- sqrt(1 - beta_i) x + sqrt(beta_i) z, in place
-        if ((rc = chain_noise(e, noise, slab, numel, st, &nz))) return rc;
-        if (noise) ++slab;
+        if ((rc = chain_noise(e, noise, cur.row(k), numel, st, &nz))) return rc;
         const float beta = (float)s->betas[i];
         if ((rc = launch_q_sample_scalar(std::sqrt(1.0f - beta), std::sqrt(beta), x, nz, numel, x, st))) return rc;
       }
@@ -1038,8 +1025,8 @@ int latte_sample_loop(latte_engine_t* e, const latte_schedule_t* s, int method, 
 int latte_sample_loop_ex(latte_engine_t* e, const latte_schedule_t* s, int method, float eta, int clip_denoised, int guided,
                          float cfg_scale, float* x, const int64_t* y, int batch, int start_index, int end_index,
                          const float* noise, float* trail_sample, float* trail_x0, void* stream) {
-  return sampler_chain("sample_loop", e, s, method, -1, eta, clip_denoised, guided, cfg_scale, x, y, batch, start_index, end_index, noise,
-                       trail_sample, trail_x0, (hipStream_t)stream);
+  return sampler_chain("sample_loop", e, s, method, -1, eta, clip_denoised, guided, cfg_scale, x, y, batch, start_index, end_index, nullptr,
+                       noise, trail_sample, trail_x0, (hipStream_t)stream);
 }
 
 // ---- DDIM inversion (gaussian_diffusion.py:566-602 ddim_reverse_sample, stepped over ascending indices: index i carries level i to
@@ -1047,7 +1034,7 @@ int latte_sample_loop_ex(latte_engine_t* e, const latte_schedule_t* s, int metho
 int latte_invert_loop(latte_engine_t* e, const latte_schedule_t* s, int clip_denoised, int guided, float cfg_scale, float* x,
                       const int64_t* y, int batch, int start_index, int end_index, float* trail_sample, float* trail_x0, void* stream) {
   return sampler_chain("invert_loop", e, s, LATTE_METHOD_DDIM_REVERSE, +1, 0.0f, clip_denoised, guided, cfg_scale, x, y, batch, start_index,
-                       end_index, nullptr, trail_sample, trail_x0, (hipStream_t)stream);
+                       end_index, nullptr, nullptr, trail_sample, trail_x0, (hipStream_t)stream);
 }
 
 // ---- known-region sampling: prediction, interpolation, inpainting by replacement (include/latte_amd.h)
@@ -1055,8 +1042,9 @@ int latte_sample_loop_known(latte_engine_t* e, const latte_schedule_t* s, int me
                             float cfg_scale, float* x, const int64_t* y, int batch, int start_index, int end_index, const float* known,
                             const float* mask, int resample, int blend_start, const float* noise, float* trail_sample, float* trail_x0,
                             void* stream) {
-  return known_chain("sample_loop_known", e, s, method, eta, clip_denoised, guided, cfg_scale, x, y, batch, start_index, end_index, known,
-                     mask, resample, blend_start, noise, trail_sample, trail_x0, (hipStream_t)stream);
+  const KnownRegion kn{known, mask, resample, blend_start};
+  return sampler_chain("sample_loop_known", e, s, method, -1, eta, clip_denoised, guided, cfg_scale, x, y, batch, start_index, end_index, &kn,
+                       noise, trail_sample, trail_x0, (hipStream_t)stream);
 }
 
 int latte_known_chain_slabs(const latte_schedule_t* s, int method, float eta, int start_index, int end_index, int resample,

@@ -439,102 +439,95 @@ int latte_t2v_forward(latte_t2v_t* e, const float* x, const int64_t* t, const fl
   return launch_permute_cf(e->out_bf, out, batch, c.out_channels, e->F, e->H * e->H, 0, st);   // back to [B, C, F, H, W]
 }
 
+// The argument block the three guided loops share: loaded weights, the guidance pair within max_batch, its text context, C or 2C outputs
+static int t2v_chain_check(const std::string& who, latte_t2v* e, int samples) {
+  int rc = latte_t2v_check_weights(e);
+  if (rc) return rc;
+  const int B = 2 * samples;
+  if (B > e->max_batch) return fail(LATTE_ERR_STATE, who + ": the guidance pair exceeds max_batch of the engine");
+  if (e->txt_batch != B)
+    return fail(LATTE_ERR_STATE, who + ": install the text context of the guidance pair first "
+                                 "(latte_t2v_set_text with [negative | prompt] embeddings, 2 * samples rows)");
+  const auto& c = e->cfg;
+  if (c.out_channels != c.in_channels && c.out_channels != 2 * c.in_channels)
+    return fail(LATTE_ERR_INVALID, who + ": out_channels must be C or 2C (learned sigma)");
+  return LATTE_OK;
+}
+
+// n host timesteps (n <= tsteps_cap, checked by the caller) into e->tsteps
+static int t2v_upload_timesteps(latte_t2v* e, const int64_t* ts, int n, hipStream_t st) {
+  LATTE_HIP(hipMemcpyAsync(e->tsteps, ts, sizeof(int64_t) * n, hipMemcpyHostToDevice, st));
+  LATTE_HIP(hipStreamSynchronize(st));   // the caller's host array may go away
+  return LATTE_OK;
+}
+
+// The guided DDIM loop (diffusers DDIMScheduler.step, eta = 0, no clipping).  With `known`, the known part of x is replaced at the level
+// each step reaches: noise slab 0 for the blend at alpha_t[0] before step 0, slab k + 1 for the blend at alpha_prev[k] after step k; the
+// last step blends with (1, 0).  known == NULL: no blends, no noise read.
+static int t2v_ddim_chain(const std::string& who, latte_t2v* e, float* x, int samples, int n_steps, const int64_t* timesteps,
+                          const double* alpha_t, const double* alpha_prev, float guidance_scale, const float* known, const float* mask,
+                          const float* noise, int enable_temporal_attentions, hipStream_t st) {
+  int rc = t2v_chain_check(who, e, samples);
+  if (rc) return rc;
+  const auto& c = e->cfg;
+  const int B = 2 * samples, HW = e->H * e->H;
+  if (known && HW % 4) return fail(LATTE_ERR_INVALID, who + ": H * W must be a multiple of 4 (16-byte accesses of the blend kernel)");
+  if (n_steps > e->tsteps_cap) return fail(LATTE_ERR_INVALID, who + ": more than 1024 steps");
+  for (int k = 0; k < n_steps; ++k)
+    if (!(alpha_t[k] > 0.0 && alpha_t[k] < 1.0) || !(alpha_prev[k] > 0.0 && alpha_prev[k] <= 1.0))
+      return fail(LATTE_ERR_INVALID, who + ": alpha out of range");
+  if ((rc = t2v_upload_timesteps(e, timesteps, n_steps, st))) return rc;
+  const size_t numel = (size_t)samples * c.in_channels * e->F * HW;
+  auto blend = [&](double abar, const float* nz) {
+    const bool clean = nz == nullptr;
+    return launch_known_blend(x, known, mask, nz, 0, 0, clean ? 1.0f : (float)std::sqrt(abar), clean ? 0.0f : (float)std::sqrt(1.0 - abar),
+                              samples, e->F, c.in_channels, HW, 1, st);
+  };
+  if (known && (rc = blend(alpha_t[0], noise))) return rc;
+  for (int k = 0; k < n_steps; ++k) {
+    if ((rc = t2v_core(e, x, e->tsteps + k, true, B, true, enable_temporal_attentions, st))) return rc;
+    // Python-float coefficients times fp32 tensors
+    const double at = alpha_t[k], ap = alpha_prev[k];
+    if ((rc = launch_t2v_guided_ddim(x, e->out_bf, samples, c.in_channels, c.out_channels, e->F, HW, guidance_scale,
+                                     (float)std::sqrt(1.0 - at), (float)std::sqrt(at), (float)std::sqrt(ap),
+                                     (float)std::sqrt(1.0 - ap), st))) return rc;
+    if (known && (rc = blend(ap, k + 1 < n_steps ? noise + (size_t)(k + 1) * numel : nullptr))) return rc;
+  }
+  return LATTE_OK;
+}
+
 int latte_t2v_guided_ddim_loop(latte_t2v_t* e, float* x, int samples, int n_steps, const int64_t* timesteps,
                                const double* alpha_t, const double* alpha_prev, float guidance_scale,
                                int enable_temporal_attentions, void* stream) {
   if (!e || !x || !timesteps || !alpha_t || !alpha_prev || samples <= 0 || n_steps <= 0)
     return fail(LATTE_ERR_INVALID, "t2v_guided_ddim_loop: bad arguments");
-  int rc = latte_t2v_check_weights(e);
-  if (rc) return rc;
-  const int B = 2 * samples;
-  if (B > e->max_batch) return fail(LATTE_ERR_STATE, "t2v_guided_ddim_loop: the guidance pair exceeds max_batch of the engine");
-  if (e->txt_batch != B)
-    return fail(LATTE_ERR_STATE, "t2v_guided_ddim_loop: install the text context of the guidance pair first "
-                                 "(latte_t2v_set_text with [negative | prompt] embeddings, 2 * samples rows)");
-  const auto& c = e->cfg;
-  if (c.out_channels != c.in_channels && c.out_channels != 2 * c.in_channels)
-    return fail(LATTE_ERR_INVALID, "t2v_guided_ddim_loop: out_channels must be C or 2C (learned sigma)");
-  hipStream_t st = (hipStream_t)stream;
-  if (n_steps > e->tsteps_cap) return fail(LATTE_ERR_INVALID, "t2v_guided_ddim_loop: more than 1024 steps");
-  LATTE_HIP(hipMemcpyAsync(e->tsteps, timesteps, sizeof(int64_t) * n_steps, hipMemcpyHostToDevice, st));
-  LATTE_HIP(hipStreamSynchronize(st));   // the caller's host array may go away
-  for (int k = 0; k < n_steps; ++k) {
-    if ((rc = t2v_core(e, x, e->tsteps + k, true, B, true, enable_temporal_attentions, st))) return rc;
-    // diffusers DDIMScheduler.step, eta = 0, no clipping: Python-float coefficients times fp32 tensors
-    const double at = alpha_t[k], ap = alpha_prev[k];
-    if (!(at > 0.0 && at < 1.0) || !(ap > 0.0 && ap <= 1.0)) return fail(LATTE_ERR_INVALID, "t2v_guided_ddim_loop: alpha out of range");
-    if ((rc = launch_t2v_guided_ddim(x, e->out_bf, samples, c.in_channels, c.out_channels, e->F, e->H * e->H, guidance_scale,
-                                     (float)std::sqrt(1.0 - at), (float)std::sqrt(at), (float)std::sqrt(ap),
-                                     (float)std::sqrt(1.0 - ap), st))) return rc;
-  }
-  return LATTE_OK;
+  return t2v_ddim_chain("t2v_guided_ddim_loop", e, x, samples, n_steps, timesteps, alpha_t, alpha_prev, guidance_scale, nullptr, nullptr,
+                        nullptr, enable_temporal_attentions, (hipStream_t)stream);
 }
 
 // The guided DDIM loop with the known part of x replaced at the level each step reaches (include/latte_amd.h)
 int latte_t2v_guided_ddim_loop_known(latte_t2v_t* e, float* x, int samples, int n_steps, const int64_t* timesteps,
                                      const double* alpha_t, const double* alpha_prev, float guidance_scale, const float* known,
                                      const float* mask, const float* noise, int enable_temporal_attentions, void* stream) {
-  const char* who = "t2v_guided_ddim_loop_known";
-  if (!e || !x || !timesteps || !alpha_t || !alpha_prev || samples <= 0 || n_steps <= 0)
-    return fail(LATTE_ERR_INVALID, std::string(who) + ": bad arguments");
+  const std::string who = "t2v_guided_ddim_loop_known";
+  if (!e || !x || !timesteps || !alpha_t || !alpha_prev || samples <= 0 || n_steps <= 0) return fail(LATTE_ERR_INVALID, who + ": bad arguments");
   if (!known || !mask || !noise)
-    return fail(LATTE_ERR_INVALID, std::string(who) + ": known, mask and noise [n_steps, ...] are required (this engine draws no noise)");
-  int rc = latte_t2v_check_weights(e);
-  if (rc) return rc;
-  const int B = 2 * samples;
-  if (B > e->max_batch) return fail(LATTE_ERR_STATE, std::string(who) + ": the guidance pair exceeds max_batch of the engine");
-  if (e->txt_batch != B)
-    return fail(LATTE_ERR_STATE, std::string(who) + ": install the text context of the guidance pair first "
-                                 "(latte_t2v_set_text with [negative | prompt] embeddings, 2 * samples rows)");
-  const auto& c = e->cfg;
-  if (c.out_channels != c.in_channels && c.out_channels != 2 * c.in_channels)
-    return fail(LATTE_ERR_INVALID, std::string(who) + ": out_channels must be C or 2C (learned sigma)");
-  const int HW = e->H * e->H;
-  if (HW % 4) return fail(LATTE_ERR_INVALID, std::string(who) + ": H * W must be a multiple of 4 (16-byte accesses of the blend kernel)");
-  if (n_steps > e->tsteps_cap) return fail(LATTE_ERR_INVALID, std::string(who) + ": more than 1024 steps");
-  for (int k = 0; k < n_steps; ++k)
-    if (!(alpha_t[k] > 0.0 && alpha_t[k] < 1.0) || !(alpha_prev[k] > 0.0 && alpha_prev[k] <= 1.0))
-      return fail(LATTE_ERR_INVALID, std::string(who) + ": alpha out of range");
-  hipStream_t st = (hipStream_t)stream;
-  LATTE_HIP(hipMemcpyAsync(e->tsteps, timesteps, sizeof(int64_t) * n_steps, hipMemcpyHostToDevice, st));
-  LATTE_HIP(hipStreamSynchronize(st));   // the caller's host array may go away
-  const size_t numel = (size_t)samples * c.in_channels * e->F * HW;
-  // slab 0: the blend at alpha_t[0] before step 0; slab k + 1: the blend at alpha_prev[k] after step k; the last step blends with (1, 0)
-  auto blend = [&](double abar, const float* nz) {
-    const bool clean = nz == nullptr;
-    return launch_known_blend(x, known, mask, nz, 0, 0, clean ? 1.0f : (float)std::sqrt(abar), clean ? 0.0f : (float)std::sqrt(1.0 - abar),
-                              samples, e->F, c.in_channels, HW, 1, st);
-  };
-  if ((rc = blend(alpha_t[0], noise))) return rc;
-  for (int k = 0; k < n_steps; ++k) {
-    if ((rc = t2v_core(e, x, e->tsteps + k, true, B, true, enable_temporal_attentions, st))) return rc;
-    const double at = alpha_t[k], ap = alpha_prev[k];
-    if ((rc = launch_t2v_guided_ddim(x, e->out_bf, samples, c.in_channels, c.out_channels, e->F, HW, guidance_scale,
-                                     (float)std::sqrt(1.0 - at), (float)std::sqrt(at), (float)std::sqrt(ap),
-                                     (float)std::sqrt(1.0 - ap), st))) return rc;
-    if ((rc = blend(ap, k + 1 < n_steps ? noise + (size_t)(k + 1) * numel : nullptr))) return rc;
-  }
-  return LATTE_OK;
+    return fail(LATTE_ERR_INVALID, who + ": known, mask and noise [n_steps, ...] are required (this engine draws no noise)");
+  return t2v_ddim_chain(who, e, x, samples, n_steps, timesteps, alpha_t, alpha_prev, guidance_scale, known, mask, noise,
+                        enable_temporal_attentions, (hipStream_t)stream);
 }
 
 int latte_t2v_guided_linear_loop(latte_t2v_t* e, float* x, int samples, int n_evals, const double* plan, const float* noise,
                                  float guidance_scale, int enable_temporal_attentions, void* stream) {
   if (!e || !x || !plan || samples <= 0 || n_evals <= 0) return fail(LATTE_ERR_INVALID, "t2v_guided_linear_loop: bad arguments");
-  int rc = latte_t2v_check_weights(e);
+  int rc = t2v_chain_check("t2v_guided_linear_loop", e, samples);
   if (rc) return rc;
   const int B = 2 * samples;
-  if (B > e->max_batch) return fail(LATTE_ERR_STATE, "t2v_guided_linear_loop: the guidance pair exceeds max_batch of the engine");
-  if (e->txt_batch != B)
-    return fail(LATTE_ERR_STATE, "t2v_guided_linear_loop: install the text context of the guidance pair first "
-                                 "(latte_t2v_set_text with [negative | prompt] embeddings, 2 * samples rows)");
   const auto& c = e->cfg;
-  if (c.out_channels != c.in_channels && c.out_channels != 2 * c.in_channels)
-    return fail(LATTE_ERR_INVALID, "t2v_guided_linear_loop: out_channels must be C or 2C (learned sigma)");
   PlanInfo info;   // no trained-range bound, and this engine draws no noise of its own
   if ((rc = plan_check("t2v_guided_linear_loop", plan, n_evals, e->tsteps_cap, 0, noise != nullptr, false, &info))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  LATTE_HIP(hipMemcpyAsync(e->tsteps, info.ts.data(), sizeof(int64_t) * n_evals, hipMemcpyHostToDevice, st));
-  LATTE_HIP(hipStreamSynchronize(st));   // info.ts goes away
+  if ((rc = t2v_upload_timesteps(e, info.ts.data(), n_evals, st))) return rc;
   const int HW = e->H * e->H;
   const size_t per_chain = (size_t)samples * c.in_channels * e->F * HW;
   // what the denoiser reads: x itself when every in_scale is 1, else in_scale * x kept beside it by the step kernel

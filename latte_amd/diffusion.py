@@ -13,6 +13,7 @@
   replacement), as ``latte_sample_loop_known`` calls for a ``latte_amd.Latte`` method.
 """
 import ctypes
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -91,9 +92,72 @@ class SpacedDiffusion:
                 return owner, True
         return None, False
 
-    def _device(self, model, device):
+    def _engine_chain(self, model, img, model_kwargs, hooks=False):
+        """The engine path of a loop: None unless `model` is a bound latte_amd.Latte method called with kwargs the engine knows and no
+        hooks; else what its chain calls take -- eng, x32 (`img` on the model's device, sampled in place), y64, B, uses_cfg, cfg_scale --
+        with the text embedding installed."""
+        owner, uses_cfg = self._engine_model(model)
+        if owner is None or hooks or not set(model_kwargs) <= {"y", "use_fp16", "cfg_scale", "text_embedding"}:
+            return None
+        _lib.require_gpu()
+        B = img.shape[0]
+        x32, _, y64 = owner._prep(img, torch.zeros(B, dtype=torch.int64), model_kwargs.get("y"))
+        cfg_scale = float(model_kwargs.get("cfg_scale", 7.0)) if uses_cfg else 1.0
+        eng = owner.engine(B, guided=uses_cfg)
+        owner._set_text(model_kwargs.get("text_embedding"), B, guided=uses_cfg)
+        return SimpleNamespace(eng=eng, x32=x32, y64=y64, B=B, uses_cfg=int(uses_cfg), cfg_scale=cfg_scale)
+
+    @staticmethod
+    def _segments(start, end, seg):
+        """Inclusive (first, last) index segments of at most `seg` indices from `start` to `end`, descending when end < start."""
+        step = -1 if end < start else 1
+        i = start
+        while (end - i) * step >= 0:
+            last = i + step * min(seg - 1, (end - i) * step)
+            yield i, last
+            i = last + step
+
+    def _engine_run(self, ec, start, end, seg, progressive, call, x0_trail=True):
+        """The chain of `ec` over the indices start ... end, one engine call per segment: ``call(first, last, trail_sample, trail_x0)``
+        (trail pointers, NULL unless progressive) makes it and returns the noise it fed, or None.  Only ONE segment's noise and trails
+        exist at a time.  Yields {"sample", "pred_xstart"} per index when progressive, else the final sample once."""
+        x32 = ec.x32
+        for first, last in self._segments(start, end, seg):
+            cnt = abs(last - first) + 1
+            trail_s = trail_0 = None
+            if progressive:
+                trail_s = torch.empty((cnt,) + tuple(x32.shape), device=x32.device, dtype=torch.float32)
+                trail_0 = torch.empty_like(trail_s) if x0_trail else None
+            with torch.cuda.device(x32.device):
+                nz = call(first, last, ptr(trail_s), ptr(trail_0))
+                if nz is not None or progressive:
+                    torch.cuda.current_stream().synchronize()      # the segment's buffers are released / handed out next
+            for k in range(cnt if progressive else 0):
+                yield {"sample": trail_s[k], "pred_xstart": None if trail_0 is None else trail_0[k]}
+        if not progressive:
+            yield {"sample": x32, "pred_xstart": None}
+
+    @staticmethod
+    def _progress(seq, progress):
+        if progress:
+            from tqdm.auto import tqdm
+            return tqdm(seq)
+        return seq
+
+    @staticmethod
+    def _last_sample(loop):
+        """Runs a progressive generator to its last item -> that item's sample."""
+        final = None
+        for final in loop:
+            pass
+        return final["sample"]
+
+    def _device(self, model, device, fallback=None):
+        """`fallback`: the tensor whose device a callable that is no latte_amd.Latte method runs on."""
         if device is not None:
             return torch.device(device)
+        if fallback is not None and self._engine_model(model)[0] is None:
+            return fallback.device
         owner = getattr(model, "__self__", model)
         return next(owner.parameters()).device                                     # gd:487-488
 
@@ -191,50 +255,26 @@ class SpacedDiffusion:
         img = img.to(device=device, dtype=torch.float32).contiguous().clone()
         n = self.num_timesteps
         needs_noise = method == "ddpm" or eta != 0.0
-        owner, uses_cfg = self._engine_model(model)
-        known = {"y", "use_fp16", "cfg_scale", "text_embedding"}
-        if owner is not None and set(model_kwargs) <= known and denoised_fn is None and cond_fn is None:
+        ec = self._engine_chain(model, img, model_kwargs, denoised_fn is not None or cond_fn is not None)
+        if ec is not None:
             # ---- whole chain inside the engine
-            B = img.shape[0]
-            y = model_kwargs.get("y")
-            x32, _, y64 = owner._prep(img, torch.zeros(B, dtype=torch.int64), y)
-            cfg_scale = float(model_kwargs.get("cfg_scale", 7.0)) if uses_cfg else 1.0
-            eng = owner.engine(B, guided=uses_cfg)
-            owner._set_text(model_kwargs.get("text_embedding"), B, guided=uses_cfg)
             # The chain runs in segments of consecutive steps so that the per-step noise (and the progressive trails) of
             # only ONE segment exist at a time: 65 MB per 250-step sample-chain otherwise, 4.2 GB at B = 64.  The draws
             # are the reference's -- one torch.randn_like per step, in step order (gd:413,555) -- whatever the split.
-            numel_bytes = x32.numel() * 4
-            seg = max(1, min(n, self.SEGMENT_BYTES // max(numel_bytes, 1)))
+            seg = max(1, min(n, self.SEGMENT_BYTES // max(ec.x32.numel() * 4, 1)))
             lib = load_library()
-            i = start
-            while i >= end:
-                lo = max(end, i - seg + 1)
-                cnt = i - lo + 1
-                nz = torch.stack([torch.randn_like(x32) for _ in range(cnt)]) if needs_noise else None
-                trail_s = trail_0 = None
-                if progressive:
-                    trail_s = torch.empty((cnt,) + tuple(x32.shape), device=device, dtype=torch.float32)
-                    trail_0 = torch.empty_like(trail_s)
-                with torch.cuda.device(device):
-                    check(lib.latte_sample_loop_ex(eng, self._h, _METHOD[method], float(eta), int(bool(clip_denoised)),
-                                                   int(uses_cfg), cfg_scale, ptr(x32), ptr(y64), B, i, lo, ptr(nz),
-                                                   ptr(trail_s), ptr(trail_0), stream_ptr()))
-                    if nz is not None or progressive:
-                        torch.cuda.current_stream().synchronize()      # the segment's buffers are released / handed out next
-                if progressive:
-                    for k in range(cnt):
-                        yield {"sample": trail_s[k], "pred_xstart": trail_0[k]}
-                i = lo - 1
-            if not progressive:
-                yield {"sample": x32, "pred_xstart": None}
+
+            def call(i, lo, trail_s, trail_0):
+                nz = torch.stack([torch.randn_like(ec.x32) for _ in range(i - lo + 1)]) if needs_noise else None
+                check(lib.latte_sample_loop_ex(ec.eng, self._h, _METHOD[method], float(eta), int(bool(clip_denoised)), ec.uses_cfg,
+                                               ec.cfg_scale, ptr(ec.x32), ptr(ec.y64), ec.B, i, lo, ptr(nz), trail_s, trail_0,
+                                               stream_ptr()))
+                return nz
+
+            yield from self._engine_run(ec, start, end, seg, progressive, call)
             return
         # ---- generic model callable, step by step
-        indices = list(range(end, start + 1))[::-1]
-        if progress:
-            from tqdm.auto import tqdm
-            indices = tqdm(indices)
-        for i in indices:
+        for i in self._progress(list(range(end, start + 1))[::-1], progress):
             out = self._call_model(model, img, i, model_kwargs)
             nz = torch.randn_like(img) if needs_noise else None
             r = self._step(method, out, img, i, nz, eta, clip_denoised, denoised_fn, cond_fn, model_kwargs)
@@ -253,22 +293,16 @@ class SpacedDiffusion:
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                       model_kwargs=None, device=None, progress=False):
-        final = None
-        for final in self._loop("ddpm", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
-                                progress, 0.0, False):
-            pass
-        return final["sample"]
+        return self._last_sample(self._loop("ddpm", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
+                                            progress, 0.0, False))
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, start_index=None, end_index=None):
         """``GaussianDiffusion.ddim_sample_loop`` (gd:604-635).  ``start_index`` / ``end_index`` (not in the reference; default
         the full chain T-1 ... 0) run the respaced steps start ... end descending on ``noise`` taken as level ``start``: the
         way back from a ``ddim_reverse_sample_loop`` that ended at ``end_index = start - 1``."""
-        final = None
-        for final in self._loop("ddim", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
-                                progress, eta, False, start_index, end_index):
-            pass
-        return final["sample"]
+        return self._last_sample(self._loop("ddim", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
+                                            progress, eta, False, start_index, end_index))
 
     # ------------------------------------------------------------------ linear samplers (not in the reference)
     def linear_scheduler(self, method="dpmsolver++"):
@@ -289,10 +323,7 @@ class SpacedDiffusion:
         n_evals = plan.shape[0]
         model_kwargs = dict(model_kwargs or {})
         assert isinstance(shape, (tuple, list))
-        owner, uses_cfg = self._engine_model(model)
-        if device is None and owner is None and noise is not None:
-            device = noise.device
-        device = self._device(model, device)
+        device = self._device(model, device, noise)
         img = noise if noise is not None else torch.randn(*shape, device=device)
         img = img.to(device=device, dtype=torch.float32).contiguous() * float(sch.init_noise_sigma)
         if img.dim() != 5:
@@ -302,35 +333,22 @@ class SpacedDiffusion:
             if tuple(step_noise.shape) != (n_evals,) + tuple(img.shape):
                 raise LatteError(f"step_noise must be [{n_evals}, ...latents]: one slab per denoiser evaluation of {method!r}")
             nz = step_noise.to(device=device, dtype=torch.float32).contiguous()
-        known = {"y", "use_fp16", "cfg_scale", "text_embedding"}
-        if owner is not None and set(model_kwargs) <= known:
-            # ---- whole chain inside the engine: one call
-            _lib.require_gpu()
-            B = img.shape[0]
-            x32, _, y64 = owner._prep(img, torch.zeros(B, dtype=torch.int64), model_kwargs.get("y"))
-            cfg_scale = float(model_kwargs.get("cfg_scale", 7.0)) if uses_cfg else 1.0
-            eng = owner.engine(B, guided=uses_cfg)
-            owner._set_text(model_kwargs.get("text_embedding"), B, guided=uses_cfg)
+        ec = self._engine_chain(model, img, model_kwargs)
+        if ec is not None:
+            # ---- whole chain inside the engine: one call, one trail
             lib = load_library()
-            check(lib.latte_engine_set_option(eng, b"train_timesteps", self.original_num_steps))
-            trail = torch.empty((n_evals,) + tuple(x32.shape), device=x32.device, dtype=torch.float32) if progressive else None
-            with torch.cuda.device(x32.device):
-                check(lib.latte_sample_plan_loop(eng, int(uses_cfg), cfg_scale, ptr(x32), ptr(y64), B, n_evals, plan.ctypes.data,
-                                                 ptr(nz), ptr(trail), stream_ptr()))
-                if nz is not None or progressive:
-                    torch.cuda.current_stream().synchronize()      # the noise may be released / the trail is handed out next
-            for k in range(n_evals if progressive else 0):
-                yield {"sample": trail[k], "pred_xstart": None}
-            if not progressive:
-                yield {"sample": x32, "pred_xstart": None}
+            check(lib.latte_engine_set_option(ec.eng, b"train_timesteps", self.original_num_steps))
+
+            def call(first, last, trail, _):
+                check(lib.latte_sample_plan_loop(ec.eng, ec.uses_cfg, ec.cfg_scale, ptr(ec.x32), ptr(ec.y64), ec.B, n_evals,
+                                                 plan.ctypes.data, ptr(nz), trail, stream_ptr()))
+                return nz
+
+            yield from self._engine_run(ec, 0, n_evals - 1, n_evals, progressive, call, x0_trail=False)
             return
         # ---- generic model callable, step by step: the scheduler's own scale_model_input / step around it
         C = img.shape[2]
-        steps = list(enumerate(sch.timesteps.tolist()))
-        if progress:
-            from tqdm.auto import tqdm
-            steps = tqdm(steps)
-        for k, t in steps:
+        for k, t in self._progress(list(enumerate(sch.timesteps.tolist())), progress):
             tt = torch.full((img.shape[0],), t, device=img.device, dtype=torch.int64)   # ORIGINAL timesteps: no _WrappedModel here
             out = model(sch.scale_model_input(img, t), tt, **model_kwargs)
             if isinstance(out, tuple):
@@ -365,10 +383,7 @@ class SpacedDiffusion:
         same timesteps, "euler" is ``ddim_sample_loop(eta=0, clip_denoised=False)``.  No hooks (``denoised_fn`` / ``cond_fn``), and no
         known-region sampling: ``known`` / ``known_mask`` raise (``known_sample_loop`` serves DDIM / DDPM)."""
         self._no_known(known, known_mask)
-        final = None
-        for final in self._linear_loop(model, shape, noise, method, model_kwargs, device, progress, step_noise, False):
-            pass
-        return final["sample"]
+        return self._last_sample(self._linear_loop(model, shape, noise, method, model_kwargs, device, progress, step_noise, False))
 
     # ------------------------------------------------------------------ known-region sampling (not in the reference)
     def known_chain_slabs(self, method="ddim", eta=0.0, resample=1, start_index=None, end_index=None, blend_start=True):
@@ -390,10 +405,7 @@ class SpacedDiffusion:
         _lib.require_gpu()
         start, end = self._index_range(start_index, end_index, ascending=False)
         model_kwargs = dict(model_kwargs or {})
-        owner, uses_cfg = self._engine_model(model)
-        if device is None and owner is None:                        # a plain callable: where the start, else the known clip, lives
-            device = noise.device if noise is not None else known.device
-        device = self._device(model, device)
+        device = self._device(model, device, noise if noise is not None else known)   # a plain callable: the start, else the known clip
         assert isinstance(shape, (tuple, list))
         img = noise if noise is not None else torch.randn(*shape, device=device)
         img = img.to(device=device, dtype=torch.float32).contiguous().clone()
@@ -402,7 +414,6 @@ class SpacedDiffusion:
         B, F, C, H, W = img.shape
         if (H * W) % 4:
             raise LatteError("known_sample_loop: H * W must be a multiple of 4 (16-byte accesses of the blend kernel)")
-        owner, uses_cfg = self._engine_model(model)
         kn = known.to(device=device, dtype=torch.float32)
         mk = known_mask.to(device=device, dtype=torch.float32)
         if kn.shape[0] * 2 == B:                                    # the doubled batch of forward_with_cfg: double them as z is doubled
@@ -428,37 +439,22 @@ class SpacedDiffusion:
                 return None
             return slabs[taken - cnt:taken] if slabs is not None else torch.stack([torch.randn_like(img) for _ in range(cnt)])
 
-        lib = load_library()
-        engine_kwargs = {"y", "use_fp16", "cfg_scale", "text_embedding"}
-        if owner is not None and set(model_kwargs) <= engine_kwargs and denoised_fn is None and cond_fn is None:
+        ec = self._engine_chain(model, img, model_kwargs, denoised_fn is not None or cond_fn is not None)
+        if ec is not None:
             # ---- whole chain inside the engine, in segments of consecutive indices as _loop segments its noise
-            x32, _, y64 = owner._prep(img, torch.zeros(B, dtype=torch.int64), model_kwargs.get("y"))
-            cfg_scale = float(model_kwargs.get("cfg_scale", 7.0)) if uses_cfg else 1.0
-            eng = owner.engine(B, guided=uses_cfg)
-            owner._set_text(model_kwargs.get("text_embedding"), B, guided=uses_cfg)
-            seg = max(1, min(self.num_timesteps, self.SEGMENT_BYTES // max(x32.numel() * 4 * 3 * resample, 1)))
-            i = start
-            while i >= end:
-                lo = max(end, i - seg + 1)
-                cnt = i - lo + 1
+            seg = max(1, min(self.num_timesteps, self.SEGMENT_BYTES // max(ec.x32.numel() * 4 * 3 * resample, 1)))
+            lib = load_library()
+
+            def call(i, lo, trail_s, trail_0):
                 first = int(bool(blend_start) and i == start)
                 nz = take(self.known_chain_slabs(method, eta, resample, i, lo, first))
-                trail_s = trail_0 = None
-                if progressive:
-                    trail_s = torch.empty((cnt,) + tuple(x32.shape), device=device, dtype=torch.float32)
-                    trail_0 = torch.empty_like(trail_s)
-                with torch.cuda.device(device):
-                    check(lib.latte_sample_loop_known(eng, self._h, _METHOD[method], float(eta), int(bool(clip_denoised)), int(uses_cfg),
-                                                      cfg_scale, ptr(x32), ptr(y64), B, i, lo, ptr(kn), ptr(mk), resample, first, ptr(nz),
-                                                      ptr(trail_s), ptr(trail_0), stream_ptr()))
-                    if nz is not None or progressive:
-                        torch.cuda.current_stream().synchronize()      # the segment's buffers are released / handed out next
-                for k in range(cnt if progressive else 0):
-                    yield {"sample": trail_s[k], "pred_xstart": trail_0[k]}
-                i = lo - 1
+                check(lib.latte_sample_loop_known(ec.eng, self._h, _METHOD[method], float(eta), int(bool(clip_denoised)), ec.uses_cfg,
+                                                  ec.cfg_scale, ptr(ec.x32), ptr(ec.y64), B, i, lo, ptr(kn), ptr(mk), resample, first,
+                                                  ptr(nz), trail_s, trail_0, stream_ptr()))
+                return nz
+
+            yield from self._engine_run(ec, start, end, seg, progressive, call)
             assert taken == n_slabs
-            if not progressive:
-                yield {"sample": x32, "pred_xstart": None}
             return
         # ---- generic model callable, step by step: _step, then latte_known_blend, then the jump
         def blend(x, abar, draws):
@@ -468,11 +464,7 @@ class SpacedDiffusion:
 
         if blend_start:
             img = blend(img, self.alphas_cumprod[start], True)
-        indices = list(range(end, start + 1))[::-1]
-        if progress:
-            from tqdm.auto import tqdm
-            indices = tqdm(indices)
-        for i in indices:
+        for i in self._progress(list(range(end, start + 1))[::-1], progress):
             # the step's own draws: what the one-index chain takes besides its blend
             step_draws = self.known_chain_slabs(method, eta, 1, i, i, False) - int(i > 0)
             for u in range(1, resample + 1):
@@ -510,11 +502,9 @@ class SpacedDiffusion:
         ``latte_sample_loop_known`` call per segment; any other callable goes step by step through the step kernel and
         ``latte_known_blend``.  ``chain_noise`` [known_chain_slabs(...), ...latents] gives every draw to either path, in slab order;
         without it each slab is one ``torch.randn_like``.  The linear samplers have no known-region form (``linear_sample_loop``)."""
-        final = None
-        for final in self._known_loop(method, model, shape, known, known_mask, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
-                                      device, progress, eta, resample, start_index, end_index, chain_noise, blend_start, False):
-            pass
-        return final["sample"]
+        return self._last_sample(self._known_loop(method, model, shape, known, known_mask, noise, clip_denoised, denoised_fn, cond_fn,
+                                                  model_kwargs, device, progress, eta, resample, start_index, end_index, chain_noise,
+                                                  blend_start, False))
 
     # ------------------------------------------------------------------ DDIM inversion (gd:566-602)
     def _reverse_loop(self, model, x, clip_denoised, denoised_fn, cond_fn, model_kwargs, progress, start_index, end_index,
@@ -525,44 +515,22 @@ class SpacedDiffusion:
         img = x.to(dtype=torch.float32).contiguous().clone()
         if img.dim() != 5:
             raise LatteError("x must be [N, F, C, H, W]")
-        owner, uses_cfg = self._engine_model(model)
-        known = {"y", "use_fp16", "cfg_scale", "text_embedding"}
-        if owner is not None and set(model_kwargs) <= known and denoised_fn is None and cond_fn is None:
+        ec = self._engine_chain(model, img, model_kwargs, denoised_fn is not None or cond_fn is not None)
+        if ec is not None:
             # ---- whole range inside the engine (the dispatch rule of _loop); only progressive trails split it
-            B = img.shape[0]
-            x32, _, y64 = owner._prep(img, torch.zeros(B, dtype=torch.int64), model_kwargs.get("y"))
-            cfg_scale = float(model_kwargs.get("cfg_scale", 7.0)) if uses_cfg else 1.0
-            eng = owner.engine(B, guided=uses_cfg)
-            owner._set_text(model_kwargs.get("text_embedding"), B, guided=uses_cfg)
             seg = end - start + 1
             if progressive:
-                seg = max(1, min(seg, self.SEGMENT_BYTES // max(x32.numel() * 4, 1)))
+                seg = max(1, min(seg, self.SEGMENT_BYTES // max(ec.x32.numel() * 4, 1)))
             lib = load_library()
-            i = start
-            while i <= end:
-                hi = min(end, i + seg - 1)
-                cnt = hi - i + 1
-                trail_s = trail_0 = None
-                if progressive:
-                    trail_s = torch.empty((cnt,) + tuple(x32.shape), device=x32.device, dtype=torch.float32)
-                    trail_0 = torch.empty_like(trail_s)
-                with torch.cuda.device(x32.device):
-                    check(lib.latte_invert_loop(eng, self._h, int(bool(clip_denoised)), int(uses_cfg), cfg_scale, ptr(x32),
-                                                ptr(y64), B, i, hi, ptr(trail_s), ptr(trail_0), stream_ptr()))
-                    if progressive:
-                        torch.cuda.current_stream().synchronize()      # the segment's trails are handed out next, as in _loop
-                for k in range(cnt if progressive else 0):
-                    yield {"sample": trail_s[k], "pred_xstart": trail_0[k]}
-                i = hi + 1
-            if not progressive:
-                yield {"sample": x32, "pred_xstart": None}
+
+            def call(i, hi, trail_s, trail_0):
+                check(lib.latte_invert_loop(ec.eng, self._h, int(bool(clip_denoised)), ec.uses_cfg, ec.cfg_scale, ptr(ec.x32), ptr(ec.y64),
+                                            ec.B, i, hi, trail_s, trail_0, stream_ptr()))
+
+            yield from self._engine_run(ec, start, end, seg, progressive, call)
             return
         # ---- generic model callable, step by step
-        indices = list(range(start, end + 1))
-        if progress:
-            from tqdm.auto import tqdm
-            indices = tqdm(indices)
-        for i in indices:
+        for i in self._progress(list(range(start, end + 1)), progress):
             out = self._call_model(model, img, i, model_kwargs)
             r = self._step("ddim_reverse", out, img, i, None, 0.0, clip_denoised, denoised_fn, cond_fn, model_kwargs)
             yield r
@@ -583,11 +551,8 @@ class SpacedDiffusion:
         so the way back from ``end_index = k - 1`` is ``ddim_sample_loop(..., noise=x_k, start_index=k)``.  With
         ``model.forward`` / ``model.forward_with_cfg`` of a ``latte_amd.Latte``, known kwargs and no hooks, the whole range is
         ONE ``latte_invert_loop`` call; any other callable is driven step by step.  Returns the inverted latent."""
-        final = None
-        for final in self._reverse_loop(model, x, clip_denoised, denoised_fn, cond_fn, model_kwargs, progress, start_index,
-                                        end_index, False):
-            pass
-        return final["sample"]
+        return self._last_sample(self._reverse_loop(model, x, clip_denoised, denoised_fn, cond_fn, model_kwargs, progress, start_index,
+                                                    end_index, False))
 
     # ------------------------------------------------------------------ training path, forward evaluation
     def q_sample(self, x_start, t, noise=None):

@@ -107,6 +107,15 @@ class LattePipeline:
             return masked.squeeze(1), neg
         return prompt_embeds, negative_prompt_embeds
 
+    def _ddim_tables(self, steps):
+        """(timesteps, alpha_t, alpha_prev) of the DDIM scheduler's steps, as the engine's guided DDIM loops take them."""
+        sch = self.scheduler
+        ts = [int(t) for t in steps]
+        ratio = sch.num_train_timesteps // sch.num_inference_steps
+        a_t = [float(sch.alphas_cumprod[t]) for t in ts]
+        a_p = [float(sch.alphas_cumprod[t - ratio]) if t - ratio >= 0 else float(sch.final_alpha_cumprod) for t in ts]
+        return ts, a_t, a_p
+
     def _fused_loop(self, steps, do_cfg, eta, callback, latent_channels):
         """(timesteps, alpha_t, alpha_prev) when the loop can run inside the engine (latte_t2v_guided_ddim_loop): guidance on,
         the self-contained DDIM scheduler at eta = 0 without clipping, the engine transformer, no per-step callback.  Any
@@ -118,11 +127,7 @@ class LattePipeline:
                 and isinstance(tr, LatteT2V) and tr.config.out_channels in (latent_channels, 2 * latent_channels)
                 and getattr(self, "allow_fused_loop", True)):
             return None
-        ts = [int(t) for t in steps]
-        ratio = sch.num_train_timesteps // sch.num_inference_steps
-        a_t = [float(sch.alphas_cumprod[t]) for t in ts]
-        a_p = [float(sch.alphas_cumprod[t - ratio]) if t - ratio >= 0 else float(sch.final_alpha_cumprod) for t in ts]
-        return ts, a_t, a_p
+        return self._ddim_tables(steps)
 
     def _known_loop(self, latents, known, mask, steps, prompt_embeds, do_cfg, guidance_scale, eta, generator, callback, callback_steps,
                     enable_temporal_attentions):
@@ -147,10 +152,7 @@ class LattePipeline:
                              f"{tuple(mask.shape)}")
         if (H * W) % 4:
             raise LatteError("known_latents: h * w must be a multiple of 4 (16-byte accesses of the blend kernel)")
-        ts = [int(t) for t in steps]
-        ratio = sch.num_train_timesteps // sch.num_inference_steps
-        a_t = [float(sch.alphas_cumprod[t]) for t in ts]
-        a_p = [float(sch.alphas_cumprod[t - ratio]) if t - ratio >= 0 else float(sch.final_alpha_cumprod) for t in ts]
+        ts, a_t, a_p = self._ddim_tables(steps)
         # slab 0: the blend before step 0; slab k + 1: the blend after step k (the last step takes none)
         noise = torch.stack([draw_noise(latents.shape, generator, device, latents.dtype) for _ in ts])
         if (do_cfg and callback is None and isinstance(tr, LatteT2V) and cfg.out_channels in (C, 2 * C)

@@ -181,9 +181,9 @@ class LatteT2V:
             torch.cuda.current_stream().synchronize()          # the inputs may be released by the caller
         return self
 
-    def guided_ddim_loop(self, latents, timesteps, alphas_t, alphas_prev, guidance_scale, enable_temporal_attentions=True):
-        """The classifier-free-guidance DDIM loop (eta = 0) inside the engine on ``latents`` [b, C, F, H, W]; ``set_text`` must
-        hold the 2 b rows [negative | prompt].  ``timesteps`` / ``alphas_*``: one entry per step (host sequences)."""
+    def _ddim_loop(self, who, latents, timesteps, alphas_t, alphas_prev, guidance_scale, enable_temporal_attentions, known=None,
+                   known_mask=None, noise=None):
+        """The shared body of ``guided_ddim_loop`` (known is None) and ``guided_ddim_loop_known``; ``who`` names the caller in errors."""
         import numpy as np
         dev = self._device
         x = latents.to(device=dev, dtype=torch.float32).contiguous().clone()
@@ -191,43 +191,40 @@ class LatteT2V:
         at = np.ascontiguousarray(np.asarray(alphas_t, dtype=np.float64))
         ap = np.ascontiguousarray(np.asarray(alphas_prev, dtype=np.float64))
         if not (len(ts) == len(at) == len(ap)) or len(ts) == 0:
-            raise LatteError("guided_ddim_loop: timesteps, alphas_t and alphas_prev must have one entry per step")
+            raise LatteError(f"{who}: timesteps, alphas_t and alphas_prev must have one entry per step")
+        args = (len(ts), ts.ctypes.data, at.ctypes.data, ap.ctypes.data, float(guidance_scale))
+        lib = load_library()
+        if known is not None:
+            kn = known.to(device=dev, dtype=torch.float32).contiguous()
+            mk = known_mask.to(device=dev, dtype=torch.float32).contiguous()
+            nz = noise.to(device=dev, dtype=torch.float32).contiguous()
+            b, C, F, H, W = x.shape
+            if kn.shape != x.shape or tuple(mk.shape) != (b, F, H, W) or tuple(nz.shape) != (len(ts),) + tuple(x.shape):
+                raise LatteError(f"{who}: known must have the latents' shape [b, C, F, H, W], known_mask must be [b, F, H, W] "
+                                 "and noise [n_steps, b, C, F, H, W]")
+            fn, args = lib.latte_t2v_guided_ddim_loop_known, args + (ptr(kn), ptr(mk), ptr(nz))
+        else:
+            fn = lib.latte_t2v_guided_ddim_loop
         if self._h is None:
-            raise LatteError("guided_ddim_loop: call set_text first")
+            raise LatteError(f"{who}: call set_text first")
         with torch.cuda.device(dev):
-            check(load_library().latte_t2v_guided_ddim_loop(self._h, ptr(x), x.shape[0], len(ts), ts.ctypes.data, at.ctypes.data,
-                                                            ap.ctypes.data, float(guidance_scale),
-                                                            int(bool(enable_temporal_attentions)), stream_ptr()))
+            check(fn(self._h, ptr(x), x.shape[0], *args, int(bool(enable_temporal_attentions)), stream_ptr()))
+            if known is not None:
+                torch.cuda.current_stream().synchronize()      # the noise may be released by the caller
         return x
+
+    def guided_ddim_loop(self, latents, timesteps, alphas_t, alphas_prev, guidance_scale, enable_temporal_attentions=True):
+        """The classifier-free-guidance DDIM loop (eta = 0) inside the engine on ``latents`` [b, C, F, H, W]; ``set_text`` must
+        hold the 2 b rows [negative | prompt].  ``timesteps`` / ``alphas_*``: one entry per step (host sequences)."""
+        return self._ddim_loop("guided_ddim_loop", latents, timesteps, alphas_t, alphas_prev, guidance_scale, enable_temporal_attentions)
 
     def guided_ddim_loop_known(self, latents, timesteps, alphas_t, alphas_prev, guidance_scale, known, known_mask, noise,
                                enable_temporal_attentions=True):
         """``guided_ddim_loop`` with part of the clip held fixed (``latte_t2v_guided_ddim_loop_known``): ``known`` [b, C, F, H, W] clean
         latents, ``known_mask`` [b, F, H, W] (1 = known), ``noise`` [n_steps, b, C, F, H, W] -- slab 0 diffuses the known part to the
         first level before step 0, slab k + 1 to ``alphas_prev[k]`` after step k; the last step writes the clean known latents."""
-        import numpy as np
-        dev = self._device
-        x = latents.to(device=dev, dtype=torch.float32).contiguous().clone()
-        ts = np.ascontiguousarray(np.asarray(timesteps, dtype=np.int64))
-        at = np.ascontiguousarray(np.asarray(alphas_t, dtype=np.float64))
-        ap = np.ascontiguousarray(np.asarray(alphas_prev, dtype=np.float64))
-        if not (len(ts) == len(at) == len(ap)) or len(ts) == 0:
-            raise LatteError("guided_ddim_loop_known: timesteps, alphas_t and alphas_prev must have one entry per step")
-        kn = known.to(device=dev, dtype=torch.float32).contiguous()
-        mk = known_mask.to(device=dev, dtype=torch.float32).contiguous()
-        nz = noise.to(device=dev, dtype=torch.float32).contiguous()
-        b, C, F, H, W = x.shape
-        if kn.shape != x.shape or tuple(mk.shape) != (b, F, H, W) or tuple(nz.shape) != (len(ts),) + tuple(x.shape):
-            raise LatteError("guided_ddim_loop_known: known must have the latents' shape [b, C, F, H, W], known_mask must be [b, F, H, W] "
-                             "and noise [n_steps, b, C, F, H, W]")
-        if self._h is None:
-            raise LatteError("guided_ddim_loop_known: call set_text first")
-        with torch.cuda.device(dev):
-            check(load_library().latte_t2v_guided_ddim_loop_known(self._h, ptr(x), b, len(ts), ts.ctypes.data, at.ctypes.data,
-                                                                  ap.ctypes.data, float(guidance_scale), ptr(kn), ptr(mk), ptr(nz),
-                                                                  int(bool(enable_temporal_attentions)), stream_ptr()))
-            torch.cuda.current_stream().synchronize()          # the noise may be released by the caller
-        return x
+        return self._ddim_loop("guided_ddim_loop_known", latents, timesteps, alphas_t, alphas_prev, guidance_scale,
+                               enable_temporal_attentions, known, known_mask, noise)
 
     def guided_linear_loop(self, latents, plan, noise, guidance_scale, enable_temporal_attentions=True):
         """The classifier-free-guidance loop of any sampler with a linear update (``engine_plan()`` of latte_amd.schedulers: Euler,

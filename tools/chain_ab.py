@@ -1,10 +1,13 @@
-"""A/B of two builds of the library on the engine's fused loops: every loop on fixed seeds, sha256 of every returned tensor.
+"""A/B of two builds of the library, or of two trees with their front ends, on the engine's fused loops: every loop on fixed seeds,
+sha256 of every returned tensor.
 
   python tools/chain_ab.py --out profiles/chain_refactor_head.json                                   # the tree's library
   LATTE_AMD_LIB=<other build>.so python tools/chain_ab.py --out profiles/chain_refactor_parent.json  # another build
+  python tools/chain_ab.py --tree <built checkout of another commit> --out profiles/known_refactor_parent.json   # library AND front end
   python tools/chain_ab.py --compare profiles/chain_refactor_parent.json profiles/chain_refactor_head.json
 
-Builds nothing: it loads LATTE_AMD_LIB or latte_amd/lib/liblatte_amd.so.  Models: the tiny_classcond and tiny_uncond golden fixtures
+Builds nothing: it loads LATTE_AMD_LIB or latte_amd/lib/liblatte_amd.so of the tree ``latte_amd`` and ``tests/_util`` are imported from
+(--tree, default this one).  Models: the tiny_classcond and tiny_uncond golden fixtures
 (f16 operands, max_batch 4) and the tiny text-to-video pipeline of tests/test_t2v_schedulers.py.  Cases:
   sample loop   DDPM, DDIM eta 0 and eta 0.5 with both trails, noise drawn by the engine (option "seed"); on the class-conditional model
                 guided at batch 4 over 70 steps (bu = 4: the conditioning chunk holds 64), once whole and once as two segments
@@ -12,7 +15,13 @@ Builds nothing: it loads LATTE_AMD_LIB or latte_amd/lib/liblatte_amd.so.  Models
   bpd loop      given noise and drawn noise, both models
   plan loop     Euler, Euler-ancestral (drawn noise), Heun, DPM-Solver++ on create_diffusion("6"), guided and plain, with the trail; Heun
                 on create_diffusion("40") (79 rows, guided batch 4).  Euler / Heun scale the model input.
-  T2V           latte_t2v_guided_linear_loop for the four methods and the guided DDIM loop, through LattePipeline
+  T2V           latte_t2v_guided_linear_loop for the four methods and the guided DDIM loop, through LattePipeline; the known-region DDIM
+                loop through LattePipeline(known_latents=, known_mask=)
+  known loop    latte_sample_loop_known for DDPM, DDIM eta 0 and eta 0.5 at resample 1 and 2, both trails: guided batch 4 over 70 steps
+                whole and as two calls (blend_start on the first only), plain batch 3, unconditional batch 2; each with noise drawn by the
+                engine and with given slabs
+  front end     p_sample_loop_progressive, ddim_reverse_sample_loop_progressive and known_sample_loop_progressive of SpacedDiffusion
+                on torch.manual_seed draws with SEGMENT_BYTES cut to three indices per engine call
 After every class-engine case the option "seed" is read back and one further engine-drawn DDPM step is hashed, so the Philox offset
 must have advanced identically.  Two runs agree when every hash agrees."""
 import argparse
@@ -24,7 +33,9 @@ import sys
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_pre = argparse.ArgumentParser(add_help=False)
+_pre.add_argument("--tree")
+ROOT = os.path.abspath(_pre.parse_known_args()[0].tree or os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
@@ -94,6 +105,67 @@ class ClassEngine:
         self.tail(rec, B, guided, d, y)
         return rec
 
+    def known(self, d, method, eta, B, guided, segments, resample, given, seed):
+        """latte_sample_loop_known over descending segments (hi ... lo each), the start blend in the first call only"""
+        x, y = self.inputs(B, guided, seed)
+        g = torch.Generator("cpu").manual_seed(seed + 100)
+        half = B // 2 if guided else B
+        known = torch.randn((half,) + self.shape, generator=g)
+        mask = torch.zeros(half, self.shape[0], self.shape[2], self.shape[3])
+        mask[:, 0] = 1.0                                             # the first frame, and a box in the others
+        mask[:, 1:, 2:5, 3:7] = 1.0
+        if guided:
+            known, mask = torch.cat([known, known]), torch.cat([mask, mask])
+        known, mask = known.cuda().contiguous(), mask.cuda().contiguous()
+        self.m.set_engine_option("seed", seed, batch=B, guided=guided)
+        eng, rec = self.m.engine(B, guided), {}
+        name = "ddpm" if method == DDPM else "ddim"
+        counts = [d.known_chain_slabs(name, eta, resample, hi, lo, j == 0) for j, (lo, hi) in enumerate(segments)]
+        slabs = torch.randn((sum(counts),) + tuple(x.shape), generator=g).cuda() if given else None
+        n = sum(hi - lo + 1 for lo, hi in segments)
+        trail_s = torch.empty((n,) + tuple(x.shape), device="cuda")
+        trail_0 = torch.empty_like(trail_s)
+        k = taken = 0
+        for j, (lo, hi) in enumerate(segments):
+            nz = slabs[taken:taken + counts[j]].contiguous() if given and counts[j] else None
+            check(self.lib.latte_sample_loop_known(eng, d._h, method, eta, 1, int(guided), CFG, ptr(x), ptr(y), B, hi, lo, ptr(known), ptr(mask),
+                                                   resample, int(j == 0), ptr(nz), ptr(trail_s[k:]), ptr(trail_0[k:]), stream_ptr()))
+            torch.cuda.synchronize()
+            k += hi - lo + 1
+            taken += counts[j]
+        rec.update(x=sha(x), trail_sample=sha(trail_s), trail_x0=sha(trail_0), n_slabs=sum(counts))
+        self.tail(rec, B, guided, d, y)
+        return rec
+
+    def front_end(self, d, loop, B, guided, seed):
+        """A progressive loop of SpacedDiffusion on torch.manual_seed draws, three indices per engine call"""
+        x, y = self.inputs(B, guided, seed)
+        mk = {} if y is None else dict(y=y)
+        if guided:
+            mk["cfg_scale"] = CFG
+        fn = self.m.forward_with_cfg if guided else self.m.forward
+        torch.manual_seed(seed)
+        per_index = x.numel() * 4
+        if loop == "p_sample":
+            it = d.p_sample_loop_progressive(fn, x.shape, x, model_kwargs=mk)
+        elif loop == "ddim_reverse":
+            it = d.ddim_reverse_sample_loop_progressive(fn, x, model_kwargs=mk)
+        else:
+            g = torch.Generator("cpu").manual_seed(seed + 100)
+            known = torch.randn(tuple(x.shape), generator=g).cuda()
+            mask = torch.zeros(B, self.shape[0], self.shape[2], self.shape[3], device="cuda")
+            mask[:, 0] = 1.0
+            if guided:
+                known[B // 2:] = known[:B // 2]
+            per_index *= 3 * 2
+            it = d.known_sample_loop_progressive(fn, x.shape, known, mask, method="ddpm", noise=x, model_kwargs=mk, resample=2)
+        d.SEGMENT_BYTES = 3 * per_index
+        try:
+            out = [(r["sample"].clone(), r["pred_xstart"].clone()) for r in it]
+        finally:
+            del d.SEGMENT_BYTES
+        return {"n": len(out), "trail_sample": sha(torch.stack([a for a, _ in out])), "trail_x0": sha(torch.stack([b for _, b in out]))}
+
     def bpd(self, d, B, given, seed):
         x, y = self.inputs(B, False, seed)
         self.m.set_engine_option("seed", seed, batch=B)
@@ -138,6 +210,17 @@ def class_cases(out):
         out[f"plan::{method}::classcond::plain3"] = cc.plan(d6, method, 3, False, 18)
         out[f"plan::{method}::uncond::plain2"] = un.plan(d6, method, 2, False, 19)
     out["plan::heun::classcond::guided4::40"] = cc.plan(d40, "heun", 4, True, 20)
+    for tag, method, eta in (("ddpm", DDPM, 0.0), ("ddim_eta0", DDIM, 0.0), ("ddim_eta0.5", DDIM, 0.5)):
+        for r in (1, 2):
+            for given in (False, True):
+                key = f"known::{tag}::resample{r}::{'given' if given else 'drawn'}"
+                out[f"{key}::classcond::guided4::whole"] = cc.known(d80, method, eta, 4, True, whole, r, given, 22)
+                out[f"{key}::classcond::guided4::split"] = cc.known(d80, method, eta, 4, True, split, r, given, 22)
+                out[f"{key}::classcond::plain3"] = cc.known(d10, method, eta, 3, False, [(0, 9)], r, given, 23)
+                out[f"{key}::uncond::plain2"] = un.known(d10, method, eta, 2, False, [(0, 9)], r, given, 24)
+    for loop in ("p_sample", "ddim_reverse", "known"):
+        out[f"front_end::{loop}::classcond::guided4"] = cc.front_end(d10, loop, 4, True, 25)
+        out[f"front_end::{loop}::uncond::plain2"] = un.front_end(d10, loop, 2, False, 26)
 
 
 def t2v_cases(out):
@@ -162,6 +245,13 @@ def t2v_cases(out):
         video = pipe(prompt_embeds=pe, negative_prompt_embeds=ne, num_inference_steps=6, guidance_scale=4.5, latents=lat,
                      generator=torch.Generator("cpu").manual_seed(21), output_type="latents").video
         out[f"t2v::{name}"] = {"latents": sha(video)}
+    pipe.scheduler = DDIMScheduler()
+    known = torch.randn(lat.shape, generator=g)
+    mask = torch.zeros(2, cfg["video_length"], cfg["sample_size"], cfg["sample_size"])
+    mask[:, 0] = 1.0
+    video = pipe(prompt_embeds=pe, negative_prompt_embeds=ne, num_inference_steps=6, guidance_scale=4.5, latents=lat,
+                 generator=torch.Generator("cpu").manual_seed(21), output_type="latents", known_latents=known, known_mask=mask).video
+    out["t2v::ddim::known"] = {"latents": sha(video)}
 
 
 def compare(a, b):
@@ -175,6 +265,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
     ap.add_argument("--compare", nargs=2, metavar="JSON")
+    ap.add_argument("--tree", help="the built checkout to import latte_amd and tests/_util from (default: this one)")
     a = ap.parse_args()
     if a.compare:
         raise SystemExit(compare(*a.compare))
