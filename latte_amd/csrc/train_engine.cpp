@@ -14,7 +14,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -27,6 +26,9 @@ struct ParamInfo {
   std::string key;
   int64_t offset, numel;
 };
+// Offsets of the trained tensors inside the flat buffers, resolved once while latte_trainer_create_joint adds the keys
+struct BlockParams { int64_t qkv_w, qkv_b, proj_w, proj_b, fc1_w, fc1_b, fc2_w, fc2_b, ada_w, ada_b; };
+struct RestParams { int64_t pe_w, pe_b, t0_w, t0_b, t2_w, t2_b, y_table /* -1: no label table */, fin_w, fin_b, fin_ada_w, fin_ada_b; };
 struct BlockBuf {
   half_t *xn1, *qkv, *att, *y1, *xn2, *u, *h, *y2;
   half_t *qkv_w, *qkv_wt, *proj_w, *proj_wt, *fc1_w, *fc1_wt, *fc2_w, *fc2_wt;
@@ -65,11 +67,13 @@ struct latte_trainer {
   float loss_divisor = 1.0f;     // d loss.mean() / loss_divisor (train.py:222 `loss / gradient_accumulation_steps`); terms stay undivided
   float *pg1 = nullptr, *pl1 = nullptr, *pg2 = nullptr, *pg2b = nullptr, *pl2 = nullptr, *pc_fc1 = nullptr, *pc_qkv = nullptr, *dc_ws = nullptr, *no_ws = nullptr;
   PackDesc* pack_descs = nullptr;
+  std::vector<PackDesc> pack_host;   // [block][qkv, proj, fc1, fc2]: the host copy of pack_descs (latte_trainer_bind)
   PackPlan pack_plan{};
   float growth_interval = 2000.0f;
   float* scaler = nullptr;
   std::vector<ParamInfo> params;
-  std::map<std::string, int> index;
+  std::vector<BlockParams> bp;   // + rp: where every trained tensor lies in the flat buffers
+  RestParams rp{};
   int64_t total = 0;
   float *Pm = nullptr, *Gr = nullptr, *M1 = nullptr, *V2 = nullptr, *Ema = nullptr;   // bound flat buffers (caller-owned)
   float *pos = nullptr, *temp = nullptr, *pe_wt = nullptr, *fin_wt = nullptr;
@@ -113,15 +117,28 @@ struct latte_trainer {
 
 namespace {
 
-void add_param(latte_trainer* e, const std::string& key, int64_t numel) {
-  ParamInfo p{key, e->total, numel};
-  e->index[key] = (int)e->params.size();
-  e->params.push_back(p);
+// -> the offset the tensor got
+int64_t add_param(latte_trainer* e, const std::string& key, int64_t numel) {
+  const int64_t off = e->total;
+  e->params.push_back(ParamInfo{key, off, numel});
   e->total += (numel + 3) / 4 * 4;   // 16-byte aligned tensors inside the flat buffers
+  return off;
 }
 
-float* P_(latte_trainer* e, const std::string& key) { return e->Pm + e->params[e->index.at(key)].offset; }
-float* G_(latte_trainer* e, const std::string& key) { return e->Gr + e->params[e->index.at(key)].offset; }
+float* P(const latte_trainer* e, int64_t off) { return e->Pm + off; }
+float* G(const latte_trainer* e, int64_t off) { return e->Gr + off; }
+// a step is in flight: begin / seed ran and a backward stage is still due
+bool step_in_flight(const latte_trainer* e) { return e->next_stage <= e->cfg.depth + 1; }
+bool pow2_in(double v, double lo, double hi) {
+  int ex = 0;
+  return v >= lo && v <= hi && std::frexp(v, &ex) == 0.5;
+}
+// the sequence layout of a block's attention (forward and backward): spatial blocks attend inside a frame (B F sequences of T
+// contiguous rows), temporal ones across the F frames of a token (rows T apart)
+void seq_layout(AttnArgs& a, bool spatial, int B, int F, int T) {
+  if (spatial) { a.num_seq = B * F; a.L = T; a.U = F; a.seq_stride = T; a.row_stride = 1; }
+  else         { a.num_seq = B * T; a.L = F; a.U = T; a.seq_stride = 1; a.row_stride = T; }
+}
 
 int gemm_half(latte_trainer* e, const half_t* A, const half_t* W, const float* bias, half_t* out, int M, int N, int K, hipStream_t st) {
   GemmArgs g{};
@@ -142,8 +159,9 @@ int gemm_gelu(latte_trainer* e, int epi, const half_t* A, const half_t* W, const
   return launch_gemm_pw(g, epi, e->dt, 1, st);
 }
 
-bool scaling_active(const latte_trainer* e);
-const float* acc_scale(const latte_trainer* e);
+bool scaling_active(const latte_trainer* e) { return e->loss_scale != 1.0f || e->dynamic_scale; }
+// accumulate mode: the gradient writers unscale what they add themselves (device loss scale), nullptr otherwise
+const float* acc_scale(const latte_trainer* e) { return e->grad_accumulate && scaling_active(e) ? e->scaler : nullptr; }
 // dW[N, K] = dY[M, N]^T X[M, K] on the transposed-operand GEMM (gemm_tn.hip: no transposed copies), the contraction split so
 // that about four workgroups per CU are in flight; the partial products are reduced in a fixed order; result ASSIGNED to dW
 // ("grad_accumulate": ADDED by the reduction's own store, unscaled there)
@@ -179,9 +197,6 @@ int upload_scaler(latte_trainer* e, int what) {
   LATTE_HIP(hipMemcpy(e->scaler, h, sizeof(h), hipMemcpyHostToDevice));
   return LATTE_OK;
 }
-bool scaling_active(const latte_trainer* e) { return e->loss_scale != 1.0f || e->dynamic_scale; }
-// accumulate mode: the gradient writers unscale what they add themselves (device loss scale), nullptr otherwise
-const float* acc_scale(const latte_trainer* e) { return e->grad_accumulate && scaling_active(e) ? e->scaler : nullptr; }
 
 }  // namespace
 
@@ -199,7 +214,7 @@ int latte_trainer_create_joint(const latte_model_config_t* cfg, int max_batch, i
     return fail(LATTE_ERR_INVALID, "trainer: use_image_num must not exceed num_frames (the image pass runs in the video pass's row buffers)");
   const auto& c = *cfg;
   if (c.extras != 1 && c.extras != 2) return fail(LATTE_ERR_INVALID, "trainer: extras must be 1 or 2 (train.py:213-218 refuses text-to-video training)");
-  if (c.hidden_size % 128 || c.hidden_size > 1280 || c.depth % 2 || c.hidden_size % c.num_heads)
+  if (c.hidden_size % 128 || c.hidden_size > 1280 || c.depth < 2 || c.depth % 2 || c.hidden_size % c.num_heads)   // (bp[0], bp[1] exist)
     return fail(LATTE_ERR_INVALID, "trainer: hidden_size must be a multiple of 128 (<= 1280), depth even");
   const int hd = c.hidden_size / c.num_heads;
   if (hd != 64 && hd != 72) return fail(LATTE_ERR_INVALID, "trainer: head dim must be 64 or 72");
@@ -227,30 +242,33 @@ int latte_trainer_create_joint(const latte_model_config_t* cfg, int max_batch, i
   e->ld = (e->rows_max + 63) / 64 * 64;
   const int D = e->D, Hm = e->Hm;
   // ---- parameter table: reference named_parameters() order (latte.py:226-255), frozen tables excluded
-  add_param(e, "x_embedder.proj.weight", (int64_t)D * e->KPE);
-  add_param(e, "x_embedder.proj.bias", D);
-  add_param(e, "t_embedder.mlp.0.weight", (int64_t)D * 256);
-  add_param(e, "t_embedder.mlp.0.bias", D);
-  add_param(e, "t_embedder.mlp.2.weight", (int64_t)D * D);
-  add_param(e, "t_embedder.mlp.2.bias", D);
-  if (c.extras == 2) add_param(e, "y_embedder.embedding_table.weight", (int64_t)(c.num_classes + 1) * D);
+  RestParams& r = e->rp;
+  r.pe_w = add_param(e, "x_embedder.proj.weight", (int64_t)D * e->KPE);
+  r.pe_b = add_param(e, "x_embedder.proj.bias", D);
+  r.t0_w = add_param(e, "t_embedder.mlp.0.weight", (int64_t)D * 256);
+  r.t0_b = add_param(e, "t_embedder.mlp.0.bias", D);
+  r.t2_w = add_param(e, "t_embedder.mlp.2.weight", (int64_t)D * D);
+  r.t2_b = add_param(e, "t_embedder.mlp.2.bias", D);
+  r.y_table = c.extras == 2 ? add_param(e, "y_embedder.embedding_table.weight", (int64_t)(c.num_classes + 1) * D) : -1;
+  e->bp.resize(c.depth);
   for (int i = 0; i < c.depth; ++i) {
     const std::string p = "blocks." + std::to_string(i) + ".";
-    add_param(e, p + "attn.qkv.weight", (int64_t)3 * D * D);
-    add_param(e, p + "attn.qkv.bias", 3 * D);
-    add_param(e, p + "attn.proj.weight", (int64_t)D * D);
-    add_param(e, p + "attn.proj.bias", D);
-    add_param(e, p + "mlp.fc1.weight", (int64_t)Hm * D);
-    add_param(e, p + "mlp.fc1.bias", Hm);
-    add_param(e, p + "mlp.fc2.weight", (int64_t)D * Hm);
-    add_param(e, p + "mlp.fc2.bias", D);
-    add_param(e, p + "adaLN_modulation.1.weight", (int64_t)6 * D * D);
-    add_param(e, p + "adaLN_modulation.1.bias", 6 * D);
+    BlockParams& w = e->bp[i];
+    w.qkv_w = add_param(e, p + "attn.qkv.weight", (int64_t)3 * D * D);
+    w.qkv_b = add_param(e, p + "attn.qkv.bias", 3 * D);
+    w.proj_w = add_param(e, p + "attn.proj.weight", (int64_t)D * D);
+    w.proj_b = add_param(e, p + "attn.proj.bias", D);
+    w.fc1_w = add_param(e, p + "mlp.fc1.weight", (int64_t)Hm * D);
+    w.fc1_b = add_param(e, p + "mlp.fc1.bias", Hm);
+    w.fc2_w = add_param(e, p + "mlp.fc2.weight", (int64_t)D * Hm);
+    w.fc2_b = add_param(e, p + "mlp.fc2.bias", D);
+    w.ada_w = add_param(e, p + "adaLN_modulation.1.weight", (int64_t)6 * D * D);
+    w.ada_b = add_param(e, p + "adaLN_modulation.1.bias", 6 * D);
   }
-  add_param(e, "final_layer.linear.weight", (int64_t)e->P * D);
-  add_param(e, "final_layer.linear.bias", e->P);
-  add_param(e, "final_layer.adaLN_modulation.1.weight", (int64_t)2 * D * D);
-  add_param(e, "final_layer.adaLN_modulation.1.bias", 2 * D);
+  r.fin_w = add_param(e, "final_layer.linear.weight", (int64_t)e->P * D);
+  r.fin_b = add_param(e, "final_layer.linear.bias", e->P);
+  r.fin_ada_w = add_param(e, "final_layer.adaLN_modulation.1.weight", (int64_t)2 * D * D);
+  r.fin_ada_b = add_param(e, "final_layer.adaLN_modulation.1.bias", 2 * D);
 
   int rc = LATTE_OK;
   const size_t R = (size_t)e->rows_pad;
@@ -346,14 +364,15 @@ int latte_trainer_bind(latte_trainer_t* e, float* params, float* grads, float* e
   e->weights_synced = false;
   {   // pointer table of the one-launch weight pack (train_fin.hip): [block][qkv, proj, fc1, fc2]
     const int D = e->D, Hm = e->Hm;
-    std::vector<PackDesc> h((size_t)e->cfg.depth * 4);
+    std::vector<PackDesc>& h = e->pack_host;
+    h.resize((size_t)e->cfg.depth * 4);
     for (int i = 0; i < e->cfg.depth; ++i) {
-      const std::string p = "blocks." + std::to_string(i) + ".";
+      const BlockParams& w = e->bp[i];
       BlockBuf& b = e->blk[i];
-      h[i * 4 + 0] = PackDesc{P_(e, p + "attn.qkv.weight"), b.qkv_w, b.qkv_wt, 3 * D, D};
-      h[i * 4 + 1] = PackDesc{P_(e, p + "attn.proj.weight"), b.proj_w, b.proj_wt, D, D};
-      h[i * 4 + 2] = PackDesc{P_(e, p + "mlp.fc1.weight"), b.fc1_w, b.fc1_wt, Hm, D};
-      h[i * 4 + 3] = PackDesc{P_(e, p + "mlp.fc2.weight"), b.fc2_w, b.fc2_wt, D, Hm};
+      h[i * 4 + 0] = PackDesc{P(e, w.qkv_w), b.qkv_w, b.qkv_wt, 3 * D, D};
+      h[i * 4 + 1] = PackDesc{P(e, w.proj_w), b.proj_w, b.proj_wt, D, D};
+      h[i * 4 + 2] = PackDesc{P(e, w.fc1_w), b.fc1_w, b.fc1_wt, Hm, D};
+      h[i * 4 + 3] = PackDesc{P(e, w.fc2_w), b.fc2_w, b.fc2_wt, D, Hm};
     }
     LATTE_HIP(hipDeviceSynchronize());
     LATTE_HIP(hipMemcpy(e->pack_descs, h.data(), h.size() * sizeof(PackDesc), hipMemcpyHostToDevice));
@@ -373,21 +392,15 @@ int latte_trainer_set_frozen(latte_trainer_t* e, const float* pos_embed, const f
 int latte_trainer_sync_weights(latte_trainer_t* e, void* stream) {
   if (!e || !e->Pm) return fail(LATTE_ERR_STATE, "trainer_sync_weights: bind the parameter buffers first");
   hipStream_t st = (hipStream_t)stream;
-  const int D = e->D, Hm = e->Hm;
   int rc;
   if (e->fuse_small) {
     if ((rc = launch_pack_weights(e->pack_descs, e->cfg.depth, e->pack_plan, e->dt, st))) return rc;
-  } else
-  for (int i = 0; i < e->cfg.depth; ++i) {
-    const std::string p = "blocks." + std::to_string(i) + ".";
-    BlockBuf& b = e->blk[i];
-    if ((rc = launch_pack_weight(P_(e, p + "attn.qkv.weight"), b.qkv_w, b.qkv_wt, 3 * D, D, e->dt, st))) return rc;
-    if ((rc = launch_pack_weight(P_(e, p + "attn.proj.weight"), b.proj_w, b.proj_wt, D, D, e->dt, st))) return rc;
-    if ((rc = launch_pack_weight(P_(e, p + "mlp.fc1.weight"), b.fc1_w, b.fc1_wt, Hm, D, e->dt, st))) return rc;
-    if ((rc = launch_pack_weight(P_(e, p + "mlp.fc2.weight"), b.fc2_w, b.fc2_wt, D, Hm, e->dt, st))) return rc;
+  } else {   // the same table, one launch per entry
+    for (const PackDesc& d : e->pack_host)
+      if ((rc = launch_pack_weight(d.w, d.wn, d.wt, d.N, d.K, e->dt, st))) return rc;
   }
-  if ((rc = launch_transpose_f32(P_(e, "x_embedder.proj.weight"), e->pe_wt, D, e->KPE, st))) return rc;
-  if ((rc = launch_transpose_f32(P_(e, "final_layer.linear.weight"), e->fin_wt, e->P, D, st))) return rc;
+  if ((rc = launch_transpose_f32(P(e, e->rp.pe_w), e->pe_wt, e->D, e->KPE, st))) return rc;
+  if ((rc = launch_transpose_f32(P(e, e->rp.fin_w), e->fin_wt, e->P, e->D, st))) return rc;
   e->weights_synced = true;
   return LATTE_OK;
 }
@@ -420,6 +433,7 @@ int qsample_part(latte_trainer_t* e, const latte_schedule_t* s, const float* tab
 // ---- forward of model(e->x_t, e->t_orig, y) with saved activations -> e->model_out (and model_out_copy)
 int forward_part(latte_trainer_t* e, const int64_t* y, int batch, float* model_out_copy, hipStream_t st) {
   const auto& c = e->cfg;
+  const RestParams& r = e->rp;
   int rc;
   const int D = e->D, T = e->T, F = e->run_F, Hm = e->Hm, B = batch, dt = e->dt, nmod = e->nmod;
   const bool temporal = e->run_temporal != 0;
@@ -428,28 +442,24 @@ int forward_part(latte_trainer_t* e, const int64_t* y, int batch, float* model_o
   // ================================================================ forward
   // conditioning (latte.py:119-123,332-348): temb_pre = W0 freq(t) + b0; c = W2 SiLU(temb_pre) + b2 (+ y_emb); mod = adaLN(SiLU(c))
   if ((rc = launch_tfreq(e->t_orig, e->tfreq, B, st))) return rc;
-  if ((rc = launch_small_linear(IN_PLAIN, e->tfreq, nullptr, P_(e, "t_embedder.mlp.0.weight"), P_(e, "t_embedder.mlp.0.bias"), nullptr,
-                                nullptr, e->temb_pre, B, D, 256, D, st))) return rc;
+  if ((rc = launch_small_linear(IN_PLAIN, e->tfreq, nullptr, P(e, r.t0_w), P(e, r.t0_b), nullptr, nullptr, e->temb_pre, B, D, 256, D, st))) return rc;
   if ((rc = launch_silu_rows(e->temb_pre, e->temb_act, (size_t)B * D, st))) return rc;
-  if ((rc = launch_small_linear(IN_PLAIN, e->temb_act, nullptr, P_(e, "t_embedder.mlp.2.weight"), P_(e, "t_embedder.mlp.2.bias"),
-                                c.extras == 2 ? P_(e, "y_embedder.embedding_table.weight") : nullptr, c.extras == 2 ? y : nullptr, e->cvec, B,
-                                D, D, D, st))) return rc;
+  if ((rc = launch_small_linear(IN_PLAIN, e->temb_act, nullptr, P(e, r.t2_w), P(e, r.t2_b), c.extras == 2 ? P(e, r.y_table) : nullptr,
+                                c.extras == 2 ? y : nullptr, e->cvec, B, D, D, D, st))) return rc;
   if ((rc = launch_silu_rows(e->cvec, e->csilu, (size_t)B * D, st))) return rc;
   for (int i = 0; i < c.depth; ++i) {
-    const std::string p = "blocks." + std::to_string(i) + ".adaLN_modulation.1.";
-    if ((rc = launch_small_linear(IN_PLAIN, e->csilu, nullptr, P_(e, p + "weight"), P_(e, p + "bias"), nullptr, nullptr,
+    if ((rc = launch_small_linear(IN_PLAIN, e->csilu, nullptr, P(e, e->bp[i].ada_w), P(e, e->bp[i].ada_b), nullptr, nullptr,
                                   e->mod + (size_t)i * 6 * D, B, 6 * D, D, nmod, st))) return rc;
   }
-  if ((rc = launch_small_linear(IN_PLAIN, e->csilu, nullptr, P_(e, "final_layer.adaLN_modulation.1.weight"),
-                                P_(e, "final_layer.adaLN_modulation.1.bias"), nullptr, nullptr, e->mod + (size_t)c.depth * 6 * D, B, 2 * D, D,
-                                nmod, st))) return rc;
-  if ((rc = launch_patch_embed(e->x_t, e->pe_wt, P_(e, "x_embedder.proj.bias"), e->pos, e->xs[0], B * F, e->Cin, e->H, c.patch_size, D, st)))
+  if ((rc = launch_small_linear(IN_PLAIN, e->csilu, nullptr, P(e, r.fin_ada_w), P(e, r.fin_ada_b), nullptr, nullptr,
+                                e->mod + (size_t)c.depth * 6 * D, B, 2 * D, D, nmod, st))) return rc;
+  if ((rc = launch_patch_embed(e->x_t, e->pe_wt, P(e, r.pe_b), e->pos, e->xs[0], B * F, e->Cin, e->H, c.patch_size, D, st)))
     return rc;
   for (int i = 0; i < c.depth; ++i) {
     const bool spatial = (i % 2) == 0;
     if (!temporal && !spatial) continue;
     const int nx = temporal ? i + 1 : i + 2;   // the next block that runs: its input snapshot is xs[2 nx] (depth is even: nx <= depth)
-    const std::string p = "blocks." + std::to_string(i) + ".";
+    const BlockParams& w = e->bp[i];
     BlockBuf& b = e->blk[i];
     const float* mb = e->mod + (size_t)i * 6 * D;
     float* x0 = e->xs[2 * i];
@@ -458,14 +468,13 @@ int forward_part(latte_trainer_t* e, const int64_t* y, int batch, float* model_o
     // (fuse_small: blocks 1 .. depth-1 got xn1 -- and the temporal embedding -- from the previous block's closing gated add)
     if ((!e->fuse_small || i == 0) &&
         (rc = launch_ln_modulate(x0, x0, b.xn1, mb, mb + D, nmod, M, D, rps, i == 1 ? e->temp : nullptr, T, F, dt, st))) return rc;
-    if ((rc = gemm_half(e, b.xn1, b.qkv_w, P_(e, p + "attn.qkv.bias"), b.qkv, M, 3 * D, D, st))) return rc;
+    if ((rc = gemm_half(e, b.xn1, b.qkv_w, P(e, w.qkv_b), b.qkv, M, 3 * D, D, st))) return rc;
     AttnArgs a{};
     a.qkv = b.qkv; a.out = b.att; a.heads = c.num_heads; a.hd = e->hd; a.D = D;
     a.sample_stride = rps; a.scale = 1.0f / std::sqrt((float)e->hd);
-    if (spatial) { a.num_seq = B * F; a.L = T; a.U = F; a.seq_stride = T; a.row_stride = 1; }
-    else         { a.num_seq = B * T; a.L = F; a.U = T; a.seq_stride = 1; a.row_stride = T; }
+    seq_layout(a, spatial, B, F, T);
     if ((rc = launch_attention(a, dt, st))) return rc;
-    if ((rc = gemm_half(e, b.att, b.proj_w, P_(e, p + "attn.proj.bias"), b.y1, M, D, D, st))) return rc;
+    if ((rc = gemm_half(e, b.att, b.proj_w, P(e, w.proj_b), b.y1, M, D, D, st))) return rc;
     if (e->fuse_small) {   // x1 = x0 + g1 y1 and xn2 = LN-modulate(x1) in one pass over the rows
       if ((rc = launch_gated_add_ln(x0, b.y1, mb + 2 * D, nmod, x1, b.xn2, mb + 3 * D, mb + 4 * D, nmod, M, D, rps, nullptr, T, F, dt, st)))
         return rc;
@@ -474,12 +483,12 @@ int forward_part(latte_trainer_t* e, const int64_t* y, int batch, float* model_o
       if ((rc = launch_ln_modulate(x1, x1, b.xn2, mb + 3 * D, mb + 4 * D, nmod, M, D, rps, nullptr, T, F, dt, st))) return rc;
     }
     if (gelu_fusable(e, M, Hm, D)) {   // u and h = gelu(u) out of one launch (bit-identical to the separate pass)
-      if ((rc = gemm_gelu(e, EPI_BIAS_GELU_DUAL_H16, b.xn2, b.fc1_w, P_(e, p + "mlp.fc1.bias"), b.u, b.h, M, Hm, D, st))) return rc;
+      if ((rc = gemm_gelu(e, EPI_BIAS_GELU_DUAL_H16, b.xn2, b.fc1_w, P(e, w.fc1_b), b.u, b.h, M, Hm, D, st))) return rc;
     } else {
-      if ((rc = gemm_half(e, b.xn2, b.fc1_w, P_(e, p + "mlp.fc1.bias"), b.u, M, Hm, D, st))) return rc;
+      if ((rc = gemm_half(e, b.xn2, b.fc1_w, P(e, w.fc1_b), b.u, M, Hm, D, st))) return rc;
       if ((rc = launch_gelu_fwd(b.u, b.h, (size_t)M * Hm, dt, st))) return rc;
     }
-    if ((rc = gemm_half(e, b.h, b.fc2_w, P_(e, p + "mlp.fc2.bias"), b.y2, M, D, Hm, st))) return rc;
+    if ((rc = gemm_half(e, b.h, b.fc2_w, P(e, w.fc2_b), b.y2, M, D, Hm, st))) return rc;
     if (e->fuse_small && nx < c.depth) {   // x2 = x1 + g2 y2 (+ temp_embed in front of block 1) and the NEXT running block's xn1
       const float* nb = e->mod + (size_t)nx * 6 * D;
       if ((rc = launch_gated_add_ln(x1, b.y2, mb + 5 * D, nmod, x2, e->blk[nx].xn1, nb, nb + D, nmod, M, D, rps,
@@ -488,7 +497,7 @@ int forward_part(latte_trainer_t* e, const int64_t* y, int batch, float* model_o
   }
   float* xl = e->xs[2 * c.depth];
   const float* fm = e->mod + (size_t)c.depth * 6 * D;
-  if ((rc = launch_final_layer(xl, fm, fm + D, nmod, e->fin_wt, P_(e, "final_layer.linear.bias"), e->model_out, M, D, rps, T, c.patch_size,
+  if ((rc = launch_final_layer(xl, fm, fm + D, nmod, e->fin_wt, P(e, r.fin_b), e->model_out, M, D, rps, T, c.patch_size,
                                e->Cout, e->H, st))) return rc;
   if (model_out_copy)
     LATTE_HIP(hipMemcpyAsync(model_out_copy, e->model_out, sizeof(float) * (size_t)B * F * e->Cout * hw, hipMemcpyDeviceToDevice, st));
@@ -599,19 +608,198 @@ int latte_trainer_begin_joint(latte_trainer_t* e, const latte_schedule_t* s, int
 // adaLN linear of block i (i == depth: the final layer's): bias / weight gradients from the finished dmod rows, and its
 // contribution to d SiLU(c)
 static int adaln_bwd(latte_trainer_t* e, int i, hipStream_t st) {
-  const auto& c = e->cfg;
   const int D = e->D, B = e->cur_batch, nmod = e->nmod;
-  const bool fin = i == c.depth;
-  const std::string p = fin ? "final_layer.adaLN_modulation.1." : "blocks." + std::to_string(i) + ".adaLN_modulation.1.";
+  const bool fin = i == e->cfg.depth;
+  const int64_t w = fin ? e->rp.fin_ada_w : e->bp[i].ada_w, bias = fin ? e->rp.fin_ada_b : e->bp[i].ada_b;
   const int N = fin ? 2 * D : 6 * D;
   const float* dm = e->dmod + (size_t)i * 6 * D;
   int rc;
   const int acc = e->grad_accumulate;
   const float* gs = acc_scale(e);
-  if ((rc = launch_rows_sum(dm, B, nmod, N, G_(e, p + "bias"), acc, st, gs))) return rc;
-  if ((rc = launch_naive_gemm(dm, 1, nmod, e->csilu, D, 1, G_(e, p + "weight"), D, 1, N, D, B, 1.0f, acc, st, 1, nullptr, gs))) return rc;   // dW[n, k]
-  if ((rc = launch_naive_gemm(dm, nmod, 1, P_(e, p + "weight"), D, 1, e->dtmp, D, 1, B, D, N, 1.0f, 0, st, 48, e->ng_ws))) return rc;  // d csilu
+  if ((rc = launch_rows_sum(dm, B, nmod, N, G(e, bias), acc, st, gs))) return rc;
+  if ((rc = launch_naive_gemm(dm, 1, nmod, e->csilu, D, 1, G(e, w), D, 1, N, D, B, 1.0f, acc, st, 1, nullptr, gs))) return rc;   // dW[n, k]
+  if ((rc = launch_naive_gemm(dm, nmod, 1, P(e, w), D, 1, e->dtmp, D, 1, B, D, N, 1.0f, 0, st, 48, e->ng_ws))) return rc;  // d csilu
   return launch_add_rows(e->dc, e->dtmp, (size_t)B * D, st);
+}
+
+// the MLP gate's partial rows of block i wait in one of two buffers for its stage's finalize launch, which follows the pass that
+// fills the NEXT running block's: consecutive running blocks alternate (temporal off: blocks 0, 2, 4, ...)
+static float* pg2_of(const latte_trainer_t* e, int i) { return ((e->run_temporal ? i : i >> 1) & 1) ? e->pg2b : e->pg2; }
+
+// The backward of one linear y = x W^T + b behind dY [M, N] (x [M, K]; wt: the [K, N] operand copy of W): the bias gradient in the
+// form the mode asks for, dW, then dX = dY W -- through gelu'(u) where the linear's input was gelu(u).
+// fuse_small: the bias gradient is column-sum partial rows that wait for launch_stage_finalize -- pc [*pc_rows][N], filled here (on
+// the weight-gradient launch where the 8-wave kernel takes the shape), or pc == nullptr where the LayerNorm backward that produced dY
+// left them beside the gate's -- and wgrad unscales what it writes.  Otherwise launch_colsum_half sums straight into the gradient.
+static int linear_bwd(latte_trainer_t* e, const half_t* dY, const half_t* x, const half_t* wt, int M, int N, int K, int64_t w, int64_t bias,
+                      float* pc, int* pc_rows, half_t* dX, half_t* u, hipStream_t st) {
+  int rc;
+  if (e->fuse_small) {
+    const bool ride = pc && gemm_tn8_ok(M, N, K);
+    if (pc && !ride && (rc = launch_colsum_half(dY, M, N, pc, nullptr, 0, e->dt, st))) return rc;
+    if ((rc = wgrad(e, dY, x, M, N, K, G(e, w), st, scaling_active(e), ride ? pc : nullptr, ride ? pc_rows : nullptr))) return rc;
+  } else {
+    if ((rc = launch_colsum_half(dY, M, N, e->part_cols, G(e, bias), e->grad_accumulate, e->dt, st, acc_scale(e)))) return rc;
+    if ((rc = wgrad(e, dY, x, M, N, K, G(e, w), st))) return rc;
+  }
+  // du = (dy W) gelu'(u) in the GEMM's epilogue where it takes the shape (the product is not rounded to half in between)
+  if (u && gelu_fusable(e, M, K, N)) return gemm_gelu(e, EPI_DGELU_H16, dY, wt, e->zeros, dX, u, M, K, N, st);
+  if ((rc = gemm_half(e, dY, wt, e->zeros, dX, M, K, N, st))) return rc;
+  return u ? launch_gelu_bwd(u, dX, dX, (size_t)M * K, e->dt, st) : LATTE_OK;
+}
+
+// ---- stage 0, the final layer: out = unpatchify(Linear(LN-mod(x)))
+static int backward_final(latte_trainer_t* e, hipStream_t st) {
+  const auto& c = e->cfg;
+  const RestParams& r = e->rp;
+  int rc;
+  const int D = e->D, T = e->T, F = e->run_F, B = e->cur_batch, dt = e->dt, nmod = e->nmod;
+  const int M = B * F * T, rps = F * T;
+  const int acc = e->grad_accumulate;
+  const float* gs = acc_scale(e);
+  float* xl = e->xs[2 * c.depth];
+  const float* fm = e->mod + (size_t)c.depth * 6 * D;
+  if ((rc = launch_unpatchify_bwd(e->dmodel_out, e->dtok, B * F, e->G, c.patch_size, e->Cout, st))) return rc;
+  if (e->fuse_small && e->P <= 32) {
+    // the linear's weight / bias gradients (exact fp32 products of dtok with the half LN output, as below) in one launch + its
+    // reductions, and its input gradient straight to half (train_fin.hip)
+    if ((rc = launch_ln_modulate(xl, xl, e->xnh, fm, fm + D, nmod, M, D, rps, nullptr, T, F, dt, st))) return rc;
+    if ((rc = launch_narrow_outer(e->dtok, e->P, e->xnh, 1, D, M, G(e, r.fin_w), D, 1, G(e, r.fin_b), nullptr, e->no_ws, dt, gs, st, acc)))
+      return rc;
+    if ((rc = launch_narrow_dx(e->dtok, e->P, P(e, r.fin_w), D, M, e->dxnH, dt, st))) return rc;
+  } else {
+    if ((rc = launch_naive_gemm(e->ones, 0, 1, e->dtok, e->P, 1, G(e, r.fin_b), e->P, 1, 1, e->P, M, 1.0f, acc, st, 64, e->ng_ws, gs))) return rc;
+    if ((rc = launch_ln_modulate(xl, xl, e->xnh, fm, fm + D, nmod, M, D, rps, nullptr, T, F, dt, st))) return rc;
+    if ((rc = launch_convert_h16_to_f32(e->xnh, e->f32a, (int64_t)M * D, dt, st))) return rc;
+    if ((rc = launch_naive_gemm(e->dtok, 1, e->P, e->f32a, D, 1, G(e, r.fin_w), D, 1, e->P, D, M, 1.0f, acc, st, 64, e->ng_ws, gs))) return rc;
+    if ((rc = launch_naive_gemm(e->dtok, e->P, 1, P(e, r.fin_w), D, 1, e->f32b, D, 1, M, D, e->P, 1.0f, 0, st))) return rc;
+    if ((rc = launch_convert_f32_to_h16(e->f32b, e->dxnH, (int64_t)M * D, dt, st))) return rc;
+  }
+  float* dm = e->dmod + (size_t)c.depth * 6 * D;
+  if (!e->fuse_small) {
+    if ((rc = launch_ln_bwd(e->dxnH, xl, fm + D, nmod, nullptr, e->dx, e->part_rows, dm, dm + D, nmod, M, D, rps, dt, st))) return rc;
+    return adaln_bwd(e, c.depth, st);
+  }
+  // fuse_small: shift / scale gradients of the final modulation and its adaLN linear's bias / weight gradients in one launch ... and the
+  // gated residual's backward of the last block's MLP branch on the same pass over dx (its stage starts at the wgrad)
+  const int il = e->run_temporal ? c.depth - 1 : c.depth - 2;   // the last block that ran
+  if ((rc = launch_ln_bwd(e->dxnH, xl, fm + D, nmod, nullptr, e->dx, e->pl1, nullptr, nullptr, nmod, M, D, rps, dt, st, e->blk[il].y2,
+                          e->mod + (size_t)il * 6 * D + 5 * D, nmod, e->dyD, pg2_of(e, il)))) return rc;
+  StageFinArgs a{};
+  a.mod_src[0] = a.mod_src[1] = e->pl1; a.mod_nsum[0] = a.mod_nsum[1] = 2; a.mod_which[0] = 0; a.mod_which[1] = 1;
+  a.n_mod = 2; a.rows_per_sample = rps / (4 * train_rows_per_run(rps)); a.B = B; a.D = D;
+  a.dmod = dm; a.dmod_stride = nmod; a.csilu = e->csilu;
+  a.dW = G(e, r.fin_ada_w); a.db = G(e, r.fin_ada_b);
+  a.n_bias = 0; a.scaler = gs;   // assign mode: this stage's slice is unscaled by the pass behind the stage
+  a.accumulate = acc;
+  return launch_stage_finalize(a, st);
+}
+
+// ---- stages 1 .. depth, block i = depth - stage: x1 = x0 + g1 * proj(attn(qkv(xn1))), x2 = x1 + g2 * fc2(gelu(fc1(xn2)))
+static int backward_block(latte_trainer_t* e, int i, hipStream_t st) {
+  int rc;
+  const int D = e->D, T = e->T, F = e->run_F, Hm = e->Hm, B = e->cur_batch, dt = e->dt, nmod = e->nmod;
+  const bool temporal = e->run_temporal != 0, spatial = (i % 2) == 0, fs = e->fuse_small != 0;
+  const int M = B * F * T, rps = F * T;
+  if (!temporal && !spatial) return LATTE_OK;   // the block did not run: its gradient slice, dx and the waiting partial rows stay
+  const int ip = temporal ? i - 1 : i - 2;      // the running block in front of this one
+  const BlockParams& w = e->bp[i];
+  BlockBuf& b = e->blk[i];
+  const float* mb = e->mod + (size_t)i * 6 * D;
+  float* dm = e->dmod + (size_t)i * 6 * D;
+  float* pg2 = pg2_of(e, i);
+  // bias gradients of fc1 / qkv under fuse_small: partial rows per column-sum chunk, or per split of the weight-gradient launch
+  int fc1_rows = colsum_chunks(M), qkv_rows = colsum_chunks(M);
+  // ---- MLP branch.  fuse_small: dy = g2 dx and the gate / bias partial rows were left by the LayerNorm backward that produced dx
+  // (the previous stage's last pass); the partial rows wait for this stage's finalize launch
+  if (!fs && (rc = launch_gate_bwd(e->dx, b.y2, mb + 5 * D, nmod, e->dyD, e->part_rows, dm + 5 * D, nmod, M, D, rps, dt, st))) return rc;
+  if ((rc = linear_bwd(e, e->dyD, b.h, b.fc2_wt, M, D, Hm, w.fc2_w, w.fc2_b, nullptr, nullptr, e->dhH, b.u, st))) return rc;
+  if ((rc = linear_bwd(e, e->dhH, b.xn2, b.fc1_wt, M, Hm, D, w.fc1_w, w.fc1_b, e->pc_fc1, &fc1_rows, e->dxnH, nullptr, st))) return rc;
+  // ---- attention branch.  fuse_small: its gate backward rides on LN2's backward
+  if (fs) {
+    if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i + 1], mb + 4 * D, nmod, e->dx, e->dx, e->pl2, nullptr, nullptr, nmod, M, D, rps, dt, st, b.y1,
+                            mb + 2 * D, nmod, e->dyD, e->pg1))) return rc;
+  } else {
+    if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i + 1], mb + 4 * D, nmod, e->dx, e->dx, e->part_rows, dm + 3 * D, dm + 4 * D, nmod, M, D, rps, dt,
+                            st))) return rc;
+    if ((rc = launch_gate_bwd(e->dx, b.y1, mb + 2 * D, nmod, e->dyD, e->part_rows, dm + 2 * D, nmod, M, D, rps, dt, st))) return rc;
+  }
+  if ((rc = linear_bwd(e, e->dyD, b.att, b.proj_wt, M, D, D, w.proj_w, w.proj_b, nullptr, nullptr, e->dxnH, nullptr, st))) return rc;   // d(attention output)
+  AttnArgs sl{};
+  seq_layout(sl, spatial, B, F, T);
+  if ((rc = launch_attention_bwd(b.qkv, b.att, e->dxnH, e->dqkvH, e->attn_stats, sl.num_seq, sl.L, e->cfg.num_heads, e->hd, sl.U, rps,
+                                 sl.seq_stride, sl.row_stride, dt, st))) return rc;
+  if ((rc = linear_bwd(e, e->dqkvH, b.xn1, b.qkv_wt, M, 3 * D, D, w.qkv_w, w.qkv_b, e->pc_qkv, &qkv_rows, e->dxnH, nullptr, st))) return rc;
+  // ---- LN1's backward, and the stage's tail
+  if (!fs) {
+    if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i], mb + D, nmod, e->dx, e->dx, e->part_rows, dm, dm + D, nmod, M, D, rps, dt, st))) return rc;
+    return adaln_bwd(e, i, st);
+  }
+  if (ip >= 0) {   // + the gate backward of the previous running block's MLP branch (the next stage's first step)
+    if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i], mb + D, nmod, e->dx, e->dx, e->pl1, nullptr, nullptr, nmod, M, D, rps, dt, st, e->blk[ip].y2,
+                            e->mod + (size_t)ip * 6 * D + 5 * D, nmod, e->dyD, pg2_of(e, ip)))) return rc;
+  } else if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i], mb + D, nmod, e->dx, e->dx, e->pl1, nullptr, nullptr, nmod, M, D, rps, dt, st)))
+    return rc;
+  // one launch: the six modulation gradients, the adaLN linear's bias / weight gradients, the four linears' bias gradients
+  StageFinArgs a{};
+  const float* msrc[6] = {e->pl1, e->pl1, e->pg1, e->pl2, e->pl2, pg2};
+  const int mwhich[6] = {0, 1, 0, 0, 1, 0};
+  for (int k = 0; k < 6; ++k) { a.mod_src[k] = msrc[k]; a.mod_nsum[k] = 2; a.mod_which[k] = mwhich[k]; }
+  const int rb = rps / (4 * train_rows_per_run(rps));   // partial rows (blocks of 4 runs) per sample
+  a.n_mod = 6; a.rows_per_sample = rb; a.B = B; a.D = D;
+  a.dmod = dm; a.dmod_stride = nmod; a.csilu = e->csilu;
+  a.dW = G(e, w.ada_w); a.db = G(e, w.ada_b);
+  a.n_bias = 4;
+  a.bias_src[0] = e->pc_qkv;  a.bias_rows[0] = qkv_rows; a.bias_stride[0] = 3 * D; a.bias_cols[0] = 3 * D; a.bias_out[0] = G(e, w.qkv_b);
+  a.bias_src[1] = e->pg1 + D; a.bias_rows[1] = B * rb;   a.bias_stride[1] = 2 * D; a.bias_cols[1] = D;     a.bias_out[1] = G(e, w.proj_b);
+  a.bias_src[2] = e->pc_fc1;  a.bias_rows[2] = fc1_rows; a.bias_stride[2] = Hm;    a.bias_cols[2] = Hm;    a.bias_out[2] = G(e, w.fc1_b);
+  a.bias_src[3] = pg2 + D;    a.bias_rows[3] = B * rb;   a.bias_stride[3] = 2 * D; a.bias_cols[3] = D;     a.bias_out[3] = G(e, w.fc2_b);
+  a.scaler = scaling_active(e) ? e->scaler : nullptr;
+  a.accumulate = e->grad_accumulate;
+  return launch_stage_finalize(a, st);
+}
+
+// ---- stage depth + 1: patch embed (latte.py:233,330-331: tokens = pix W^T + b + pos) and the conditioning tail
+static int backward_embed(latte_trainer_t* e, hipStream_t st) {
+  const auto& c = e->cfg;
+  const RestParams& r = e->rp;
+  int rc;
+  const int D = e->D, T = e->T, F = e->run_F, B = e->cur_batch, dt = e->dt, nmod = e->nmod;
+  const int M = B * F * T;
+  const int acc = e->grad_accumulate;
+  const float* gs = acc_scale(e);
+  if (e->fuse_small && e->KPE <= 32) {   // dW[k][j] = sum_m dx[m][k] pix[m][j], db[k] = sum_m dx[m][k]: one launch + reductions
+    if ((rc = launch_im2col_patch(e->x_t, e->pix, B * F, e->G, c.patch_size, e->Cin, st))) return rc;
+    if ((rc = launch_narrow_outer(e->pix, e->KPE, e->dx, 0, D, M, G(e, r.pe_w), 1, e->KPE, nullptr, G(e, r.pe_b), e->no_ws, dt, gs, st, acc)))
+      return rc;
+  } else {
+    if ((rc = launch_naive_gemm(e->ones, 0, 1, e->dx, D, 1, G(e, r.pe_b), D, 1, 1, D, M, 1.0f, acc, st, 64, e->ng_ws, gs))) return rc;
+    if ((rc = launch_im2col_patch(e->x_t, e->pix, B * F, e->G, c.patch_size, e->Cin, st))) return rc;
+    if ((rc = launch_naive_gemm(e->dx, 1, D, e->pix, e->KPE, 1, G(e, r.pe_w), e->KPE, 1, D, e->KPE, M, 1.0f, acc, st, 64, e->ng_ws, gs))) return rc;
+  }
+  // ---- conditioning tail: d SiLU(c) (summed by the stages) -> c = temb (+ y_emb) -> t_embedder MLP
+  if (e->fuse_small) {   // d SiLU(c) = dmod W over every adaLN linear of the model at once (the stages left their dmod rows)
+    const int64_t stride = e->bp[1].ada_w - e->bp[0].ada_w;   // depth is even: block 1 exists
+    if ((rc = launch_adaln_dc(e->dmod, nmod, B, P(e, e->bp[0].ada_w), (long)stride, c.depth, 6 * D, P(e, r.fin_ada_w), D, e->dc_ws, e->dc, st)))
+      return rc;
+  }
+  if ((rc = launch_silu_bwd(e->dc, e->cvec, e->dtmp, (size_t)B * D, 0, st))) return rc;     // dtmp = dc (gradient of c = temb + y_emb)
+  if (c.extras == 2) {
+    // the scatter accumulates (a label may repeat inside the batch): clear the slice first, so that forward_backward ASSIGNS this
+    // gradient like every other one (two calls without an optimiser step in between must not double it).  Accumulate mode: no
+    // clear -- the scatter's own add IS the accumulation (rows of labels this micro-batch does not hold keep their sum)
+    float* gy = G(e, r.y_table);
+    if (!acc) LATTE_HIP(hipMemsetAsync(gy, 0, (size_t)(c.num_classes + 1) * D * sizeof(float), st));
+    if ((rc = launch_embedding_bwd(e->dtmp, e->cur_y, gy, B, D, st, gs))) return rc;
+  }
+  // temb = W2 SiLU(temb_pre) + b2
+  if ((rc = launch_rows_sum(e->dtmp, B, D, D, G(e, r.t2_b), acc, st, gs))) return rc;
+  if ((rc = launch_naive_gemm(e->dtmp, 1, D, e->temb_act, D, 1, G(e, r.t2_w), D, 1, D, D, B, 1.0f, acc, st, 1, nullptr, gs))) return rc;
+  if ((rc = launch_naive_gemm(e->dtmp, D, 1, P(e, r.t2_w), D, 1, e->dtmp2, D, 1, B, D, D, 1.0f, 0, st))) return rc;
+  if ((rc = launch_silu_bwd(e->dtmp2, e->temb_pre, e->dtmp2, (size_t)B * D, 0, st))) return rc;
+  // temb_pre = W0 freq(t) + b0
+  if ((rc = launch_rows_sum(e->dtmp2, B, D, D, G(e, r.t0_b), acc, st, gs))) return rc;
+  return launch_naive_gemm(e->dtmp2, 1, D, e->tfreq, 256, 1, G(e, r.t0_w), 256, 1, D, 256, B, 1.0f, acc, st, 1, nullptr, gs);
 }
 
 int latte_trainer_num_stages(const latte_trainer_t* e) { return e ? e->cfg.depth + 2 : 0; }
@@ -620,28 +808,32 @@ int latte_trainer_num_stages(const latte_trainer_t* e) { return e ? e->cfg.depth
 // depth + 1 = patch embed + t / y embedders (the head of the buffer)
 int latte_trainer_stage_range(const latte_trainer_t* e, int stage, int64_t* offset, int64_t* numel) {
   if (!e || !offset || !numel || stage < 0 || stage > e->cfg.depth + 1) return fail(LATTE_ERR_INVALID, "stage_range: bad stage");
-  auto off = [&](const std::string& k) { return e->params[e->index.at(k)].offset; };
   const int depth = e->cfg.depth;
-  if (stage == 0) { *offset = off("final_layer.linear.weight"); *numel = e->total - *offset; }
+  if (stage == 0) { *offset = e->rp.fin_w; *numel = e->total - *offset; }
   else if (stage <= depth) {
     const int i = depth - stage;
-    *offset = off("blocks." + std::to_string(i) + ".attn.qkv.weight");
-    const int64_t end = i + 1 < depth ? off("blocks." + std::to_string(i + 1) + ".attn.qkv.weight") : off("final_layer.linear.weight");
-    *numel = end - *offset;
-  } else { *offset = 0; *numel = off("blocks.0.attn.qkv.weight"); }
+    *offset = e->bp[i].qkv_w;
+    *numel = (i + 1 < depth ? e->bp[i + 1].qkv_w : e->rp.fin_w) - *offset;
+  } else { *offset = 0; *numel = e->bp[0].qkv_w; }
   return LATTE_OK;
 }
 
 // Backward of one stage (in order 0, 1, ..., depth + 1 after latte_trainer_begin).  After stage k the gradient slice
 // latte_trainer_stage_range(k) is final: the data-parallel driver starts its all-reduce while the next stages run.
-static int backward_stage_impl(latte_trainer_t* e, int stage, void* stream);
 int latte_trainer_backward_stage(latte_trainer_t* e, int stage, void* stream) {
-  int rc = backward_stage_impl(e, stage, stream);
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if (!e || !e->Pm) rc = fail(LATTE_ERR_STATE, "backward_stage: no step in flight");
+  else if (stage != e->next_stage || stage > e->cfg.depth + 1) rc = fail(LATTE_ERR_STATE, "backward_stage: stages run in order after latte_trainer_begin");
+  else {
+    e->next_stage = stage + 1;
+    rc = stage == 0 ? backward_final(e, st) : stage <= e->cfg.depth ? backward_block(e, e->cfg.depth - stage, st) : backward_embed(e, st);
+  }
   // (fuse_small: the block stages' slices were unscaled by the kernels that wrote them; accumulate mode: every slice was)
   if (!rc && scaling_active(e) && !e->grad_accumulate && !(e->fuse_small && stage >= 1 && stage <= e->cfg.depth)) {   // the slice this stage finalised leaves the loss-scaled domain
     int64_t off = 0, n = 0;
     if ((rc = latte_trainer_stage_range(e, stage, &off, &n))) return rc;
-    rc = launch_scale_f32_dev(e->Gr + off, e->scaler, 1, (size_t)n, (hipStream_t)stream);
+    rc = launch_scale_f32_dev(e->Gr + off, e->scaler, 1, (size_t)n, st);
   }
   if (e && e->joint_saved_acc >= 0 && (rc || stage == e->cfg.depth + 1)) {   // the image pass of a joint micro-batch is over
     plain_mode(e);
@@ -652,234 +844,42 @@ int latte_trainer_backward_stage(latte_trainer_t* e, int stage, void* stream) {
 
 int latte_trainer_set_option(latte_trainer_t* e, const char* name, double value) {
   if (!e || !name) return fail(LATTE_ERR_INVALID, "trainer_set_option: null argument");
-  if (std::string(name) == "loss_scale") {
-    int ex = 0;
-    if (!(value >= 1.0) || value > 16777216.0 || std::frexp(value, &ex) != 0.5)
-      return fail(LATTE_ERR_INVALID, "loss_scale must be a power of two in [1, 2^24]");
+  const std::string n(name);
+  if (n == "loss_scale") {
+    if (!pow2_in(value, 1.0, 16777216.0)) return fail(LATTE_ERR_INVALID, "loss_scale must be a power of two in [1, 2^24]");
     e->loss_scale = (float)value;
     return upload_scaler(e, 1);
   }
-  if (std::string(name) == "dynamic_loss_scale") {   // 0: the scale stays what "loss_scale" set (overflowing steps are still skipped)
+  if (n == "dynamic_loss_scale") {   // 0: the scale stays what "loss_scale" set (overflowing steps are still skipped)
     e->dynamic_scale = value != 0.0 ? 1 : 0;
     return upload_scaler(e, 2);
   }
-  if (std::string(name) == "loss_scale_growth_interval") {
+  if (n == "loss_scale_growth_interval") {
     if (!(value >= 1.0) || value > 1e7) return fail(LATTE_ERR_INVALID, "loss_scale_growth_interval must be in [1, 1e7]");
     e->growth_interval = (float)value;
     return upload_scaler(e, 2);
   }
-  if (std::string(name) == "fuse_small") {   // 0: the separate finalize / column-sum / adaLN launches of rounds 2 - 6, 1: train_fin.hip (default)
-    if (e->next_stage <= e->cfg.depth + 1 || e->custom == 1) return fail(LATTE_ERR_STATE, "fuse_small: a step is in flight");
+  if (n == "fuse_small") {   // 0: the separate finalize / column-sum / adaLN launches of rounds 2 - 6, 1: train_fin.hip (default)
+    if (step_in_flight(e) || e->custom == 1) return fail(LATTE_ERR_STATE, "fuse_small: a step is in flight");
     e->fuse_small = value != 0.0 ? 1 : 0;
     return LATTE_OK;
   }
-  if (std::string(name) == "grad_accumulate") {   // 0: the gradient writers assign (default), 1: they add (struct latte_trainer)
-    if (e->next_stage <= e->cfg.depth + 1) return fail(LATTE_ERR_STATE, "grad_accumulate: a step is in flight");
+  if (n == "grad_accumulate") {   // 0: the gradient writers assign (default), 1: they add (struct latte_trainer)
+    if (step_in_flight(e)) return fail(LATTE_ERR_STATE, "grad_accumulate: a step is in flight");
     e->grad_accumulate = value != 0.0 ? 1 : 0;
     return LATTE_OK;
   }
-  if (std::string(name) == "loss_divisor") {
-    if (e->next_stage <= e->cfg.depth + 1) return fail(LATTE_ERR_STATE, "loss_divisor: a step is in flight");
+  if (n == "loss_divisor") {
+    if (step_in_flight(e)) return fail(LATTE_ERR_STATE, "loss_divisor: a step is in flight");
     if (!(value >= 1.0) || value > 65536.0) return fail(LATTE_ERR_INVALID, "loss_divisor must be in [1, 65536]");
     e->loss_divisor = (float)value;
     return LATTE_OK;
   }
-  if (std::string(name) == "fuse_gelu") {   // 0: separate GELU passes (rounds 2 - 5), 1: inside the GEMM epilogues (default)
+  if (n == "fuse_gelu") {   // 0: separate GELU passes (rounds 2 - 5), 1: inside the GEMM epilogues (default)
     e->fuse_gelu = value != 0.0 ? 1 : 0;
     return LATTE_OK;
   }
   return fail(LATTE_ERR_INVALID, std::string("trainer_set_option: unknown option '") + name + "'");
-}
-
-static int backward_stage_impl(latte_trainer_t* e, int stage, void* stream) {
-  if (!e || !e->Pm) return fail(LATTE_ERR_STATE, "backward_stage: no step in flight");
-  if (stage != e->next_stage || stage > e->cfg.depth + 1) return fail(LATTE_ERR_STATE, "backward_stage: stages run in order after latte_trainer_begin");
-  e->next_stage = stage + 1;
-  const auto& c = e->cfg;
-  hipStream_t st = (hipStream_t)stream;
-  int rc;
-  const int D = e->D, T = e->T, F = e->run_F, Hm = e->Hm, B = e->cur_batch, dt = e->dt, nmod = e->nmod;
-  const bool temporal = e->run_temporal != 0;
-  const int M = B * F * T, rps = F * T;
-  const int64_t* y = e->cur_y;
-  // the MLP gate's partial rows of block i wait in one of two buffers for its stage's finalize launch, which follows the pass that
-  // fills the NEXT running block's: consecutive running blocks alternate (temporal off: blocks 0, 2, 4, ...)
-  auto pg2_of = [&](int i) { return ((temporal ? i : i >> 1) & 1) ? e->pg2b : e->pg2; };
-  const int acc = e->grad_accumulate;
-  const float* gs = acc_scale(e);
-  if (stage == 0) {
-  float* xl = e->xs[2 * c.depth];
-  const float* fm = e->mod + (size_t)c.depth * 6 * D;
-  // final layer: out = unpatchify(Linear(LN-mod(x)))
-  if ((rc = launch_unpatchify_bwd(e->dmodel_out, e->dtok, B * F, e->G, c.patch_size, e->Cout, st))) return rc;
-  if (e->fuse_small && e->P <= 32) {
-    // the linear's weight / bias gradients (exact fp32 products of dtok with the half LN output, as below) in one launch + its
-    // reductions, and its input gradient straight to half (train_fin.hip)
-    if ((rc = launch_ln_modulate(xl, xl, e->xnh, fm, fm + D, nmod, M, D, rps, nullptr, T, F, dt, st))) return rc;
-    if ((rc = launch_narrow_outer(e->dtok, e->P, e->xnh, 1, D, M, G_(e, "final_layer.linear.weight"), D, 1, G_(e, "final_layer.linear.bias"),
-                                  nullptr, e->no_ws, dt, gs, st, acc))) return rc;
-    if ((rc = launch_narrow_dx(e->dtok, e->P, P_(e, "final_layer.linear.weight"), D, M, e->dxnH, dt, st))) return rc;
-  } else {
-  if ((rc = launch_naive_gemm(e->ones, 0, 1, e->dtok, e->P, 1, G_(e, "final_layer.linear.bias"), e->P, 1, 1, e->P, M, 1.0f, acc, st, 64, e->ng_ws, gs)))
-    return rc;
-  if ((rc = launch_ln_modulate(xl, xl, e->xnh, fm, fm + D, nmod, M, D, rps, nullptr, T, F, dt, st))) return rc;
-  if ((rc = launch_convert_h16_to_f32(e->xnh, e->f32a, (int64_t)M * D, dt, st))) return rc;
-  if ((rc = launch_naive_gemm(e->dtok, 1, e->P, e->f32a, D, 1, G_(e, "final_layer.linear.weight"), D, 1, e->P, D, M, 1.0f, acc, st, 64, e->ng_ws, gs)))
-    return rc;
-  if ((rc = launch_naive_gemm(e->dtok, e->P, 1, P_(e, "final_layer.linear.weight"), D, 1, e->f32b, D, 1, M, D, e->P, 1.0f, 0, st))) return rc;
-  if ((rc = launch_convert_f32_to_h16(e->f32b, e->dxnH, (int64_t)M * D, dt, st))) return rc;
-  }
-  {
-    float* dm = e->dmod + (size_t)c.depth * 6 * D;
-    if (e->fuse_small) {   // shift / scale gradients of the final modulation and its adaLN linear's bias / weight gradients in one launch
-      {   // ... and the gated residual's backward of the last block's MLP branch on the same pass over dx (its stage starts at the wgrad)
-        const int il = temporal ? c.depth - 1 : c.depth - 2;   // the last block that ran
-        if ((rc = launch_ln_bwd(e->dxnH, xl, fm + D, nmod, nullptr, e->dx, e->pl1, nullptr, nullptr, nmod, M, D, rps, dt, st, e->blk[il].y2,
-                                e->mod + (size_t)il * 6 * D + 5 * D, nmod, e->dyD, pg2_of(il)))) return rc;
-      }
-      StageFinArgs a{};
-      a.mod_src[0] = a.mod_src[1] = e->pl1; a.mod_nsum[0] = a.mod_nsum[1] = 2; a.mod_which[0] = 0; a.mod_which[1] = 1;
-      a.n_mod = 2; a.rows_per_sample = rps / (4 * train_rows_per_run(rps)); a.B = B; a.D = D;
-      a.dmod = dm; a.dmod_stride = nmod; a.csilu = e->csilu;
-      a.dW = G_(e, "final_layer.adaLN_modulation.1.weight"); a.db = G_(e, "final_layer.adaLN_modulation.1.bias");
-      a.n_bias = 0; a.scaler = gs;   // assign mode: this stage's slice is unscaled by the pass behind the stage
-      a.accumulate = acc;
-      return launch_stage_finalize(a, st);
-    }
-    if ((rc = launch_ln_bwd(e->dxnH, xl, fm + D, nmod, nullptr, e->dx, e->part_rows, dm, dm + D, nmod, M, D, rps, dt, st))) return rc;
-  }
-  return adaln_bwd(e, c.depth, st);
-  }
-  if (stage <= c.depth) {
-    const int i = c.depth - stage;
-    const bool spatial = (i % 2) == 0;
-    if (!temporal && !spatial) return LATTE_OK;   // the block did not run: its gradient slice, dx and the waiting partial rows stay
-    const int ip = temporal ? i - 1 : i - 2;      // the running block in front of this one
-    const std::string p = "blocks." + std::to_string(i) + ".";
-    BlockBuf& b = e->blk[i];
-    const float* mb = e->mod + (size_t)i * 6 * D;
-    float* dm = e->dmod + (size_t)i * 6 * D;
-    if (e->fuse_small) {
-      const bool us = scaling_active(e);
-      // ---- MLP branch: x2 = x1 + g2 * (fc2(gelu(fc1(xn2)))).  dy = g2 dx and the gate / bias partial rows were left by the LayerNorm
-      // backward that produced dx (the previous stage's last pass); the partial rows wait for this stage's finalize launch
-      float* pg2 = pg2_of(i);
-      if ((rc = wgrad(e, e->dyD, b.h, M, D, Hm, G_(e, p + "mlp.fc2.weight"), st, us))) return rc;
-      if (gelu_fusable(e, M, Hm, D)) {
-        if ((rc = gemm_gelu(e, EPI_DGELU_H16, e->dyD, b.fc2_wt, e->zeros, e->dhH, b.u, M, Hm, D, st))) return rc;
-      } else {
-        if ((rc = gemm_half(e, e->dyD, b.fc2_wt, e->zeros, e->dhH, M, Hm, D, st))) return rc;
-        if ((rc = launch_gelu_bwd(b.u, e->dhH, e->dhH, (size_t)M * Hm, dt, st))) return rc;
-      }
-      // bias gradients of fc1 / qkv: column sums of dY on the weight-gradient launch where the 8-wave kernel takes the shape
-      int fc1_rows = colsum_chunks(M), qkv_rows = colsum_chunks(M);
-      const bool cs_fc1 = gemm_tn8_ok(M, Hm, D), cs_qkv = gemm_tn8_ok(M, 3 * D, D);
-      if (!cs_fc1 && (rc = launch_colsum_half(e->dhH, M, Hm, e->pc_fc1, nullptr, 0, dt, st))) return rc;
-      if ((rc = wgrad(e, e->dhH, b.xn2, M, Hm, D, G_(e, p + "mlp.fc1.weight"), st, us, cs_fc1 ? e->pc_fc1 : nullptr, cs_fc1 ? &fc1_rows : nullptr)))
-        return rc;
-      if ((rc = gemm_half(e, e->dhH, b.fc1_wt, e->zeros, e->dxnH, M, D, Hm, st))) return rc;
-      // ---- attention branch: x1 = x0 + g1 * proj(attn(qkv(xn1))): its gate backward rides on LN2's backward
-      if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i + 1], mb + 4 * D, nmod, e->dx, e->dx, e->pl2, nullptr, nullptr, nmod, M, D, rps, dt, st,
-                              b.y1, mb + 2 * D, nmod, e->dyD, e->pg1))) return rc;
-      if ((rc = wgrad(e, e->dyD, b.att, M, D, D, G_(e, p + "attn.proj.weight"), st, us))) return rc;
-      if ((rc = gemm_half(e, e->dyD, b.proj_wt, e->zeros, e->dxnH, M, D, D, st))) return rc;   // d(attention output)
-      if (spatial) rc = launch_attention_bwd(b.qkv, b.att, e->dxnH, e->dqkvH, e->attn_stats, B * F, T, c.num_heads, e->hd, F, rps, T, 1, dt, st);
-      else         rc = launch_attention_bwd(b.qkv, b.att, e->dxnH, e->dqkvH, e->attn_stats, B * T, F, c.num_heads, e->hd, T, rps, 1, T, dt, st);
-      if (rc) return rc;
-      if (!cs_qkv && (rc = launch_colsum_half(e->dqkvH, M, 3 * D, e->pc_qkv, nullptr, 0, dt, st))) return rc;
-      if ((rc = wgrad(e, e->dqkvH, b.xn1, M, 3 * D, D, G_(e, p + "attn.qkv.weight"), st, us, cs_qkv ? e->pc_qkv : nullptr,
-                      cs_qkv ? &qkv_rows : nullptr))) return rc;
-      if ((rc = gemm_half(e, e->dqkvH, b.qkv_wt, e->zeros, e->dxnH, M, D, 3 * D, st))) return rc;
-      if (ip >= 0) {   // LN1's backward + the gate backward of the previous running block's MLP branch (the next stage's first step)
-        if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i], mb + D, nmod, e->dx, e->dx, e->pl1, nullptr, nullptr, nmod, M, D, rps, dt, st,
-                                e->blk[ip].y2, e->mod + (size_t)ip * 6 * D + 5 * D, nmod, e->dyD, pg2_of(ip))))
-          return rc;
-      } else if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i], mb + D, nmod, e->dx, e->dx, e->pl1, nullptr, nullptr, nmod, M, D, rps, dt, st)))
-        return rc;
-      // ---- one launch: the six modulation gradients, the adaLN linear's bias / weight gradients, the four linears' bias gradients
-      StageFinArgs a{};
-      const float* msrc[6] = {e->pl1, e->pl1, e->pg1, e->pl2, e->pl2, pg2};
-      const int mwhich[6] = {0, 1, 0, 0, 1, 0};
-      for (int k = 0; k < 6; ++k) { a.mod_src[k] = msrc[k]; a.mod_nsum[k] = 2; a.mod_which[k] = mwhich[k]; }
-      const int rb = rps / (4 * train_rows_per_run(rps));   // partial rows (blocks of 4 runs) per sample
-      a.n_mod = 6; a.rows_per_sample = rb; a.B = B; a.D = D;
-      a.dmod = dm; a.dmod_stride = nmod; a.csilu = e->csilu;
-      a.dW = G_(e, p + "adaLN_modulation.1.weight"); a.db = G_(e, p + "adaLN_modulation.1.bias");
-      a.n_bias = 4;
-      a.bias_src[0] = e->pc_qkv;   a.bias_rows[0] = qkv_rows;   a.bias_stride[0] = 3 * D; a.bias_cols[0] = 3 * D; a.bias_out[0] = G_(e, p + "attn.qkv.bias");
-      a.bias_src[1] = e->pg1 + D;  a.bias_rows[1] = B * rb; a.bias_stride[1] = 2 * D; a.bias_cols[1] = D;     a.bias_out[1] = G_(e, p + "attn.proj.bias");
-      a.bias_src[2] = e->pc_fc1;   a.bias_rows[2] = fc1_rows;   a.bias_stride[2] = Hm;    a.bias_cols[2] = Hm;    a.bias_out[2] = G_(e, p + "mlp.fc1.bias");
-      a.bias_src[3] = pg2 + D;      a.bias_rows[3] = B * rb; a.bias_stride[3] = 2 * D; a.bias_cols[3] = D;     a.bias_out[3] = G_(e, p + "mlp.fc2.bias");
-      a.scaler = us ? e->scaler : nullptr;
-      a.accumulate = acc;
-      return launch_stage_finalize(a, st);
-    }
-    // ---- MLP branch: x2 = x1 + g2 * (fc2(gelu(fc1(xn2))))
-    if ((rc = launch_gate_bwd(e->dx, b.y2, mb + 5 * D, nmod, e->dyD, e->part_rows, dm + 5 * D, nmod, M, D, rps, dt, st))) return rc;
-    if ((rc = launch_colsum_half(e->dyD, M, D, e->part_cols, G_(e, p + "mlp.fc2.bias"), acc, dt, st, gs))) return rc;
-    if ((rc = wgrad(e, e->dyD, b.h, M, D, Hm, G_(e, p + "mlp.fc2.weight"), st))) return rc;
-    if (gelu_fusable(e, M, Hm, D)) {   // du = (dy W2) gelu'(u) in the GEMM's epilogue (the product is not rounded to half in between)
-      if ((rc = gemm_gelu(e, EPI_DGELU_H16, e->dyD, b.fc2_wt, e->zeros, e->dhH, b.u, M, Hm, D, st))) return rc;
-    } else {
-      if ((rc = gemm_half(e, e->dyD, b.fc2_wt, e->zeros, e->dhH, M, Hm, D, st))) return rc;
-      if ((rc = launch_gelu_bwd(b.u, e->dhH, e->dhH, (size_t)M * Hm, dt, st))) return rc;
-    }
-    if ((rc = launch_colsum_half(e->dhH, M, Hm, e->part_cols, G_(e, p + "mlp.fc1.bias"), acc, dt, st, gs))) return rc;
-    if ((rc = wgrad(e, e->dhH, b.xn2, M, Hm, D, G_(e, p + "mlp.fc1.weight"), st))) return rc;
-    if ((rc = gemm_half(e, e->dhH, b.fc1_wt, e->zeros, e->dxnH, M, D, Hm, st))) return rc;
-    if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i + 1], mb + 4 * D, nmod, e->dx, e->dx, e->part_rows, dm + 3 * D, dm + 4 * D, nmod, M, D, rps, dt,
-                            st))) return rc;
-    // ---- attention branch: x1 = x0 + g1 * proj(attn(qkv(xn1)))
-    if ((rc = launch_gate_bwd(e->dx, b.y1, mb + 2 * D, nmod, e->dyD, e->part_rows, dm + 2 * D, nmod, M, D, rps, dt, st))) return rc;
-    if ((rc = launch_colsum_half(e->dyD, M, D, e->part_cols, G_(e, p + "attn.proj.bias"), acc, dt, st, gs))) return rc;
-    if ((rc = wgrad(e, e->dyD, b.att, M, D, D, G_(e, p + "attn.proj.weight"), st))) return rc;
-    if ((rc = gemm_half(e, e->dyD, b.proj_wt, e->zeros, e->dxnH, M, D, D, st))) return rc;   // d(attention output)
-    if (spatial) rc = launch_attention_bwd(b.qkv, b.att, e->dxnH, e->dqkvH, e->attn_stats, B * F, T, c.num_heads, e->hd, F, rps, T, 1, dt, st);
-    else         rc = launch_attention_bwd(b.qkv, b.att, e->dxnH, e->dqkvH, e->attn_stats, B * T, F, c.num_heads, e->hd, T, rps, 1, T, dt, st);
-    if (rc) return rc;
-    if ((rc = launch_colsum_half(e->dqkvH, M, 3 * D, e->part_cols, G_(e, p + "attn.qkv.bias"), acc, dt, st, gs))) return rc;
-    if ((rc = wgrad(e, e->dqkvH, b.xn1, M, 3 * D, D, G_(e, p + "attn.qkv.weight"), st))) return rc;
-    if ((rc = gemm_half(e, e->dqkvH, b.qkv_wt, e->zeros, e->dxnH, M, D, 3 * D, st))) return rc;
-    if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i], mb + D, nmod, e->dx, e->dx, e->part_rows, dm, dm + D, nmod, M, D, rps, dt, st))) return rc;
-    return adaln_bwd(e, i, st);
-  }
-  // ---- patch embed (latte.py:233,330-331): tokens = pix W^T + b + pos
-  if (e->fuse_small && e->KPE <= 32) {   // dW[k][j] = sum_m dx[m][k] pix[m][j], db[k] = sum_m dx[m][k]: one launch + reductions
-    if ((rc = launch_im2col_patch(e->x_t, e->pix, B * F, e->G, c.patch_size, e->Cin, st))) return rc;
-    if ((rc = launch_narrow_outer(e->pix, e->KPE, e->dx, 0, D, M, G_(e, "x_embedder.proj.weight"), 1, e->KPE, nullptr,
-                                  G_(e, "x_embedder.proj.bias"), e->no_ws, dt, gs, st, acc))) return rc;
-  } else {
-  if ((rc = launch_naive_gemm(e->ones, 0, 1, e->dx, D, 1, G_(e, "x_embedder.proj.bias"), D, 1, 1, D, M, 1.0f, acc, st, 64, e->ng_ws, gs))) return rc;
-  if ((rc = launch_im2col_patch(e->x_t, e->pix, B * F, e->G, c.patch_size, e->Cin, st))) return rc;
-  if ((rc = launch_naive_gemm(e->dx, 1, D, e->pix, e->KPE, 1, G_(e, "x_embedder.proj.weight"), e->KPE, 1, D, e->KPE, M, 1.0f, acc, st, 64,
-                              e->ng_ws, gs))) return rc;
-  }
-  // ---- conditioning tail: d SiLU(c) (summed by the stages) -> c = temb (+ y_emb) -> t_embedder MLP
-  if (e->fuse_small) {   // d SiLU(c) = dmod W over every adaLN linear of the model at once (the stages left their dmod rows)
-    auto off = [&](const std::string& k) { return e->params[e->index.at(k)].offset; };
-    const int64_t o0 = off("blocks.0.adaLN_modulation.1.weight");
-    const int64_t stride = off("blocks.1.adaLN_modulation.1.weight") - o0;
-    if ((rc = launch_adaln_dc(e->dmod, nmod, B, e->Pm + o0, (long)stride, c.depth, 6 * D, P_(e, "final_layer.adaLN_modulation.1.weight"), D,
-                              e->dc_ws, e->dc, st))) return rc;
-  }
-  if ((rc = launch_silu_bwd(e->dc, e->cvec, e->dtmp, (size_t)B * D, 0, st))) return rc;     // dtmp = dc (gradient of c = temb + y_emb)
-  if (c.extras == 2) {
-    // the scatter accumulates (a label may repeat inside the batch): clear the slice first, so that forward_backward ASSIGNS this
-    // gradient like every other one (two calls without an optimiser step in between must not double it).  Accumulate mode: no
-    // clear -- the scatter's own add IS the accumulation (rows of labels this micro-batch does not hold keep their sum)
-    float* gy = G_(e, "y_embedder.embedding_table.weight");
-    if (!acc) LATTE_HIP(hipMemsetAsync(gy, 0, (size_t)(c.num_classes + 1) * D * sizeof(float), st));
-    if ((rc = launch_embedding_bwd(e->dtmp, y, gy, B, D, st, gs))) return rc;
-  }
-  // temb = W2 SiLU(temb_pre) + b2
-  if ((rc = launch_rows_sum(e->dtmp, B, D, D, G_(e, "t_embedder.mlp.2.bias"), acc, st, gs))) return rc;
-  if ((rc = launch_naive_gemm(e->dtmp, 1, D, e->temb_act, D, 1, G_(e, "t_embedder.mlp.2.weight"), D, 1, D, D, B, 1.0f, acc, st, 1, nullptr, gs))) return rc;
-  if ((rc = launch_naive_gemm(e->dtmp, D, 1, P_(e, "t_embedder.mlp.2.weight"), D, 1, e->dtmp2, D, 1, B, D, D, 1.0f, 0, st))) return rc;
-  if ((rc = launch_silu_bwd(e->dtmp2, e->temb_pre, e->dtmp2, (size_t)B * D, 0, st))) return rc;
-  // temb_pre = W0 freq(t) + b0
-  if ((rc = launch_rows_sum(e->dtmp2, B, D, D, G_(e, "t_embedder.mlp.0.bias"), acc, st, gs))) return rc;
-  if ((rc = launch_naive_gemm(e->dtmp2, 1, D, e->tfreq, 256, 1, G_(e, "t_embedder.mlp.0.weight"), 256, 1, D, 256, B, 1.0f, acc, st, 1, nullptr, gs))) return rc;
-  return LATTE_OK;
 }
 
 // begin + every stage: one micro-batch, gradients of terms["loss"].mean() in the bound gradient buffer
@@ -904,7 +904,7 @@ int latte_trainer_forward(latte_trainer_t* e, const float* x, const int64_t* t_m
   if (!e || !x || !t_model || !model_out) return fail(LATTE_ERR_INVALID, "trainer_forward: null argument");
   if (!e->Pm) return fail(LATTE_ERR_STATE, "trainer_forward: bind the parameter buffers first");
   if (e->joint_saved_acc >= 0) return fail(LATTE_ERR_STATE, "trainer_forward: the image pass of a joint micro-batch is in flight");
-  if (e->next_stage <= e->cfg.depth + 1) return fail(LATTE_ERR_STATE, "trainer_forward: a step is in flight");
+  if (step_in_flight(e)) return fail(LATTE_ERR_STATE, "trainer_forward: a step is in flight");
   if (batch <= 0 || batch > e->max_batch) return fail(LATTE_ERR_STATE, "trainer_forward: batch exceeds max_batch");
   if (e->cfg.extras == 2 && !y) return fail(LATTE_ERR_INVALID, "trainer_forward: class-conditional model needs y");
   hipStream_t st = (hipStream_t)stream;
@@ -940,7 +940,7 @@ int latte_trainer_input_grad(latte_trainer_t* e, float* dx_out, void* stream) {
   if (e->custom != 2 || e->next_stage != e->cfg.depth + 2)
     return fail(LATTE_ERR_STATE, "trainer_input_grad: valid after the last backward stage of a pass that latte_trainer_seed started");
   // e->dx is the gradient of the patch embed's output (block 0's LayerNorm backward left it), e->pix is free after the last stage
-  return launch_patch_embed_dgrad(e->dx, P_(e, "x_embedder.proj.weight"), dx_out, e->cur_batch * e->F, e->G, e->cfg.patch_size, e->Cin, e->D,
+  return launch_patch_embed_dgrad(e->dx, P(e, e->rp.pe_w), dx_out, e->cur_batch * e->F, e->G, e->cfg.patch_size, e->Cin, e->D,
                                   e->pix, scaling_active(e) ? e->scaler : nullptr, (hipStream_t)stream);
 }
 
@@ -975,10 +975,8 @@ int latte_trainer_scaler_state(latte_trainer_t* e, double* out8) {
 // count, AdamW's bias-correction count = applied updates, the skip counters, the policy).  Not while a step is in flight.
 int latte_trainer_set_scaler_state(latte_trainer_t* e, const double* in8) {
   if (!e || !in8) return fail(LATTE_ERR_INVALID, "trainer_set_scaler_state: null argument");
-  if (e->next_stage <= e->cfg.depth + 1) return fail(LATTE_ERR_STATE, "trainer_set_scaler_state: a step is in flight");
-  int ex = 0;
-  if (!(in8[0] >= 1.0) || in8[0] > 16777216.0 || std::frexp(in8[0], &ex) != 0.5 || !(in8[7] >= in8[0]) || in8[7] > 16777216.0 ||
-      std::frexp(in8[7], &ex) != 0.5)
+  if (step_in_flight(e)) return fail(LATTE_ERR_STATE, "trainer_set_scaler_state: a step is in flight");
+  if (!pow2_in(in8[0], 1.0, 16777216.0) || !pow2_in(in8[7], in8[0], 16777216.0))
     return fail(LATTE_ERR_INVALID, "trainer_set_scaler_state: loss scale and largest scale must be powers of two in [1, 2^24], scale <= largest");
   for (int i = 1; i <= 4; ++i)
     if (!(in8[i] >= 0.0) || in8[i] > 16777216.0 || in8[i] != std::floor(in8[i]))
