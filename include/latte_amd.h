@@ -455,6 +455,32 @@ int latte_trainer_scaler_state(latte_trainer_t* e, double* out8);
 int latte_trainer_set_scaler_state(latte_trainer_t* e, const double* in8);
 int latte_trainer_optimizer_step(latte_trainer_t* e, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                                  float clip_max_norm, int clip, float ema_decay, float* norm_out, void* stream);
+/* LoRA fine-tuning (DESIGN.md 4.4 "LoRA"; not part of the reference): every targeted block linear y = x W^T + b, W [N, K], runs with
+ * W_eff = W + s B A -- A [rank, K], B [N, rank], s = alpha / rank.  The whole base (W, b and every other parameter) is frozen; only A
+ * and B are trained.  The forward and the input gradients run on the merged half operand copies (the step-end pack writes
+ * half(W + s B A), one rounding), the adapter gradients come from dY, x and the adapters themselves (csrc/train_lora.hip).
+ * latte_trainer_lora_enable: rank in {4, 8, 16, 32} (64 is refused: its step measured slower than the full step), alpha > 0, target_mask a non-empty subset of qkv = 1 | proj = 2 | fc1 = 4 |
+ * fc2 = 8.  Legal once, BEFORE the buffers are bound; refused (LATTE_ERR_STATE) afterwards or while a step is in flight.
+ * The adapters live in a second set of caller-owned flat fp32 buffers laid out by latte_trainer_lora_param_*: keys
+ * blocks.{i}.attn.qkv.lora_A / .lora_B, blocks.{i}.attn.proj.*, blocks.{i}.mlp.fc1.*, blocks.{i}.mlp.fc2.* in block order, 16-byte
+ * aligned tensors.  latte_trainer_bind_lora replaces latte_trainer_bind (which is then refused): base_params is the plain trainer's
+ * parameter buffer, read only; there are no base gradient, moment or EMA buffers.  In LoRA mode every writer of a base gradient is
+ * skipped (one that is reached anyway ends its stage with LATTE_ERR_STATE before any launch), latte_trainer_sync_weights packs the
+ * merged weights, latte_trainer_optimizer_step runs norm / clip / AdamW / EMA over the adapter buffers, latte_trainer_stage_range
+ * reports slices of the ADAPTER gradient buffer (block stages: the block's adapters; the two other stages: empty), and
+ * latte_trainer_input_grad, gradient accumulation, joint steps and custom losses work as before.
+ * latte_trainer_lora_merge: fp32 W + s B A of every targeted weight -- the pack's arithmetic in its order, so half() of it is the
+ * operand the LoRA trainer ran with -- into params_out, a copy of the flat parameter buffer (or the bound buffer itself, which ends the
+ * LoRA run: a later sync would add the adapters again); lora_params NULL = the bound adapters, else e.g. their EMA.  Synchronises. */
+int latte_trainer_lora_enable(latte_trainer_t* e, int rank, float alpha, int target_mask);
+int latte_trainer_lora_num_params(const latte_trainer_t* e);
+const char* latte_trainer_lora_param_key(const latte_trainer_t* e, int i);
+int64_t latte_trainer_lora_param_offset(const latte_trainer_t* e, int i);
+int64_t latte_trainer_lora_param_numel(const latte_trainer_t* e, int i);
+int64_t latte_trainer_lora_total_numel(const latte_trainer_t* e);
+int latte_trainer_bind_lora(latte_trainer_t* e, float* base_params, float* lora_params, float* lora_grads, float* lora_exp_avg,
+                            float* lora_exp_avg_sq, float* lora_ema);
+int latte_trainer_lora_merge(latte_trainer_t* e, const float* lora_params, float* params_out, void* stream);
 
 /* ------------------------------------------------------------------ VAE decoder
  * Replaces diffusers.AutoencoderKL (sample/sample.py:69 from_pretrained, :113-115 vae.decode(z / 0.18215).sample;

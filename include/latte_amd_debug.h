@@ -294,6 +294,28 @@ int latte_debug_patch_embed_dgrad(const float* dx, const float* W, float* out, i
 int latte_debug_pack_weights(const float* const* w_ptrs, const int* N, const int* K, void* const* wn_ptrs, void* const* wt_ptrs, int blocks,
                              int dtype, void* stream);
 int latte_debug_pack_weight(const float* w, void* wn, void* wt, int N, int K, int dtype, void* stream);
+/* LoRA kernels of csrc/train_lora.hip (rank in {4, 8, 16, 32, 64} at kernel level -- latte_trainer_lora_enable offers 4 .. 32 --; R16 = rank rounded up to a multiple of 16).
+ * pack_weights_lora: latte_debug_pack_weights with W + s B A in place of W -- HOST arrays a_ptrs / b_ptrs [blocks * 4] of fp32 A [rank, K]
+ * and B [N, rank] (both NULL: the linear is not targeted); the sum is fp32, rank index ascending, and B = 0 leaves W's bits.  wf_ptrs
+ * != NULL: the merge form -- the fp32 sum goes to wf_ptrs[i] ([N, K], targeted linears only) and no half copy is written.
+ * lora_down: out half [M, 2 R16] = the split pair [hi | lo] of v = scale * big [M, Kbig] wd [R16, Kbig]^T (wd zero-padded by the caller):
+ * hi = half(v), lo = half((v - hi) * L), L = 2048 for f16 and 256 for bf16; M % 64 == 0, Kbig % 128 == 0.
+ * lora_outer: small half [M, 2 R16] in that form; sum over rows m of (hi + lo / L) [m, R16] (x) big [m, Kbig] as chunked partial products (rows_per_chunk rows each, a multiple of
+ * 64; latte_debug_lora_outer_plan is the trainer's choice) + the fixed-order reduction: kr == 0: out fp32 [rank, Kbig], kr != 0: out
+ * fp32 [Kbig, rank]; columns rank .. R16 - 1 of hi and of lo are not stored.  accumulate / inv_scale_dev as latte_debug_split_reduce.
+ * workspace >= ceil(M / rows_per_chunk) * rank * Kbig floats. */
+int latte_debug_pack_weights_lora(const float* const* w_ptrs, const int* N, const int* K, void* const* wn_ptrs, void* const* wt_ptrs,
+                                  float* const* wf_ptrs, const float* const* a_ptrs, const float* const* b_ptrs, int blocks, int rank,
+                                  float s, int dtype, void* stream);
+/* Host logic only: the adapter table latte_trainer_lora_enable(rank, alpha, target_mask) lays out for a model of `cfg` (hidden_size,
+ * mlp_hidden, depth are read) -- *num_params entries, *total floats; index >= 0: that entry's key (NUL-terminated into key_out
+ * [key_cap]), offset and numel.  A rank, alpha or mask that latte_trainer_lora_enable refuses is refused here with its message. */
+int latte_debug_lora_table(const struct latte_model_config* cfg, int rank, float alpha, int target_mask, int index, char* key_out,
+                           int key_cap, int64_t* offset, int64_t* numel, int* num_params, int64_t* total);
+int latte_debug_lora_down(const void* big, const void* wd, void* out, int M, int Kbig, int rank, float scale, int dtype, void* stream);
+int latte_debug_lora_outer_plan(int M, int Kbig, int* rows_per_chunk);
+int latte_debug_lora_outer(const void* small, const void* big, float* out, float* workspace, int64_t workspace_floats, int M, int Kbig,
+                           int rank, int rows_per_chunk, int kr, int accumulate, const float* inv_scale_dev, int dtype, void* stream);
 /* d mean_b(terms["loss"]) / d model_output of GaussianDiffusion.training_losses (gaussian_diffusion.py:719-795) for the schedule's
  * model types: loss_type 0 MSE, 1 RESCALED_MSE; x_start / x_t / noise [batch, frames, channels, hw], model_out and dmodel_out
  * [batch, frames, channels (x 2 when the schedule learns sigma), hw] fp32; t: int64 [batch] timestep indices. */

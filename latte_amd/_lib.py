@@ -118,6 +118,14 @@ PROTOTYPES = {
     "latte_trainer_input_grad": (c_int, [c_void, c_void, c_void]),
     "latte_trainer_optimizer_step": (c_int, [c_void, c_f32, c_f32, c_f32, c_f32, c_f32, c_int, c_f32, c_int, c_f32, c_void, c_void]),
     "latte_trainer_set_option": (c_int, [c_void, c_char, ctypes.c_double]),
+    "latte_trainer_lora_enable": (c_int, [c_void, c_int, c_f32, c_int]),
+    "latte_trainer_lora_num_params": (c_int, [c_void]),
+    "latte_trainer_lora_param_key": (c_char, [c_void, c_int]),
+    "latte_trainer_lora_param_offset": (c_i64, [c_void, c_int]),
+    "latte_trainer_lora_param_numel": (c_i64, [c_void, c_int]),
+    "latte_trainer_lora_total_numel": (c_i64, [c_void]),
+    "latte_trainer_bind_lora": (c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
+    "latte_trainer_lora_merge": (c_int, [c_void, c_void, c_void, c_void]),
     "latte_trainer_scaler_state": (c_int, [c_void, ctypes.POINTER(ctypes.c_double)]),
     "latte_trainer_set_scaler_state": (c_int, [c_void, ctypes.POINTER(ctypes.c_double)]),
     "latte_profile_forward": (c_int, [c_void, c_void, c_void, c_void, c_int, c_void, c_void, c_void, c_int, c_void]),
@@ -252,6 +260,14 @@ PROTOTYPES = {
     "latte_debug_patch_embed_dgrad": (c_int, [c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_void, c_void]),
     "latte_debug_pack_weights": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_void]),
     "latte_debug_pack_weight": (c_int, [c_void, c_void, c_void, c_int, c_int, c_int, c_void]),
+    "latte_debug_pack_weights_lora": (c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_f32,
+                                              c_int, c_void]),
+    "latte_debug_lora_table": (c_int, [ctypes.POINTER(ModelConfig), c_int, c_f32, c_int, c_int, c_void, c_int, ctypes.POINTER(c_i64),
+                                       ctypes.POINTER(c_i64), ctypes.POINTER(c_int), ctypes.POINTER(c_i64)]),
+    "latte_debug_lora_down": (c_int, [c_void, c_void, c_void, c_int, c_int, c_int, c_f32, c_int, c_void]),
+    "latte_debug_lora_outer_plan": (c_int, [c_int, c_int, ctypes.POINTER(c_int)]),
+    "latte_debug_lora_outer": (c_int, [c_void, c_void, c_void, c_void, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_void, c_int,
+                                       c_void]),
     "latte_debug_loss_grad": (c_int, [c_void, c_int, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void,
                                       c_void]),
     "latte_debug_fill_normal": (c_int, [c_void, c_i64, c_u64, c_u64, c_void]),

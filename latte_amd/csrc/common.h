@@ -384,6 +384,16 @@ int launch_patch_embed_dgrad(const float* dx, const float* W, float* out, int BF
 struct PackDesc { const float* w; half_t* wn; half_t* wt; int N, K; };
 struct PackPlan { int tiles_per_block; int tile0[4]; };
 int launch_pack_weights(const PackDesc* descs_dev, int blocks, const PackPlan& pl, int dtype, hipStream_t st);
+// LoRA on the four block linears (train_lora.hip).  A table entry: the frozen fp32 weight and its half operand copies as in PackDesc;
+// A [r, K] / B [N, r] the fp32 adapters (nullptr: the linear is not targeted) and their zero-padded half copies a_h [R16, K],
+// bt_h [R16, N] (R16 = r rounded up to 16); wf != nullptr: the pack writes the fp32 merged weight there instead of the half copies
+struct LoraPackDesc { const float* w; half_t* wn; half_t* wt; float* wf; int N, K; const float* A; const float* B; half_t* a_h; half_t* bt_h; };
+int launch_pack_weights_lora(const LoraPackDesc* descs_dev, int blocks, const PackPlan& pl, int r, float s, int dtype, hipStream_t st);
+int launch_lora_operands(const LoraPackDesc* descs_dev, int entries, int r, int dtype, hipStream_t st);
+int launch_lora_down(const half_t* big, const half_t* wd, half_t* out, int M, int Kbig, int r, float scale, int dtype, hipStream_t st);
+int lora_outer_plan(int M, int Kbig, int* chunk);
+int launch_lora_outer(const half_t* small, const half_t* big, float* partial, int M, int Kbig, int r, int m_chunk, int kr, int dtype,
+                      hipStream_t st);
 int launch_naive_gemm(const float* A, long sam, long sak, const float* B, long sbk, long sbn, float* C, long scm, long scn, int M, int N,
                       int K, float alpha, int accumulate, hipStream_t st, int splits = 1, float* ws = nullptr,
                       const float* inv_scale_dev = nullptr);

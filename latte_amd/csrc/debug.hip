@@ -667,6 +667,60 @@ int latte_debug_pack_weights(const float* const* w_ptrs, const int* N, const int
   return rc;
 }
 
+int latte_debug_pack_weights_lora(const float* const* w_ptrs, const int* N, const int* K, void* const* wn_ptrs, void* const* wt_ptrs,
+                                  float* const* wf_ptrs, const float* const* a_ptrs, const float* const* b_ptrs, int blocks, int rank,
+                                  float s, int dtype, void* stream) {
+  if (!w_ptrs || !N || !K || !a_ptrs || !b_ptrs || blocks < 1 || (!wf_ptrs && (!wn_ptrs || !wt_ptrs)))
+    return fail(LATTE_ERR_INVALID, "pack_weights_lora: bad arguments");
+  PackPlan pl{};
+  int t0 = 0;
+  for (int j = 0; j < 4; ++j) {
+    if (N[j] < 1 || K[j] < 1) return fail(LATTE_ERR_INVALID, "pack_weights_lora: bad shape");
+    pl.tile0[j] = t0;
+    t0 += ((N[j] + 31) / 32) * ((K[j] + 31) / 32);
+  }
+  pl.tiles_per_block = t0;
+  std::vector<LoraPackDesc> h((size_t)blocks * 4);
+  for (int i = 0; i < blocks * 4; ++i) {
+    if (!w_ptrs[i] || (wf_ptrs ? !wf_ptrs[i] : (!wn_ptrs[i] || !wt_ptrs[i])) || !a_ptrs[i] != !b_ptrs[i])
+      return fail(LATTE_ERR_INVALID, "pack_weights_lora: null tensor");
+    h[i] = LoraPackDesc{w_ptrs[i], wf_ptrs ? nullptr : (half_t*)wn_ptrs[i], wf_ptrs ? nullptr : (half_t*)wt_ptrs[i],
+                        wf_ptrs ? wf_ptrs[i] : nullptr, N[i & 3], K[i & 3], a_ptrs[i], b_ptrs[i], nullptr, nullptr};
+  }
+  hipStream_t st = (hipStream_t)stream;
+  LoraPackDesc* descs = nullptr;
+  LATTE_HIP(hipMalloc((void**)&descs, h.size() * sizeof(LoraPackDesc)));
+  int rc = LATTE_OK;
+  if (hipMemcpy(descs, h.data(), h.size() * sizeof(LoraPackDesc), hipMemcpyHostToDevice) != hipSuccess)
+    rc = fail(LATTE_ERR_HIP, "pack_weights_lora: table upload failed");
+  if (!rc) rc = launch_pack_weights_lora(descs, blocks, pl, rank, s, dtype, st);
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(descs);
+  return rc;
+}
+
+int latte_debug_lora_down(const void* big, const void* wd, void* out, int M, int Kbig, int rank, float scale, int dtype, void* stream) {
+  if (!big || !wd || !out) return fail(LATTE_ERR_INVALID, "lora_down: null argument");
+  return launch_lora_down((const half_t*)big, (const half_t*)wd, (half_t*)out, M, Kbig, rank, scale, dtype, (hipStream_t)stream);
+}
+
+int latte_debug_lora_outer_plan(int M, int Kbig, int* rows_per_chunk) {
+  if (M < 64 || Kbig < 128 || !rows_per_chunk) return fail(LATTE_ERR_INVALID, "lora_outer_plan: bad arguments");
+  return lora_outer_plan(M, Kbig, rows_per_chunk);
+}
+
+int latte_debug_lora_outer(const void* small, const void* big, float* out, float* workspace, int64_t workspace_floats, int M, int Kbig,
+                           int rank, int rows_per_chunk, int kr, int accumulate, const float* inv_scale_dev, int dtype, void* stream) {
+  if (!small || !big || !out || !workspace || rows_per_chunk <= 0 || M <= 0 || rank <= 0 || Kbig <= 0)
+    return fail(LATTE_ERR_INVALID, "lora_outer: bad arguments");
+  const int chunks = (M + rows_per_chunk - 1) / rows_per_chunk;
+  const size_t n = (size_t)rank * Kbig;
+  if ((int64_t)(chunks * n) > workspace_floats) return fail(LATTE_ERR_INVALID, "lora_outer: workspace too small");
+  if (int rc = launch_lora_outer((const half_t*)small, (const half_t*)big, workspace, M, Kbig, rank, rows_per_chunk, kr, dtype,
+                                 (hipStream_t)stream)) return rc;
+  return launch_split_reduce(workspace, chunks, n, n, out, accumulate ? 1 : 0, (hipStream_t)stream, inv_scale_dev);
+}
+
 int latte_debug_pack_weight(const float* w, void* wn, void* wt, int N, int K, int dtype, void* stream) {
   if (!w || N < 1 || K < 1) return fail(LATTE_ERR_INVALID, "pack_weight: bad arguments");
   return launch_pack_weight(w, (half_t*)wn, (half_t*)wt, N, K, dtype, (hipStream_t)stream);

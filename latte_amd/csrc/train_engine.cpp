@@ -33,6 +33,11 @@ struct BlockBuf {
   half_t *xn1, *qkv, *att, *y1, *xn2, *u, *h, *y2;
   half_t *qkv_w, *qkv_wt, *proj_w, *proj_wt, *fc1_w, *fc1_wt, *fc2_w, *fc2_wt;
 };
+// LoRA: where a block's adapters lie in the flat adapter buffers (-1: the linear is not targeted), linear j = qkv, proj, fc1, fc2
+struct LoraOffsets { int64_t a[4], b[4], begin; };
+const char* const LORA_LINEAR[4] = {"attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2"};
+// a gradient writer of the frozen base was reached in LoRA mode (G() below): the stage ends with LATTE_ERR_STATE before its launch
+struct FrozenBaseWrite {};
 }  // namespace
 
 struct latte_trainer {
@@ -112,6 +117,19 @@ struct latte_trainer {
   // 2 = seeded (its stages run, or have run: the token gradient e->dx of the last one is what latte_trainer_input_grad reads)
   int custom = 0, fwd_batch = 0;
   const int64_t* fwd_y = nullptr;
+  // LoRA (latte_trainer_lora_enable; train_lora.hip): the base buffer is frozen -- no base gradient, moment or EMA buffer
+  // is bound, every base-gradient writer is skipped -- and rank-r adapters on the targeted block linears train instead.  The half operand
+  // copies hold W + s B A (the pack adds it), so the forward and the input-gradient GEMMs are the plain trainer's launches; linear_bwd
+  // replaces the weight-gradient GEMM by the adapter gradients.  A second flat table (lparams) lays the adapters out.
+  int lora_rank = 0, lora_mask = 0;
+  float lora_s = 0.f;
+  std::vector<ParamInfo> lparams;
+  std::vector<LoraOffsets> lo;
+  int64_t ltotal = 0;
+  float *LP = nullptr, *LG = nullptr, *LM1 = nullptr, *LV2 = nullptr, *LEma = nullptr;   // bound flat adapter buffers (caller-owned)
+  std::vector<LoraPackDesc> lora_host;   // [block][qkv, proj, fc1, fc2]
+  LoraPackDesc *lora_descs = nullptr, *lora_merge_descs = nullptr;
+  half_t *lora_h = nullptr, *lora_g = nullptr;   // [rows_pad, 2 R16]: s x A^T and s dY B of the linear in hand, as split pairs hi | lo
   DeviceArena arena;
 };
 
@@ -125,8 +143,53 @@ int64_t add_param(latte_trainer* e, const std::string& key, int64_t numel) {
   return off;
 }
 
+// ---- LoRA: what latte_trainer_lora_enable accepts, and the adapter table (host logic: latte_debug_lora_table reads it without a device)
+int lora_validate(int rank, float alpha, int target_mask) {
+  // rank 64: the kernels take it (train_lora.hip, tested per element), the trainer does not -- at Latte-B/2, batch 5 its step measured
+  // slower than the full step it replaces (18.41 against 17.93 ms, profiles/train_lora.json); it comes back with the fused dY pass
+  if (rank == 64)
+    return fail(LATTE_ERR_INVALID, "lora_enable: rank 64 is not offered: its step is slower than full fine-tuning at Latte-B/2 (DESIGN 4.4); rank must be one of 4, 8, 16, 32");
+  if (rank != 4 && rank != 8 && rank != 16 && rank != 32)
+    return fail(LATTE_ERR_INVALID, "lora_enable: rank must be one of 4, 8, 16, 32");
+  if (target_mask < 1 || target_mask > 15)
+    return fail(LATTE_ERR_INVALID, "lora_enable: target_mask must be a non-empty subset of qkv = 1, proj = 2, fc1 = 4, fc2 = 8");
+  if (!(alpha > 0.0f) || !std::isfinite(alpha)) return fail(LATTE_ERR_INVALID, "lora_enable: alpha must be positive and finite");
+  return LATTE_OK;
+}
+void lora_shape(int D, int Hm, int j, int* N, int* K) {   // W [N, K] of linear j
+  const int shp[4][2] = {{3 * D, D}, {D, D}, {Hm, D}, {D, Hm}};
+  *N = shp[j][0]; *K = shp[j][1];
+}
+// block-major, per block qkv, proj, fc1, fc2 (the targeted ones), per linear lora_A [rank, K] then lora_B [N, rank] -> total floats
+int64_t lora_table(int D, int Hm, int depth, int rank, int target_mask, std::vector<ParamInfo>& lp, std::vector<LoraOffsets>& lo) {
+  int64_t total = 0;
+  auto add = [&](const std::string& key, int64_t numel) {
+    const int64_t off = total;
+    lp.push_back(ParamInfo{key, off, numel});
+    total += (numel + 3) / 4 * 4;   // 16-byte aligned tensors, as in the base table
+    return off;
+  };
+  lo.assign((size_t)depth, LoraOffsets{});
+  for (int i = 0; i < depth; ++i) {
+    lo[i].begin = total;
+    for (int j = 0; j < 4; ++j) {
+      lo[i].a[j] = lo[i].b[j] = -1;
+      if (!(target_mask >> j & 1)) continue;
+      int N, K;
+      lora_shape(D, Hm, j, &N, &K);
+      const std::string p = "blocks." + std::to_string(i) + "." + LORA_LINEAR[j];
+      lo[i].a[j] = add(p + ".lora_A", (int64_t)rank * K);
+      lo[i].b[j] = add(p + ".lora_B", (int64_t)N * rank);
+    }
+  }
+  return total;
+}
+
 float* P(const latte_trainer* e, int64_t off) { return e->Pm + off; }
-float* G(const latte_trainer* e, int64_t off) { return e->Gr + off; }
+float* G(const latte_trainer* e, int64_t off) {
+  if (e->lora_rank || !e->Gr) throw FrozenBaseWrite{};   // LoRA: there is no base gradient buffer (latte_trainer_backward_stage catches)
+  return e->Gr + off;
+}
 // a step is in flight: begin / seed ran and a backward stage is still due
 bool step_in_flight(const latte_trainer* e) { return e->next_stage <= e->cfg.depth + 1; }
 bool pow2_in(double v, double lo, double hi) {
@@ -360,6 +423,7 @@ int64_t latte_trainer_total_numel(const latte_trainer_t* e) { return e ? e->tota
 
 int latte_trainer_bind(latte_trainer_t* e, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* ema) {
   if (!e || !params || !grads || !exp_avg || !exp_avg_sq) return fail(LATTE_ERR_INVALID, "trainer_bind: null buffer");
+  if (e->lora_rank) return fail(LATTE_ERR_STATE, "trainer_bind: LoRA is enabled, bind with latte_trainer_bind_lora");
   e->Pm = params; e->Gr = grads; e->M1 = exp_avg; e->V2 = exp_avg_sq; e->Ema = ema;
   e->weights_synced = false;
   {   // pointer table of the one-launch weight pack (train_fin.hip): [block][qkv, proj, fc1, fc2]
@@ -380,6 +444,116 @@ int latte_trainer_bind(latte_trainer_t* e, float* params, float* grads, float* e
   return LATTE_OK;
 }
 
+// ---- LoRA: enable (before bind), the adapter table, bind, merge
+int latte_trainer_lora_enable(latte_trainer_t* e, int rank, float alpha, int target_mask) {
+  if (!e) return fail(LATTE_ERR_INVALID, "lora_enable: null trainer");
+  if (step_in_flight(e) || e->custom == 1) return fail(LATTE_ERR_STATE, "lora_enable: a step is in flight");
+  if (e->Pm || e->lora_rank) return fail(LATTE_ERR_STATE, "lora_enable: legal once, before the buffers are bound");
+  int rc;
+  if ((rc = lora_validate(rank, alpha, target_mask))) return rc;
+  const int D = e->D, Hm = e->Hm, depth = e->cfg.depth, R16 = (rank + 15) / 16 * 16;
+  std::vector<ParamInfo> lp;
+  std::vector<LoraOffsets> lo;
+  const int64_t total = lora_table(D, Hm, depth, rank, target_mask, lp, lo);
+  std::vector<LoraPackDesc> host((size_t)depth * 4);
+  auto A = [&](auto** p, size_t n) { if (!rc) rc = e->arena.alloc(p, n); };
+  for (int i = 0; i < depth; ++i)
+    for (int j = 0; j < 4; ++j) {
+      LoraPackDesc& d = host[(size_t)i * 4 + j];
+      d = LoraPackDesc{};
+      lora_shape(D, Hm, j, &d.N, &d.K);
+      if (lo[i].a[j] < 0) continue;
+      A(&d.a_h, (size_t)R16 * d.K);
+      A(&d.bt_h, (size_t)R16 * d.N);
+    }
+  A(&e->lora_h, (size_t)e->rows_pad * 2 * R16);   // split pairs [hi | lo]
+  A(&e->lora_g, (size_t)e->rows_pad * 2 * R16);
+  A(&e->lora_descs, (size_t)depth * 4);
+  A(&e->lora_merge_descs, (size_t)depth * 4);
+  if (rc) return rc;
+  e->lparams = std::move(lp);
+  e->lo = std::move(lo);
+  e->lora_host = std::move(host);
+  e->ltotal = total;
+  e->lora_mask = target_mask;
+  e->lora_s = alpha / (float)rank;
+  e->lora_rank = rank;
+  return LATTE_OK;
+}
+
+// Host logic only (include/latte_amd_debug.h): entry `index` of the adapter table a trainer of `cfg` would get
+int latte_debug_lora_table(const latte_model_config_t* cfg, int rank, float alpha, int target_mask, int index, char* key_out, int key_cap,
+                           int64_t* offset, int64_t* numel, int* num_params, int64_t* total) {
+  if (!cfg || cfg->depth < 1 || cfg->hidden_size < 1 || cfg->mlp_hidden < 1) return fail(LATTE_ERR_INVALID, "lora_table: bad config");
+  if (int rc = lora_validate(rank, alpha, target_mask)) return rc;
+  std::vector<ParamInfo> lp;
+  std::vector<LoraOffsets> lo;
+  const int64_t t = lora_table(cfg->hidden_size, cfg->mlp_hidden, cfg->depth, rank, target_mask, lp, lo);
+  if (num_params) *num_params = (int)lp.size();
+  if (total) *total = t;
+  if (index < 0) return LATTE_OK;   // the counts only
+  if (index >= (int)lp.size() || !key_out || key_cap <= (int)lp[index].key.size()) return fail(LATTE_ERR_INVALID, "lora_table: bad index or key buffer");
+  std::copy(lp[index].key.begin(), lp[index].key.end(), key_out);
+  key_out[lp[index].key.size()] = 0;
+  if (offset) *offset = lp[index].offset;
+  if (numel) *numel = lp[index].numel;
+  return LATTE_OK;
+}
+
+int latte_trainer_lora_num_params(const latte_trainer_t* e) { return e ? (int)e->lparams.size() : 0; }
+const char* latte_trainer_lora_param_key(const latte_trainer_t* e, int i) {
+  return (e && i >= 0 && i < (int)e->lparams.size()) ? e->lparams[i].key.c_str() : nullptr;
+}
+int64_t latte_trainer_lora_param_offset(const latte_trainer_t* e, int i) { return (e && i >= 0 && i < (int)e->lparams.size()) ? e->lparams[i].offset : -1; }
+int64_t latte_trainer_lora_param_numel(const latte_trainer_t* e, int i) { return (e && i >= 0 && i < (int)e->lparams.size()) ? e->lparams[i].numel : -1; }
+int64_t latte_trainer_lora_total_numel(const latte_trainer_t* e) { return e ? e->ltotal : 0; }
+
+int latte_trainer_bind_lora(latte_trainer_t* e, float* base_params, float* lora_params, float* lora_grads, float* lora_exp_avg,
+                            float* lora_exp_avg_sq, float* lora_ema) {
+  if (!e || !base_params || !lora_params || !lora_grads || !lora_exp_avg || !lora_exp_avg_sq) return fail(LATTE_ERR_INVALID, "trainer_bind_lora: null buffer");
+  if (!e->lora_rank) return fail(LATTE_ERR_STATE, "trainer_bind_lora: call latte_trainer_lora_enable first");
+  if (step_in_flight(e) || e->custom == 1) return fail(LATTE_ERR_STATE, "trainer_bind_lora: a step is in flight");
+  e->Pm = base_params; e->Gr = nullptr; e->M1 = nullptr; e->V2 = nullptr; e->Ema = nullptr;
+  e->LP = lora_params; e->LG = lora_grads; e->LM1 = lora_exp_avg; e->LV2 = lora_exp_avg_sq; e->LEma = lora_ema;
+  e->weights_synced = false;
+  for (int i = 0; i < e->cfg.depth; ++i) {
+    const BlockParams& w = e->bp[i];
+    BlockBuf& b = e->blk[i];
+    const int64_t wo[4] = {w.qkv_w, w.proj_w, w.fc1_w, w.fc2_w};
+    half_t* const wn[4] = {b.qkv_w, b.proj_w, b.fc1_w, b.fc2_w};
+    half_t* const wt[4] = {b.qkv_wt, b.proj_wt, b.fc1_wt, b.fc2_wt};
+    for (int j = 0; j < 4; ++j) {
+      LoraPackDesc& d = e->lora_host[(size_t)i * 4 + j];
+      d.w = P(e, wo[j]); d.wn = wn[j]; d.wt = wt[j]; d.wf = nullptr;
+      d.A = e->lo[i].a[j] >= 0 ? e->LP + e->lo[i].a[j] : nullptr;
+      d.B = e->lo[i].b[j] >= 0 ? e->LP + e->lo[i].b[j] : nullptr;
+    }
+  }
+  LATTE_HIP(hipDeviceSynchronize());
+  LATTE_HIP(hipMemcpy(e->lora_descs, e->lora_host.data(), e->lora_host.size() * sizeof(LoraPackDesc), hipMemcpyHostToDevice));
+  return LATTE_OK;
+}
+
+// params_out: a caller's copy of the flat base buffer (or the bound buffer itself: every element is read before it is written);
+// lora_params: the adapters to merge (NULL: the bound ones; the EMA buffer merges the EMA adapters).  Synchronises.
+int latte_trainer_lora_merge(latte_trainer_t* e, const float* lora_params, float* params_out, void* stream) {
+  if (!e || !params_out) return fail(LATTE_ERR_INVALID, "lora_merge: null argument");
+  if (!e->lora_rank || !e->Pm) return fail(LATTE_ERR_STATE, "lora_merge: bind the LoRA buffers first");
+  if (step_in_flight(e)) return fail(LATTE_ERR_STATE, "lora_merge: a step is in flight");
+  const float* lp = lora_params ? lora_params : e->LP;
+  std::vector<LoraPackDesc> h = e->lora_host;
+  for (LoraPackDesc& d : h) {
+    d.wf = params_out + (d.w - e->Pm);
+    d.wn = d.wt = nullptr;
+    if (d.A) { d.A = lp + (d.A - e->LP); d.B = lp + (d.B - e->LP); }
+  }
+  LATTE_HIP(hipDeviceSynchronize());
+  LATTE_HIP(hipMemcpy(e->lora_merge_descs, h.data(), h.size() * sizeof(LoraPackDesc), hipMemcpyHostToDevice));
+  if (int rc = launch_pack_weights_lora(e->lora_merge_descs, e->cfg.depth, e->pack_plan, e->lora_rank, e->lora_s, e->dt, (hipStream_t)stream)) return rc;
+  LATTE_HIP(hipStreamSynchronize((hipStream_t)stream));
+  return LATTE_OK;
+}
+
 int latte_trainer_set_frozen(latte_trainer_t* e, const float* pos_embed, const float* temp_embed, int on_device, void* stream) {
   if (!e || !pos_embed || !temp_embed) return fail(LATTE_ERR_INVALID, "trainer_set_frozen: null");
   const hipMemcpyKind k = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -393,7 +567,10 @@ int latte_trainer_sync_weights(latte_trainer_t* e, void* stream) {
   if (!e || !e->Pm) return fail(LATTE_ERR_STATE, "trainer_sync_weights: bind the parameter buffers first");
   hipStream_t st = (hipStream_t)stream;
   int rc;
-  if (e->fuse_small) {
+  if (e->lora_rank) {   // half(W + s B A) into the same operand copies, and the adapters' own padded half copies
+    if ((rc = launch_pack_weights_lora(e->lora_descs, e->cfg.depth, e->pack_plan, e->lora_rank, e->lora_s, e->dt, st))) return rc;
+    if ((rc = launch_lora_operands(e->lora_descs, e->cfg.depth * 4, e->lora_rank, e->dt, st))) return rc;
+  } else if (e->fuse_small) {
     if ((rc = launch_pack_weights(e->pack_descs, e->cfg.depth, e->pack_plan, e->dt, st))) return rc;
   } else {   // the same table, one launch per entry
     for (const PackDesc& d : e->pack_host)
@@ -626,15 +803,42 @@ static int adaln_bwd(latte_trainer_t* e, int i, hipStream_t st) {
 // fills the NEXT running block's: consecutive running blocks alternate (temporal off: blocks 0, 2, 4, ...)
 static float* pg2_of(const latte_trainer_t* e, int i) { return ((e->run_temporal ? i : i >> 1) & 1) ? e->pg2b : e->pg2; }
 
+// The adapter gradients of targeted linear li behind dY [M, N] (x [M, K]): h = s x A^T and g = s dY B by the row-local product (kept as
+// split half pairs, train_lora.hip), then
+// dB = dY^T h and dA = g^T x as chunked outer products whose partials launch_split_reduce sums in chunk order, takes out of the
+// loss-scaled domain and assigns -- or, in accumulate mode, adds -- to the adapter gradient buffer.  Four launches + two reductions.
+static int lora_grads(latte_trainer_t* e, int li, const half_t* dY, const half_t* x, int M, int N, int K, hipStream_t st) {
+  const LoraPackDesc& d = e->lora_host[li];
+  if (!d.A) return LATTE_OK;
+  const int r = e->lora_rank, dt = e->dt;
+  const float* us = scaling_active(e) ? e->scaler : nullptr;
+  float* dA = e->LG + (d.A - e->LP);
+  float* dB = e->LG + (d.B - e->LP);
+  int rc, chunk = 0;
+  if ((rc = launch_lora_down(x, d.a_h, e->lora_h, M, K, r, e->lora_s, dt, st))) return rc;
+  if ((rc = launch_lora_down(dY, d.bt_h, e->lora_g, M, N, r, e->lora_s, dt, st))) return rc;
+  int splits = lora_outer_plan(M, N, &chunk);
+  if ((int64_t)splits * r * N > e->wg_ws_floats) return fail(LATTE_ERR_STATE, "lora: workspace too small");
+  if ((rc = launch_lora_outer(e->lora_h, dY, e->wg_ws, M, N, r, chunk, 1, dt, st))) return rc;
+  if ((rc = launch_split_reduce(e->wg_ws, splits, (size_t)r * N, (size_t)r * N, dB, e->grad_accumulate, st, us))) return rc;
+  splits = lora_outer_plan(M, K, &chunk);
+  if ((int64_t)splits * r * K > e->wg_ws_floats) return fail(LATTE_ERR_STATE, "lora: workspace too small");
+  if ((rc = launch_lora_outer(e->lora_g, x, e->wg_ws, M, K, r, chunk, 0, dt, st))) return rc;
+  return launch_split_reduce(e->wg_ws, splits, (size_t)r * K, (size_t)r * K, dA, e->grad_accumulate, st, us);
+}
+
 // The backward of one linear y = x W^T + b behind dY [M, N] (x [M, K]; wt: the [K, N] operand copy of W): the bias gradient in the
 // form the mode asks for, dW, then dX = dY W -- through gelu'(u) where the linear's input was gelu(u).
 // fuse_small: the bias gradient is column-sum partial rows that wait for launch_stage_finalize -- pc [*pc_rows][N], filled here (on
 // the weight-gradient launch where the 8-wave kernel takes the shape), or pc == nullptr where the LayerNorm backward that produced dY
 // left them beside the gate's -- and wgrad unscales what it writes.  Otherwise launch_colsum_half sums straight into the gradient.
+// LoRA (li = block * 4 + linear): W and b are frozen -- no bias sums, no weight gradient; a targeted linear gets its adapter gradients.
 static int linear_bwd(latte_trainer_t* e, const half_t* dY, const half_t* x, const half_t* wt, int M, int N, int K, int64_t w, int64_t bias,
-                      float* pc, int* pc_rows, half_t* dX, half_t* u, hipStream_t st) {
+                      int li, float* pc, int* pc_rows, half_t* dX, half_t* u, hipStream_t st) {
   int rc;
-  if (e->fuse_small) {
+  if (e->lora_rank) {
+    if ((rc = lora_grads(e, li, dY, x, M, N, K, st))) return rc;
+  } else if (e->fuse_small) {
     const bool ride = pc && gemm_tn8_ok(M, N, K);
     if (pc && !ride && (rc = launch_colsum_half(dY, M, N, pc, nullptr, 0, e->dt, st))) return rc;
     if ((rc = wgrad(e, dY, x, M, N, K, G(e, w), st, scaling_active(e), ride ? pc : nullptr, ride ? pc_rows : nullptr))) return rc;
@@ -659,32 +863,36 @@ static int backward_final(latte_trainer_t* e, hipStream_t st) {
   const float* gs = acc_scale(e);
   float* xl = e->xs[2 * c.depth];
   const float* fm = e->mod + (size_t)c.depth * 6 * D;
+  const bool lora = e->lora_rank != 0;   // the base is frozen: only the input gradients of the stage are due
   if ((rc = launch_unpatchify_bwd(e->dmodel_out, e->dtok, B * F, e->G, c.patch_size, e->Cout, st))) return rc;
   if (e->fuse_small && e->P <= 32) {
     // the linear's weight / bias gradients (exact fp32 products of dtok with the half LN output, as below) in one launch + its
     // reductions, and its input gradient straight to half (train_fin.hip)
     if ((rc = launch_ln_modulate(xl, xl, e->xnh, fm, fm + D, nmod, M, D, rps, nullptr, T, F, dt, st))) return rc;
-    if ((rc = launch_narrow_outer(e->dtok, e->P, e->xnh, 1, D, M, G(e, r.fin_w), D, 1, G(e, r.fin_b), nullptr, e->no_ws, dt, gs, st, acc)))
+    if (!lora && (rc = launch_narrow_outer(e->dtok, e->P, e->xnh, 1, D, M, G(e, r.fin_w), D, 1, G(e, r.fin_b), nullptr, e->no_ws, dt, gs, st, acc)))
       return rc;
     if ((rc = launch_narrow_dx(e->dtok, e->P, P(e, r.fin_w), D, M, e->dxnH, dt, st))) return rc;
   } else {
-    if ((rc = launch_naive_gemm(e->ones, 0, 1, e->dtok, e->P, 1, G(e, r.fin_b), e->P, 1, 1, e->P, M, 1.0f, acc, st, 64, e->ng_ws, gs))) return rc;
+    if (!lora && (rc = launch_naive_gemm(e->ones, 0, 1, e->dtok, e->P, 1, G(e, r.fin_b), e->P, 1, 1, e->P, M, 1.0f, acc, st, 64, e->ng_ws, gs))) return rc;
     if ((rc = launch_ln_modulate(xl, xl, e->xnh, fm, fm + D, nmod, M, D, rps, nullptr, T, F, dt, st))) return rc;
-    if ((rc = launch_convert_h16_to_f32(e->xnh, e->f32a, (int64_t)M * D, dt, st))) return rc;
-    if ((rc = launch_naive_gemm(e->dtok, 1, e->P, e->f32a, D, 1, G(e, r.fin_w), D, 1, e->P, D, M, 1.0f, acc, st, 64, e->ng_ws, gs))) return rc;
+    if (!lora) {
+      if ((rc = launch_convert_h16_to_f32(e->xnh, e->f32a, (int64_t)M * D, dt, st))) return rc;
+      if ((rc = launch_naive_gemm(e->dtok, 1, e->P, e->f32a, D, 1, G(e, r.fin_w), D, 1, e->P, D, M, 1.0f, acc, st, 64, e->ng_ws, gs))) return rc;
+    }
     if ((rc = launch_naive_gemm(e->dtok, e->P, 1, P(e, r.fin_w), D, 1, e->f32b, D, 1, M, D, e->P, 1.0f, 0, st))) return rc;
     if ((rc = launch_convert_f32_to_h16(e->f32b, e->dxnH, (int64_t)M * D, dt, st))) return rc;
   }
   float* dm = e->dmod + (size_t)c.depth * 6 * D;
   if (!e->fuse_small) {
     if ((rc = launch_ln_bwd(e->dxnH, xl, fm + D, nmod, nullptr, e->dx, e->part_rows, dm, dm + D, nmod, M, D, rps, dt, st))) return rc;
-    return adaln_bwd(e, c.depth, st);
+    return lora ? LATTE_OK : adaln_bwd(e, c.depth, st);
   }
   // fuse_small: shift / scale gradients of the final modulation and its adaLN linear's bias / weight gradients in one launch ... and the
   // gated residual's backward of the last block's MLP branch on the same pass over dx (its stage starts at the wgrad)
   const int il = e->run_temporal ? c.depth - 1 : c.depth - 2;   // the last block that ran
   if ((rc = launch_ln_bwd(e->dxnH, xl, fm + D, nmod, nullptr, e->dx, e->pl1, nullptr, nullptr, nmod, M, D, rps, dt, st, e->blk[il].y2,
                           e->mod + (size_t)il * 6 * D + 5 * D, nmod, e->dyD, pg2_of(e, il)))) return rc;
+  if (lora) return LATTE_OK;   // the finalize launch writes base gradients only
   StageFinArgs a{};
   a.mod_src[0] = a.mod_src[1] = e->pl1; a.mod_nsum[0] = a.mod_nsum[1] = 2; a.mod_which[0] = 0; a.mod_which[1] = 1;
   a.n_mod = 2; a.rows_per_sample = rps / (4 * train_rows_per_run(rps)); a.B = B; a.D = D;
@@ -713,8 +921,8 @@ static int backward_block(latte_trainer_t* e, int i, hipStream_t st) {
   // ---- MLP branch.  fuse_small: dy = g2 dx and the gate / bias partial rows were left by the LayerNorm backward that produced dx
   // (the previous stage's last pass); the partial rows wait for this stage's finalize launch
   if (!fs && (rc = launch_gate_bwd(e->dx, b.y2, mb + 5 * D, nmod, e->dyD, e->part_rows, dm + 5 * D, nmod, M, D, rps, dt, st))) return rc;
-  if ((rc = linear_bwd(e, e->dyD, b.h, b.fc2_wt, M, D, Hm, w.fc2_w, w.fc2_b, nullptr, nullptr, e->dhH, b.u, st))) return rc;
-  if ((rc = linear_bwd(e, e->dhH, b.xn2, b.fc1_wt, M, Hm, D, w.fc1_w, w.fc1_b, e->pc_fc1, &fc1_rows, e->dxnH, nullptr, st))) return rc;
+  if ((rc = linear_bwd(e, e->dyD, b.h, b.fc2_wt, M, D, Hm, w.fc2_w, w.fc2_b, i * 4 + 3, nullptr, nullptr, e->dhH, b.u, st))) return rc;
+  if ((rc = linear_bwd(e, e->dhH, b.xn2, b.fc1_wt, M, Hm, D, w.fc1_w, w.fc1_b, i * 4 + 2, e->pc_fc1, &fc1_rows, e->dxnH, nullptr, st))) return rc;
   // ---- attention branch.  fuse_small: its gate backward rides on LN2's backward
   if (fs) {
     if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i + 1], mb + 4 * D, nmod, e->dx, e->dx, e->pl2, nullptr, nullptr, nmod, M, D, rps, dt, st, b.y1,
@@ -724,22 +932,23 @@ static int backward_block(latte_trainer_t* e, int i, hipStream_t st) {
                             st))) return rc;
     if ((rc = launch_gate_bwd(e->dx, b.y1, mb + 2 * D, nmod, e->dyD, e->part_rows, dm + 2 * D, nmod, M, D, rps, dt, st))) return rc;
   }
-  if ((rc = linear_bwd(e, e->dyD, b.att, b.proj_wt, M, D, D, w.proj_w, w.proj_b, nullptr, nullptr, e->dxnH, nullptr, st))) return rc;   // d(attention output)
+  if ((rc = linear_bwd(e, e->dyD, b.att, b.proj_wt, M, D, D, w.proj_w, w.proj_b, i * 4 + 1, nullptr, nullptr, e->dxnH, nullptr, st))) return rc;   // d(attention output)
   AttnArgs sl{};
   seq_layout(sl, spatial, B, F, T);
   if ((rc = launch_attention_bwd(b.qkv, b.att, e->dxnH, e->dqkvH, e->attn_stats, sl.num_seq, sl.L, e->cfg.num_heads, e->hd, sl.U, rps,
                                  sl.seq_stride, sl.row_stride, dt, st))) return rc;
-  if ((rc = linear_bwd(e, e->dqkvH, b.xn1, b.qkv_wt, M, 3 * D, D, w.qkv_w, w.qkv_b, e->pc_qkv, &qkv_rows, e->dxnH, nullptr, st))) return rc;
+  if ((rc = linear_bwd(e, e->dqkvH, b.xn1, b.qkv_wt, M, 3 * D, D, w.qkv_w, w.qkv_b, i * 4 + 0, e->pc_qkv, &qkv_rows, e->dxnH, nullptr, st))) return rc;
   // ---- LN1's backward, and the stage's tail
   if (!fs) {
     if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i], mb + D, nmod, e->dx, e->dx, e->part_rows, dm, dm + D, nmod, M, D, rps, dt, st))) return rc;
-    return adaln_bwd(e, i, st);
+    return e->lora_rank ? LATTE_OK : adaln_bwd(e, i, st);
   }
   if (ip >= 0) {   // + the gate backward of the previous running block's MLP branch (the next stage's first step)
     if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i], mb + D, nmod, e->dx, e->dx, e->pl1, nullptr, nullptr, nmod, M, D, rps, dt, st, e->blk[ip].y2,
                             e->mod + (size_t)ip * 6 * D + 5 * D, nmod, e->dyD, pg2_of(e, ip)))) return rc;
   } else if ((rc = launch_ln_bwd(e->dxnH, e->xs[2 * i], mb + D, nmod, e->dx, e->dx, e->pl1, nullptr, nullptr, nmod, M, D, rps, dt, st)))
     return rc;
+  if (e->lora_rank) return LATTE_OK;   // modulation, adaLN and bias gradients: all of the frozen base
   // one launch: the six modulation gradients, the adaLN linear's bias / weight gradients, the four linears' bias gradients
   StageFinArgs a{};
   const float* msrc[6] = {e->pl1, e->pl1, e->pg1, e->pl2, e->pl2, pg2};
@@ -768,6 +977,7 @@ static int backward_embed(latte_trainer_t* e, hipStream_t st) {
   const int M = B * F * T;
   const int acc = e->grad_accumulate;
   const float* gs = acc_scale(e);
+  if (e->lora_rank) return LATTE_OK;   // the whole stage writes base gradients; e->dx stays for latte_trainer_input_grad
   if (e->fuse_small && e->KPE <= 32) {   // dW[k][j] = sum_m dx[m][k] pix[m][j], db[k] = sum_m dx[m][k]: one launch + reductions
     if ((rc = launch_im2col_patch(e->x_t, e->pix, B * F, e->G, c.patch_size, e->Cin, st))) return rc;
     if ((rc = launch_narrow_outer(e->pix, e->KPE, e->dx, 0, D, M, G(e, r.pe_w), 1, e->KPE, nullptr, G(e, r.pe_b), e->no_ws, dt, gs, st, acc)))
@@ -809,6 +1019,12 @@ int latte_trainer_num_stages(const latte_trainer_t* e) { return e ? e->cfg.depth
 int latte_trainer_stage_range(const latte_trainer_t* e, int stage, int64_t* offset, int64_t* numel) {
   if (!e || !offset || !numel || stage < 0 || stage > e->cfg.depth + 1) return fail(LATTE_ERR_INVALID, "stage_range: bad stage");
   const int depth = e->cfg.depth;
+  if (e->lora_rank) {   // the adapter buffers: a block stage finishes its block's adapters, the other two stages nothing
+    const int i = depth - stage;
+    *offset = stage == 0 ? e->ltotal : stage <= depth ? e->lo[i].begin : 0;
+    *numel = stage >= 1 && stage <= depth ? (i + 1 < depth ? e->lo[i + 1].begin : e->ltotal) - e->lo[i].begin : 0;
+    return LATTE_OK;
+  }
   if (stage == 0) { *offset = e->rp.fin_w; *numel = e->total - *offset; }
   else if (stage <= depth) {
     const int i = depth - stage;
@@ -827,10 +1043,15 @@ int latte_trainer_backward_stage(latte_trainer_t* e, int stage, void* stream) {
   else if (stage != e->next_stage || stage > e->cfg.depth + 1) rc = fail(LATTE_ERR_STATE, "backward_stage: stages run in order after latte_trainer_begin");
   else {
     e->next_stage = stage + 1;
-    rc = stage == 0 ? backward_final(e, st) : stage <= e->cfg.depth ? backward_block(e, e->cfg.depth - stage, st) : backward_embed(e, st);
+    try {
+      rc = stage == 0 ? backward_final(e, st) : stage <= e->cfg.depth ? backward_block(e, e->cfg.depth - stage, st) : backward_embed(e, st);
+    } catch (const FrozenBaseWrite&) {
+      rc = fail(LATTE_ERR_STATE, "backward_stage: a writer of a base gradient was reached, but no base gradient buffer is bound (LoRA)");
+    }
   }
   // (fuse_small: the block stages' slices were unscaled by the kernels that wrote them; accumulate mode: every slice was)
-  if (!rc && scaling_active(e) && !e->grad_accumulate && !(e->fuse_small && stage >= 1 && stage <= e->cfg.depth)) {   // the slice this stage finalised leaves the loss-scaled domain
+  // (LoRA: the adapter gradients' reductions unscale in every mode)
+  if (!rc && !e->lora_rank && scaling_active(e) && !e->grad_accumulate && !(e->fuse_small && stage >= 1 && stage <= e->cfg.depth)) {   // the slice this stage finalised leaves the loss-scaled domain
     int64_t off = 0, n = 0;
     if ((rc = latte_trainer_stage_range(e, stage, &off, &n))) return rc;
     rc = launch_scale_f32_dev(e->Gr + off, e->scaler, 1, (size_t)n, st);
@@ -953,9 +1174,12 @@ int latte_trainer_optimizer_step(latte_trainer_t* e, float lr, float beta1, floa
   e->custom = 0;   // the weights and perhaps the loss scale change: a forward awaiting its seed is abandoned, the input gradient's time is over
   hipStream_t st = (hipStream_t)stream;
   int rc;
-  if ((rc = launch_grad_norm(e->Gr, (size_t)e->total, e->sumsq, clip_max_norm, clip, e->stats, e->scaler, st))) return rc;
+  const bool lora = e->lora_rank != 0;   // the trained buffers: the adapters' (the base has no gradient, moments or EMA of its own)
+  float *p = lora ? e->LP : e->Pm, *g = lora ? e->LG : e->Gr, *m1 = lora ? e->LM1 : e->M1, *v2 = lora ? e->LV2 : e->V2, *ema = lora ? e->LEma : e->Ema;
+  const size_t n = (size_t)(lora ? e->ltotal : e->total);
+  if ((rc = launch_grad_norm(g, n, e->sumsq, clip_max_norm, clip, e->stats, e->scaler, st))) return rc;
   if (norm_out) LATTE_HIP(hipMemcpyAsync(norm_out, e->stats, sizeof(float) * 2, hipMemcpyDeviceToDevice, st));
-  if ((rc = launch_adamw_ema(e->Pm, e->Gr, e->M1, e->V2, e->Ema, (size_t)e->total, lr, beta1, beta2, eps, weight_decay, step, ema_decay,
+  if ((rc = launch_adamw_ema(p, g, m1, v2, ema, n, lr, beta1, beta2, eps, weight_decay, step, ema_decay,
                              e->stats, e->scaler + 2, st))) return rc;
   return latte_trainer_sync_weights(e, stream);
 }

@@ -12,6 +12,8 @@ buffers (the model's ``nn.Parameter``s become views of the parameter buffer, as 
 averages the gradient buffer across ranks with ONE RCCL all-reduce per step when ``torch.distributed`` is initialised
 (train.py:125 wraps the model in DDP; the engine itself never communicates).  There is no CPU / autograd fallback.
 """
+import math
+
 import torch
 
 from . import _lib
@@ -20,6 +22,19 @@ from .diffusion import SpacedDiffusion, _LOSS
 from .models import Latte
 
 FROZEN = ("pos_embed", "temp_embed")   # nn.Parameter(requires_grad=False), latte.py:246-247
+LORA_TARGETS = ("qkv", "proj", "fc1", "fc2")   # bit j of latte_trainer_lora_enable's target_mask
+LORA_RANKS = (4, 8, 16, 32)   # rank 64 is refused: measured slower than the full step at Latte-B/2 (DESIGN.md 4.4 "LoRA")
+
+
+def lora_target_mask(targets):
+    """("qkv", "fc2") -> the engine's target mask; a string "qkv,fc2" is accepted as the configs write it."""
+    if isinstance(targets, str):
+        targets = [t.strip() for t in targets.split(",") if t.strip()]
+    targets = tuple(targets)
+    bad = [t for t in targets if t not in LORA_TARGETS]
+    if bad or not targets:
+        raise LatteError(f"lora_targets must be a non-empty subset of {LORA_TARGETS}, got {list(targets)}")
+    return sum(1 << LORA_TARGETS.index(t) for t in set(targets))
 
 
 def _world(group=None):
@@ -40,6 +55,22 @@ def average_gradients(flat_grads, group=None, async_op=False):
     dist.all_reduce(flat_grads, op=dist.ReduceOp.SUM, group=group)
     flat_grads.div_(world)
     return flat_grads
+
+
+def merge_lora_state_dict(sd, lora_sd, config):
+    """A checkpoint's state dict with the adapters of ``lora_state_dict()`` folded in: W + (lora_alpha / lora_rank) B A in torch fp32
+    for every ``<linear>.lora_A`` / ``.lora_B`` pair (``config``: ``lora_config()``).  For tools that have no trainer at hand
+    (tools/sample.py --lora); ``LatteTrainer.merge_lora`` is the engine's own merge, whose fp32 sum may differ in the last bit."""
+    s = float(config["lora_alpha"]) / int(config["lora_rank"])
+    out = dict(sd)
+    for k, a in lora_sd.items():
+        if not k.endswith(".lora_A"):
+            continue
+        w, b = k[:-len(".lora_A")] + ".weight", lora_sd[k[:-1] + "B"]
+        if w not in sd or tuple(sd[w].shape) != (b.shape[0], a.shape[1]):
+            raise LatteError(f"merge_lora_state_dict: {k} does not fit {w}")
+        out[w] = (sd[w].float() + s * (b.float().to(sd[w].device) @ a.float().to(sd[w].device))).to(sd[w].dtype)
+    return out
 
 
 class _EngineDenoiser(torch.autograd.Function):
@@ -95,11 +126,18 @@ class LatteTrainer:
     micro-batch is ONE micro-batch of an accumulation window.  N <= num_frames; with N = 0 nothing changes.
     Custom losses: ``forward(x_t, t, y)`` returns the model output as a node of the torch autograd graph -- any torch loss of it calls
     ``backward()``, which seeds the engine's backward and fills ``x_t.grad`` -- and ``train_step(..., loss_fn=f)`` runs a whole step
-    on ``f(model_out, x_start=, x_t=, t=, noise=) -> [B]``; diffusions with ``use_kl`` / ``predict_xstart`` train only that way."""
+    on ``f(model_out, x_start=, x_t=, t=, noise=) -> [B]``; diffusions with ``use_kl`` / ``predict_xstart`` train only that way.
+    lora_rank = r > 0: LoRA fine-tuning (DESIGN.md 4.4 "LoRA").  The model's parameters are frozen; every targeted block linear
+    (``lora_targets``, default all of qkv / proj / fc1 / fc2) runs with ``W + (lora_alpha / r) B A`` and only ``A [r, K]`` (kaiming-uniform,
+    a = sqrt(5)) and ``B [N, r]`` (zero) train -- r in 4, 8, 16, 32; ``lora_alpha`` defaults to r.  No gradient, moment or EMA buffer of
+    the base is allocated: ``grads`` / ``exp_avg`` / ``exp_avg_sq`` / ``ema`` are None and ``lora_params`` / ``lora_grads`` / ... take their
+    place in every method (``lora_state_dict()`` is the small file to ship, ``merge_lora()`` turns the model into an ordinary
+    checkpoint).  With lora_rank = 0 nothing changes and nothing is allocated."""
 
     def __init__(self, model, diffusion, max_batch, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_max_norm=0.1,
                  start_clip_iter=20000, ema_decay=0.9999, class_dropout_prob=0.1, compute_dtype="f16", process_group=None,
-                 loss_scale=None, dynamic_loss_scale=None, gradient_accumulation_steps=1, use_image_num=0):
+                 loss_scale=None, dynamic_loss_scale=None, gradient_accumulation_steps=1, use_image_num=0, lora_rank=0, lora_alpha=None,
+                 lora_targets=LORA_TARGETS):
         if not isinstance(model, Latte):
             raise LatteError("LatteTrainer needs a latte_amd.Latte model")
         if not isinstance(diffusion, SpacedDiffusion):
@@ -111,6 +149,14 @@ class LatteTrainer:
         _lib.require_gpu()
         self.model, self.diffusion = model, diffusion
         self.max_batch = int(max_batch)
+        self.lora_rank = int(lora_rank)
+        self.lora_alpha = float(lora_alpha) if lora_alpha is not None else float(self.lora_rank)
+        self.lora_targets = tuple(t for t in LORA_TARGETS if self.lora_rank and lora_target_mask(lora_targets) >> LORA_TARGETS.index(t) & 1)
+        self.lora_merged = False
+        if self.lora_rank and self.lora_rank not in LORA_RANKS:
+            raise LatteError(f"lora_rank must be 0 or one of {LORA_RANKS}, got {self.lora_rank}")
+        if self.lora_rank and not (self.lora_alpha > 0 and math.isfinite(self.lora_alpha)):
+            raise LatteError("lora_alpha must be positive and finite")
         self.use_image_num = int(use_image_num)
         if self.use_image_num < 0:
             raise LatteError("use_image_num must be >= 0")
@@ -145,6 +191,8 @@ class LatteTrainer:
             else:
                 check(lib.latte_trainer_create(cfg, self.max_batch, h))
         self._h = h
+        if self.lora_rank:
+            check(lib.latte_trainer_lora_enable(h, self.lora_rank, self.lora_alpha, lora_target_mask(self.lora_targets)))
         if loss_scale is not None:
             check(lib.latte_trainer_set_option(h, b"loss_scale", float(loss_scale)))
         if dynamic_loss_scale is not None:
@@ -161,18 +209,42 @@ class LatteTrainer:
         if [k for k, _, _ in self.layout] != want:
             raise LatteError("parameter order of the engine and of the model differ")
         self.params = torch.zeros(total, device=dev)
-        self.grads = torch.zeros(total, device=dev)
-        self.exp_avg = torch.zeros(total, device=dev)
-        self.exp_avg_sq = torch.zeros(total, device=dev)
-        self.ema = torch.zeros(total, device=dev)
+        lora = bool(self.lora_rank)
+        self.grads = None if lora else torch.zeros(total, device=dev)
+        self.exp_avg = None if lora else torch.zeros(total, device=dev)
+        self.exp_avg_sq = None if lora else torch.zeros(total, device=dev)
+        self.ema = None if lora else torch.zeros(total, device=dev)
         with torch.no_grad():
             for k, off, numel in self.layout:
                 p = named[k]
                 self.params[off:off + numel].copy_(p.detach().reshape(-1).float())
                 p.data = self.params[off:off + numel].view(p.shape)          # the module's parameters are views of the flat buffer
-            self.ema.copy_(self.params)                                        # update_ema(ema, model, decay=0), train.py:165
+            if not lora:
+                self.ema.copy_(self.params)                                    # update_ema(ema, model, decay=0), train.py:165
+        if lora:
+            self._linear_shapes = {k[:-len(".weight")]: tuple(p.shape) for k, p in named.items() if k.endswith(".weight") and p.dim() == 2}
+            n = lib.latte_trainer_lora_num_params(h)
+            self.lora_layout = [(lib.latte_trainer_lora_param_key(h, i).decode(), int(lib.latte_trainer_lora_param_offset(h, i)),
+                                 int(lib.latte_trainer_lora_param_numel(h, i))) for i in range(n)]
+            ltotal = int(lib.latte_trainer_lora_total_numel(h))
+            self.lora_params = torch.zeros(ltotal, device=dev)
+            self.lora_grads = torch.zeros(ltotal, device=dev)
+            self.lora_exp_avg = torch.zeros(ltotal, device=dev)
+            self.lora_exp_avg_sq = torch.zeros(ltotal, device=dev)
+            self.lora_ema = torch.zeros(ltotal, device=dev)
+            with torch.no_grad():
+                for k, off, numel in self.lora_layout:
+                    if k.endswith(".lora_A"):                                 # nn.Linear's own init, as peft's LoRA layers; B stays 0
+                        a = torch.empty(self.lora_shape(k))
+                        torch.nn.init.kaiming_uniform_(a, a=math.sqrt(5))
+                        self.lora_params[off:off + numel].copy_(a.reshape(-1))
+                self.lora_ema.copy_(self.lora_params)
         with torch.cuda.device(dev):
-            check(lib.latte_trainer_bind(h, ptr(self.params), ptr(self.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(self.ema)))
+            if lora:
+                check(lib.latte_trainer_bind_lora(h, ptr(self.params), ptr(self.lora_params), ptr(self.lora_grads), ptr(self.lora_exp_avg),
+                                                  ptr(self.lora_exp_avg_sq), ptr(self.lora_ema)))
+            else:
+                check(lib.latte_trainer_bind(h, ptr(self.params), ptr(self.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(self.ema)))
             check(lib.latte_trainer_set_frozen(h, ptr(named["pos_embed"].detach().float().contiguous()),
                                                ptr(named["temp_embed"].detach().float().contiguous()), 1, stream_ptr()))
             check(lib.latte_trainer_sync_weights(h, stream_ptr()))
@@ -199,8 +271,79 @@ class LatteTrainer:
     # ------------------------------------------------------------------ views
     def grad_dict(self):
         """{reference key: gradient view} of the last forward_backward."""
+        if self.lora_rank:
+            raise LatteError("a LoRA trainer has no base gradients: lora_grad_dict()")
         named = dict(self.model.named_parameters())
         return {k: self.grads[off:off + numel].view(named[k].shape) for k, off, numel in self.layout}
+
+    # ------------------------------------------------------------------ LoRA
+    def lora_shape(self, key):
+        """Shape of adapter ``key``: lora_A [r, in_features], lora_B [out_features, r] of the linear it belongs to."""
+        n, k = self._linear_shapes[key.rsplit(".", 1)[0]]
+        return (self.lora_rank, k) if key.endswith(".lora_A") else (n, self.lora_rank)
+
+    def _need_lora(self):
+        if not self.lora_rank:
+            raise LatteError("this trainer was built without LoRA (lora_rank=0)")
+
+    def _lora_keyed(self, flat):
+        return {k: flat[off:off + numel].view(self.lora_shape(k)).clone() for k, off, numel in self.lora_layout}
+
+    def lora_state_dict(self):
+        """{``blocks.{i}.attn.qkv.lora_A``: [r, K], ``....lora_B``: [N, r], ...} of the targeted linears: the file a fine-tune ships
+        (with ``lora_config()`` beside it)."""
+        self._need_lora()
+        return self._lora_keyed(self.lora_params)
+
+    def ema_lora_state_dict(self):
+        self._need_lora()
+        return self._lora_keyed(self.lora_ema)
+
+    def lora_grad_dict(self):
+        """{adapter key: gradient view} of the last backward."""
+        self._need_lora()
+        return {k: self.lora_grads[off:off + numel].view(self.lora_shape(k)) for k, off, numel in self.lora_layout}
+
+    def lora_config(self):
+        return {"lora_rank": self.lora_rank, "lora_alpha": self.lora_alpha, "lora_targets": list(self.lora_targets)}
+
+    def load_lora_state_dict(self, sd, ema_sd=None):
+        """Adapters (and their EMA: ``ema_sd``, default the adapters themselves) back into the flat buffers; the merged operand copies
+        are re-packed."""
+        self._need_lora()
+        self._not_merged()
+        missing = [k for k, _, _ in self.lora_layout if k not in sd]
+        extra = [k for k in sd if k not in {k for k, _, _ in self.lora_layout}]
+        if missing or extra:
+            raise LatteError(f"load_lora_state_dict: missing keys {missing[:4]}, unexpected keys {extra[:4]} (rank / targets differ?)")
+        with torch.no_grad():
+            for k, off, numel in self.lora_layout:
+                for src, dst in ((sd, self.lora_params), (ema_sd or sd, self.lora_ema)):
+                    if tuple(src[k].shape) != self.lora_shape(k):
+                        raise LatteError(f"load_lora_state_dict: {k} is {list(src[k].shape)}, expected {list(self.lora_shape(k))}")
+                    dst[off:off + numel].copy_(src[k].reshape(-1).float())
+        with torch.cuda.device(self.device):
+            check(load_library().latte_trainer_sync_weights(self._h, stream_ptr()))
+
+    def _not_merged(self):
+        if self.lora_merged:
+            raise LatteError("merge_lora() folded the adapters into the model: this trainer is finished, build a new one to go on")
+
+    def merge_lora(self, ema=False):
+        """Writes ``W + (alpha / r) B A`` (``ema``: of the EMA adapters) into the model's parameters through the engine's merge entry --
+        the pack's fp32 arithmetic, so a plain trainer or the sampling engine on the merged model runs the operands this trainer ran.
+        ``model.state_dict()`` is an ordinary checkpoint afterwards; this trainer is finished (its base now holds the adapters)."""
+        self._need_lora()
+        self._not_merged()
+        if self.micro_step:
+            raise LatteError("merge_lora inside an accumulation window")
+        self._live = None
+        with torch.cuda.device(self.device):
+            check(load_library().latte_trainer_lora_merge(self._h, ptr(self.lora_ema) if ema else None, ptr(self.params), stream_ptr()))
+        self.lora_merged = True
+        if hasattr(self.model, "mark_weights_dirty"):
+            self.model.mark_weights_dirty()
+        return self.model
 
     def model_state_dict(self):
         """The ``"model"`` entry of train.py's checkpoints (:257-262), built from the flat fp32 master buffer through the layout --
@@ -220,15 +363,18 @@ class LatteTrainer:
     def ema_state_dict(self):
         """The ``"ema"`` entry of train.py's checkpoints (:257-262): every key of model.state_dict()."""
         sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        ema = self.params if self.lora_rank else self.ema                       # LoRA: the base is frozen, its average is itself
         for k, off, numel in self.layout:
-            sd[k] = self.ema[off:off + numel].view(sd[k].shape).clone()
+            sd[k] = ema[off:off + numel].view(sd[k].shape).clone()
         return sd
 
     def load_state_dict(self, sd, ema_sd=None):
+        self._not_merged()
         with torch.no_grad():
             for k, off, numel in self.layout:
                 self.params[off:off + numel].copy_(sd[k].reshape(-1).float())
-                self.ema[off:off + numel].copy_((ema_sd or sd)[k].reshape(-1).float())
+                if not self.lora_rank:
+                    self.ema[off:off + numel].copy_((ema_sd or sd)[k].reshape(-1).float())
         with torch.cuda.device(self.device):
             check(load_library().latte_trainer_sync_weights(self._h, stream_ptr()))
 
@@ -259,6 +405,7 @@ class LatteTrainer:
         -> dict(loss, mse, vb [, model_out])."""
         self._reduced = False
         self._live = None                                                          # a custom ``forward`` awaiting its backward is abandoned
+        self._not_merged()
         d = self.diffusion
         self._builtin_loss_check()
         x0 = x_start.to(device=self.device, dtype=torch.float32).contiguous()
@@ -315,6 +462,12 @@ class LatteTrainer:
         the next stages run (no-op without a process group) and ``self.grads`` leaves here averaged."""
         lib = load_library()
         handles = []
+        if self.lora_rank:        # megabytes of adapter gradients: one collective behind the last stage (all_reduce_gradients)
+            for k in range(lib.latte_trainer_num_stages(self._h)):
+                check(lib.latte_trainer_backward_stage(self._h, k, stream_ptr()))
+            if reduce:
+                self.all_reduce_gradients()
+            return
         for k in range(lib.latte_trainer_num_stages(self._h)):
             check(lib.latte_trainer_backward_stage(self._h, k, stream_ptr()))
             if not reduce:
@@ -359,6 +512,7 @@ class LatteTrainer:
         is orders of magnitude away from the built-in one's."""
         if self.micro_step >= self.gradient_accumulation_steps:
             raise LatteError("the accumulation window is complete: optimizer_step() is due")
+        self._not_merged()
         Fr, C, H = self.model.num_frames, self.model.in_channels, self.model.input_size
         if not torch.is_tensor(x) or x.dim() != 5 or tuple(x.shape[1:]) != (Fr, C, H, H):
             raise LatteError(f"forward: x must be [batch, {Fr}, {C}, {H}, {H}], got {list(getattr(x, 'shape', []))}"
@@ -419,7 +573,7 @@ class LatteTrainer:
         """DDP's gradient averaging (train.py:125) as ONE collective over the flat gradient buffer: RCCL over xGMI when the
         process group's backend is nccl, gloo in the CPU tests."""
         if not getattr(self, "_reduced", False):
-            average_gradients(self.grads, self.process_group)
+            average_gradients(self.lora_grads if self.lora_rank else self.grads, self.process_group)
             self._reduced = True
 
     def _set_accumulate(self, on):
@@ -469,6 +623,7 @@ class LatteTrainer:
 
     def optimizer_step(self):
         """clip_grad_norm_ + AdamW + update_ema; -> gradient norm (0-d tensor, device).  Ends the accumulation window."""
+        self._not_merged()
         self.micro_step = 0
         self._set_accumulate(False)     # a plain forward_backward assigns again
         self.train_steps += 1
@@ -506,6 +661,16 @@ class LatteTrainer:
         """Everything a run continues from: ``model`` / ``ema`` (the reference's checkpoint entries, train.py:257-262), ``opt``
         (AdamW's ``exp_avg`` / ``exp_avg_sq``, state-dict keyed), ``scaler`` (the eight counters), ``train_steps``, ``micro_step``
         and, inside a window (``micro_step != 0``), the partial gradient buffer ``grads``."""
+        if self.lora_rank:
+            # the frozen base once (its EMA is itself, it has no moments), then everything of the adapters
+            st = {"model": self.model_state_dict(),
+                  "lora": {"config": self.lora_config(), "params": self.lora_state_dict(), "ema": self.ema_lora_state_dict(),
+                           "exp_avg": self._lora_keyed(self.lora_exp_avg), "exp_avg_sq": self._lora_keyed(self.lora_exp_avg_sq)},
+                  "scaler": self.scaler_state(), "train_steps": int(self.train_steps), "micro_step": int(self.micro_step),
+                  "gradient_accumulation_steps": int(self.gradient_accumulation_steps)}
+            if self.micro_step:
+                st["lora"]["grads"] = self._lora_keyed(self.lora_grads)
+            return st
         st = {"model": self.model_state_dict(), "ema": self.ema_state_dict(),
               "opt": {"exp_avg": self._keyed(self.exp_avg), "exp_avg_sq": self._keyed(self.exp_avg_sq)},
               "scaler": self.scaler_state(), "train_steps": int(self.train_steps), "micro_step": int(self.micro_step),
@@ -519,6 +684,30 @@ class LatteTrainer:
         micro = int(state.get("micro_step", 0))
         if micro and int(state.get("gradient_accumulation_steps", self.gradient_accumulation_steps)) != self.gradient_accumulation_steps:
             raise LatteError("the state was saved inside an accumulation window of another gradient_accumulation_steps")
+        if bool(self.lora_rank) != ("lora" in state):
+            raise LatteError("the state and the trainer disagree on LoRA")
+        if self.lora_rank:
+            lo = state["lora"]
+            if lo["config"] != self.lora_config():
+                raise LatteError(f"the state's adapters are {lo['config']}, the trainer's {self.lora_config()}")
+            if micro and "grads" not in lo:
+                raise LatteError("the state was saved inside an accumulation window but holds no gradients")
+            with torch.no_grad():
+                for k, off, numel in self.lora_layout:
+                    self.lora_exp_avg[off:off + numel].copy_(lo["exp_avg"][k].reshape(-1).float())
+                    self.lora_exp_avg_sq[off:off + numel].copy_(lo["exp_avg_sq"][k].reshape(-1).float())
+                    if micro:
+                        self.lora_grads[off:off + numel].copy_(lo["grads"][k].reshape(-1).float())
+                if not micro:
+                    self.lora_grads.zero_()
+                for k, off, numel in self.layout:
+                    self.params[off:off + numel].copy_(state["model"][k].reshape(-1).float())
+            self.load_lora_state_dict(lo["params"], lo["ema"])           # (syncs the merged operand copies)
+            self.set_scaler_state(state["scaler"])
+            self.train_steps, self.micro_step = int(state["train_steps"]), micro
+            if hasattr(self.model, "mark_weights_dirty"):
+                self.model.mark_weights_dirty()
+            return
         if micro and "grads" not in state:
             raise LatteError("the state was saved inside an accumulation window but holds no gradients")
         with torch.no_grad():

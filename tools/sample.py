@@ -33,7 +33,12 @@ def main(args, cli):
     args.max_batch = 2 if using_cfg else 1
     model = get_models(args).to(device)                                    # :56
     if args.get("ckpt"):
-        model.load_state_dict(find_model(args.ckpt))                       # :62-64
+        sd = find_model(args.ckpt)                                         # :62-64
+        if cli.lora:                                                       # adapters of tools/train.py's <step>.lora.pt, merged first
+            from latte_amd.training import merge_lora_state_dict
+            f = torch.load(cli.lora, map_location="cpu")
+            sd = merge_lora_state_dict(sd, f["lora_ema"] if cli.lora_ema else f["lora"], f["config"])
+        model.load_state_dict(sd)
     else:
         g = torch.Generator("cpu").manual_seed(1)
         for _, p in model.named_parameters():
@@ -94,6 +99,8 @@ if __name__ == "__main__":
     parser.add_argument("--save_video_path", type=str, default="")
     parser.add_argument("--vae", type=str, default="")
     parser.add_argument("--steps", type=int, default=0)
+    parser.add_argument("--lora", type=str, default="", help="<step>.lora.pt of a LoRA fine-tune of --ckpt: merged into it before sampling, in torch fp32 -- the merged weights may differ from LatteTrainer.merge_lora()'s in the last fp32 bit, so the sampled operands are not guaranteed to be the trainer's bit for bit")
+    parser.add_argument("--lora_ema", action="store_true", help="merge the adapters' EMA instead of the adapters")
     cli = parser.parse_args()
     conf = latte_amd.load_config(cli.config)                               # :136
     if cli.ckpt:

@@ -30,6 +30,11 @@ from the micro-batch's seeded generator (a resumed run redraws the same ones); w
 `loss_fn: "package.module:function"` replaces the built-in loss by a torch one (`LatteTrainer.train_step(loss_fn=...)`:
 `function(model_out, x_start=, x_t=, t=, noise=) -> per-sample loss [B]`, differentiated through `LatteTrainer.forward`); video
 micro-batches only (not with `use_image_num`).
+LoRA fine-tuning (`lora_rank: r` with `pretrained:`; `lora_alpha`, default r; `lora_targets`, default "qkv,proj,fc1,fc2"): the checkpoint
+named by `pretrained:` stays frozen and rank-r adapters on the targeted block linears train (LatteTrainer(lora_rank=...)).  A
+checkpoint then is `<step>.lora.pt` = {"config", "lora", "lora_ema"} -- megabytes; the base is not written again -- with the same
+`<step>.state.pt` / `<step>.rng<rank>.pt` beside it, and `resume_from_checkpoint: True` continues from the highest-numbered one bit for
+bit.  `tools/sample.py --ckpt <pretrained> --lora <step>.lora.pt` samples the fine-tune.
 """
 import argparse
 import glob
@@ -47,6 +52,14 @@ import latte_amd  # noqa: E402
 from latte_amd import parallel  # noqa: E402
 from latte_amd.train_util import (checkpoint_step, data_seed, draw_image_frames, latest_checkpoint, latte_preset_name,  # noqa: E402
                                   resolve_loss_fn, rng_state, scheduled_lr, set_rng_state, state_path)
+
+
+def latest_lora_checkpoint(ckpt_dir):
+    """The numerically highest <step>.lora.pt under ``ckpt_dir``, or None."""
+    import re
+    found = [(int(m.group(1)), f) for f in (os.listdir(ckpt_dir) if os.path.isdir(ckpt_dir) else [])
+             for m in [re.fullmatch(r"(\d+)\.lora\.pt", f)] if m]
+    return os.path.join(ckpt_dir, max(found)[1]) if found else None
 
 
 def clip_label(path):
@@ -186,9 +199,19 @@ def main():
         own = model.state_dict()
         model.load_state_dict({**own, **{k: v for k, v in sd.items() if k in own}})          # train.py:109-122
     diffusion = latte_amd.create_diffusion(timestep_respacing="")                                # train.py:92
+    lora_rank = int(args.get("lora_rank") or 0)
+    lora_kw = {}
+    if lora_rank:
+        if not args.get("pretrained"):
+            raise SystemExit("lora_rank: LoRA fine-tunes a checkpoint -- set pretrained:")
+        lora_kw = dict(lora_rank=lora_rank, lora_alpha=float(args.get("lora_alpha") or lora_rank),
+                       lora_targets=args.get("lora_targets") or latte_amd.training.LORA_TARGETS)
     trainer = latte_amd.LatteTrainer(model, diffusion, max_batch=nb, lr=float(args.learning_rate), clip_max_norm=float(args.clip_max_norm),
                                      start_clip_iter=int(args.start_clip_iter), gradient_accumulation_steps=accum,
-                                     use_image_num=use_image_num)
+                                     use_image_num=use_image_num, **lora_kw)
+    if lora_rank and rank == 0:
+        print(f"LoRA: rank {lora_rank}, alpha {trainer.lora_alpha:g}, targets {','.join(trainer.lora_targets)}; "
+              f"{trainer.lora_params.numel():,} trained parameters, the base is frozen", flush=True)
     # Replicas were initialised from the shared seed; from here every rank draws its own timesteps, noise and label-dropout
     # masks, as the reference does (train.py:62 `seed = args.global_seed + rank`): a global batch covers world * nb independent
     # draws, not nb draws replicated world times.
@@ -213,8 +236,23 @@ def main():
     if args.get("resume_from_checkpoint"):
         # train.py:176-192: the highest-numbered checkpoint of THIS run's results_dir -- with the state file beside it the whole run
         # comes back: parameters, EMA, AdamW moments, bias-correction count, loss scale and its growth count, step, random streams
-        ck = latest_checkpoint(os.path.join(out_dir, "checkpoints"))
-        if ck is None:
+        ck = (latest_lora_checkpoint if lora_rank else latest_checkpoint)(os.path.join(out_dir, "checkpoints"))
+        if ck is not None and lora_rank:
+            # the adapters, their EMA and (state file) their moments and the counters; the frozen base came from `pretrained:`
+            sp = state_path(ck[:-len(".lora.pt")] + ".pt")
+            if not os.path.isfile(sp):
+                raise SystemExit(f"resume_from_checkpoint: {ck} has no {os.path.basename(sp)} beside it")
+            ad, rest = torch.load(ck, map_location="cpu"), torch.load(sp, map_location="cpu")
+            trainer.load_training_state({**{k: v for k, v in rest.items() if k not in ("rng", "lora_opt")}, "model": trainer.model_state_dict(),
+                                         "lora": {"config": ad["config"], "params": ad["lora"], "ema": ad["lora_ema"], **rest["lora_opt"]}})
+            first_step = int(rest["train_steps"])
+            rp = state_path(ck[:-len(".lora.pt")] + ".pt", rank)
+            mine = rest if rank == 0 else (torch.load(rp, map_location="cpu") if os.path.isfile(rp) else None)
+            if mine is not None:
+                set_rng_state(mine["rng"], device)
+            if rank == 0:
+                print(f"Resumed from {ck}: step {first_step}", flush=True)
+        elif ck is None:
             if rank == 0:
                 print(f"resume_from_checkpoint: no checkpoint under {out_dir}/checkpoints yet, starting a new run", flush=True)
         else:
@@ -316,7 +354,16 @@ def main():
             # every rank its random state, rank 0 also the AdamW moments and the counters
             path = os.path.join(out_dir, "checkpoints", f"{step:07d}.pt")
             mine = {"rng": rng_state(device), "train_steps": step}
-            if rank == 0:
+            if rank == 0 and lora_rank:
+                st = trainer.training_state()
+                lo_ = st["lora"]
+                cpu = lambda d: {k: v.cpu() for k, v in d.items()}
+                lpath = path[:-len(".pt")] + ".lora.pt"
+                torch.save({"config": lo_["config"], "lora": cpu(lo_["params"]), "lora_ema": cpu(lo_["ema"])}, lpath)
+                print(f"Saved checkpoint to {lpath}", flush=True)
+                mine.update({k: v for k, v in st.items() if k not in ("model", "lora")})
+                mine["lora_opt"] = {m: cpu(lo_[m]) for m in ("exp_avg", "exp_avg_sq")}
+            elif rank == 0:
                 st = trainer.training_state()
                 torch.save({"model": {k: v.cpu() for k, v in st["model"].items()}, "ema": {k: v.cpu() for k, v in st["ema"].items()}}, path)
                 print(f"Saved checkpoint to {path}", flush=True)

@@ -5,7 +5,11 @@ optimiser step make a window; LATTE_TRAIN_STEPS counts windows).
 LATTE_TRAIN_CUSTOM=1: the cost of the custom-loss path instead -- three arms in one process, interleaved, LATTE_TRAIN_RUNS (5) runs of
 LATTE_TRAIN_STEPS steps each: the built-in step, train_step(loss_fn=) with the built-in loss (MSE + variational bound) written in
 torch, and the same through LatteTrainer.forward with x_t.requires_grad (the input gradient on top).  Prints the medians, each
-arm's spread and the ratios against the built-in step of the same process."""
+arm's spread and the ratios against the built-in step of the same process.
+--lora-rank R (or LATTE_TRAIN_LORA_RANK=R): the LoRA step (LatteTrainer(lora_rank=R), all four targets) instead of the full one.
+LATTE_TRAIN_LORA_AB=16,32: the full step against the LoRA step at those ranks -- one trainer per arm in one process, interleaved,
+LATTE_TRAIN_RUNS (5) runs of LATTE_TRAIN_STEPS steps each; prints the medians, each arm's spread, the speed-ups, the adapter file size
+and the device memory each trainer took."""
 import sys, os, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -16,19 +20,69 @@ B = int(os.environ.get("LATTE_TRAIN_BATCH", "5"))
 steps = int(os.environ.get("LATTE_TRAIN_STEPS", "10"))
 dtype = os.environ.get("LATTE_TRAIN_DTYPE", "f16")
 accum = int(os.environ.get("LATTE_TRAIN_ACCUM", "1"))
-model = latte_amd.Latte_models[name](input_size=32, num_frames=16, extras=1, max_batch=B).to("cuda")
-with torch.no_grad():
-    for p in model.parameters():
-        if p.requires_grad and float(p.abs().max()) == 0.0:
-            p.normal_(0, 0.02)
+lora_rank = int(os.environ.get("LATTE_TRAIN_LORA_RANK", "0"))
+if "--lora-rank" in sys.argv:
+    lora_rank = int(sys.argv[sys.argv.index("--lora-rank") + 1])
+
+
+def make_trainer(rank=0, **kw):
+    model = latte_amd.Latte_models[name](input_size=32, num_frames=16, extras=1, max_batch=B).to("cuda")
+    with torch.no_grad():
+        gen = torch.Generator("cuda").manual_seed(1)
+        for p in model.parameters():
+            if p.requires_grad and float(p.abs().max()) == 0.0:
+                p.normal_(0, 0.02, generator=gen)
+    if rank:
+        kw["lora_rank"] = rank
+    return model, latte_amd.LatteTrainer(model, latte_amd.create_diffusion(""), max_batch=B, compute_dtype=dtype, **kw)
+
+
+def lora_ab(ranks):
+    import statistics
+    runs = int(os.environ.get("LATTE_TRAIN_RUNS", "5"))
+    arms, mem = {}, {}
+    for key, r in [("full", 0)] + [(f"lora{r}", r) for r in ranks]:
+        torch.cuda.synchronize()
+        before = torch.cuda.memory_allocated()
+        free0 = torch.cuda.mem_get_info()[0]
+        arms[key] = make_trainer(r)[1]
+        torch.cuda.synchronize()
+        # torch's buffers (parameters, gradients, moments, EMA / adapters) and everything the engine allocated itself
+        mem[key] = {"torch_mb": round((torch.cuda.memory_allocated() - before) / 2 ** 20, 1),
+                    "device_mb": round((free0 - torch.cuda.mem_get_info()[0]) / 2 ** 20, 1)}
+    for tr_ in arms.values():
+        for _ in range(3):
+            tr_.train_step(x)
+    ms = {k: [] for k in arms}
+    for _ in range(runs):
+        for k, tr_ in arms.items():
+            torch.cuda.synchronize()
+            t0 = time.time()
+            for _ in range(steps):
+                out_ = tr_.train_step(x)
+            torch.cuda.synchronize()
+            ms[k].append((time.time() - t0) / steps * 1e3)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    print(json.dumps({"model": name, "operands": dtype, "local_batch": B, "steps_per_run": steps, "runs": runs,
+                      "ms_per_step": {k: round(v, 3) for k, v in med.items()},
+                      "ms_per_step_runs": {k: [round(x_, 3) for x_ in v] for k, v in ms.items()},
+                      "spread": {k: round((max(v) - min(v)) / med[k], 4) for k, v in ms.items()},
+                      "speedup": {k: round(med["full"] / med[k], 4) for k in med if k != "full"},
+                      "adapter_file_mb": {k: round(arms[k].lora_params.numel() * 4 / 2 ** 20, 2) for k in arms if k != "full"},
+                      "memory": mem}))
+
+
 kw = {"gradient_accumulation_steps": accum} if accum != 1 else {}
-tr = latte_amd.LatteTrainer(model, latte_amd.create_diffusion(""), max_batch=B, compute_dtype=dtype, **kw)
+g = torch.Generator("cpu").manual_seed(0)
+x = torch.randn(B, 16, 4, 32, 32, generator=g).cuda()
+if os.environ.get("LATTE_TRAIN_LORA_AB"):
+    lora_ab([int(r) for r in os.environ["LATTE_TRAIN_LORA_AB"].split(",")])
+    sys.exit(0)
+model, tr = make_trainer(lora_rank, **kw)
 for kv in os.environ.get("LATTE_TRAIN_OPTIONS", "").split(","):   # e.g. LATTE_TRAIN_OPTIONS=fuse_gelu=0
     if kv:
         k, v = kv.split("=")
         tr.set_option(k, float(v))
-g = torch.Generator("cpu").manual_seed(0)
-x = torch.randn(B, 16, 4, 32, 32, generator=g).cuda()
 
 
 def custom_arms():
@@ -119,6 +173,6 @@ M = B * 16 * 256
 lin = depth * 2.0 * M * (4 * D * D + 2 * D * Hm)
 attn = (depth // 2) * (4.0 * B * 16 * 256 * 256 * D + 4.0 * B * 256 * 16 * 16 * D)
 fwd = lin + attn
-print(json.dumps({"model": name, "operands": dtype, "local_batch": B, "accum": accum, "ms_per_step": round(dt * 1e3, 3), "samples_per_s": round(B / dt, 2),
+print(json.dumps({"model": name, "operands": dtype, "local_batch": B, "accum": accum, "lora_rank": lora_rank, "ms_per_step": round(dt * 1e3, 3), "samples_per_s": round(B / dt, 2),
                   "algorithmic_tflops": round(3 * fwd / dt / 1e12, 1), "forward_gflop": round(fwd / 1e9, 1),
                   "loss": float(out["loss"].mean()), "grad_norm": float(out["grad_norm"])}))
