@@ -89,6 +89,11 @@ void latte_engine_destroy(latte_engine_t* e);
  * CUs, and which the 128x144 tile does not take, runs as 2..4 partial products + one reduction into the residual stream; 1 = never; 2..4 = force that many),
  * "gated_rmw_shape" (how the rolling 12-wave kernel requests the fp32 residual of a gated GEMM: 0 = one 16 x 16 accumulator
  * fragment, 16 rows x 64 B, per instruction; 1 = the default: the whole 128-byte line of a wave's span as 8 rows x 128 B; same bits),
+ * "stream_policy" (bit mask, default 3: which once-used streams of a block are issued with the `nt` cache-policy hint so that they do not
+ * displace the fp32 residual from the Infinity Cache -- bit 0 = fc1's hidden-activation stores, bit 1 = fc2's activation operand, bit 2 = the
+ * fused attention kernel's output stores, bit 3 = the out-projection's activation operand; the large-batch kernels of unguided calls only,
+ * every other kernel ignores it; the library's default applies only where the hidden activations and the residual together exceed the
+ * 256 MiB cache, a value set here applies at every batch; same bits),
  * "fc2_temp_embed" (1 = the default: x + temp_embed of latte.py:357-358 is added by the first block's fc2 epilogue where fc2 runs on the
  * rolling 12-wave kernel; 0 = by the second block's first LayerNorm pass, as for every other fc2 kernel; same bits),
  * "fuse_qkv_attn" (bit 0: spatial blocks, bit 1: temporal blocks run the QKV projection and the attention core of

@@ -431,6 +431,7 @@ int latte_debug_dma_probe(const void* src, long long* out, int mode, int waves, 
  *                     conv_out).  A decode / encode call reads the choice once, when it starts, and runs entirely on that mask
  *   "gated_rmw_shape" latte_debug_gemm / _lo8 / _lo4 with epi 2 on the rolling 12-wave kernel: 1 = fragment-wise residual accesses (16 rows x 64 B
  *                     per instruction), 2 = line-wise (8 rows x 128 B on the whole line of a wave's span): the engine option of the same name + 1
+ *   "stream_policy"   16 + m: latte_debug_gemm / _lo8 / _lo4 and latte_debug_qkv_attention run with the engine option "stream_policy" = m (0..15)
  * Anything else is refused (LATTE_ERR_INVALID).  Replaces the LATTE_* environment variables round 3 read at every launch; the
  * measurement ablations whose results are garbage (attention variants 7-10, 16-19) were removed; profiles/ keeps their logs. */
 int latte_debug_set_choice(const char* name, int value);

@@ -102,6 +102,7 @@ struct GemmArgs {
   int group_m;        // persistent kernel: tile rows walked together by the grouped tile order (0 = 8)
   int rmw_mode;       // rolling 12-wave kernel, EPI_GATE_RES_F32: access shape of the residual read-modify-write, 0 = one 16 x 16 fragment
                       // (16 rows x 64 B) per instruction, 1 = the whole line of a wave's span as 8 rows x 128 B (gemm_pw.hip); same bits
+  int stream_policy;  // StreamPolicy bits: the once-used stream of this GEMM carries the `nt` hint where its kernel has the form (same bits)
   int tag;            // call site of a gated-residual GEMM (0 = attention out-projection, 1 = fc2): separate kernel symbols
   int k_chunk;        // plain kernels (variants 1-3) only: > 0 splits the contraction, grid.y = ceil(K / k_chunk) partial products
   long split_stride;  // ... written to (float*)out + blockIdx.y * split_stride (use EPI_BIAS_F32 with a zero bias)
@@ -129,6 +130,20 @@ struct GemmArgs {
 // constant block scales of the correction pass: A8 holds the rounding remainder of a half operand (|lo| <= 2^-11 |x|), W8 weights of
 // |w| < 7; the MFMA multiplies the products back by 2^-(LO8_A_SHIFT + LO8_W_SHIFT) (E8M0 scale bytes 127 - shift)
 constexpr int LO8_A_SHIFT = 12, LO8_W_SHIFT = 6;
+// Cache-policy hints of the once-used streams of a block (engine option "stream_policy", a bit mask; DESIGN.md section 8,
+// tools/stream_policy_probe.hip): a hinted stream is issued `nt` so that it does not displace the fp32 residual from the Infinity
+// Cache.  A hint is a template argument of its kernel (the DMA's policy operand is an immediate) and changes no value.  Only the
+// kernels of the large-batch forward have the forms; every other kernel ignores the bits.
+enum StreamPolicy : int {
+  SP_FC1_STORE = 1,    // fc1's hidden stores: gemm_pps_kernel<256, EPI_BIAS_GELU_H16> (gemm.hip)
+  SP_FC2_A = 2,        // fc2's A-operand DMA: the producer waves of gemm_pwr_kernel<EPI_GATE_RES_F32, tag 1 / 2> (gemm_pw.hip)
+  SP_ATTN_STORE = 4,   // attention output stores: qkv_attn_kernel<..., SPLIT = 0> (qkv_attn.hip)
+  SP_PROJ_A = 8,       // out-projection's A-operand DMA: gemm_pwr_kernel<EPI_GATE_RES_F32, tag 0>
+  SP_ALL = 15
+};
+// the default: fc1's hidden stores and fc2's read of them (headline 264.08 -> 266.89 sample-steps/s, ranges apart:
+// profiles/r8_stream_policy_ab.json); the attention output's 8-byte stores do not combine when hinted and stay plain
+constexpr int STREAM_POLICY_DEFAULT = SP_FC1_STORE | SP_FC2_A;
 // GemmArgs::rmw_mode of the denoiser's gated GEMMs unless the engine option "gated_rmw_shape" says otherwise
 constexpr int GATED_RMW_SHAPE_DEFAULT = 1;
 inline int lo4_pitch(int K) { return (K + 255) / 256 * 128; }   // bytes per row of an fp4 correction operand
@@ -190,6 +205,7 @@ struct QkvAttnArgs {
   int out_split;       // 1: out is [B F T, 2 D] = [hi | lo] -- the attention output as a split operand pair (mfma_util.h: split2)
                        // 2 (f16): out stays [B F T, D], out8 receives the fp8 remainder (mfma_util.h: split8_f16; GemmArgs::A8)
   unsigned char* out8; // [B F T, D] bytes
+  int stream_policy;   // StreamPolicy bits: SP_ATTN_STORE issues the plain (out_split == 0) output stores `nt`
 };
 bool qkv_attention_fusable(int D, int heads, int hd, int F, int T, int mode, int64_t rows);
 int launch_qkv_attention(const QkvAttnArgs& a, int dtype, hipStream_t st);
@@ -235,7 +251,7 @@ int launch_fill_f32(float* p, float v, size_t n, hipStream_t st);
 // Kernel-choice overrides of the A/B tests (latte_debug_set_choice, include/latte_amd_debug.h; engine.cpp).  Process-global, 0 = the
 // library's own choice.  Every value selects another implementation of the SAME function; nothing here can change a result beyond
 // rounding.  (Round 3 read environment variables at every launch instead, among them ablations with garbage results.)
-enum DebugChoice { DBG_ATTN_VARIANT = 0, DBG_XATTN_FLASH, DBG_TN_KERNEL, DBG_TN_WN, DBG_ATTN_BWD_TILES, DBG_CONV_KERNEL, DBG_VAE_SPLIT, DBG_GATED_RMW_SHAPE, DBG_NUM_CHOICES };
+enum DebugChoice { DBG_ATTN_VARIANT = 0, DBG_XATTN_FLASH, DBG_TN_KERNEL, DBG_TN_WN, DBG_ATTN_BWD_TILES, DBG_CONV_KERNEL, DBG_VAE_SPLIT, DBG_GATED_RMW_SHAPE, DBG_STREAM_POLICY, DBG_NUM_CHOICES };
 int debug_choice(DebugChoice c);
 int set_debug_choice(const char* name, int value);   // 0 = ok, -1 = unknown name / value not offered by this build
 

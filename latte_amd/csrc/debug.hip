@@ -129,6 +129,13 @@ __global__ void __launch_bounds__(512) dma_probe_kernel(const char* src, long lo
 }  // namespace
 
 using namespace latte;
+
+// latte_debug_set_choice("stream_policy", 16 | mask): the StreamPolicy bits of the debug GEMM and fused-attention entries; 0 = the default
+static int debug_stream_policy() {
+  const int v = debug_choice(DBG_STREAM_POLICY);
+  return v ? (v & SP_ALL) : STREAM_POLICY_DEFAULT;
+}
+
 extern "C" {
 
 // out: int64 [8 waves][2] = {ticks spent issuing, ticks until landed}, each summed over `reps` bursts of 16 instructions.
@@ -148,6 +155,7 @@ int latte_debug_gemm(const void* A, const void* W, const float* bias, void* out,
   // latte_debug_set_choice("gated_rmw_shape", 1 | 2): the fragment-wise | line-wise residual accesses of the rolling kernel's gated epilogue
   const int shape = debug_choice(DBG_GATED_RMW_SHAPE);
   g.rmw_mode = shape ? shape - 1 : GATED_RMW_SHAPE_DEFAULT;
+  g.stream_policy = debug_stream_policy();
   return launch_gemm(g, epi, dtype, variant, (hipStream_t)stream);
 }
 
@@ -169,6 +177,7 @@ int latte_debug_gemm_lo8(const void* A, const void* W, const void* A8, const voi
   g.A8 = (const uint8_t*)A8; g.W8 = (const uint8_t*)W8;
   const int shape = debug_choice(DBG_GATED_RMW_SHAPE);
   g.rmw_mode = shape ? shape - 1 : GATED_RMW_SHAPE_DEFAULT;
+  g.stream_policy = debug_stream_policy();
   return launch_gemm(g, epi, dtype, 0, (hipStream_t)stream);
 }
 
@@ -182,6 +191,7 @@ int latte_debug_gemm_lo4(const void* A, const void* W, const void* A4, const voi
   g.A4 = (const uint8_t*)A4; g.A4s = (const uint8_t*)A4s; g.W4 = (const uint8_t*)W4; g.W4s = (const uint8_t*)W4s;
   const int shape = debug_choice(DBG_GATED_RMW_SHAPE);
   g.rmw_mode = shape ? shape - 1 : GATED_RMW_SHAPE_DEFAULT;
+  g.stream_policy = debug_stream_policy();
   return launch_gemm(g, epi, dtype, 0, (hipStream_t)stream);
 }
 
@@ -354,6 +364,7 @@ int latte_debug_qkv_attention_trace(const void* xn, const void* w, const float* 
   a.xn = (const half_t*)xn; a.w = (const half_t*)w; a.bias = bias; a.out = (half_t*)out; a.dbg_qkv = (half_t*)dbg_qkv;
   a.dbg_trace = trace;
   a.B = B; a.F = F; a.T = T; a.D = D; a.heads = heads; a.hd = D / heads; a.mode = mode; a.flags = flags & 255;
+  a.stream_policy = debug_stream_policy();
   a.out_split = (flags >> 8) & 1;   // flags bit 8: out is [rows, 2 D] = [hi | lo] (the split-pair output of guided calls)
   a.scale = 1.0f / sqrtf((float)a.hd);
   return launch_qkv_attention(a, dtype, (hipStream_t)stream);

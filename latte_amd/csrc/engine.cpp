@@ -26,13 +26,14 @@ static thread_local std::string g_last_error;
 static std::atomic<int> g_debug_choice[DBG_NUM_CHOICES];
 int debug_choice(DebugChoice c) { return g_debug_choice[c].load(std::memory_order_relaxed); }
 int set_debug_choice(const char* name, int value) {
-  static const char* const names[DBG_NUM_CHOICES] = {"attn_variant", "xattn_flash", "tn_kernel", "tn_wn", "attn_bwd_tiles", "conv_kernel", "vae_split", "gated_rmw_shape"};
-  static const int allowed[DBG_NUM_CHOICES][4] = {{1, 5, 12, 13}, {1, 0, 0, 0}, {4, 0, 0, 0}, {4, 0, 0, 0}, {1, 2, 0, 0}, {1, 2, 3, 4}, {0, 0, 0, 0}, {1, 2, 0, 0}};
+  static const char* const names[DBG_NUM_CHOICES] = {"attn_variant", "xattn_flash", "tn_kernel", "tn_wn", "attn_bwd_tiles", "conv_kernel", "vae_split", "gated_rmw_shape", "stream_policy"};
+  static const int allowed[DBG_NUM_CHOICES][4] = {{1, 5, 12, 13}, {1, 0, 0, 0}, {4, 0, 0, 0}, {4, 0, 0, 0}, {1, 2, 0, 0}, {1, 2, 3, 4}, {0, 0, 0, 0}, {1, 2, 0, 0}, {0, 0, 0, 0}};
   for (int i = 0; i < DBG_NUM_CHOICES; ++i) {
     if (name && std::string(name) == names[i]) {
       bool ok = value == 0;
       for (int k = 0; k < 4; ++k) ok = ok || (allowed[i][k] != 0 && value == allowed[i][k]);
       ok = ok || (i == DBG_VAE_SPLIT && (value >> 24) == 1);   // (1 << 24) | pass mask (vae_engine.cpp: vae_split_mask)
+      ok = ok || (i == DBG_STREAM_POLICY && (value >> 4) == 1);   // 16 | StreamPolicy mask (debug.hip: debug_stream_policy)
       if (!ok) return -1;
       g_debug_choice[i].store(value, std::memory_order_relaxed);
       return 0;
@@ -73,6 +74,8 @@ struct latte_engine {
                                            // bits 2, 3: QkvAttnArgs::flags (schedule variants, same results)
   int gated_split_k = 0;                   // gated GEMMs of small batches: 0 = rule of gated_gemm, 1 = never split, 2..4 = force
   int gated_rmw_shape = GATED_RMW_SHAPE_DEFAULT;   // GemmArgs::rmw_mode of the out-projection and fc2: 0 = fragment-wise, 1 = line-wise residual accesses
+  int stream_policy = STREAM_POLICY_DEFAULT;       // StreamPolicy bits: which once-used streams of a block are issued `nt` (unguided forward)
+  bool stream_policy_set = false;                  // set through the option: applies at every batch, not only where the streams overflow the cache
   int fc2_temp_embed = 1;                  // the first block's fc2 adds temp_embed in its epilogue where its kernel can (GemmArgs::te); 0 = the
                                            // second block's first LayerNorm pass adds it (an extra write of the residual stream); same bits
   // Guided calls (forward_with_cfg, latte.py:379-398): eps_u + s (eps_c - eps_u) amplifies the part of the operand rounding that differs
@@ -292,6 +295,11 @@ int run_forward(latte_engine* e, const float* x, const int64_t* t, const int64_t
   if ((gsplit & 8) && !gemm_lo8_ok(M, e->Hm, D)) gsplit = (gsplit & ~8) | 2;
   if ((gsplit & 3) && (uint64_t)e->rows_pad * 2 * D * 2 >= (1ull << 32)) gsplit &= ~3;
   if (gsplit) gsplit = ensure_split_weights(e, gsplit, st);
+  // Stream hints: the split-operand kernels of a guided call have no hinted forms; and the library's own default applies only where
+  // the hidden activations cannot stay in the 256 MiB Infinity Cache beside the residual anyway (B = 8 at XL/2: 302 + 151 MB) -- a
+  // hidden stream that fits (B <= 4) is served from the cache when fc2 reads it back, and a hint would take that away.
+  const bool streams_overflow = (int64_t)M * (2 * e->Hm + 4 * D) > (256ll << 20);
+  const int stream_policy = gsplit ? 0 : (e->stream_policy_set || streams_overflow) ? e->stream_policy : 0;
   int gactive = gsplit & 26;   // bits 1 / 3 / 4 always apply; bits 0 / 2 once a fused attention kernel has produced the pair
 
   for (int i = 0; i < c.depth; ++i) {
@@ -307,7 +315,7 @@ int run_forward(latte_engine* e, const float* x, const int64_t* t, const int64_t
     if ((rc = launch_ln_modulate(e->xres, e->xres, e->xn, mb, mb + D, mstride, M, D, rps, te, T, F, dt, st))) return rc;
     tm.mark(C_LN);
     GemmArgs g{};
-    g.M = M; g.rows_per_sample = rps; g.gate_stride = mstride; g.rmw_mode = e->gated_rmw_shape;
+    g.M = M; g.rows_per_sample = rps; g.gate_stride = mstride; g.rmw_mode = e->gated_rmw_shape; g.stream_policy = stream_policy;
     const half_t* attn_out = e->xn;
     if (((e->fuse_qkv_attn >> (spatial ? 0 : 1)) & 1) && qkv_attention_fusable(D, c.num_heads, e->hd, F, T, spatial ? 0 : 1, M)) {
       // qkv projection + attention core in one kernel (q / k / v of a head only in LDS); the output goes to the (otherwise idle)
@@ -319,6 +327,7 @@ int run_forward(latte_engine* e, const float* x, const int64_t* t, const int64_t
       split_proj = gsplit & 5;
       qa.out_split = (gsplit & 4) ? 2 : (gsplit & 1);   // 1: [rows, 2 D] = [hi | lo] inside the [rows, 3 D] qkv buffer; 2: + fp8 remainder
       qa.out8 = e->lo8;
+      qa.stream_policy = stream_policy;
       gactive |= gsplit & 5;
       if ((rc = launch_qkv_attention(qa, dt, st))) return rc;
       tm.mark(spatial ? C_QKVATTN_S : C_QKVATTN_T);
@@ -847,6 +856,13 @@ int latte_engine_set_option(latte_engine_t* e, const char* name, int64_t value) 
     e->gated_rmw_shape = (int)value;
     return LATTE_OK;
   }
+  if (k == "stream_policy") {
+    if (value < 0 || value > SP_ALL)
+      return fail(LATTE_ERR_INVALID, "stream_policy: bit 0 = fc1's hidden stores, bit 1 = fc2's A operand, bit 2 = attention output stores, bit 3 = the out-projection's A operand carry the nt hint (0..15)");
+    e->stream_policy = (int)value;
+    e->stream_policy_set = true;
+    return LATTE_OK;
+  }
   if (k == "fc2_temp_embed") {
     if (value < 0 || value > 1) return fail(LATTE_ERR_INVALID, "fc2_temp_embed: 0 (LayerNorm pass adds temp_embed) or 1 (the first block's fc2 epilogue does)");
     e->fc2_temp_embed = (int)value;
@@ -887,6 +903,7 @@ int latte_engine_get_option(const latte_engine_t* e, const char* name, int64_t* 
   else if (k == "gemm_variant_fc2") *value = e->gemm_variant_of[3];
   else if (k == "gated_split_k") *value = e->gated_split_k;
   else if (k == "gated_rmw_shape") *value = e->gated_rmw_shape;
+  else if (k == "stream_policy") *value = e->stream_policy;
   else if (k == "fc2_temp_embed") *value = e->fc2_temp_embed;
   else if (k == "fuse_qkv_attn") *value = e->fuse_qkv_attn;
   else if (k == "guided_split") *value = e->guided_split;

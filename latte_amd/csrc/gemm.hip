@@ -556,7 +556,8 @@ __global__ void __launch_bounds__(512) gemm_pp_kernel(GemmArgs g) {
 // stores (deeper look-ahead and non-temporal loads were measured and not kept: DESIGN.md Appendix A).
 // TAG only separates the instantiations of the two gated-residual call sites (0 = attention out-projection, 1 = fc2), which
 // share every other template argument, so that a kernel trace lists them as two kernels.
-template <int BN, int EPI, int DT, int TAG = 0>
+// NT (GemmArgs::stream_policy & SP_FC1_STORE, the LDS-patch epilogue only): the half-precision output stores carry the `nt` hint.
+template <int BN, int EPI, int DT, int TAG = 0, int NT = 0>
 __global__ void __launch_bounds__(512) gemm_pps_kernel(GemmArgs g) {
   constexpr int BM = 256, NW = 8;
   constexpr int WTN = BN / 4, FN = WTN / 16;
@@ -710,7 +711,7 @@ __global__ void __launch_bounds__(512) gemm_pps_kernel(GemmArgs g) {
           const int row = kq * 8 + (le >> 3), piece = le & 7;
           const u32x4 v = *(const u32x4*)(patch + row * 128 + ((piece ^ ((row >> 1) & 7)) << 4));
           const int m = mrow0 + c * 32 + row;
-          if (m < g.M) *(u32x4*)((half_t*)g.out + (size_t)m * g.N + ncol0 + piece * 8) = v;
+          if (m < g.M) store_policy<NT != 0>((u32x4*)((half_t*)g.out + (size_t)m * g.N + ncol0 + piece * 8), v);
         }
       }
     } else {
@@ -873,7 +874,11 @@ int launch_pps(const GemmArgs& a, int epi, hipStream_t st) {
     return launch_lds<gemm_pps_kernel<BN, EPI_GATE_RES_F32, DT, 1>>(grid, block, LDS, st, a);
   switch (epi) {
     case EPI_BIAS_H16: return launch_lds<gemm_pps_kernel<BN, EPI_BIAS_H16, DT>>(grid, block, LDS, st, a);
-    case EPI_BIAS_GELU_H16: return launch_lds<gemm_pps_kernel<BN, EPI_BIAS_GELU_H16, DT>>(grid, block, LDS, st, a);
+    case EPI_BIAS_GELU_H16:
+      if constexpr (BN == 256) {   // fc1's hidden activations as a hinted stream
+        if (a.stream_policy & SP_FC1_STORE) return launch_lds<gemm_pps_kernel<BN, EPI_BIAS_GELU_H16, DT, 0, 1>>(grid, block, LDS, st, a);
+      }
+      return launch_lds<gemm_pps_kernel<BN, EPI_BIAS_GELU_H16, DT>>(grid, block, LDS, st, a);
     case EPI_GATE_RES_F32: return launch_lds<gemm_pps_kernel<BN, EPI_GATE_RES_F32, DT>>(grid, block, LDS, st, a);
     case EPI_BIAS_F32: return launch_lds<gemm_pps_kernel<BN, EPI_BIAS_F32, DT>>(grid, block, LDS, st, a);
     default:

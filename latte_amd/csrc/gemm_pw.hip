@@ -342,7 +342,9 @@ __global__ void __launch_bounds__(768) gemm_pw_kernel(GemmArgs g) {
 // pitch, the consumers run lo_tile() (24 MFMAs of 16 passes on the same fragment reads) instead of ktile() (48 of 8 passes).
 // RS: access shape of the gated epilogue's residual traffic (GemmArgs::rmw_mode): 0 = one 16 x 16 fragment per instruction,
 // 1 = the whole 128-byte line of the wave's span in 8-row instructions (see the epilogue).  TAG = 2: fc2 + temporal embedding.
-template <int EPI, int DT, int TAG, int LO = 0, int RS = 0>
+// ANT (GemmArgs::stream_policy, SP_FC2_A / SP_PROJ_A by call site; LO == 0 only): the producers' A-operand DMA carries the `nt`
+// hint -- A is a once-used activation stream, the weights keep the default policy (every XCD re-reads them every round).
+template <int EPI, int DT, int TAG, int LO = 0, int RS = 0, int ANT = 0>
 __global__ void __launch_bounds__(768) gemm_pwr_kernel(GemmArgs g) {
   constexpr int BM = 256, BN = 192, FN = 3, WTN = 48;
   constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128;
@@ -407,7 +409,7 @@ __global__ void __launch_bounds__(768) gemm_pwr_kernel(GemmArgs g) {
       }
       const unsigned so = (unsigned)(tm_ * BM + pw * 8) * row_bytes + (unsigned)kt * 128u;
 #pragma unroll
-      for (int j = 0; j < 2 * AH_INSTR; ++j) bload_lds16(rsA, sA + j * 4 * 1024, voff, so + (unsigned)j * step32);
+      for (int j = 0; j < 2 * AH_INSTR; ++j) bload_lds16<ANT ? 2 : 0>(rsA, sA + j * 4 * 1024, voff, so + (unsigned)j * step32);
     };
     auto dma_b = [&](int tn_, int kt, int stg) {
       char* sB = smem + B_BASE + stg * B_BYTES + pw * 1024;
@@ -968,8 +970,16 @@ __global__ void __launch_bounds__(768) gemm_pwr_kernel(GemmArgs g) {
 
 // roll != 0: the rolling schedule (variant 11), else the two-segment one (variant 10)
 // the rolling kernel's gated-residual instantiations: residual access shape (GemmArgs::rmw_mode) x call site / correction pass
+// and, for the plain (LO == 0) forms, the policy of the A-operand stream (GemmArgs::stream_policy: fc2's bit for TAG 1, the
+// out-projection's for TAG 0)
 template <int DT, int TAG, int LO>
 int launch_pwr_gated(const GemmArgs& a, dim3 grid, dim3 block, int lds, hipStream_t st) {
+  if constexpr (LO == 0) {
+    if (a.stream_policy & (TAG ? SP_FC2_A : SP_PROJ_A)) {
+      if (a.rmw_mode) return launch_lds<gemm_pwr_kernel<EPI_GATE_RES_F32, DT, TAG, LO, 1, 1>>(grid, block, lds, st, a);
+      return launch_lds<gemm_pwr_kernel<EPI_GATE_RES_F32, DT, TAG, LO, 0, 1>>(grid, block, lds, st, a);
+    }
+  }
   if (a.rmw_mode) return launch_lds<gemm_pwr_kernel<EPI_GATE_RES_F32, DT, TAG, LO, 1>>(grid, block, lds, st, a);
   return launch_lds<gemm_pwr_kernel<EPI_GATE_RES_F32, DT, TAG, LO, 0>>(grid, block, lds, st, a);
 }
@@ -1016,6 +1026,7 @@ int launch_pw_dt(const GemmArgs& a, int epi, int roll, hipStream_t st) {
     case EPI_GATE_RES_F32:
       if (a.te) {   // fc2 + temporal embedding (GemmArgs::te): the rolling kernel's TAG = 2 instantiations
         if (!roll || a.te_T <= 0 || a.te_F <= 0) return fail(LATTE_ERR_INVALID, "gemm (producer-wave kernel): GemmArgs::te needs the rolling kernel and te_T, te_F > 0");
+        if (a.stream_policy & SP_FC2_A) return launch_lds<gemm_pwr_kernel<EPI_GATE_RES_F32, DT, 2, 0, 0, 1>>(grid, block, LDS, st, a);
         return launch_lds<gemm_pwr_kernel<EPI_GATE_RES_F32, DT, 2, 0, 0>>(grid, block, LDS, st, a);
       }
       if (a.tag == 1) return launch_pw_roll<EPI_GATE_RES_F32, DT, 1>(a, roll, grid, block, LDS, st);

@@ -100,8 +100,16 @@ typedef __attribute__((address_space(3))) void lds_void;
 __device__ __forceinline__ void glds16(const half_t* g, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (lds_void*)lds_wave_base, 16, 0, 0);
 }
+// AUX: the instruction's cache-policy immediate, 0 = default, 2 = `nt` (a once-used stream: GemmArgs::stream_policy)
+template <int AUX = 0>
 __device__ __forceinline__ void bload_lds16(__amdgpu_buffer_rsrc_t rs, char* lds_wave_base, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)lds_wave_base, 16, voff, soff, 0, 0);
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)lds_wave_base, 16, voff, soff, 0, AUX);
+}
+// a global store of one 8- or 16-byte vector with the policy chosen at compile time
+template <bool NT, class V>
+__device__ __forceinline__ void store_policy(V* p, const V& v) {
+  if constexpr (NT) __builtin_nontemporal_store(v, p);
+  else *p = v;
 }
 
 // Attention kernels: the score of a masked key in the exp2-domain softmax, and the first row of sequence `seq` in the canonical

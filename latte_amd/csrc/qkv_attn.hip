@@ -72,7 +72,9 @@ __device__ __forceinline__ void rows_transpose4(unsigned int& x0, unsigned int& 
 // SPLIT: the output leaves as [hi | lo] pairs, row pitch 2 D (QkvAttnArgs::out_split) -- a template parameter, not a run-time branch: a
 // branch on the kernel argument inside the attention phase changed the f16 instantiation's results (hipcc, ROCm 7.2; the bf16 one was
 // unaffected), so the plain kernel stays byte for byte what rounds 3 / 4 measured and verified.
-template <int HD, int DT, int MODE, int FLAGS, int SPLIT = 0>
+// ONT (QkvAttnArgs::stream_policy & SP_ATTN_STORE, SPLIT == 0 only): the output stores carry the `nt` hint -- a template parameter
+// for the same reason.
+template <int HD, int DT, int MODE, int FLAGS, int SPLIT = 0, int ONT = 0>
 __global__ void __launch_bounds__(512) qkv_attn_kernel(QkvAttnArgs a) {
   constexpr bool EARLY = (FLAGS & 1) != 0, PRIO = (FLAGS & 2) != 0;
   constexpr int NQ = 3 * HD;
@@ -437,7 +439,7 @@ __global__ void __launch_bounds__(512) qkv_attn_kernel(QkvAttnArgs a) {
               } else {
                 const u32x2 pk = {pack2<DT>(o[gq][d][0] * inv[gq], o[gq][d][1] * inv[gq]),
                                   pack2<DT>(o[gq][d][2] * inv[gq], o[gq][d][3] * inv[gq])};
-                *(u32x2*)(orow + dd) = pk;
+                store_policy<ONT != 0>((u32x2*)(orow + dd), pk);
               }
             }
           }
@@ -520,7 +522,7 @@ __global__ void __launch_bounds__(512) qkv_attn_kernel(QkvAttnArgs a) {
               *(u32x2*)(orow + dd) = (u32x2){h0_, h1_};
             } else {
               const u32x2 pk = {pack2<DT>(oacc[0] * inv, oacc[1] * inv), pack2<DT>(oacc[2] * inv, oacc[3] * inv)};
-              *(u32x2*)(orow + dd) = pk;
+              store_policy<ONT != 0>((u32x2*)(orow + dd), pk);
             }
           }
         }
@@ -555,6 +557,9 @@ __global__ void __launch_bounds__(512) qkv_attn_kernel(QkvAttnArgs a) {
 
 template <int HD, int DT, int MODE, int FLAGS, int SPLIT = 0>
 int launch_one(const QkvAttnArgs& a, dim3 grid, hipStream_t st) {
+  if constexpr (SPLIT == 0 && HD == 72 && FLAGS == (MODE == 0 ? 3 : 1)) {   // the hinted form exists for the headline's instantiations
+    if (a.stream_policy & SP_ATTN_STORE) return launch_lds<qkv_attn_kernel<HD, DT, MODE, FLAGS, 0, 1>>(grid, dim3(512), FUSED_LDS, st, a);
+  }
   return launch_lds<qkv_attn_kernel<HD, DT, MODE, FLAGS, SPLIT>>(grid, dim3(512), FUSED_LDS, st, a);
 }
 
