@@ -466,7 +466,8 @@ int latte_trainer_optimizer_step(latte_trainer_t* e, float lr, float beta1, floa
  * half(W + s B A), one rounding), the adapter gradients come from dY, x and the adapters themselves (csrc/train_lora.hip).
  * latte_trainer_lora_enable: rank in {4, 8, 16, 32} (64 is refused: its step measured slower than the full step), alpha > 0, target_mask a non-empty subset of qkv = 1 | proj = 2 | fc1 = 4 |
  * fc2 = 8.  Legal once, BEFORE the buffers are bound; refused (LATTE_ERR_STATE) afterwards or while a step is in flight.
- * The adapters live in a second set of caller-owned flat fp32 buffers laid out by latte_trainer_lora_param_*: keys
+ * The adapters are a trained set of their own -- five caller-owned flat fp32 buffers and the table that lays them out, exactly what
+ * latte_trainer_param_* and latte_trainer_bind are for the base -- read through latte_trainer_lora_param_*: keys
  * blocks.{i}.attn.qkv.lora_A / .lora_B, blocks.{i}.attn.proj.*, blocks.{i}.mlp.fc1.*, blocks.{i}.mlp.fc2.* in block order, 16-byte
  * aligned tensors.  latte_trainer_bind_lora replaces latte_trainer_bind (which is then refused): base_params is the plain trainer's
  * parameter buffer, read only; there are no base gradient, moment or EMA buffers.  In LoRA mode every writer of a base gradient is

@@ -33,8 +33,26 @@ struct BlockBuf {
   half_t *xn1, *qkv, *att, *y1, *xn2, *u, *h, *y2;
   half_t *qkv_w, *qkv_wt, *proj_w, *proj_wt, *fc1_w, *fc1_wt, *fc2_w, *fc2_wt;
 };
+// A flat table of trained tensors and the caller-owned fp32 buffers it lays out: the base (reference named_parameters() order) or the
+// LoRA adapters.  block_begin[i]: where block i's tensors begin, block_begin[depth]: where the tensors behind the blocks do -- the
+// boundaries of the backward stages' gradient slices (latte_trainer_stage_range).
+struct TrainedSet {
+  std::vector<ParamInfo> table;
+  std::vector<int64_t> block_begin;
+  int64_t total = 0;
+  float *p = nullptr, *g = nullptr, *m1 = nullptr, *v2 = nullptr, *ema = nullptr;
+  // -> the offset the tensor got
+  int64_t add(const std::string& key, int64_t numel) {
+    const int64_t off = total;
+    table.push_back(ParamInfo{key, off, numel});
+    total += (numel + 3) / 4 * 4;   // 16-byte aligned tensors inside the flat buffers
+    return off;
+  }
+  void bind(float* p_, float* g_, float* m1_, float* v2_, float* ema_) { p = p_; g = g_; m1 = m1_; v2 = v2_; ema = ema_; }
+  const ParamInfo* entry(int i) const { return i >= 0 && i < (int)table.size() ? &table[i] : nullptr; }
+};
 // LoRA: where a block's adapters lie in the flat adapter buffers (-1: the linear is not targeted), linear j = qkv, proj, fc1, fc2
-struct LoraOffsets { int64_t a[4], b[4], begin; };
+struct LoraOffsets { int64_t a[4], b[4]; };
 const char* const LORA_LINEAR[4] = {"attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2"};
 // a gradient writer of the frozen base was reached in LoRA mode (G() below): the stage ends with LATTE_ERR_STATE before its launch
 struct FrozenBaseWrite {};
@@ -76,11 +94,11 @@ struct latte_trainer {
   PackPlan pack_plan{};
   float growth_interval = 2000.0f;
   float* scaler = nullptr;
-  std::vector<ParamInfo> params;
-  std::vector<BlockParams> bp;   // + rp: where every trained tensor lies in the flat buffers
+  // The model's own tensors and, under LoRA, the adapters; the optimiser trains ONE of them (trained() below).  A third kind of
+  // trained tensor is a third set here: its table built through add(), its buffers bound, trained() told when it is the one
+  TrainedSet base, adapters;
+  std::vector<BlockParams> bp;   // + rp: where every tensor of the base lies in its flat buffers
   RestParams rp{};
-  int64_t total = 0;
-  float *Pm = nullptr, *Gr = nullptr, *M1 = nullptr, *V2 = nullptr, *Ema = nullptr;   // bound flat buffers (caller-owned)
   float *pos = nullptr, *temp = nullptr, *pe_wt = nullptr, *fin_wt = nullptr;
   std::vector<float*> xs;        // 2 depth + 1 residual-stream snapshots, fp32 [rows_pad, D]
   std::vector<BlockBuf> blk;
@@ -120,13 +138,10 @@ struct latte_trainer {
   // LoRA (latte_trainer_lora_enable; train_lora.hip): the base buffer is frozen -- no base gradient, moment or EMA buffer
   // is bound, every base-gradient writer is skipped -- and rank-r adapters on the targeted block linears train instead.  The half operand
   // copies hold W + s B A (the pack adds it), so the forward and the input-gradient GEMMs are the plain trainer's launches; linear_bwd
-  // replaces the weight-gradient GEMM by the adapter gradients.  A second flat table (lparams) lays the adapters out.
+  // replaces the weight-gradient GEMM by the adapter gradients.  The `adapters` set lays them out; lo: per block, per linear.
   int lora_rank = 0, lora_mask = 0;
   float lora_s = 0.f;
-  std::vector<ParamInfo> lparams;
   std::vector<LoraOffsets> lo;
-  int64_t ltotal = 0;
-  float *LP = nullptr, *LG = nullptr, *LM1 = nullptr, *LV2 = nullptr, *LEma = nullptr;   // bound flat adapter buffers (caller-owned)
   std::vector<LoraPackDesc> lora_host;   // [block][qkv, proj, fc1, fc2]
   LoraPackDesc *lora_descs = nullptr, *lora_merge_descs = nullptr;
   half_t *lora_h = nullptr, *lora_g = nullptr;   // [rows_pad, 2 R16]: s x A^T and s dY B of the linear in hand, as split pairs hi | lo
@@ -135,13 +150,17 @@ struct latte_trainer {
 
 namespace {
 
-// -> the offset the tensor got
-int64_t add_param(latte_trainer* e, const std::string& key, int64_t numel) {
-  const int64_t off = e->total;
-  e->params.push_back(ParamInfo{key, off, numel});
-  e->total += (numel + 3) / 4 * 4;   // 16-byte aligned tensors inside the flat buffers
-  return off;
-}
+int64_t add_param(latte_trainer* e, const std::string& key, int64_t numel) { return e->base.add(key, numel); }
+// the set the optimiser trains: the adapters under LoRA (the base is frozen), the base otherwise
+const TrainedSet& trained(const latte_trainer* e) { return e->lora_rank ? e->adapters : e->base; }
+// the bodies of the two accessor families (latte_trainer_param_* / latte_trainer_lora_param_*): s = the family's set, NULL without a trainer
+int set_size(const TrainedSet* s) { return s ? (int)s->table.size() : 0; }
+const char* set_key(const TrainedSet* s, int i) { return s && s->entry(i) ? s->entry(i)->key.c_str() : nullptr; }
+int64_t set_offset(const TrainedSet* s, int i) { return s && s->entry(i) ? s->entry(i)->offset : -1; }
+int64_t set_numel(const TrainedSet* s, int i) { return s && s->entry(i) ? s->entry(i)->numel : -1; }
+int64_t set_total(const TrainedSet* s) { return s ? s->total : 0; }
+const TrainedSet* base_of(const latte_trainer* e) { return e ? &e->base : nullptr; }
+const TrainedSet* adapters_of(const latte_trainer* e) { return e ? &e->adapters : nullptr; }
 
 // ---- LoRA: what latte_trainer_lora_enable accepts, and the adapter table (host logic: latte_debug_lora_table reads it without a device)
 int lora_validate(int rank, float alpha, int target_mask) {
@@ -160,35 +179,28 @@ void lora_shape(int D, int Hm, int j, int* N, int* K) {   // W [N, K] of linear 
   const int shp[4][2] = {{3 * D, D}, {D, D}, {Hm, D}, {D, Hm}};
   *N = shp[j][0]; *K = shp[j][1];
 }
-// block-major, per block qkv, proj, fc1, fc2 (the targeted ones), per linear lora_A [rank, K] then lora_B [N, rank] -> total floats
-int64_t lora_table(int D, int Hm, int depth, int rank, int target_mask, std::vector<ParamInfo>& lp, std::vector<LoraOffsets>& lo) {
-  int64_t total = 0;
-  auto add = [&](const std::string& key, int64_t numel) {
-    const int64_t off = total;
-    lp.push_back(ParamInfo{key, off, numel});
-    total += (numel + 3) / 4 * 4;   // 16-byte aligned tensors, as in the base table
-    return off;
-  };
+// block-major, per block qkv, proj, fc1, fc2 (the targeted ones), per linear lora_A [rank, K] then lora_B [N, rank]
+void lora_table(int D, int Hm, int depth, int rank, int target_mask, TrainedSet& set, std::vector<LoraOffsets>& lo) {
   lo.assign((size_t)depth, LoraOffsets{});
   for (int i = 0; i < depth; ++i) {
-    lo[i].begin = total;
+    set.block_begin.push_back(set.total);
     for (int j = 0; j < 4; ++j) {
       lo[i].a[j] = lo[i].b[j] = -1;
       if (!(target_mask >> j & 1)) continue;
       int N, K;
       lora_shape(D, Hm, j, &N, &K);
       const std::string p = "blocks." + std::to_string(i) + "." + LORA_LINEAR[j];
-      lo[i].a[j] = add(p + ".lora_A", (int64_t)rank * K);
-      lo[i].b[j] = add(p + ".lora_B", (int64_t)N * rank);
+      lo[i].a[j] = set.add(p + ".lora_A", (int64_t)rank * K);
+      lo[i].b[j] = set.add(p + ".lora_B", (int64_t)N * rank);
     }
   }
-  return total;
+  set.block_begin.push_back(set.total);   // nothing lies behind the blocks
 }
 
-float* P(const latte_trainer* e, int64_t off) { return e->Pm + off; }
+float* P(const latte_trainer* e, int64_t off) { return e->base.p + off; }
 float* G(const latte_trainer* e, int64_t off) {
-  if (e->lora_rank || !e->Gr) throw FrozenBaseWrite{};   // LoRA: there is no base gradient buffer (latte_trainer_backward_stage catches)
-  return e->Gr + off;
+  if (e->lora_rank || !e->base.g) throw FrozenBaseWrite{};   // LoRA: there is no base gradient buffer (latte_trainer_backward_stage catches)
+  return e->base.g + off;
 }
 // a step is in flight: begin / seed ran and a backward stage is still due
 bool step_in_flight(const latte_trainer* e) { return e->next_stage <= e->cfg.depth + 1; }
@@ -317,6 +329,7 @@ int latte_trainer_create_joint(const latte_model_config_t* cfg, int max_batch, i
   for (int i = 0; i < c.depth; ++i) {
     const std::string p = "blocks." + std::to_string(i) + ".";
     BlockParams& w = e->bp[i];
+    e->base.block_begin.push_back(e->base.total);
     w.qkv_w = add_param(e, p + "attn.qkv.weight", (int64_t)3 * D * D);
     w.qkv_b = add_param(e, p + "attn.qkv.bias", 3 * D);
     w.proj_w = add_param(e, p + "attn.proj.weight", (int64_t)D * D);
@@ -328,6 +341,7 @@ int latte_trainer_create_joint(const latte_model_config_t* cfg, int max_batch, i
     w.ada_w = add_param(e, p + "adaLN_modulation.1.weight", (int64_t)6 * D * D);
     w.ada_b = add_param(e, p + "adaLN_modulation.1.bias", 6 * D);
   }
+  e->base.block_begin.push_back(e->base.total);   // the final layer lies behind the blocks
   r.fin_w = add_param(e, "final_layer.linear.weight", (int64_t)e->P * D);
   r.fin_b = add_param(e, "final_layer.linear.bias", e->P);
   r.fin_ada_w = add_param(e, "final_layer.adaLN_modulation.1.weight", (int64_t)2 * D * D);
@@ -413,18 +427,21 @@ void latte_trainer_destroy(latte_trainer_t* e) {
   delete e;   // the arena frees every device block
 }
 
-int latte_trainer_num_params(const latte_trainer_t* e) { return e ? (int)e->params.size() : 0; }
-const char* latte_trainer_param_key(const latte_trainer_t* e, int i) {
-  return (e && i >= 0 && i < (int)e->params.size()) ? e->params[i].key.c_str() : nullptr;
-}
-int64_t latte_trainer_param_offset(const latte_trainer_t* e, int i) { return (e && i >= 0 && i < (int)e->params.size()) ? e->params[i].offset : -1; }
-int64_t latte_trainer_param_numel(const latte_trainer_t* e, int i) { return (e && i >= 0 && i < (int)e->params.size()) ? e->params[i].numel : -1; }
-int64_t latte_trainer_total_numel(const latte_trainer_t* e) { return e ? e->total : 0; }
+int latte_trainer_num_params(const latte_trainer_t* e) { return set_size(base_of(e)); }
+const char* latte_trainer_param_key(const latte_trainer_t* e, int i) { return set_key(base_of(e), i); }
+int64_t latte_trainer_param_offset(const latte_trainer_t* e, int i) { return set_offset(base_of(e), i); }
+int64_t latte_trainer_param_numel(const latte_trainer_t* e, int i) { return set_numel(base_of(e), i); }
+int64_t latte_trainer_total_numel(const latte_trainer_t* e) { return set_total(base_of(e)); }
+int latte_trainer_lora_num_params(const latte_trainer_t* e) { return set_size(adapters_of(e)); }
+const char* latte_trainer_lora_param_key(const latte_trainer_t* e, int i) { return set_key(adapters_of(e), i); }
+int64_t latte_trainer_lora_param_offset(const latte_trainer_t* e, int i) { return set_offset(adapters_of(e), i); }
+int64_t latte_trainer_lora_param_numel(const latte_trainer_t* e, int i) { return set_numel(adapters_of(e), i); }
+int64_t latte_trainer_lora_total_numel(const latte_trainer_t* e) { return set_total(adapters_of(e)); }
 
 int latte_trainer_bind(latte_trainer_t* e, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* ema) {
   if (!e || !params || !grads || !exp_avg || !exp_avg_sq) return fail(LATTE_ERR_INVALID, "trainer_bind: null buffer");
   if (e->lora_rank) return fail(LATTE_ERR_STATE, "trainer_bind: LoRA is enabled, bind with latte_trainer_bind_lora");
-  e->Pm = params; e->Gr = grads; e->M1 = exp_avg; e->V2 = exp_avg_sq; e->Ema = ema;
+  e->base.bind(params, grads, exp_avg, exp_avg_sq, ema);
   e->weights_synced = false;
   {   // pointer table of the one-launch weight pack (train_fin.hip): [block][qkv, proj, fc1, fc2]
     const int D = e->D, Hm = e->Hm;
@@ -448,13 +465,13 @@ int latte_trainer_bind(latte_trainer_t* e, float* params, float* grads, float* e
 int latte_trainer_lora_enable(latte_trainer_t* e, int rank, float alpha, int target_mask) {
   if (!e) return fail(LATTE_ERR_INVALID, "lora_enable: null trainer");
   if (step_in_flight(e) || e->custom == 1) return fail(LATTE_ERR_STATE, "lora_enable: a step is in flight");
-  if (e->Pm || e->lora_rank) return fail(LATTE_ERR_STATE, "lora_enable: legal once, before the buffers are bound");
+  if (e->base.p || e->lora_rank) return fail(LATTE_ERR_STATE, "lora_enable: legal once, before the buffers are bound");
   int rc;
   if ((rc = lora_validate(rank, alpha, target_mask))) return rc;
   const int D = e->D, Hm = e->Hm, depth = e->cfg.depth, R16 = (rank + 15) / 16 * 16;
-  std::vector<ParamInfo> lp;
+  TrainedSet set;
   std::vector<LoraOffsets> lo;
-  const int64_t total = lora_table(D, Hm, depth, rank, target_mask, lp, lo);
+  lora_table(D, Hm, depth, rank, target_mask, set, lo);
   std::vector<LoraPackDesc> host((size_t)depth * 4);
   auto A = [&](auto** p, size_t n) { if (!rc) rc = e->arena.alloc(p, n); };
   for (int i = 0; i < depth; ++i)
@@ -471,10 +488,9 @@ int latte_trainer_lora_enable(latte_trainer_t* e, int rank, float alpha, int tar
   A(&e->lora_descs, (size_t)depth * 4);
   A(&e->lora_merge_descs, (size_t)depth * 4);
   if (rc) return rc;
-  e->lparams = std::move(lp);
+  e->adapters = std::move(set);
   e->lo = std::move(lo);
   e->lora_host = std::move(host);
-  e->ltotal = total;
   e->lora_mask = target_mask;
   e->lora_s = alpha / (float)rank;
   e->lora_rank = rank;
@@ -486,35 +502,28 @@ int latte_debug_lora_table(const latte_model_config_t* cfg, int rank, float alph
                            int64_t* offset, int64_t* numel, int* num_params, int64_t* total) {
   if (!cfg || cfg->depth < 1 || cfg->hidden_size < 1 || cfg->mlp_hidden < 1) return fail(LATTE_ERR_INVALID, "lora_table: bad config");
   if (int rc = lora_validate(rank, alpha, target_mask)) return rc;
-  std::vector<ParamInfo> lp;
+  TrainedSet set;
   std::vector<LoraOffsets> lo;
-  const int64_t t = lora_table(cfg->hidden_size, cfg->mlp_hidden, cfg->depth, rank, target_mask, lp, lo);
-  if (num_params) *num_params = (int)lp.size();
-  if (total) *total = t;
+  lora_table(cfg->hidden_size, cfg->mlp_hidden, cfg->depth, rank, target_mask, set, lo);
+  if (num_params) *num_params = set_size(&set);
+  if (total) *total = set.total;
   if (index < 0) return LATTE_OK;   // the counts only
-  if (index >= (int)lp.size() || !key_out || key_cap <= (int)lp[index].key.size()) return fail(LATTE_ERR_INVALID, "lora_table: bad index or key buffer");
-  std::copy(lp[index].key.begin(), lp[index].key.end(), key_out);
-  key_out[lp[index].key.size()] = 0;
-  if (offset) *offset = lp[index].offset;
-  if (numel) *numel = lp[index].numel;
+  const ParamInfo* p = set.entry(index);
+  if (!p || !key_out || key_cap <= (int)p->key.size()) return fail(LATTE_ERR_INVALID, "lora_table: bad index or key buffer");
+  std::copy(p->key.begin(), p->key.end(), key_out);
+  key_out[p->key.size()] = 0;
+  if (offset) *offset = p->offset;
+  if (numel) *numel = p->numel;
   return LATTE_OK;
 }
-
-int latte_trainer_lora_num_params(const latte_trainer_t* e) { return e ? (int)e->lparams.size() : 0; }
-const char* latte_trainer_lora_param_key(const latte_trainer_t* e, int i) {
-  return (e && i >= 0 && i < (int)e->lparams.size()) ? e->lparams[i].key.c_str() : nullptr;
-}
-int64_t latte_trainer_lora_param_offset(const latte_trainer_t* e, int i) { return (e && i >= 0 && i < (int)e->lparams.size()) ? e->lparams[i].offset : -1; }
-int64_t latte_trainer_lora_param_numel(const latte_trainer_t* e, int i) { return (e && i >= 0 && i < (int)e->lparams.size()) ? e->lparams[i].numel : -1; }
-int64_t latte_trainer_lora_total_numel(const latte_trainer_t* e) { return e ? e->ltotal : 0; }
 
 int latte_trainer_bind_lora(latte_trainer_t* e, float* base_params, float* lora_params, float* lora_grads, float* lora_exp_avg,
                             float* lora_exp_avg_sq, float* lora_ema) {
   if (!e || !base_params || !lora_params || !lora_grads || !lora_exp_avg || !lora_exp_avg_sq) return fail(LATTE_ERR_INVALID, "trainer_bind_lora: null buffer");
   if (!e->lora_rank) return fail(LATTE_ERR_STATE, "trainer_bind_lora: call latte_trainer_lora_enable first");
   if (step_in_flight(e) || e->custom == 1) return fail(LATTE_ERR_STATE, "trainer_bind_lora: a step is in flight");
-  e->Pm = base_params; e->Gr = nullptr; e->M1 = nullptr; e->V2 = nullptr; e->Ema = nullptr;
-  e->LP = lora_params; e->LG = lora_grads; e->LM1 = lora_exp_avg; e->LV2 = lora_exp_avg_sq; e->LEma = lora_ema;
+  e->base.bind(base_params, nullptr, nullptr, nullptr, nullptr);
+  e->adapters.bind(lora_params, lora_grads, lora_exp_avg, lora_exp_avg_sq, lora_ema);
   e->weights_synced = false;
   for (int i = 0; i < e->cfg.depth; ++i) {
     const BlockParams& w = e->bp[i];
@@ -525,8 +534,8 @@ int latte_trainer_bind_lora(latte_trainer_t* e, float* base_params, float* lora_
     for (int j = 0; j < 4; ++j) {
       LoraPackDesc& d = e->lora_host[(size_t)i * 4 + j];
       d.w = P(e, wo[j]); d.wn = wn[j]; d.wt = wt[j]; d.wf = nullptr;
-      d.A = e->lo[i].a[j] >= 0 ? e->LP + e->lo[i].a[j] : nullptr;
-      d.B = e->lo[i].b[j] >= 0 ? e->LP + e->lo[i].b[j] : nullptr;
+      d.A = e->lo[i].a[j] >= 0 ? lora_params + e->lo[i].a[j] : nullptr;
+      d.B = e->lo[i].b[j] >= 0 ? lora_params + e->lo[i].b[j] : nullptr;
     }
   }
   LATTE_HIP(hipDeviceSynchronize());
@@ -538,14 +547,16 @@ int latte_trainer_bind_lora(latte_trainer_t* e, float* base_params, float* lora_
 // lora_params: the adapters to merge (NULL: the bound ones; the EMA buffer merges the EMA adapters).  Synchronises.
 int latte_trainer_lora_merge(latte_trainer_t* e, const float* lora_params, float* params_out, void* stream) {
   if (!e || !params_out) return fail(LATTE_ERR_INVALID, "lora_merge: null argument");
-  if (!e->lora_rank || !e->Pm) return fail(LATTE_ERR_STATE, "lora_merge: bind the LoRA buffers first");
+  if (!e->lora_rank || !e->base.p) return fail(LATTE_ERR_STATE, "lora_merge: bind the LoRA buffers first");
   if (step_in_flight(e)) return fail(LATTE_ERR_STATE, "lora_merge: a step is in flight");
-  const float* lp = lora_params ? lora_params : e->LP;
+  const float* lp = lora_params ? lora_params : e->adapters.p;
   std::vector<LoraPackDesc> h = e->lora_host;
-  for (LoraPackDesc& d : h) {
-    d.wf = params_out + (d.w - e->Pm);
+  for (size_t li = 0; li < h.size(); ++li) {   // li = block * 4 + linear
+    LoraPackDesc& d = h[li];
+    const LoraOffsets& o = e->lo[li / 4];
+    d.wf = params_out + (d.w - e->base.p);   // the same offset in the caller's copy of the base buffer
     d.wn = d.wt = nullptr;
-    if (d.A) { d.A = lp + (d.A - e->LP); d.B = lp + (d.B - e->LP); }
+    if (d.A) { d.A = lp + o.a[li % 4]; d.B = lp + o.b[li % 4]; }
   }
   LATTE_HIP(hipDeviceSynchronize());
   LATTE_HIP(hipMemcpy(e->lora_merge_descs, h.data(), h.size() * sizeof(LoraPackDesc), hipMemcpyHostToDevice));
@@ -564,7 +575,7 @@ int latte_trainer_set_frozen(latte_trainer_t* e, const float* pos_embed, const f
 }
 
 int latte_trainer_sync_weights(latte_trainer_t* e, void* stream) {
-  if (!e || !e->Pm) return fail(LATTE_ERR_STATE, "trainer_sync_weights: bind the parameter buffers first");
+  if (!e || !e->base.p) return fail(LATTE_ERR_STATE, "trainer_sync_weights: bind the parameter buffers first");
   hipStream_t st = (hipStream_t)stream;
   int rc;
   if (e->lora_rank) {   // half(W + s B A) into the same operand copies, and the adapters' own padded half copies
@@ -697,7 +708,7 @@ int arm_backward(latte_trainer_t* e, const int64_t* y, int B, hipStream_t st) {
 int begin_impl(latte_trainer_t* e, const latte_schedule_t* s, int loss_type, const float* x_start, const float* noise, const int64_t* t,
                const int64_t* y, int batch, int batch_cap, float* terms_out, float* model_out_copy, void* stream) {
   if (!e || !s || !x_start || !noise || !t || !terms_out) return fail(LATTE_ERR_INVALID, "train step: null argument");
-  if (!e->Pm) return fail(LATTE_ERR_STATE, "train step: bind the parameter buffers first");
+  if (!e->base.p) return fail(LATTE_ERR_STATE, "train step: bind the parameter buffers first");
   if (batch <= 0 || batch > batch_cap) return fail(LATTE_ERR_STATE, "train step: batch exceeds max_batch");
   if (loss_type != 0 && loss_type != 1) return fail(LATTE_ERR_INVALID, "train step: loss_type must be 0 (MSE) or 1 (RESCALED_MSE); the KL losses train no mean head (gaussian_diffusion.py:741-752)");
   if (s->mean_type != 0) return fail(LATTE_ERR_INVALID, "train step: only the epsilon-prediction models of train.py:92 are supported");
@@ -809,11 +820,12 @@ static float* pg2_of(const latte_trainer_t* e, int i) { return ((e->run_temporal
 // loss-scaled domain and assigns -- or, in accumulate mode, adds -- to the adapter gradient buffer.  Four launches + two reductions.
 static int lora_grads(latte_trainer_t* e, int li, const half_t* dY, const half_t* x, int M, int N, int K, hipStream_t st) {
   const LoraPackDesc& d = e->lora_host[li];
-  if (!d.A) return LATTE_OK;
+  const LoraOffsets& o = e->lo[li / 4];
+  if (o.a[li % 4] < 0) return LATTE_OK;
   const int r = e->lora_rank, dt = e->dt;
   const float* us = scaling_active(e) ? e->scaler : nullptr;
-  float* dA = e->LG + (d.A - e->LP);
-  float* dB = e->LG + (d.B - e->LP);
+  float* dA = e->adapters.g + o.a[li % 4];
+  float* dB = e->adapters.g + o.b[li % 4];
   int rc, chunk = 0;
   if ((rc = launch_lora_down(x, d.a_h, e->lora_h, M, K, r, e->lora_s, dt, st))) return rc;
   if ((rc = launch_lora_down(dY, d.bt_h, e->lora_g, M, N, r, e->lora_s, dt, st))) return rc;
@@ -1015,22 +1027,14 @@ static int backward_embed(latte_trainer_t* e, hipStream_t st) {
 int latte_trainer_num_stages(const latte_trainer_t* e) { return e ? e->cfg.depth + 2 : 0; }
 
 // the slice of the flat gradient buffer that stage `stage` finalises: 0 = final layer, 1 .. depth = blocks depth-1 .. 0,
-// depth + 1 = patch embed + t / y embedders (the head of the buffer)
+// depth + 1 = patch embed + t / y embedders (the head of the buffer) -- of the TRAINED set: the adapters have nothing in front of
+// or behind their blocks, so their stages 0 and depth + 1 finish the empty slices at the buffer's end and head
 int latte_trainer_stage_range(const latte_trainer_t* e, int stage, int64_t* offset, int64_t* numel) {
   if (!e || !offset || !numel || stage < 0 || stage > e->cfg.depth + 1) return fail(LATTE_ERR_INVALID, "stage_range: bad stage");
-  const int depth = e->cfg.depth;
-  if (e->lora_rank) {   // the adapter buffers: a block stage finishes its block's adapters, the other two stages nothing
-    const int i = depth - stage;
-    *offset = stage == 0 ? e->ltotal : stage <= depth ? e->lo[i].begin : 0;
-    *numel = stage >= 1 && stage <= depth ? (i + 1 < depth ? e->lo[i + 1].begin : e->ltotal) - e->lo[i].begin : 0;
-    return LATTE_OK;
-  }
-  if (stage == 0) { *offset = e->rp.fin_w; *numel = e->total - *offset; }
-  else if (stage <= depth) {
-    const int i = depth - stage;
-    *offset = e->bp[i].qkv_w;
-    *numel = (i + 1 < depth ? e->bp[i + 1].qkv_w : e->rp.fin_w) - *offset;
-  } else { *offset = 0; *numel = e->bp[0].qkv_w; }
+  const TrainedSet& s = trained(e);
+  const int depth = e->cfg.depth, i = depth - stage;   // block i, or: -1 = in front of the blocks, depth = behind them
+  *offset = i < 0 ? 0 : s.block_begin[i];
+  *numel = (i < depth ? s.block_begin[i + 1] : s.total) - *offset;
   return LATTE_OK;
 }
 
@@ -1039,7 +1043,7 @@ int latte_trainer_stage_range(const latte_trainer_t* e, int stage, int64_t* offs
 int latte_trainer_backward_stage(latte_trainer_t* e, int stage, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   int rc;
-  if (!e || !e->Pm) rc = fail(LATTE_ERR_STATE, "backward_stage: no step in flight");
+  if (!e || !e->base.p) rc = fail(LATTE_ERR_STATE, "backward_stage: no step in flight");
   else if (stage != e->next_stage || stage > e->cfg.depth + 1) rc = fail(LATTE_ERR_STATE, "backward_stage: stages run in order after latte_trainer_begin");
   else {
     e->next_stage = stage + 1;
@@ -1054,7 +1058,7 @@ int latte_trainer_backward_stage(latte_trainer_t* e, int stage, void* stream) {
   if (!rc && !e->lora_rank && scaling_active(e) && !e->grad_accumulate && !(e->fuse_small && stage >= 1 && stage <= e->cfg.depth)) {   // the slice this stage finalised leaves the loss-scaled domain
     int64_t off = 0, n = 0;
     if ((rc = latte_trainer_stage_range(e, stage, &off, &n))) return rc;
-    rc = launch_scale_f32_dev(e->Gr + off, e->scaler, 1, (size_t)n, st);
+    rc = launch_scale_f32_dev(trained(e).g + off, e->scaler, 1, (size_t)n, st);
   }
   if (e && e->joint_saved_acc >= 0 && (rc || stage == e->cfg.depth + 1)) {   // the image pass of a joint micro-batch is over
     plain_mode(e);
@@ -1123,7 +1127,7 @@ int latte_trainer_forward_backward_joint(latte_trainer_t* e, const latte_schedul
 int latte_trainer_forward(latte_trainer_t* e, const float* x, const int64_t* t_model, const int64_t* y, int batch, float* model_out,
                           void* stream) {
   if (!e || !x || !t_model || !model_out) return fail(LATTE_ERR_INVALID, "trainer_forward: null argument");
-  if (!e->Pm) return fail(LATTE_ERR_STATE, "trainer_forward: bind the parameter buffers first");
+  if (!e->base.p) return fail(LATTE_ERR_STATE, "trainer_forward: bind the parameter buffers first");
   if (e->joint_saved_acc >= 0) return fail(LATTE_ERR_STATE, "trainer_forward: the image pass of a joint micro-batch is in flight");
   if (step_in_flight(e)) return fail(LATTE_ERR_STATE, "trainer_forward: a step is in flight");
   if (batch <= 0 || batch > e->max_batch) return fail(LATTE_ERR_STATE, "trainer_forward: batch exceeds max_batch");
@@ -1169,17 +1173,16 @@ int latte_trainer_input_grad(latte_trainer_t* e, float* dx_out, void* stream) {
 // half operand copies are re-packed.  norm_out: optional device float[2] = {total gradient norm, applied clip coefficient}.
 int latte_trainer_optimizer_step(latte_trainer_t* e, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                                  float clip_max_norm, int clip, float ema_decay, float* norm_out, void* stream) {
-  if (!e || !e->Pm) return fail(LATTE_ERR_STATE, "optimizer_step: bind the parameter buffers first");
+  if (!e || !e->base.p) return fail(LATTE_ERR_STATE, "optimizer_step: bind the parameter buffers first");
   if (step < 0) return fail(LATTE_ERR_INVALID, "optimizer_step: step counts from 1 (0: the trainer's own count of applied updates)");
   e->custom = 0;   // the weights and perhaps the loss scale change: a forward awaiting its seed is abandoned, the input gradient's time is over
   hipStream_t st = (hipStream_t)stream;
   int rc;
-  const bool lora = e->lora_rank != 0;   // the trained buffers: the adapters' (the base has no gradient, moments or EMA of its own)
-  float *p = lora ? e->LP : e->Pm, *g = lora ? e->LG : e->Gr, *m1 = lora ? e->LM1 : e->M1, *v2 = lora ? e->LV2 : e->V2, *ema = lora ? e->LEma : e->Ema;
-  const size_t n = (size_t)(lora ? e->ltotal : e->total);
-  if ((rc = launch_grad_norm(g, n, e->sumsq, clip_max_norm, clip, e->stats, e->scaler, st))) return rc;
+  const TrainedSet& s = trained(e);
+  const size_t n = (size_t)s.total;
+  if ((rc = launch_grad_norm(s.g, n, e->sumsq, clip_max_norm, clip, e->stats, e->scaler, st))) return rc;
   if (norm_out) LATTE_HIP(hipMemcpyAsync(norm_out, e->stats, sizeof(float) * 2, hipMemcpyDeviceToDevice, st));
-  if ((rc = launch_adamw_ema(p, g, m1, v2, ema, n, lr, beta1, beta2, eps, weight_decay, step, ema_decay,
+  if ((rc = launch_adamw_ema(s.p, s.g, s.m1, s.v2, s.ema, n, lr, beta1, beta2, eps, weight_decay, step, ema_decay,
                              e->stats, e->scaler + 2, st))) return rc;
   return latte_trainer_sync_weights(e, stream);
 }

@@ -12,6 +12,7 @@ buffers (the model's ``nn.Parameter``s become views of the parameter buffer, as 
 averages the gradient buffer across ranks with ONE RCCL all-reduce per step when ``torch.distributed`` is initialised
 (train.py:125 wraps the model in DDP; the engine itself never communicates).  There is no CPU / autograd fallback.
 """
+import ctypes
 import math
 
 import torch
@@ -24,6 +25,8 @@ from .models import Latte
 FROZEN = ("pos_embed", "temp_embed")   # nn.Parameter(requires_grad=False), latte.py:246-247
 LORA_TARGETS = ("qkv", "proj", "fc1", "fc2")   # bit j of latte_trainer_lora_enable's target_mask
 LORA_RANKS = (4, 8, 16, 32)   # rank 64 is refused: measured slower than the full step at Latte-B/2 (DESIGN.md 4.4 "LoRA")
+SCALER_KEYS = ("loss_scale", "good_steps", "applied_updates", "skipped_updates", "last_skipped", "dynamic", "growth_interval", "max_scale")
+_BUFFERS = ("params", "grads", "exp_avg", "exp_avg_sq", "ema")   # latte_trainer_bind's order
 
 
 def lora_target_mask(targets):
@@ -71,6 +74,49 @@ def merge_lora_state_dict(sd, lora_sd, config):
             raise LatteError(f"merge_lora_state_dict: {k} does not fit {w}")
         out[w] = (sd[w].float() + s * (b.float().to(sd[w].device) @ a.float().to(sd[w].device))).to(sd[w].dtype)
     return out
+
+
+class _FlatSet:
+    """One trained set of the engine (the base, or the LoRA adapters) as PyTorch holds it: ``layout`` [(key, offset, numel)], the shape
+    of every key and the five flat fp32 buffers the table lays out -- None for a buffer the set has none of (the frozen base of a
+    LoRA trainer has ``params`` only).  family: "" reads latte_trainer_param_*, "lora_" reads latte_trainer_lora_param_*."""
+
+    def __init__(self, h, family, shape_of, device, buffers=_BUFFERS):
+        lib = load_library()
+        fn = lambda name: getattr(lib, "latte_trainer_" + family + name)   # noqa: E731
+        self.layout = [(fn("param_key")(h, i).decode(), int(fn("param_offset")(h, i)), int(fn("param_numel")(h, i)))
+                       for i in range(fn("num_params")(h))]
+        self.shapes = {k: tuple(shape_of(k)) for k, _, _ in self.layout}
+        total = int(fn("total_numel")(h))
+        for name in _BUFFERS:
+            setattr(self, name, torch.zeros(total, device=device) if name in buffers else None)
+
+    def pointers(self):
+        return [ptr(getattr(self, name)) for name in _BUFFERS if getattr(self, name) is not None]
+
+    def views(self, name):
+        """{key: view of buffer ``name`` in the key's shape}"""
+        flat = getattr(self, name)
+        return {k: flat[off:off + numel].view(self.shapes[k]) for k, off, numel in self.layout}
+
+    def keyed(self, name):
+        return {k: v.clone() for k, v in self.views(name).items()}
+
+    def load(self, name, sd, what=None):
+        """``sd[key]`` of every key into buffer ``name``.  what (the caller's name in the messages): ``sd`` must hold exactly the set's
+        keys in the set's shapes; without it further keys are ignored (a model's state dict also holds the frozen tables)."""
+        if what:
+            missing = [k for k in self.shapes if k not in sd]
+            extra = [k for k in sd if k not in self.shapes]
+            if missing or extra:
+                raise LatteError(f"{what}: missing keys {missing[:4]}, unexpected keys {extra[:4]} (rank / targets differ?)")
+            for k, shape in self.shapes.items():
+                if tuple(sd[k].shape) != shape:
+                    raise LatteError(f"{what}: {k} is {list(sd[k].shape)}, expected {list(shape)}")
+        flat = getattr(self, name)
+        with torch.no_grad():
+            for k, off, numel in self.layout:
+                flat[off:off + numel].copy_(sd[k].reshape(-1).float())
 
 
 class _EngineDenoiser(torch.autograd.Function):
@@ -200,58 +246,39 @@ class LatteTrainer:
         if self.gradient_accumulation_steps != 1:
             check(lib.latte_trainer_set_option(h, b"loss_divisor", float(self.gradient_accumulation_steps)))
         self.compute_dtype = compute_dtype
-        n = lib.latte_trainer_num_params(h)
-        self.layout = [(lib.latte_trainer_param_key(h, i).decode(), int(lib.latte_trainer_param_offset(h, i)),
-                        int(lib.latte_trainer_param_numel(h, i))) for i in range(n)]
-        total = int(lib.latte_trainer_total_numel(h))
         named = dict(model.named_parameters())
-        want = [k for k in named if k not in FROZEN]
-        if [k for k, _, _ in self.layout] != want:
-            raise LatteError("parameter order of the engine and of the model differ")
-        self.params = torch.zeros(total, device=dev)
         lora = bool(self.lora_rank)
-        self.grads = None if lora else torch.zeros(total, device=dev)
-        self.exp_avg = None if lora else torch.zeros(total, device=dev)
-        self.exp_avg_sq = None if lora else torch.zeros(total, device=dev)
-        self.ema = None if lora else torch.zeros(total, device=dev)
+        # the base -- under LoRA frozen: parameters only, no gradient, moment or EMA buffer -- and the adapters; _trained: the set the
+        # optimiser trains, whose buffers every step, state and collective below is about
+        self._base = _FlatSet(h, "", lambda k: getattr(named.get(k), "shape", ()), dev, ("params",) if lora else _BUFFERS)
+        if [k for k, _, _ in self._base.layout] != [k for k in named if k not in FROZEN]:
+            raise LatteError("parameter order of the engine and of the model differ")
+        self._linear_shapes = {k[:-len(".weight")]: tuple(p.shape) for k, p in named.items() if k.endswith(".weight") and p.dim() == 2}
+        self._adapters = _FlatSet(h, "lora_", self.lora_shape, dev) if lora else None
+        self._trained = self._adapters or self._base
+        # the public names alias the sets' tensors: params / grads / exp_avg / exp_avg_sq / ema / layout, and lora_params ... lora_layout
+        for prefix, fs in [("", self._base)] + ([("lora_", self._adapters)] if lora else []):
+            for name in _BUFFERS + ("layout",):
+                setattr(self, prefix + name, getattr(fs, name))
         with torch.no_grad():
-            for k, off, numel in self.layout:
-                p = named[k]
-                self.params[off:off + numel].copy_(p.detach().reshape(-1).float())
-                p.data = self.params[off:off + numel].view(p.shape)          # the module's parameters are views of the flat buffer
-            if not lora:
-                self.ema.copy_(self.params)                                    # update_ema(ema, model, decay=0), train.py:165
-        if lora:
-            self._linear_shapes = {k[:-len(".weight")]: tuple(p.shape) for k, p in named.items() if k.endswith(".weight") and p.dim() == 2}
-            n = lib.latte_trainer_lora_num_params(h)
-            self.lora_layout = [(lib.latte_trainer_lora_param_key(h, i).decode(), int(lib.latte_trainer_lora_param_offset(h, i)),
-                                 int(lib.latte_trainer_lora_param_numel(h, i))) for i in range(n)]
-            ltotal = int(lib.latte_trainer_lora_total_numel(h))
-            self.lora_params = torch.zeros(ltotal, device=dev)
-            self.lora_grads = torch.zeros(ltotal, device=dev)
-            self.lora_exp_avg = torch.zeros(ltotal, device=dev)
-            self.lora_exp_avg_sq = torch.zeros(ltotal, device=dev)
-            self.lora_ema = torch.zeros(ltotal, device=dev)
-            with torch.no_grad():
-                for k, off, numel in self.lora_layout:
-                    if k.endswith(".lora_A"):                                 # nn.Linear's own init, as peft's LoRA layers; B stays 0
-                        a = torch.empty(self.lora_shape(k))
-                        torch.nn.init.kaiming_uniform_(a, a=math.sqrt(5))
-                        self.lora_params[off:off + numel].copy_(a.reshape(-1))
-                self.lora_ema.copy_(self.lora_params)
+            for k, p in self._base.views("params").items():
+                p.copy_(named[k].detach().float())
+                named[k].data = p                                              # the module's parameters are views of the flat buffer
+            for k, a in self._adapters.views("params").items() if lora else ():
+                if k.endswith(".lora_A"):                                      # nn.Linear's own init, as peft's LoRA layers; B stays 0
+                    a.copy_(torch.nn.init.kaiming_uniform_(torch.empty(a.shape), a=math.sqrt(5)))
+            self._trained.ema.copy_(self._trained.params)                      # update_ema(ema, model, decay=0), train.py:165
         with torch.cuda.device(dev):
             if lora:
-                check(lib.latte_trainer_bind_lora(h, ptr(self.params), ptr(self.lora_params), ptr(self.lora_grads), ptr(self.lora_exp_avg),
-                                                  ptr(self.lora_exp_avg_sq), ptr(self.lora_ema)))
+                check(lib.latte_trainer_bind_lora(h, *self._base.pointers(), *self._adapters.pointers()))
             else:
-                check(lib.latte_trainer_bind(h, ptr(self.params), ptr(self.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(self.ema)))
+                check(lib.latte_trainer_bind(h, *self._base.pointers()))
             check(lib.latte_trainer_set_frozen(h, ptr(named["pos_embed"].detach().float().contiguous()),
                                                ptr(named["temp_embed"].detach().float().contiguous()), 1, stream_ptr()))
             check(lib.latte_trainer_sync_weights(h, stream_ptr()))
         self._norm = torch.zeros(2, device=dev)
         self._anchor = torch.zeros((), device=dev, requires_grad=True)   # makes ``forward``'s output a node of the autograd graph
-        if hasattr(model, "mark_weights_dirty"):
-            model.mark_weights_dirty()
+        self._weights_changed()
 
     def set_option(self, name, value):
         """Engine options of the trainer (latte_trainer_set_option): "loss_scale", "dynamic_loss_scale", "loss_scale_growth_interval",
@@ -273,8 +300,11 @@ class LatteTrainer:
         """{reference key: gradient view} of the last forward_backward."""
         if self.lora_rank:
             raise LatteError("a LoRA trainer has no base gradients: lora_grad_dict()")
-        named = dict(self.model.named_parameters())
-        return {k: self.grads[off:off + numel].view(named[k].shape) for k, off, numel in self.layout}
+        return self._base.views("grads")
+
+    def _weights_changed(self):
+        if hasattr(self.model, "mark_weights_dirty"):
+            self.model.mark_weights_dirty()
 
     # ------------------------------------------------------------------ LoRA
     def lora_shape(self, key):
@@ -286,23 +316,20 @@ class LatteTrainer:
         if not self.lora_rank:
             raise LatteError("this trainer was built without LoRA (lora_rank=0)")
 
-    def _lora_keyed(self, flat):
-        return {k: flat[off:off + numel].view(self.lora_shape(k)).clone() for k, off, numel in self.lora_layout}
-
     def lora_state_dict(self):
         """{``blocks.{i}.attn.qkv.lora_A``: [r, K], ``....lora_B``: [N, r], ...} of the targeted linears: the file a fine-tune ships
         (with ``lora_config()`` beside it)."""
         self._need_lora()
-        return self._lora_keyed(self.lora_params)
+        return self._adapters.keyed("params")
 
     def ema_lora_state_dict(self):
         self._need_lora()
-        return self._lora_keyed(self.lora_ema)
+        return self._adapters.keyed("ema")
 
     def lora_grad_dict(self):
         """{adapter key: gradient view} of the last backward."""
         self._need_lora()
-        return {k: self.lora_grads[off:off + numel].view(self.lora_shape(k)) for k, off, numel in self.lora_layout}
+        return self._adapters.views("grads")
 
     def lora_config(self):
         return {"lora_rank": self.lora_rank, "lora_alpha": self.lora_alpha, "lora_targets": list(self.lora_targets)}
@@ -312,16 +339,8 @@ class LatteTrainer:
         are re-packed."""
         self._need_lora()
         self._not_merged()
-        missing = [k for k, _, _ in self.lora_layout if k not in sd]
-        extra = [k for k in sd if k not in {k for k, _, _ in self.lora_layout}]
-        if missing or extra:
-            raise LatteError(f"load_lora_state_dict: missing keys {missing[:4]}, unexpected keys {extra[:4]} (rank / targets differ?)")
-        with torch.no_grad():
-            for k, off, numel in self.lora_layout:
-                for src, dst in ((sd, self.lora_params), (ema_sd or sd, self.lora_ema)):
-                    if tuple(src[k].shape) != self.lora_shape(k):
-                        raise LatteError(f"load_lora_state_dict: {k} is {list(src[k].shape)}, expected {list(self.lora_shape(k))}")
-                    dst[off:off + numel].copy_(src[k].reshape(-1).float())
+        self._adapters.load("params", sd, "load_lora_state_dict")
+        self._adapters.load("ema", ema_sd or sd, "load_lora_state_dict")
         with torch.cuda.device(self.device):
             check(load_library().latte_trainer_sync_weights(self._h, stream_ptr()))
 
@@ -341,18 +360,14 @@ class LatteTrainer:
         with torch.cuda.device(self.device):
             check(load_library().latte_trainer_lora_merge(self._h, ptr(self.lora_ema) if ema else None, ptr(self.params), stream_ptr()))
         self.lora_merged = True
-        if hasattr(self.model, "mark_weights_dirty"):
-            self.model.mark_weights_dirty()
+        self._weights_changed()
         return self.model
 
     def model_state_dict(self):
         """The ``"model"`` entry of train.py's checkpoints (:257-262), built from the flat fp32 master buffer through the layout --
         not through the module's parameter views: a later ``model.cuda()`` / ``.to()`` / ``.float()`` re-materialises the
         ``nn.Parameter``s and silently ends the aliasing, after which ``model.state_dict()`` would be stale."""
-        sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        for k, off, numel in self.layout:
-            sd[k] = self.params[off:off + numel].view(sd[k].shape).clone()
-        return sd
+        return {**{k: v.detach().clone() for k, v in self.model.state_dict().items()}, **self._base.keyed("params")}
 
     def check_aliasing(self):
         """True while every trained ``nn.Parameter`` of the module still is a view of the flat master buffer."""
@@ -362,19 +377,14 @@ class LatteTrainer:
 
     def ema_state_dict(self):
         """The ``"ema"`` entry of train.py's checkpoints (:257-262): every key of model.state_dict()."""
-        sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        ema = self.params if self.lora_rank else self.ema                       # LoRA: the base is frozen, its average is itself
-        for k, off, numel in self.layout:
-            sd[k] = ema[off:off + numel].view(sd[k].shape).clone()
-        return sd
+        ema = self._base.keyed("params" if self.lora_rank else "ema")            # LoRA: the base is frozen, its average is itself
+        return {**{k: v.detach().clone() for k, v in self.model.state_dict().items()}, **ema}
 
     def load_state_dict(self, sd, ema_sd=None):
         self._not_merged()
-        with torch.no_grad():
-            for k, off, numel in self.layout:
-                self.params[off:off + numel].copy_(sd[k].reshape(-1).float())
-                if not self.lora_rank:
-                    self.ema[off:off + numel].copy_((ema_sd or sd)[k].reshape(-1).float())
+        self._base.load("params", sd)
+        if not self.lora_rank:
+            self._base.load("ema", ema_sd or sd)
         with torch.cuda.device(self.device):
             check(load_library().latte_trainer_sync_weights(self._h, stream_ptr()))
 
@@ -408,7 +418,7 @@ class LatteTrainer:
         self._not_merged()
         d = self.diffusion
         self._builtin_loss_check()
-        x0 = x_start.to(device=self.device, dtype=torch.float32).contiguous()
+        x0, nz, t64 = self._on_device(x_start, noise, t)
         B = x0.shape[0]
         if B > self.max_batch:
             raise LatteError(f"batch {B} exceeds max_batch {self.max_batch}")
@@ -416,10 +426,8 @@ class LatteTrainer:
         if N and (x0.dim() != 5 or x0.shape[1] not in (F, F + N)):
             raise LatteError(f"x_start must be [batch, {F + N} (or {F}: video only), C, H, W], got {list(x0.shape)}")
         joint = N > 0 and x0.shape[1] == F + N
-        nz = noise.to(device=self.device, dtype=torch.float32).contiguous()
         if nz.shape != x0.shape:
             raise AssertionError("noise.shape == x_start.shape")
-        t64 = t.to(device=self.device, dtype=torch.int64).contiguous()
         yy = self._labels(y, drop_mask)
         terms = torch.empty(3, B, device=self.device)
         mo = torch.empty(B, x0.shape[1], self.model.out_channels, x0.shape[3], x0.shape[4], device=self.device) if return_model_out else None
@@ -459,30 +467,41 @@ class LatteTrainer:
 
     def _run_stages(self, reduce):
         """The backward stages behind a begin / seed, in order.  reduce: each stage's finished gradient slice is all-reduced while
-        the next stages run (no-op without a process group) and ``self.grads`` leaves here averaged."""
+        the next stages run (no-op without a process group) and the trained set's ``grads`` leaves here averaged.  Adapters are
+        megabytes of gradients: they take one collective behind the last stage instead (all_reduce_gradients)."""
         lib = load_library()
-        handles = []
-        if self.lora_rank:        # megabytes of adapter gradients: one collective behind the last stage (all_reduce_gradients)
-            for k in range(lib.latte_trainer_num_stages(self._h)):
-                check(lib.latte_trainer_backward_stage(self._h, k, stream_ptr()))
-            if reduce:
-                self.all_reduce_gradients()
-            return
+        grads, per_stage, handles = self._trained.grads, reduce and not self.lora_rank, []
         for k in range(lib.latte_trainer_num_stages(self._h)):
             check(lib.latte_trainer_backward_stage(self._h, k, stream_ptr()))
-            if not reduce:
+            if not per_stage:
                 continue
             off, n = _lib.c_i64(), _lib.c_i64()
             check(lib.latte_trainer_stage_range(self._h, k, off, n))
-            h = average_gradients(self.grads[off.value:off.value + n.value], self.process_group, async_op=True)
+            h = average_gradients(grads[off.value:off.value + n.value], self.process_group, async_op=True)
             if h is not None:
                 handles.append(h)
         for h in handles:
             h.wait()
         if handles:
-            self.grads.div_(_world(self.process_group))
-        if reduce:
+            grads.div_(_world(self.process_group))
+        if per_stage:
             self._reduced = True
+        elif reduce:
+            self.all_reduce_gradients()
+
+    def _on_device(self, x_start, noise, t):
+        """-> x_start and noise as float32, t as int64: on the trainer's device, contiguous"""
+        return (x_start.to(device=self.device, dtype=torch.float32).contiguous(),
+                noise.to(device=self.device, dtype=torch.float32).contiguous(), t.to(device=self.device, dtype=torch.int64).contiguous())
+
+    def _staged(self, last):
+        """A window's last micro-batch takes the staged, all-reducing backward when there is a process group (or the test hook)."""
+        return last and (_world(self.process_group) > 1 or self.always_staged)
+
+    def _end_micro_batch(self, last):
+        self.micro_step += 1
+        if last:
+            self.all_reduce_gradients()
 
     # ------------------------------------------------------------------ custom losses: forward / backward through torch.autograd
     def _labels(self, y, drop_mask):
@@ -558,22 +577,20 @@ class LatteTrainer:
         dx = None
         with torch.cuda.device(self.device):
             check(lib.latte_trainer_seed(self._h, ptr(g), stream_ptr()))
-            self._run_stages(last and (_world(self.process_group) > 1 or self.always_staged))
+            self._run_stages(self._staged(last))
             if want_dx:
                 dx = torch.empty(shape[0], shape[1], self.model.in_channels, shape[3], shape[4], device=self.device)
                 check(lib.latte_trainer_input_grad(self._h, ptr(dx), stream_ptr()))
                 if self.gradient_accumulation_steps != 1:       # the engine's gradients are those of loss / A; x.grad is the loss's own
                     dx.mul_(float(self.gradient_accumulation_steps))
-        self.micro_step += 1
-        if last:
-            self.all_reduce_gradients()
+        self._end_micro_batch(last)
         return dx
 
     def all_reduce_gradients(self):
         """DDP's gradient averaging (train.py:125) as ONE collective over the flat gradient buffer: RCCL over xGMI when the
         process group's backend is nccl, gloo in the CPU tests."""
         if not getattr(self, "_reduced", False):
-            average_gradients(self.lora_grads if self.lora_rank else self.grads, self.process_group)
+            average_gradients(self._trained.grads, self.process_group)
             self._reduced = True
 
     def _set_accumulate(self, on):
@@ -597,9 +614,7 @@ class LatteTrainer:
             if y_image is not None or (torch.is_tensor(x_start) and x_start.dim() == 5 and x_start.shape[1] != self.model.num_frames):
                 raise LatteError("custom losses take video micro-batches of num_frames frames: no joint image-video pass")
             d = self.diffusion
-            x0 = x_start.to(device=self.device, dtype=torch.float32).contiguous()
-            t64 = t.to(device=self.device, dtype=torch.int64).contiguous()
-            nz = noise.to(device=self.device, dtype=torch.float32).contiguous()
+            x0, nz, t64 = self._on_device(x_start, noise, t)
             x_t = d.q_sample(x0, t64, nz)
             t_model = torch.tensor(d.timestep_map, device=self.device, dtype=torch.int64)[t64]
             with torch.enable_grad():
@@ -613,12 +628,9 @@ class LatteTrainer:
                 raise LatteError("loss_fn's result does not depend on model_out")
             return {"loss": per_sample.detach()}, last
         self._set_accumulate(self.micro_step > 0)
-        out = self.forward_backward(x_start, t, noise, y, drop_mask,
-                                    overlap_all_reduce=last and (_world(self.process_group) > 1 or self.always_staged),
-                                    y_image=y_image, image_drop_mask=image_drop_mask)
-        self.micro_step += 1
-        if last:
-            self.all_reduce_gradients()
+        out = self.forward_backward(x_start, t, noise, y, drop_mask, overlap_all_reduce=self._staged(last), y_image=y_image,
+                                    image_drop_mask=image_drop_mask)
+        self._end_micro_batch(last)
         return out, last
 
     def optimizer_step(self):
@@ -633,50 +645,43 @@ class LatteTrainer:
             check(load_library().latte_trainer_optimizer_step(self._h, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
                                                               0, self.clip_max_norm, clip, self.ema_decay,
                                                               ptr(self._norm), stream_ptr()))
-        if hasattr(self.model, "mark_weights_dirty"):
-            self.model.mark_weights_dirty()
+        self._weights_changed()
         return self._norm[0]
 
     def scaler_state(self):
         """Loss-scaling / update counters of the engine (synchronises): dict(loss_scale, good_steps, applied_updates,
         skipped_updates, last_skipped, dynamic, growth_interval, max_scale)."""
-        import ctypes
         out = (ctypes.c_double * 8)()
         check(load_library().latte_trainer_scaler_state(self._h, out))
-        keys = ("loss_scale", "good_steps", "applied_updates", "skipped_updates", "last_skipped", "dynamic", "growth_interval", "max_scale")
-        return dict(zip(keys, [float(v) for v in out]))
+        return dict(zip(SCALER_KEYS, [float(v) for v in out]))
 
     def set_scaler_state(self, state):
         """Puts the eight values of ``scaler_state()`` back (latte_trainer_set_scaler_state)."""
-        import ctypes
-        keys = ("loss_scale", "good_steps", "applied_updates", "skipped_updates", "last_skipped", "dynamic", "growth_interval", "max_scale")
-        check(load_library().latte_trainer_set_scaler_state(self._h, (ctypes.c_double * 8)(*[float(state[k]) for k in keys])))
+        check(load_library().latte_trainer_set_scaler_state(self._h, (ctypes.c_double * 8)(*[float(state[k]) for k in SCALER_KEYS])))
 
     # ------------------------------------------------------------------ the whole state of a run
-    def _keyed(self, flat):
-        named = dict(self.model.named_parameters())
-        return {k: flat[off:off + numel].view(named[k].shape).clone() for k, off, numel in self.layout}
+    def _state_slots(self, state):
+        """Where the trained set's entries live in a ``training_state()`` dict: -> (the dict of the moments ``exp_avg`` /
+        ``exp_avg_sq``, the dict of the partial gradient buffer ``grads``)."""
+        return (state["lora"], state["lora"]) if self.lora_rank else (state["opt"], state)
 
     def training_state(self):
         """Everything a run continues from: ``model`` / ``ema`` (the reference's checkpoint entries, train.py:257-262), ``opt``
         (AdamW's ``exp_avg`` / ``exp_avg_sq``, state-dict keyed), ``scaler`` (the eight counters), ``train_steps``, ``micro_step``
-        and, inside a window (``micro_step != 0``), the partial gradient buffer ``grads``."""
+        and, inside a window (``micro_step != 0``), the partial gradient buffer ``grads``.  A LoRA trainer: the frozen base once as
+        ``model`` (its EMA is itself, it has no moments), and under ``lora`` everything of the adapters -- ``config``, ``params``,
+        ``ema``, the moments and the partial gradients."""
+        st = {"model": self.model_state_dict()}
         if self.lora_rank:
-            # the frozen base once (its EMA is itself, it has no moments), then everything of the adapters
-            st = {"model": self.model_state_dict(),
-                  "lora": {"config": self.lora_config(), "params": self.lora_state_dict(), "ema": self.ema_lora_state_dict(),
-                           "exp_avg": self._lora_keyed(self.lora_exp_avg), "exp_avg_sq": self._lora_keyed(self.lora_exp_avg_sq)},
-                  "scaler": self.scaler_state(), "train_steps": int(self.train_steps), "micro_step": int(self.micro_step),
-                  "gradient_accumulation_steps": int(self.gradient_accumulation_steps)}
-            if self.micro_step:
-                st["lora"]["grads"] = self._lora_keyed(self.lora_grads)
-            return st
-        st = {"model": self.model_state_dict(), "ema": self.ema_state_dict(),
-              "opt": {"exp_avg": self._keyed(self.exp_avg), "exp_avg_sq": self._keyed(self.exp_avg_sq)},
-              "scaler": self.scaler_state(), "train_steps": int(self.train_steps), "micro_step": int(self.micro_step),
-              "gradient_accumulation_steps": int(self.gradient_accumulation_steps)}
+            st["lora"] = {"config": self.lora_config(), "params": self.lora_state_dict(), "ema": self.ema_lora_state_dict()}
+        else:
+            st["ema"], st["opt"] = self.ema_state_dict(), {}
+        st.update(scaler=self.scaler_state(), train_steps=int(self.train_steps), micro_step=int(self.micro_step),
+                  gradient_accumulation_steps=int(self.gradient_accumulation_steps))
+        moments, partial = self._state_slots(st)
+        moments.update(exp_avg=self._trained.keyed("exp_avg"), exp_avg_sq=self._trained.keyed("exp_avg_sq"))
         if self.micro_step:
-            st["grads"] = self._keyed(self.grads)
+            partial["grads"] = self._trained.keyed("grads")
         return st
 
     def load_training_state(self, state):
@@ -686,43 +691,25 @@ class LatteTrainer:
             raise LatteError("the state was saved inside an accumulation window of another gradient_accumulation_steps")
         if bool(self.lora_rank) != ("lora" in state):
             raise LatteError("the state and the trainer disagree on LoRA")
-        if self.lora_rank:
-            lo = state["lora"]
-            if lo["config"] != self.lora_config():
-                raise LatteError(f"the state's adapters are {lo['config']}, the trainer's {self.lora_config()}")
-            if micro and "grads" not in lo:
-                raise LatteError("the state was saved inside an accumulation window but holds no gradients")
-            with torch.no_grad():
-                for k, off, numel in self.lora_layout:
-                    self.lora_exp_avg[off:off + numel].copy_(lo["exp_avg"][k].reshape(-1).float())
-                    self.lora_exp_avg_sq[off:off + numel].copy_(lo["exp_avg_sq"][k].reshape(-1).float())
-                    if micro:
-                        self.lora_grads[off:off + numel].copy_(lo["grads"][k].reshape(-1).float())
-                if not micro:
-                    self.lora_grads.zero_()
-                for k, off, numel in self.layout:
-                    self.params[off:off + numel].copy_(state["model"][k].reshape(-1).float())
-            self.load_lora_state_dict(lo["params"], lo["ema"])           # (syncs the merged operand copies)
-            self.set_scaler_state(state["scaler"])
-            self.train_steps, self.micro_step = int(state["train_steps"]), micro
-            if hasattr(self.model, "mark_weights_dirty"):
-                self.model.mark_weights_dirty()
-            return
-        if micro and "grads" not in state:
+        if self.lora_rank and state["lora"]["config"] != self.lora_config():
+            raise LatteError(f"the state's adapters are {state['lora']['config']}, the trainer's {self.lora_config()}")
+        moments, partial = self._state_slots(state)
+        if micro and "grads" not in partial:
             raise LatteError("the state was saved inside an accumulation window but holds no gradients")
-        with torch.no_grad():
-            for k, off, numel in self.layout:
-                self.exp_avg[off:off + numel].copy_(state["opt"]["exp_avg"][k].reshape(-1).float())
-                self.exp_avg_sq[off:off + numel].copy_(state["opt"]["exp_avg_sq"][k].reshape(-1).float())
-                if micro:
-                    self.grads[off:off + numel].copy_(state["grads"][k].reshape(-1).float())
-            if not micro:
-                self.grads.zero_()
-        self.load_state_dict(state["model"], state["ema"])
+        self._trained.load("exp_avg", moments["exp_avg"])
+        self._trained.load("exp_avg_sq", moments["exp_avg_sq"])
+        if micro:
+            self._trained.load("grads", partial["grads"])
+        else:
+            self._trained.grads.zero_()
+        if self.lora_rank:                                                 # (both branches sync the packed operand copies)
+            self._base.load("params", state["model"])
+            self.load_lora_state_dict(state["lora"]["params"], state["lora"]["ema"])
+        else:
+            self.load_state_dict(state["model"], state["ema"])
         self.set_scaler_state(state["scaler"])
         self.train_steps, self.micro_step = int(state["train_steps"]), micro
-        if hasattr(self.model, "mark_weights_dirty"):
-            self.model.mark_weights_dirty()
+        self._weights_changed()
 
     def train_step(self, x_start, y=None, t=None, noise=None, drop_mask=None, y_image=None, image_drop_mask=None, loss_fn=None):
         """train.py:197-236 for one micro-batch; the optimiser step runs after the ``gradient_accumulation_steps``-th of a window

@@ -62,6 +62,35 @@ def latest_lora_checkpoint(ckpt_dir):
     return os.path.join(ckpt_dir, max(found)[1]) if found else None
 
 
+def _cpu(d):
+    return {k: v.cpu() for k, v in d.items()}
+
+
+def split_run_state(trainer_state, lora):
+    """``LatteTrainer.training_state()`` as a run directory holds it -> (checkpoint file name suffix, checkpoint payload, state-file
+    payload).  The checkpoint is the file to ship: ``<step>.pt`` = the reference's {model, ema}, or with ``lora`` ``<step>.lora.pt`` =
+    {config, lora, lora_ema} (the frozen base stays the `pretrained:` file).  The state file takes the rest: the AdamW moments (``opt``,
+    or ``lora_opt``) and the counters; main() adds the random state."""
+    st = trainer_state
+    if lora:
+        lo = st["lora"]
+        rest = {k: v for k, v in st.items() if k not in ("model", "lora")}
+        rest["lora_opt"] = {m: _cpu(lo[m]) for m in ("exp_avg", "exp_avg_sq")}
+        return ".lora.pt", {"config": lo["config"], "lora": _cpu(lo["params"]), "lora_ema": _cpu(lo["ema"])}, rest
+    rest = {k: v for k, v in st.items() if k not in ("model", "ema", "opt")}
+    rest["opt"] = {m: _cpu(st["opt"][m]) for m in st["opt"]}
+    return ".pt", {"model": _cpu(st["model"]), "ema": _cpu(st["ema"])}, rest
+
+
+def join_run_state(checkpoint, state, lora, base_model=None):
+    """The inverse of ``split_run_state``: the two payloads as read back -> what ``LatteTrainer.load_training_state`` takes.
+    base_model: with ``lora`` the frozen base's state dict, which the run directory does not hold."""
+    if lora:
+        return {**{k: v for k, v in state.items() if k not in ("rng", "lora_opt")}, "model": base_model,
+                "lora": {"config": checkpoint["config"], "params": checkpoint["lora"], "ema": checkpoint["lora_ema"], **state["lora_opt"]}}
+    return {**state, "model": checkpoint["model"], "ema": checkpoint["ema"]}
+
+
 def clip_label(path):
     name = os.path.basename(path)
     return int(name.split("_")[0]) if name.split("_")[0].isdigit() else 0
@@ -236,42 +265,29 @@ def main():
     if args.get("resume_from_checkpoint"):
         # train.py:176-192: the highest-numbered checkpoint of THIS run's results_dir -- with the state file beside it the whole run
         # comes back: parameters, EMA, AdamW moments, bias-correction count, loss scale and its growth count, step, random streams
+        # (LoRA: the adapters, their EMA, their moments and the counters; the frozen base came from `pretrained:`)
         ck = (latest_lora_checkpoint if lora_rank else latest_checkpoint)(os.path.join(out_dir, "checkpoints"))
-        if ck is not None and lora_rank:
-            # the adapters, their EMA and (state file) their moments and the counters; the frozen base came from `pretrained:`
-            sp = state_path(ck[:-len(".lora.pt")] + ".pt")
-            if not os.path.isfile(sp):
-                raise SystemExit(f"resume_from_checkpoint: {ck} has no {os.path.basename(sp)} beside it")
-            ad, rest = torch.load(ck, map_location="cpu"), torch.load(sp, map_location="cpu")
-            trainer.load_training_state({**{k: v for k, v in rest.items() if k not in ("rng", "lora_opt")}, "model": trainer.model_state_dict(),
-                                         "lora": {"config": ad["config"], "params": ad["lora"], "ema": ad["lora_ema"], **rest["lora_opt"]}})
-            first_step = int(rest["train_steps"])
-            rp = state_path(ck[:-len(".lora.pt")] + ".pt", rank)
-            mine = rest if rank == 0 else (torch.load(rp, map_location="cpu") if os.path.isfile(rp) else None)
-            if mine is not None:
-                set_rng_state(mine["rng"], device)
-            if rank == 0:
-                print(f"Resumed from {ck}: step {first_step}", flush=True)
-        elif ck is None:
+        if ck is None:
             if rank == 0:
                 print(f"resume_from_checkpoint: no checkpoint under {out_dir}/checkpoints yet, starting a new run", flush=True)
         else:
-            if not os.path.isfile(state_path(ck)):
-                raise SystemExit(f"resume_from_checkpoint: {ck} has no {os.path.basename(state_path(ck))} beside it (written by an older "
-                                 "version?); continue from its weights alone with `pretrained:`")
-            both = torch.load(ck, map_location="cpu")
-            rest = torch.load(state_path(ck), map_location="cpu")
-            trainer.load_training_state({**rest, "model": both["model"], "ema": both["ema"]})
+            base_pt = ck[:-len(".lora.pt")] + ".pt" if lora_rank else ck          # the state files are named after <step>.pt
+            if not os.path.isfile(state_path(base_pt)):
+                raise SystemExit(f"resume_from_checkpoint: {ck} has no {os.path.basename(state_path(base_pt))} beside it"
+                                 + ("" if lora_rank else " (written by an older version?); continue from its weights alone with `pretrained:`"))
+            rest = torch.load(state_path(base_pt), map_location="cpu")
+            trainer.load_training_state(join_run_state(torch.load(ck, map_location="cpu"), rest, lora_rank,
+                                                       trainer.model_state_dict() if lora_rank else None))
             first_step = int(rest["train_steps"])
-            if checkpoint_step(ck) != first_step:
+            if not lora_rank and checkpoint_step(ck) != first_step:
                 raise SystemExit(f"resume_from_checkpoint: {ck} holds the state of step {first_step}")
-            mine = rest if rank == 0 else (torch.load(state_path(ck, rank), map_location="cpu") if os.path.isfile(state_path(ck, rank)) else None)
+            mine = rest if rank == 0 else (torch.load(state_path(base_pt, rank), map_location="cpu") if os.path.isfile(state_path(base_pt, rank)) else None)
             if mine is not None:
                 set_rng_state(mine["rng"], device)
             sc = trainer.scaler_state()
             if rank == 0:
-                print(f"Resumed from {ck}: step {first_step}, loss scale {sc['loss_scale']:g}, applied updates {int(sc['applied_updates'])}, "
-                      f"skipped updates {int(sc['skipped_updates'])}", flush=True)
+                print(f"Resumed from {ck}: step {first_step}" + ("" if lora_rank else f", loss scale {sc['loss_scale']:g}, applied updates "
+                      f"{int(sc['applied_updates'])}, skipped updates {int(sc['skipped_updates'])}"), flush=True)
     raw = args.get("frame_interval") not in (None, "") and args.get("data_path") not in (None, "", "synthetic")
     if raw:                                                   # raw clips through the dataset's frame pipeline (datasets/__init__.py:13-76)
         from latte_amd import video_transforms
@@ -354,21 +370,11 @@ def main():
             # every rank its random state, rank 0 also the AdamW moments and the counters
             path = os.path.join(out_dir, "checkpoints", f"{step:07d}.pt")
             mine = {"rng": rng_state(device), "train_steps": step}
-            if rank == 0 and lora_rank:
-                st = trainer.training_state()
-                lo_ = st["lora"]
-                cpu = lambda d: {k: v.cpu() for k, v in d.items()}
-                lpath = path[:-len(".pt")] + ".lora.pt"
-                torch.save({"config": lo_["config"], "lora": cpu(lo_["params"]), "lora_ema": cpu(lo_["ema"])}, lpath)
-                print(f"Saved checkpoint to {lpath}", flush=True)
-                mine.update({k: v for k, v in st.items() if k not in ("model", "lora")})
-                mine["lora_opt"] = {m: cpu(lo_[m]) for m in ("exp_avg", "exp_avg_sq")}
-            elif rank == 0:
-                st = trainer.training_state()
-                torch.save({"model": {k: v.cpu() for k, v in st["model"].items()}, "ema": {k: v.cpu() for k, v in st["ema"].items()}}, path)
-                print(f"Saved checkpoint to {path}", flush=True)
-                mine.update({k: v for k, v in st.items() if k not in ("model", "ema", "opt")})
-                mine["opt"] = {m: {k: v.cpu() for k, v in st["opt"][m].items()} for m in st["opt"]}
+            if rank == 0:
+                suffix, payload, rest = split_run_state(trainer.training_state(), lora_rank)
+                torch.save(payload, path[:-len(".pt")] + suffix)
+                print(f"Saved checkpoint to {path[:-len('.pt')] + suffix}", flush=True)
+                mine.update(rest)
             torch.save(mine, state_path(path, rank))
             parallel.barrier()
     if world > 1:

@@ -21,6 +21,10 @@ Cases:
   J, a joint micro-batch, both fuse_small
   A, the custom path (forward, a caller's seed, the stages, latte_trainer_input_grad), both fuse_small
   A, the staged path (begin + stages, every latte_trainer_stage_range recorded), both fuse_small
+  A with LoRA adapters (rank 8, B seeded nonzero so that A receives a gradient on the first step), both fuse_small: all four targets on
+     the built-in step, two accumulated micro-batches, the staged path and the custom path; targets qkv,fc2 on the built-in step.  These
+     hash the ADAPTER buffers where the other cases hash the base's, and the base parameter buffer, which must not move
+  A, plain and LoRA: ``training_state()`` after one optimiser step and one micro-batch of the next window, keys walked in sorted order
 Every case hashes the loss terms, the model output copy and the flat gradient buffer; then, after optimizer_step, the parameters, both
 moments, the EMA and the eight scaler fields; then the gradient buffer of a second forward_backward (the re-packed weights).
 The label-table gradient is a scatter with atomic adds: labels and drop masks are chosen so that no table row, the null class
@@ -177,6 +181,79 @@ def custom(kw, sd, inp, fuse_small):
     return after_step(tr, rec, run)
 
 
+def seeded_adapters(tr, seed=41):
+    """A ~ U(+-1 / sqrt(K)) and a NONZERO B ~ N(0, 0.02) from a fixed seed, in the trainer's table order"""
+    g = torch.Generator("cpu").manual_seed(seed)
+    return {k: (torch.rand(v.shape, generator=g) * 2 - 1) * v.shape[1] ** -0.5 if k.endswith(".lora_A") else
+            torch.randn(v.shape, generator=g) * 0.02 for k, v in tr.lora_state_dict().items()}
+
+
+def lora(kw, sd, inp, fuse_small, path, targets="qkv,proj,fc1,fc2"):
+    """path: "step" (forward_backward), "accumulate2", "staged" or "custom" -- the plain cases' paths on a rank-8 LoRA trainer"""
+    x0, noise, t, y, drop = inp
+    tr = make_trainer(kw, sd, x0.shape[0], "f16", fuse_small, lora_rank=8, lora_alpha=16.0, lora_targets=targets,
+                      gradient_accumulation_steps=2 if path == "accumulate2" else 1)
+    tr.load_lora_state_dict(seeded_adapters(tr))
+    rec = {}
+    if path == "staged":
+        lib = load_library()
+        rec["stage_ranges"] = []
+        for k in range(lib.latte_trainer_num_stages(tr._h)):
+            off, n = _lib.c_i64(), _lib.c_i64()
+            check(lib.latte_trainer_stage_range(tr._h, k, off, n))
+            rec["stage_ranges"].append([off.value, n.value])
+
+    def run(tag=""):
+        if path == "custom":
+            x = x0.cuda().requires_grad_(True)
+            out = tr.forward(x, t, y, drop)
+            out.backward((torch.randn(out.shape, generator=torch.Generator("cpu").manual_seed(5)) * 1e-4).cuda())
+            return {"loss": x.grad, "model_out": out}
+        if path == "accumulate2":
+            out, last = tr.backward_micro_batch(x0, t, noise, y, drop)
+            assert not last
+            terms(out, rec, "::micro1" + tag)
+            rec["lora_grads::micro1" + tag] = sha(tr.lora_grads)
+            out, last = tr.backward_micro_batch(x0.flip(0), t.flip(0), noise.flip(0), torch.tensor([0, 3, 2]), None)
+            assert last
+            return out
+        return tr.forward_backward(x0, t, noise, y, drop, return_model_out=True, overlap_all_reduce=path == "staged")
+    terms(run(), rec)
+    rec["lora_grads"] = sha(tr.lora_grads)
+    rec["grad_norm"] = sha(tr.optimizer_step())
+    rec.update(lora_params=sha(tr.lora_params), lora_exp_avg=sha(tr.lora_exp_avg), lora_exp_avg_sq=sha(tr.lora_exp_avg_sq),
+               lora_ema=sha(tr.lora_ema), params=sha(tr.params))
+    rec["scaler"] = [float(v).hex() for v in tr.scaler_state().values()]
+    out = run("::window2")
+    rec.update(lora_grads_2=sha(tr.lora_grads), loss_2=sha(out["loss"]))
+    return rec
+
+
+def state_sha(kw, sd, inp, lora_rank):
+    """sha256 over ``training_state()`` inside the second window of two micro-batches: keys in sorted order, tensors by their bytes"""
+    x0, noise, t, y, drop = inp
+    tkw = dict(lora_rank=lora_rank, lora_alpha=16.0) if lora_rank else {}
+    tr = make_trainer(kw, sd, x0.shape[0], "f16", 1, gradient_accumulation_steps=2, **tkw)
+    if lora_rank:
+        tr.load_lora_state_dict(seeded_adapters(tr))
+    for _ in range(3):
+        tr.train_step(x0, y=y, t=t, noise=noise, drop_mask=drop)
+    torch.cuda.synchronize()
+    h, keys = hashlib.sha256(), []
+
+    def walk(v, path):
+        if isinstance(v, dict):
+            for k in sorted(v):
+                walk(v[k], path + "/" + str(k))
+            return
+        keys.append(path)
+        h.update(path.encode())
+        h.update(v.detach().cpu().contiguous().numpy().tobytes() if torch.is_tensor(v) else
+                 (float(v).hex() if isinstance(v, float) else repr(v)).encode())
+    walk(tr.training_state(), "")
+    return {"training_state": h.hexdigest(), "entries": len(keys), "top": sorted({k.split("/")[1] for k in keys})}
+
+
 def cases():
     """name -> thunk"""
     c = {}
@@ -201,6 +278,11 @@ def cases():
         c[f"J::joint::fuse_small{fs}"] = lambda f=fs: joint(f)
         c[f"A::custom::fuse_small{fs}"] = lambda f=fs: custom(*inputs_a(3, 31), f)
         c[f"A::staged::fuse_small{fs}"] = lambda f=fs: plain(*inputs_a(3, 31), "f16", f, staged=True)
+        for path in ("step", "accumulate2", "staged", "custom"):
+            c[f"A::lora8::{path}::fuse_small{fs}"] = lambda f=fs, p=path: lora(*inputs_a(3, 31), f, p)
+        c[f"A::lora8::qkv,fc2::step::fuse_small{fs}"] = lambda f=fs: lora(*inputs_a(3, 31), f, "step", "qkv,fc2")
+    c["A::training_state::plain"] = lambda: state_sha(*inputs_a(3, 31), 0)
+    c["A::training_state::lora8"] = lambda: state_sha(*inputs_a(3, 31), 8)
     return c
 
 
