@@ -183,6 +183,12 @@ struct AttnArgs {
   int Lk, q_ld;
   unsigned char* out8;    // f16 only, may be nullptr: [rows, D] bytes receive the fp8 remainder of the output (mfma_util.h: split8_f16)
 };
+// the sequence layout of a block's attention (forward and backward): spatial blocks attend inside a frame (B F sequences of T
+// contiguous rows), temporal ones across the F frames of a token (rows T apart)
+inline void seq_layout(AttnArgs& a, bool spatial, int B, int F, int T) {
+  if (spatial) { a.num_seq = B * F; a.L = T; a.U = F; a.seq_stride = T; a.row_stride = 1; }
+  else         { a.num_seq = B * T; a.L = F; a.U = T; a.seq_stride = 1; a.row_stride = T; }
+}
 int launch_attention(const AttnArgs& a, int dtype, hipStream_t st);
 int launch_cross_attention(const AttnArgs& a, int dtype, hipStream_t st);
 
@@ -237,7 +243,7 @@ int launch_cond_rows(const float* temb, const float* ytab, const int64_t* y, flo
 int launch_text_proj(const float* text, const float* W, const float* bias, float* out, int B, int N, int K, hipStream_t st);
 int launch_iota(int64_t* p, int n, hipStream_t st);
 // x[M, N] += gate[m / rows_per_sample, :] * (sum of `splits` fp32 partial products (slab stride `stride`) + bias): the reduction
-// of a split-K gated GEMM (engine.cpp: gated_gemm)
+// of a split-K gated GEMM (block.cpp: gated_gemm)
 int launch_gated_split_reduce(float* x, const float* ws, int splits, size_t stride, const float* bias, const float* gate,
                               int gate_stride, int rows_per_sample, int M, int N, hipStream_t st);
 int launch_silu_rows(const float* in, float* out, size_t n, hipStream_t st);   // out = SiLU(in), may alias

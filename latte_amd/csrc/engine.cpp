@@ -16,7 +16,7 @@
 #include <string>
 #include <vector>
 
-#include "event_profile.h"
+#include "block.h"
 #include "plan.h"
 #include "weight_store.h"
 
@@ -49,14 +49,6 @@ int fail(int code, const std::string& msg) {
 
 enum PackKind { PK_F32, PK_F32_TRANSPOSE, PK_H16 };   // WeightSlot::kind; PK_F32_TRANSPOSE: source [rows][cols]
 
-struct BlockW {
-  half_t *qkv_w, *proj_w, *fc1_w, *fc2_w;
-  float *qkv_b, *proj_b, *fc1_b, *fc2_b;
-  half_t *proj_w2 = nullptr, *fc1_w2 = nullptr;   // [N, 2 K] = [W | W]: the weight of a split-operand linear (guided_split bits 0 / 1), built lazily
-  unsigned char *fc1_w4 = nullptr, *fc1_w4s = nullptr;    // fp4 image of fc1's weight + its row scales (guided_split bit 4; GemmArgs::W4 / W4s)
-  unsigned char *proj_w8 = nullptr, *fc1_w8 = nullptr;   // [N, K] e4m3(W 2^LO8_W_SHIFT): the weight of a GEMM's fp8 correction pass (bits 2 / 3)
-};
-
 }  // namespace latte
 
 using namespace latte;
@@ -72,7 +64,7 @@ struct latte_engine {
   int fuse_qkv_attn = 3;                   // bit 0: spatial blocks, bit 1: temporal blocks run qkv projection + attention as ONE kernel
                                            // (qkv_attn.hip) wherever the shape allows it (T == 256 / F == 16); 0 = the un-fused pair;
                                            // bits 2, 3: QkvAttnArgs::flags (schedule variants, same results)
-  int gated_split_k = 0;                   // gated GEMMs of small batches: 0 = rule of gated_gemm, 1 = never split, 2..4 = force
+  int gated_split_k = 0;                   // gated GEMMs of small batches: 0 = rule of gated_gemm (block.cpp), 1 = never split, 2..4 = force
   int gated_rmw_shape = GATED_RMW_SHAPE_DEFAULT;   // GemmArgs::rmw_mode of the out-projection and fc2: 0 = fragment-wise, 1 = line-wise residual accesses
   int stream_policy = STREAM_POLICY_DEFAULT;       // StreamPolicy bits: which once-used streams of a block are issued `nt` (unguided forward)
   bool stream_policy_set = false;                  // set through the option: applies at every batch, not only where the streams overflow the cache
@@ -102,7 +94,7 @@ struct latte_engine {
   unsigned char* lo8 = nullptr;            // [rows_pad, D] bytes: the fp8 remainder of the attention output, then of fc1's operand
   unsigned char *lo4 = nullptr, *lo4s = nullptr;   // [rows_pad, lo4_pitch(D)] e2m1 codes + [rows_pad] row scales: the fp4 remainder of fc1's operand (bit 4)
   float *split_ws = nullptr, *zero_bias = nullptr;   // partial products of the split gated GEMMs, a zero bias row for them
-  std::vector<BlockW> blocks;
+  std::vector<BlockLinears> blocks;
   float *ada_w = nullptr, *ada_b = nullptr, *pos = nullptr, *temp = nullptr, *pe_wt = nullptr, *pe_b = nullptr,
         *t0_w = nullptr, *t0_b = nullptr, *t2_w = nullptr, *t2_b = nullptr, *ytab = nullptr, *fin_wt = nullptr,
         *fin_b = nullptr;
@@ -138,56 +130,6 @@ struct latte_engine {
 };
 
 namespace {
-
-struct Timer {  // optional per-launch HIP events (latte_profile_forward)
-  EventProfile* p;
-  hipStream_t st;
-  void mark(int cls) {
-    if (p) p->mark(cls, st);
-  }
-};
-enum { C_QKV = 0, C_PROJ, C_FC1, C_FC2, C_ATTN_S, C_ATTN_T, C_LN, C_COND, C_PATCH, C_FINAL, C_QKVATTN_S, C_QKVATTN_T, C_NONE = -1 };
-
-// Gated read-modify-write GEMM x += gate * (A W^T + bias) (attention out-projection, fc2; latte.py:179-180).  At small batches
-// its 256 x 192 output tiles fill a fraction of the 256 CUs (B = 1 at XL/2: 96 tiles, fc2 78 us per launch against 33 us at the
-// B = 8 rate): when at least two splits of a DEEP contraction fit on the chip, the GEMM runs as `s` partial products (tile
-// variant 5, grid.y = s, fp32 slabs in split_ws) and gated_split_reduce adds them to the residual stream in slab order.
-// Measured inside the XL/2 forward at B = 1 (same box): fc2 (K = 4608) 77.6 -> 68.2 us including the reduction, the out-projection
-// (K = 1152) 30.6 -> 39.0 us -- the reduction pass costs more than half of a 18-K-tile GEMM, hence the >= 32 K tiles per split.
-// (A stream-K decomposition of the 12-wave kernel with in-launch hand-over of the partial products was built and measured
-// slower than this at every small-batch shape: DESIGN.md section 8.)
-constexpr int64_t SPLIT_WS_FLOATS = 256ll * 256 * 192;   // s * tiles <= 256 tiles of 256 x 192
-int gated_split_choice(const latte_engine* e, int M, int N, int K, int variant) {
-  if (variant != 0 || e->gated_split_k == 1 || N % 192 || K % 64) return 1;
-  if (e->gated_split_k == 0 && gemm_small_tile_ok(M, N, K)) return 1;   // one 128 x 144 tile per CU beats the split (launch_gemm)
-  const int tiles = ((M + 255) / 256) * (N / 192), nk = K / 64;
-  if (e->gated_split_k >= 2) {
-    const int s = e->gated_split_k;
-    return (nk % s == 0 && (int64_t)s * M * N <= SPLIT_WS_FLOATS) ? s : 1;
-  }
-  for (int s = 4; s >= 2; --s)
-    if (tiles * s <= 256 && nk % s == 0 && nk / s >= 32 && (int64_t)s * M * N <= SPLIT_WS_FLOATS) return s;
-  return 1;
-}
-// the gated GEMM of this shape runs on the rolling 12-wave kernel, whose epilogue can add the temporal embedding (GemmArgs::te)
-bool gated_gemm_takes_te(const latte_engine* e, int M, int N, int K, int variant) {
-  if (gated_split_choice(e, M, N, K, variant) != 1) return false;
-  return (variant ? variant : gemm_resolve_variant(M, N, K, EPI_GATE_RES_F32)) == 11;
-}
-int gated_gemm(latte_engine* e, const GemmArgs& g, int dt, int variant, hipStream_t st) {
-  if (g.A8) return launch_gemm(g, EPI_GATE_RES_F32, dt, 0, st);   // fp8 correction pass: the rolling 12-wave kernel carries it
-  const int s = gated_split_choice(e, g.M, g.N, g.K, variant);
-  if (s == 1) return launch_gemm(g, EPI_GATE_RES_F32, dt, variant, st);
-  GemmArgs p = g;
-  p.bias = e->zero_bias;
-  p.gate = nullptr;
-  p.out = e->split_ws;
-  p.k_chunk = g.K / s;
-  p.split_stride = (long)g.M * g.N;
-  if (int rc = launch_gemm(p, EPI_BIAS_F32, dt, 5, st)) return rc;
-  return launch_gated_split_reduce((float*)g.out, e->split_ws, s, (size_t)g.M * g.N, g.bias, g.gate, g.gate_stride,
-                                   g.rows_per_sample, g.M, g.N, st);
-}
 
 // Derived weights / operand buffers of the split operands of a guided call, for the bits of `need` only (guided_split), each pointer
 // guarded on its own.  An allocation failure does not fail the forward: it is reported once on stderr, `split_failed` is set and this
@@ -300,85 +242,31 @@ int run_forward(latte_engine* e, const float* x, const int64_t* t, const int64_t
   // hidden stream that fits (B <= 4) is served from the cache when fc2 reads it back, and a hint would take that away.
   const bool streams_overflow = (int64_t)M * (2 * e->Hm + 4 * D) > (256ll << 20);
   const int stream_policy = gsplit ? 0 : (e->stream_policy_set || streams_overflow) ? e->stream_policy : 0;
-  int gactive = gsplit & 26;   // bits 1 / 3 / 4 always apply; bits 0 / 2 once a fused attention kernel has produced the pair
-
+  BlockCtx bc{};
+  bc.B = B; bc.F = F; bc.T = T; bc.D = D; bc.heads = c.num_heads; bc.hd = e->hd; bc.Hm = e->Hm; bc.dt = dt;
+  bc.xres = e->xres; bc.xn = e->xn; bc.qkv = e->qkv; bc.hbuf = e->hbuf;
+  bc.mod_stride = mstride;
+  bc.fuse_qkv_attn = e->fuse_qkv_attn;
+  for (int k = 0; k < 4; ++k) bc.gemm_variant_of[k] = e->gemm_variant_of[k] ? e->gemm_variant_of[k] : e->gemm_variant;
+  bc.gated_split_k = e->gated_split_k; bc.rmw_mode = e->gated_rmw_shape; bc.stream_policy = stream_policy;
+  bc.split_ws = e->split_ws; bc.zero_bias = e->zero_bias;
+  bc.gsplit = gsplit; bc.xn2 = e->xn2; bc.lo8 = e->lo8; bc.lo4 = e->lo4; bc.lo4s = e->lo4s;
+  bc.guided_split_active = gsplit & 26;   // bits 1 / 3 / 4 always apply; bits 0 / 2 once an attention kernel has produced the pair
+  bc.prof = prof;
+  // x + temp_embed once, after the first spatial block (latte.py:357-358): in that block's fc2 epilogue where fc2 runs on the
+  // rolling 12-wave kernel, else in the second block's first LayerNorm pass
+  bc.temp = e->temp;
+  bc.te_in_fc2 = e->fc2_temp_embed && c.depth > 1 && block_fc2_takes_te(bc);
   for (int i = 0; i < c.depth; ++i) {
-    const bool spatial = (i % 2) == 0;  // latte.py:345-346
-    const BlockW& w = e->blocks[i];
     const float* mb = modp + (size_t)i * 6 * D;  // chunk(6): shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-    bool split_proj = false;   // this block's attention output leaves the fused kernel as a split pair
-    // x + temp_embed once, after the first spatial block (latte.py:357-358): in that block's fc2 epilogue where fc2 runs on the
-    // rolling 12-wave kernel (every element of x is in a register there), else in this LayerNorm pass, which then rewrites x
-    const int fc2_variant = e->gemm_variant_of[3] ? e->gemm_variant_of[3] : e->gemm_variant;
-    const bool te_in_fc2 = e->fc2_temp_embed && c.depth > 1 && gated_gemm_takes_te(e, M, D, e->Hm, fc2_variant);
-    const float* te = (i == 1 && !te_in_fc2) ? e->temp : nullptr;
-    if ((rc = launch_ln_modulate(e->xres, e->xres, e->xn, mb, mb + D, mstride, M, D, rps, te, T, F, dt, st))) return rc;
-    tm.mark(C_LN);
-    GemmArgs g{};
-    g.M = M; g.rows_per_sample = rps; g.gate_stride = mstride; g.rmw_mode = e->gated_rmw_shape; g.stream_policy = stream_policy;
-    const half_t* attn_out = e->xn;
-    if (((e->fuse_qkv_attn >> (spatial ? 0 : 1)) & 1) && qkv_attention_fusable(D, c.num_heads, e->hd, F, T, spatial ? 0 : 1, M)) {
-      // qkv projection + attention core in one kernel (q / k / v of a head only in LDS); the output goes to the (otherwise idle)
-      // qkv buffer viewed as [rows, D], because xn is still being read by other units of the same launch
-      QkvAttnArgs qa{};
-      qa.xn = e->xn; qa.w = w.qkv_w; qa.bias = w.qkv_b; qa.out = e->qkv; qa.B = B; qa.F = F; qa.T = T; qa.D = D;
-      qa.heads = c.num_heads; qa.hd = e->hd; qa.mode = spatial ? 0 : 1; qa.scale = 1.0f / std::sqrt((float)e->hd);
-      qa.flags = ((e->fuse_qkv_attn >> 2) & 7) ^ 7;   // option bits 2-4 switch the default schedule features OFF (A/B hook)
-      split_proj = gsplit & 5;
-      qa.out_split = (gsplit & 4) ? 2 : (gsplit & 1);   // 1: [rows, 2 D] = [hi | lo] inside the [rows, 3 D] qkv buffer; 2: + fp8 remainder
-      qa.out8 = e->lo8;
-      qa.stream_policy = stream_policy;
-      gactive |= gsplit & 5;
-      if ((rc = launch_qkv_attention(qa, dt, st))) return rc;
-      tm.mark(spatial ? C_QKVATTN_S : C_QKVATTN_T);
-      attn_out = e->qkv;
-    } else {
-      g.A = e->xn; g.W = w.qkv_w; g.bias = w.qkv_b; g.out = e->qkv; g.N = 3 * D; g.K = D;
-      if ((rc = launch_gemm(g, EPI_BIAS_H16, dt, e->gemm_variant_of[0] ? e->gemm_variant_of[0] : e->gemm_variant, st))) return rc;
-      tm.mark(C_QKV);
-      AttnArgs a{};
-      a.qkv = e->qkv; a.out = e->xn; a.heads = c.num_heads; a.hd = e->hd; a.D = D;
-      a.sample_stride = rps; a.scale = 1.0f / std::sqrt((float)e->hd);
-      if (spatial) { a.num_seq = B * F; a.L = T; a.U = F; a.seq_stride = T; a.row_stride = 1; }
-      else         { a.num_seq = B * T; a.L = F; a.U = T; a.seq_stride = 1; a.row_stride = T; }
-      if (gsplit & 4) {   // the un-fused attention kernels carry the fp8 remainder too (round 6); the f16-pair form (bit 0) exists in the fused kernel only
-        a.out8 = e->lo8;
-        split_proj = true;
-        gactive |= 4;
-      }
-      if ((rc = launch_attention(a, dt, st))) return rc;
-      tm.mark(spatial ? C_ATTN_S : C_ATTN_T);
-    }
-    g.A = attn_out; g.W = w.proj_w; g.bias = w.proj_b; g.out = e->xres; g.gate = mb + 2 * D; g.N = D; g.K = D; g.tag = 0;
-    if (split_proj && (gsplit & 4)) { g.A8 = e->lo8; g.W8 = w.proj_w8; }          // o_hi . W^T + o_lo8 . W8^T in one launch
-    else if (split_proj) { g.W = w.proj_w2; g.K = 2 * D; }                          // [o_hi | o_lo] . [W | W]^T
-    if ((rc = gated_gemm(e, g, dt, e->gemm_variant_of[1] ? e->gemm_variant_of[1] : e->gemm_variant, st))) return rc;
-    g.A8 = nullptr; g.W8 = nullptr;
-    tm.mark(C_PROJ);
-    const int split_fc1 = (gsplit & 16) ? 3 : (gsplit & 8) ? 2 : (gsplit & 2) ? 1 : 0;
-    if (split_fc1 == 3) rc = launch_ln_modulate_split4(e->xres, e->xn, e->lo4, e->lo4s, mb + 3 * D, mb + 4 * D, mstride, M, D, rps, dt, st);
-    else rc = launch_ln_modulate(e->xres, e->xres, split_fc1 == 1 ? e->xn2 : e->xn, mb + 3 * D, mb + 4 * D, mstride, M, D, rps, nullptr, T, F, dt, st,
-                                 split_fc1, e->lo8);
-    if (rc) return rc;
-    tm.mark(C_LN);
-    g.A = e->xn; g.W = w.fc1_w; g.bias = w.fc1_b; g.out = e->hbuf; g.gate = nullptr; g.N = e->Hm; g.K = D;
-    if (split_fc1 == 1) { g.A = e->xn2; g.W = w.fc1_w2; g.K = 2 * D; }
-    if (split_fc1 == 2) { g.A8 = e->lo8; g.W8 = w.fc1_w8; }
-    if (split_fc1 == 3) { g.A4 = e->lo4; g.A4s = e->lo4s; g.W4 = w.fc1_w4; g.W4s = w.fc1_w4s; }
-    if ((rc = launch_gemm(g, EPI_BIAS_GELU_H16, dt, e->gemm_variant_of[2] ? e->gemm_variant_of[2] : e->gemm_variant, st))) return rc;
-    g.A8 = nullptr; g.W8 = nullptr; g.A4 = nullptr; g.A4s = nullptr; g.W4 = nullptr; g.W4s = nullptr;
-    tm.mark(C_FC1);
-    g.A = e->hbuf; g.W = w.fc2_w; g.bias = w.fc2_b; g.out = e->xres; g.gate = mb + 5 * D; g.N = D; g.K = e->Hm; g.tag = 1;
-    if (i == 0 && te_in_fc2) { g.te = e->temp; g.te_T = T; g.te_F = F; }
-    if ((rc = gated_gemm(e, g, dt, fc2_variant, st))) return rc;
-    tm.mark(C_FC2);
+    if ((rc = block_attention(bc, e->blocks[i], i, mb, st)) || (rc = block_mlp(bc, e->blocks[i], i, mb, st))) return rc;
   }
   // --- final layer (latte.py:197-201) + unpatchify (:297-310)
   const float* fm = modp + (size_t)c.depth * 6 * D;  // chunk(2): shift, scale
   if ((rc = launch_final_layer(e->xres, fm, fm + D, mstride, e->fin_wt, e->fin_b, out, M, D, rps, T, c.patch_size,
                                e->Cout, e->H, st))) return rc;
   tm.mark(C_FINAL);
-  if (cfg_dup) e->guided_split_active = gactive;
+  if (cfg_dup) e->guided_split_active = bc.guided_split_active;
   return LATTE_OK;
 }
 
@@ -775,15 +663,8 @@ int latte_engine_create(const latte_model_config_t* cfg, int max_batch, latte_en
   }
   e->blocks.resize(c.depth);
   for (int i = 0; i < c.depth; ++i) {
-    BlockW& w = e->blocks[i];
-    TRY(e->arena.alloc(&w.qkv_w, (size_t)3 * D * D));
-    TRY(e->arena.alloc(&w.proj_w, (size_t)D * D));
-    TRY(e->arena.alloc(&w.fc1_w, (size_t)e->Hm * D));
-    TRY(e->arena.alloc(&w.fc2_w, (size_t)D * e->Hm));
-    TRY(e->arena.alloc(&w.qkv_b, (size_t)3 * D));
-    TRY(e->arena.alloc(&w.proj_b, (size_t)D));
-    TRY(e->arena.alloc(&w.fc1_b, (size_t)e->Hm));
-    TRY(e->arena.alloc(&w.fc2_b, (size_t)D));
+    BlockLinears& w = e->blocks[i];
+    TRY(alloc_block_linears(e->arena, w, D, e->Hm));
     const std::string p = "blocks." + std::to_string(i) + ".";
     e->weights.add(p + "attn.qkv.weight", (int64_t)3 * D * D, PK_H16, w.qkv_w);
     e->weights.add(p + "attn.qkv.bias", 3 * D, PK_F32, w.qkv_b);

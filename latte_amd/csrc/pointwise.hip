@@ -415,7 +415,7 @@ __global__ void __launch_bounds__(256) text_proj_kernel(const float* __restrict_
   }
 }
 
-// Second half of the split-K gated GEMM of small batches (engine.cpp: gated_gemm): the GEMM wrote `splits` fp32 partial products
+// Second half of the split-K gated GEMM of small batches (block.cpp: gated_gemm): the GEMM wrote `splits` fp32 partial products
 // [M, N] (slab stride `stride`); x += gate * ((p0 + p1 + ...) + bias), the partials summed in slab order (deterministic), the
 // expression of the gated read-modify-write epilogue (latte.py:179-180).  16 bytes per lane, N % 4 == 0.
 __global__ void __launch_bounds__(256) gated_split_reduce_kernel(float* __restrict__ x, const float* __restrict__ ws, int splits,

@@ -22,8 +22,8 @@
 #include <vector>
 
 #include "../../include/latte_amd.h"
+#include "block.h"
 #include "plan.h"
-#include "weight_store.h"
 
 using namespace latte;
 
@@ -31,9 +31,9 @@ namespace {
 
 enum T2VKind { TK_F32, TK_F32_TRANSPOSE, TK_H16 };   // WeightSlot::kind
 
-struct T2VBlock {
-  half_t *qkv_w, *o_w, *q2_w, *kv2_w, *o2_w, *fc1_w, *fc2_w;   // q2 / kv2 / o2: spatial blocks only
-  float *qkv_b, *o_b, *q2_b, *kv2_b, *o2_b, *fc1_b, *fc2_b;
+struct T2VBlock : BlockLinears {   // attn1 and ff; attn1.to_out is proj
+  half_t *q2_w, *kv2_w, *o2_w;     // attn2 (cross-attention): spatial blocks only
+  float *q2_b, *kv2_b, *o2_b;
 };
 
 void sincos_1d(int dim, const std::vector<double>& pos, std::vector<double>& out /* [n][dim] */) {
@@ -47,6 +47,16 @@ void sincos_1d(int dim, const std::vector<double>& pos, std::vector<double>& out
       out[(size_t)m * dim + half + d] = std::cos(v);
     }
 }
+
+// The block policy of this engine (BlockCtx, block.h).  These values reproduce the launches t2v_core made while it carried its own copy of
+// the block body; they are inherited, NOT measured against the class-conditional engine's defaults.
+constexpr int T2V_RMW_MODE = 0;             // gated GEMMs (attn2's out-projection too): fragment-wise residual accesses (engine.cpp: line-wise)
+constexpr int T2V_STREAM_POLICY = 0;        // no `nt` hints on the once-used streams
+constexpr int T2V_GATED_SPLIT_K = 1;        // never split: a gated GEMM is one launch_gemm at every batch (and no split-K workspace exists)
+constexpr bool T2V_TEMP_EMBED_IN_FC2 = false;   // temp_pos_embed through block 1's first LayerNorm pass, and only when F > 1
+constexpr int T2V_GEMM_VARIANT = 0;         // every GEMM on the per-shape tile choice
+constexpr int T2V_GUIDED_SPLIT = 0;         // plain f16 operands in guided chains too
+constexpr EventProfile* T2V_PROFILE = nullptr;   // no per-launch events
 
 }  // namespace
 
@@ -160,14 +170,7 @@ int latte_t2v_create(const latte_t2v_config_t* cfg, int max_batch, latte_t2v_t**
     T2VBlock& w = e->blocks[i];
     const bool spatial = (i % 2) == 0;
     const std::string p = std::string(spatial ? "transformer_blocks." : "temporal_transformer_blocks.") + std::to_string(i / 2) + ".";
-    TRY(e->arena.alloc(&w.qkv_w, (size_t)3 * D * D));
-    TRY(e->arena.alloc(&w.qkv_b, (size_t)3 * D));
-    TRY(e->arena.alloc(&w.o_w, (size_t)D * D));
-    TRY(e->arena.alloc(&w.o_b, (size_t)D));
-    TRY(e->arena.alloc(&w.fc1_w, (size_t)e->Hm * D));
-    TRY(e->arena.alloc(&w.fc1_b, (size_t)e->Hm));
-    TRY(e->arena.alloc(&w.fc2_w, (size_t)D * e->Hm));
-    TRY(e->arena.alloc(&w.fc2_b, (size_t)D));
+    TRY(alloc_block_linears(e->arena, w, D, e->Hm));
     e->weights.add(p + "scale_shift_table", 6 * D, TK_F32, e->tables + (size_t)i * 6 * D);
     // to_q | to_k | to_v concatenated: one fused GEMM, columns ordered [3][heads][hd] like latte.py:50
     e->weights.add(p + "attn1.to_q.weight", (int64_t)D * D, TK_H16, w.qkv_w);
@@ -176,8 +179,8 @@ int latte_t2v_create(const latte_t2v_config_t* cfg, int max_batch, latte_t2v_t**
     e->weights.add(p + "attn1.to_q.bias", D, TK_F32, w.qkv_b);
     e->weights.add(p + "attn1.to_k.bias", D, TK_F32, w.qkv_b + D);
     e->weights.add(p + "attn1.to_v.bias", D, TK_F32, w.qkv_b + 2 * D);
-    e->weights.add(p + "attn1.to_out.0.weight", (int64_t)D * D, TK_H16, w.o_w);
-    e->weights.add(p + "attn1.to_out.0.bias", D, TK_F32, w.o_b);
+    e->weights.add(p + "attn1.to_out.0.weight", (int64_t)D * D, TK_H16, w.proj_w);
+    e->weights.add(p + "attn1.to_out.0.bias", D, TK_F32, w.proj_b);
     if (spatial) {
       TRY(e->arena.alloc(&w.q2_w, (size_t)D * D));
       TRY(e->arena.alloc(&w.q2_b, (size_t)D));
@@ -347,58 +350,40 @@ static int t2v_core(latte_t2v* e, const float* x, const int64_t* t, bool t_share
   if (dup && (rc = launch_patch_embed(e->xin, e->pe_wt, e->pe_b, e->pos, e->xres + (size_t)xb * rps * D, xb * F, c.in_channels,
                                       e->H, c.patch_size, D, st))) return rc;
 
-  GemmArgs g{};
+  BlockCtx bc{};   // zero: no split-K workspace, no guided-split operands
+  bc.B = B; bc.F = F; bc.T = T; bc.D = D; bc.heads = e->heads; bc.hd = e->hd; bc.Hm = e->Hm; bc.dt = dt;
+  bc.xres = e->xres; bc.xn = e->xn; bc.qkv = e->qkv; bc.hbuf = e->hbuf;
+  bc.mod_stride = mstride;
+  bc.temp = F > 1 ? e->temp : nullptr;   // latte_t2v.py:889-890
+  bc.te_in_fc2 = T2V_TEMP_EMBED_IN_FC2;
+  bc.fuse_qkv_attn = e->fuse_qkv_attn;
+  for (int k = 0; k < 4; ++k) bc.gemm_variant_of[k] = T2V_GEMM_VARIANT;
+  bc.gated_split_k = T2V_GATED_SPLIT_K; bc.rmw_mode = T2V_RMW_MODE; bc.stream_policy = T2V_STREAM_POLICY;
+  bc.gsplit = T2V_GUIDED_SPLIT;
+  bc.prof = T2V_PROFILE;
   for (int i = 0; i < e->nblk; ++i) {
     const bool spatial = (i % 2) == 0;
     if (!spatial && !enable_temporal) continue;
     const T2VBlock& w = e->blocks[i];
     const float* mb = e->mod + (size_t)i * 6 * D;   // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-    const float* te = (i == 1 && F > 1) ? e->temp : nullptr;                  // latte_t2v.py:889-890
-    if ((rc = launch_ln_modulate(e->xres, e->xres, e->xn, mb, mb + D, mstride, M, D, rps, te, T, F, dt, st))) return rc;
-    g = GemmArgs{};
-    g.M = M; g.rows_per_sample = rps; g.gate_stride = mstride;
-    const half_t* attn_out = e->xn;
-    const float attn_scale = 1.0f / std::sqrt((float)e->hd);
-    if (((e->fuse_qkv_attn >> (spatial ? 0 : 1)) & 1) && qkv_attention_fusable(D, e->heads, e->hd, F, T, spatial ? 0 : 1, M)) {
-      // to_q | to_k | to_v + the attention core in one kernel, q / k / v only in LDS (Latte-1: the temporal blocks, 16 frames per
-      // token; the 1024-token spatial sequences keep the separate kernels); output to the idle qkv buffer viewed as [rows, D]
-      QkvAttnArgs qa{};
-      qa.xn = e->xn; qa.w = w.qkv_w; qa.bias = w.qkv_b; qa.out = e->qkv; qa.B = B; qa.F = F; qa.T = T; qa.D = D;
-      qa.heads = e->heads; qa.hd = e->hd; qa.mode = spatial ? 0 : 1; qa.scale = attn_scale; qa.flags = ((e->fuse_qkv_attn >> 2) & 7) ^ 7;
-      if ((rc = launch_qkv_attention(qa, dt, st))) return rc;
-      attn_out = e->qkv;
-    } else {
-      g.A = e->xn; g.W = w.qkv_w; g.bias = w.qkv_b; g.out = e->qkv; g.N = 3 * D; g.K = D;
-      if ((rc = launch_gemm(g, EPI_BIAS_H16, dt, 0, st))) return rc;
-      AttnArgs a{};
-      a.qkv = e->qkv; a.out = e->xn; a.heads = e->heads; a.hd = e->hd; a.D = D;
-      a.sample_stride = rps; a.scale = attn_scale;
-      if (spatial) { a.num_seq = B * F; a.L = T; a.U = F; a.seq_stride = T; a.row_stride = 1; }
-      else         { a.num_seq = B * T; a.L = F; a.U = T; a.seq_stride = 1; a.row_stride = T; }
-      if ((rc = launch_attention(a, dt, st))) return rc;
-    }
-    g.A = attn_out; g.W = w.o_w; g.bias = w.o_b; g.out = e->xres; g.gate = mb + 2 * D; g.N = D; g.K = D; g.tag = 0;
-    if ((rc = launch_gemm(g, EPI_GATE_RES_F32, dt, 0, st))) return rc;
+    if ((rc = block_attention(bc, w, i, mb, st))) return rc;
     if (spatial) {
       // cross-attention on the UN-normalised stream (PixArt: no norm before attn2, no gate after it)
       if ((rc = launch_convert_f32_to_h16(e->xres, e->xn, (int64_t)M * D, dt, st))) return rc;
-      g.A = e->xn; g.W = w.q2_w; g.bias = w.q2_b; g.out = e->qkv; g.gate = nullptr; g.N = D; g.K = D;
-      if ((rc = launch_gemm(g, EPI_BIAS_H16, dt, 0, st))) return rc;
+      GemmArgs g{};
+      g.M = M; g.rows_per_sample = rps; g.gate_stride = mstride; g.rmw_mode = T2V_RMW_MODE; g.stream_policy = T2V_STREAM_POLICY;
+      g.A = e->xn; g.W = w.q2_w; g.bias = w.q2_b; g.out = e->qkv; g.N = D; g.K = D;
+      if ((rc = launch_gemm(g, EPI_BIAS_H16, dt, T2V_GEMM_VARIANT, st))) return rc;
       AttnArgs x2{};
       x2.qkv = e->qkv; x2.q_ld = D; x2.kv = e->kv_all + (size_t)(i / 2) * e->trows_pad * 2 * D; x2.kbias = kbias; x2.Lk = Lk;
       x2.out = e->xn;
-      x2.heads = e->heads; x2.hd = e->hd; x2.D = D; x2.sample_stride = rps; x2.scale = attn_scale;
-      x2.num_seq = B * F; x2.L = T; x2.U = F; x2.seq_stride = T; x2.row_stride = 1;
+      x2.heads = e->heads; x2.hd = e->hd; x2.D = D; x2.sample_stride = rps; x2.scale = 1.0f / std::sqrt((float)e->hd);
+      seq_layout(x2, true, B, F, T);
       if ((rc = launch_cross_attention(x2, dt, st))) return rc;
-      g.A = e->xn; g.W = w.o2_w; g.bias = w.o2_b; g.out = e->xres; g.gate = e->ones; g.gate_stride = 0; g.N = D; g.K = D;
-      if ((rc = launch_gemm(g, EPI_GATE_RES_F32, dt, 0, st))) return rc;
-      g.gate_stride = mstride;
+      g.A = e->xn; g.W = w.o2_w; g.bias = w.o2_b; g.out = e->xres; g.gate = e->ones; g.gate_stride = 0;
+      if ((rc = launch_gemm(g, EPI_GATE_RES_F32, dt, T2V_GEMM_VARIANT, st))) return rc;
     }
-    if ((rc = launch_ln_modulate(e->xres, e->xres, e->xn, mb + 3 * D, mb + 4 * D, mstride, M, D, rps, nullptr, T, F, dt, st))) return rc;
-    g.A = e->xn; g.W = w.fc1_w; g.bias = w.fc1_b; g.out = e->hbuf; g.gate = nullptr; g.N = e->Hm; g.K = D;
-    if ((rc = launch_gemm(g, EPI_BIAS_GELU_H16, dt, 0, st))) return rc;
-    g.A = e->hbuf; g.W = w.fc2_w; g.bias = w.fc2_b; g.out = e->xres; g.gate = mb + 5 * D; g.N = D; g.K = e->Hm; g.tag = 1;
-    if ((rc = launch_gemm(g, EPI_GATE_RES_F32, dt, 0, st))) return rc;
+    if ((rc = block_mlp(bc, w, i, mb, st))) return rc;
   }
   // ---- output head (latte_t2v.py:913-931), frame layout
   const float* hm = e->mod + (size_t)e->nblk * 6 * D;   // chunk(2): shift, scale

@@ -208,13 +208,6 @@ bool pow2_in(double v, double lo, double hi) {
   int ex = 0;
   return v >= lo && v <= hi && std::frexp(v, &ex) == 0.5;
 }
-// the sequence layout of a block's attention (forward and backward): spatial blocks attend inside a frame (B F sequences of T
-// contiguous rows), temporal ones across the F frames of a token (rows T apart)
-void seq_layout(AttnArgs& a, bool spatial, int B, int F, int T) {
-  if (spatial) { a.num_seq = B * F; a.L = T; a.U = F; a.seq_stride = T; a.row_stride = 1; }
-  else         { a.num_seq = B * T; a.L = F; a.U = T; a.seq_stride = 1; a.row_stride = T; }
-}
-
 int gemm_half(latte_trainer* e, const half_t* A, const half_t* W, const float* bias, half_t* out, int M, int N, int K, hipStream_t st) {
   GemmArgs g{};
   g.A = A; g.W = W; g.bias = bias; g.out = out; g.M = M; g.N = N; g.K = K; g.rows_per_sample = M; g.gate_stride = 0;

@@ -20,6 +20,13 @@ Builds nothing: it loads LATTE_AMD_LIB or latte_amd/lib/liblatte_amd.so of the t
   known loop    latte_sample_loop_known for DDPM, DDIM eta 0 and eta 0.5 at resample 1 and 2, both trails: guided batch 4 over 70 steps
                 whole and as two calls (blend_start on the first only), plain batch 3, unconditional batch 2; each with noise drawn by the
                 engine and with given slabs
+  forward       (--only forward runs it alone) one denoiser forward per case on models of XL width and depth 2, where the block's shape
+                rules reach every kernel: Latte at B = 1, 2, 8 under the engine options that select a block-level path (gated_split_k,
+                stream_policy, gated_rmw_shape, fc2_temp_embed, gemm_variant_fc2, fuse_qkv_attn), forward_with_cfg under guided_split
+                0 / 3 / 12 / 20 with "guided_split_active" read back, bf16, the three tiny fixtures; LatteT2V (one layer, 20 text tokens,
+                partly masked) at 256-token x 16-frame, 1024-token x 16-frame and single-frame geometries, temporal blocks on and off.
+                Values cannot show WHICH kernel ran where two give the same bits: run it under
+                ``rocprofv3 --kernel-trace --stats`` and compare the name -> calls tables (profiles/block_body_kernel_stats_*.csv)
   front end     p_sample_loop_progressive, ddim_reverse_sample_loop_progressive and known_sample_loop_progressive of SpacedDiffusion
                 on torch.manual_seed draws with SEGMENT_BYTES cut to three indices per engine call
 After every class-engine case the option "seed" is read back and one further engine-drawn DDPM step is hashed, so the Philox offset
@@ -254,6 +261,97 @@ def t2v_cases(out):
     out["t2v::ddim::known"] = {"latents": sha(video)}
 
 
+def forward_cases(out):
+    """One denoiser forward per case, at the width where the block's shape rules select every kernel: the rolling kernel, the 128 x 144 tile,
+    split-K and the split operands of guided calls never run at the golden fixtures' D = 128."""
+    from _util import engine_model, load_golden_model
+    from latte_amd.random_init import randomize_zero_init, t2v_state_dict
+
+    def xl(dtype, max_batch):
+        torch.manual_seed(31)
+        m = latte_amd.Latte(hidden_size=1152, num_heads=16, depth=2, patch_size=2, input_size=32, num_frames=16, num_classes=10, extras=2,
+                            learn_sigma=True, compute_dtype=dtype, max_batch=max_batch)
+        return randomize_zero_init(m, seed=32).cuda().eval()
+
+    def inputs(B, guided):
+        g = torch.Generator("cpu").manual_seed(33 + B + 100 * guided)
+        half = B // 2 if guided else B
+        x, t, y = torch.randn(half, 16, 4, 32, 32, generator=g), torch.randint(0, 1000, (half,), generator=g), torch.randint(0, 10, (half,), generator=g)
+        if guided:
+            x, t, y = torch.cat([x, x]), torch.cat([t, t]), torch.cat([y, torch.full_like(y, 10)])
+        return x.cuda(), t.cuda(), y.cuda()
+
+    def run(m, key, B, guided=False, **options):
+        """the forward under `options`, which are put back to what they were behind it"""
+        before = {k: m.get_engine_option(k, batch=B, guided=guided) for k in options}
+        for k, v in options.items():
+            m.set_engine_option(k, v, batch=B, guided=guided)
+        x, t, y = inputs(B, guided)
+        if guided:
+            rec = {"out": sha(m.forward_with_cfg(x, t, y=y, cfg_scale=CFG))}
+            rec["guided_split_active"] = m.get_engine_option("guided_split_active", batch=B, guided=True)
+        else:
+            rec = {"out": sha(m(x, t, y=y))}
+        for k, v in before.items():
+            m.set_engine_option(k, v, batch=B, guided=guided)
+        out["forward::xl::" + key] = rec
+
+    m = xl("f16", 8)
+    for B in (1, 2, 8):
+        run(m, f"B{B}", B)
+    for v in (1, 2):
+        run(m, f"B1::gated_split_k{v}", 1, gated_split_k=v)
+    run(m, "B8::gated_rmw_shape0", 8, gated_rmw_shape=0)
+    run(m, "B8::fc2_temp_embed0", 8, fc2_temp_embed=0)
+    for v in (8, 11):
+        run(m, f"B8::gemm_variant_fc2_{v}", 8, gemm_variant_fc2=v)
+    for v in (0, 1, 2, 31):
+        run(m, f"B8::fuse_qkv_attn{v}", 8, fuse_qkv_attn=v)
+    for B in (2, 8):
+        for v in (0, 3, 12, 20):
+            run(m, f"cfg::B{B}::guided_split{v}", B, guided=True, guided_split=v)
+    for v in (0, 15):          # last: once set, the option holds at every batch
+        run(m, f"B8::stream_policy{v}", 8, stream_policy=v)
+    del m
+    m = xl("bf16", 2)
+    run(m, "bf16::B2", 2)
+    run(m, "bf16::cfg::B2", 2, guided=True)
+    del m
+    for name in ("tiny_classcond", "tiny_uncond", "tiny_textcond"):      # the un-fused flash path, extras == 78
+        kw, sd, r = load_golden_model(name)
+        m = engine_model(kw, sd, "f16", max_batch=4)
+        mk = {k: torch.from_numpy(r[k]).cuda() for k in ("y", "text_embedding") if k in r}
+        out[f"forward::{name}"] = {"out": sha(m(torch.from_numpy(r["x"]).cuda(), torch.from_numpy(r["t"]).cuda(), **mk))}
+        if "x_cfg" in r:
+            if "y_cfg" in r:
+                mk["y"] = torch.from_numpy(r["y_cfg"]).cuda()
+            xc = torch.from_numpy(r["x_cfg"]).cuda()
+            tc = torch.from_numpy(r["t"]).cuda()[:1].expand(xc.shape[0]).contiguous()
+            out[f"forward::{name}::cfg"] = {"out": sha(m.forward_with_cfg(xc, tc, cfg_scale=CFG, **mk)),
+                                            "guided_split_active": m.get_engine_option("guided_split_active", batch=xc.shape[0], guided=True)}
+        del m
+
+    sd = t2v_state_dict(34, num_layers=1, caption_channels=128)
+    g = torch.Generator("cpu").manual_seed(35)
+    enc, mask = torch.randn(2, 20, 128, generator=g).cuda(), torch.ones(2, 20).cuda()
+    mask[0, 12:] = 0
+    mask[1, 17:] = 0
+    for size, frames, variants in ((32, 16, [(temporal, fuse) for temporal in (True, False) for fuse in (0, 3)]), (64, 16, [(True, 3)]),
+                                   (16, 1, [(True, 3)])):
+        m = latte_amd.LatteT2V(num_attention_heads=16, attention_head_dim=72, num_layers=1, caption_channels=128, sample_size=size,
+                               video_length=frames, compute_dtype="f16", max_batch=2).load_state_dict(sd).to("cuda")
+        x, t = torch.randn(2, 4, frames, size, size, generator=g).cuda(), torch.tensor([500, 20]).cuda()
+        m.set_text(enc, mask)                                            # an engine exists from here on (set_engine_option)
+        for temporal, fuse in variants:
+            m.set_engine_option("fuse_qkv_attn", fuse)
+            o = m(x, t, enc, encoder_attention_mask=mask, enable_temporal_attentions=temporal).sample
+            out[f"forward::t2v::size{size}::frames{frames}::temporal{int(temporal)}::fuse_qkv_attn{fuse}"] = {"out": sha(o)}
+        del m
+
+
+GROUPS = {"class": class_cases, "t2v": t2v_cases, "forward": forward_cases}
+
+
 def compare(a, b):
     ra, rb = (json.load(open(p))["cases"] for p in (a, b))
     bad = sorted(k for k in set(ra) | set(rb) if ra.get(k) != rb.get(k))
@@ -266,6 +364,7 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--compare", nargs=2, metavar="JSON")
     ap.add_argument("--tree", help="the built checkout to import latte_amd and tests/_util from (default: this one)")
+    ap.add_argument("--only", choices=sorted(GROUPS), help="run this case group alone (default: all of them)")
     a = ap.parse_args()
     if a.compare:
         raise SystemExit(compare(*a.compare))
@@ -273,8 +372,9 @@ def main():
         raise SystemExit("tools/chain_ab.py needs an MI355X")
     torch.set_grad_enabled(False)
     cases = {}
-    class_cases(cases)
-    t2v_cases(cases)
+    for name, group in GROUPS.items():
+        if a.only in (None, name):
+            group(cases)
     result = {"what": "sha256 of every tensor the engine's fused loops return, fixed seeds (tools/chain_ab.py)",
               "library": "LATTE_AMD_LIB" if os.environ.get("LATTE_AMD_LIB") else "tree", "version": load_library().latte_version().decode(),
               "device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName, "cases": cases}
