@@ -281,6 +281,42 @@ int latte_known_blend(float* x, const float* known, const float* mask, const flo
 int latte_sample_plan_loop(latte_engine_t* e, int guided, float cfg_scale, float* x, const int64_t* y, int batch, int n_evals,
                            const double* plan, const float* noise, float* trail_sample, void* stream);
 
+/* ------------------------------------------------------------------ clips longer than num_frames: overlapping temporal windows
+ * Temporal co-denoising (Gen-L-Video, MultiDiffusion along time; not in the reference): a long latent of L = total_frames >= F frames
+ * (F = the model's num_frames / video_length) is denoised as ONE chain.  With 1 <= stride <= F the windows are
+ *   W = ceil((L - F) / stride) + 1,   s_w = min(w * stride, L - F)   (the last window is pulled back so that it ends at L)
+ * and every denoiser evaluation of a chain is
+ *   gather   clips[g W + w] = x[g, s_w : s_w + F]          g over the batch rows as the loop sees them (the doubled batch when guided)
+ *   forward  once, on the G W clips (labels repeated per window; a text context is installed per clip)
+ *   merge    merged[g, f] = (sum over the windows covering f, ascending w, of out[g W + w, f - s_w]) / count(f), fp32, every output
+ *            channel (the learned-sigma ones included); a frame one window covers is copied exactly
+ * followed by the loop's own update kernel with frames = L: guidance, clipping, noise, trails and the history ring are unchanged.
+ * Uniform weights, the same windows at every step, every clip of a call in one forward: G W <= max_batch.
+ *
+ * latte_window_plan: host only.  Writes the W starts (starts_out, `cap` entries; NULL: skipped) and the per-frame window counts
+ * (counts_out, total_frames entries; NULL: skipped) and returns W >= 1, or -LATTE_ERR_INVALID (latte_last_error) for
+ * total_frames < frames, stride outside 1 ... frames, or cap < W. */
+int latte_window_plan(int total_frames, int frames, int stride, int* starts_out, int* counts_out, int cap);
+/* The two kernels on their own (device pointers, fp32).  frames_inner = 0: x / merged [G, L, C, H*W], clips / out [G W, F, C, H*W] (the
+ * class-conditional engine's layout, and the layout of BOTH engines' model outputs); 1: [G, C, L, H*W] and [G W, C, F, H*W]
+ * (text-to-video latents).  hw % 4 != 0 and a bad window set are refused (LATTE_ERR_INVALID). */
+int latte_window_gather(const float* x, float* clips, int groups, int total_frames, int frames, int stride, int channels, int hw,
+                        int frames_inner, void* stream);
+int latte_window_merge(const float* out, float* merged, int groups, int total_frames, int frames, int stride, int channels, int hw,
+                       int frames_inner, void* stream);
+/* latte_sample_loop_ex / latte_sample_plan_loop on x [batch, total_frames, C, H, W]; the noise rows and the trails have that shape too
+ * (row k of the caller's noise is read at step k, else one engine draw of that size per step).  The conditioning rows are per clip.
+ * After the checks of the plain loop, in its order: LATTE_ERR_INVALID for total_frames < num_frames, stride < 1, stride > num_frames
+ * and H * W % 4 != 0, then LATTE_ERR_STATE for batch * W > max_batch (a text-embedding model needs batch * W installed rows).  Every
+ * check runs before the first launch: x is untouched when one fails.  The clip and merged-output buffers are taken from the engine's
+ * arena by the first call.  total_frames == num_frames gives the bits of the plain loop. */
+int latte_sample_loop_windows(latte_engine_t* e, const latte_schedule_t* s, int method, float eta, int clip_denoised, int guided,
+                              float cfg_scale, float* x, const int64_t* y, int batch, int start_index, int end_index, const float* noise,
+                              float* trail_sample, float* trail_x0, int total_frames, int stride, void* stream);
+int latte_sample_plan_loop_windows(latte_engine_t* e, int guided, float cfg_scale, float* x, const int64_t* y, int batch, int n_evals,
+                                   const double* plan, const float* noise, float* trail_sample, int total_frames, int stride,
+                                   void* stream);
+
 /* ------------------------------------------------------------------ training path, forward evaluation
  * SURVEY.md section 8(f) rank 3, first slice: the loss VALUES of GaussianDiffusion.training_losses
  * (gaussian_diffusion.py:719-795, through SpacedDiffusion.training_losses respace.py:95-98; called by train.py:224-226)
@@ -646,6 +682,17 @@ int latte_t2v_guided_ddim_loop_known(latte_t2v_t* e, float* x, int samples, int 
 #define LATTE_T2V_PLAN_COLS LATTE_PLAN_COLS
 int latte_t2v_guided_linear_loop(latte_t2v_t* e, float* x, int samples, int n_evals, const double* plan, const float* noise,
                                  float guidance_scale, int enable_temporal_attentions, void* stream);
+/* The two guided loops on x [samples, C, total_frames, H, W] with overlapping temporal windows (the scheme of
+ * latte_sample_loop_windows, F = video_length; the noise rows of the linear loop have x's shape).  The installed text context must hold
+ * 2 * samples * W rows ordered [negative prompts | prompts], each prompt's row repeated W times.  Behind the weights check:
+ * LATTE_ERR_INVALID for total_frames < video_length, stride outside 1 ... video_length and H * W % 4 != 0; then LATTE_ERR_STATE for
+ * 2 * samples * W > max_batch and a text context of another row count; then the checks of the plain loops.  Nothing is launched
+ * when a check fails. */
+int latte_t2v_guided_ddim_loop_windows(latte_t2v_t* e, float* x, int samples, int n_steps, const int64_t* timesteps, const double* alpha_t,
+                                       const double* alpha_prev, float guidance_scale, int enable_temporal_attentions, int total_frames,
+                                       int stride, void* stream);
+int latte_t2v_guided_linear_loop_windows(latte_t2v_t* e, float* x, int samples, int n_evals, const double* plan, const float* noise,
+                                         float guidance_scale, int enable_temporal_attentions, int total_frames, int stride, void* stream);
 
 /* ------------------------------------------------------------------ T5 v1.1 text encoder
  * transformers.T5EncoderModel (feed_forward_proj "gated-gelu"): the text_encoder of Latte-1 text-to-video (T5-v1.1-XXL: d_model 4096,

@@ -16,6 +16,7 @@ from .schedulers import (DDIMInverseScheduler, DDIMScheduler, DPMSolverMultistep
 from .t2v import LatteT2V  # noqa: F401
 from .t5 import T5EncoderModel  # noqa: F401
 from .training import LatteTrainer  # noqa: F401
+from .windows import window_counts, window_gather, window_merge, window_starts  # noqa: F401
 from .vae import AutoencoderKL, AutoencoderKLTemporalDecoder  # noqa: F401
 from .video_io import read_avi, read_mp4, write_avi, write_mp4  # noqa: F401
 from . import parallel  # noqa: F401

@@ -85,6 +85,13 @@ PROTOTYPES = {
     "latte_known_blend": (c_int, [c_void, c_void, c_void, c_void, c_u64, c_u64, c_f32, c_f32, c_int, c_int, c_int, c_int, c_int,
                                   c_void]),
     "latte_sample_plan_loop": (c_int, [c_void, c_int, c_f32, c_void, c_void, c_int, c_int, c_void, c_void, c_void, c_void]),
+    "latte_window_plan": (c_int, [c_int, c_int, c_int, c_void, c_void, c_int]),
+    "latte_window_gather": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void]),
+    "latte_window_merge": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void]),
+    "latte_sample_loop_windows": (c_int, [c_void, c_void, c_int, c_f32, c_int, c_int, c_f32, c_void, c_void, c_int, c_int, c_int,
+                                          c_void, c_void, c_void, c_int, c_int, c_void]),
+    "latte_sample_plan_loop_windows": (c_int, [c_void, c_int, c_f32, c_void, c_void, c_int, c_int, c_void, c_void, c_void, c_int, c_int,
+                                               c_void]),
     "latte_q_sample": (c_int, [c_void, c_void, c_void, c_void, c_int, c_i64, c_void, c_void]),
     "latte_training_workspace_floats": (c_i64, [c_int, c_i64]),
     "latte_training_losses": (c_int, [c_void, c_int, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void,
@@ -143,6 +150,9 @@ PROTOTYPES = {
     "latte_t2v_guided_ddim_loop_known": (c_int, [c_void, c_void, c_int, c_int, c_void, c_void, c_void, c_f32, c_void, c_void, c_void,
                                                  c_int, c_void]),
     "latte_t2v_guided_linear_loop": (c_int, [c_void, c_void, c_int, c_int, c_void, c_void, c_f32, c_int, c_void]),
+    "latte_t2v_guided_ddim_loop_windows": (c_int, [c_void, c_void, c_int, c_int, c_void, c_void, c_void, c_f32, c_int, c_int, c_int,
+                                                   c_void]),
+    "latte_t2v_guided_linear_loop_windows": (c_int, [c_void, c_void, c_int, c_int, c_void, c_void, c_f32, c_int, c_int, c_int, c_void]),
     "latte_bench_gemm": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_f32), c_void]),
     "latte_vae_create": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_void)]),
     "latte_vae_create_temporal": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_void)]),

@@ -304,6 +304,25 @@ int launch_fill_normal(float* out, size_t n, uint64_t seed, uint64_t offset, hip
 // launch_fill_normal(seed, offset).  hw % 4 is refused.
 int launch_known_blend(float* x, const float* known, const float* mask, const float* z, uint64_t seed, uint64_t offset, float a, float b,
                        int batch, int frames, int channels, int hw, int frames_inner, hipStream_t st);
+// Overlapping temporal windows of a clip longer than the model's: window w covers frames
+// [start(w), start(w) + F) of the L; the last one is pulled back so that it ends at L.  The one definition of the window set: the
+// two kernels restate start(), everything else asks here.
+struct WindowSet {
+  int L, F, stride;
+  bool valid() const { return F >= 1 && L >= F && stride >= 1 && stride <= F; }
+  int count() const { return (L - F + stride - 1) / stride + 1; }
+  int start(int w) const { return w * stride < L - F ? w * stride : L - F; }
+};
+// `who`-prefixed refusals of a window set and of H * W % 4 (16-byte accesses of both kernels), LATTE_ERR_INVALID
+int window_check(const std::string& who, const WindowSet& ws, int hw);
+// clips[g W + w] = x[g, start(w) : start(w) + F]: x [G, L, C, HW] -> clips [G W, F, C, HW] (frames_inner = 0) or x [G, C, L, HW] ->
+// clips [G W, C, F, HW] (1)
+int launch_window_gather(const float* x, float* clips, int groups, const WindowSet& ws, int channels, int hw, int frames_inner,
+                         hipStream_t st);
+// merged[g, f] = mean over the windows covering f (ascending w) of out[g W + w, f - start(w)], a frame of one window copied; the
+// layouts of launch_window_gather, out in the clips' and merged in x's
+int launch_window_merge(const float* out, float* merged, int groups, const WindowSet& ws, int channels, int hw, int frames_inner,
+                        hipStream_t st);
 
 // ---- VAE decoder kernels (vae.hip) -----------------------------------------------------------------
 // out32 != nullptr: fp32 output  out32 = conv + bias (+ res32)  (the decoder's residual stream is fp32); else half `out` (+ res)

@@ -123,6 +123,10 @@ struct latte_engine {
   // max_batch latents each; t_embedder of every row of the plan, in chain order
   float *plan_hist[3] = {nullptr, nullptr, nullptr}, *plan_xin = nullptr, *plan_temb = nullptr;
   int64_t plan_temb_cap = 0;
+  // overlapping temporal windows (taken from the arena by the first windowed chain): the gathered clips (the size of noise_buf), the
+  // merged model output (the size of model_out), the labels repeated per window
+  float *win_clips = nullptr, *win_merged = nullptr;
+  int64_t* win_y = nullptr;
   int train_timesteps = 1000;   // latte_sample_plan_loop refuses timesteps at or above it (diffusion_steps of create_diffusion)
   WeightSlots weights;
   DeviceArena arena;
@@ -400,8 +404,9 @@ int range_check(const std::string& who, int n, int lo, int hi, const char* why2)
 }
 
 // The argument block, in this order: batch, learn_sigma (skipped without a schedule), doubled batch, y, text.
+// rows_per_sample: the denoiser rows of one sample, > 1 for a windowed chain (the text rows are installed per clip)
 int chain_check(const std::string& who, const latte_engine* e, const latte_schedule_t* s, int batch, bool guided, const int64_t* y,
-                bool text_allowed) {
+                bool text_allowed, int rows_per_sample = 1) {
   if (batch <= 0 || batch > e->max_batch) return fail(LATTE_ERR_STATE, who + ": batch exceeds max_batch");
   if (s && (s->var_type == 0) != (e->Cout == 2 * e->Cin))
     return fail(LATTE_ERR_INVALID, who + ": the model's learn_sigma and the diffusion's learn_sigma disagree "
@@ -410,7 +415,7 @@ int chain_check(const std::string& who, const latte_engine* e, const latte_sched
   const int ex = e->cfg.extras;
   if (ex == 2 && y == nullptr) return fail(LATTE_ERR_INVALID, who + ": class-conditional model needs y");
   if (ex == 78 && !text_allowed) return fail(LATTE_ERR_INVALID, who + ": serves the class-conditional and unconditional models only");
-  if (ex == 78 && e->txt_rows != batch)
+  if (ex == 78 && e->txt_rows != batch * rows_per_sample)
     return fail(LATTE_ERR_STATE, who + ": text-conditioned model needs latte_engine_set_text_embedding with one row per sample first");
   return LATTE_OK;
 }
@@ -432,6 +437,52 @@ int chain_noise(latte_engine* e, const float* noise, int k, size_t numel, hipStr
 int chain_trail(float* trail, int k, const float* x, size_t numel, hipStream_t st) {
   if (trail) LATTE_HIP(hipMemcpyAsync(trail + (size_t)k * numel, x, sizeof(float) * numel, hipMemcpyDeviceToDevice, st));
   return LATTE_OK;
+}
+
+// ---- overlapping temporal windows: a chain over x of ws.L >= F frames evaluates the denoiser on the W
+// windows of every batch row at once and averages their outputs where they overlap; the update kernels then run with frames = L.
+// The checks of a windowed chain, after the shared ones: the window set and H * W % 4 (LATTE_ERR_INVALID), then the clips against
+// max_batch (LATTE_ERR_STATE).
+int chain_window_check(const std::string& who, const latte_engine* e, const WindowSet& ws, int batch) {
+  int rc = window_check(who, ws, e->H * e->H);
+  if (rc) return rc;
+  if ((int64_t)batch * ws.count() > e->max_batch) return fail(LATTE_ERR_STATE, who + ": the clips (batch * windows) exceed max_batch");
+  return LATTE_OK;
+}
+
+// First use: the clip and merged-output buffers (batch * L <= batch * W * F, so the sizes of noise_buf and model_out hold them); then
+// the labels of the clips, y repeated per window.  *y_clips: what the conditioning and the forward of the chain index.
+int chain_window_prepare(latte_engine* e, const WindowSet& ws, const int64_t* y, int batch, hipStream_t st, const int64_t** y_clips) {
+  int rc;
+  const size_t frame = (size_t)e->max_batch * e->F * e->H * e->H;
+  if (!e->win_clips && (rc = e->arena.alloc(&e->win_clips, frame * e->Cin, false))) return rc;
+  if (!e->win_merged && (rc = e->arena.alloc(&e->win_merged, frame * e->Cout, false))) return rc;
+  if (!e->win_y && (rc = e->arena.alloc(&e->win_y, (size_t)e->max_batch, false))) return rc;
+  *y_clips = y;
+  if (!y) return LATTE_OK;
+  const int W = ws.count();
+  for (int w = 0; w < W; ++w)   // win_y[g W + w] = y[g]
+    LATTE_HIP(hipMemcpy2DAsync(e->win_y + w, sizeof(int64_t) * W, y, sizeof(int64_t), sizeof(int64_t), batch, hipMemcpyDeviceToDevice, st));
+  *y_clips = e->win_y;
+  return LATTE_OK;
+}
+
+// One denoiser evaluation of a chain on x_in, *out = where its output lies ([batch, frames, Cout, HW]): the forward itself, or with
+// windows gather -> the forward on the batch * W clips -> merge.
+int chain_forward(latte_engine* e, const WindowSet* ws, const float* x_in, const int64_t* y, int batch, bool use_cfg, const float* mod,
+                  int mstride, hipStream_t st, const float** out) {
+  int rc;
+  const int HW = e->H * e->H;
+  if (ws) {
+    if ((rc = launch_window_gather(x_in, e->win_clips, batch, *ws, e->Cin, HW, 0, st))) return rc;
+    x_in = e->win_clips;
+    batch *= ws->count();
+  }
+  if ((rc = run_forward(e, x_in, nullptr, y, batch, use_cfg, e->model_out, st, nullptr, mod, mstride))) return rc;
+  *out = e->model_out;
+  if (!ws) return LATTE_OK;
+  *out = e->win_merged;
+  return launch_window_merge(e->model_out, e->win_merged, batch / ws->count(), *ws, e->Cout, HW, 0, st);
 }
 
 SamplerCoefs make_coefs(const latte_schedule_t* s, int method, int i, float eta, int clip) {
@@ -511,18 +562,20 @@ struct NoiseCursor {
 };
 
 // latte_sample_loop_ex (dir = -1: start_index down to end_index), latte_invert_loop (dir = +1: start_index up to end_index) and
-// latte_sample_loop_known (dir = -1 with `kn`: every index `resample` times, the known part of x replaced after every step)
+// latte_sample_loop_known (dir = -1 with `kn`: every index `resample` times, the known part of x replaced after every step);
+// latte_sample_loop_windows (`ws`: x, the noise rows and the trails have ws->L frames)
 int sampler_chain(const std::string& who, latte_engine* e, const latte_schedule_t* s, int method, int dir, float eta, int clip_denoised,
                   int guided, float cfg_scale, float* x, const int64_t* y, int batch, int start_index, int end_index, const KnownRegion* kn,
-                  const float* noise, float* trail_sample, float* trail_x0, hipStream_t st) {
+                  const float* noise, float* trail_sample, float* trail_x0, hipStream_t st, const WindowSet* ws = nullptr) {
   if (!e || !s || !x) return fail(LATTE_ERR_INVALID, who + ": null argument");
   int rc = latte_engine_check_weights(e);
   if (rc) return rc;
   if ((rc = range_check(who, s->num_timesteps, dir > 0 ? start_index : end_index, dir > 0 ? end_index : start_index,
                         "learned-range variance needs >= 2 timesteps"))) return rc;
   const bool use_cfg = guided != 0;   // forward_with_cfg semantics for ANY scale (latte.py:379-398 has no threshold)
-  if ((rc = chain_check(who, e, s, batch, use_cfg, y, true))) return rc;
+  if ((rc = chain_check(who, e, s, batch, use_cfg, y, true, ws && ws->valid() ? ws->count() : 1))) return rc;
   const int HW = e->H * e->H;
+  if (ws && (rc = chain_window_check(who, e, *ws, batch))) return rc;
   if (kn) {
     if ((rc = known_method_check(who, method, kn->resample))) return rc;
     if (!kn->known || !kn->mask) return fail(LATTE_ERR_INVALID, who + ": known and mask are required");
@@ -536,9 +589,11 @@ int sampler_chain(const std::string& who, latte_engine* e, const latte_schedule_
   // Unconditional models have one row per step shared by every sample (row stride 0).  The adaLN weights (0.9 GB
   // fp32) are then streamed once per 64 rows instead of once per denoising step.
   const int n_run = (end_index - start_index) * dir + 1;
+  const int frames = ws ? ws->L : e->F, rows = ws ? batch * ws->count() : batch;   // with windows the conditioning rows are per clip
+  if (ws && (rc = chain_window_prepare(e, *ws, y, batch, st, &y))) return rc;
   ChainCond cc;
-  if ((rc = chain_prepare(e, s, e->cfg.extras == 1 ? 1 : batch, n_run, st, &cc))) return rc;
-  const size_t numel = (size_t)batch * e->F * e->Cin * HW;
+  if ((rc = chain_prepare(e, s, e->cfg.extras == 1 ? 1 : rows, n_run, st, &cc))) return rc;
+  const size_t numel = (size_t)batch * frames * e->Cin * HW;
   const int reps = kn ? kn->resample : 1;
   NoiseCursor cur{kn == nullptr};
   // one blend at the level abar; its noise is the caller's next slab, or drawn in the kernel from the engine's stream
@@ -565,10 +620,11 @@ int sampler_chain(const std::string& who, latte_engine* e, const latte_schedule_
     float* x0 = trail_x0 ? trail_x0 + (size_t)k * numel : nullptr;
     for (int u = 1; u <= reps; ++u) {
       const KnownSlabs need = known_slabs(method, c, i, u, reps);   // a plain chain takes the step's noise only
-      if ((rc = run_forward(e, x, nullptr, y, batch, use_cfg, e->model_out, st, nullptr, mod_i, mstride))) return rc;
+      const float* mo;
+      if ((rc = chain_forward(e, ws, x, y, batch, use_cfg, mod_i, mstride, st, &mo))) return rc;
       const float* nz = nullptr;
       if (need.step && (rc = chain_noise(e, noise, cur.row(k), numel, st, &nz))) return rc;
-      if ((rc = launch_sampler_update(c, x, e->model_out, nz, batch, e->F, e->Cin, HW, use_cfg ? 1 : 0, x, x0, st))) return rc;
+      if ((rc = launch_sampler_update(c, x, mo, nz, batch, frames, e->Cin, HW, use_cfg ? 1 : 0, x, x0, st))) return rc;
       if (!kn) continue;
       if ((rc = blend(s->alphas_cumprod_prev[i], need.blend))) return rc;   // (1, 0) at i == 0: the known latents themselves
       if (need.jump) {   // back to level i: x <- sqrt(1 - beta_i) x + sqrt(beta_i) z, in place
@@ -965,22 +1021,28 @@ int latte_known_blend(float* x, const float* known, const float* mask, const flo
   return launch_known_blend(x, known, mask, noise, seed, offset, a, b, batch, frames, channels, hw, frames_inner, (hipStream_t)stream);
 }
 
-// ---- linear samplers as a plan (include/latte_amd.h; the table is latte_amd/schedulers.py: engine_plan())
-int latte_sample_plan_loop(latte_engine_t* e, int guided, float cfg_scale, float* x, const int64_t* y, int batch, int n_evals,
-                           const double* plan, const float* noise, float* trail_sample, void* stream) {
-  if (!e || !x || !plan || batch <= 0 || n_evals <= 0) return fail(LATTE_ERR_INVALID, "sample_plan_loop: bad arguments");
+}  // extern "C"
+
+namespace {
+// ---- linear samplers as a plan (include/latte_amd.h; the table is latte_amd/schedulers.py: engine_plan()): the body of
+// latte_sample_plan_loop, and latte_sample_plan_loop_windows (`ws`: x, the noise rows and the trail have ws->L frames)
+int plan_chain(const std::string& who, latte_engine* e, int guided, float cfg_scale, float* x, const int64_t* y, int batch, int n_evals,
+               const double* plan, const float* noise, float* trail_sample, hipStream_t st, const WindowSet* ws) {
+  if (!e || !x || !plan || batch <= 0 || n_evals <= 0) return fail(LATTE_ERR_INVALID, who + ": bad arguments");
   int rc = latte_engine_check_weights(e);
   if (rc) return rc;
   const bool use_cfg = guided != 0;   // forward_with_cfg semantics for ANY scale, as latte_sample_loop_ex
-  if ((rc = chain_check("sample_plan_loop", e, nullptr, batch, use_cfg, y, true))) return rc;
+  if ((rc = chain_check(who, e, nullptr, batch, use_cfg, y, true, ws && ws->valid() ? ws->count() : 1))) return rc;
   const int HW = e->H * e->H;
   if (n_evals <= LATTE_PLAN_MAX_EVALS && HW % 4)   // plan_check refuses a longer table first
-    return fail(LATTE_ERR_INVALID, "sample_plan_loop: H * W must be a multiple of 4 (16-byte accesses of the step kernel)");
+    return fail(LATTE_ERR_INVALID, who + ": H * W must be a multiple of 4 (16-byte accesses of the step kernel)");
   PlanInfo info;   // the engine may draw the noise of a row itself
-  if ((rc = plan_check("sample_plan_loop", plan, n_evals, LATTE_PLAN_MAX_EVALS, e->train_timesteps, noise != nullptr, true, &info))) return rc;
-  hipStream_t st = (hipStream_t)stream;
+  if ((rc = plan_check(who.c_str(), plan, n_evals, LATTE_PLAN_MAX_EVALS, e->train_timesteps, noise != nullptr, true, &info))) return rc;
+  if (ws && (rc = chain_window_check(who, e, *ws, batch))) return rc;
+  const int frames = ws ? ws->L : e->F, rows = ws ? batch * ws->count() : batch;   // with windows the conditioning rows are per clip
+  if (ws && (rc = chain_window_prepare(e, *ws, y, batch, st, &y))) return rc;
   const size_t per = (size_t)e->F * e->Cin * HW;
-  const size_t numel = (size_t)batch * per;
+  const size_t numel = (size_t)batch * frames * e->Cin * HW;   // <= rows * per <= max_batch * per: the ring and plan_xin hold it
   if (!e->plan_xin) {   // first use: the ring and the scaled model input
     for (auto& h : e->plan_hist)
       if (!h && (rc = e->arena.alloc(&h, (size_t)e->max_batch * per, false))) return rc;
@@ -991,7 +1053,7 @@ int latte_sample_plan_loop(latte_engine_t* e, int guided, float cfg_scale, float
   if ((rc = compute_temb_rows(e, info.ts.data(), n_evals, e->plan_temb, st))) return rc;
   ChainCond cc;
   cc.temb = e->plan_temb;
-  cc.bu = e->cfg.extras == 1 ? 1 : batch;
+  cc.bu = e->cfg.extras == 1 ? 1 : rows;
   if ((rc = chain_row_buffers(e, n_evals, &cc))) return rc;
   // what the denoiser reads: x itself when every in_scale is 1, else in_scale * x kept beside it by the step kernel
   float* x_in = info.scaled ? e->plan_xin : x;
@@ -1004,16 +1066,67 @@ int latte_sample_plan_loop(latte_engine_t* e, int guided, float cfg_scale, float
     const float* mod_k;
     int mstride;
     if ((rc = chain_mod(e, &cc, y, k, n_evals - 1, st, &mod_k, &mstride))) return rc;
-    if ((rc = run_forward(e, x_in, nullptr, y, batch, use_cfg, e->model_out, st, nullptr, mod_k, mstride))) return rc;
+    const float* mo;
+    if ((rc = chain_forward(e, ws, x_in, y, batch, use_cfg, mod_k, mstride, st, &mo))) return rc;
     const LinearStep s = plan_step(plan, k, n_evals, cfg_scale);
     const float* nz = nullptr;
     if (plan[(size_t)k * LATTE_PLAN_COLS + P_CN] != 0.0 && (rc = chain_noise(e, noise, k, numel, st, &nz))) return rc;
-    if ((rc = launch_linear_step(x, k + 1 == n_evals ? x : x_in, e->model_out, ring.h1(), ring.h2(), ring.h3(), nz, ring.write(), batch,
-                                 e->Cin, e->Cout, e->F, HW, use_cfg ? 1 : 0, s, st))) return rc;
+    if ((rc = launch_linear_step(x, k + 1 == n_evals ? x : x_in, mo, ring.h1(), ring.h2(), ring.h3(), nz, ring.write(), batch,
+                                 e->Cin, e->Cout, frames, HW, use_cfg ? 1 : 0, s, st))) return rc;
     if (s.push) ring.push();
     if ((rc = chain_trail(trail_sample, k, x, numel, st))) return rc;
   }
   return LATTE_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int latte_sample_plan_loop(latte_engine_t* e, int guided, float cfg_scale, float* x, const int64_t* y, int batch, int n_evals,
+                           const double* plan, const float* noise, float* trail_sample, void* stream) {
+  return plan_chain("sample_plan_loop", e, guided, cfg_scale, x, y, batch, n_evals, plan, noise, trail_sample, (hipStream_t)stream, nullptr);
+}
+
+// ---- overlapping temporal windows (include/latte_amd.h)
+int latte_window_plan(int total_frames, int frames, int stride, int* starts_out, int* counts_out, int cap) {
+  const WindowSet ws{total_frames, frames, stride};
+  if (window_check("window_plan", ws, 4)) return -LATTE_ERR_INVALID;
+  const int W = ws.count();
+  if (starts_out && cap < W) return -fail(LATTE_ERR_INVALID, "window_plan: starts_out holds fewer than the windows");
+  for (int w = 0; starts_out && w < W; ++w) starts_out[w] = ws.start(w);
+  for (int f = 0; counts_out && f < total_frames; ++f) {
+    counts_out[f] = 0;
+    for (int w = 0; w < W; ++w) counts_out[f] += f >= ws.start(w) && f < ws.start(w) + frames;
+  }
+  return W;
+}
+
+int latte_window_gather(const float* x, float* clips, int groups, int total_frames, int frames, int stride, int channels, int hw,
+                        int frames_inner, void* stream) {
+  return launch_window_gather(x, clips, groups, WindowSet{total_frames, frames, stride}, channels, hw, frames_inner, (hipStream_t)stream);
+}
+
+int latte_window_merge(const float* out, float* merged, int groups, int total_frames, int frames, int stride, int channels, int hw,
+                       int frames_inner, void* stream) {
+  return launch_window_merge(out, merged, groups, WindowSet{total_frames, frames, stride}, channels, hw, frames_inner, (hipStream_t)stream);
+}
+
+int latte_sample_loop_windows(latte_engine_t* e, const latte_schedule_t* s, int method, float eta, int clip_denoised, int guided,
+                              float cfg_scale, float* x, const int64_t* y, int batch, int start_index, int end_index, const float* noise,
+                              float* trail_sample, float* trail_x0, int total_frames, int stride, void* stream) {
+  if (!e) return fail(LATTE_ERR_INVALID, "sample_loop_windows: null argument");
+  const WindowSet ws{total_frames, e->F, stride};
+  return sampler_chain("sample_loop_windows", e, s, method, -1, eta, clip_denoised, guided, cfg_scale, x, y, batch, start_index, end_index,
+                       nullptr, noise, trail_sample, trail_x0, (hipStream_t)stream, &ws);
+}
+
+int latte_sample_plan_loop_windows(latte_engine_t* e, int guided, float cfg_scale, float* x, const int64_t* y, int batch, int n_evals,
+                                   const double* plan, const float* noise, float* trail_sample, int total_frames, int stride,
+                                   void* stream) {
+  if (!e) return fail(LATTE_ERR_INVALID, "sample_plan_loop_windows: bad arguments");
+  const WindowSet ws{total_frames, e->F, stride};
+  return plan_chain("sample_plan_loop_windows", e, guided, cfg_scale, x, y, batch, n_evals, plan, noise, trail_sample, (hipStream_t)stream,
+                    &ws);
 }
 
 // fp32 device copies of the schedule tables for the batched-timestep kernels (one device per schedule object)

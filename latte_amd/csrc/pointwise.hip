@@ -1053,6 +1053,58 @@ __global__ void known_blend_kernel(float* __restrict__ x, const float* __restric
   }
 }
 
+// Overlapping temporal windows of a long latent: window w of W covers frames [s_w, s_w + F) of the L, with
+// s_w = min(w * stride, L - F) (common.h: WindowSet).  One thread per 16-byte access (hw4 = HW / 4), as known_blend_kernel.
+// Gather: clips[g W + w] = x[g, s_w : s_w + F].  frames_inner = 0: x [G, L, C, HW] -> clips [G W, F, C, HW]; 1: x [G, C, L, HW] ->
+// clips [G W, C, F, HW].  `quads` counts the float4 of the clips.
+__global__ void window_gather_kernel(const float* __restrict__ x, float* __restrict__ clips, size_t quads, int L, int F, int stride, int W,
+                                     int C, int hw4, int frames_inner) {
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (size_t)gridDim.x * blockDim.x) {
+    const size_t r4 = q % hw4, row = q / hw4;   // row = (clip F + f) C + c, or (clip C + c) F + f
+    const size_t clip = row / ((size_t)F * C), in = row % ((size_t)F * C);
+    const size_t f = frames_inner ? in % F : in / C, c = frames_inner ? in / F : in % C;
+    const size_t g = clip / W, w = clip % W;
+    const size_t s = (size_t)min((int)w * stride, L - F);
+    const size_t src = frames_inner ? (g * C + c) * L + s + f : (g * L + s + f) * C + c;
+    ((float4*)clips)[q] = ((const float4*)x)[src * hw4 + r4];
+  }
+}
+
+// Merge: merged[g, f] = (sum over the windows covering f, ascending w, of out[g W + w, f - s_w]) / count(f), in fp32, one thread per
+// 16-byte access of the merged tensor and no atomics; a frame one window covers is copied.  frames_inner = 0: out [G W, F, C, HW] ->
+// merged [G, L, C, HW] (what both engines' forwards write); 1: out [G W, C, F, HW] -> merged [G, C, L, HW].  `quads` counts the
+// float4 of the merged tensor.
+__global__ void window_merge_kernel(const float* __restrict__ out, float* __restrict__ merged, size_t quads, int L, int F, int stride,
+                                    int W, int C, int hw4, int frames_inner) {
+#pragma clang fp contract(off)
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (size_t)gridDim.x * blockDim.x) {
+    const size_t r4 = q % hw4, row = q / hw4;   // row = (g L + f) C + c, or (g C + c) L + f
+    const size_t g = row / ((size_t)L * C), in = row % ((size_t)L * C);
+    const int f = (int)(frames_inner ? in % L : in / C);
+    const size_t c = frames_inner ? in / L : in % C;
+    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    int n = 0;
+    for (int w = 0; w < W; ++w) {
+      const int s = min(w * stride, L - F);
+      if (f < s || f >= s + F) continue;
+      const size_t clip = g * W + w, fw = (size_t)(f - s);
+      const size_t src = frames_inner ? (clip * C + c) * F + fw : (clip * F + fw) * C + c;
+      const float4 v = ((const float4*)out)[src * hw4 + r4];
+      if (n == 0) {
+        acc = v;
+      } else {
+        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+      }
+      ++n;
+    }
+    if (n > 1) {
+      const float d = (float)n;
+      acc.x /= d; acc.y /= d; acc.z /= d; acc.w /= d;
+    }
+    ((float4*)merged)[q] = acc;
+  }
+}
+
 inline int grid_for(size_t n, int block) {
   size_t g = (n + block - 1) / block;
   return (int)(g > 4096 ? 4096 : (g == 0 ? 1 : g));
@@ -1452,6 +1504,40 @@ int launch_known_blend(float* x, const float* known, const float* mask, const fl
   const size_t quads = (size_t)batch * frames * channels * (hw / 4);
   hipLaunchKernelGGL(known_blend_kernel, dim3(grid_for(quads, 256)), dim3(256), 0, st, x, known, mask, z, a, b, quads, frames, channels,
                      hw / 4, frames_inner ? 1 : 0, (unsigned long long)seed, (unsigned long long)offset);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+
+int window_check(const std::string& who, const WindowSet& ws, int hw) {
+  if (ws.F < 1 || ws.L < ws.F) return fail(LATTE_ERR_INVALID, who + ": total_frames must be at least the model's frames");
+  if (ws.stride < 1 || ws.stride > ws.F) return fail(LATTE_ERR_INVALID, who + ": stride must be in 1 ... frames (every frame is covered)");
+  if (hw <= 0 || hw % 4) return fail(LATTE_ERR_INVALID, who + ": H * W must be a multiple of 4 (16-byte accesses of the window kernels)");
+  return LATTE_OK;
+}
+
+int launch_window_gather(const float* x, float* clips, int groups, const WindowSet& ws, int channels, int hw, int frames_inner,
+                         hipStream_t st) {
+  if (!x || !clips) return fail(LATTE_ERR_INVALID, "window_gather: null argument");
+  if (groups <= 0 || channels <= 0) return fail(LATTE_ERR_INVALID, "window_gather: bad shape");
+  int rc = window_check("window_gather", ws, hw);
+  if (rc) return rc;
+  const int W = ws.count();
+  const size_t quads = (size_t)groups * W * ws.F * channels * (hw / 4);
+  hipLaunchKernelGGL(window_gather_kernel, dim3(grid_for(quads, 256)), dim3(256), 0, st, x, clips, quads, ws.L, ws.F, ws.stride, W, channels,
+                     hw / 4, frames_inner ? 1 : 0);
+  LATTE_HIP(hipGetLastError());
+  return LATTE_OK;
+}
+
+int launch_window_merge(const float* out, float* merged, int groups, const WindowSet& ws, int channels, int hw, int frames_inner,
+                        hipStream_t st) {
+  if (!out || !merged) return fail(LATTE_ERR_INVALID, "window_merge: null argument");
+  if (groups <= 0 || channels <= 0) return fail(LATTE_ERR_INVALID, "window_merge: bad shape");
+  int rc = window_check("window_merge", ws, hw);
+  if (rc) return rc;
+  const size_t quads = (size_t)groups * ws.L * channels * (hw / 4);
+  hipLaunchKernelGGL(window_merge_kernel, dim3(grid_for(quads, 256)), dim3(256), 0, st, out, merged, quads, ws.L, ws.F, ws.stride, ws.count(),
+                     channels, hw / 4, frames_inner ? 1 : 0);
   LATTE_HIP(hipGetLastError());
   return LATTE_OK;
 }

@@ -84,6 +84,9 @@ struct latte_t2v {
   int tsteps_cap = 0;
   // latte_t2v_guided_linear_loop: a ring of three remembered outputs and the scaled denoiser input, max_batch / 2 latents each
   float *hist[3] = {nullptr, nullptr, nullptr}, *x_scaled = nullptr;
+  // overlapping temporal windows (taken from the arena by the first windowed loop): the gathered clips, max_batch / 2 latents, and the
+  // merged output of the guidance pair (the size of out_bf)
+  float *win_clips = nullptr, *win_merged = nullptr;
   WeightSlots weights;
   DeviceArena arena;
 };
@@ -424,15 +427,19 @@ int latte_t2v_forward(latte_t2v_t* e, const float* x, const int64_t* t, const fl
   return launch_permute_cf(e->out_bf, out, batch, c.out_channels, e->F, e->H * e->H, 0, st);   // back to [B, C, F, H, W]
 }
 
-// The argument block the three guided loops share: loaded weights, the guidance pair within max_batch, its text context, C or 2C outputs
-static int t2v_chain_check(const std::string& who, latte_t2v* e, int samples) {
+// The argument block the guided loops share: loaded weights, the guidance pair within max_batch, its text context, C or 2C outputs.
+// With windows (`ws`) the window set is checked behind the weights, and the pair is 2 * samples * W clips.
+static int t2v_chain_check(const std::string& who, latte_t2v* e, int samples, const WindowSet* ws = nullptr) {
   int rc = latte_t2v_check_weights(e);
   if (rc) return rc;
-  const int B = 2 * samples;
-  if (B > e->max_batch) return fail(LATTE_ERR_STATE, who + ": the guidance pair exceeds max_batch of the engine");
+  if (ws && (rc = window_check(who, *ws, e->H * e->H))) return rc;
+  const int64_t B = 2 * (int64_t)samples * (ws ? ws->count() : 1);
+  if (B > e->max_batch)
+    return fail(LATTE_ERR_STATE, who + (ws ? ": the clips of the guidance pair (2 * samples * windows) exceed max_batch of the engine"
+                                           : ": the guidance pair exceeds max_batch of the engine"));
   if (e->txt_batch != B)
     return fail(LATTE_ERR_STATE, who + ": install the text context of the guidance pair first "
-                                 "(latte_t2v_set_text with [negative | prompt] embeddings, 2 * samples rows)");
+                                 "(latte_t2v_set_text with [negative | prompt] embeddings, 2 * samples rows" + (ws ? " per window)" : ")"));
   const auto& c = e->cfg;
   if (c.out_channels != c.in_channels && c.out_channels != 2 * c.in_channels)
     return fail(LATTE_ERR_INVALID, who + ": out_channels must be C or 2C (learned sigma)");
@@ -446,16 +453,39 @@ static int t2v_upload_timesteps(latte_t2v* e, const int64_t* ts, int n, hipStrea
   return LATTE_OK;
 }
 
+// One evaluation of the guidance pair of a chain on x_in [samples, C, frames, HW], *out = where its output lies
+// ([2 * samples, frames, Cout, HW]): t2v_core itself, or with windows gather -> t2v_core on the 2 * samples * W clips -> merge.  The
+// window buffers come from the arena on first use.
+static int t2v_chain_forward(latte_t2v* e, const WindowSet* ws, const float* x_in, const int64_t* t, int samples, int enable_temporal,
+                             hipStream_t st, const float** out) {
+  const auto& c = e->cfg;
+  const int HW = e->H * e->H;
+  int rc;
+  if (ws) {
+    const size_t frame = (size_t)e->F * HW;
+    if (!e->win_clips && (rc = e->arena.alloc(&e->win_clips, (size_t)(e->max_batch / 2) * frame * c.in_channels, false))) return rc;
+    if (!e->win_merged && (rc = e->arena.alloc(&e->win_merged, (size_t)e->max_batch * frame * c.out_channels, false))) return rc;
+    if ((rc = launch_window_gather(x_in, e->win_clips, samples, *ws, c.in_channels, HW, 1, st))) return rc;
+    x_in = e->win_clips;
+  }
+  const int B = 2 * samples * (ws ? ws->count() : 1);
+  if ((rc = t2v_core(e, x_in, t, true, B, true, enable_temporal, st))) return rc;
+  *out = e->out_bf;
+  if (!ws) return LATTE_OK;
+  *out = e->win_merged;
+  return launch_window_merge(e->out_bf, e->win_merged, 2 * samples, *ws, c.out_channels, HW, 0, st);
+}
+
 // The guided DDIM loop (diffusers DDIMScheduler.step, eta = 0, no clipping).  With `known`, the known part of x is replaced at the level
 // each step reaches: noise slab 0 for the blend at alpha_t[0] before step 0, slab k + 1 for the blend at alpha_prev[k] after step k; the
 // last step blends with (1, 0).  known == NULL: no blends, no noise read.
 static int t2v_ddim_chain(const std::string& who, latte_t2v* e, float* x, int samples, int n_steps, const int64_t* timesteps,
                           const double* alpha_t, const double* alpha_prev, float guidance_scale, const float* known, const float* mask,
-                          const float* noise, int enable_temporal_attentions, hipStream_t st) {
-  int rc = t2v_chain_check(who, e, samples);
+                          const float* noise, int enable_temporal_attentions, hipStream_t st, const WindowSet* ws = nullptr) {
+  int rc = t2v_chain_check(who, e, samples, ws);
   if (rc) return rc;
   const auto& c = e->cfg;
-  const int B = 2 * samples, HW = e->H * e->H;
+  const int HW = e->H * e->H, frames = ws ? ws->L : e->F;
   if (known && HW % 4) return fail(LATTE_ERR_INVALID, who + ": H * W must be a multiple of 4 (16-byte accesses of the blend kernel)");
   if (n_steps > e->tsteps_cap) return fail(LATTE_ERR_INVALID, who + ": more than 1024 steps");
   for (int k = 0; k < n_steps; ++k)
@@ -470,10 +500,11 @@ static int t2v_ddim_chain(const std::string& who, latte_t2v* e, float* x, int sa
   };
   if (known && (rc = blend(alpha_t[0], noise))) return rc;
   for (int k = 0; k < n_steps; ++k) {
-    if ((rc = t2v_core(e, x, e->tsteps + k, true, B, true, enable_temporal_attentions, st))) return rc;
+    const float* mo;
+    if ((rc = t2v_chain_forward(e, ws, x, e->tsteps + k, samples, enable_temporal_attentions, st, &mo))) return rc;
     // Python-float coefficients times fp32 tensors
     const double at = alpha_t[k], ap = alpha_prev[k];
-    if ((rc = launch_t2v_guided_ddim(x, e->out_bf, samples, c.in_channels, c.out_channels, e->F, HW, guidance_scale,
+    if ((rc = launch_t2v_guided_ddim(x, mo, samples, c.in_channels, c.out_channels, frames, HW, guidance_scale,
                                      (float)std::sqrt(1.0 - at), (float)std::sqrt(at), (float)std::sqrt(ap),
                                      (float)std::sqrt(1.0 - ap), st))) return rc;
     if (known && (rc = blend(ap, k + 1 < n_steps ? noise + (size_t)(k + 1) * numel : nullptr))) return rc;
@@ -502,19 +533,18 @@ int latte_t2v_guided_ddim_loop_known(latte_t2v_t* e, float* x, int samples, int 
                         enable_temporal_attentions, (hipStream_t)stream);
 }
 
-int latte_t2v_guided_linear_loop(latte_t2v_t* e, float* x, int samples, int n_evals, const double* plan, const float* noise,
-                                 float guidance_scale, int enable_temporal_attentions, void* stream) {
-  if (!e || !x || !plan || samples <= 0 || n_evals <= 0) return fail(LATTE_ERR_INVALID, "t2v_guided_linear_loop: bad arguments");
-  int rc = t2v_chain_check("t2v_guided_linear_loop", e, samples);
+// latte_t2v_guided_linear_loop, and latte_t2v_guided_linear_loop_windows (`ws`: x and the noise rows have ws->L frames)
+static int t2v_linear_chain(const std::string& who, latte_t2v* e, float* x, int samples, int n_evals, const double* plan, const float* noise,
+                            float guidance_scale, int enable_temporal_attentions, hipStream_t st, const WindowSet* ws) {
+  if (!e || !x || !plan || samples <= 0 || n_evals <= 0) return fail(LATTE_ERR_INVALID, who + ": bad arguments");
+  int rc = t2v_chain_check(who, e, samples, ws);
   if (rc) return rc;
-  const int B = 2 * samples;
   const auto& c = e->cfg;
   PlanInfo info;   // no trained-range bound, and this engine draws no noise of its own
-  if ((rc = plan_check("t2v_guided_linear_loop", plan, n_evals, e->tsteps_cap, 0, noise != nullptr, false, &info))) return rc;
-  hipStream_t st = (hipStream_t)stream;
+  if ((rc = plan_check(who.c_str(), plan, n_evals, e->tsteps_cap, 0, noise != nullptr, false, &info))) return rc;
   if ((rc = t2v_upload_timesteps(e, info.ts.data(), n_evals, st))) return rc;
-  const int HW = e->H * e->H;
-  const size_t per_chain = (size_t)samples * c.in_channels * e->F * HW;
+  const int HW = e->H * e->H, frames = ws ? ws->L : e->F;
+  const size_t per_chain = (size_t)samples * c.in_channels * frames * HW;   // <= max_batch / 2 latents: the ring and x_scaled hold it
   // what the denoiser reads: x itself when every in_scale is 1, else in_scale * x kept beside it by the step kernel
   float* x_in = info.scaled ? e->x_scaled : x;
   if (info.scaled) {
@@ -523,14 +553,40 @@ int latte_t2v_guided_linear_loop(latte_t2v_t* e, float* x, int samples, int n_ev
   }
   HistRing ring{{e->hist[0], e->hist[1], e->hist[2]}};
   for (int k = 0; k < n_evals; ++k) {
-    if ((rc = t2v_core(e, x_in, e->tsteps + k, true, B, true, enable_temporal_attentions, st))) return rc;
+    const float* mo;
+    if ((rc = t2v_chain_forward(e, ws, x_in, e->tsteps + k, samples, enable_temporal_attentions, st, &mo))) return rc;
     const LinearStep s = plan_step(plan, k, n_evals, guidance_scale);
-    if ((rc = launch_t2v_guided_linear_step(x, k + 1 == n_evals ? x : x_in, e->out_bf, ring.h1(), ring.h2(), ring.h3(),
+    if ((rc = launch_t2v_guided_linear_step(x, k + 1 == n_evals ? x : x_in, mo, ring.h1(), ring.h2(), ring.h3(),
                                             noise ? noise + (size_t)k * per_chain : nullptr, ring.write(), samples, c.in_channels,
-                                            c.out_channels, e->F, HW, s, st))) return rc;
+                                            c.out_channels, frames, HW, s, st))) return rc;
     if (s.push) ring.push();
   }
   return LATTE_OK;
+}
+
+int latte_t2v_guided_linear_loop(latte_t2v_t* e, float* x, int samples, int n_evals, const double* plan, const float* noise,
+                                 float guidance_scale, int enable_temporal_attentions, void* stream) {
+  return t2v_linear_chain("t2v_guided_linear_loop", e, x, samples, n_evals, plan, noise, guidance_scale, enable_temporal_attentions,
+                          (hipStream_t)stream, nullptr);
+}
+
+// ---- overlapping temporal windows: the two guided loops on x [samples, C, total_frames, H, W] (include/latte_amd.h)
+int latte_t2v_guided_ddim_loop_windows(latte_t2v_t* e, float* x, int samples, int n_steps, const int64_t* timesteps, const double* alpha_t,
+                                       const double* alpha_prev, float guidance_scale, int enable_temporal_attentions, int total_frames,
+                                       int stride, void* stream) {
+  if (!e || !x || !timesteps || !alpha_t || !alpha_prev || samples <= 0 || n_steps <= 0)
+    return fail(LATTE_ERR_INVALID, "t2v_guided_ddim_loop_windows: bad arguments");
+  const WindowSet ws{total_frames, e->F, stride};
+  return t2v_ddim_chain("t2v_guided_ddim_loop_windows", e, x, samples, n_steps, timesteps, alpha_t, alpha_prev, guidance_scale, nullptr,
+                        nullptr, nullptr, enable_temporal_attentions, (hipStream_t)stream, &ws);
+}
+
+int latte_t2v_guided_linear_loop_windows(latte_t2v_t* e, float* x, int samples, int n_evals, const double* plan, const float* noise,
+                                         float guidance_scale, int enable_temporal_attentions, int total_frames, int stride, void* stream) {
+  if (!e) return fail(LATTE_ERR_INVALID, "t2v_guided_linear_loop_windows: bad arguments");
+  const WindowSet ws{total_frames, e->F, stride};
+  return t2v_linear_chain("t2v_guided_linear_loop_windows", e, x, samples, n_evals, plan, noise, guidance_scale,
+                          enable_temporal_attentions, (hipStream_t)stream, &ws);
 }
 
 }  // extern "C"

@@ -10,7 +10,9 @@
 * ``linear_sample_loop`` (not in the reference): Euler, Euler-ancestral, Heun and DPM-Solver++(2M) on the diffusion's own
   timesteps, as ONE ``latte_sample_plan_loop`` call for a ``latte_amd.Latte`` method;
 * ``known_sample_loop`` (not in the reference): DDIM / DDPM with part of the clip held fixed (prediction, interpolation, inpainting by
-  replacement), as ``latte_sample_loop_known`` calls for a ``latte_amd.Latte`` method.
+  replacement), as ``latte_sample_loop_known`` calls for a ``latte_amd.Latte`` method;
+* ``window_sample_loop`` (not in the reference): clips longer than ``num_frames`` by overlapping temporal windows, as
+  ``latte_sample_loop_windows`` / ``latte_sample_plan_loop_windows`` calls for a ``latte_amd.Latte`` method.
 """
 import ctypes
 from types import SimpleNamespace
@@ -21,6 +23,7 @@ import torch
 from . import _lib
 from ._lib import LatteError, check, load_library, ptr, stream_ptr
 from .known import known_blend, level_coefs
+from .windows import repeat_per_window, window_gather, window_merge, window_starts
 from .models import Latte
 from .schedulers import (DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler,
                          HeunDiscreteScheduler)
@@ -92,19 +95,23 @@ class SpacedDiffusion:
                 return owner, True
         return None, False
 
-    def _engine_chain(self, model, img, model_kwargs, hooks=False):
+    def _engine_chain(self, model, img, model_kwargs, hooks=False, windows=None):
         """The engine path of a loop: None unless `model` is a bound latte_amd.Latte method called with kwargs the engine knows and no
         hooks; else what its chain calls take -- eng, x32 (`img` on the model's device, sampled in place), y64, B, uses_cfg, cfg_scale --
-        with the text embedding installed."""
+        with the text embedding installed.  ``windows`` (window_sample_loop): `img` is a long clip, the engine holds B * windows clips
+        and the text embedding is installed per clip."""
         owner, uses_cfg = self._engine_model(model)
         if owner is None or hooks or not set(model_kwargs) <= {"y", "use_fp16", "cfg_scale", "text_embedding"}:
             return None
         _lib.require_gpu()
         B = img.shape[0]
-        x32, _, y64 = owner._prep(img, torch.zeros(B, dtype=torch.int64), model_kwargs.get("y"))
+        x32, _, y64 = owner._prep(img, torch.zeros(B, dtype=torch.int64), model_kwargs.get("y"),
+                                   frames=None if windows is None else img.shape[1])
+        windows = windows or 1
         cfg_scale = float(model_kwargs.get("cfg_scale", 7.0)) if uses_cfg else 1.0
-        eng = owner.engine(B, guided=uses_cfg)
-        owner._set_text(model_kwargs.get("text_embedding"), B, guided=uses_cfg)
+        eng = owner.engine(B * windows, guided=uses_cfg)
+        te = model_kwargs.get("text_embedding")
+        owner._set_text(te if te is None or windows == 1 else te.repeat_interleave(windows, dim=0), B * windows, guided=uses_cfg)
         return SimpleNamespace(eng=eng, x32=x32, y64=y64, B=B, uses_cfg=int(uses_cfg), cfg_scale=cfg_scale)
 
     @staticmethod
@@ -505,6 +512,130 @@ class SpacedDiffusion:
         return self._last_sample(self._known_loop(method, model, shape, known, known_mask, noise, clip_denoised, denoised_fn, cond_fn,
                                                   model_kwargs, device, progress, eta, resample, start_index, end_index, chain_noise,
                                                   blend_start, False))
+
+    # ------------------------------------------------------------------ clips longer than num_frames (not in the reference)
+    WINDOW_METHODS = ("ddim", "ddpm") + tuple(LINEAR_METHODS)
+
+    def _window_loop(self, model, shape, noise, method, stride, clip_denoised, model_kwargs, eta, device, progress, step_noise,
+                     num_frames, progressive):
+        if method not in self.WINDOW_METHODS:
+            raise LatteError(f"window_sample_loop: method must be one of {sorted(self.WINDOW_METHODS)}, got {method!r}")
+        owner = self._engine_model(model)[0]
+        F = num_frames or getattr(owner if owner is not None else getattr(model, "__self__", model), "num_frames", None)
+        if F is None:
+            raise LatteError("window_sample_loop: pass num_frames, the clip length of a model callable that (like the object it is "
+                             "bound to) carries no num_frames")
+        F = int(F)
+        assert isinstance(shape, (tuple, list))
+        if len(shape) != 5:
+            raise LatteError("shape must be [N, L, C, H, W]")
+        B, L, C, H, Wd = (int(v) for v in shape)
+        stride = max(1, F // 2) if stride is None else int(stride)
+        W = len(window_starts(L, F, stride))                       # refuses L < F and a stride outside 1 ... F
+        if (H * Wd) % 4:
+            raise LatteError("window_sample_loop: H * W must be a multiple of 4 (16-byte accesses of the window kernels)")
+        linear = method in LINEAR_METHODS
+        sch = plan = None
+        if linear:
+            sch = self.linear_scheduler(method)
+            plan = np.ascontiguousarray(sch.engine_plan(), dtype=np.float64)
+        _lib.require_gpu()
+        model_kwargs = dict(model_kwargs or {})
+        device = self._device(model, device, noise)
+        img = noise if noise is not None else torch.randn(*shape, device=device)
+        img = img.to(device=device, dtype=torch.float32).contiguous().clone()
+        if tuple(img.shape) != (B, L, C, H, Wd):
+            raise LatteError(f"window_sample_loop: noise must be {(B, L, C, H, Wd)}, got {tuple(img.shape)}")
+        if linear:
+            img = img * float(sch.init_noise_sigma)
+        n = plan.shape[0] if linear else self.num_timesteps
+        needs_noise = method == "ddpm" or (method == "ddim" and eta != 0.0)
+        nz_all = None
+        if step_noise is not None:
+            if tuple(step_noise.shape) != (n,) + tuple(img.shape):
+                raise LatteError(f"step_noise must be [{n}, ...latents]: one slab per denoiser evaluation of {method!r}")
+            nz_all = step_noise.to(device=device, dtype=torch.float32).contiguous()
+        ec = self._engine_chain(model, img, model_kwargs, windows=W)
+        lib = load_library()
+        if ec is not None and linear:
+            # ---- whole chain inside the engine: one call, one trail
+            check(lib.latte_engine_set_option(ec.eng, b"train_timesteps", self.original_num_steps))
+
+            def call(first, last, trail, _):
+                check(lib.latte_sample_plan_loop_windows(ec.eng, ec.uses_cfg, ec.cfg_scale, ptr(ec.x32), ptr(ec.y64), ec.B, n,
+                                                         plan.ctypes.data, ptr(nz_all), trail, L, stride, stream_ptr()))
+                return nz_all
+
+            yield from self._engine_run(ec, 0, n - 1, n, progressive, call, x0_trail=False)
+            return
+        if ec is not None:
+            # ---- whole chain inside the engine, in segments of consecutive steps as _loop segments its noise
+            seg = max(1, min(n, self.SEGMENT_BYTES // max(ec.x32.numel() * 4, 1)))
+
+            def call(i, lo, trail_s, trail_0):
+                nz = None
+                if needs_noise:   # row k of the segment is read at its k-th step: index i - k
+                    nz = (nz_all[n - 1 - i:n - lo] if nz_all is not None
+                          else torch.stack([torch.randn_like(ec.x32) for _ in range(i - lo + 1)])).contiguous()
+                check(lib.latte_sample_loop_windows(ec.eng, self._h, _METHOD[method], float(eta), int(bool(clip_denoised)), ec.uses_cfg,
+                                                    ec.cfg_scale, ptr(ec.x32), ptr(ec.y64), ec.B, i, lo, ptr(nz), trail_s, trail_0, L,
+                                                    stride, stream_ptr()))
+                return nz
+
+            yield from self._engine_run(ec, n - 1, 0, seg, progressive, call)
+            return
+        # ---- generic model callable, step by step: gather, the model on the clips, latte_window_merge, the existing step
+        kw = repeat_per_window(model_kwargs, B, W)
+
+        def denoise(x, t):
+            tt = torch.full((B * W,), t, device=x.device, dtype=torch.int64)
+            out = model(window_gather(x, F, stride), tt, **kw)
+            if isinstance(out, tuple):
+                out = out[0]
+            return window_merge(out.float().contiguous(), L, stride)
+
+        if linear:
+            for k, t in self._progress(list(enumerate(sch.timesteps.tolist())), progress):
+                out = denoise(sch.scale_model_input(img, t).contiguous(), t)   # ORIGINAL timesteps, as _linear_loop
+                if out.shape[2] not in (C, 2 * C):
+                    raise AssertionError(f"model output has {out.shape[2]} channels for {C}-channel latents")
+                img = sch.step(out[:, :, :C], t, img, return_dict=False, noise=None if nz_all is None else nz_all[k])[0]
+                yield {"sample": img, "pred_xstart": None}
+            return
+        for k, i in enumerate(self._progress(list(range(n))[::-1], progress)):
+            out = denoise(img, self.timestep_map[i])
+            nz = None
+            if needs_noise:
+                nz = nz_all[k] if nz_all is not None else torch.randn_like(img)
+            r = self._step(method, out, img, i, nz, eta, clip_denoised)
+            yield r
+            img = r["sample"]
+
+    def window_sample_loop_progressive(self, model, shape, noise=None, method="ddim", stride=None, clip_denoised=True,
+                                       model_kwargs=None, eta=0.0, device=None, progress=False, step_noise=None, num_frames=None):
+        """``window_sample_loop`` yielding {"sample", "pred_xstart"} after every step (``pred_xstart`` is None for the linear
+        methods, one item per denoiser evaluation)."""
+        yield from self._window_loop(model, shape, noise, method, stride, clip_denoised, model_kwargs, eta, device, progress, step_noise,
+                                     num_frames, True)
+
+    def window_sample_loop(self, model, shape, noise=None, method="ddim", stride=None, clip_denoised=True, model_kwargs=None, eta=0.0,
+                           device=None, progress=False, step_noise=None, num_frames=None):
+        """A clip of ``shape`` = [N, L, C, H, W] with L >= the model's ``num_frames`` F, by temporal co-denoising on unchanged weights
+        (Gen-L-Video / MultiDiffusion along time; not in the reference; F is read from the model or the object the callable is bound
+        to, else ``num_frames`` gives it): at every denoiser evaluation the model runs on the
+        W = ceil((L - F) / stride) + 1 overlapping F-frame windows of the long latent (``latte_amd.window_starts``; ``stride`` in
+        1 ... F, default F // 2), the outputs are averaged with uniform weights where windows overlap, and ONE ordinary update of
+        ``method`` -- "ddim" (``eta``), "ddpm", or a linear one ("euler", "euler_a", "heun", "dpmsolver++" on ``linear_scheduler``'s
+        plan; ``clip_denoised`` and ``eta`` do not apply) -- is applied to the long latent.  L == F is the plain loop bit for bit.
+        With ``model.forward`` / ``model.forward_with_cfg`` of a ``latte_amd.Latte`` and known kwargs the chain is ONE
+        ``latte_sample_loop_windows`` call per segment / ONE ``latte_sample_plan_loop_windows`` call, every clip of the batch in
+        one forward (the engine is sized to N * W clips); any other callable is called on the gathered clips with every
+        ``model_kwargs`` tensor of leading dimension N repeated per window, then ``latte_window_merge`` and the existing step.
+        ``step_noise`` [steps or evaluations, ...latents] gives the draws to either path in execution order; without it the
+        DDPM / DDIM paths draw one ``torch.randn_like`` per step and "euler_a" draws as ``linear_sample_loop`` does.  No hooks and no
+        known region.  Nothing is claimed about sample quality: the arithmetic is the stated scheme."""
+        return self._last_sample(self._window_loop(model, shape, noise, method, stride, clip_denoised, model_kwargs, eta, device, progress,
+                                                   step_noise, num_frames, False))
 
     # ------------------------------------------------------------------ DDIM inversion (gd:566-602)
     def _reverse_loop(self, model, x, clip_denoised, denoised_fn, cond_fn, model_kwargs, progress, start_index, end_index,

@@ -284,13 +284,14 @@ class Latte(nn.Module):
             check(load_library().latte_engine_set_text_embedding(self.engine(B, guided), ptr(te), B, stream_ptr()))
         self._text_keepalive = te     # the projection kernel is stream-ordered; keep its input alive
 
-    def _prep(self, x, t, y):
+    def _prep(self, x, t, y, frames=None):
+        """``frames``: the length of a long clip sampled with temporal windows (default: ``num_frames``)."""
         if x.dim() != 5:
             raise LatteError("x must be [B, F, C, H, W]")
         B, F, C, H, W = x.shape
-        if (F, C, H, W) != (self.num_frames, self.in_channels, self.input_size, self.input_size):
+        if (F, C, H, W) != (frames or self.num_frames, self.in_channels, self.input_size, self.input_size):
             raise LatteError(f"input shape {tuple(x.shape)} does not match the model "
-                             f"(F={self.num_frames}, C={self.in_channels}, H=W={self.input_size})")
+                             f"(F={frames or self.num_frames}, C={self.in_channels}, H=W={self.input_size})")
         dev = self.pos_embed.device
         x32 = x.to(device=dev, dtype=torch.float32).contiguous()
         t64 = t.to(device=dev, dtype=torch.int64).contiguous()

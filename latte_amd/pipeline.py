@@ -282,13 +282,19 @@ class LattePipeline:
                  num_images_per_prompt=1, video_length=None, height=None, width=None, eta=0.0, generator=None, latents=None,
                  prompt_embeds=None, negative_prompt_embeds=None, output_type="pil", return_dict=True, callback=None,
                  callback_steps=1, clean_caption=True, mask_feature=True, enable_temporal_attentions=True,
-                 enable_vae_temporal_decoder=False, known_latents=None, known_mask=None):
-        """``known_latents`` [B, 4, F, h, w] with ``known_mask`` [B, F, h, w] (``latte_amd.known_mask``; 1 = known) hold part of the clip
+                 enable_vae_temporal_decoder=False, known_latents=None, known_mask=None, window_stride=None):
+        """``window_stride`` (not in the reference; None = off): ``video_length`` may exceed the transformer's by temporal co-denoising --
+        at every step the transformer runs on the overlapping windows of the long latents (``latte_amd.window_starts``), the
+        prompt embeddings repeated per window, and the window outputs are averaged before the scheduler's one update (DESIGN.md
+        section 4.10e).  The chain runs inside the engine under the rule of the plain call; decode covers every frame.
+        ``known_latents`` [B, 4, F, h, w] with ``known_mask`` [B, F, h, w] (``latte_amd.known_mask``; 1 = known) hold part of the clip
         fixed and generate the rest (not in the reference): before the first step and after every step the known part of the latents
         is overwritten with ``known_latents`` diffused to the level the latents are at, the clean ones after the last step.  DDIM
         scheduler of latte_amd at eta = 0 only; the noise comes from ``generator``, one latent-shaped draw per step, in slab order."""
         if (known_latents is None) != (known_mask is None):
             raise LatteError("known_latents and known_mask come together")
+        if window_stride is not None and known_latents is not None:
+            raise LatteError("window_stride: no known-region sampling on a windowed clip")
         if enable_vae_temporal_decoder and not getattr(self.vae, "_TEMPORAL", False):
             raise LatteError("enable_vae_temporal_decoder=True needs a latte_amd.AutoencoderKLTemporalDecoder as the pipeline's vae "
                              "(sample_t2x.py:31-32 loads it from subfolder 'vae_temporal_decoder')")
@@ -324,6 +330,14 @@ class LattePipeline:
         if "generator" in params:
             extra["generator"] = generator
         added_cond_kwargs = {"resolution": None, "aspect_ratio": None}
+        tr = self.transformer
+        if window_stride is not None:
+            from .windows import window_gather, window_merge, window_starts
+            if latents.dim() != 5 or (latents.shape[3] * latents.shape[4]) % 4:
+                raise LatteError("window_stride: latents must be [b, C, L, h, w] with h * w a multiple of 4")
+            window_stride = int(window_stride)
+            windows = len(window_starts(latents.shape[2], cfg.video_length, window_stride))   # refuses a bad length / stride
+            prompt_embeds = prompt_embeds.repeat_interleave(windows, dim=0)                   # row g W + w = row g: [negative | prompt] kept
         if known_latents is not None:
             latents = self._known_loop(latents, known_latents, known_mask, steps, prompt_embeds, do_cfg, guidance_scale, eta, generator,
                                        callback, callback_steps, enable_temporal_attentions)
@@ -331,9 +345,12 @@ class LattePipeline:
         fused = self._fused_loop(steps, do_cfg, eta, callback, latent_channels) if known_latents is None else None
         if fused is not None:
             # the whole guided DDIM chain inside the engine: no torch op between the first and the last step
-            self.transformer.set_text(prompt_embeds)
-            latents = self.transformer.guided_ddim_loop(latents, fused[0], fused[1], fused[2], guidance_scale,
-                                                        enable_temporal_attentions)
+            tr.set_text(prompt_embeds)
+            if window_stride is None:
+                latents = tr.guided_ddim_loop(latents, fused[0], fused[1], fused[2], guidance_scale, enable_temporal_attentions)
+            else:
+                latents = tr.guided_ddim_loop_windows(latents, fused[0], fused[1], fused[2], guidance_scale, window_stride,
+                                                      enable_temporal_attentions)
             steps = []
         plan = self._fused_plan(do_cfg, callback, latent_channels) if fused is None and known_latents is None else None
         if plan is not None:
@@ -343,17 +360,26 @@ class LattePipeline:
             from .schedulers import P_CN, draw_noise
             if (plan[:, P_CN] != 0.0).any():
                 noise = torch.stack([draw_noise(latents.shape, generator, device, latents.dtype) for _ in range(plan.shape[0])])
-            self.transformer.set_text(prompt_embeds)
-            latents = self.transformer.guided_linear_loop(latents, plan, noise, guidance_scale, enable_temporal_attentions)
+            tr.set_text(prompt_embeds)
+            if window_stride is None:
+                latents = tr.guided_linear_loop(latents, plan, noise, guidance_scale, enable_temporal_attentions)
+            else:
+                latents = tr.guided_linear_loop_windows(latents, plan, noise, guidance_scale, window_stride, enable_temporal_attentions)
             steps = []
         for i, t in enumerate(steps):
             latent_model_input = torch.cat([latents] * 2) if do_cfg else latents
             latent_model_input = self.scheduler.scale_model_input(latent_model_input, t)
             current = t if torch.is_tensor(t) else torch.tensor([t], dtype=torch.int64, device=device)
+            if window_stride is not None:   # the clips of every row of the (doubled) batch
+                latent_model_input = window_gather(latent_model_input.to(dtype=torch.float32).contiguous(), cfg.video_length,
+                                                   window_stride, frames_inner=True)
             current = current.reshape(-1)[:1].to(device).expand(latent_model_input.shape[0])
             noise_pred = self.transformer(latent_model_input, encoder_hidden_states=prompt_embeds, timestep=current,
                                           added_cond_kwargs=added_cond_kwargs,
                                           enable_temporal_attentions=enable_temporal_attentions, return_dict=False)[0]
+            if window_stride is not None:
+                noise_pred = window_merge(noise_pred.to(dtype=torch.float32).contiguous(), latents.shape[2], window_stride,
+                                          frames_inner=True)
             if do_cfg:
                 uncond, text = noise_pred.chunk(2)
                 noise_pred = uncond + guidance_scale * (text - uncond)                           # :748-749

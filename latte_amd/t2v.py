@@ -182,8 +182,9 @@ class LatteT2V:
         return self
 
     def _ddim_loop(self, who, latents, timesteps, alphas_t, alphas_prev, guidance_scale, enable_temporal_attentions, known=None,
-                   known_mask=None, noise=None):
-        """The shared body of ``guided_ddim_loop`` (known is None) and ``guided_ddim_loop_known``; ``who`` names the caller in errors."""
+                   known_mask=None, noise=None, stride=None):
+        """The shared body of ``guided_ddim_loop`` (known is None), ``guided_ddim_loop_known`` and ``guided_ddim_loop_windows`` (stride
+        given); ``who`` names the caller in errors."""
         import numpy as np
         dev = self._device
         x = latents.to(device=dev, dtype=torch.float32).contiguous().clone()
@@ -205,10 +206,15 @@ class LatteT2V:
             fn, args = lib.latte_t2v_guided_ddim_loop_known, args + (ptr(kn), ptr(mk), ptr(nz))
         else:
             fn = lib.latte_t2v_guided_ddim_loop
+        tail = ()
+        if stride is not None:
+            if x.dim() != 5:
+                raise LatteError(f"{who}: latents must be [b, C, L, H, W]")
+            fn, tail = lib.latte_t2v_guided_ddim_loop_windows, (int(x.shape[2]), int(stride))
         if self._h is None:
             raise LatteError(f"{who}: call set_text first")
         with torch.cuda.device(dev):
-            check(fn(self._h, ptr(x), x.shape[0], *args, int(bool(enable_temporal_attentions)), stream_ptr()))
+            check(fn(self._h, ptr(x), x.shape[0], *args, int(bool(enable_temporal_attentions)), *tail, stream_ptr()))
             if known is not None:
                 torch.cuda.current_stream().synchronize()      # the noise may be released by the caller
         return x
@@ -226,24 +232,46 @@ class LatteT2V:
         return self._ddim_loop("guided_ddim_loop_known", latents, timesteps, alphas_t, alphas_prev, guidance_scale,
                                enable_temporal_attentions, known, known_mask, noise)
 
+    def guided_ddim_loop_windows(self, latents, timesteps, alphas_t, alphas_prev, guidance_scale, stride, enable_temporal_attentions=True):
+        """``guided_ddim_loop`` on ``latents`` [b, C, L, H, W] with L >= ``video_length``, by overlapping temporal windows at
+        ``stride`` (``latte_t2v_guided_ddim_loop_windows``; the scheme of ``SpacedDiffusion.window_sample_loop``).  ``set_text`` must hold
+        the 2 b W rows [negative | prompt], every row repeated per window (``repeat_interleave(W, 0)``,
+        W = ``len(latte_amd.window_starts(L, video_length, stride))``)."""
+        return self._ddim_loop("guided_ddim_loop_windows", latents, timesteps, alphas_t, alphas_prev, guidance_scale,
+                               enable_temporal_attentions, stride=stride)
+
+    def guided_linear_loop_windows(self, latents, plan, noise, guidance_scale, stride, enable_temporal_attentions=True):
+        """``guided_linear_loop`` on ``latents`` [b, C, L, H, W] with L >= ``video_length``, by overlapping temporal windows at ``stride``
+        (``latte_t2v_guided_linear_loop_windows``); text context as ``guided_ddim_loop_windows``; ``noise`` [n_evals, b, C, L, H, W]."""
+        return self._linear_loop("guided_linear_loop_windows", latents, plan, noise, guidance_scale, enable_temporal_attentions, stride)
+
     def guided_linear_loop(self, latents, plan, noise, guidance_scale, enable_temporal_attentions=True):
         """The classifier-free-guidance loop of any sampler with a linear update (``engine_plan()`` of latte_amd.schedulers: Euler,
         Euler-ancestral, Heun, DPM-Solver++) inside the engine on ``latents`` [b, C, F, H, W]; ``set_text`` must hold the 2 b rows
         [negative | prompt].  ``plan``: [n_evals, 12] float64 (host); ``noise``: [n_evals, b, C, F, H, W] or None."""
+        return self._linear_loop("guided_linear_loop", latents, plan, noise, guidance_scale, enable_temporal_attentions)
+
+    def _linear_loop(self, who, latents, plan, noise, guidance_scale, enable_temporal_attentions, _stride=None):
+        """The shared body of ``guided_linear_loop`` and ``guided_linear_loop_windows`` (stride given); ``who`` names the caller in errors."""
         import numpy as np
         dev = self._device
         x = latents.to(device=dev, dtype=torch.float32).contiguous().clone()
         plan = np.ascontiguousarray(np.asarray(plan, dtype=np.float64))
         if plan.ndim != 2 or plan.shape[1] != _lib.T2V_PLAN_COLS or plan.shape[0] == 0:
-            raise LatteError(f"guided_linear_loop: plan must be [n_evals, {_lib.T2V_PLAN_COLS}]")
+            raise LatteError(f"{who}: plan must be [n_evals, {_lib.T2V_PLAN_COLS}]")
         if noise is not None:
             noise = noise.to(device=dev, dtype=torch.float32).contiguous()
             if noise.numel() != plan.shape[0] * x.numel():
-                raise LatteError("guided_linear_loop: noise must hold one latent-shaped slab per evaluation")
+                raise LatteError(f"{who}: noise must hold one latent-shaped slab per evaluation")
         if self._h is None:
-            raise LatteError("guided_linear_loop: call set_text first")
+            raise LatteError(f"{who}: call set_text first")
+        lib = load_library()
+        fn, tail = lib.latte_t2v_guided_linear_loop, ()
+        if _stride is not None:
+            fn, tail = lib.latte_t2v_guided_linear_loop_windows, (int(x.shape[2]), int(_stride))
         with torch.cuda.device(dev):
-            check(load_library().latte_t2v_guided_linear_loop(self._h, ptr(x), x.shape[0], plan.shape[0], plan.ctypes.data, ptr(noise),
-                                                              float(guidance_scale), int(bool(enable_temporal_attentions)),
-                                                              stream_ptr()))
+            check(fn(self._h, ptr(x), x.shape[0], plan.shape[0], plan.ctypes.data, ptr(noise), float(guidance_scale),
+                     int(bool(enable_temporal_attentions)), *tail, stream_ptr()))
+            if noise is not None and _stride is not None:
+                torch.cuda.current_stream().synchronize()      # the noise may be released by the caller
         return x

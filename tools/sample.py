@@ -1,6 +1,10 @@
 """sample/sample.py of the reference on the MI355X engine: single process, one video.
 
   python tools/sample.py --config configs/ffs_sample.yaml [--ckpt model.pt] [--vae DIR] [--save_video_path DIR]
+                         [--frames L --window-stride S]
+
+--frames L (config key ``total_frames``) samples a clip longer than the model's ``num_frames`` by overlapping temporal windows at
+--window-stride S (``window_stride``; default num_frames // 2): SpacedDiffusion.window_sample_loop, not in the reference.
 
 The flow of /root/reference/sample/sample.py:39-126 statement by statement, with its three import lines swapped for
 latte_amd: config -> get_models -> find_model / load_state_dict -> create_diffusion ->
@@ -30,7 +34,11 @@ def main(args, cli):
         raise SystemExit("tools/sample.py needs an MI355X (latte_amd has no CPU fallback)")
     using_cfg = float(args.cfg_scale) > 1.0                                # :51
     args.latent_size = args.image_size // 8                                # :55
-    args.max_batch = 2 if using_cfg else 1
+    total_frames = int(args.get("total_frames") or 0)                      # > 0: a long clip by temporal windows (not in the reference)
+    stride = int(args.get("window_stride") or max(1, args.num_frames // 2))
+    windows = len(latte_amd.window_starts(total_frames, args.num_frames, stride)) if total_frames else 1
+    frames = total_frames or args.num_frames
+    args.max_batch = (2 if using_cfg else 1) * windows                     # every clip of a step in one forward
     model = get_models(args).to(device)                                    # :56
     if args.get("ckpt"):
         sd = find_model(args.ckpt)                                         # :62-64
@@ -49,16 +57,16 @@ def main(args, cli):
     diffusion = create_diffusion(str(args.num_sampling_steps))             # :67
     if cli.vae or args.get("pretrained_model_path") and os.path.isdir(os.path.join(args.pretrained_model_path, "vae")):
         root = cli.vae or os.path.join(args.pretrained_model_path, "vae")
-        vae = latte_amd.AutoencoderKL.from_pretrained(root, latent_size=args.latent_size, max_frames=args.num_frames).to(device)
+        vae = latte_amd.AutoencoderKL.from_pretrained(root, latent_size=args.latent_size, max_frames=frames).to(device)
     else:
         from latte_amd.random_init import vae_decoder_state_dict
-        vae = latte_amd.AutoencoderKL(latent_size=args.latent_size, max_frames=args.num_frames)
+        vae = latte_amd.AutoencoderKL(latent_size=args.latent_size, max_frames=frames)
         vae.load_state_dict(vae_decoder_state_dict(0))
         vae.to(device)
     if args.get("use_fp16"):                                               # :72-75
         model.to(dtype=torch.float16)
         vae.to(dtype=torch.float16)
-    z = torch.randn(1, args.num_frames, 4, args.latent_size, args.latent_size, device=device)    # :81-84
+    z = torch.randn(1, frames, 4, args.latent_size, args.latent_size, device=device)             # :81-84
     if using_cfg:                                                          # :86-94
         z = torch.cat([z, z], 0)
         y = torch.randint(0, args.num_classes, (1,), device=device)
@@ -69,7 +77,10 @@ def main(args, cli):
     else:                                                                  # :95-98
         sample_fn = model.forward
         model_kwargs = dict(y=None, use_fp16=bool(args.get("use_fp16")))
-    if args.sample_method == "ddim":                                       # :100-107
+    if total_frames:
+        samples = diffusion.window_sample_loop(sample_fn, z.shape, z, method=args.sample_method, stride=stride, clip_denoised=False,
+                                               model_kwargs=model_kwargs, progress=True, device=device)
+    elif args.sample_method == "ddim":                                     # :100-107
         samples = diffusion.ddim_sample_loop(sample_fn, z.shape, z, clip_denoised=False, model_kwargs=model_kwargs,
                                              progress=True, device=device)
     elif args.sample_method in latte_amd.LINEAR_METHODS:                   # euler | euler_a | heun | dpmsolver++ (not in the reference)
@@ -101,6 +112,8 @@ if __name__ == "__main__":
     parser.add_argument("--steps", type=int, default=0)
     parser.add_argument("--lora", type=str, default="", help="<step>.lora.pt of a LoRA fine-tune of --ckpt: merged into it before sampling, in torch fp32 -- the merged weights may differ from LatteTrainer.merge_lora()'s in the last fp32 bit, so the sampled operands are not guaranteed to be the trainer's bit for bit")
     parser.add_argument("--lora_ema", action="store_true", help="merge the adapters' EMA instead of the adapters")
+    parser.add_argument("--frames", type=int, default=0, help="sample a clip of this many frames (>= num_frames) by overlapping temporal windows")
+    parser.add_argument("--window-stride", type=int, default=0, help="frames between window starts, 1 ... num_frames (default num_frames // 2)")
     cli = parser.parse_args()
     conf = latte_amd.load_config(cli.config)                               # :136
     if cli.ckpt:
@@ -109,4 +122,8 @@ if __name__ == "__main__":
         conf.save_video_path = cli.save_video_path                         # :138
     if cli.steps:
         conf.num_sampling_steps = cli.steps
+    if cli.frames:
+        conf.total_frames = cli.frames
+    if cli.window_stride:
+        conf.window_stride = cli.window_stride
     main(conf, cli)

@@ -1,6 +1,10 @@
 """sample/sample_t2x.py of the reference on the MI355X engine: Latte-1 text-to-video.
 
   python tools/sample_t2x.py --config configs/t2v_sample.yaml [--random] [--steps N] [--layers L] [--sample-method NAME]
+                             [--video-length L --window-stride S]
+
+--video-length L above the config's ``video_length`` (the transformer's clip length) with --window-stride S samples the longer clip by
+overlapping temporal windows (LattePipeline(window_stride=), not in the reference); the VAE decodes all L frames.
 
 With a real checkpoint directory (`pretrained_model_path` holding transformer/, vae/, tokenizer/, text_encoder/) the flow is
 the reference's (sample_t2x.py:21-140): the T5 tokenizer from `transformers`, the T5 encoder on the engine
@@ -58,6 +62,8 @@ def main():
     ap.add_argument("--sample-method", default=None, help="overrides the config's sample_method: " + ", ".join(SAMPLE_METHODS))
     ap.add_argument("--layers", type=int, default=28)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--video-length", type=int, default=0, help="frames to sample, >= the config's video_length: a longer clip by temporal windows")
+    ap.add_argument("--window-stride", type=int, default=0, help="frames between window starts, 1 ... video_length (default video_length // 2)")
     a = ap.parse_args()
     args = latte_amd.load_config(a.config)
     if a.sample_method:
@@ -68,6 +74,9 @@ def main():
     cdt = "f16"                       # sample_t2x.py:29 .to(device, dtype=torch.float16): the only operand type of latte_amd.LatteT2V
     latent = args.image_size[0] // 8
     scheduler = make_scheduler(args)
+    total = a.video_length or args.video_length                # frames sampled and decoded; the transformer stays at args.video_length
+    stride = (a.window_stride or max(1, args.video_length // 2)) if (a.video_length or a.window_stride) else None
+    pair = 2 * (len(latte_amd.window_starts(total, args.video_length, stride)) if stride else 1)   # the guidance pair's clips per step
     tokenizer = text_encoder = None
     if a.random:
         from latte_amd.random_init import t2v_state_dict, t5_state_dict, vae_decoder_state_dict
@@ -75,24 +84,24 @@ def main():
         tokenizer = HashTokenizer()
         text_encoder = latte_amd.T5EncoderModel(num_layers=a.t5_layers, max_batch=1).load_state_dict(t5_state_dict(0, num_layers=a.t5_layers))
         transformer = latte_amd.LatteT2V(num_layers=a.layers, sample_size=latent, video_length=args.video_length,
-                                         compute_dtype=cdt, max_batch=2).load_state_dict(t2v_state_dict(0, num_layers=a.layers))
+                                         compute_dtype=cdt, max_batch=pair).load_state_dict(t2v_state_dict(0, num_layers=a.layers))
         if args.enable_vae_temporal_decoder:                       # sample_t2x.py:31-32
             from latte_amd.random_init import vae_temporal_decoder_state_dict
             vae = latte_amd.AutoencoderKLTemporalDecoder(latent_size=latent, max_frames=14, compute_dtype="f16")
             vae.load_state_dict(vae_temporal_decoder_state_dict(0))
         else:
-            vae = latte_amd.AutoencoderKL(latent_size=latent, max_frames=args.video_length, compute_dtype="f16")
+            vae = latte_amd.AutoencoderKL(latent_size=latent, max_frames=total, compute_dtype="f16")
             vae.load_state_dict(vae_decoder_state_dict(0))
     else:
         from transformers import T5Tokenizer
         p = args.pretrained_model_path
         transformer = latte_amd.LatteT2V.from_pretrained_2d(p, subfolder="transformer", video_length=args.video_length,
-                                                            compute_dtype=cdt, max_batch=2)
+                                                            compute_dtype=cdt, max_batch=pair)
         if args.enable_vae_temporal_decoder:                       # sample_t2x.py:31-32
             vae = latte_amd.AutoencoderKLTemporalDecoder.from_pretrained(p, subfolder="vae_temporal_decoder", latent_size=latent,
                                                                          max_frames=14)
         else:
-            vae = latte_amd.AutoencoderKL.from_pretrained(p, subfolder="vae", latent_size=latent, max_frames=args.video_length)
+            vae = latte_amd.AutoencoderKL.from_pretrained(p, subfolder="vae", latent_size=latent, max_frames=total)
         tokenizer = T5Tokenizer.from_pretrained(p, subfolder="tokenizer")
         text_encoder = latte_amd.T5EncoderModel.from_pretrained(p, subfolder="text_encoder", max_batch=1).eval()
     pipe = latte_amd.LattePipeline(vae=vae, text_encoder=text_encoder, tokenizer=tokenizer, scheduler=scheduler,
@@ -106,7 +115,7 @@ def main():
         kw = dict(prompt=prompt)
         torch.cuda.synchronize()
         t0 = time.time()
-        video = pipe(video_length=args.video_length, height=args.image_size[0], width=args.image_size[1],
+        video = pipe(video_length=total, window_stride=stride, height=args.image_size[0], width=args.image_size[1],
                      num_inference_steps=steps, guidance_scale=args.guidance_scale,
                      enable_temporal_attentions=args.enable_temporal_attentions, num_images_per_prompt=1, mask_feature=True,
                      enable_vae_temporal_decoder=bool(args.enable_vae_temporal_decoder), generator=g, **kw).video
