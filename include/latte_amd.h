@@ -578,6 +578,19 @@ int latte_vae_encode(latte_vae_t* v, const void* x, int n_frames, int in_mode, c
 /* The posterior on moments [n, 8, hw] already encoded -> out [n, 4, hw]: what 1 mean * scale (mode), 2 (mean + std noise) * scale
  * (sample, noise [n, 4, hw]), 3 logvar (clamped to [-30, 20]), 4 std = exp(0.5 logvar), 5 var = exp(logvar); scale applies to 1 and 2. */
 int latte_vae_posterior(const float* moments, const float* noise, int n, int hw, float scale, int what, float* out, void* stream);
+/* Training batches from STORED moments: out[r] from row rows[r] of store, DEVICE [n_rows, 8, hw] fp32 (store_half = 0) or f16 (1) in
+ * the out_mode 0 layout of latte_vae_encode, computed in fp32.  what keeps the codes of latte_vae_posterior, plus 0: 0 the moments
+ * themselves, out [n_out, 8, hw] (gather + upcast); 1 mean * scale and 2 (mean + exp(0.5 clamp(logvar, -30, 20)) noise) * scale, out
+ * [n_out, 4, hw] -- the device function of latte_vae_posterior, so the two agree bit for bit on the gathered rows.  noise: DEVICE
+ * [n_out, 4, hw], or NULL with what == 2: the noise is drawn in the kernel, element i of out taking the normal the engine's generator
+ * writes at i of a slab at (seed, offset) (as latte_known_blend); seed == LATTE_SEED_NONE then says "no seed either" and is refused.
+ * rows: a HOST array of n_out entries, each checked against [0, n_rows) BEFORE anything is launched -- a bad entry returns
+ * LATTE_ERR_INVALID, latte_last_error() names it, and out is untouched -- and handed to the kernel by value, 256 per launch: the call
+ * keeps no reference to it, needs no staging buffer and does not synchronise.  LATTE_ERR_INVALID also for hw % 8 != 0 (16-byte accesses
+ * of eight halves), n_out <= 0, a NULL store / rows / out, and a store, noise or out that is not 16-byte aligned. */
+#define LATTE_SEED_NONE UINT64_MAX
+int latte_moment_sample(const void* store, int store_half, int64_t n_rows, int hw, const int64_t* rows, int n_out, const float* noise,
+                        uint64_t seed, uint64_t offset, float scale, int what, float* out, void* stream);
 /* latte_vae_profile_decode for the encoder: the same five kernel classes (4 = conv_in, conv_out + posterior, fp32 -> half copies). */
 int latte_vae_profile_encode(latte_vae_t* v, const void* x, int n_frames, int in_mode, const float* noise, float scale, int out_mode, float* out,
                              float* ms_out, int* launches_out, int n, void* stream);

@@ -10,6 +10,7 @@ from .config import Config, load_config  # noqa: F401
 from .diffusion import LINEAR_METHODS, SpacedDiffusion, create_diffusion  # noqa: F401
 from .known import known_blend, known_mask  # noqa: F401
 from .models import Latte, Latte_models, find_model, get_models  # noqa: F401
+from .moment_store import MomentStore  # noqa: F401
 from .pipeline import LattePipeline  # noqa: F401
 from .schedulers import (DDIMInverseScheduler, DDIMScheduler, DPMSolverMultistepScheduler,  # noqa: F401
                          EulerAncestralDiscreteScheduler, EulerDiscreteScheduler, HeunDiscreteScheduler)

@@ -166,6 +166,7 @@ PROTOTYPES = {
     "latte_vae_create_encoder": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_void)]),
     "latte_vae_encode": (c_int, [c_void, c_void, c_int, c_int, c_void, c_f32, c_int, c_void, c_void]),
     "latte_vae_posterior": (c_int, [c_void, c_void, c_int, c_int, c_f32, c_int, c_void, c_void]),
+    "latte_moment_sample": (c_int, [c_void, c_int, c_i64, c_int, c_void, c_int, c_void, c_u64, c_u64, c_f32, c_int, c_void, c_void]),
     "latte_vae_profile_encode": (c_int, [c_void, c_void, c_int, c_int, c_void, c_f32, c_int, c_void, c_void, c_void, c_int, c_void]),
     "latte_video_transform_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(VideoPlan)]),
     "latte_video_transform": (c_int, [c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_void, c_void, c_void]),

@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "liblatte_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-SOURCES = ["gemm.hip", "gemm_pw.hip", "gemm_tn.hip", "train.hip", "train_fin.hip", "train_lora.hip", "train_attn.hip", "attention.hip", "qkv_attn.hip", "pointwise.hip", "debug.hip", "vae.hip", "t5.hip", "video.hip", "engine.cpp", "block.cpp", "train_engine.cpp", "vae_engine.cpp", "t2v_engine.cpp", "t5_engine.cpp", "weight_store.cpp", "schedule.cpp", "plan.cpp"]
+SOURCES = ["gemm.hip", "gemm_pw.hip", "gemm_tn.hip", "train.hip", "train_fin.hip", "train_lora.hip", "train_attn.hip", "attention.hip", "qkv_attn.hip", "pointwise.hip", "debug.hip", "vae.hip", "moments.hip", "t5.hip", "video.hip", "engine.cpp", "block.cpp", "train_engine.cpp", "vae_engine.cpp", "t2v_engine.cpp", "t5_engine.cpp", "weight_store.cpp", "schedule.cpp", "plan.cpp"]
 COMMON = ["--offload-arch=" + ARCH, "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # compiler-flag A/B builds (measurement only): LATTE_BUILD_TAG=<tag> LATTE_EXTRA_HIPFLAGS="<flags>" builds lib/liblatte_amd_<tag>.so
 # from objects under build_<tag>/ with the extra flags on the .hip files; loaded through LATTE_AMD_LIB (tools/flag_ab_probe.py)

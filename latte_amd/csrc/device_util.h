@@ -80,5 +80,54 @@ __device__ __forceinline__ unsigned int quant4_pk4(float v0, float v1, float v2,
   return w & 0xffffu;
 }
 
+// Philox4x32-10 (Salmon et al. 2011): counter = element-quad index, key = seed.
+__device__ __forceinline__ void philox_round(unsigned int (&c)[4], unsigned int k0, unsigned int k1) {
+  const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
+  const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
+  const unsigned int n0 = (unsigned int)(p1 >> 32) ^ c[1] ^ k0;
+  const unsigned int n1 = (unsigned int)p1;
+  const unsigned int n2 = (unsigned int)(p0 >> 32) ^ c[3] ^ k1;
+  const unsigned int n3 = (unsigned int)p0;
+  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+}
+
+// The four standard normals of element quad q of a draw at (seed, offset): quad q covers elements [4q, 4q+4) of THAT draw; the counter
+// is the global element-quad index.  The one definition of the stream: fill_normal_kernel, known_blend_kernel's inline draw
+// (pointwise.hip) and moment_sample_kernel's (moments.hip).
+__device__ __forceinline__ void philox_normal_quad(unsigned long long seed, unsigned long long offset, size_t q, float (&z)[4]) {
+  const unsigned long long ctr = (offset >> 2) + q;
+  unsigned int c[4] = {(unsigned int)ctr, (unsigned int)(ctr >> 32), (unsigned int)(offset & 3), 0u};
+  unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    philox_round(c, k0, k1);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float r = sqrtf(-2.0f * logf(u1));
+    float sn, cs;
+    sincosf(6.283185307179586f * u2, &sn, &cs);
+    z[2 * h] = r * cs;
+    z[2 * h + 1] = r * sn;
+  }
+}
+
+// One element of DiagonalGaussianDistribution from its mean and its RAW logvar (clamped to [-30, 20] here): what 1 mode * scale,
+// 2 (mean + exp(0.5 logvar) *z) * scale (z is read for what 2 only), 3 logvar, 4 std, 5 var.  The one definition of that arithmetic:
+// posterior_kernel (vae.hip) and moment_sample_kernel (moments.hip) agree bit for bit because both call this.
+__device__ __forceinline__ float posterior_value(float mean, float logvar, const float* __restrict__ z, float scale, int what) {
+#pragma clang fp contract(off)
+  const float lv = fminf(fmaxf(logvar, -30.0f), 20.0f);
+  if (what == 1) return mean * scale;
+  if (what == 2) return (mean + expf(0.5f * lv) * *z) * scale;
+  if (what == 3) return lv;
+  if (what == 4) return expf(0.5f * lv);
+  return expf(lv);
+}
+
 }  // namespace
 }  // namespace latte

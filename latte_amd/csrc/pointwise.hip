@@ -968,41 +968,7 @@ __global__ void transpose_kernel(const float* __restrict__ in, float* __restrict
   }
 }
 
-// Philox4x32-10 (Salmon et al. 2011): counter = element-quad index, key = seed.
-__device__ __forceinline__ void philox_round(unsigned int (&c)[4], unsigned int k0, unsigned int k1) {
-  const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
-  const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
-  const unsigned int n0 = (unsigned int)(p1 >> 32) ^ c[1] ^ k0;
-  const unsigned int n1 = (unsigned int)p1;
-  const unsigned int n2 = (unsigned int)(p0 >> 32) ^ c[3] ^ k1;
-  const unsigned int n3 = (unsigned int)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
-// The four standard normals of element quad q of a draw at (seed, offset): quad q covers elements [4q, 4q+4) of THAT draw; the counter
-// is the global element-quad index.  The one definition of the stream: fill_normal_kernel and known_blend_kernel's inline draw.
-__device__ __forceinline__ void philox_normal_quad(unsigned long long seed, unsigned long long offset, size_t q, float (&z)[4]) {
-  const unsigned long long ctr = (offset >> 2) + q;
-  unsigned int c[4] = {(unsigned int)ctr, (unsigned int)(ctr >> 32), (unsigned int)(offset & 3), 0u};
-  unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float r = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincosf(6.283185307179586f * u2, &sn, &cs);
-    z[2 * h] = r * cs;
-    z[2 * h + 1] = r * sn;
-  }
-}
-
+// N(0, 1) from the Philox stream of device_util.h (philox_normal_quad): element i takes value i of the draw at (seed, offset)
 __global__ void fill_normal_kernel(float* __restrict__ out, size_t n, unsigned long long seed, unsigned long long offset) {
   const size_t quads = (n + 3) / 4;
   for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (size_t)gridDim.x * blockDim.x) {

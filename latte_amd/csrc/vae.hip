@@ -1081,14 +1081,7 @@ __global__ void posterior_kernel(const float* __restrict__ m, const float* __res
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const size_t img = i / per, r = i - img * per;
     const float mean = m[img * 2 * per + r];
-    const float lv = fminf(fmaxf(m[img * 2 * per + per + r], -30.0f), 20.0f);
-    float v;
-    if (what == 1) v = mean * scale;
-    else if (what == 2) v = (mean + expf(0.5f * lv) * noise[i]) * scale;
-    else if (what == 3) v = lv;
-    else if (what == 4) v = expf(0.5f * lv);
-    else v = expf(lv);
-    out[i] = v;
+    out[i] = posterior_value(mean, m[img * 2 * per + per + r], noise + i, scale, what);   // (device_util.h)
   }
 }
 

@@ -19,6 +19,12 @@ def scheduled_lr(base_lr, step, warmup_steps=0, scheduler="constant"):
     raise ValueError(f"lr_scheduler must be 'constant' or 'constant_with_warmup', got {scheduler!r}")
 
 
+def clip_label(path):
+    """The class label of a clip file: the ``<label>_...`` prefix of its name, 0 when it has none."""
+    name = os.path.basename(path)
+    return int(name.split("_")[0]) if name.split("_")[0].isdigit() else 0
+
+
 def data_seed(seed, step, micro, accum, rank, world):
     """Seed of the data generator of micro-batch ``micro`` (0 .. accum-1) of optimiser step ``step`` on ``rank``: micro-batches are
     numbered step * accum + micro, ranks interleave inside one -- distinct for every (step, micro, rank), and step * world + rank

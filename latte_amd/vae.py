@@ -345,6 +345,20 @@ class AutoencoderKL:
         out = self._encode_run(x.reshape(b * f, 3, s, s), 0, 2, noise, self.config.scaling_factor)
         return out.view(b, f, *out.shape[1:])
 
+    def encode_video_raw_moments(self, frames, transform, flip=None):
+        """``encode_video_raw`` up to the posterior: the same transform launch and the same fp32 encode path, stopped at the moments
+        (``out_mode`` 0) -> fp32 [B, F, 8, S/8, S/8] (mean | logvar), no noise drawn.  What ``latte_amd.MomentStore`` keeps."""
+        if not self.with_encoder:
+            raise LatteError(_NO_ENCODER)
+        x = transform(frames.to(self._device), flip=flip)
+        if x.dim() == 4:
+            x = x.unsqueeze(0)
+        b, f, _, s, sw = x.shape
+        if s != sw:
+            raise LatteError(f"the transform must produce square frames for the encoder, got {s} x {sw}")
+        out = self._encode_run(x.reshape(b * f, 3, s, s), 0, 0)
+        return out.view(b, f, *out.shape[1:])
+
     def profile_encode(self, x, in_mode=0):
         """Measurement hook (tools/vae_encode_bench.py): one encode of x [N <= max_frames, 3, H, W] fp32 (in_mode 0) or uint8
         [N, H, W, 3] (in_mode 1) to the moments with a HIP event behind every launch -> {class: (milliseconds, launches)}."""

@@ -31,6 +31,8 @@ LOCAL = re.compile(r"(\.L[A-Za-z_]+)\d+_")   # .LBB<function index>_<block>: the
 
 def kernels(tree, name):
     """Sorted list of per-kernel chunks of `name` compiled in `tree`."""
+    if not os.path.exists(os.path.join(tree, "latte_amd", "csrc", name)):
+        return []          # a file the revision does not have yet: all of its kernels are new
     # cwd = the source's directory and a relative path: nothing in the output names the tree
     cmd = [B.HIPCC] + B.FLAGS[".hip"] + ["--cuda-device-only", "-S", name, "-o", "-"]
     r = subprocess.run(cmd, cwd=os.path.join(tree, "latte_amd", "csrc"), capture_output=True, text=True)

@@ -22,6 +22,10 @@ micro-batches per optimiser step (steps, logs and checkpoints count optimiser st
     and step a `TemporalRandomCrop(num_frames * frame_interval)` window and the flip coin from a seeded generator, the `num_frames` frames
     of `frame_indices` gathered on the host, one upload, one `latte_amd.video_transforms` launch for `dataset`'s pipeline
     (ffs | ucf101 | taichi | sky), then the encode above -- nothing of the augmentation is frozen into the stored data.
+`moments_path` (with `frame_interval`; configs/tiny_train_moments.yaml) replaces `data_path` by the stored VAE moments of those raw
+clips (tools/encode_clips.py --moments; latte_amd.MomentStore): the same window, flip and posterior-noise draws as the raw mode for the
+same seed, served by one gather-and-sample launch per micro-batch -- no VAE is loaded.  `frame_moments_path` does the same for the single
+images of `use_image_num`; `--moments-device cpu` keeps the stores in host memory.
 Joint image-video training (train_with_img.py, the `*_img_train.yaml` configs): `use_image_num: N` appends N single frames to every
 clip and `model: LatteIMG-*` is mapped to the `Latte-*` preset of the same size (identical parameters; the checkpoint is sampled with
 it).  `frame_data_path` is a directory of single frames -- .npy latents [4, h, w] (scaled by 0.18215) or uint8 [H, W, 3] at the
@@ -50,7 +54,7 @@ sys.path.insert(0, ROOT)
 
 import latte_amd  # noqa: E402
 from latte_amd import parallel  # noqa: E402
-from latte_amd.train_util import (checkpoint_step, data_seed, draw_image_frames, latest_checkpoint, latte_preset_name,  # noqa: E402
+from latte_amd.train_util import (checkpoint_step, clip_label, data_seed, draw_image_frames, latest_checkpoint, latte_preset_name,  # noqa: E402
                                   resolve_loss_fn, rng_state, scheduled_lr, set_rng_state, state_path)
 
 
@@ -91,11 +95,6 @@ def join_run_state(checkpoint, state, lora, base_model=None):
     return {**state, "model": checkpoint["model"], "ema": checkpoint["ema"]}
 
 
-def clip_label(path):
-    name = os.path.basename(path)
-    return int(name.split("_")[0]) if name.split("_")[0].isdigit() else 0
-
-
 class RawClips:
     """Raw uint8 clips [T, Hs, Ws, 3] of any length and size, memory-mapped: per item the reference's temporal window, frame indices and
     flip coin (datasets/ucf101_datasets.py:198-216, video_transforms.py:386-427) from a generator seeded by (seed, step, micro, rank)."""
@@ -131,6 +130,61 @@ class RawClips:
             items.append((torch.from_numpy(np.ascontiguousarray(a[idx])), transform.draw_flips(1)[0]))
             ys.append(clip_label(self.files[i]))
         return items, torch.tensor(ys)
+
+
+class MomentClips:
+    """Stored VAE moments of raw clips (`moments_path`, a directory tools/encode_clips.py --moments wrote; latte_amd.MomentStore): the
+    SAME draws as RawClips.batch for the same (seed, step, micro, rank) -- the clip index over the sorted file list, then per item the
+    temporal window and the flip coin -- turned into rows of the store instead of gathered frames."""
+    frames = False
+    accum = 1             # micro-batches per optimiser step (main sets it)
+
+    def __init__(self, store, args, rank, world, seed):
+        self.store, self.args, self.rank, self.world, self.seed = store, args, rank, world, seed
+        self.num_frames = int(args.num_frames)
+
+    def batch(self, step, n, micro=0):
+        """-> ([(clip, frame indices [num_frames], flip)] * n, labels)"""
+        import random
+        from latte_amd import video_transforms
+        s = data_seed(self.seed, step, micro, self.accum, self.rank, self.world)
+        g = torch.Generator("cpu").manual_seed(s)
+        transform, temporal_sample = video_transforms.get_transform(self.args, rng=random.Random(s))
+        frames, labels = self.store.clip_frames, self.store.labels
+        items, ys = [], []
+        for i in torch.randint(0, self.store.num_clips, (n,), generator=g).tolist():
+            start, end = temporal_sample(frames[i])
+            assert end - start >= self.num_frames, f"{self.store.names[i]}: {frames[i]} frames, fewer than num_frames = {self.num_frames}"
+            items.append((i, video_transforms.frame_indices(start, end, self.num_frames), transform.draw_flips(1)[0]))
+            ys.append(labels[i])
+        return items, torch.tensor(ys)
+
+    def latents(self, items, gen):
+        """The items' latents [n, num_frames, 4, h, w] in one launch; the posterior noise is drawn item by item from ``gen``, as the
+        raw path's per-item ``encode_video_raw`` draws it."""
+        from latte_amd.vae import randn_tensor
+        dev = torch.device("cuda", torch.cuda.current_device())
+        noise = torch.cat([randn_tensor((self.num_frames, 4, *self.store.latent_hw), generator=gen, device=dev) for _ in items])
+        x = self.store.sample_frames(np.concatenate([self.store.frame_rows(i, idx, fl) for i, idx, fl in items]), noise=noise)
+        return x.view(len(items), self.num_frames, *x.shape[1:])
+
+
+class MomentFrames:
+    """The single images of joint training from stored moments (`frame_moments_path`: one-frame clips, plane 0): the indices
+    ImageFrames.batch draws, as rows."""
+    frames = False
+    accum = 1
+
+    def __init__(self, store, images, rank, world, seed):
+        self.store, self.images, self.rank, self.world, self.seed = store, int(images), rank, world, seed
+
+    def batch(self, step, n, micro=0):
+        """-> (rows int64 [n * N], labels [n, N])"""
+        g = torch.Generator("cpu").manual_seed(data_seed(self.seed, step, micro, self.accum, self.rank, self.world) + 500009)
+        idx = draw_image_frames(self.store.num_clips, n, self.images, g).reshape(-1).tolist()
+        labels = self.store.labels
+        rows = np.concatenate([self.store.frame_rows(i, [0], False) for i in idx])
+        return rows, torch.tensor([labels[i] for i in idx]).reshape(n, self.images)
 
 
 class LatentClips:
@@ -206,6 +260,8 @@ def main():
     ap.add_argument("--log-every", type=int, default=None)
     ap.add_argument("--ckpt-every", type=int, default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--moments-device", choices=("cuda", "cpu"), default="cuda",
+                    help="where the stores of moments_path / frame_moments_path live: resident on the GPU, or in host memory (rows uploaded per batch)")
     a = ap.parse_args()
     args = latte_amd.load_config(a.config)
     rank, world, local = parallel.setup_distributed()
@@ -288,8 +344,18 @@ def main():
             if rank == 0:
                 print(f"Resumed from {ck}: step {first_step}" + ("" if lora_rank else f", loss scale {sc['loss_scale']:g}, applied updates "
                       f"{int(sc['applied_updates'])}, skipped updates {int(sc['skipped_updates'])}"), flush=True)
-    raw = args.get("frame_interval") not in (None, "") and args.get("data_path") not in (None, "", "synthetic")
-    if raw:                                                   # raw clips through the dataset's frame pipeline (datasets/__init__.py:13-76)
+    moments = args.get("moments_path") not in (None, "")
+    if moments and args.get("frame_interval") in (None, ""):
+        raise SystemExit("moments_path: set frame_interval (the temporal window is drawn per item, as on raw clips)")
+    raw = not moments and args.get("frame_interval") not in (None, "") and args.get("data_path") not in (None, "", "synthetic")
+    if moments:                                               # stored moments of the raw clips: the raw path's draws, no encoder in the step
+        data = MomentClips(latte_amd.MomentStore.load(args.moments_path, device=a.moments_device), args, rank, world, seed)
+        if data.store.latent_hw != (args.latent_size, args.latent_size):
+            raise SystemExit(f"moments_path holds {data.store.latent_hw} latents, image_size {args.image_size} needs {args.latent_size} x {args.latent_size}")
+        if rank == 0:
+            print(f"Moment store: {data.store.num_clips} clips, {sum(data.store.clip_frames)} frames x {len(data.store.planes)} planes, "
+                  f"{data.store.dtype}, {data.store.nbytes / 2 ** 20:.1f} MiB on {a.moments_device}", flush=True)
+    elif raw:                                                   # raw clips through the dataset's frame pipeline (datasets/__init__.py:13-76)
         from latte_amd import video_transforms
         data = RawClips(args.data_path, args, rank, world, seed)
         raw_transform, _ = video_transforms.get_transform(args)
@@ -297,10 +363,13 @@ def main():
         data = LatentClips(args.get("data_path"), int(args.num_frames), args.latent_size, rank, world, seed, int(args.get("num_classes") or 0))
     images = None
     if use_image_num:
-        frame_path = "synthetic" if args.get("data_path") in (None, "", "synthetic") else args.get("frame_data_path")
-        if not frame_path:
-            raise SystemExit("use_image_num: set frame_data_path (a directory of single frames)")
-        images = ImageFrames(frame_path, use_image_num, args.latent_size, rank, world, seed, int(args.get("num_classes") or 0))
+        frame_path = "synthetic" if not moments and args.get("data_path") in (None, "", "synthetic") else args.get("frame_data_path")
+        if args.get("frame_moments_path"):
+            images = MomentFrames(latte_amd.MomentStore.load(args.frame_moments_path, device=a.moments_device), use_image_num, rank, world, seed)
+        elif not frame_path:
+            raise SystemExit("use_image_num: set frame_data_path (a directory of single frames) or frame_moments_path (their stored moments)")
+        else:
+            images = ImageFrames(frame_path, use_image_num, args.latent_size, rank, world, seed, int(args.get("num_classes") or 0))
         images.accum = accum
     vae = None
     if data.frames or (images is not None and images.frames):                                           # train.py:94 (+ the encoder): frames -> latents on the GPU every step
@@ -322,16 +391,21 @@ def main():
         trainer.lr = scheduled_lr(base_lr, step, warmup, lr_sched)     # get_scheduler(...).step(), train.py:169-173,233 (host side only)
         for micro in range(accum):                            # the optimiser step runs inside the last train_step of the window
             x, y = data.batch(step, nb, micro)
-            if vae is not None:                               # train.py:204-211, posterior noise from this micro-batch's seeded generator
+            stored = moments or isinstance(images, MomentFrames)
+            if vae is not None or stored:                     # train.py:204-211, posterior noise from this micro-batch's seeded generator
                 gen = torch.Generator(device).manual_seed(data_seed(seed, step, micro, accum, rank, world))
-                if raw:                                       # per item (sizes differ): one upload, one transform launch, the encode
+                if moments:                                   # the raw path's latents from the stored moments: one launch
+                    x = data.latents(x, gen)
+                elif raw:                                     # per item (sizes differ): one upload, one transform launch, the encode
                     x = torch.cat([vae.encode_video_raw(fr.to(device).unsqueeze(0), raw_transform, flip=[fl], generator=gen) for fr, fl in x])
                 elif data.frames:
                     x = vae.encode_video_uint8(x.to(device), generator=gen)
             y_image = None
             if images is not None:                            # train_with_img.py:214-221: N single frames behind every clip
                 xi, y_image = images.batch(step, nb, micro)
-                if images.frames:
+                if isinstance(images, MomentFrames):          # xi: rows of the image store
+                    xi = images.store.sample_frames(xi, generator=gen).view(nb, use_image_num, 4, args.latent_size, args.latent_size)
+                elif images.frames:
                     xi = vae.encode_video_uint8(xi.to(device), generator=gen)
                 x = torch.cat([x.to(device).float(), xi.to(device).float()], dim=1)
                 y_image = y_image.to(device) if int(args.extras) == 2 else None
